@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- train rays/s of thermal-nerfacto (BASELINE.json metric) on N MI355X GPUs of one node.
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10          # the headline line only
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full   # + long run, roofline / per-kernel figures, parity, extra legs, CPU baseline
+    python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs DIR   # + the timed path replayed 2 steps from a fixed state, as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --mode separate --rays 8192          # BASELINE configs[2]
     python bench.py --path model-api                     # the reference Trainer's call sequence instead of the fused step
@@ -195,6 +197,70 @@ def make_fused_trainer(model, cam_t, cache, rays):
                          shuffle=False)
     cls = type("HipTrainer", (FusedTrainerMixin, _TrainerShim), {})
     return cls(model, Optimizers(model.get_param_groups(), optimizer_cls=HipFusedAdam), src.next)
+
+
+DUMP_SAMPLE = 1 << 19  # --dump-outputs: elements kept of a larger array (2 MB in float32; the whole dump stays under 64 MB)
+DUMP_REPLAY = 2  # --dump-outputs: steps replayed from the fixed state; the last one is dumped (see dump_step)
+
+
+def _dump(out_dir, name, t, dtype, key=None):
+    """one array of --dump-outputs; above DUMP_SAMPLE elements a fixed sample of the flattened array, at indices drawn by a generator seeded
+    with `key` (default: the array's name) -- the same in every run, so that two builds compare element for element"""
+    flat = torch.as_tensor(t).detach().reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        rng = np.random.default_rng(int(hashlib.sha256((key or name).encode()).hexdigest()[:8], 16))
+        flat = flat[torch.from_numpy(np.unique(rng.integers(0, flat.numel(), DUMP_SAMPLE))).to(flat.device)]
+    safe = "".join(c if c.isalnum() or c in "._-" else "_" for c in name)
+    np.save(os.path.join(out_dir, safe + ".npy"), flat.cpu().numpy().astype(dtype))
+
+
+def dump_outputs(out_dir, losses, arena, params_in):
+    """--dump-outputs of one train step: every loss it returned (float64); the parameters it started from and the Adam moments it left,
+    exp_avg and exp_avg_sq (float32; the same sampled indices for the three arrays of a parameter)."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for k, v in losses.items():
+        _dump(out_dir, f"loss.{k}", v, np.float64)
+    for name in arena.names():
+        _dump(out_dir, f"param_in.{name}", arena._view(params_in, name), np.float32, key=name)
+        _dump(out_dir, f"exp_avg.{name}", arena._view(arena.exp_avg, name), np.float32, key=name)
+        _dump(out_dir, f"exp_avg_sq.{name}", arena._view(arena.exp_avg_sq, name), np.float32, key=name)
+
+
+def dump_step(args, device, rank, cam_t, cache):
+    """--dump-outputs: the timed path replayed for DUMP_REPLAY steps after the timed region, from a state that is the same in every run (fresh
+    synthetic weights, fresh optimiser and loss-scale state, the run's seed and so its batches) -> (losses, arena, params_in) of the last
+    replayed step.  That step, like every timed step, takes the batch the previous step's launches planned (the first step samples in line),
+    and its Adam update depends on gradient magnitudes (the first step's is lr x sign(g)).  Its outputs are dumped as what carries them
+    reproducibly: the losses, the parameters it started from, and the moments it left (0.9 x 0.1 g1 + 0.1 g2, ...).
+    How this differs from the timed run's last step: that step starts from a trained state that is not the same in every run.  The backward's
+    float atomic sums differ in the last bits between runs, and Adam (eps 1e-15) gives a near-zero gradient, or an entry a sample newly touches,
+    a full lr step.  Observed on an MI355X (not recorded under profiles/): one step from the same state differs by rounding (parameters by
+    2e-7 at most), two steps leave a few % of the table entries 1e-2 apart.  For the same reason the parameters AFTER the dumped step are not
+    dumped: they carry those lr-sized steps; the moments carry the same gradients continuously."""
+    from nerfstudio_thermal_amd.parallel import rank_seed
+
+    if args.path == "model-api":
+        from nerfstudio_thermal_amd.optim import HipFusedAdam, Optimizers
+
+        _, arena, model = build_model(device, mode=args.mode, nerf_samples=args.nerf_samples)
+        optimizers = Optimizers(model.get_param_groups(), optimizer_cls=HipFusedAdam)
+        scaler = None if args.no_grad_scaler else torch.amp.GradScaler("cuda")
+        run = lambda st: one_step_api(model, optimizers, cam_t, cache, args.rays, st, scaler)  # noqa: E731
+    else:
+        from nerfstudio_thermal_amd.optim import DeviceGradScaler
+
+        _, arena, eng = build_engine(device, mode=args.mode, nerf_samples=args.nerf_samples)
+        eng.overlap_adam = os.environ.get("TN_OVERLAP_ADAM", "0") == "1"
+        scaler = None if args.no_grad_scaler else DeviceGradScaler(device, num_groups=len(arena.optimised_groups))
+        run = lambda st: one_step(eng, cam_t, cache, args.rays, st, None, scaler)  # noqa: E731
+    torch.manual_seed(rank_seed(42, rank))
+    for st in range(DUMP_REPLAY):
+        torch.cuda.synchronize()
+        params_in = arena.params.detach().clone()
+        losses = run(st)
+    torch.cuda.synchronize()
+    return losses, arena, params_in
 
 
 def time_ms(fn, iters=10, warmup=2):
@@ -408,7 +474,12 @@ def bench_splat(args):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     ms = dt / args.steps * 1e3
-    # raster alone, HIP events on torch's current stream (the stream the library launches on)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in out.items():
+            if torch.is_tensor(v) and v.is_floating_point():
+                _dump(args.dump_outputs, k, v, np.float32)
+    # raster alone (--full), HIP events on torch's current stream (the stream the library launches on)
     import ctypes as C
 
     from nerfstudio_thermal_amd import _lib
@@ -425,18 +496,20 @@ def bench_splat(args):
         _lib.check(lib.tn_splat_raster(C.byref(cs), N, C.c_void_p(m._ws.data_ptr()), m._cap, bg4, 0, C.c_void_p(rgbt.data_ptr()), C.c_void_p(dep.data_ptr()),
                                        C.c_void_p(alp.data_ptr()), _stream()), "tn_splat_raster")
 
-    t_r = time_ms(raster, iters=10, warmup=2)
+    t_r = time_ms(raster, iters=10, warmup=2) if args.full else None
     line = {
         "metric": "thermal-splatfacto forward render, frames/s at 1080p", "value": world * 1e3 / ms, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"thermal-splatfacto (RGB+T Gaussians) forward render, 1920x1080, 16x16 tiles, {N} synthetic Gaussians, degree-3 SH, classic mode",
                    "visible": int((m.last_projection["radii"] > 0).sum()), "tile_pairs": m.last_num_intersections, "parallelism": f"replicas x{world}",
                    "parity": "unpinned (gsplat outside the reference tree; oracle = published algorithm)"},
-        "roofline": {"bound": "valu", "kernel": "k_splat_raster", "avg_launch_ms": t_r, "achieved": None, "peak": None, "unit": "VALU issue", "frac": None,
-                     "traffic": None, "note": "VALU-issue bound (SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x duration) in profiles/r02_splat_pmc.md); neither HBM- nor MFMA-bound"},
         "Mpix_per_s": W * H / ms / 1e3, "mean_accumulation": float(out["accumulation"].mean()),
     }
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full:
+        line["roofline"] = {"bound": "valu", "kernel": "k_splat_raster", "avg_launch_ms": t_r, "achieved": None, "peak": None, "unit": "VALU issue", "frac": None,
+                            "traffic": None, "note": "VALU-issue bound (SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x duration) in profiles/r02_splat_pmc.md); neither "
+                                                     "HBM- nor MFMA-bound"}
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         # the oracle (port) on a BOUNDED sample: 1/64 of the frame (240x135, intrinsics scaled) with 1/64 of the Gaussians, host cores
         n_s, Ws, Hs = max(N // 64, 1000), W // 8, H // 8
         ps = {k: v[:n_s] for k, v in p.items()}
@@ -807,7 +880,7 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=0, help="torch CPU threads for the baseline (0 = min(host cores, 16): more threads make the"
                     " many small ATen ops of this path slower; measured on the 256-thread GPU-box host at 1024 rays: 8 -> 2427, 16 -> 2286, 32 -> 1906, 64 -> 1025,"
                     " 256 -> 24 rays/s)")
-    ap.add_argument("--ops", action="store_true", help="print the per-kernel timing table to stderr")
+    ap.add_argument("--ops", action="store_true", help="--full: print the per-kernel timing table to stderr")
     ap.add_argument("--dp-chunks", type=int, default=-1, help="N>1: level ranges of the main table exchanged separately (-1 = the default "
                     "schedule, n = n equal ranges, 0 = one all-reduce after the backward)")
     ap.add_argument("--dp-adam-per-range", action="store_true", help="N>1 / --force-dp: one Adam launch per exchanged range instead of one after the exchange")
@@ -821,9 +894,21 @@ def main():
     ap.add_argument("--no-dp-guard", action="store_true", help="N>1 / --force-dp: skip parallel.ScheduleGuard (a few plain and a few overlapped steps are timed before "
                     "the warm-up, and a few of the simple schedule; the faster of the two real schedules runs -- switched in process)")
     ap.add_argument("--rendezvous-only", action="store_true", help="launcher test: spawn / join the ranks, all-reduce once, print the rank count, exit")
-    ap.add_argument("--long-steps", type=int, default=200, help="extra steps after the timed region for the BASELINE.md 3.4 figure (median of >= 200 "
-                    "per-step times, reported as extra keys; `value` always follows --steps).  0 disables")
+    ap.add_argument("--long-steps", type=int, default=200, help="--full: extra steps after the timed region for the BASELINE.md 3.4 figure (median of "
+                    ">= 200 per-step times, reported as extra keys; `value` always follows --steps).  0 disables")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the long run, the roofline and per-kernel figures, "
+                    "the parity block against the reference golden, the extra legs and the CPU baseline.  Off: set up, warm up, time --steps steps, "
+                    "print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, replay the timed path for 2 steps from a state that is the "
+                    "same in every run (fresh synthetic weights and optimiser state, the run's seed) and write what the second step computed as "
+                    "DIR/<name>.npy: its losses (float64), the parameters it started from and the Adam moments it left (float32; a fixed, seeded sample of "
+                    "each large table).  Not the timed run's own last step: its trained state differs between runs (float atomic sums, amplified by "
+                    "Adam), see dump_step.  One rank, HIP Adam")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload == "nerfacto" and (args.gpus > 1 or args.force_dp or (args.path == "model-api" and args.api_optimizer != "hip")):
+        ap.error("--dump-outputs replays the step on one rank with the arena's Adam: use it with --gpus 1, without --force-dp and --api-optimizer torch")
+    if args.ops and not args.full:
+        ap.error("--ops prints the per-kernel timings that --full measures: add --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))  # before any GPU call of this process
     if args.rendezvous_only:
@@ -927,7 +1012,7 @@ def main():
     # The "render PSNR vs ref" half of the metric, on the untouched synthetic weights the reference golden was rendered with (before any training
     # step changes them -- the schedule guard's timing steps below included --, outside every timed region)
     parity = None
-    if rank == 0 and world == 1 and not api and args.mode == "shared" and args.nerf_samples == 48 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not api and args.mode == "shared" and args.nerf_samples == 48 and not args.no_extras:
         try:
             parity = parity_vs_reference(eng, device)
         except Exception as e:  # noqa: BLE001  (an extra must never cost the headline line)
@@ -1005,11 +1090,13 @@ def main():
         assert rccl_ranks == torch.distributed.get_world_size() == world, (rccl_ranks, world)
     final_loss = {k: float(v) for k, v in losses.items()}
     assert all(np.isfinite(v) for v in final_loss.values()), final_loss
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *dump_step(args, device, rank, cam_t, cache))
 
     # "median of >= 200 steps after skipping 2".  `value` above follows --steps; this is the long-run figure beside it:
     # every step bracketed by HIP events on the launch stream (no host sync inside the loop), median / mean of the per-step device times.
     long_run = None
-    if args.long_steps > 0:
+    if args.full and args.long_steps > 0:
         n_long = args.long_steps
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_long + 1)]
         upd_flags = []
@@ -1040,69 +1127,71 @@ def main():
                     "note": "BASELINE.md 3.4 figure (median of per-step HIP-event times, first 2 skipped; max over ranks); `value` follows --steps"}
 
     if rank == 0:
-        # (measured BEFORE the stand-alone launches below, so that the LAST launches of every kernel in a rocprofv3 trace of this command are the
-        # stand-alone ones: scripts/rocpd_stats.py --tail 10 then reproduces roofline.avg_launch_ms, the all-launch mean the in-step figure)
-        # the same launch pair INSIDE the step (HIP events on the launch stream around the scatter phase, 20 extra steps): what runs beside it
-        # (k_field_dpos; on update steps the proposal networks' backward on the side streams) shares the chip with it
-        in_step = None
-        if not api and world == 1 and hook is None:
-            eng.scatter_events = []
-            for _ in range(20):
-                run(step)
-                step += 1
-            torch.cuda.synchronize()
-            tms = [(e0.elapsed_time(e1), u) for e0, e1, u in eng.scatter_events]
-            eng.scatter_events = None
-            if tms:
-                in_step = {"mean_ms": float(np.mean([t for t, _ in tms])),
-                           "mean_ms_update_steps": float(np.mean([t for t, u in tms if u])) if any(u for _, u in tms) else None,
-                           "mean_ms_other_steps": float(np.mean([t for t, u in tms if not u])) if any(not u for _, u in tms) else None}
-        rows, mfma_rows = kernel_roofline(eng, cam_t, idx, img, is_th)
-        if args.ops:
-            for name, ms, nbytes in rows:
-                print(f"{name:60s} {ms*1e3:9.1f} us  {nbytes/ms/1e6:8.1f} GB/s algorithmic", file=sys.stderr)
-        # the dominant HBM-bound launch (pair) = largest measured share of a step: stand-alone time x launches per step (the proposal grids'
-        # scatters run on update steps only).  The MFMA-bound kernel has its own object (`roofline.mfma`).
-        upd_share = updates / max(args.steps, 1)
-        shares = {r[0]: r[1] * (upd_share if "prop" in r[0] and r[0].startswith("scatter") else 1.0) for r in rows}
-        name, ms, nbytes = max(rows, key=lambda r: shares[r[0]])
-        achieved = nbytes / (ms * 1e-3) / 1e9
-        pmc, why = load_pmc() if (rays == 4096 and args.mode == "shared") else (None, "PMC passes cover the 4096-ray shared workload only")
-        traffic = None
-        if pmc is not None and pmc_lookup(pmc, PMC_KEYS.get(name, ["?"])) is not None:
-            traffic = sum(v["traffic_bytes"] for v in pmc_lookup(pmc, PMC_KEYS[name]))
-        elif pmc is not None:
-            why = f"profiles/r06_pmc.json holds no (single) entry for {PMC_KEYS.get(name)}"
-        upd = updates / max(args.steps, 1)
-        step_bytes = step_algorithmic_bytes(arena, args.mode, rays, upd, args.nerf_samples)
-        step_gbs = step_bytes / (dt / args.steps) / 1e9
-        roofline = {"bound": "hbm", "kernel": name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                    "traffic": traffic, "algorithmic_bytes_per_launch": nbytes, "avg_launch_ms": ms,
-                    "avg_launch_ms_in_step": None if in_step is None else in_step["mean_ms"], "in_step": in_step,
-                    "in_step_schedule": "phased backward: tn_field_bwd_phase(MLP) / HIP event / SCATTER / HIP event / JOIN in 20 EXTRA steps after the timed "
-                                        "region -- the timed `value` runs the one-call backward (tn_render_rays_train_bwd), which cannot take events",
-                    "frac_in_step": None if in_step is None else nbytes / (in_step["mean_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                    "note": "the main grid's scatter entry point = k_seg_bin + k_seg_fold as the field backward calls it (d position comes from "
-                            "k_field_dpos); the bin pass is bound by instruction issue, the fold streams its records into double-precision LDS atomics",
-                    "dominant_by": {"rule": "stand-alone ms x launches per step at this run's proposal-update fraction", "ms_per_step": shares},
-                    # rows whose table is L2-resident (the proposal grids: 5 MB each, 12 MB fetched for 335 MB algorithmic in the PMC passes) are stated
-                    # against the L2 rate of the guide, not against HBM -- their algorithmic bytes carry no cache credit and would exceed 1.0 there
-                    "all_kernels": {n: ({"ms": m, "GB/s": bts / (m * 1e-3) / 1e9, "bound": "l2", "peak": L2_PEAK_GBS, "frac": bts / (m * 1e-3) / 1e9 / L2_PEAK_GBS}
-                                        if n.startswith("k_prop_fwd") else
-                                        {"ms": m, "GB/s": bts / (m * 1e-3) / 1e9, "bound": "hbm", "peak": HBM_PEAK_GBS, "frac": bts / (m * 1e-3) / 1e9 / HBM_PEAK_GBS})
-                                    for n, m, bts in rows},
-                    # the MFMA-bound launches (fp32 MFMA: v_mfma_f32_32x32x2_f32 / 16x16x4_f32): achieved TFLOP/s against the dense fp32 peak
-                    "mfma": mfma_rows[1], "mfma_all": mfma_rows,
-                    # SURVEY 8d's whole-step figure: (N x bytes_ray + bytes_step) / t_step against the HBM peak
-                    "step": {"algorithmic_bytes": step_bytes, "achieved": step_gbs, "frac": step_gbs / HBM_PEAK_GBS, "proposal_update_fraction": upd}}
-        if traffic is None:
-            roofline["traffic_unavailable"] = why
-        if pmc is not None:
-            roofline["traffic_all_kernels"] = {n: sum(v["traffic_bytes"] for v in pmc_lookup(pmc, ks)) for n, ks in PMC_KEYS.items()
-                                               if pmc_lookup(pmc, ks) is not None}
-            roofline["mfma_busy_frac"] = {k.split(" ")[0]: v["mfma_busy_frac"] for k, v in pmc.items()
-                                          if k.split(" ")[0] in ("k_field_mlp_fwd<true>", "k_field_bwd_fused<false>") and "mfma_busy_frac" in v}
-            roofline["pmc_source"] = "profiles/r06_pmc.json (read bytes = FETCH_SIZE x the calibrated factor of the kernel's read shape, scripts/pmc_summary.py)"
+        roofline = None
+        if args.full:
+            # (measured BEFORE the stand-alone launches below, so that the LAST launches of every kernel in a rocprofv3 trace of this command are the
+            # stand-alone ones: scripts/rocpd_stats.py --tail 10 then reproduces roofline.avg_launch_ms, the all-launch mean the in-step figure)
+            # the same launch pair INSIDE the step (HIP events on the launch stream around the scatter phase, 20 extra steps): what runs beside it
+            # (k_field_dpos; on update steps the proposal networks' backward on the side streams) shares the chip with it
+            in_step = None
+            if not api and world == 1 and hook is None:
+                eng.scatter_events = []
+                for _ in range(20):
+                    run(step)
+                    step += 1
+                torch.cuda.synchronize()
+                tms = [(e0.elapsed_time(e1), u) for e0, e1, u in eng.scatter_events]
+                eng.scatter_events = None
+                if tms:
+                    in_step = {"mean_ms": float(np.mean([t for t, _ in tms])),
+                               "mean_ms_update_steps": float(np.mean([t for t, u in tms if u])) if any(u for _, u in tms) else None,
+                               "mean_ms_other_steps": float(np.mean([t for t, u in tms if not u])) if any(not u for _, u in tms) else None}
+            rows, mfma_rows = kernel_roofline(eng, cam_t, idx, img, is_th)
+            if args.ops:
+                for name, ms, nbytes in rows:
+                    print(f"{name:60s} {ms*1e3:9.1f} us  {nbytes/ms/1e6:8.1f} GB/s algorithmic", file=sys.stderr)
+            # the dominant HBM-bound launch (pair) = largest measured share of a step: stand-alone time x launches per step (the proposal grids'
+            # scatters run on update steps only).  The MFMA-bound kernel has its own object (`roofline.mfma`).
+            upd_share = updates / max(args.steps, 1)
+            shares = {r[0]: r[1] * (upd_share if "prop" in r[0] and r[0].startswith("scatter") else 1.0) for r in rows}
+            name, ms, nbytes = max(rows, key=lambda r: shares[r[0]])
+            achieved = nbytes / (ms * 1e-3) / 1e9
+            pmc, why = load_pmc() if (rays == 4096 and args.mode == "shared") else (None, "PMC passes cover the 4096-ray shared workload only")
+            traffic = None
+            if pmc is not None and pmc_lookup(pmc, PMC_KEYS.get(name, ["?"])) is not None:
+                traffic = sum(v["traffic_bytes"] for v in pmc_lookup(pmc, PMC_KEYS[name]))
+            elif pmc is not None:
+                why = f"profiles/r06_pmc.json holds no (single) entry for {PMC_KEYS.get(name)}"
+            upd = updates / max(args.steps, 1)
+            step_bytes = step_algorithmic_bytes(arena, args.mode, rays, upd, args.nerf_samples)
+            step_gbs = step_bytes / (dt / args.steps) / 1e9
+            roofline = {"bound": "hbm", "kernel": name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                        "traffic": traffic, "algorithmic_bytes_per_launch": nbytes, "avg_launch_ms": ms,
+                        "avg_launch_ms_in_step": None if in_step is None else in_step["mean_ms"], "in_step": in_step,
+                        "in_step_schedule": "phased backward: tn_field_bwd_phase(MLP) / HIP event / SCATTER / HIP event / JOIN in 20 EXTRA steps after the timed "
+                                            "region -- the timed `value` runs the one-call backward (tn_render_rays_train_bwd), which cannot take events",
+                        "frac_in_step": None if in_step is None else nbytes / (in_step["mean_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                        "note": "the main grid's scatter entry point = k_seg_bin + k_seg_fold as the field backward calls it (d position comes from "
+                                "k_field_dpos); the bin pass is bound by instruction issue, the fold streams its records into double-precision LDS atomics",
+                        "dominant_by": {"rule": "stand-alone ms x launches per step at this run's proposal-update fraction", "ms_per_step": shares},
+                        # rows whose table is L2-resident (the proposal grids: 5 MB each, 12 MB fetched for 335 MB algorithmic in the PMC passes) are stated
+                        # against the L2 rate of the guide, not against HBM -- their algorithmic bytes carry no cache credit and would exceed 1.0 there
+                        "all_kernels": {n: ({"ms": m, "GB/s": bts / (m * 1e-3) / 1e9, "bound": "l2", "peak": L2_PEAK_GBS, "frac": bts / (m * 1e-3) / 1e9 / L2_PEAK_GBS}
+                                            if n.startswith("k_prop_fwd") else
+                                            {"ms": m, "GB/s": bts / (m * 1e-3) / 1e9, "bound": "hbm", "peak": HBM_PEAK_GBS, "frac": bts / (m * 1e-3) / 1e9 / HBM_PEAK_GBS})
+                                        for n, m, bts in rows},
+                        # the MFMA-bound launches (fp32 MFMA: v_mfma_f32_32x32x2_f32 / 16x16x4_f32): achieved TFLOP/s against the dense fp32 peak
+                        "mfma": mfma_rows[1], "mfma_all": mfma_rows,
+                        # SURVEY 8d's whole-step figure: (N x bytes_ray + bytes_step) / t_step against the HBM peak
+                        "step": {"algorithmic_bytes": step_bytes, "achieved": step_gbs, "frac": step_gbs / HBM_PEAK_GBS, "proposal_update_fraction": upd}}
+            if traffic is None:
+                roofline["traffic_unavailable"] = why
+            if pmc is not None:
+                roofline["traffic_all_kernels"] = {n: sum(v["traffic_bytes"] for v in pmc_lookup(pmc, ks)) for n, ks in PMC_KEYS.items()
+                                                   if pmc_lookup(pmc, ks) is not None}
+                roofline["mfma_busy_frac"] = {k.split(" ")[0]: v["mfma_busy_frac"] for k, v in pmc.items()
+                                              if k.split(" ")[0] in ("k_field_mlp_fwd<true>", "k_field_bwd_fused<false>") and "mfma_busy_frac" in v}
+                roofline["pmc_source"] = "profiles/r06_pmc.json (read bytes = FETCH_SIZE x the calibrated factor of the kernel's read shape, scripts/pmc_summary.py)"
         result = {
             "metric": "train rays/sec (4096-ray batch, 96 samples/ray)",
             "value": world * rays * args.steps / dt,
@@ -1125,13 +1214,13 @@ def main():
             "per_rank_ms_per_step": per_rank_ms,
             "dp": dp_info,
             "hw_queues_env": os.environ.get("GPU_MAX_HW_QUEUES"),
-            "long_run": long_run,
-            "roofline": roofline,
         }
+        if args.full:
+            result.update(long_run=long_run, roofline=roofline)
         if parity is not None:
             result["parity"] = parity
         default_run = world == 1 and not api and hook is None and args.mode == "shared" and rays == RAYS_PER_GPU and args.nerf_samples == 48
-        if default_run and not args.no_extras:
+        if args.full and default_run and not args.no_extras:
             # after the timed region, outside `value`: the render parity figure BASELINE.json's metric names, and the configs the driver never runs
             result["extra"] = {}
             for key, kw in (("separate_8192", dict(mode="separate", rays=8192, nerf_samples=48, path="fused", steps=12, warmup=4)),
@@ -1153,7 +1242,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 result["extra"]["eval_render"] = {"error": repr(e)}
             torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             torch.cuda.synchronize()
             cores = args.cpu_threads or min(os.cpu_count() or 1, 16)
             v, t = cpu_baseline(rays, args.cpu_steps if args.mode == "shared" else max(2, args.cpu_steps // 2), cores, args.mode)

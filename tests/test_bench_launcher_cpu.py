@@ -10,6 +10,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _env(**extra):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    # the ranks see no GPU, on a GPU machine too: they join over gloo, as on the CPU (with a device present they would take RCCL and need one GPU each)
+    env.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     env.update(extra)
     return env
 
@@ -59,3 +61,30 @@ def test_pmc_figures_are_only_quoted_for_the_kernels_they_were_measured_on(tmp_p
     f.write_text(json.dumps({"source_hash": bench.source_hash(), "kernels": pmc}))
     got, why = bench.load_pmc()
     assert got == pmc and why is None
+
+
+def test_dump_samples_large_arrays_the_same_way_every_run(tmp_path):
+    """--dump-outputs: a large array is written as a fixed sample (same indices in every run, so two builds compare element for element)."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    t = torch.arange(3 * bench.DUMP_SAMPLE, dtype=torch.float32)
+    for d in ("a", "b"):
+        (tmp_path / d).mkdir()
+        bench._dump(str(tmp_path / d), "param.field.table", t, np.float32)
+        bench._dump(str(tmp_path / d), "loss.rgb_loss", torch.tensor(0.25), np.float64)
+    a, b = np.load(tmp_path / "a" / "param.field.table.npy"), np.load(tmp_path / "b" / "param.field.table.npy")
+    assert a.dtype == np.float32 and 0.5 * bench.DUMP_SAMPLE < a.size <= bench.DUMP_SAMPLE and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0)  # distinct, sorted indices of the flattened array
+    s = np.load(tmp_path / "a" / "loss.rgb_loss.npy")
+    assert s.dtype == np.float64 and float(s) == 0.25
+
+
+def test_options_that_need_full_or_one_rank_are_refused():
+    """--ops prints what --full measures; --dump-outputs replays the step on one rank: refused loudly, before any GPU work."""
+    for extra in (["--ops"], ["--gpus", "2", "--dump-outputs", "d"], ["--force-dp", "--dump-outputs", "d"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, env=_env(), capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "error:" in r.stderr, (extra, r.stderr[-500:])

@@ -1,4 +1,4 @@
-"""bench.py's default line on the GPU, end to end: one subprocess run with few steps, every object the contract and DESIGN.md section 5 name is
+"""bench.py's line on the GPU, end to end.  --full: one subprocess run with few steps, every object the contract and DESIGN.md section 5 name is
 there and NO extra leg failed (an extra's exception is caught into {"error": ...} so that it never costs the headline -- which also means nothing
 else notices it: round 5 shipped a NameError in all four legs for an hour)."""
 import json
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_default_line_has_every_object_and_no_failed_leg():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--long-steps", "8", "--cpu-steps", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--long-steps", "8", "--cpu-steps", "1"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -48,3 +48,38 @@ def test_default_line_has_every_object_and_no_failed_leg():
     assert set(d["extra"]) == {"separate_8192", "nerf_samples_96", "model_api_amp", "fused_trainer", "eval_render", "head_bf16x3"}
     ak = rf["all_kernels"]
     assert all(v["bound"] == ("l2" if k.startswith("k_prop_fwd") else "hbm") and 0 < v["frac"] < 1.0 for k, v in ak.items()), ak
+
+
+def test_plain_line_is_the_headline_and_its_dump_is_the_same_every_run(tmp_path):
+    """Without --full: the headline keys only and --steps timed steps.  --dump-outputs: the second step of the timed path replayed from a fixed
+    state -- its losses, the parameters it started from and the Adam moments it left (float32 / float64, under 64 MB) -- the same in two runs up
+    to rounding: each array within 1e-3 of its own largest magnitude (measured: 2.4e-4 on the camera poses, whose gradient is a cancelling sum
+    over every ray; 1e-6 and below elsewhere), the losses within 1e-5."""
+    import numpy as np
+
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "rays/s" and d["higher_is_better"] is True
+        assert abs(d["value"] - 4096 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+        for k in ("roofline", "long_run", "parity", "extra", "cpu_baseline"):
+            assert k not in d, k
+        files = sorted(out.glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        dumps.append({f.name[:-len(".npy")]: np.load(f) for f in files})
+    a, b = dumps
+    assert a.keys() == b.keys()
+    assert {n.split(".")[0] for n in a} == {"loss", "param_in", "exp_avg", "exp_avg_sq"}
+    table = "field.mlp_base.model.0.hash_table"
+    assert np.abs(a[f"exp_avg.{table}"]).max() > 0 and np.abs(a[f"exp_avg_sq.{table}"]).max() > 0  # the backward's magnitudes are in the dump
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and np.isfinite(a[name]).all(), name
+        x, y = a[name].astype(np.float64), b[name].astype(np.float64)
+        if name.startswith("loss."):
+            assert np.allclose(x, y, rtol=1e-5, atol=0), (name, x, y)
+        else:
+            assert np.abs(x - y).max() <= 1e-3 * np.abs(x).max(), (name, float(np.abs(x - y).max()), float(np.abs(x).max()))
