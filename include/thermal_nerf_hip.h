@@ -660,6 +660,38 @@ TN_API int tn_splat_bin(const TnSplatCamera* camera, const float* depths, int64_
 TN_API int tn_splat_raster(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections, const float* background4,
                     int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, tn_stream_t stream);
 
+/* ---- N4 backward: the exact derivative of the render above with respect to the Gaussians (rgb, thermal, accumulation; depth is not
+ * differentiated).  Deterministic: no float atomics, the same inputs give bit-identical gradients.  Call order of one training frame:
+ * tn_splat_project -> tn_splat_bin -> tn_splat_raster_train, then tn_splat_raster_backward -> tn_splat_project_backward on the SAME
+ * workspace (nothing may run a frame through it in between).
+ *
+ * tn_splat_raster_train: tn_splat_raster plus, per pixel, out_transmittance [H,W] (final T) and out_last [H,W] int32 (number of entries of the
+ * pixel's tile list up to and including the last Gaussian that contributed; 0 = none).  out_rgbt [H,W,4] holds the colour BEFORE the clamp to
+ * 1 (the caller clamps, and owns the clamp's gradient); out_depth and out_alpha are as tn_splat_raster writes them. */
+TN_API int tn_splat_raster_train(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections, const float* background4,
+                          int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, float* out_transmittance, int32_t* out_last,
+                          tn_stream_t stream);
+/* scratch of tn_splat_raster_backward: one record of partial gradients per (Gaussian, tile) pair and a per-Gaussian map; -1 on bad sizes */
+TN_API int64_t tn_splat_backward_workspace_bytes(int64_t num_gaussians, int64_t max_intersections);
+/* raster backward.  num_intersections = tn_splat_bin's count; transmittance / last from tn_splat_raster_train; conics [N,3] from
+ * tn_splat_project; v_rgbt [H,W,4] = dL / d(colour before the clamp), v_alpha [H,W] = dL / d accumulation.  Outputs per Gaussian: v_xys [N,2],
+ * v_conics [N,3], v_colors [N,4] (RGB + thermal after the SH clamp / sigmoid), v_log_opacity [N] = dL / d ln(opacity used by the rasteriser,
+ * x compensation in antialiased mode).  Gaussians the forward culled get zeros. */
+TN_API int tn_splat_raster_backward(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                             int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last, const float* conics,
+                             const float* v_rgbt, const float* v_alpha, void* bwd_workspace, int64_t bwd_workspace_bytes, float* v_xys, float* v_conics,
+                             float* v_colors, float* v_log_opacity, tn_stream_t stream);
+/* projection + SH backward: the parameters and settings of the tn_splat_project call, its radii, and tn_splat_raster_backward's outputs ->
+ * gradients in the parameters' layouts: v_means [N,3], v_log_scales [N,3], v_quats [N,4] (through the normalisation), v_opacities [N]
+ * (logits), v_features_dc [N,3], v_features_rest [N,K,3], v_thermal_dc [N,1], v_thermal_rest [N,K,1] (zero beyond sh_degree).  The view
+ * directions of the SH colours carry no gradient (splatfacto.py:770 detaches the means there). */
+TN_API int tn_splat_project_backward(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
+                              const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
+                              int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, const int32_t* radii,
+                              const float* v_xys, const float* v_conics, const float* v_colors, const float* v_log_opacity, float* v_means,
+                              float* v_log_scales, float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest,
+                              float* v_thermal_dc, float* v_thermal_rest, tn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TN_LIB names another build of the same library (A/B timing of kernel variants); there is still no fallback if it cannot be loaded
 LIB_PATH = os.path.abspath(os.environ["TN_LIB"]) if os.environ.get("TN_LIB") else os.path.join(_HERE, "libthermal_nerf_hip.so")
-ABI_VERSION = 307  # include/thermal_nerf_hip.h as this binding was written for (tn_version() of the library must match)
+ABI_VERSION = 308  # include/thermal_nerf_hip.h as this binding was written for (tn_version() of the library must match)
 TN_MAX_LEVELS = 16
 TN_MAX_SAMPLES = 256
 TN_RENDER_SCRATCH_FLOATS = 4096
@@ -177,6 +177,10 @@ SIGNATURES = {
     "tn_splat_project": (C.c_int, [_p] * 9 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, _p]),
     "tn_splat_bin": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _p]),
     "tn_splat_raster": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _p, _p, _p]),
+    "tn_splat_raster_train": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _p, _p, _p, _p, _p]),
+    "tn_splat_backward_workspace_bytes": (_i64, [_i64, _i64]),
+    "tn_splat_raster_backward": (C.c_int, [_p, _i64, _p, _i64, _i64] + [_p] * 7 + [_i64] + [_p] * 5),
+    "tn_splat_project_backward": (C.c_int, [_p] * 9 + [_i64, _i32, _i32, _i32] + [_p] * 14),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -21,7 +21,8 @@
 //                      one); every lane then walks the batch front to back.  The LDS reads are wave-uniform broadcasts (conflict-free);
 //                      a wave whose 64 pixels are all finished skips the arithmetic; the colour (RGB+T) and depth images come out of ONE
 //                      pass (the reference runs the rasteriser twice; in "antialiased" mode the depth pass uses the uncompensated
-//                      opacity, so that variant carries a second transmittance).
+//                      opacity, so that variant carries a second transmittance).  The TRAIN instantiation (tn_splat_raster_train) also
+//                      keeps each pixel's final transmittance and last contributor for the backward at the end of this file.
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -375,11 +376,15 @@ __global__ void k_splat_tile_len(const int32_t* __restrict__ tile_bins, int num_
 }
 
 // ------------------------------------------------------------------------------------------------ rasteriser
-template <bool AA>
+// TRAIN: the training variant (tn_splat_raster_train) also leaves what the backward needs per pixel -- the final transmittance and the number
+// of list entries up to and including the last Gaussian that contributed -- and writes the colour BEFORE the clamp to 1 (the caller clamps,
+// so the clamp's gradient mask is the caller's).  TRAIN = false is the eval rasteriser, unchanged.
+template <bool AA, bool TRAIN>
 __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict__ recs, const int32_t* __restrict__ sorted_ids,
                                                       const int32_t* __restrict__ tile_bins, const int32_t* __restrict__ tile_order, int W, int H,
                                                       int tbx, float4 background, float* __restrict__ out_rgbt, float* __restrict__ out_depth,
-                                                      float* __restrict__ out_alpha, uint32_t* __restrict__ depth_max) {
+                                                      float* __restrict__ out_alpha, uint32_t* __restrict__ depth_max, float* __restrict__ out_T,
+                                                      int32_t* __restrict__ out_last) {
   __shared__ float4 sa[SPLAT_BATCH], sb[SPLAT_BATCH], sc[SPLAT_BATCH], sd[SPLAT_BATCH];
   __shared__ float smax[4];
   const int tile = tile_order[blockIdx.x];
@@ -397,6 +402,7 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
   f32x2 acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};
   float dacc = 0.f;
   bool done = !inside, done_d = !inside;
+  int last = 0;  // TRAIN: list entries of this tile up to and including the last contributor
   // software pipeline: the records of batch i+1 are fetched (two dependent gathers: id, then the 64-byte record) while batch i is blended
   float4 ra, rb, rc, rd;
   ra = rb = rc = rd = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -457,6 +463,7 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
             acc23 = __builtin_elementwise_fma(v2, (f32x2){c.z, c.w}, acc23);
             if (!AA) dacc = fmaf(vis, sd[k].x, dacc);
             T = nT;
+            if (TRAIN) last = base + k - begin + 1;
           }
         }
         if (AA) {
@@ -475,9 +482,16 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
   float dmax = 0.f;
   if (inside) {
     int64_t p = (int64_t)iy * W + ix;
-    float4 o = make_float4(fminf(acc[0] + T * background.x, 1.0f), fminf(acc[1] + T * background.y, 1.0f), fminf(acc[2] + T * background.z, 1.0f),
-                           fminf(acc[3] + T * background.w, 1.0f));
-    reinterpret_cast<float4*>(out_rgbt)[p] = o;
+    if (TRAIN) {
+      reinterpret_cast<float4*>(out_rgbt)[p] =
+          make_float4(acc[0] + T * background.x, acc[1] + T * background.y, acc[2] + T * background.z, acc[3] + T * background.w);
+      out_T[p] = T;
+      out_last[p] = last;
+    } else {
+      float4 o = make_float4(fminf(acc[0] + T * background.x, 1.0f), fminf(acc[1] + T * background.y, 1.0f), fminf(acc[2] + T * background.z, 1.0f),
+                             fminf(acc[3] + T * background.w, 1.0f));
+      reinterpret_cast<float4*>(out_rgbt)[p] = o;
+    }
     out_alpha[p] = 1.0f - T;
     out_depth[p] = dacc;  // un-normalised: k_splat_depth_finalize divides by alpha
     dmax = dacc;
@@ -498,6 +512,383 @@ __global__ void k_splat_depth_finalize(float* __restrict__ depth, const float* _
   if (i >= n) return;
   float a = alpha[i];
   depth[i] = a > 0.f ? depth[i] / a : __uint_as_float(*depth_max);
+}
+
+// ------------------------------------------------------------------------------------------------ backward
+// The exact derivative of the forward above (rgb, thermal, accumulation; depth is not differentiated).  Three steps, no float atomics, so
+// the gradients are bit-reproducible:
+//   k_splat_raster_bwd  block = one tile, same lane -> pixel map as the forward.  Every pixel walks its list from the last contributor back
+//                       to the front, recomputing alpha under the forward's rules and the transmittance before each Gaussian as T / (1 - alpha).
+//                       The SPLAT_PAIR_GRADS partial sums of a (tile, Gaussian) pair are reduced over the wave (fixed butterfly), then over the
+//                       4 waves (fixed order), and written ONCE to the pair's record.  Records sit at the pair's position in the depth-ordered
+//                       list k_splat_intersect emitted before the sort by tile: there each Gaussian's pairs form one contiguous run.
+//   k_splat_pair_fold   thread = Gaussian: sums its run in list order -> d xys, d conics, d colour (RGB+T), d ln(opacity)
+//   k_splat_project_bwd thread = Gaussian: through the EWA projection, the covariance, the quaternion normalisation, SH and sigmoids to the
+//                       parameters, written in their own layouts.
+#define SPLAT_PAIR_GRADS 10  // per pair, summed over pixels: dsigma*dx, dsigma*dy, dsigma*dx^2/2, dsigma*dx*dy, dsigma*dy^2/2, d colour (4), d ln(opacity)
+
+struct SplatBwdWs {
+  float* pair;     // [max_intersections][SPLAT_PAIR_GRADS]
+  int32_t* start;  // [N] first record of each Gaussian's run
+};
+
+static SplatBwdWs splat_bwd_layout(void* base, int64_t N, int64_t capacity, size_t* total) {
+  SplatBwdWs w;
+  char* p = (char*)base;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return base ? (void*)(p + o) : (void*)nullptr; };
+  w.pair = (float*)take(sizeof(float) * SPLAT_PAIR_GRADS * (size_t)std::max<int64_t>(capacity, 1));
+  w.start = (int32_t*)take(4 * (size_t)std::max<int64_t>(N, 1));
+  if (total) *total = off;
+  return w;
+}
+
+extern "C" int64_t tn_splat_backward_workspace_bytes(int64_t num_gaussians, int64_t max_intersections) {
+  if (num_gaussians < 0 || max_intersections < 0) return -1;
+  size_t total = 0;
+  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, &total);
+  return (int64_t)total;
+}
+
+// start of Gaussian order[j]'s run of pairs: cum is the inclusive scan of the tight tile counts in depth order
+__global__ void k_splat_run_start(const int32_t* __restrict__ order, const int32_t* __restrict__ cum, const int32_t* __restrict__ thits, int64_t N,
+                                  int32_t* __restrict__ start) {
+  int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (j >= N) return;
+  const int32_t g = order[j];
+  start[g] = cum[j] - thits[g];
+}
+
+__global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __restrict__ recs, const int32_t* __restrict__ sorted_ids,
+                                                          const int32_t* __restrict__ tile_bins, const int32_t* __restrict__ tile_order, int W, int H,
+                                                          int tbx, float4 background, const float* __restrict__ final_T, const int32_t* __restrict__ last,
+                                                          const float* __restrict__ v_rgbt, const float* __restrict__ v_alpha,
+                                                          const int32_t* __restrict__ start, const int32_t* __restrict__ tbox, float* __restrict__ pair) {
+  __shared__ float4 sa[SPLAT_BATCH], sb[SPLAT_BATCH], sc[SPLAT_BATCH];
+  __shared__ float sp[4][SPLAT_PAIR_GRADS][SPLAT_BATCH];  // per wave partial sums of the batch's Gaussians
+  __shared__ int s_n;
+  const int tile = tile_order[blockIdx.x];
+  const int tile_x = tile % tbx, tile_y = tile / tbx;
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int qx0 = tile_x * SPLAT_BLOCK + 8 * (wv & 1), qy0 = tile_y * SPLAT_BLOCK + 8 * (wv >> 1);
+  const int ix = qx0 + (lane & 7), iy = qy0 + (lane >> 3);
+  const bool inside = ix < W && iy < H;
+  const float pxf = (float)ix + 0.5f, pyf = (float)iy + 0.5f;
+  const float qcx = (float)qx0 + 4.0f, qcy = (float)qy0 + 4.0f;
+  const int begin = tile_bins[2 * tile];
+  // T: transmittance after the Gaussian being visited (starts at the final one); rest: sum over the Gaussians behind it of
+  // alpha_j T_j <colour_j, v> plus the background's T_final <bg, v> - T_final d accumulation (accumulation = 1 - T_final)
+  float T = 1.f, rest = 0.f;
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  int n = 0;
+  if (inside) {
+    const int64_t p = (int64_t)iy * W + ix;
+    T = final_T[p];
+    n = last[p];
+    v = reinterpret_cast<const float4*>(v_rgbt)[p];
+    rest = T * (v.x * background.x + v.y * background.y + v.z * background.z + v.w * background.w - v_alpha[p]);
+  }
+  int wn = n;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) wn = max(wn, __shfl_xor(wn, o, 64));
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  if (lane == 0 && wn > 0) atomicMax(&s_n, wn);
+  __syncthreads();
+  const int top = begin + s_n;
+  for (int hi = top; hi > begin; hi -= SPLAT_BATCH) {
+    const int lo = max(begin, hi - SPLAT_BATCH), cnt = hi - lo;
+    __syncthreads();  // the previous batch's records and partial sums are consumed
+    int64_t dst = -1;
+    if ((int)threadIdx.x < cnt) {
+      const int g = sorted_ids[lo + (int)threadIdx.x];
+      const SplatRec* r = recs + g;
+      sa[threadIdx.x] = r->a; sb[threadIdx.x] = r->b; sc[threadIdx.x] = r->c;
+      const int4 bx = reinterpret_cast<const int4*>(tbox)[g];
+      dst = (int64_t)start[g] + (tile_y - bx.y) * (bx.z - bx.x) + (tile_x - bx.x);
+    }
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+#pragma unroll
+      for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) sp[w][c][threadIdx.x] = 0.f;
+    __syncthreads();
+    // back to front; per-wave culling as in the forward (the quadrant test is exact: outside it alpha < 1/255)
+#pragma unroll 1
+    for (int q = (cnt - 1) >> 6; q >= 0; --q) {
+      const int kk = q * 64 + lane;
+      bool keep = false;
+      if (kk < cnt && lo + kk < begin + wn) {
+        float4 a = sa[kk], b = sb[kk];
+        keep = fabsf(a.x - qcx) <= b.z + 3.5f && fabsf(a.y - qcy) <= b.w + 3.5f;
+      }
+      uint64_t live = __ballot(keep);
+      while (live) {
+        const int bit = 63 - __builtin_clzll(live);
+        live &= ~(1ull << bit);
+        const int k = q * 64 + bit;
+        // the forward's arithmetic, bit for bit: the same set of contributors
+        const float4 a = sa[k], b = sb[k];
+        const float dx = a.x - pxf, dy = a.y - pyf;
+        const float power = fmaf(dx, fmaf(a.z, dx, a.w * dy), b.x * dy * dy);
+        const float raw = __builtin_amdgcn_exp2f(b.y - power);
+        const float alpha = fminf(0.999f, raw);
+        const bool use = lo + k - begin < n && power >= 0.f && alpha >= (1.0f / 255.0f);
+        if (!__any(use ? 1 : 0)) continue;
+        float g[SPLAT_PAIR_GRADS];
+#pragma unroll
+        for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) g[c] = 0.f;
+        if (use) {
+          const float om = 1.0f - alpha;
+          T = T / om;  // transmittance in front of this Gaussian
+          const float4 col = sc[k];
+          const float cv = col.x * v.x + col.y * v.y + col.z * v.z + col.w * v.w;
+          const float vis = alpha * T;
+          const float d_alpha = T * cv - rest / om;
+          rest = fmaf(vis, cv, rest);
+          g[5] = vis * v.x; g[6] = vis * v.y; g[7] = vis * v.z; g[8] = vis * v.w;
+          if (raw <= 0.999f) {  // the clamp passes gradient where torch.clamp's backward does
+            const float d_lnop = d_alpha * alpha;  // alpha = opacity exp(-sigma)
+            const float d_sigma = -d_lnop;
+            g[0] = d_sigma * dx; g[1] = d_sigma * dy;
+            g[2] = 0.5f * d_sigma * dx * dx; g[3] = d_sigma * dx * dy; g[4] = 0.5f * d_sigma * dy * dy;
+            g[9] = d_lnop;
+          }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+          for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) g[c] += __shfl_xor(g[c], o, 64);
+        if (lane == 0) {
+#pragma unroll
+          for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) sp[wv][c][k] = g[c];
+        }
+      }
+    }
+    __syncthreads();
+    if (dst >= 0) {
+      float* o = pair + dst * SPLAT_PAIR_GRADS;
+#pragma unroll
+      for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) o[c] = ((sp[0][c][threadIdx.x] + sp[1][c][threadIdx.x]) + sp[2][c][threadIdx.x]) + sp[3][c][threadIdx.x];
+    }
+  }
+}
+
+__global__ void k_splat_pair_fold(const float* __restrict__ pair, const int32_t* __restrict__ start, const int32_t* __restrict__ thits,
+                                  const float* __restrict__ conics, int64_t N, float* __restrict__ v_xys, float* __restrict__ v_conics,
+                                  float* __restrict__ v_colors, float* __restrict__ v_lnop) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  float s[SPLAT_PAIR_GRADS];
+#pragma unroll
+  for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) s[c] = 0.f;
+  const int cnt = thits[i];
+  if (cnt > 0) {
+    const float* p = pair + (int64_t)start[i] * SPLAT_PAIR_GRADS;
+    for (int j = 0; j < cnt; ++j, p += SPLAT_PAIR_GRADS)
+#pragma unroll
+      for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) s[c] += p[c];
+  }
+  // d sigma / d xy = (cx dx + cy dy, cy dx + cz dy), dx = x - pixel
+  const float cx = conics[3 * i], cy = conics[3 * i + 1], cz = conics[3 * i + 2];
+  v_xys[2 * i] = cx * s[0] + cy * s[1];
+  v_xys[2 * i + 1] = cy * s[0] + cz * s[1];
+  v_conics[3 * i] = s[2]; v_conics[3 * i + 1] = s[3]; v_conics[3 * i + 2] = s[4];
+  v_colors[4 * i] = s[5]; v_colors[4 * i + 1] = s[6]; v_colors[4 * i + 2] = s[7]; v_colors[4 * i + 3] = s[8];
+  v_lnop[i] = s[9];
+}
+
+// SH basis of degree <= 3 at the unit direction (x, y, z), the coefficients of sh_eval
+__device__ __forceinline__ void sh_basis(int degree, float x, float y, float z, float* b) {
+  b[0] = 0.28209479177387814f;
+  if (degree < 1) return;
+  b[1] = -0.4886025119029199f * y; b[2] = 0.4886025119029199f * z; b[3] = -0.4886025119029199f * x;
+  if (degree < 2) return;
+  float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+  b[4] = 1.0925484305920792f * xy; b[5] = -1.0925484305920792f * yz; b[6] = 0.31539156525252005f * (2.0f * zz - xx - yy);
+  b[7] = -1.0925484305920792f * xz; b[8] = 0.5462742152960396f * (xx - yy);
+  if (degree < 3) return;
+  b[9] = -0.5900435899266435f * y * (3.0f * xx - yy); b[10] = 2.890611442640554f * xy * z; b[11] = -0.4570457994644658f * y * (4.0f * zz - xx - yy);
+  b[12] = 0.3731763325901154f * z * (2.0f * zz - 3.0f * xx - 3.0f * yy); b[13] = -0.4570457994644658f * x * (4.0f * zz - xx - yy);
+  b[14] = 1.445305721320277f * z * (xx - yy); b[15] = -0.5900435899266435f * x * (xx - 3.0f * yy);
+}
+
+__global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const float* __restrict__ means, const float* __restrict__ log_scales,
+                                                           const float* __restrict__ quats, const float* __restrict__ opac_logit,
+                                                           const float* __restrict__ f_dc, const float* __restrict__ f_rest, const float* __restrict__ t_dc,
+                                                           const float* __restrict__ t_rest, int64_t N, int sh_degree, int rest_coeffs, int antialiased,
+                                                           const int32_t* __restrict__ radii, const float* __restrict__ v_xys,
+                                                           const float* __restrict__ v_conics, const float* __restrict__ v_colors,
+                                                           const float* __restrict__ v_lnop, float* __restrict__ g_means, float* __restrict__ g_scales,
+                                                           float* __restrict__ g_quats, float* __restrict__ g_opac, float* __restrict__ g_fdc,
+                                                           float* __restrict__ g_frest, float* __restrict__ g_tdc, float* __restrict__ g_trest) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  float gm[3] = {0.f, 0.f, 0.f}, gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f}, gop = 0.f;
+  float gcol[4] = {0.f, 0.f, 0.f, 0.f};  // d (colour before the clamp / sigmoid argument), per channel
+  float basis[16];
+  int nb = 0;
+  if (radii[i] > 0) {  // Gaussians the forward culled get no gradient
+    const float mx = means[3 * i], my = means[3 * i + 1], mz = means[3 * i + 2];
+    const float* V = cam.view;
+    const float px = V[0] * mx + V[1] * my + V[2] * mz + V[3];
+    const float py = V[4] * mx + V[5] * my + V[6] * mz + V[7];
+    const float pz = V[8] * mx + V[9] * my + V[10] * mz + V[11];
+    const float q0w = quats[4 * i], q0x = quats[4 * i + 1], q0y = quats[4 * i + 2], q0z = quats[4 * i + 3];
+    const float qn = 1.0f / sqrtf(q0w * q0w + q0x * q0x + q0y * q0y + q0z * q0z);
+    const float qw = q0w * qn, qx = q0x * qn, qy = q0y * qn, qz = q0z * qn;
+    const float R[9] = {1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy - qw * qz), 2.f * (qx * qz + qw * qy),
+                        2.f * (qx * qy + qw * qz), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz - qw * qx),
+                        2.f * (qx * qz - qw * qy), 2.f * (qy * qz + qw * qx), 1.f - 2.f * (qx * qx + qy * qy)};
+    const float s[3] = {expf(log_scales[3 * i]), expf(log_scales[3 * i + 1]), expf(log_scales[3 * i + 2])};
+    float M[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) M[3 * r + c] = R[3 * r + c] * s[c];
+    float S[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) S[3 * r + c] = M[3 * r] * M[3 * c] + M[3 * r + 1] * M[3 * c + 1] + M[3 * r + 2] * M[3 * c + 2];
+    const float tan_x = 0.5f * (float)cam.W / cam.fx, tan_y = 0.5f * (float)cam.H / cam.fy;
+    const float lx = 1.3f * tan_x, ly = 1.3f * tan_y;
+    const float ux = px / pz, uy = py / pz;
+    const bool in_x = ux >= -lx && ux <= lx, in_y = uy >= -ly && uy <= ly;
+    const float tx = pz * fminf(lx, fmaxf(-lx, ux));
+    const float ty = pz * fminf(ly, fmaxf(-ly, uy));
+    const float rz = 1.0f / pz, rz2 = rz * rz;
+    const float J0[3] = {cam.fx * rz, 0.f, -cam.fx * tx * rz2};
+    const float J1[3] = {0.f, cam.fy * rz, -cam.fy * ty * rz2};
+    float T0[3], T1[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      T0[c] = J0[0] * V[c] + J0[1] * V[4 + c] + J0[2] * V[8 + c];
+      T1[c] = J1[0] * V[c] + J1[1] * V[4 + c] + J1[2] * V[8 + c];
+    }
+    float ST0[3], ST1[3];  // Sigma T0^T, Sigma T1^T (Sigma is symmetric)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      ST0[r] = S[3 * r] * T0[0] + S[3 * r + 1] * T0[1] + S[3 * r + 2] * T0[2];
+      ST1[r] = S[3 * r] * T1[0] + S[3 * r + 1] * T1[1] + S[3 * r + 2] * T1[2];
+    }
+    const float c00 = T0[0] * ST0[0] + T0[1] * ST0[1] + T0[2] * ST0[2];
+    const float c01 = T0[0] * ST1[0] + T0[1] * ST1[1] + T0[2] * ST1[2];
+    const float c11 = T1[0] * ST1[0] + T1[1] * ST1[1] + T1[2] * ST1[2];
+    const float a = c00 + 0.3f, b = c01, c = c11 + 0.3f;
+    const float det = a * c - b * b, det_orig = c00 * c11 - c01 * c01;
+    // conic = (c, -b, a) / det
+    const float vcx = v_conics[3 * i], vcy = v_conics[3 * i + 1], vcz = v_conics[3 * i + 2];
+    const float id = 1.0f / det, id2 = id * id;
+    float va = -vcx * c * c * id2 + vcy * b * c * id2 + vcz * (id - a * c * id2);
+    float vb = vcx * 2.f * b * c * id2 + vcy * (-id - 2.f * b * b * id2) + vcz * 2.f * a * b * id2;
+    float vc = vcx * (id - a * c * id2) + vcy * a * b * id2 - vcz * a * a * id2;
+    const float dl = v_lnop[i];
+    if (antialiased && det_orig > 0.f) {  // ln compensation = (ln det_orig - ln det) / 2
+      const float io = 1.0f / det_orig;
+      va += 0.5f * dl * (c11 * io - c * id);
+      vb += 0.5f * dl * (-2.f * c01 * io + 2.f * b * id);
+      vc += 0.5f * dl * (c00 * io - a * id);
+    }
+    // opacity = sigmoid(logit): d ln(sigmoid) / d logit = sigmoid(-logit)
+    gop = dl / (1.0f + expf(opac_logit[i]));
+    // cov2d = T Sigma T^T, T = J W
+    float gT0[3], gT1[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      gT0[r] = 2.f * va * ST0[r] + vb * ST1[r];
+      gT1[r] = 2.f * vc * ST1[r] + vb * ST0[r];
+    }
+    float G[9];  // d Sigma, entries taken independently
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc) G[3 * r + cc] = va * T0[r] * T0[cc] + vb * T0[r] * T1[cc] + vc * T1[r] * T1[cc];
+    float gJ0[3], gJ1[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      gJ0[r] = gT0[0] * V[4 * r] + gT0[1] * V[4 * r + 1] + gT0[2] * V[4 * r + 2];
+      gJ1[r] = gT1[0] * V[4 * r] + gT1[1] * V[4 * r + 1] + gT1[2] * V[4 * r + 2];
+    }
+    float g_rz = cam.fx * gJ0[0] + cam.fy * gJ1[1];
+    const float g_rz2 = -cam.fx * tx * gJ0[2] - cam.fy * ty * gJ1[2];
+    const float g_tx = -cam.fx * rz2 * gJ0[2], g_ty = -cam.fy * rz2 * gJ1[2];
+    g_rz += 2.f * rz * g_rz2;
+    float gpx = 0.f, gpy = 0.f, gpz = -rz * rz * g_rz;
+    // tx = pz clamp(px / pz): inside the clamp d tx = d px; clamped, tx = +-lim pz
+    if (in_x) gpx += g_tx; else gpz += g_tx * (ux > 0.f ? lx : -lx);
+    if (in_y) gpy += g_ty; else gpz += g_ty * (uy > 0.f ? ly : -ly);
+#pragma unroll
+    for (int cc = 0; cc < 3; ++cc) gm[cc] = V[cc] * gpx + V[4 + cc] * gpy + V[8 + cc] * gpz;
+    // xys = 0.5 W hx / (hw + 1e-6) + cx - 0.5, ...
+    const float* P = cam.proj;
+    const float hx = P[0] * mx + P[1] * my + P[2] * mz + P[3];
+    const float hy = P[4] * mx + P[5] * my + P[6] * mz + P[7];
+    const float hw = P[12] * mx + P[13] * my + P[14] * mz + P[15];
+    const float rw = 1.0f / (hw + 1e-6f);
+    const float vx = v_xys[2 * i], vy = v_xys[2 * i + 1];
+    const float g_hx = vx * 0.5f * (float)cam.W * rw, g_hy = vy * 0.5f * (float)cam.H * rw;
+    const float g_hw = -(vx * 0.5f * (float)cam.W * hx + vy * 0.5f * (float)cam.H * hy) * rw * rw;
+#pragma unroll
+    for (int cc = 0; cc < 3; ++cc) gm[cc] += P[cc] * g_hx + P[4 + cc] * g_hy + P[12 + cc] * g_hw;
+    // Sigma = M M^T, M = R diag(s): d M = (G + G^T) M
+    float gR[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc) {
+        float gM = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gM += (G[3 * r + k] + G[3 * k + r]) * M[3 * k + cc];
+        gs[cc] += gM * R[3 * r + cc];
+        gR[3 * r + cc] = gM * s[cc];
+      }
+#pragma unroll
+    for (int cc = 0; cc < 3; ++cc) gs[cc] *= s[cc];  // d log-scale
+    // rotation matrix of the normalised quaternion
+    const float dw = 2.f * (-qz * gR[1] + qy * gR[2] + qz * gR[3] - qx * gR[5] - qy * gR[6] + qx * gR[7]);
+    const float dx = 2.f * (qy * gR[1] + qz * gR[2] + qy * gR[3] - 2.f * qx * gR[4] - qw * gR[5] + qz * gR[6] + qw * gR[7] - 2.f * qx * gR[8]);
+    const float dy = 2.f * (-2.f * qy * gR[0] + qx * gR[1] + qw * gR[2] + qx * gR[3] + qz * gR[5] - qw * gR[6] + qz * gR[7] - 2.f * qy * gR[8]);
+    const float dz = 2.f * (-2.f * qz * gR[0] - qw * gR[1] + qx * gR[2] + qw * gR[3] - 2.f * qz * gR[4] + qy * gR[5] + qx * gR[6] + qy * gR[7]);
+    const float dot = qw * dw + qx * dx + qy * dy + qz * dz;
+    gq[0] = (dw - qw * dot) * qn; gq[1] = (dx - qx * dot) * qn; gq[2] = (dy - qy * dot) * qn; gq[3] = (dz - qz * dot) * qn;
+    // colour: clamp(SH + 0.5, min 0) (view directions carry no gradient), or sigmoid of the DC term
+    const float* vcol = v_colors + 4 * i;
+    if (sh_degree >= 0) {
+      float ddx = mx - cam.pos[0], ddy = my - cam.pos[1], ddz = mz - cam.pos[2];
+      const float dn = 1.0f / sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
+      ddx *= dn; ddy *= dn; ddz *= dn;
+      const float* rest = f_rest + i * rest_coeffs * 3;
+      const float* trest = t_rest + i * rest_coeffs;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) gcol[ch] = sh_eval(sh_degree, ddx, ddy, ddz, f_dc + 3 * i, rest, 3, ch) + 0.5f >= 0.0f ? vcol[ch] : 0.f;
+      gcol[3] = sh_eval(sh_degree, ddx, ddy, ddz, t_dc + i, trest, 1, 0) + 0.5f >= 0.0f ? vcol[3] : 0.f;
+      nb = (sh_degree + 1) * (sh_degree + 1);
+      sh_basis(sh_degree, ddx, ddy, ddz, basis);
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const float sg = 1.0f / (1.0f + expf(-f_dc[3 * i + ch]));
+        gcol[ch] = vcol[ch] * sg * (1.0f - sg);
+      }
+      const float sg = 1.0f / (1.0f + expf(-t_dc[i]));
+      gcol[3] = vcol[3] * sg * (1.0f - sg);
+    }
+  }
+#pragma unroll
+  for (int cc = 0; cc < 3; ++cc) { g_means[3 * i + cc] = gm[cc]; g_scales[3 * i + cc] = gs[cc]; }
+#pragma unroll
+  for (int cc = 0; cc < 4; ++cc) g_quats[4 * i + cc] = gq[cc];
+  g_opac[i] = gop;
+  const float b0 = nb > 0 ? basis[0] : 1.0f;  // sigmoid path: the DC gradient is gcol itself
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) g_fdc[3 * i + ch] = b0 * gcol[ch];
+  g_tdc[i] = b0 * gcol[3];
+  for (int k = 1; k <= rest_coeffs; ++k) {
+    const float bk = k < nb ? basis[k] : 0.f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) g_frest[(i * rest_coeffs + (k - 1)) * 3 + ch] = bk * gcol[ch];
+    g_trest[i * rest_coeffs + (k - 1)] = bk * gcol[3];
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ entry points
@@ -625,14 +1016,104 @@ extern "C" int tn_splat_raster(const TnSplatCamera* camera, int64_t num_gaussian
   float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
   hipStream_t st = tn_s(stream);
   if (antialiased)
-    hipLaunchKernelGGL(k_splat_raster<true>, dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, out_rgbt, out_depth,
-                       out_alpha, ws.depth_max);
+    hipLaunchKernelGGL((k_splat_raster<true, false>), dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, out_rgbt, out_depth,
+                       out_alpha, ws.depth_max, nullptr, nullptr);
   else
-    hipLaunchKernelGGL(k_splat_raster<false>, dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, out_rgbt, out_depth,
-                       out_alpha, ws.depth_max);
+    hipLaunchKernelGGL((k_splat_raster<false, false>), dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, out_rgbt, out_depth,
+                       out_alpha, ws.depth_max, nullptr, nullptr);
   TN_CHECK_LAUNCH("tn_splat_raster");
   int64_t n = (int64_t)k.W * k.H;
   hipLaunchKernelGGL(k_splat_depth_finalize, dim3((unsigned)tn_cdiv(n, 256)), dim3(256), 0, st, out_depth, out_alpha, ws.depth_max, n);
   TN_CHECK_LAUNCH("tn_splat_raster(depth)");
+  return TN_OK;
+}
+
+extern "C" int tn_splat_raster_train(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                     const float* background4, int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha,
+                                     float* out_transmittance, int32_t* out_last, tn_stream_t stream) {
+  int rc = check_cam(camera, "tn_splat_raster_train");
+  if (rc) return rc;
+  TN_REQUIRE(workspace && background4 && out_rgbt && out_depth && out_alpha && out_transmittance && out_last, "tn_splat_raster_train: null pointer");
+  TN_REQUIRE(num_gaussians >= 0 && max_intersections >= 0, "tn_splat_raster_train: bad sizes");
+  SplatCamK k = make_camk(camera);
+  SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, k.tbx * k.tby, nullptr);
+  float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
+  hipStream_t st = tn_s(stream);
+  if (antialiased)
+    hipLaunchKernelGGL((k_splat_raster<true, true>), dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg,
+                       out_rgbt, out_depth, out_alpha, ws.depth_max, out_transmittance, out_last);
+  else
+    hipLaunchKernelGGL((k_splat_raster<false, true>), dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg,
+                       out_rgbt, out_depth, out_alpha, ws.depth_max, out_transmittance, out_last);
+  TN_CHECK_LAUNCH("tn_splat_raster_train");
+  int64_t n = (int64_t)k.W * k.H;
+  hipLaunchKernelGGL(k_splat_depth_finalize, dim3((unsigned)tn_cdiv(n, 256)), dim3(256), 0, st, out_depth, out_alpha, ws.depth_max, n);
+  TN_CHECK_LAUNCH("tn_splat_raster_train(depth)");
+  return TN_OK;
+}
+
+extern "C" int tn_splat_raster_backward(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                        int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
+                                        const float* conics, const float* v_rgbt, const float* v_alpha, void* bwd_workspace,
+                                        int64_t bwd_workspace_bytes, float* v_xys, float* v_conics, float* v_colors, float* v_log_opacity,
+                                        tn_stream_t stream) {
+  int rc = check_cam(camera, "tn_splat_raster_backward");
+  if (rc) return rc;
+  TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31), "tn_splat_raster_backward: bad Gaussian count");
+  TN_REQUIRE(max_intersections >= 0 && num_intersections >= 0 && num_intersections <= max_intersections,
+             "tn_splat_raster_backward: %lld intersections for a workspace of %lld", (long long)num_intersections, (long long)max_intersections);
+  if (num_gaussians == 0) return TN_OK;
+  TN_REQUIRE(workspace && background4 && transmittance && last && conics && v_rgbt && v_alpha && bwd_workspace && v_xys && v_conics && v_colors &&
+                 v_log_opacity,
+             "tn_splat_raster_backward: null pointer");
+  const int64_t need = tn_splat_backward_workspace_bytes(num_gaussians, max_intersections);
+  TN_REQUIRE(bwd_workspace_bytes >= need, "tn_splat_raster_backward: backward workspace of %lld bytes, %lld needed", (long long)bwd_workspace_bytes,
+             (long long)need);
+  SplatCamK k = make_camk(camera);
+  const int num_tiles = k.tbx * k.tby;
+  SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, num_tiles, nullptr);
+  SplatBwdWs bw = splat_bwd_layout(bwd_workspace, num_gaussians, max_intersections, nullptr);
+  hipStream_t st = tn_s(stream);
+  hipLaunchKernelGGL(k_splat_run_start, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, st, ws.order, ws.cum, ws.thits, num_gaussians, bw.start);
+  TN_CHECK_LAUNCH("tn_splat_raster_backward(runs)");
+  if (num_intersections > 0) {
+    // pairs behind every pixel's last contributor are not visited: their records stay zero
+    if (hipMemsetAsync(bw.pair, 0, sizeof(float) * SPLAT_PAIR_GRADS * (size_t)num_intersections, st) != hipSuccess) {
+      tn_set_error("tn_splat_raster_backward: memset failed");
+      return TN_ELAUNCH;
+    }
+    float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
+    hipLaunchKernelGGL(k_splat_raster_bwd, dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg,
+                       transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair);
+    TN_CHECK_LAUNCH("tn_splat_raster_backward");
+  }
+  hipLaunchKernelGGL(k_splat_pair_fold, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, st, bw.pair, bw.start, ws.thits, conics, num_gaussians,
+                     v_xys, v_conics, v_colors, v_log_opacity);
+  TN_CHECK_LAUNCH("tn_splat_raster_backward(fold)");
+  return TN_OK;
+}
+
+extern "C" int tn_splat_project_backward(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
+                                         const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
+                                         const float* thermal_rest, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
+                                         int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics, const float* v_colors,
+                                         const float* v_log_opacity, float* v_means, float* v_log_scales, float* v_quats, float* v_opacities,
+                                         float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest, tn_stream_t stream) {
+  int rc = check_cam(camera, "tn_splat_project_backward");
+  if (rc) return rc;
+  if (num_gaussians == 0) return TN_OK;
+  TN_REQUIRE(num_gaussians > 0 && num_gaussians < (1ll << 31), "tn_splat_project_backward: bad Gaussian count");
+  TN_REQUIRE(means && log_scales && quats && opacities && features_dc && thermal_dc && radii && v_xys && v_conics && v_colors && v_log_opacity &&
+                 v_means && v_log_scales && v_quats && v_opacities && v_features_dc && v_thermal_dc,
+             "tn_splat_project_backward: null pointer");
+  TN_REQUIRE(sh_degree >= -1 && sh_degree <= 3, "tn_splat_project_backward: sh_degree %d unsupported (-1 = sigmoid of the DC term, 0..3)", sh_degree);
+  TN_REQUIRE(num_rest_coeffs >= (sh_degree < 1 ? 0 : (sh_degree + 1) * (sh_degree + 1) - 1) && num_rest_coeffs <= 15,
+             "tn_splat_project_backward: %d higher-order coefficients for degree %d", num_rest_coeffs, sh_degree);
+  TN_REQUIRE(num_rest_coeffs == 0 || (features_rest && thermal_rest && v_features_rest && v_thermal_rest), "tn_splat_project_backward: null SH coefficients");
+  SplatCamK k = make_camk(camera);
+  hipLaunchKernelGGL(k_splat_project_bwd, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, tn_s(stream), k, means, log_scales, quats, opacities,
+                     features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii, v_xys, v_conics,
+                     v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc, v_thermal_rest);
+  TN_CHECK_LAUNCH("tn_splat_project_backward");
   return TN_OK;
 }

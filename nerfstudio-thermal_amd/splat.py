@@ -5,8 +5,11 @@ The reference has no thermal-splatfacto method; the boundary mirrored here is st
 features_rest) plus a second set of SH coefficients with one channel (features_dc_thermal / features_rest_thermal) rendered through the
 same rasteriser -- the splat analogue of thermal-nerfacto's shared density.  The three gsplat calls (project_gaussians,
 spherical_harmonics, rasterize_gaussians x2) run as tn_splat_project / tn_splat_bin / tn_splat_raster of libthermal_nerf_hip.so.
-Forward only (eval render): densification, the SSIM loss and the backward pass are out of scope.  Parity is unpinned (gsplat is a third-party
-package outside the reference tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
+`get_outputs` is the eval render.  `get_train_outputs` is the same render as a differentiable function of every `gauss_params` tensor: its
+backward (tn_splat_raster_backward / tn_splat_project_backward) is the exact, bit-reproducible derivative of the forward this file computes,
+and it leaves dL/d xys per Gaussian in `last_xys_grad` (what splatfacto's densification reads as `self.xys.grad`, splatfacto.py:355).
+Depth is returned detached.  Densification, culling, opacity reset, the SSIM loss and camera-pose gradients are not built.  Parity is unpinned
+(gsplat is a third-party package outside the reference tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 """
 from __future__ import annotations
 
@@ -96,8 +99,124 @@ def _ptr(t: Optional[Tensor], dtype, name: str):
     return C.c_void_p(t.data_ptr())
 
 
+_PARAM_NAMES = ("means", "scales", "quats", "opacities", "features_dc", "features_rest", "features_dc_thermal", "features_rest_thermal")
+
+
+class _SplatRender(torch.autograd.Function):
+    """project -> bin -> training raster; backward = raster backward -> projection backward.  Inputs after `frame` are the gauss_params in
+    _PARAM_NAMES order; outputs: colour before the clamp [H,W,4] (RGB + thermal over the background), accumulation [H,W,1], depth [H,W,1]
+    (not differentiable)."""
+
+    @staticmethod
+    def forward(ctx, frame, means, scales, quats, opacities, features_dc, features_rest, features_dc_thermal, features_rest_thermal):
+        model, camera = frame["model"], frame["camera"]
+        f32, i32 = torch.float32, torch.int32
+        lib = _lib.load()
+        cam, N, H, W = frame["cam"], means.shape[0], int(camera.height), int(camera.width)
+        K, deg, aa, bg4 = features_rest.shape[1], frame["deg"], frame["aa"], frame["bg4"]
+        dev = means.device
+        tiles = ((W + BLOCK_WIDTH - 1) // BLOCK_WIDTH) * ((H + BLOCK_WIDTH - 1) // BLOCK_WIDTH)
+        opac = opacities.reshape(-1)
+        xys = torch.empty((N, 2), device=dev)
+        depths = torch.empty((N,), device=dev)
+        radii = torch.empty((N,), dtype=i32, device=dev)
+        conics = torch.empty((N, 3), device=dev)
+        comp = torch.empty((N,), device=dev)
+        hit = torch.empty((N,), dtype=i32, device=dev)
+        box = torch.empty((N, 4), dtype=i32, device=dev)
+        cap = max(model._train_cap, 1 << 16)
+        total = C.c_int64(0)
+        for attempt in range(2):
+            # a workspace of this frame's own: the backward reads it after other frames may have been rendered
+            need = int(lib.tn_splat_workspace_bytes(N, cap, tiles))
+            if need < 0:
+                raise RuntimeError("tn_splat_workspace_bytes: bad sizes")
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            wsp = C.c_void_p(ws.data_ptr())
+            _lib.check(lib.tn_splat_project(C.byref(cam), _ptr(means, f32, "means"), _ptr(scales, f32, "scales"), _ptr(quats, f32, "quats"),
+                                            _ptr(opac, f32, "opacities"), _ptr(features_dc, f32, "features_dc"),
+                                            _ptr(features_rest, f32, "features_rest") if K else None,
+                                            _ptr(features_dc_thermal, f32, "features_dc_thermal"),
+                                            _ptr(features_rest_thermal, f32, "features_rest_thermal") if K else None, N, K, deg, aa,
+                                            _ptr(xys, f32, "xys"), _ptr(depths, f32, "depths"), _ptr(radii, i32, "radii"), _ptr(conics, f32, "conics"),
+                                            _ptr(comp, f32, "compensation"), _ptr(hit, i32, "num_tiles_hit"), _ptr(box, i32, "tile_box"), wsp, cap, _stream()),
+                       "tn_splat_project")
+            rc = lib.tn_splat_bin(C.byref(cam), _ptr(depths, f32, "depths"), N, wsp, cap, C.byref(total), _stream())
+            if rc == 0:
+                break
+            if attempt == 0 and total.value > cap:  # more (Gaussian, tile) pairs than the workspace holds: grow once and redo the frame
+                cap = int(total.value * 1.25) + 1024
+                continue
+            _lib.check(rc, "tn_splat_bin")
+        model._train_cap = cap
+        model.last_projection = {"xys": xys, "depths": depths, "radii": radii, "conics": conics, "compensation": comp, "num_tiles_hit": hit, "tile_box": box}
+        model.last_num_intersections = int(total.value)
+        ctx.frame, ctx.empty = frame, total.value == 0
+        if total.value == 0:  # nothing on screen: the background, and zero gradients
+            rgbt = torch.tensor(list(bg4), device=dev).repeat(H, W, 1)
+            alpha = torch.zeros((H, W, 1), device=dev)
+            depth = torch.full((H, W, 1), 10.0, device=dev)
+            ctx.mark_non_differentiable(depth)
+            ctx.save_for_backward(means, scales, quats, opacities, features_dc, features_rest, features_dc_thermal, features_rest_thermal)
+            return rgbt, alpha, depth
+        rgbt = torch.empty((H, W, 4), device=dev)
+        depth = torch.empty((H, W, 1), device=dev)
+        alpha = torch.empty((H, W, 1), device=dev)
+        final_t = torch.empty((H, W), device=dev)
+        last = torch.empty((H, W), dtype=i32, device=dev)
+        _lib.check(lib.tn_splat_raster_train(C.byref(cam), N, wsp, cap, bg4, aa, _ptr(rgbt, f32, "rgbt"), _ptr(depth, f32, "depth"), _ptr(alpha, f32, "alpha"),
+                                             _ptr(final_t, f32, "transmittance"), _ptr(last, i32, "last"), _stream()), "tn_splat_raster_train")
+        ctx.mark_non_differentiable(depth)
+        ctx.ws, ctx.cap, ctx.total = ws, cap, int(total.value)
+        ctx.save_for_backward(means, scales, quats, opacities, features_dc, features_rest, features_dc_thermal, features_rest_thermal, radii, conics,
+                              final_t, last)
+        return rgbt, alpha, depth
+
+    @staticmethod
+    def backward(ctx, v_rgbt, v_alpha, _v_depth):
+        frame = ctx.frame
+        model = frame["model"]
+        saved = ctx.saved_tensors
+        params = saved[:8]
+        means = params[0]
+        N, dev = means.shape[0], means.device
+        if ctx.empty:
+            model.last_xys_grad = torch.zeros((N, 2), device=dev)
+            return (None,) + tuple(torch.zeros_like(p) for p in params)
+        radii, conics, final_t, last = saved[8:]
+        lib = _lib.load()
+        f32 = torch.float32
+        cam, deg, aa, bg4 = frame["cam"], frame["deg"], frame["aa"], frame["bg4"]
+        H, W = final_t.shape
+        v_rgbt = torch.zeros((H, W, 4), device=dev) if v_rgbt is None else v_rgbt.float().contiguous()
+        v_alpha = torch.zeros((H, W, 1), device=dev) if v_alpha is None else v_alpha.float().contiguous()
+        need = int(lib.tn_splat_backward_workspace_bytes(N, ctx.cap))
+        bws = torch.empty(need, dtype=torch.uint8, device=dev)
+        v_xys = torch.empty((N, 2), device=dev)
+        v_conics = torch.empty((N, 3), device=dev)
+        v_colors = torch.empty((N, 4), device=dev)
+        v_lnop = torch.empty((N,), device=dev)
+        _lib.check(lib.tn_splat_raster_backward(C.byref(cam), N, C.c_void_p(ctx.ws.data_ptr()), ctx.cap, ctx.total, bg4, _ptr(final_t, f32, "transmittance"),
+                                                _ptr(last, torch.int32, "last"), _ptr(conics, f32, "conics"), _ptr(v_rgbt, f32, "v_rgbt"),
+                                                _ptr(v_alpha, f32, "v_alpha"), C.c_void_p(bws.data_ptr()), need, _ptr(v_xys, f32, "v_xys"),
+                                                _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"), _ptr(v_lnop, f32, "v_log_opacity"), _stream()),
+                   "tn_splat_raster_backward")
+        grads = [torch.empty_like(p) for p in params]
+        K = params[5].shape[1]
+        names = ("means", "scales", "quats", "opacities", "features_dc", "features_rest", "features_dc_thermal", "features_rest_thermal")
+        pp = [_ptr(p, f32, n) if (K or n not in ("features_rest", "features_rest_thermal")) else None for p, n in zip(params, names)]
+        pp[3] = _ptr(params[3].reshape(-1), f32, "opacities")
+        gp = [_ptr(g, f32, "grad") if (K or n not in ("features_rest", "features_rest_thermal")) else None for g, n in zip(grads, names)]
+        _lib.check(lib.tn_splat_project_backward(C.byref(cam), *pp, N, K, deg, aa, _ptr(radii, torch.int32, "radii"), _ptr(v_xys, f32, "v_xys"),
+                                                 _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"), _ptr(v_lnop, f32, "v_log_opacity"), *gp,
+                                                 _stream()), "tn_splat_project_backward")
+        model.last_xys_grad = v_xys
+        return (None,) + tuple(grads)
+
+
 class ThermalSplatfactoModel(nn.Module):
-    """Forward render of RGB + thermal Gaussians.  `gauss_params` keeps the reference's names (splatfacto.py:226-235)."""
+    """RGB + thermal Gaussians: eval render (`get_outputs`) and differentiable training render (`get_train_outputs`).  `gauss_params` keeps the
+    reference's names (splatfacto.py:226-235)."""
 
     def __init__(self, config: Optional[ThermalSplatfactoModelConfig] = None, num_points: Optional[int] = None, device="cuda", seed: int = 0):
         super().__init__()
@@ -124,6 +243,8 @@ class ThermalSplatfactoModel(nn.Module):
         self.step = 0
         self._ws: Optional[Tensor] = None
         self._cap = 0
+        self._train_cap = 0  # intersection capacity the training render last needed (each training frame has a workspace of its own)
+        self.last_xys_grad: Optional[Tensor] = None
         self.last_projection: Dict[str, Tensor] = {}
         self.last_num_intersections = 0
 
@@ -209,3 +330,24 @@ class ThermalSplatfactoModel(nn.Module):
         _lib.check(lib.tn_splat_raster(C.byref(cam), N, C.c_void_p(self._ws.data_ptr()), cap, bg4, aa, _ptr(rgbt, f32, "rgbt"), _ptr(depth, f32, "depth"),
                                        _ptr(alpha, f32, "alpha"), _stream()), "tn_splat_raster")
         return {"rgb": rgbt[..., :3], "thermal": rgbt[..., 3:], "depth": depth, "accumulation": alpha, "background": background}
+
+    def get_train_outputs(self, camera: PinholeCamera) -> Dict[str, Tensor]:
+        """The render of get_outputs as a differentiable function of every gauss_params tensor (splatfacto.py:659-822 in training, without
+        the random background and the crop box).  rgb [H,W,3], thermal [H,W,1] and accumulation [H,W,1] carry gradients; depth [H,W,1] is
+        detached.  The values equal get_outputs' bit for bit.  After backward(), `last_xys_grad` [N,2] holds dL/d xys per Gaussian."""
+        cfg = self.config
+        if cfg.rasterize_mode not in ("classic", "antialiased"):
+            raise ValueError(f"Unknown rasterize_mode: {cfg.rasterize_mode}")
+        gp = self.gauss_params
+        dev = gp["means"].device
+        bg = torch.ones(3) if cfg.background_color == "white" else torch.zeros(3)
+        frame = {"model": self, "camera": camera, "cam": camera_struct(camera), "aa": int(cfg.rasterize_mode == "antialiased"),
+                 "deg": min(self.step // cfg.sh_degree_interval, cfg.sh_degree) if cfg.sh_degree > 0 else -1,
+                 "bg4": (C.c_float * 4)(float(bg[0]), float(bg[1]), float(bg[2]), float(cfg.background_thermal))}
+        self.last_xys_grad = None
+        rgbt, alpha, depth = _SplatRender.apply(frame, *(gp[k] for k in _PARAM_NAMES))
+        background = bg.to(dev)
+        if self.last_num_intersections == 0:  # the background as get_outputs returns it (no clamp)
+            return {"rgb": rgbt[..., :3], "thermal": rgbt[..., 3:], "depth": depth, "accumulation": alpha, "background": background}
+        return {"rgb": torch.clamp(rgbt[..., :3], max=1.0), "thermal": torch.clamp(rgbt[..., 3:], max=1.0), "depth": depth, "accumulation": alpha,
+                "background": background}
