@@ -692,6 +692,53 @@ TN_API int tn_splat_project_backward(const TnSplatCamera* camera, const float* m
                               float* v_log_scales, float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest,
                               float* v_thermal_dc, float* v_thermal_rest, tn_stream_t stream);
 
+
+/* ---- N4 refinement: splatfacto's densification, culling and statistics (SplatfactoModel.after_train / refinement_after,
+ * nerfstudio/models/splatfacto.py:346-498).  No float atomics: the results are bit-reproducible.
+ * The thresholds of SplatfactoModelConfig (splatfacto.py:103-172) and what the decisions read besides them.  The step rules are the
+ * reference's: densify iff step < stop_split_at and step % (reset_alpha_every * refine_every) > num_train_data + refine_every; otherwise cull
+ * only iff step >= stop_split_at and continue_cull_post_densification; huge-Gaussian culls iff step > refine_every * reset_alpha_every;
+ * screen-size splits and culls iff step < stop_screen_size_at. */
+typedef struct TnSplatRefine {
+  float cull_alpha_thresh;
+  float cull_scale_thresh;
+  float densify_grad_thresh;
+  float densify_size_thresh;
+  float cull_screen_size;
+  float split_screen_size;
+  int32_t refine_every;
+  int32_t reset_alpha_every;
+  int32_t stop_screen_size_at;
+  int32_t stop_split_at;
+  int32_t n_split_samples;                  /* 1..16 */
+  int32_t continue_cull_post_densification;
+  int32_t num_train_data;
+  int32_t max_size;                         /* max(H, W) of the last training frame (the reference's last_size) */
+} TnSplatRefine;
+/* after_train's statistics for one training frame: xys_grad [N,2] = dL / d xys, radii [N] of that frame, max_size = its max(H, W).
+ * first != 0 (the first call after a reset): grad_norm_sum = |xys_grad|, vis_counts = 1 for every Gaussian and max_2d_size starts at 0;
+ * otherwise only visible Gaussians (radii > 0) add |xys_grad| and 1.  Visible Gaussians then take max_2d_size = max(max_2d_size, radii / max_size). */
+TN_API int tn_splat_grad_stats(const float* xys_grad, const int32_t* radii, int64_t num_gaussians, int32_t max_size, int32_t first,
+                               float* grad_norm_sum, float* vis_counts, float* max_2d_size, tn_stream_t stream);
+/* scratch of tn_splat_refine_plan / tn_splat_refine_apply (worst case: every Gaussian split and duplicated); -1 on bad sizes */
+TN_API int64_t tn_splat_refine_workspace_bytes(int64_t num_gaussians, int32_t n_split_samples);
+/* Classifies every Gaussian (split, duplicate, cull of each row it ends up in) and places every surviving output row.  counts_out (HOST,
+ * 4 entries): split Gaussians, surviving originals, surviving split children (all samples), surviving duplicates.  One device-to-host copy
+ * of the counts (a stream synchronisation).  When the step neither densifies nor culls nothing is launched and the counts are (0, N, 0, 0). */
+TN_API int tn_splat_refine_plan(const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities, const float* grad_norm_sum,
+                                const float* vis_counts, const float* max_2d_size, int64_t num_gaussians, void* workspace, int64_t workspace_bytes,
+                                int64_t* counts_out, tn_stream_t stream);
+/* Writes the refined Gaussians: rows = surviving originals, split children (sample-major, in index order), duplicates (in index order).
+ * params / exp_avg / exp_avg_sq / new_*: HOST arrays of 8 device pointers in the order means [N,3], log-scales [N,3], quats [N,4],
+ * opacities [N,1], features_dc [N,3], features_rest [N,K,3], features_dc_thermal [N,1], features_rest_thermal [N,K,1] (K = num_rest_coeffs;
+ * the two rest entries are ignored when K = 0).  A parameter's four moment pointers are all null (no Adam state) or all set.  Outputs hold
+ * counts[1] + counts[2] + counts[3] rows.  Surviving originals keep their moments, new rows get zero moments.  Split children take
+ * mean + R(q / |q|) (exp(log-scale) * noise row) and log(exp(log-scale) / 1.6); noise [counts[0] * n_split_samples, 3] is torch.randn's sample-major
+ * layout.  counts and workspace must be those of the tn_splat_refine_plan call on the same inputs. */
+TN_API int tn_splat_refine_apply(const TnSplatRefine* config, int64_t num_gaussians, int32_t num_rest_coeffs, const void* workspace,
+                                 int64_t workspace_bytes, const int64_t* counts, const float* noise, const float* const* params,
+                                 const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params, float* const* new_exp_avg,
+                                 float* const* new_exp_avg_sq, tn_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

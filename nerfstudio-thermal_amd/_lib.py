@@ -11,7 +11,7 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TN_LIB names another build of the same library (A/B timing of kernel variants); there is still no fallback if it cannot be loaded
 LIB_PATH = os.path.abspath(os.environ["TN_LIB"]) if os.environ.get("TN_LIB") else os.path.join(_HERE, "libthermal_nerf_hip.so")
-ABI_VERSION = 308  # include/thermal_nerf_hip.h as this binding was written for (tn_version() of the library must match)
+ABI_VERSION = 309  # include/thermal_nerf_hip.h as this binding was written for (tn_version() of the library must match)
 TN_MAX_LEVELS = 16
 TN_MAX_SAMPLES = 256
 TN_RENDER_SCRATCH_FLOATS = 4096
@@ -100,6 +100,13 @@ class TnSplatCamera(C.Structure):
                 ("clip_thresh", _f), ("width", _i32), ("height", _i32)]
 
 
+class TnSplatRefine(C.Structure):
+    """include/thermal_nerf_hip.h: the thresholds and step rules of one refinement (tn_splat_refine_plan / tn_splat_refine_apply)"""
+    _fields_ = [("cull_alpha_thresh", _f), ("cull_scale_thresh", _f), ("densify_grad_thresh", _f), ("densify_size_thresh", _f), ("cull_screen_size", _f),
+                ("split_screen_size", _f), ("refine_every", _i32), ("reset_alpha_every", _i32), ("stop_screen_size_at", _i32), ("stop_split_at", _i32),
+                ("n_split_samples", _i32), ("continue_cull_post_densification", _i32), ("num_train_data", _i32), ("max_size", _i32)]
+
+
 # name -> (restype, argtypes); must list every symbol include/thermal_nerf_hip.h declares
 SIGNATURES = {
     "tn_last_error": (C.c_char_p, []),
@@ -181,6 +188,10 @@ SIGNATURES = {
     "tn_splat_backward_workspace_bytes": (_i64, [_i64, _i64]),
     "tn_splat_raster_backward": (C.c_int, [_p, _i64, _p, _i64, _i64] + [_p] * 7 + [_i64] + [_p] * 5),
     "tn_splat_project_backward": (C.c_int, [_p] * 9 + [_i64, _i32, _i32, _i32] + [_p] * 14),
+    "tn_splat_grad_stats": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p]),
+    "tn_splat_refine_workspace_bytes": (_i64, [_i64, _i32]),
+    "tn_splat_refine_plan": (C.c_int, [C.POINTER(TnSplatRefine), _i32] + [_p] * 5 + [_i64, _p, _i64, _p, _p]),
+    "tn_splat_refine_apply": (C.c_int, [C.POINTER(TnSplatRefine), _i64, _i32, _p, _i64, _p, _p] + [_p] * 6 + [_p]),
 }
 
 _lib: Optional[C.CDLL] = None

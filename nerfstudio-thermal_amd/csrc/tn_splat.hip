@@ -1117,3 +1117,307 @@ extern "C" int tn_splat_project_backward(const TnSplatCamera* camera, const floa
   TN_CHECK_LAUNCH("tn_splat_project_backward");
   return TN_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ refinement
+// splatfacto's densification (SplatfactoModel.after_train / refinement_after, nerfstudio/models/splatfacto.py:346-498).  No float atomics:
+//   k_splat_grad_stats      thread = Gaussian: the per-step statistics of after_train
+//   k_refine_classify       thread = Gaussian: split / duplicate decisions and the cull decision of every row that Gaussian ends up in
+//                           (original, its split children, its duplicate) -> four 0/1 counters
+//   rocprim scan            inclusive scan of the counters (struct of 4 int32): each surviving row's place in the output
+//   k_refine_map            thread = Gaussian: output row -> (source row, kind)
+//   k_refine_gather         flat output elements of the eight parameter tensors and their Adam moments, one block = 1024 consecutive
+//                           elements of one tensor: coalesced writes, reads that walk the source rows in order
+// The arithmetic of the decisions is torch's as the reference evaluates it: full-precision expf / logf, sigmoid = 1 / (1 + exp(-x)), and a
+// division by a host scalar as a multiply by its float reciprocal (what torch's GPU division by a Python number computes).
+struct RefCnt {
+  int32_t split, orig, child, dup;  // is split / original survives / its split children survive / its duplicate survives
+};
+struct RefCntSum {
+  __host__ __device__ RefCnt operator()(const RefCnt& a, const RefCnt& b) const {
+    return RefCnt{a.split + b.split, a.orig + b.orig, a.child + b.child, a.dup + b.dup};
+  }
+};
+
+struct RefineK {  // the decisions of one refinement, derived on the host from TnSplatRefine and the step
+  float cull_alpha, cull_scale, grad_thresh, size_thresh, cull_screen, split_screen, max_size;
+  int densify, cull_big, screen;
+};
+
+struct RefineWs {
+  RefCnt* cnt;   // [N]
+  RefCnt* incl;  // [N] inclusive scan of cnt
+  int2* map;     // [(S + 2) N] output row -> (source row, code): -1 original, -2 duplicate, -3 duplicate of a split Gaussian, >= 0 split child (noise row)
+  void* tmp;
+  size_t tmp_bytes;
+};
+
+#define REFINE_MAX_SAMPLES 16
+#define REFINE_GATHER_ELEMS 1024  // per block: 256 threads x 4 elements
+
+static RefineWs refine_layout(void* base, int64_t N, int32_t S, size_t* total) {
+  RefineWs w;
+  char* p = (char*)base;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return base ? (void*)(p + o) : (void*)nullptr; };
+  const size_t n = (size_t)std::max<int64_t>(N, 1);
+  w.cnt = (RefCnt*)take(sizeof(RefCnt) * n);
+  w.incl = (RefCnt*)take(sizeof(RefCnt) * n);
+  w.map = (int2*)take(sizeof(int2) * n * (size_t)(S + 2));
+  size_t b = 0;
+  (void)rocprim::inclusive_scan(nullptr, b, (const RefCnt*)nullptr, (RefCnt*)nullptr, n, RefCntSum());
+  w.tmp_bytes = al256(b) + 256;
+  w.tmp = take(w.tmp_bytes);
+  if (total) *total = off;
+  return w;
+}
+
+extern "C" int64_t tn_splat_refine_workspace_bytes(int64_t num_gaussians, int32_t n_split_samples) {
+  if (num_gaussians < 0 || num_gaussians >= (1ll << 31) || n_split_samples < 1 || n_split_samples > REFINE_MAX_SAMPLES) return -1;
+  size_t total = 0;
+  (void)refine_layout(nullptr, num_gaussians, n_split_samples, &total);
+  return (int64_t)total;
+}
+
+__global__ void k_splat_grad_stats(const float2* __restrict__ xys_grad, const int32_t* __restrict__ radii, int64_t N, float inv_size, int first,
+                                   float* __restrict__ grad_norm_sum, float* __restrict__ vis_counts, float* __restrict__ max_2d_size) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const float2 g = xys_grad[i];
+  const float n = sqrtf(g.x * g.x + g.y * g.y);
+  const int32_t r = radii[i];
+  const bool vis = r > 0;
+  float m;
+  if (first) {  // the first call after a reset: every Gaussian, visible or not
+    grad_norm_sum[i] = n;
+    vis_counts[i] = 1.0f;
+    m = 0.0f;
+  } else {
+    if (vis) {
+      grad_norm_sum[i] = n + grad_norm_sum[i];
+      vis_counts[i] = vis_counts[i] + 1.0f;
+    }
+    m = max_2d_size[i];
+  }
+  if (vis) m = fmaxf(m, (float)r * inv_size);
+  max_2d_size[i] = m;
+}
+
+__device__ static inline float refine_shrink(float s) { return logf(expf(s) * (1.0f / 1.6f)); }  // log(exp(s) / 1.6), splatfacto.py:555-556
+
+__global__ void k_refine_classify(const float* __restrict__ log_scales, const float* __restrict__ opacities, const float* __restrict__ grad_norm_sum,
+                                  const float* __restrict__ vis_counts, const float* __restrict__ max_2d_size, int64_t N, RefineK k,
+                                  RefCnt* __restrict__ cnt) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const float s0 = log_scales[3 * i], s1 = log_scales[3 * i + 1], s2 = log_scales[3 * i + 2];
+  const float emax = fmaxf(fmaxf(expf(s0), expf(s1)), expf(s2));
+  const float m2d = max_2d_size[i];
+  bool split = false, dup = false;
+  float emax_new = emax;  // max exp(scale) of the rows this Gaussian adds (split children, duplicate): after the parent's shrink
+  if (k.densify) {
+    const float avg = ((grad_norm_sum[i] / vis_counts[i]) * 0.5f) * k.max_size;
+    const bool high = avg > k.grad_thresh;
+    split = (emax > k.size_thresh || (k.screen && m2d > k.split_screen)) && high;
+    if (split) emax_new = fmaxf(fmaxf(expf(refine_shrink(s0)), expf(refine_shrink(s1))), expf(refine_shrink(s2)));
+    dup = emax_new <= k.size_thresh && high;  // on the updated scales: a split Gaussian can be duplicated too (splatfacto.py:413)
+  }
+  const bool transparent = 1.0f / (1.0f + expf(-opacities[i])) < k.cull_alpha;
+  const bool cull_orig = transparent || split || (k.cull_big && (emax > k.cull_scale || (k.screen && m2d > k.cull_screen)));
+  const bool cull_new = transparent || (k.cull_big && (emax_new > k.cull_scale || (k.screen && 0.0f > k.cull_screen)));  // new rows: max_2d_size 0
+  cnt[i] = RefCnt{split ? 1 : 0, cull_orig ? 0 : 1, split && !cull_new ? 1 : 0, dup && !cull_new ? 1 : 0};
+}
+
+__global__ void k_refine_map(const RefCnt* __restrict__ cnt, const RefCnt* __restrict__ incl, int64_t N, int32_t S, int2* __restrict__ map) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const RefCnt c = cnt[i], in = incl[i], tot = incl[N - 1];
+  const int32_t src = (int32_t)i;
+  if (c.orig) map[in.orig - 1] = make_int2(src, -1);
+  if (c.child) {
+    const int64_t at = (int64_t)tot.orig + (in.child - 1);
+    const int32_t noise_row = in.split - 1;  // rank among ALL split Gaussians: the noise is drawn before the cull
+    for (int j = 0; j < S; ++j) map[at + (int64_t)j * tot.child] = make_int2(src, j * tot.split + noise_row);
+  }
+  if (c.dup) map[(int64_t)tot.orig + (int64_t)S * tot.child + (in.dup - 1)] = make_int2(src, c.split ? -3 : -2);
+}
+
+struct RefTensors {  // the eight parameter tensors (splat.py _PARAM_NAMES order) and their Adam moments; moments may be absent (null)
+  const float* src[8];
+  const float* src_m1[8];
+  const float* src_m2[8];
+  float* dst[8];
+  float* dst_m1[8];
+  float* dst_m2[8];
+  int32_t width[8];
+  int64_t block_begin[9];  // first block of each tensor
+};
+
+__global__ void __launch_bounds__(256) k_refine_gather(RefTensors t, const int2* __restrict__ map, int64_t num_out, const float* __restrict__ noise,
+                                                       int64_t noise_rows, const float* __restrict__ means, const float* __restrict__ log_scales,
+                                                       const float* __restrict__ quats, int64_t N) {
+  int k = 0;
+#pragma unroll
+  for (int j = 1; j < 8; ++j) k += (int64_t)blockIdx.x >= t.block_begin[j] ? 1 : 0;  // block-uniform
+  const int w = t.width[k];
+  const float* __restrict__ src = t.src[k];
+  const float* __restrict__ m1 = t.src_m1[k];
+  const float* __restrict__ m2 = t.src_m2[k];
+  float* __restrict__ dst = t.dst[k];
+  const int64_t count = num_out * w;
+  const int64_t base = ((int64_t)blockIdx.x - t.block_begin[k]) * REFINE_GATHER_ELEMS;
+#pragma unroll
+  for (int u = 0; u < REFINE_GATHER_ELEMS / 256; ++u) {
+    const int64_t e = base + u * 256 + threadIdx.x;
+    if (e >= count) break;
+    const int64_t row = e / w;
+    const int c = (int)(e - row * w);
+    const int2 m = map[row];
+    float v = 0.f, a = 0.f, b = 0.f;
+    if ((uint64_t)m.x < (uint64_t)N) {
+      const int64_t s = (int64_t)m.x * w + c;
+      v = src[s];
+      if (m.y == -1 && m1) {
+        a = m1[s];
+        b = m2[s];
+      }
+      if (k == 1 && m.y != -1 && m.y != -2) v = refine_shrink(v);  // split children and duplicates of split Gaussians
+      if (k == 0 && m.y >= 0) {
+        // child mean: mean + R(q / |q|) (exp(parent's log-scale) * z), splatfacto.py:541-549 (gsplat's quat_to_rotmat, w x y z)
+        if (m.y < noise_rows) {
+          const int64_t g = m.x;
+          float qw = quats[4 * g], qx = quats[4 * g + 1], qy = quats[4 * g + 2], qz = quats[4 * g + 3];
+          const float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
+          qw /= qn, qx /= qn, qy /= qn, qz /= qn;
+          float r0, r1, r2;
+          if (c == 0) {
+            r0 = 1.f - 2.f * (qy * qy + qz * qz), r1 = 2.f * (qx * qy - qw * qz), r2 = 2.f * (qx * qz + qw * qy);
+          } else if (c == 1) {
+            r0 = 2.f * (qx * qy + qw * qz), r1 = 1.f - 2.f * (qx * qx + qz * qz), r2 = 2.f * (qy * qz - qw * qx);
+          } else {
+            r0 = 2.f * (qx * qz - qw * qy), r1 = 2.f * (qy * qz + qw * qx), r2 = 1.f - 2.f * (qx * qx + qy * qy);
+          }
+          const float* z = noise + 3 * (int64_t)m.y;
+          const float* ls = log_scales + 3 * g;
+          v = (r0 * (expf(ls[0]) * z[0]) + r1 * (expf(ls[1]) * z[1]) + r2 * (expf(ls[2]) * z[2])) + means[3 * g + c];
+        }
+      }
+    }
+    dst[e] = v;
+    if (m1) {
+      t.dst_m1[k][e] = a;
+      t.dst_m2[k][e] = b;
+    }
+  }
+}
+
+static int refine_k(const TnSplatRefine* cfg, int32_t step, const char* who, RefineK* k, int* cull) {
+  TN_REQUIRE(cfg != nullptr, "%s: null config", who);
+  TN_REQUIRE(cfg->refine_every >= 1 && cfg->reset_alpha_every >= 1, "%s: refine_every %d / reset_alpha_every %d must be >= 1", who, cfg->refine_every,
+             cfg->reset_alpha_every);
+  TN_REQUIRE(cfg->n_split_samples >= 1 && cfg->n_split_samples <= REFINE_MAX_SAMPLES, "%s: n_split_samples %d outside [1, %d]", who, cfg->n_split_samples,
+             REFINE_MAX_SAMPLES);
+  TN_REQUIRE(cfg->max_size >= 1, "%s: max_size %d (the training frame's max(H, W)) must be >= 1", who, cfg->max_size);
+  TN_REQUIRE(step >= 0, "%s: negative step", who);
+  const int64_t R = (int64_t)cfg->reset_alpha_every * cfg->refine_every;
+  k->densify = step < cfg->stop_split_at && (int64_t)step % R > (int64_t)cfg->num_train_data + cfg->refine_every;
+  *cull = k->densify || (step >= cfg->stop_split_at && cfg->continue_cull_post_densification);
+  k->cull_big = (int64_t)step > R;
+  k->screen = step < cfg->stop_screen_size_at;
+  k->cull_alpha = cfg->cull_alpha_thresh, k->cull_scale = cfg->cull_scale_thresh, k->grad_thresh = cfg->densify_grad_thresh;
+  k->size_thresh = cfg->densify_size_thresh, k->cull_screen = cfg->cull_screen_size, k->split_screen = cfg->split_screen_size;
+  k->max_size = (float)cfg->max_size;
+  return TN_OK;
+}
+
+extern "C" int tn_splat_grad_stats(const float* xys_grad, const int32_t* radii, int64_t num_gaussians, int32_t max_size, int32_t first,
+                                   float* grad_norm_sum, float* vis_counts, float* max_2d_size, tn_stream_t stream) {
+  TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31), "tn_splat_grad_stats: bad Gaussian count");
+  TN_REQUIRE(max_size >= 1, "tn_splat_grad_stats: max_size %d (the frame's max(H, W)) must be >= 1", max_size);
+  if (num_gaussians == 0) return TN_OK;
+  TN_REQUIRE(xys_grad && radii && grad_norm_sum && vis_counts && max_2d_size, "tn_splat_grad_stats: null pointer");
+  hipLaunchKernelGGL(k_splat_grad_stats, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, tn_s(stream), (const float2*)xys_grad, radii,
+                     num_gaussians, 1.0f / (float)max_size, first ? 1 : 0, grad_norm_sum, vis_counts, max_2d_size);
+  TN_CHECK_LAUNCH("tn_splat_grad_stats");
+  return TN_OK;
+}
+
+extern "C" int tn_splat_refine_plan(const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities,
+                                    const float* grad_norm_sum, const float* vis_counts, const float* max_2d_size, int64_t num_gaussians,
+                                    void* workspace, int64_t workspace_bytes, int64_t* counts_out, tn_stream_t stream) {
+  RefineK k;
+  int cull = 0;
+  int rc = refine_k(config, step, "tn_splat_refine_plan", &k, &cull);
+  if (rc) return rc;
+  TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31), "tn_splat_refine_plan: bad Gaussian count");
+  TN_REQUIRE(counts_out != nullptr, "tn_splat_refine_plan: null output");
+  const int64_t N = num_gaussians;
+  counts_out[0] = 0, counts_out[1] = N, counts_out[2] = 0, counts_out[3] = 0;
+  if (N == 0 || !cull) return TN_OK;  // nothing to refine: every Gaussian stays where it is
+  TN_REQUIRE(log_scales && opacities && grad_norm_sum && vis_counts && max_2d_size && workspace, "tn_splat_refine_plan: null pointer");
+  const int64_t need = tn_splat_refine_workspace_bytes(N, config->n_split_samples);
+  TN_REQUIRE(workspace_bytes >= need, "tn_splat_refine_plan: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
+  RefineWs ws = refine_layout(workspace, N, config->n_split_samples, nullptr);
+  hipStream_t st = tn_s(stream);
+  hipLaunchKernelGGL(k_refine_classify, dim3((unsigned)tn_cdiv(N, 256)), dim3(256), 0, st, log_scales, opacities, grad_norm_sum, vis_counts, max_2d_size, N,
+                     k, ws.cnt);
+  TN_CHECK_LAUNCH("tn_splat_refine_plan(classify)");
+  size_t tb = ws.tmp_bytes;
+  if (rocprim::inclusive_scan(ws.tmp, tb, (const RefCnt*)ws.cnt, ws.incl, (size_t)N, RefCntSum(), st) != hipSuccess) {
+    tn_set_error("tn_splat_refine_plan: scan failed");
+    return TN_ELAUNCH;
+  }
+  RefCnt tot;
+  if (hipMemcpyAsync(&tot, ws.incl + (N - 1), sizeof(RefCnt), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    tn_set_error("tn_splat_refine_plan: read-back of the counts failed");
+    return TN_ELAUNCH;
+  }
+  counts_out[0] = tot.split, counts_out[1] = tot.orig, counts_out[2] = (int64_t)tot.child * config->n_split_samples, counts_out[3] = tot.dup;
+  return TN_OK;
+}
+
+extern "C" int tn_splat_refine_apply(const TnSplatRefine* config, int64_t num_gaussians, int32_t num_rest_coeffs, const void* workspace,
+                                     int64_t workspace_bytes, const int64_t* counts, const float* noise, const float* const* params,
+                                     const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params, float* const* new_exp_avg,
+                                     float* const* new_exp_avg_sq, tn_stream_t stream) {
+  TN_REQUIRE(config != nullptr && counts != nullptr, "tn_splat_refine_apply: null pointer");
+  const int32_t S = config->n_split_samples;
+  TN_REQUIRE(S >= 1 && S <= REFINE_MAX_SAMPLES, "tn_splat_refine_apply: n_split_samples %d outside [1, %d]", S, REFINE_MAX_SAMPLES);
+  TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31), "tn_splat_refine_apply: bad Gaussian count");
+  TN_REQUIRE(num_rest_coeffs >= 0 && num_rest_coeffs <= 15, "tn_splat_refine_apply: %d higher-order coefficients", num_rest_coeffs);
+  const int64_t N = num_gaussians;
+  TN_REQUIRE(counts[0] >= 0 && counts[0] <= N && counts[1] >= 0 && counts[1] <= N && counts[2] >= 0 && counts[2] <= S * counts[0] &&
+                 counts[2] % S == 0 && counts[3] >= 0 && counts[3] <= N,
+             "tn_splat_refine_apply: counts (%lld, %lld, %lld, %lld) are not a plan of %lld Gaussians", (long long)counts[0], (long long)counts[1],
+             (long long)counts[2], (long long)counts[3], (long long)N);
+  const int64_t num_out = counts[1] + counts[2] + counts[3];
+  if (num_out == 0) return TN_OK;  // everything culled (N == 0 included): nothing to write
+  TN_REQUIRE(params && exp_avg && exp_avg_sq && new_params && new_exp_avg && new_exp_avg_sq && workspace, "tn_splat_refine_apply: null pointer");
+  TN_REQUIRE(counts[2] == 0 || noise != nullptr, "tn_splat_refine_apply: null noise for %lld split children", (long long)counts[2]);
+  const int64_t need = tn_splat_refine_workspace_bytes(N, S);
+  TN_REQUIRE(workspace_bytes >= need, "tn_splat_refine_apply: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
+  const int32_t widths[8] = {3, 3, 4, 1, 3, 3 * num_rest_coeffs, 1, num_rest_coeffs};
+  RefTensors t;
+  int64_t blocks = 0;
+  for (int j = 0; j < 8; ++j) {
+    const bool on = widths[j] > 0;
+    TN_REQUIRE(!on || (params[j] && new_params[j]), "tn_splat_refine_apply: null parameter %d", j);
+    TN_REQUIRE((exp_avg[j] == nullptr) == (exp_avg_sq[j] == nullptr) && (exp_avg[j] == nullptr) == (new_exp_avg[j] == nullptr) &&
+                   (exp_avg[j] == nullptr) == (new_exp_avg_sq[j] == nullptr),
+               "tn_splat_refine_apply: moments of parameter %d are partly null", j);
+    t.src[j] = params[j], t.src_m1[j] = on ? exp_avg[j] : nullptr, t.src_m2[j] = on ? exp_avg_sq[j] : nullptr;
+    t.dst[j] = new_params[j], t.dst_m1[j] = on ? new_exp_avg[j] : nullptr, t.dst_m2[j] = on ? new_exp_avg_sq[j] : nullptr;
+    t.width[j] = std::max(widths[j], 1);
+    t.block_begin[j] = blocks;
+    blocks += on ? tn_cdiv(num_out * widths[j], REFINE_GATHER_ELEMS) : 0;
+  }
+  t.block_begin[8] = blocks;
+  TN_REQUIRE(blocks < (1ll << 31), "tn_splat_refine_apply: %lld output rows are too many", (long long)num_out);
+  RefineWs ws = refine_layout(const_cast<void*>(workspace), N, S, nullptr);
+  hipStream_t st = tn_s(stream);
+  hipLaunchKernelGGL(k_refine_map, dim3((unsigned)tn_cdiv(N, 256)), dim3(256), 0, st, ws.cnt, ws.incl, N, S, ws.map);
+  TN_CHECK_LAUNCH("tn_splat_refine_apply(map)");
+  hipLaunchKernelGGL(k_refine_gather, dim3((unsigned)blocks), dim3(256), 0, st, t, ws.map, num_out, noise, (int64_t)counts[0] * S, params[0], params[1],
+                     params[2], N);
+  TN_CHECK_LAUNCH("tn_splat_refine_apply(gather)");
+  return TN_OK;
+}

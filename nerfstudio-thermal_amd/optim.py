@@ -203,6 +203,54 @@ class HipFusedAdam(torch.optim.Optimizer):
                 self._steps[id(p)] = int(float(st["step"]))
                 st["step"] = torch.tensor(float(self._steps[id(p)]))
 
+class HipAdam(torch.optim.Adam):
+    """torch.optim.Adam whose step() is one `tn_adam_step` launch per parameter that has a gradient, for parameters that do not live in a
+    ParamArena: the Gaussian-splat groups, whose tensors refinement replaces (splatfacto.py:292-344).  The state is torch.optim.Adam's
+    (`step` a CPU float tensor, `exp_avg`, `exp_avg_sq`), so state_dict() / load_state_dict() and the refinement's moment surgery work as
+    they do on torch.optim.Adam."""
+
+    def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, **kwargs):
+        if weight_decay != 0.0 or kwargs.get("amsgrad", False) or kwargs.get("maximize", False):
+            raise NotImplementedError("HipAdam implements plain Adam (weight_decay = 0, no amsgrad): what the splatfacto optimisers use")
+        super().__init__(params, lr=lr, betas=betas, eps=eps)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            beta1, beta2 = group["betas"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if len(st) == 0:
+                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                st["step"] += 1
+                if p.numel():
+                    ops.adam_step(p.data, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"], int(st["step"].item()), group["lr"], beta1, beta2,
+                                  group["eps"])
+        return loss
+
+
+# splatfacto's optimisers (configs/method_configs.py:655-703) in the (lr, lr_final, max_steps) format Optimizers reads; the thermal SH groups
+# take the rates of their RGB counterparts.  The constant groups run a schedule from lr to lr (the same rate to within a double's last bit).
+SPLAT_OPTIMIZERS = {
+    "xyz": (1.6e-4, 1.6e-6, 30000),
+    "features_dc": (0.0025, 0.0025, 30000),
+    "features_rest": (0.0025 / 20, 0.0025 / 20, 30000),
+    "opacity": (0.05, 0.05, 30000),
+    "scaling": (0.005, 0.005, 30000),
+    "rotation": (0.001, 0.001, 30000),
+    "features_dc_thermal": (0.0025, 0.0025, 30000),
+    "features_rest_thermal": (0.0025 / 20, 0.0025 / 20, 30000),
+}
+
+
 def _cut_launches(work: list, max_ranges: int = 8) -> List[list]:
     """work: ranges in optimiser order, each (flag, arena, lo, hi, step, lr, (beta1, beta2, eps)).  Launches of <= max_ranges consecutive ranges
     over one arena with one (beta1, beta2, eps), cut at optimiser boundaries: an optimiser is split only when it alone exceeds a launch, so

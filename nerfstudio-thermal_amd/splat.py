@@ -8,15 +8,18 @@ spherical_harmonics, rasterize_gaussians x2) run as tn_splat_project / tn_splat_
 `get_outputs` is the eval render.  `get_train_outputs` is the same render as a differentiable function of every `gauss_params` tensor: its
 backward (tn_splat_raster_backward / tn_splat_project_backward) is the exact, bit-reproducible derivative of the forward this file computes,
 and it leaves dL/d xys per Gaussian in `last_xys_grad` (what splatfacto's densification reads as `self.xys.grad`, splatfacto.py:355).
-Depth is returned detached.  Densification, culling, opacity reset, the SSIM loss and camera-pose gradients are not built.  Parity is unpinned
-(gsplat is a third-party package outside the reference tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
+Depth is returned detached.  Training follows splatfacto's refinement (splatfacto.py:346-498): `after_train` accumulates the gradient
+statistics (tn_splat_grad_stats), `refinement_after` splits, duplicates and culls the Gaussians (tn_splat_refine_plan / tn_splat_refine_apply)
+and carries every optimiser's parameter and Adam moments along, and resets the opacities now and then.  The SSIM loss, random backgrounds,
+the resolution schedule and camera-pose gradients are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
+tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor, nn
@@ -29,7 +32,7 @@ BLOCK_WIDTH = 16  # splatfacto.py:738
 
 @dataclass
 class ThermalSplatfactoModelConfig:
-    """The fields of SplatfactoModelConfig (splatfacto.py:103-172) that the forward render reads."""
+    """The fields of SplatfactoModelConfig (splatfacto.py:103-172) that the render and the refinement read, with the reference's defaults."""
 
     sh_degree: int = 3
     sh_degree_interval: int = 1000
@@ -38,6 +41,20 @@ class ThermalSplatfactoModelConfig:
     background_thermal: float = 0.0
     num_random: int = 50000
     random_scale: float = 10.0
+    # refinement (splatfacto.py:108-148)
+    warmup_length: int = 500
+    refine_every: int = 100
+    cull_alpha_thresh: float = 0.1
+    cull_scale_thresh: float = 0.5
+    continue_cull_post_densification: bool = True
+    reset_alpha_every: int = 30
+    densify_grad_thresh: float = 0.0002
+    densify_size_thresh: float = 0.01
+    n_split_samples: int = 2
+    cull_screen_size: float = 0.15
+    split_screen_size: float = 0.05
+    stop_screen_size_at: int = 4000
+    stop_split_at: int = 15000
 
 
 @dataclass
@@ -100,6 +117,9 @@ def _ptr(t: Optional[Tensor], dtype, name: str):
 
 
 _PARAM_NAMES = ("means", "scales", "quats", "opacities", "features_dc", "features_rest", "features_dc_thermal", "features_rest_thermal")
+# optimiser group -> gauss_params entry (splatfacto.py:620-628, plus the thermal SH coefficients)
+GROUP_PARAMS = {"xyz": "means", "features_dc": "features_dc", "features_rest": "features_rest", "opacity": "opacities", "scaling": "scales",
+                "rotation": "quats", "features_dc_thermal": "features_dc_thermal", "features_rest_thermal": "features_rest_thermal"}
 
 
 class _SplatRender(torch.autograd.Function):
@@ -126,7 +146,7 @@ class _SplatRender(torch.autograd.Function):
         box = torch.empty((N, 4), dtype=i32, device=dev)
         cap = max(model._train_cap, 1 << 16)
         total = C.c_int64(0)
-        for attempt in range(2):
+        for attempt in range(2 if N > 0 else 0):  # (no Gaussians: nothing to project, the frame is the background)
             # a workspace of this frame's own: the backward reads it after other frames may have been rendered
             need = int(lib.tn_splat_workspace_bytes(N, cap, tiles))
             if need < 0:
@@ -151,6 +171,8 @@ class _SplatRender(torch.autograd.Function):
         model._train_cap = cap
         model.last_projection = {"xys": xys, "depths": depths, "radii": radii, "conics": conics, "compensation": comp, "num_tiles_hit": hit, "tile_box": box}
         model.last_num_intersections = int(total.value)
+        # what after_train reads of the training frame (the reference's self.radii / self.last_size); eval renders leave these alone
+        model.last_radii, model.last_size = radii, (H, W)
         ctx.frame, ctx.empty = frame, total.value == 0
         if total.value == 0:  # nothing on screen: the background, and zero gradients
             rgbt = torch.tensor(list(bg4), device=dev).repeat(H, W, 1)
@@ -218,9 +240,11 @@ class ThermalSplatfactoModel(nn.Module):
     """RGB + thermal Gaussians: eval render (`get_outputs`) and differentiable training render (`get_train_outputs`).  `gauss_params` keeps the
     reference's names (splatfacto.py:226-235)."""
 
-    def __init__(self, config: Optional[ThermalSplatfactoModelConfig] = None, num_points: Optional[int] = None, device="cuda", seed: int = 0):
+    def __init__(self, config: Optional[ThermalSplatfactoModelConfig] = None, num_points: Optional[int] = None, device="cuda", seed: int = 0,
+                 num_train_data: int = 0):
         super().__init__()
         self.config = config or ThermalSplatfactoModelConfig()
+        self.num_train_data = num_train_data
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("ThermalSplatfactoModel needs a HIP device: there is no CPU fallback on this path")
@@ -247,6 +271,14 @@ class ThermalSplatfactoModel(nn.Module):
         self.last_xys_grad: Optional[Tensor] = None
         self.last_projection: Dict[str, Tensor] = {}
         self.last_num_intersections = 0
+        self.last_radii: Optional[Tensor] = None  # radii [N] and (H, W) of the last TRAINING frame
+        self.last_size: Optional[Tuple[int, int]] = None
+        # refinement statistics (after_train); None = the next after_train is the first after a reset
+        self.xys_grad_norm: Optional[Tensor] = None
+        self.vis_counts: Optional[Tensor] = None
+        self.max_2Dsize: Optional[Tensor] = None
+        self.noise_generator = torch.Generator(device=dev)  # the split noise (splatfacto.py:541)
+        self.noise_generator.manual_seed(seed)
 
     # the reference's accessors
     @property
@@ -283,6 +315,10 @@ class ThermalSplatfactoModel(nn.Module):
             raise ValueError(f"Unknown rasterize_mode: {cfg.rasterize_mode}")
         aa = int(cfg.rasterize_mode == "antialiased")
         bg = torch.ones(3) if cfg.background_color == "white" else torch.zeros(3)
+        if N == 0:  # every Gaussian culled: the background (splatfacto.py:759-764)
+            background = bg.to(dev)
+            return {"rgb": background.repeat(H, W, 1), "thermal": torch.full((H, W, 1), cfg.background_thermal, device=dev),
+                    "depth": torch.full((H, W, 1), 10.0, device=dev), "accumulation": torch.zeros((H, W, 1), device=dev), "background": background}
         cam = camera_struct(camera)
         tiles = ((W + BLOCK_WIDTH - 1) // BLOCK_WIDTH) * ((H + BLOCK_WIDTH - 1) // BLOCK_WIDTH)
         K = gp["features_rest"].shape[1]
@@ -351,3 +387,155 @@ class ThermalSplatfactoModel(nn.Module):
             return {"rgb": rgbt[..., :3], "thermal": rgbt[..., 3:], "depth": depth, "accumulation": alpha, "background": background}
         return {"rgb": torch.clamp(rgbt[..., :3], max=1.0), "thermal": torch.clamp(rgbt[..., 3:], max=1.0), "depth": depth, "accumulation": alpha,
                 "background": background}
+
+    # ------------------------------------------------------------------------------------------------ training (splatfacto.py:258-628)
+    def step_cb(self, step: int) -> None:
+        self.step = step
+
+    def get_gaussian_param_groups(self) -> Dict[str, List[nn.Parameter]]:
+        """splatfacto.py:620-628: the reference's six groups plus the thermal SH coefficients."""
+        return {g: [self.gauss_params[k]] for g, k in GROUP_PARAMS.items()}
+
+    def get_param_groups(self) -> Dict[str, List[nn.Parameter]]:
+        return self.get_gaussian_param_groups()
+
+    def get_training_callbacks(self, training_callback_attributes) -> List["TrainingCallback"]:
+        """splatfacto.py:595-617.  `training_callback_attributes` carries the `Optimizers` as `.optimizers` (or is the `Optimizers`); the
+        refinement callback reaches them through a closure."""
+        from .model import TrainingCallback, TrainingCallbackLocation
+
+        opts = training_callback_attributes
+        if not isinstance(getattr(opts, "optimizers", None), dict):
+            opts = opts.optimizers
+        after = [TrainingCallbackLocation.AFTER_TRAIN_ITERATION]
+        return [TrainingCallback([TrainingCallbackLocation.BEFORE_TRAIN_ITERATION], self.step_cb), TrainingCallback(after, self.after_train),
+                TrainingCallback(after, lambda step: self.refinement_after(opts, step), update_every_num_iters=self.config.refine_every)]
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kwargs):
+        """splatfacto.py:258-271: resize the Gaussians to the checkpoint's count, then load (and, as the reference, step = 30000: every SH degree on)."""
+        self.step = 30000
+        n = state_dict["gauss_params.means"].shape[0]
+        dev = self.means.device
+        self.gauss_params = nn.ParameterDict({k: nn.Parameter(torch.zeros((n,) + tuple(self.gauss_params[k].shape[1:]), device=dev)) for k in _PARAM_NAMES})
+        self.xys_grad_norm = self.vis_counts = self.max_2Dsize = None
+        return super().load_state_dict(state_dict, strict=strict, **kwargs)
+
+    def _refine_struct(self) -> _lib.TnSplatRefine:
+        cfg = self.config
+        r = _lib.TnSplatRefine()
+        r.cull_alpha_thresh, r.cull_scale_thresh = cfg.cull_alpha_thresh, cfg.cull_scale_thresh
+        r.densify_grad_thresh, r.densify_size_thresh = cfg.densify_grad_thresh, cfg.densify_size_thresh
+        r.cull_screen_size, r.split_screen_size = cfg.cull_screen_size, cfg.split_screen_size
+        r.refine_every, r.reset_alpha_every = cfg.refine_every, cfg.reset_alpha_every
+        r.stop_screen_size_at, r.stop_split_at = cfg.stop_screen_size_at, cfg.stop_split_at
+        r.n_split_samples, r.continue_cull_post_densification = cfg.n_split_samples, int(cfg.continue_cull_post_densification)
+        r.num_train_data = self.num_train_data
+        r.max_size = max(self.last_size) if self.last_size else 1
+        return r
+
+    @torch.no_grad()
+    def after_train(self, step: int) -> None:
+        """splatfacto.py:346-372 on the last training frame (its radii, size and, after backward(), last_xys_grad): tn_splat_grad_stats."""
+        assert step == self.step
+        if self.step >= self.config.stop_split_at:
+            return
+        if self.last_xys_grad is None or self.last_radii is None or self.last_size is None:
+            raise RuntimeError("after_train needs a get_train_outputs() frame and its backward()")
+        N, dev = self.num_points, self.means.device
+        if self.last_radii.shape[0] != N or self.last_xys_grad.shape[0] != N:
+            raise RuntimeError("after_train: the Gaussians changed since the last training frame")
+        first = self.xys_grad_norm is None
+        if first:
+            self.xys_grad_norm = torch.empty(N, device=dev)
+            self.vis_counts = torch.empty(N, device=dev)
+            self.max_2Dsize = torch.empty(N, device=dev)
+        f32 = torch.float32
+        _lib.check(_lib.load().tn_splat_grad_stats(_ptr(self.last_xys_grad.contiguous(), f32, "xys_grad"), _ptr(self.last_radii, torch.int32, "radii"), N,
+                                                   max(self.last_size), int(first), _ptr(self.xys_grad_norm, f32, "grad_norm_sum"),
+                                                   _ptr(self.vis_counts, f32, "vis_counts"), _ptr(self.max_2Dsize, f32, "max_2d_size"), _stream()),
+                   "tn_splat_grad_stats")
+
+    @torch.no_grad()
+    def refinement_after(self, optimizers, step: int) -> None:
+        """splatfacto.py:381-498: densify (split + duplicate) and cull, or cull only after stop_split_at; then the opacity reset and a reset of
+        the statistics.  `optimizers`: an `Optimizers` (or a dict group -> torch.optim optimiser, or None); every optimiser's parameter is
+        replaced by the model's new one, surviving Gaussians keep their Adam moments, new ones start at zero, step counts are kept."""
+        assert step == self.step
+        cfg = self.config
+        if self.step <= cfg.warmup_length:
+            return
+        opts = getattr(optimizers, "optimizers", optimizers) or {}
+        reset_interval = cfg.reset_alpha_every * cfg.refine_every
+        densify = self.step < cfg.stop_split_at and self.step % reset_interval > self.num_train_data + cfg.refine_every
+        if densify or (self.step >= cfg.stop_split_at and cfg.continue_cull_post_densification):
+            if densify and self.xys_grad_norm is None:
+                raise RuntimeError("refinement_after: densification needs after_train statistics")
+            self._refine(optimizers, opts, densify)
+        if self.step < cfg.stop_split_at and self.step % reset_interval == cfg.refine_every:
+            op = self.gauss_params["opacities"]
+            reset_value = cfg.cull_alpha_thresh * 2.0
+            op.data = torch.clamp(op.data, max=torch.logit(torch.tensor(reset_value, device=op.device)).item())
+            o = opts.get("opacity")
+            if o is not None and o.state.get(op):
+                st = o.state[op]
+                st["exp_avg"] = torch.zeros_like(st["exp_avg"])
+                st["exp_avg_sq"] = torch.zeros_like(st["exp_avg_sq"])
+        self.xys_grad_norm = self.vis_counts = self.max_2Dsize = None
+
+    def _refine(self, optimizers, opts, densify: bool) -> None:
+        """One tn_splat_refine_plan (one host sync: the counts) + one tn_splat_refine_apply into freshly allocated tensors."""
+        lib = _lib.load()
+        gp = self.gauss_params
+        N, dev, f32 = self.num_points, self.means.device, torch.float32
+        S, K = self.config.n_split_samples, gp["features_rest"].shape[1]
+        rs = self._refine_struct()
+        need = int(lib.tn_splat_refine_workspace_bytes(N, S))
+        if need < 0:
+            raise RuntimeError("tn_splat_refine_workspace_bytes: bad sizes")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        stats = [self.xys_grad_norm, self.vis_counts, self.max_2Dsize]
+        if stats[0] is None:  # cull only, straight after a reset: no screen sizes recorded
+            stats = [torch.ones(N, device=dev), torch.ones(N, device=dev), torch.zeros(N, device=dev)]
+        counts = (C.c_int64 * 4)()
+        _lib.check(lib.tn_splat_refine_plan(C.byref(rs), int(self.step), _ptr(gp["scales"], f32, "scales"), _ptr(gp["opacities"].reshape(-1), f32, "opacities"),
+                                            _ptr(stats[0], f32, "grad_norm_sum"), _ptr(stats[1], f32, "vis_counts"), _ptr(stats[2], f32, "max_2d_size"), N,
+                                            C.c_void_p(ws.data_ptr()), need, counts, _stream()), "tn_splat_refine_plan")
+        n_split, n_orig, n_child, n_dup = (int(c) for c in counts)
+        # the reference's noise: randn((n_split_samples * n_split, 3)), sample-major (splatfacto.py:541)
+        noise = torch.randn((S * n_split, 3), device=dev, generator=self.noise_generator) if densify else None
+        self.last_refine_counts = (n_split, n_orig, n_child, n_dup)
+        if n_orig == N and n_child == 0 and n_dup == 0:
+            return  # nothing split, duplicated or culled: every tensor stays as it is
+        M = n_orig + n_child + n_dup
+        old = {k: gp[k] for k in _PARAM_NAMES}
+        group_of = {v: g for g, v in GROUP_PARAMS.items()}
+        moments = {}
+        for k in _PARAM_NAMES:
+            o = opts.get(group_of[k])
+            st = o.state.get(old[k]) if o is not None else None
+            if st and "exp_avg" in st:
+                moments[k] = (st["exp_avg"].contiguous(), st["exp_avg_sq"].contiguous())
+        new = {k: torch.empty((M,) + tuple(old[k].shape[1:]), device=dev) for k in _PARAM_NAMES}
+        new_m = {k: (torch.empty_like(new[k]), torch.empty_like(new[k])) for k in moments}
+        arr = lambda ts: (C.c_void_p * 8)(*[t.data_ptr() if t is not None and t.numel() else None for t in ts])  # noqa: E731
+        _lib.check(lib.tn_splat_refine_apply(C.byref(rs), N, K, C.c_void_p(ws.data_ptr()), need, counts,
+                                             _ptr(noise, f32, "noise") if noise is not None and noise.numel() else None,
+                                             arr([old[k].detach() for k in _PARAM_NAMES]), arr([moments[k][0] if k in moments else None for k in _PARAM_NAMES]),
+                                             arr([moments[k][1] if k in moments else None for k in _PARAM_NAMES]), arr([new[k] for k in _PARAM_NAMES]),
+                                             arr([new_m[k][0] if k in new_m else None for k in _PARAM_NAMES]),
+                                             arr([new_m[k][1] if k in new_m else None for k in _PARAM_NAMES]), _stream()), "tn_splat_refine_apply")
+        self.gauss_params = nn.ParameterDict({k: nn.Parameter(new[k]) for k in _PARAM_NAMES})
+        for k in _PARAM_NAMES:  # dup_in_optim / remove_from_optim (splatfacto.py:292-344)
+            g = group_of[k]
+            o = opts.get(g)
+            if o is None:
+                continue
+            st = o.state.pop(old[k], None)
+            p = self.gauss_params[k]
+            o.param_groups[0]["params"] = [p]
+            if st is not None:
+                if k in new_m:
+                    st["exp_avg"], st["exp_avg_sq"] = new_m[k]
+                o.state[p] = st
+            if isinstance(getattr(optimizers, "parameters", None), dict) and g in optimizers.parameters:
+                optimizers.parameters[g] = [p]
