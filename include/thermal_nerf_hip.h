@@ -739,6 +739,21 @@ TN_API int tn_splat_refine_apply(const TnSplatRefine* config, int64_t num_gaussi
                                  int64_t workspace_bytes, const int64_t* counts, const float* noise, const float* const* params,
                                  const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params, float* const* new_exp_avg,
                                  float* const* new_exp_avg_sq, tn_stream_t stream);
+/* ---- N4 training loss: splatfacto's (1 - ssim_lambda) * L1 + ssim_lambda * (1 - SSIM) (nerfstudio/models/splatfacto.py:863-903), SSIM as
+ * pytorch_msssim computes it: an 11-tap Gaussian window (sigma 1.5) applied separably as a VALID correlation, C1 = 0.01^2, C2 = 0.03^2 (data
+ * range 1), mean over the (H-10) x (W-10) valid pixels and the channels.  L1 = mean |pred - gt| over all H W C values.  Deterministic: no
+ * float atomics, the same inputs give bit-identical loss and gradient.  No host synchronisation.
+ *
+ * scratch of tn_image_loss: per-block partial sums and the SSIM's three per-pixel derivative maps; -1 on bad sizes (H or W < 11, channels
+ * outside 1..4) */
+TN_API int64_t tn_image_loss_workspace_bytes(int32_t height, int32_t width, int32_t channels);
+/* pred / gt: [H,W,*] fp32 images whose pixels are pred_pixel_stride / gt_pixel_stride floats apart (rows W strides apart; channels 0..C-1 of
+ * each pixel are read, so an [H,W,4] buffer serves C = 3 with stride 4).  out_loss: DEVICE [3] = weight * main loss, L1, SSIM.  out_grad:
+ * [H,W,C] contiguous = d out_loss[0] / d pred (the ground truth gets none), or NULL for the loss alone.  Refused with TN_EINVAL before any
+ * launch: null pointers, H or W < 11 or > 32768, channels outside 1..4, a pixel stride below the channel count, a short workspace. */
+TN_API int tn_image_loss(const float* pred, int64_t pred_pixel_stride, const float* gt, int64_t gt_pixel_stride, int32_t height, int32_t width,
+                         int32_t channels, float ssim_lambda, float weight, void* workspace, int64_t workspace_bytes, float* out_loss, float* out_grad,
+                         tn_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

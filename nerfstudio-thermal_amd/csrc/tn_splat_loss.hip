@@ -1,0 +1,324 @@
+// N4 training loss: splatfacto's (1 - lambda) * L1 + lambda * (1 - SSIM) of one rendered frame (nerfstudio/models/splatfacto.py:863-903), its
+// value and its gradient with respect to the prediction.  SSIM is pytorch_msssim's (ssim / _ssim / gaussian_filter, v1.x): an 11-tap Gaussian
+// window with sigma 1.5 applied separably as a VALID correlation, C1 = 0.01^2, C2 = 0.03^2, mean over the valid pixels and the channels.
+//
+// Three launches, no float atomics (bit-reproducible):
+//   k_ssim_fwd    one block per 64 x 16 tile of the VALID map: stages x and y with their 10-pixel halo in LDS, filters the five moments
+//                 (rows, then columns), writes the per-pixel SSIM's partial derivatives a = dS/d mu_x, b = dS/d G*(x^2), c = dS/d G*(xy) to
+//                 the workspace (gradient requested) and one partial sum of S per block.
+//   k_ssim_bwd    one block per 64 x 16 tile of the IMAGE: stages a, b, c with their halo (zero outside the valid map), filters them back with
+//                 the transposed ("full") correlation and writes d loss / d pred = L1 term + SSIM term; one partial L1 sum per block.
+//   k_loss_finish one block: the partial sums in a fixed order (double) -> [main_loss, L1, SSIM] on the device.
+#include "tn_common.h"
+
+namespace {
+
+constexpr int LW = 11;            // window taps
+constexpr int LR = LW - 1;        // halo
+constexpr int LTX = 64;           // tile width (one wave of columns)
+constexpr int LTY = 16;           // tile height
+constexpr int LSX = LTX + LR;     // staged columns
+constexpr int LSY = LTY + LR;     // staged rows
+constexpr int LB = 256;           // threads per block
+constexpr int LRO = LTY / (LB / LTX);  // output rows per thread in the column pass (4)
+constexpr int LCO = 4;            // output columns per item in the row pass
+constexpr float LC1 = 0.01f * 0.01f;
+constexpr float LC2 = 0.03f * 0.03f;
+static_assert(LTX % LCO == 0 && LTY % (LB / LTX) == 0, "tile shape");
+
+struct LossK {
+  const float* pred;
+  const float* gt;
+  int64_t ps, gs;  // pixel strides (floats)
+  int H, W, C, Hv, Wv;
+  float g[LW];
+  float* abc;      // [C][3][Hv][Wv] or null (no gradient)
+  float* grad;     // [H][W][C] or null
+  float* part_s;   // one partial sum of S per k_ssim_fwd block
+  float* part_l1;  // one partial sum of |x - y| per k_ssim_bwd block
+  float cl;        // weight * (1 - lambda) / (C H W): the L1 term's gradient per unit sign
+  float cs;        // -weight * lambda / (C Nq): the SSIM term's gradient per unit of (G^T a + 2 x G^T b + y G^T c)
+};
+
+// the block's sum of v in thread 0, in a fixed order (butterfly within each wave, then the waves in order)
+__device__ __forceinline__ float block_sum(float v, float* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = 0.0f;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < LB / 64; ++i) s += red[i];
+  }
+  return s;
+}
+
+__global__ __launch_bounds__(LB) void k_ssim_fwd(LossK k) {
+  __shared__ float sx[LSY][LSX], sy[LSY][LSX];
+  __shared__ float hf[5][LSY][LTX];  // row-filtered x, y, x^2, y^2, xy
+  __shared__ float red[LB / 64];
+  const int t = threadIdx.x, tx0 = blockIdx.x * LTX, ty0 = blockIdx.y * LTY;
+  const int col = t & (LTX - 1), r0 = (t / LTX) * LRO;
+  const int64_t nv = (int64_t)k.Hv * k.Wv;
+  float ssum = 0.0f;
+  for (int c = 0; c < k.C; ++c) {
+    for (int i = t; i < LSY * LSX; i += LB) {
+      const int r = i / LSX, q = i - r * LSX, y = ty0 + r, x = tx0 + q;
+      float a = 0.0f, b = 0.0f;
+      if (y < k.H && x < k.W) {
+        const int64_t p = (int64_t)y * k.W + x;
+        a = k.pred[p * k.ps + c];
+        b = k.gt[p * k.gs + c];
+      }
+      sx[r][q] = a;
+      sy[r][q] = b;
+    }
+    __syncthreads();
+    for (int i = t; i < LSY * (LTX / LCO); i += LB) {
+      const int r = i / (LTX / LCO), q0 = (i % (LTX / LCO)) * LCO;
+      float acc[5][LCO];
+#pragma unroll
+      for (int m = 0; m < 5; ++m)
+#pragma unroll
+        for (int o = 0; o < LCO; ++o) acc[m][o] = 0.0f;
+#pragma unroll
+      for (int j = 0; j < LCO + LR; ++j) {
+        const float xv = sx[r][q0 + j], yv = sy[r][q0 + j];
+        const float v[5] = {xv, yv, xv * xv, yv * yv, xv * yv};
+#pragma unroll
+        for (int o = 0; o < LCO; ++o) {
+          const int tap = j - o;
+          if (tap >= 0 && tap < LW) {
+#pragma unroll
+            for (int m = 0; m < 5; ++m) acc[m][o] = fmaf(k.g[tap], v[m], acc[m][o]);
+          }
+        }
+      }
+#pragma unroll
+      for (int m = 0; m < 5; ++m)
+#pragma unroll
+        for (int o = 0; o < LCO; ++o) hf[m][r][q0 + o] = acc[m][o];
+    }
+    __syncthreads();
+    float mo[5][LRO];
+#pragma unroll
+    for (int m = 0; m < 5; ++m)
+#pragma unroll
+      for (int o = 0; o < LRO; ++o) mo[m][o] = 0.0f;
+#pragma unroll
+    for (int j = 0; j < LRO + LR; ++j) {
+#pragma unroll
+      for (int m = 0; m < 5; ++m) {
+        const float v = hf[m][r0 + j][col];
+#pragma unroll
+        for (int o = 0; o < LRO; ++o) {
+          const int tap = j - o;
+          if (tap >= 0 && tap < LW) mo[m][o] = fmaf(k.g[tap], v, mo[m][o]);
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 0; o < LRO; ++o) {
+      const int qy = ty0 + r0 + o, qx = tx0 + col;
+      if (qy < k.Hv && qx < k.Wv) {
+        const float mx = mo[0][o], my = mo[1][o];
+        const float mxx = mx * mx, myy = my * my, mxy = mx * my;
+        const float sxx = mo[2][o] - mxx, syy = mo[3][o] - myy, sxy = mo[4][o] - mxy;
+        const float ad = mxx + myy + LC1, D = sxx + syy + LC2;
+        const float A = (2.0f * mxy + LC1) / ad, B = (2.0f * sxy + LC2) / D;
+        ssum += A * B;
+        if (k.abc != nullptr) {
+          const float da = B * (2.0f * my - 2.0f * mx * A) / ad + A * (2.0f * mx * B - 2.0f * my) / D;
+          const float db = -A * B / D;
+          const float dc = 2.0f * A / D;
+          float* dst = k.abc + (int64_t)c * 3 * nv + (int64_t)qy * k.Wv + qx;
+          dst[0] = da;
+          dst[nv] = db;
+          dst[2 * nv] = dc;
+        }
+      }
+    }
+    __syncthreads();  // sx / sy / hf are restaged for the next channel
+  }
+  const float s = block_sum(ssum, red);
+  if (t == 0) k.part_s[blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(LB) void k_ssim_bwd(LossK k) {
+  __shared__ float sm[3][LSY][LSX];  // a, b, c over the tile's window of the valid map (zero outside it)
+  __shared__ float hf[3][LSY][LTX];
+  __shared__ float red[LB / 64];
+  const int t = threadIdx.x, tx0 = blockIdx.x * LTX, ty0 = blockIdx.y * LTY;
+  const int col = t & (LTX - 1), r0 = (t / LTX) * LRO;
+  const int64_t nv = (int64_t)k.Hv * k.Wv;
+  const bool grad = k.grad != nullptr;  // block-uniform
+  float l1 = 0.0f;
+  for (int c = 0; c < k.C; ++c) {
+    float gm[3][LRO];
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+#pragma unroll
+      for (int o = 0; o < LRO; ++o) gm[m][o] = 0.0f;
+    if (grad) {
+      const float* src = k.abc + (int64_t)c * 3 * nv;
+      for (int i = t; i < LSY * LSX; i += LB) {
+        const int r = i / LSX, q = i - r * LSX, y = ty0 - LR + r, x = tx0 - LR + q;
+        const bool in = y >= 0 && y < k.Hv && x >= 0 && x < k.Wv;
+        const int64_t p = in ? (int64_t)y * k.Wv + x : 0;
+        sm[0][r][q] = in ? src[p] : 0.0f;
+        sm[1][r][q] = in ? src[nv + p] : 0.0f;
+        sm[2][r][q] = in ? src[2 * nv + p] : 0.0f;
+      }
+      __syncthreads();
+      // pixel p receives from the valid pixels q = p - j, j = 0..10, with weight g[j]: staged column (p - tx0) + LR - j
+      for (int i = t; i < LSY * (LTX / LCO); i += LB) {
+        const int r = i / (LTX / LCO), q0 = (i % (LTX / LCO)) * LCO;
+        float acc[3][LCO];
+#pragma unroll
+        for (int m = 0; m < 3; ++m)
+#pragma unroll
+          for (int o = 0; o < LCO; ++o) acc[m][o] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < LCO + LR; ++j) {
+          const float v[3] = {sm[0][r][q0 + j], sm[1][r][q0 + j], sm[2][r][q0 + j]};
+#pragma unroll
+          for (int o = 0; o < LCO; ++o) {
+            const int tap = LR - (j - o);
+            if (tap >= 0 && tap < LW) {
+#pragma unroll
+              for (int m = 0; m < 3; ++m) acc[m][o] = fmaf(k.g[tap], v[m], acc[m][o]);
+            }
+          }
+        }
+#pragma unroll
+        for (int m = 0; m < 3; ++m)
+#pragma unroll
+          for (int o = 0; o < LCO; ++o) hf[m][r][q0 + o] = acc[m][o];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < LRO + LR; ++j) {
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+          const float v = hf[m][r0 + j][col];
+#pragma unroll
+          for (int o = 0; o < LRO; ++o) {
+            const int tap = LR - (j - o);
+            if (tap >= 0 && tap < LW) gm[m][o] = fmaf(k.g[tap], v, gm[m][o]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 0; o < LRO; ++o) {
+      const int py = ty0 + r0 + o, px = tx0 + col;
+      if (py < k.H && px < k.W) {
+        const int64_t p = (int64_t)py * k.W + px;
+        const float x = k.pred[p * k.ps + c], y = k.gt[p * k.gs + c];
+        const float d = x - y;
+        l1 += fabsf(d);
+        if (grad) {
+          const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
+          const float s = gm[0][o] + 2.0f * x * gm[1][o] + y * gm[2][o];
+          k.grad[p * k.C + c] = k.cl * sg + k.cs * s;
+        }
+      }
+    }
+    if (grad) __syncthreads();  // sm / hf are restaged for the next channel
+  }
+  const float s = block_sum(l1, red);
+  if (t == 0) k.part_l1[blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(LB) void k_loss_finish(const float* part_s, int n_s, const float* part_l1, int n_l1, double n_valid, double n_all,
+                                                    float lambda, float weight, float* out) {
+  __shared__ double r_s[LB], r_l[LB];
+  const int t = threadIdx.x;
+  double a = 0.0, b = 0.0;
+  for (int i = t; i < n_s; i += LB) a += (double)part_s[i];
+  for (int i = t; i < n_l1; i += LB) b += (double)part_l1[i];
+  r_s[t] = a;
+  r_l[t] = b;
+  __syncthreads();
+  for (int s = LB / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      r_s[t] += r_s[t + s];
+      r_l[t] += r_l[t + s];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    const double ssim = r_s[0] / n_valid, l1 = r_l[0] / n_all;
+    out[0] = (float)((double)weight * ((1.0 - (double)lambda) * l1 + (double)lambda * (1.0 - ssim)));
+    out[1] = (float)l1;
+    out[2] = (float)ssim;
+  }
+}
+
+constexpr int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
+
+struct LossLayout {
+  int64_t bx1, by1, bx2, by2, off_l1, off_abc, total;
+};
+
+LossLayout loss_layout(int32_t H, int32_t W, int32_t C) {
+  LossLayout L;
+  const int64_t Hv = H - LR, Wv = W - LR;
+  L.bx1 = tn_cdiv(Wv, LTX), L.by1 = tn_cdiv(Hv, LTY);
+  L.bx2 = tn_cdiv(W, LTX), L.by2 = tn_cdiv(H, LTY);
+  L.off_l1 = align256(L.bx1 * L.by1 * 4);
+  L.off_abc = L.off_l1 + align256(L.bx2 * L.by2 * 4);
+  L.total = L.off_abc + align256(3 * (int64_t)C * Hv * Wv * 4);
+  return L;
+}
+
+constexpr int32_t kMaxSide = 1 << 15;
+
+}  // namespace
+
+extern "C" int64_t tn_image_loss_workspace_bytes(int32_t height, int32_t width, int32_t channels) {
+  if (height < LW || width < LW || height > kMaxSide || width > kMaxSide || channels < 1 || channels > 4) return -1;
+  return loss_layout(height, width, channels).total;
+}
+
+extern "C" int tn_image_loss(const float* pred, int64_t pred_pixel_stride, const float* gt, int64_t gt_pixel_stride, int32_t height, int32_t width,
+                             int32_t channels, float ssim_lambda, float weight, void* workspace, int64_t workspace_bytes, float* out_loss,
+                             float* out_grad, tn_stream_t stream) {
+  TN_REQUIRE(pred && gt && workspace && out_loss, "tn_image_loss: null pointer");
+  TN_REQUIRE(height >= LW && width >= LW, "tn_image_loss: %d x %d image, SSIM's %d-tap window needs at least %d x %d", height, width, LW, LW, LW);
+  TN_REQUIRE(height <= kMaxSide && width <= kMaxSide, "tn_image_loss: %d x %d image is larger than %d on a side", height, width, kMaxSide);
+  TN_REQUIRE(channels >= 1 && channels <= 4, "tn_image_loss: %d channels (1..4)", channels);
+  TN_REQUIRE(pred_pixel_stride >= channels && gt_pixel_stride >= channels, "tn_image_loss: pixel strides %lld / %lld below the channel count %d",
+             (long long)pred_pixel_stride, (long long)gt_pixel_stride, channels);
+  const LossLayout L = loss_layout(height, width, channels);
+  TN_REQUIRE(workspace_bytes >= L.total, "tn_image_loss: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)L.total);
+  LossK k;
+  k.pred = pred, k.gt = gt, k.ps = pred_pixel_stride, k.gs = gt_pixel_stride;
+  k.H = height, k.W = width, k.C = channels, k.Hv = height - LR, k.Wv = width - LR;
+  // gaussian_filter's window: coords = arange(11) - 5, g = exp(-coords^2 / (2 sigma^2)), g /= g.sum(), in fp32
+  float gs = 0.0f;
+  for (int i = 0; i < LW; ++i) {
+    const float x = (float)(i - LW / 2);
+    k.g[i] = expf(-(x * x) / (2.0f * 1.5f * 1.5f));
+    gs += k.g[i];
+  }
+  for (int i = 0; i < LW; ++i) k.g[i] /= gs;
+  char* ws = static_cast<char*>(workspace);
+  k.part_s = reinterpret_cast<float*>(ws);
+  k.part_l1 = reinterpret_cast<float*>(ws + L.off_l1);
+  k.abc = out_grad ? reinterpret_cast<float*>(ws + L.off_abc) : nullptr;
+  k.grad = out_grad;
+  const double n_valid = (double)channels * k.Hv * k.Wv, n_all = (double)channels * height * width;
+  k.cl = (float)((double)weight * (1.0 - (double)ssim_lambda) / n_all);
+  k.cs = (float)(-(double)weight * (double)ssim_lambda / n_valid);
+  hipStream_t st = tn_s(stream);
+  hipLaunchKernelGGL(k_ssim_fwd, dim3((unsigned)L.bx1, (unsigned)L.by1), dim3(LB), 0, st, k);
+  TN_CHECK_LAUNCH("tn_image_loss(ssim_fwd)");
+  hipLaunchKernelGGL(k_ssim_bwd, dim3((unsigned)L.bx2, (unsigned)L.by2), dim3(LB), 0, st, k);
+  TN_CHECK_LAUNCH("tn_image_loss(ssim_bwd)");
+  hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(LB), 0, st, k.part_s, (int)(L.bx1 * L.by1), k.part_l1, (int)(L.bx2 * L.by2), n_valid, n_all,
+                     ssim_lambda, weight, out_loss);
+  TN_CHECK_LAUNCH("tn_image_loss(finish)");
+  return TN_OK;
+}

@@ -10,8 +10,10 @@ backward (tn_splat_raster_backward / tn_splat_project_backward) is the exact, bi
 and it leaves dL/d xys per Gaussian in `last_xys_grad` (what splatfacto's densification reads as `self.xys.grad`, splatfacto.py:355).
 Depth is returned detached.  Training follows splatfacto's refinement (splatfacto.py:346-498): `after_train` accumulates the gradient
 statistics (tn_splat_grad_stats), `refinement_after` splits, duplicates and culls the Gaussians (tn_splat_refine_plan / tn_splat_refine_apply)
-and carries every optimiser's parameter and Adam moments along, and resets the opacities now and then.  The SSIM loss, random backgrounds,
-the resolution schedule and camera-pose gradients are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
+and carries every optimiser's parameter and Adam moments along, and resets the opacities now and then.  The objective is splatfacto's
+(splatfacto.py:848-903): `get_loss_dict` takes (1 - ssim_lambda) * L1 + ssim_lambda * (1 - SSIM) of the frame's spectrum in one fused HIP call
+(tn_image_loss: the loss and d loss / d prediction, no host synchronisation), with pytorch_msssim's SSIM; `background_color = "random"` draws
+a random RGB + thermal background per training frame.  The resolution schedule, masks and camera-pose gradients are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
 tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 """
 from __future__ import annotations
@@ -37,8 +39,13 @@ class ThermalSplatfactoModelConfig:
     sh_degree: int = 3
     sh_degree_interval: int = 1000
     rasterize_mode: str = "classic"  # or "antialiased"
-    background_color: str = "black"  # "black" | "white" (eval render; "random" is a training-only setting)
+    background_color: str = "black"  # "black" | "white" | "random" (a random RGB + thermal background per training frame; eval: the viewer colour)
     background_thermal: float = 0.0
+    # loss (splatfacto.py:146-160); thermal_loss_mult weights a thermal frame's loss (this project's: the reference has no thermal splat model)
+    ssim_lambda: float = 0.2
+    use_scale_regularization: bool = False
+    max_gauss_ratio: float = 10.0
+    thermal_loss_mult: float = 1.0
     num_random: int = 50000
     random_scale: float = 10.0
     # refinement (splatfacto.py:108-148)
@@ -114,6 +121,88 @@ def _ptr(t: Optional[Tensor], dtype, name: str):
     if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
         raise ValueError(f"{name} must be a contiguous {dtype} HIP tensor (the splat path has no CPU fallback)")
     return C.c_void_p(t.data_ptr())
+
+
+VIEWER_BACKGROUND = (0.1490, 0.1647, 0.2157)  # eval background of "random" (splatfacto.py:680-682)
+
+
+class _ImageLoss(torch.autograd.Function):
+    """tn_image_loss as an autograd node: forward computes [weight * main loss, L1, SSIM] and d main / d pred in one call; backward scales that
+    gradient.  Only entry 0 of the output is differentiable (image_loss hands out the other two detached)."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, ssim_lambda, weight):
+        out, grad = _image_loss_call(pred, gt, ssim_lambda, weight, True)
+        ctx.save_for_backward(grad)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g[0], None, None, None
+
+
+def _image_view(t: Tensor, name: str) -> Tuple[Tensor, int]:
+    """An [H,W,C] fp32 HIP image as (tensor, pixel stride): pixels may be further apart than C (a view into an [H,W,4] buffer), rows must follow
+    pixels and channels must be adjacent; anything else is made contiguous."""
+    if not t.is_cuda or t.dtype != torch.float32:
+        raise ValueError(f"{name} must be an fp32 HIP tensor (the splat path has no CPU fallback)")
+    if t.dim() != 3:
+        raise ValueError(f"{name} must be [H, W, C], got {tuple(t.shape)}")
+    H, W, Cc = t.shape
+    if not (t.stride(2) == 1 or Cc == 1) or t.stride(1) < Cc or t.stride(0) != W * t.stride(1):
+        t = t.contiguous()
+    return t, t.stride(1)
+
+
+def _image_loss_call(pred: Tensor, gt: Tensor, ssim_lambda: float, weight: float, want_grad: bool) -> Tuple[Tensor, Optional[Tensor]]:
+    if pred.shape != gt.shape:
+        raise ValueError(f"prediction {tuple(pred.shape)} and ground truth {tuple(gt.shape)} differ")
+    pred, ps = _image_view(pred.detach(), "prediction")
+    gt, gs = _image_view(gt.detach(), "ground truth")
+    H, W, Cc = pred.shape
+    if H < 11 or W < 11:
+        raise ValueError(f"the SSIM loss needs images of at least 11 x 11 pixels (its window), got {H} x {W}")
+    if not 1 <= Cc <= 4:
+        raise ValueError(f"the SSIM loss takes 1..4 channels, got {Cc}")
+    lib = _lib.load()
+    need = int(lib.tn_image_loss_workspace_bytes(H, W, Cc))
+    if need < 0:
+        raise ValueError(f"tn_image_loss_workspace_bytes: bad sizes {H} x {W} x {Cc}")
+    dev = pred.device
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(3, device=dev)
+    grad = torch.empty((H, W, Cc), device=dev) if want_grad else None
+    _lib.check(lib.tn_image_loss(C.c_void_p(pred.data_ptr()), ps, C.c_void_p(gt.data_ptr()), gs, H, W, Cc, float(ssim_lambda), float(weight),
+                                 C.c_void_p(ws.data_ptr()), need, C.c_void_p(out.data_ptr()), C.c_void_p(grad.data_ptr()) if grad is not None else None,
+                                 _stream()), "tn_image_loss")
+    return out, grad
+
+
+def image_loss(pred: Tensor, gt: Tensor, ssim_lambda: float = 0.2, weight: float = 1.0) -> Tuple[Tensor, Tensor, Tensor]:
+    """splatfacto's training loss of one [H,W,C] frame (C = 1..4, H and W >= 11) on the device, without a host synchronisation:
+    (weight * ((1 - ssim_lambda) * L1 + ssim_lambda * (1 - SSIM)), L1, SSIM).  SSIM is pytorch_msssim's (11-tap Gaussian window, sigma 1.5, valid
+    filtering, data range 1); gt gets no gradient.  The first entry is differentiable in pred when gradients are on."""
+    if torch.is_grad_enabled() and pred.requires_grad:
+        out = _ImageLoss.apply(pred, gt, ssim_lambda, weight)
+        return out[0], out[1].detach(), out[2].detach()
+    out, _ = _image_loss_call(pred, gt, ssim_lambda, weight, False)
+    return out[0], out[1], out[2]
+
+
+def ssim(pred: Tensor, gt: Tensor) -> Tensor:
+    """pytorch_msssim's SSIM(data_range=1) of two [H,W,C] images (mean over channels), a device scalar; no gradient."""
+    return image_loss(pred.detach(), gt, 1.0, 1.0)[2]
+
+
+def _psnr(pred: Tensor, gt: Tensor) -> Tensor:
+    """PeakSignalNoiseRatio(data_range=1.0)."""
+    return -10.0 * torch.log10(torch.mean((pred - gt) ** 2))
+
+
+def _is_thermal_frame(batch) -> bool:
+    is_th = batch["is_thermal"]
+    return bool(is_th) if not hasattr(is_th, "__len__") else bool(torch.as_tensor(is_th).reshape(-1)[0])
 
 
 _PARAM_NAMES = ("means", "scales", "quats", "opacities", "features_dc", "features_rest", "features_dc_thermal", "features_rest_thermal")
@@ -279,6 +368,7 @@ class ThermalSplatfactoModel(nn.Module):
         self.max_2Dsize: Optional[Tensor] = None
         self.noise_generator = torch.Generator(device=dev)  # the split noise (splatfacto.py:541)
         self.noise_generator.manual_seed(seed)
+        self.background_generator = torch.Generator().manual_seed(seed)  # background_color "random": host draws, no synchronisation
 
     # the reference's accessors
     @property
@@ -293,6 +383,17 @@ class ThermalSplatfactoModel(nn.Module):
         dev = self.means.device
         self.gauss_params = nn.ParameterDict({k: nn.Parameter(v.detach().float().contiguous().to(dev)) for k, v in params.items()})
 
+    def _background4(self, training: bool) -> List[float]:
+        """The frame's background, RGB + thermal (splatfacto.py:668-682): "white", "random" (training: four uniform draws of the model's own
+        generator; eval: the viewer colour and background_thermal) or black."""
+        cfg = self.config
+        if cfg.background_color == "random":
+            if training:
+                return torch.rand(4, generator=self.background_generator).tolist()
+            return [*VIEWER_BACKGROUND, float(cfg.background_thermal)]
+        v = 1.0 if cfg.background_color == "white" else 0.0
+        return [v, v, v, float(cfg.background_thermal)]
+
     def _workspace(self, n: int, cap: int, tiles: int) -> Tensor:
         need = int(_lib.load().tn_splat_workspace_bytes(n, cap, tiles))
         if need < 0:
@@ -305,7 +406,7 @@ class ThermalSplatfactoModel(nn.Module):
     @torch.no_grad()
     def get_outputs(self, camera: PinholeCamera) -> Dict[str, Tensor]:
         """splatfacto.py:659-822 (eval mode, no crop box): project -> SH colours -> tile binning -> raster (colour + depth in one pass).
-        Returns rgb [H,W,3], thermal [H,W,1], depth [H,W,1], accumulation [H,W,1], background [3]."""
+        Returns rgb [H,W,3], thermal [H,W,1], depth [H,W,1], accumulation [H,W,1], background [3], background_thermal [1]."""
         cfg = self.config
         lib = _lib.load()
         gp = self.gauss_params
@@ -314,11 +415,14 @@ class ThermalSplatfactoModel(nn.Module):
         if cfg.rasterize_mode not in ("classic", "antialiased"):
             raise ValueError(f"Unknown rasterize_mode: {cfg.rasterize_mode}")
         aa = int(cfg.rasterize_mode == "antialiased")
-        bg = torch.ones(3) if cfg.background_color == "white" else torch.zeros(3)
+        bgl = self._background4(training=False)
+        bg = torch.tensor(bgl[:3])
+        bg_th = torch.tensor(bgl[3:], device=dev)
         if N == 0:  # every Gaussian culled: the background (splatfacto.py:759-764)
             background = bg.to(dev)
-            return {"rgb": background.repeat(H, W, 1), "thermal": torch.full((H, W, 1), cfg.background_thermal, device=dev),
-                    "depth": torch.full((H, W, 1), 10.0, device=dev), "accumulation": torch.zeros((H, W, 1), device=dev), "background": background}
+            return {"rgb": background.repeat(H, W, 1), "thermal": torch.full((H, W, 1), bgl[3], device=dev),
+                    "depth": torch.full((H, W, 1), 10.0, device=dev), "accumulation": torch.zeros((H, W, 1), device=dev), "background": background,
+                    "background_thermal": bg_th}
         cam = camera_struct(camera)
         tiles = ((W + BLOCK_WIDTH - 1) // BLOCK_WIDTH) * ((H + BLOCK_WIDTH - 1) // BLOCK_WIDTH)
         K = gp["features_rest"].shape[1]
@@ -357,36 +461,100 @@ class ThermalSplatfactoModel(nn.Module):
         self.last_num_intersections = int(total.value)
         background = bg.to(dev)
         if total.value == 0:  # nothing on screen (splatfacto.py:759-764)
-            return {"rgb": background.repeat(H, W, 1), "thermal": torch.full((H, W, 1), cfg.background_thermal, device=dev),
-                    "depth": torch.full((H, W, 1), 10.0, device=dev), "accumulation": torch.zeros((H, W, 1), device=dev), "background": background}
+            return {"rgb": background.repeat(H, W, 1), "thermal": torch.full((H, W, 1), bgl[3], device=dev),
+                    "depth": torch.full((H, W, 1), 10.0, device=dev), "accumulation": torch.zeros((H, W, 1), device=dev), "background": background,
+                    "background_thermal": bg_th}
         rgbt = torch.empty((H, W, 4), device=dev)
         depth = torch.empty((H, W, 1), device=dev)
         alpha = torch.empty((H, W, 1), device=dev)
-        bg4 = (C.c_float * 4)(float(bg[0]), float(bg[1]), float(bg[2]), float(cfg.background_thermal))
+        bg4 = (C.c_float * 4)(float(bg[0]), float(bg[1]), float(bg[2]), bgl[3])
         _lib.check(lib.tn_splat_raster(C.byref(cam), N, C.c_void_p(self._ws.data_ptr()), cap, bg4, aa, _ptr(rgbt, f32, "rgbt"), _ptr(depth, f32, "depth"),
                                        _ptr(alpha, f32, "alpha"), _stream()), "tn_splat_raster")
-        return {"rgb": rgbt[..., :3], "thermal": rgbt[..., 3:], "depth": depth, "accumulation": alpha, "background": background}
+        return {"rgb": rgbt[..., :3], "thermal": rgbt[..., 3:], "depth": depth, "accumulation": alpha, "background": background,
+                "background_thermal": bg_th}
 
     def get_train_outputs(self, camera: PinholeCamera) -> Dict[str, Tensor]:
         """The render of get_outputs as a differentiable function of every gauss_params tensor (splatfacto.py:659-822 in training, without
-        the random background and the crop box).  rgb [H,W,3], thermal [H,W,1] and accumulation [H,W,1] carry gradients; depth [H,W,1] is
-        detached.  The values equal get_outputs' bit for bit.  After backward(), `last_xys_grad` [N,2] holds dL/d xys per Gaussian."""
+        the crop box).  rgb [H,W,3], thermal [H,W,1] and accumulation [H,W,1] carry gradients; depth [H,W,1] is detached.  With a fixed
+        background the values equal get_outputs' bit for bit; background_color "random" draws this frame's RGB + thermal background from the
+        model's generator (background [3], background_thermal [1]).  After backward(), `last_xys_grad` [N,2] holds dL/d xys per Gaussian."""
         cfg = self.config
         if cfg.rasterize_mode not in ("classic", "antialiased"):
             raise ValueError(f"Unknown rasterize_mode: {cfg.rasterize_mode}")
         gp = self.gauss_params
         dev = gp["means"].device
-        bg = torch.ones(3) if cfg.background_color == "white" else torch.zeros(3)
+        bgl = self._background4(training=True)
+        bg = torch.tensor(bgl[:3])
         frame = {"model": self, "camera": camera, "cam": camera_struct(camera), "aa": int(cfg.rasterize_mode == "antialiased"),
                  "deg": min(self.step // cfg.sh_degree_interval, cfg.sh_degree) if cfg.sh_degree > 0 else -1,
-                 "bg4": (C.c_float * 4)(float(bg[0]), float(bg[1]), float(bg[2]), float(cfg.background_thermal))}
+                 "bg4": (C.c_float * 4)(*bgl)}
         self.last_xys_grad = None
         rgbt, alpha, depth = _SplatRender.apply(frame, *(gp[k] for k in _PARAM_NAMES))
-        background = bg.to(dev)
+        background, bg_th = bg.to(dev), torch.tensor(bgl[3:], device=dev)
         if self.last_num_intersections == 0:  # the background as get_outputs returns it (no clamp)
-            return {"rgb": rgbt[..., :3], "thermal": rgbt[..., 3:], "depth": depth, "accumulation": alpha, "background": background}
+            return {"rgb": rgbt[..., :3], "thermal": rgbt[..., 3:], "depth": depth, "accumulation": alpha, "background": background,
+                    "background_thermal": bg_th}
         return {"rgb": torch.clamp(rgbt[..., :3], max=1.0), "thermal": torch.clamp(rgbt[..., 3:], max=1.0), "depth": depth, "accumulation": alpha,
-                "background": background}
+                "background": background, "background_thermal": bg_th}
+
+    # ------------------------------------------------------------------------------------------------ loss and metrics (splatfacto.py:824-934)
+    def get_gt_img(self, image: Tensor) -> Tensor:
+        """splatfacto.py:824-834 without the resolution schedule: uint8 -> [0, 1] float, on the model's device."""
+        if image.dtype == torch.uint8:
+            image = image.float() / 255.0
+        return image.to(self.means.device)
+
+    def composite_with_background(self, image: Tensor, background: Tensor) -> Tensor:
+        """splatfacto.py:836-846: an [H,W,4] image (alpha last) over the frame's background -- background [3] for an RGB frame, [1] (the
+        thermal background) for a thermal one; other images pass through."""
+        if image.shape[2] == 4:
+            alpha = image[..., -1].unsqueeze(-1).repeat((1, 1, 3))
+            return alpha * image[..., :3] + (1 - alpha) * background
+        return image
+
+    def _frame_pred_gt(self, outputs: Dict[str, Tensor], batch) -> Tuple[bool, Tensor, Tensor]:
+        """(is thermal, prediction, ground truth) of the frame's spectrum: RGB [H,W,3] against image[..., :3], or thermal [H,W,1] against
+        image[..., 0:1] (model.rgb_to_rgbt_image), the ground truth composited over the frame's background."""
+        th = _is_thermal_frame(batch)
+        bg = outputs["background_thermal"] if th else outputs["background"]
+        gt = self.composite_with_background(self.get_gt_img(batch["image"]), bg)
+        return (True, outputs["thermal"], gt[..., 0:1]) if th else (False, outputs["rgb"], gt[..., :3])
+
+    def get_loss_dict(self, outputs: Dict[str, Tensor], batch, metrics_dict=None) -> Dict[str, Tensor]:
+        """splatfacto.py:863-903 on the frame's spectrum: main_loss = (1 - ssim_lambda) * L1 + ssim_lambda * (1 - SSIM) (one tn_image_loss call,
+        times thermal_loss_mult on a thermal frame) and scale_reg (every 10th step when use_scale_regularization, else 0).  `batch`: image
+        [H,W,3|4], is_thermal."""
+        if "mask" in batch:
+            raise NotImplementedError("masks are not supported by the splat loss (DESIGN.md section 7)")
+        cfg = self.config
+        th, pred, gt = self._frame_pred_gt(outputs, batch)
+        main, _, _ = image_loss(pred, gt.float(), cfg.ssim_lambda, cfg.thermal_loss_mult if th else 1.0)
+        dev = self.means.device
+        if cfg.use_scale_regularization and self.step % 10 == 0:
+            scale_exp = torch.exp(self.gauss_params["scales"])
+            scale_reg = torch.maximum(scale_exp.amax(dim=-1) / scale_exp.amin(dim=-1), torch.tensor(cfg.max_gauss_ratio, device=dev)) - cfg.max_gauss_ratio
+            scale_reg = 0.1 * scale_reg.mean()
+        else:
+            scale_reg = torch.tensor(0.0).to(dev)
+        return {"main_loss": main, "scale_reg": scale_reg}
+
+    @torch.no_grad()
+    def get_metrics_dict(self, outputs: Dict[str, Tensor], batch) -> Dict[str, Tensor]:
+        """splatfacto.py:848-861 on the frame's spectrum: psnr (data range 1, a device scalar) and gaussian_count."""
+        _, pred, gt = self._frame_pred_gt(outputs, batch)
+        return {"psnr": _psnr(pred, gt), "gaussian_count": self.num_points}
+
+    @torch.no_grad()
+    def get_image_metrics_and_images(self, outputs: Dict[str, Tensor], batch) -> Tuple[Dict[str, float], Dict[str, Tensor]]:
+        """splatfacto.py:917-934 with ThermalNerfactoModel's keys: psnr_rgb / ssim_rgb or psnr_thermal / ssim_thermal of the frame's spectrum
+        (SSIM = the loss's, tn_image_loss), and the ground truth beside both renders.  LPIPS is left out, as elsewhere in this project."""
+        th, pred, gt = self._frame_pred_gt(outputs, batch)
+        key = "thermal" if th else "rgb"
+        metrics = {f"psnr_{key}": float(_psnr(pred, gt)), f"ssim_{key}": float(ssim(pred, gt.float()))}
+        gt3 = gt.expand(-1, -1, 3) if th else gt
+        images = {"img": torch.cat([gt3, outputs["rgb"], outputs["thermal"].expand(-1, -1, 3)], dim=1), "accumulation": outputs["accumulation"],
+                  "depth": outputs["depth"]}
+        return metrics, images
 
     # ------------------------------------------------------------------------------------------------ training (splatfacto.py:258-628)
     def step_cb(self, step: int) -> None:

@@ -1,0 +1,102 @@
+"""Splat trainer on the synthetic RGB+T cube scene: ThermalSplatfactoModel trained on whole frames with splatfacto's objective.
+
+The scene is train_eval_scene.py's (write_cube_scene: RGB 640x480 and thermal 160x120 frames on a ring, written to disk as a dataset) read back
+through this package's dataparser.  Training keeps every train frame resident on the device, turns each camera into a PinholeCamera and visits
+the frames in a shuffled order per epoch: get_train_outputs -> get_loss_dict (L1 + SSIM, tn_image_loss) -> backward -> Optimizers(SPLAT_OPTIMIZERS,
+HipAdam) -> the model's training callbacks (SH degree, gradient statistics, refinement).  At the end it reports PSNR / SSIM per spectrum on the
+val split and the time per iteration as one JSON line.  (Camera distortion is ignored: the scene's cameras have none.)"""
+import argparse
+import json
+import math
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import torch  # noqa: E402
+
+import nerfstudio_thermal_amd  # noqa: E402,F401
+from nerfstudio_thermal_amd.dataparser import ThermalNerfDataParserConfig, load_image_float32  # noqa: E402
+from nerfstudio_thermal_amd.model import TrainingCallbackLocation  # noqa: E402
+from nerfstudio_thermal_amd.optim import SPLAT_OPTIMIZERS, HipAdam, Optimizers  # noqa: E402
+from nerfstudio_thermal_amd.splat import PinholeCamera, ThermalSplatfactoModel, ThermalSplatfactoModelConfig  # noqa: E402
+from train_eval_scene import write_cube_scene  # noqa: E402
+
+
+def frames_of(outputs, device):
+    """(PinholeCamera, batch) per image of a dataparser split; images resident on the device"""
+    cams = outputs.cameras
+    out = []
+    for i, path in enumerate(outputs.image_filenames):
+        cam = PinholeCamera(cams["c2w"][i].float(), float(cams["fx"][i]), float(cams["fy"][i]), float(cams["cx"][i]), float(cams["cy"][i]),
+                            int(cams["width"][i]), int(cams["height"][i]))
+        out.append((cam, {"image": load_image_float32(path).to(device), "is_thermal": bool(outputs.metadata["is_thermal"][i])}))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--data", default=None)
+    ap.add_argument("--steps", type=int, default=3000)
+    ap.add_argument("--frames", type=int, default=12, help="frames per spectrum of the generated scene")
+    ap.add_argument("--gaussians", type=int, default=20000, help="random initial Gaussians (uniform in a cube of side --init-extent)")
+    ap.add_argument("--init-extent", type=float, default=1.0)
+    ap.add_argument("--ssim-lambda", type=float, default=0.2)
+    ap.add_argument("--background", default="random")
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    tmp = None
+    data = args.data
+    if data is None:
+        tmp = tempfile.TemporaryDirectory()
+        data = tmp.name
+        write_cube_scene(data, args.frames, dev)
+    pc = ThermalNerfDataParserConfig(data=data)
+    train, val = frames_of(pc.setup().get_dataparser_outputs("train"), dev), frames_of(pc.setup().get_dataparser_outputs("val"), dev)
+    cfg = ThermalSplatfactoModelConfig(num_random=args.gaussians, random_scale=args.init_extent, ssim_lambda=args.ssim_lambda,
+                                       background_color=args.background)
+    model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=len(train))
+    opts = Optimizers(model.get_param_groups(), SPLAT_OPTIMIZERS, optimizer_cls=HipAdam)
+    cbs = model.get_training_callbacks(opts)
+    order_gen = torch.Generator().manual_seed(args.seed)
+    order = []
+    curve = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for step in range(args.steps):
+        if not order:
+            order = torch.randperm(len(train), generator=order_gen).tolist()
+        cam, batch = train[order.pop()]
+        for cb in cbs:
+            cb.run_callback_at_location(step, TrainingCallbackLocation.BEFORE_TRAIN_ITERATION)
+        opts.zero_grad_all()
+        loss = model.get_loss_dict(model.get_train_outputs(cam), batch)
+        (loss["main_loss"] + loss["scale_reg"]).backward()
+        opts.optimizer_step_all()
+        opts.scheduler_step_all()
+        for cb in cbs:
+            cb.run_callback_at_location(step, TrainingCallbackLocation.AFTER_TRAIN_ITERATION)
+        if (step + 1) % 500 == 0 or step + 1 == args.steps:
+            torch.cuda.synchronize()
+            curve.append({"step": step + 1, "seconds": time.perf_counter() - t0, "main_loss": float(loss["main_loss"].detach()), "gaussians": model.num_points})
+    torch.cuda.synchronize()
+    train_s = time.perf_counter() - t0
+    sums = {}
+    with torch.no_grad():
+        for cam, batch in val:
+            metrics, _ = model.get_image_metrics_and_images(model.get_outputs(cam), batch)
+            for k, v in metrics.items():
+                sums.setdefault(k, []).append(v)
+    metrics = {k: sum(v) / len(v) for k, v in sums.items() if all(math.isfinite(x) for x in v)}
+    print(json.dumps({"dataset": "synthetic cube scene (train_eval_scene.write_cube_scene)" if tmp else data, "train_images": len(train),
+                      "val_images": len(val), "steps": args.steps, "ssim_lambda": args.ssim_lambda, "background_color": args.background,
+                      "initial_gaussians": args.gaussians, "final_gaussians": model.num_points, "train_seconds": train_s,
+                      "ms_per_iteration": 1e3 * train_s / max(args.steps, 1), "val_metrics": metrics, "curve": curve}))
+
+
+if __name__ == "__main__":
+    main()
