@@ -754,6 +754,18 @@ TN_API int64_t tn_image_loss_workspace_bytes(int32_t height, int32_t width, int3
 TN_API int tn_image_loss(const float* pred, int64_t pred_pixel_stride, const float* gt, int64_t gt_pixel_stride, int32_t height, int32_t width,
                          int32_t channels, float ssim_lambda, float weight, void* workspace, int64_t workspace_bytes, float* out_loss, float* out_grad,
                          tn_stream_t stream);
+/* ---- N4 seeding: exact k-nearest-neighbour distances over a point cloud (splatfacto's k_nearest_sklearn, nerfstudio/models/splatfacto.py:272-290,
+ * which seeds each Gaussian's log-scale from the mean distance to its 3 nearest neighbours).  Row i of out_dist holds the k smallest distances
+ * from point i to the points j != i, ascending; a duplicate of point i is a neighbour at distance 0.  d2 = (dx*dx + dy*dy) + dz*dz with
+ * dx = xi - xj (and dy, dz) in fp32, each operation rounded, distance = sqrtf(d2) correctly rounded; ties on d2 go to the smaller index.  The
+ * result is exact -- bit-identical to a brute force with that formula -- and deterministic (no float atomics).  No host synchronisation.
+ *
+ * scratch of tn_knn; -1 on bad sizes (n outside 0..INT32_MAX, k outside 1..8) or when the sort's scratch cannot be sized (no device) */
+TN_API int64_t tn_knn_workspace_bytes(int64_t n, int32_t k);
+/* points [n,3] fp32 -> out_dist [n,k] and, unless NULL, out_index [n,k] int32 (the neighbours' row numbers).  n == 0 does nothing.  Refused with
+ * TN_EINVAL before any launch: k outside 1..8, n < 0 or n > INT32_MAX, null pointers, n < k + 1, a short workspace. */
+TN_API int tn_knn(const float* points, int64_t n, int32_t k, float* out_dist, int32_t* out_index, void* workspace, int64_t workspace_bytes,
+                  tn_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

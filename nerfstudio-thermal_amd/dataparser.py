@@ -6,6 +6,9 @@ Reader  = ThermalNerf dataparser (data/dataparsers/thermalnerf_dataparser.py:17-
 Writer  = the layout process_data/rgbt_to_nerfstudio_dataset.py:240-266 produces: RGB frames first, then the thermal frames, every frame with
           its own fl_x/fl_y/cx/cy/w/h/k1/k2/p1/p2 and `is_thermal`, images under images/ and images_thermal/ (8-bit PNG; thermal single channel).
 Loader  = InputDataset.get_image_float32 (data/datasets/base_dataset.py:61-95): uint8 / 255, a single-channel image repeated to 3 channels.
+Points  = load_3D_points (nerfstudio_dataparser.py:352-466): the sparse point cloud named by `ply_file_path`, read by `read_ply` (the
+          subset of PLY that open3d's reader is used for there: ascii / binary little-endian vertices with optional colours), moved into the
+          dataparser's frame and scale; `write_ply` writes such a file.
 
 The outputs feed ops.ImageCache / DeviceDataManager (the per-step pixel sampling and ray generation run on the device) and
 ThermalNerfactoModel.get_outputs_for_camera.  Host-side, one-off work: plain numpy / torch CPU; nothing here is on the per-ray path.
@@ -35,6 +38,7 @@ class ThermalNerfDataParserConfig:
     eval_mode: str = "fraction"  # "fraction" | "interval" | "all"
     train_split_fraction: float = 0.9
     eval_interval: int = 8
+    load_3D_points: bool = False  # metadata points3D_xyz / points3D_rgb from transforms.json's ply_file_path (splatfacto's seed points)
 
     def setup(self) -> "ThermalNerf":
         return ThermalNerf(self)
@@ -193,9 +197,139 @@ class ThermalNerf:
             dataparser_transform = transform @ torch.cat([at, torch.tensor([[0, 0, 0, 1]], dtype=transform.dtype)], 0)
         if "applied_scale" in meta:
             scale *= float(meta["applied_scale"])
+        metadata = {"is_thermal": [frames[i]["is_thermal"] for i in indices]}
+        if c.load_3D_points:
+            if "ply_file_path" in meta:
+                metadata.update(load_3D_points(os.path.join(data_dir, meta["ply_file_path"]), transform, scale))
+            else:
+                print("Warning: load_3D_points set to true but no point cloud found. splatfacto will use random point cloud initialization.")
         return DataparserOutputs(image_filenames=[image_filenames[i] for i in indices], cameras=cams,
                                  scene_box_aabb=torch.tensor([[-a, -a, -a], [a, a, a]], dtype=torch.float32), dataparser_scale=scale,
-                                 dataparser_transform=dataparser_transform, metadata={"is_thermal": [frames[i]["is_thermal"] for i in indices]})
+                                 dataparser_transform=dataparser_transform, metadata=metadata)
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray]:
+    """The vertices of a PLY file -> (xyz [M,3] float32, rgb [M,3] uint8, or [0,3] when the file has no colours -- what
+    np.asarray(pcd.colors) gives).  Formats ascii 1.0 and binary_little_endian 1.0; x y z of any numeric type (read as float64, as open3d
+    does, then cast); red green blue as uchar (the bytes as stored) or float / double ((c * 255).astype(uint8), open3d's colours times 255 as
+    nerfstudio_dataparser.py:461 computes them; clipped to 0..255 first).  Other vertex properties and the elements after `vertex` are
+    ignored; fixed-size elements before it are skipped.  ValueError: big-endian or unknown formats, a missing x, y or z, a list property at or
+    before the vertices, a truncated body."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if not data.startswith(b"ply"):
+        raise ValueError(f"{path}: not a PLY file")
+    end = data.find(b"end_header")
+    if end < 0:
+        raise ValueError(f"{path}: PLY header without end_header")
+    body = data.index(b"\n", end) + 1
+    fmt = None
+    elements: List[Tuple[str, int, List[Tuple[str, str]]]] = []  # (name, count, [(property, numpy type)])
+    for raw in data[:end].decode("ascii", errors="replace").splitlines()[1:]:
+        tok = raw.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            if len(tok) < 3 or tok[1] not in ("ascii", "binary_little_endian", "binary_big_endian"):
+                raise ValueError(f"{path}: unknown PLY format {' '.join(tok[1:])!r}")
+            if tok[1] == "binary_big_endian":
+                raise ValueError(f"{path}: big-endian PLY is not supported (ascii 1.0 and binary_little_endian 1.0 are)")
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property":
+            if not elements:
+                raise ValueError(f"{path}: property outside an element")
+            if tok[1] == "list":
+                elements[-1][2].append((tok[-1], "list"))
+            elif tok[1] in _PLY_TYPES:
+                elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
+            else:
+                raise ValueError(f"{path}: unknown PLY property type {tok[1]!r}")
+    if fmt is None:
+        raise ValueError(f"{path}: PLY header without a format line")
+    names = [e[0] for e in elements]
+    if "vertex" not in names:
+        raise ValueError(f"{path}: PLY without a vertex element")
+    vi = names.index("vertex")
+    for name, _, props in elements[:vi + 1]:
+        if any(t == "list" for _, t in props):
+            raise ValueError(f"{path}: list property in element {name!r} at or before the vertices")
+    count, props = elements[vi][1], elements[vi][2]
+    pnames = [p for p, _ in props]
+    for axis in ("x", "y", "z"):
+        if axis not in pnames:
+            raise ValueError(f"{path}: the vertices have no {axis!r} property")
+    if fmt == "ascii":
+        lines = data[body:].decode("ascii", errors="replace").splitlines()
+        skip = sum(e[1] for e in elements[:vi])
+        rows = [ln.split() for ln in lines[skip:skip + count]]
+        if len(rows) < count or any(len(r) < len(props) for r in rows):
+            raise ValueError(f"{path}: truncated PLY body ({len(rows)} of {count} vertices)")
+        cols = {p: np.array([r[i] for r in rows], dtype=np.float64 if t[0] == "f" else np.int64).astype(t) for i, (p, t) in enumerate(props)}
+    else:
+        off = body + sum(e[1] * int(np.dtype([(p, "<" + t) for p, t in e[2]]).itemsize) for e in elements[:vi])
+        dt = np.dtype([(p, "<" + t) for p, t in props])
+        if len(data) < off + count * dt.itemsize:
+            raise ValueError(f"{path}: truncated PLY body ({len(data) - off} bytes, {count} vertices need {count * dt.itemsize})")
+        arr = np.frombuffer(data, dtype=dt, count=count, offset=off)
+        cols = {p: arr[p] for p in pnames}
+    xyz = np.stack([cols[a].astype(np.float64) for a in ("x", "y", "z")], -1).astype(np.float32)
+    if not all(c in pnames for c in ("red", "green", "blue")):
+        return xyz, np.zeros((0, 3), dtype=np.uint8)
+    rgb = np.stack([cols[c] for c in ("red", "green", "blue")], -1)
+    if rgb.dtype == np.uint8:
+        return xyz, rgb.copy()
+    if rgb.dtype.kind == "f":
+        return xyz, np.clip(rgb.astype(np.float64) * 255, 0, 255).astype(np.uint8)
+    raise ValueError(f"{path}: vertex colours of type {rgb.dtype} (uchar, float or double are read)")
+
+
+def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, binary: bool = True) -> str:
+    """xyz [M,3] (float32 or float64 -> float / double properties) and optional rgb [M,3] (uint8 -> uchar, float -> float / double) as one
+    PLY vertex element, binary little-endian or ascii."""
+    xyz = np.asarray(xyz)
+    if xyz.dtype not in (np.float32, np.float64):
+        xyz = xyz.astype(np.float32)
+    ptype = {np.dtype("u1"): "uchar", np.dtype("f4"): "float", np.dtype("f8"): "double"}
+    fields = [(a, xyz.dtype) for a in ("x", "y", "z")]
+    if rgb is not None:
+        rgb = np.asarray(rgb)
+        if rgb.dtype not in ptype:
+            raise ValueError(f"write_ply: colours of type {rgb.dtype} (uint8, float32 or float64)")
+        fields += [(c, rgb.dtype) for c in ("red", "green", "blue")]
+    head = ["ply", f"format {'binary_little_endian' if binary else 'ascii'} 1.0", f"element vertex {xyz.shape[0]}"]
+    head += [f"property {ptype[np.dtype(t)]} {n}" for n, t in fields] + ["end_header"]
+    rec = np.empty(xyz.shape[0], dtype=[(n, np.dtype(t).newbyteorder("<")) for n, t in fields])
+    for i, a in enumerate(("x", "y", "z")):
+        rec[a] = xyz[:, i]
+    if rgb is not None:
+        for i, c in enumerate(("red", "green", "blue")):
+            rec[c] = rgb[:, i]
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii"))
+        if binary:
+            f.write(rec.tobytes())
+        else:
+            for r in rec:
+                f.write((" ".join(repr(float(r[n])) if np.dtype(t).kind == "f" else str(int(r[n])) for n, t in fields) + "\n").encode("ascii"))
+    return path
+
+
+def load_3D_points(ply_path: str, transform: Tensor, scale: float) -> Dict[str, Tensor]:
+    """nerfstudio_dataparser.py:429-466: the cloud in the dataparser's frame, points3D_xyz = cat(xyz, 1) @ transform.T * scale (transform =
+    auto_orient_and_center_poses' [3,4], scale = the final scale, applied_scale included), and points3D_rgb uint8.  No keys for an empty cloud."""
+    xyz, rgb = read_ply(ply_path)
+    if xyz.shape[0] == 0:
+        return {}
+    points = torch.from_numpy(xyz)
+    points = torch.cat((points, torch.ones_like(points[..., :1])), -1) @ transform.T
+    points *= scale
+    return {"points3D_xyz": points, "points3D_rgb": torch.from_numpy(rgb)}
 
 
 def load_image_float32(path: str) -> Tensor:

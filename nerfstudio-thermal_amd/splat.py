@@ -13,7 +13,10 @@ statistics (tn_splat_grad_stats), `refinement_after` splits, duplicates and cull
 and carries every optimiser's parameter and Adam moments along, and resets the opacities now and then.  The objective is splatfacto's
 (splatfacto.py:848-903): `get_loss_dict` takes (1 - ssim_lambda) * L1 + ssim_lambda * (1 - SSIM) of the frame's spectrum in one fused HIP call
 (tn_image_loss: the loss and d loss / d prediction, no host synchronisation), with pytorch_msssim's SSIM; `background_color = "random"` draws
-a random RGB + thermal background per training frame.  The resolution schedule, masks and camera-pose gradients are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
+a random RGB + thermal background per training frame.  Construction follows splatfacto's populate_modules (splatfacto.py:190-242): from
+`seed_points` (the dataparser's points3D_xyz / points3D_rgb, dataparser.py `load_3D_points`) one Gaussian per point, its log-scale the log of the
+mean distance to its 3 nearest neighbours (`knn_distances`: tn_knn, an exact HIP search), or -- without seeds or with `random_init` -- the random
+cube of before.  The resolution schedule, masks and camera-pose gradients are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
 tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 """
 from __future__ import annotations
@@ -46,6 +49,8 @@ class ThermalSplatfactoModelConfig:
     use_scale_regularization: bool = False
     max_gauss_ratio: float = 10.0
     thermal_loss_mult: float = 1.0
+    # initialisation (splatfacto.py:127-131): random_init ignores the model's seed_points
+    random_init: bool = False
     num_random: int = 50000
     random_scale: float = 10.0
     # refinement (splatfacto.py:108-148)
@@ -121,6 +126,45 @@ def _ptr(t: Optional[Tensor], dtype, name: str):
     if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
         raise ValueError(f"{name} must be a contiguous {dtype} HIP tensor (the splat path has no CPU fallback)")
     return C.c_void_p(t.data_ptr())
+
+
+KNN_MAX_K = 8  # tn_knn's largest k
+
+
+def knn_distances(points: Tensor, k: int = 3, return_index: bool = False):
+    """Exact k-nearest-neighbour distances of every point to the OTHER points (k_nearest_sklearn, splatfacto.py:272-290: NearestNeighbors(k + 1)
+    over the cloud, the point itself dropped) in one tn_knn call on the current stream.  points: contiguous [N,3] fp32 on the device ->
+    distances [N,k] fp32, ascending (and neighbour indices [N,k] int64 with return_index).  d = sqrtf((dx*dx + dy*dy) + dz*dz) in fp32, ties go
+    to the smaller index: bit-identical to a brute force with that formula, and deterministic.  Raises ValueError for non-finite points (one
+    host synchronisation) and for N < k + 1."""
+    if not isinstance(points, Tensor) or not points.is_cuda or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("knn_distances takes an [N,3] float32 HIP tensor (the splat path has no CPU fallback)")
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"knn_distances: k = {k}, tn_knn supports 1..{KNN_MAX_K}")
+    n = points.shape[0]
+    if n < k + 1:
+        raise ValueError(f"knn_distances: {n} points, k = {k} needs at least k + 1")
+    pts = points.contiguous()
+    if not bool(torch.isfinite(pts).all()):
+        raise ValueError("knn_distances: the points must be finite")
+    lib = _lib.load()
+    need = int(lib.tn_knn_workspace_bytes(n, k))
+    if need < 0:
+        raise RuntimeError(f"tn_knn_workspace_bytes({n}, {k}) failed")
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=pts.device)
+    dist = torch.empty((n, k), device=pts.device)
+    idx = torch.empty((n, k), dtype=torch.int32, device=pts.device) if return_index else None
+    _lib.check(lib.tn_knn(_ptr(pts, torch.float32, "points"), n, k, _ptr(dist, torch.float32, "distances"), _ptr(idx, torch.int32, "indices"),
+                          C.c_void_p(ws.data_ptr()), need, _stream()), "tn_knn")
+    return (dist, idx.long()) if return_index else dist
+
+
+SH_C0 = 0.28209479177387814  # utils/spherical_harmonics.py
+
+
+def RGB2SH(rgb: Tensor) -> Tensor:
+    """utils/spherical_harmonics.py: RGB2SH"""
+    return (rgb - 0.5) / SH_C0
 
 
 VIEWER_BACKGROUND = (0.1490, 0.1647, 0.2157)  # eval background of "random" (splatfacto.py:680-682)
@@ -327,10 +371,21 @@ class _SplatRender(torch.autograd.Function):
 
 class ThermalSplatfactoModel(nn.Module):
     """RGB + thermal Gaussians: eval render (`get_outputs`) and differentiable training render (`get_train_outputs`).  `gauss_params` keeps the
-    reference's names (splatfacto.py:226-235)."""
+    reference's names (splatfacto.py:226-235).
+
+    Initialisation (populate_modules, splatfacto.py:190-242).  With `seed_points` = (xyz [M,3], rgb [M,3] uint8, either device) and
+    `random_init` False: means = xyz; scales = log(mean distance to the 3 nearest neighbours) on all three axes (knn_distances, then the
+    reference's torch ops); quats = a normalised Gaussian draw of the model's seeded CPU generator (uniform on S^3, like random_quat_tensor);
+    opacities = logit(0.1); features_dc = RGB2SH(rgb / 255) for sh_degree > 0, or logit(rgb / 255, eps=1e-10) for sh_degree 0 -- evaluated in
+    float64 and cast to float32, a deviation from the reference, whose fp32 logit is +inf for a channel value of 255 (float64 gives +-23.03);
+    random features_dc when rgb has no rows (the reference's "colors without points"); features_rest zero.  The cloud carries no thermal
+    values, so features_dc_thermal and features_rest_thermal start at zero: mid-grey in thermal under both colour modes (this project's rule).
+    Fewer than 4 seed points is a ValueError (the kNN needs 3 neighbours).  Without seeds, or with `random_init`, construction is this model's
+    random cube as before, with the constant log-scale log(0.01 * random_scale): the reference would give the random start kNN scales too,
+    which this model deliberately does not, to keep that start unchanged."""
 
     def __init__(self, config: Optional[ThermalSplatfactoModelConfig] = None, num_points: Optional[int] = None, device="cuda", seed: int = 0,
-                 num_train_data: int = 0):
+                 num_train_data: int = 0, seed_points: Optional[Tuple[Tensor, Tensor]] = None):
         super().__init__()
         self.config = config or ThermalSplatfactoModelConfig()
         self.num_train_data = num_train_data
@@ -338,21 +393,24 @@ class ThermalSplatfactoModel(nn.Module):
         if dev.type != "cuda":
             raise RuntimeError("ThermalSplatfactoModel needs a HIP device: there is no CPU fallback on this path")
         _lib.load()
-        n = self.config.num_random if num_points is None else num_points
         g = torch.Generator().manual_seed(seed)
         dim_sh = (self.config.sh_degree + 1) ** 2
-        # random_init of the reference (splatfacto.py:190-225): positions uniform in a cube, identity-ish colours, opacity logit(0.1)
-        means = (torch.rand((n, 3), generator=g) - 0.5) * self.config.random_scale
-        self.gauss_params = nn.ParameterDict({
-            "means": nn.Parameter(means.to(dev)),
-            "scales": nn.Parameter(torch.full((n, 3), math.log(0.01 * self.config.random_scale)).to(dev)),
-            "quats": nn.Parameter(torch.nn.functional.normalize(torch.randn((n, 4), generator=g), dim=-1).to(dev)),
-            "opacities": nn.Parameter(torch.logit(0.1 * torch.ones(n, 1)).to(dev)),
-            "features_dc": nn.Parameter(torch.rand((n, 3), generator=g).to(dev)),
-            "features_rest": nn.Parameter(torch.zeros((n, dim_sh - 1, 3), device=dev)),
-            "features_dc_thermal": nn.Parameter(torch.rand((n, 1), generator=g).to(dev)),
-            "features_rest_thermal": nn.Parameter(torch.zeros((n, dim_sh - 1, 1), device=dev)),
-        })
+        if seed_points is not None and not self.config.random_init:
+            self.gauss_params = self._seeded_params(seed_points, g, dim_sh, dev)
+        else:
+            n = self.config.num_random if num_points is None else num_points
+            # random_init of the reference (splatfacto.py:190-225): positions uniform in a cube, identity-ish colours, opacity logit(0.1)
+            means = (torch.rand((n, 3), generator=g) - 0.5) * self.config.random_scale
+            self.gauss_params = nn.ParameterDict({
+                "means": nn.Parameter(means.to(dev)),
+                "scales": nn.Parameter(torch.full((n, 3), math.log(0.01 * self.config.random_scale)).to(dev)),
+                "quats": nn.Parameter(torch.nn.functional.normalize(torch.randn((n, 4), generator=g), dim=-1).to(dev)),
+                "opacities": nn.Parameter(torch.logit(0.1 * torch.ones(n, 1)).to(dev)),
+                "features_dc": nn.Parameter(torch.rand((n, 3), generator=g).to(dev)),
+                "features_rest": nn.Parameter(torch.zeros((n, dim_sh - 1, 3), device=dev)),
+                "features_dc_thermal": nn.Parameter(torch.rand((n, 1), generator=g).to(dev)),
+                "features_rest_thermal": nn.Parameter(torch.zeros((n, dim_sh - 1, 1), device=dev)),
+            })
         self.step = 0
         self._ws: Optional[Tensor] = None
         self._cap = 0
@@ -369,6 +427,40 @@ class ThermalSplatfactoModel(nn.Module):
         self.noise_generator = torch.Generator(device=dev)  # the split noise (splatfacto.py:541)
         self.noise_generator.manual_seed(seed)
         self.background_generator = torch.Generator().manual_seed(seed)  # background_color "random": host draws, no synchronisation
+
+    def _seeded_params(self, seed_points: Tuple[Tensor, Tensor], g: torch.Generator, dim_sh: int, dev: torch.device) -> nn.ParameterDict:
+        """populate_modules with seed points (splatfacto.py:190-225); the rules are in the class docstring."""
+        xyz, rgb = seed_points
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or rgb.dim() != 2 or rgb.shape[1] != 3:
+            raise ValueError(f"seed_points must be (xyz [M,3], rgb [M,3]), got {tuple(xyz.shape)} and {tuple(rgb.shape)}")
+        n = xyz.shape[0]
+        if n < 4:
+            raise ValueError(f"seed_points: {n} points, the kNN scales need at least 4")
+        if rgb.shape[0] not in (0, n):
+            raise ValueError(f"seed_points: {rgb.shape[0]} colours for {n} points")
+        means = xyz.detach().to(device=dev, dtype=torch.float32).contiguous()
+        distances = knn_distances(means, 3)
+        avg_dist = distances.mean(dim=-1, keepdim=True)
+        scales = torch.log(avg_dist.repeat(1, 3))
+        quats = torch.nn.functional.normalize(torch.randn((n, 4), generator=g), dim=-1).to(dev)
+        if rgb.shape[0] > 0:
+            c = rgb.detach().to(device=dev)
+            if self.config.sh_degree > 0:
+                dc = RGB2SH(c / 255)
+            else:
+                dc = torch.logit(c.double() / 255, eps=1e-10).float()
+        else:
+            dc = torch.rand((n, 3), generator=g).to(dev)
+        return nn.ParameterDict({
+            "means": nn.Parameter(means),
+            "scales": nn.Parameter(scales),
+            "quats": nn.Parameter(quats),
+            "opacities": nn.Parameter(torch.logit(0.1 * torch.ones(n, 1)).to(dev)),
+            "features_dc": nn.Parameter(dc.float().contiguous()),
+            "features_rest": nn.Parameter(torch.zeros((n, dim_sh - 1, 3), device=dev)),
+            "features_dc_thermal": nn.Parameter(torch.zeros((n, 1), device=dev)),
+            "features_rest_thermal": nn.Parameter(torch.zeros((n, dim_sh - 1, 1), device=dev)),
+        })
 
     # the reference's accessors
     @property

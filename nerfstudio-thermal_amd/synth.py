@@ -207,6 +207,28 @@ def cube_scene_images(origins: np.ndarray, directions: np.ndarray, is_thermal: b
     return np.where(hit[:, None], face_rgb[face] * tex[:, None], bg).astype(np.float32)
 
 
+CUBE_FACE_RGB = ((0.9, 0.2, 0.2), (0.2, 0.8, 0.3), (0.2, 0.3, 0.9), (0.9, 0.8, 0.2), (0.8, 0.3, 0.8), (0.2, 0.8, 0.8))  # cube_scene_images' faces
+
+
+def cube_surface_points(num: int, seed: int = 0, half: float = 0.35, jitter: float = 0.005) -> "Tuple[np.ndarray, np.ndarray]":
+    """A sparse point cloud of cube_scene_images' cube, as SfM would give it: `num` points uniform on the six faces (face = 2 * axis + sign, as
+    there), each coloured with its face's RGB texture (uint8), then moved by Gaussian jitter of std `jitter`.  -> xyz [num,3] float32, rgb
+    [num,3] uint8 in the scene's world frame."""
+    g = np.random.default_rng(seed)
+    face = g.integers(0, 6, num)
+    axis, sign = face // 2, face % 2
+    uv = g.uniform(-half, half, (num, 2))
+    p = np.empty((num, 3))
+    rows = np.arange(num)
+    p[rows, axis] = np.where(sign == 1, half, -half)
+    p[rows, (axis + 1) % 3] = uv[:, 0]
+    p[rows, (axis + 2) % 3] = uv[:, 1]
+    tex = 0.8 + 0.2 * np.sin(5.0 * uv[:, 0] / half) * np.sin(5.0 * uv[:, 1] / half)
+    rgb = np.clip(np.rint(np.asarray(CUBE_FACE_RGB)[face] * tex[:, None] * 255.0), 0, 255).astype(np.uint8)
+    xyz = p + g.normal(0.0, jitter, (num, 3))
+    return xyz.astype(np.float32), rgb
+
+
 # ---- thermal-splatfacto (N4): synthetic Gaussians and a look-at camera (inputs of bench.py --workload splat and of the splat tests)
 def synth_gaussians(num: int, seed: int = 0, extent: float = 1.0, scale_range=(-4.5, -2.5)) -> "Dict[str, torch.Tensor]":
     """Deterministic synthetic scene: Gaussians in a cube of half-size `extent`, log-scales uniform in scale_range, random rotations,

@@ -4,7 +4,10 @@ The scene is train_eval_scene.py's (write_cube_scene: RGB 640x480 and thermal 16
 through this package's dataparser.  Training keeps every train frame resident on the device, turns each camera into a PinholeCamera and visits
 the frames in a shuffled order per epoch: get_train_outputs -> get_loss_dict (L1 + SSIM, tn_image_loss) -> backward -> Optimizers(SPLAT_OPTIMIZERS,
 HipAdam) -> the model's training callbacks (SH degree, gradient statistics, refinement).  At the end it reports PSNR / SSIM per spectrum on the
-val split and the time per iteration as one JSON line.  (Camera distortion is ignored: the scene's cameras have none.)"""
+val split and the time per iteration as one JSON line.  (Camera distortion is ignored: the scene's cameras have none.)  With --seed-points N the
+generated scene also gets a sparse point cloud -- N points on the cube's faces with their texture colours plus jitter (synth.cube_surface_points),
+written as the dataset's PLY (transforms.json ply_file_path) -- and the model starts from it as splatfacto does (load_3D_points -> seed_points,
+one Gaussian per point with kNN scales) instead of from --gaussians random ones."""
 import argparse
 import json
 import math
@@ -19,7 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 
 import nerfstudio_thermal_amd  # noqa: E402,F401
-from nerfstudio_thermal_amd.dataparser import ThermalNerfDataParserConfig, load_image_float32  # noqa: E402
+from nerfstudio_thermal_amd import synth  # noqa: E402
+from nerfstudio_thermal_amd.dataparser import ThermalNerfDataParserConfig, load_image_float32, write_ply  # noqa: E402
 from nerfstudio_thermal_amd.model import TrainingCallbackLocation  # noqa: E402
 from nerfstudio_thermal_amd.optim import SPLAT_OPTIMIZERS, HipAdam, Optimizers  # noqa: E402
 from nerfstudio_thermal_amd.splat import PinholeCamera, ThermalSplatfactoModel, ThermalSplatfactoModelConfig  # noqa: E402
@@ -37,6 +41,18 @@ def frames_of(outputs, device):
     return out
 
 
+def add_seed_points(data: str, num: int, seed: int) -> None:
+    """synth.cube_surface_points as <data>/sparse_pc.ply, named by transforms.json's ply_file_path"""
+    xyz, rgb = synth.cube_surface_points(num, seed=seed)
+    write_ply(os.path.join(data, "sparse_pc.ply"), xyz, rgb)
+    path = os.path.join(data, "transforms.json")
+    with open(path, encoding="utf-8") as f:
+        meta = json.load(f)
+    meta["ply_file_path"] = "sparse_pc.ply"
+    with open(path, "w", encoding="utf-8") as f:
+        json.dump(meta, f, indent=4)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", default=None)
@@ -47,7 +63,10 @@ def main():
     ap.add_argument("--ssim-lambda", type=float, default=0.2)
     ap.add_argument("--background", default="random")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--seed-points", type=int, default=0, help="start from N points sampled on the cube's surface (generated scene only)")
     args = ap.parse_args()
+    if args.seed_points and args.data is not None:
+        ap.error("--seed-points samples the generated scene's cube; a dataset on disk brings its own ply_file_path")
     dev = torch.device("cuda", 0)
     tmp = None
     data = args.data
@@ -55,11 +74,18 @@ def main():
         tmp = tempfile.TemporaryDirectory()
         data = tmp.name
         write_cube_scene(data, args.frames, dev)
-    pc = ThermalNerfDataParserConfig(data=data)
-    train, val = frames_of(pc.setup().get_dataparser_outputs("train"), dev), frames_of(pc.setup().get_dataparser_outputs("val"), dev)
+        if args.seed_points:
+            add_seed_points(data, args.seed_points, args.seed)
+    pc = ThermalNerfDataParserConfig(data=data, load_3D_points=bool(args.seed_points))
+    train_out = pc.setup().get_dataparser_outputs("train")
+    train, val = frames_of(train_out, dev), frames_of(pc.setup().get_dataparser_outputs("val"), dev)
+    seed_points = None
+    if args.seed_points:
+        seed_points = (train_out.metadata["points3D_xyz"], train_out.metadata["points3D_rgb"])
     cfg = ThermalSplatfactoModelConfig(num_random=args.gaussians, random_scale=args.init_extent, ssim_lambda=args.ssim_lambda,
                                        background_color=args.background)
-    model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=len(train))
+    model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=len(train), seed_points=seed_points)
+    initial = model.num_points
     opts = Optimizers(model.get_param_groups(), SPLAT_OPTIMIZERS, optimizer_cls=HipAdam)
     cbs = model.get_training_callbacks(opts)
     order_gen = torch.Generator().manual_seed(args.seed)
@@ -94,7 +120,7 @@ def main():
     metrics = {k: sum(v) / len(v) for k, v in sums.items() if all(math.isfinite(x) for x in v)}
     print(json.dumps({"dataset": "synthetic cube scene (train_eval_scene.write_cube_scene)" if tmp else data, "train_images": len(train),
                       "val_images": len(val), "steps": args.steps, "ssim_lambda": args.ssim_lambda, "background_color": args.background,
-                      "initial_gaussians": args.gaussians, "final_gaussians": model.num_points, "train_seconds": train_s,
+                      "initial_gaussians": initial, "seed_points": args.seed_points, "final_gaussians": model.num_points, "train_seconds": train_s,
                       "ms_per_iteration": 1e3 * train_s / max(args.steps, 1), "val_metrics": metrics, "curve": curve}))
 
 
