@@ -65,11 +65,16 @@ def project(means: Tensor, scales: Tensor, quats: Tensor, viewmat: Tensor, projm
 
 
 def rasterize(xys: Tensor, depths: Tensor, radii: Tensor, conics: Tensor, tile_min: Tensor, tile_max: Tensor, colors: Tensor, opacity: Tensor, H: int, W: int,
-              background: Tensor, flag_tol: float = 1e-4):
+              background: Tensor, flag_tol: float = 1e-4, clamp_channels: Optional[int] = None, stats: Optional[Dict[str, Tensor]] = None):
     """so.rasterize_gaussians with out-of-place updates (every Gaussian is evaluated over the whole image and masked to its tile box).
-    Returns the image before the clamp [H,W,C], 1 - T [H,W], the flagged pixels [H,W] and the Gaussians with a flagged pair [N]."""
+    Returns the image before the clamp [H,W,C], 1 - T [H,W], the flagged pixels [H,W] and the Gaussians with a flagged pair [N].
+    clamp_channels: only the first so many channels meet the output clamp (default: all); a depth channel behind them does not.
+    stats: a dict that receives `pair_used` [N, tiles_y, tiles_x] (the Gaussian passed every test at a pixel of the tile that was still
+    running -- the pixel it stops included: what a tile's list must hold) and `stopped` [H,W] (the pixel hit the T <= 1e-4 stop)."""
     dt, N = colors.dtype, colors.shape[0]
     bw = so.BLOCK_WIDTH
+    tby, tbx = (H + bw - 1) // bw, (W + bw - 1) // bw
+    pair_used = torch.zeros(N, tby, tbx, dtype=torch.bool) if stats is not None else None
     order = torch.argsort(depths.detach(), stable=True)
     order = order[radii[order] > 0]
     py, px = torch.meshgrid(torch.arange(H, dtype=dt) + 0.5, torch.arange(W, dtype=dt) + 0.5, indexing="ij")
@@ -92,6 +97,8 @@ def rasterize(xys: Tensor, depths: Tensor, radii: Tensor, conics: Tensor, tile_m
         next_T = T * (1.0 - alpha)
         stop = use & (next_T <= 1e-4)
         with torch.no_grad():
+            if pair_used is not None:
+                pair_used[g] = torch.nn.functional.pad(use, (0, tbx * bw - W, 0, tby * bw - H)).view(tby, bw, tbx, bw).any(3).any(1)
             live = inbox & ~done
             f = live & (((alpha * 255.0 - 1).abs() < flag_tol) | ((raw / 0.999 - 1).abs() < flag_tol) | (use & ((next_T * 1e4 - 1).abs() < 1e2 * flag_tol)))
             flag_pix |= f
@@ -104,16 +111,24 @@ def rasterize(xys: Tensor, depths: Tensor, radii: Tensor, conics: Tensor, tile_m
         T = torch.where(use, next_T, T)
     img = out + T[..., None] * background
     with torch.no_grad():
-        flag_pix |= ((img - 1).abs() < flag_tol).any(-1)
+        flag_pix |= ((img[..., :clamp_channels] - 1).abs() < flag_tol).any(-1)
+        if stats is not None:
+            stats["pair_used"], stats["stopped"] = pair_used, done
     return img, 1.0 - T, flag_pix, flag_g
 
 
 def render(params: Dict[str, Tensor], c2w: Tensor, fx: float, fy: float, cx: float, cy: float, W: int, H: int, sh_degree_to_use: int = 3,
            rasterize_mode: str = "classic", background: Optional[Tensor] = None, background_thermal: float = 0.0, flag_tol: float = 1e-4,
-           viewdir_means: Optional[Tensor] = None) -> Dict[str, Tensor]:
-    """so.render (rgb, thermal, accumulation; no depth) as a differentiable function of `params`, in the dtype of params["means"].
+           viewdir_means: Optional[Tensor] = None, with_depth: bool = False) -> Dict[str, Tensor]:
+    """so.render (rgb, thermal, accumulation) as a differentiable function of `params`, in the dtype of params["means"].
     `raw` is the RGB+T image before the output clamp.  viewdir_means: the means the SH view directions are taken from (default: the means
-    themselves, detached); finite differences pass the unperturbed ones, since the view directions carry no gradient."""
+    themselves, detached); finite differences pass the unperturbed ones, since the view directions carry no gradient.
+    with_depth (the forward tests; no gradient): also `depth` [H,W,1] as tn_splat_raster documents it -- sum(alpha T depth) / accumulation
+    where accumulation > 0, else `depth_fill`, the maximum of the un-normalised image `depth_raw` -- and the walk's statistics:
+    `contributors_per_tile` [tiles_y, tiles_x], `pair_used` [N, tiles_y, tiles_x], `stopped` [H,W], `stopped_fraction`.  "classic": the depth
+    rides the colour walk as a fifth channel (same decisions, the colour arithmetic untouched); "antialiased": as in so.render a SECOND
+    front-to-back walk with the uncompensated opacity, its own transmittance and stop, whose near-threshold decisions are flagged too and
+    whose used pairs count as contributors (the GPU's one list serves both walks); `stopped` is the colour walk's."""
     dt = params["means"].dtype
     background = torch.zeros(3) if background is None else background
     viewmat, projmat = so.camera_matrices(c2w, fx, fy, W, H)
@@ -132,16 +147,36 @@ def render(params: Dict[str, Tensor], c2w: Tensor, fx: float, fy: float, cx: flo
         colors = torch.clamp(sh, min=0.0)
     else:
         colors = torch.sigmoid(torch.cat([col[:, 0], col_t[:, 0]], -1))
-    op = torch.sigmoid(params["opacities"])[:, 0]
+    op_plain = op = torch.sigmoid(params["opacities"])[:, 0]
     if rasterize_mode == "antialiased":
         op = op * pj["compensation"]
     elif rasterize_mode != "classic":
         raise ValueError(f"Unknown rasterize_mode: {rasterize_mode}")
     bg4 = torch.cat([background, torch.tensor([background_thermal])]).to(dt)
-    img, alpha, flag_pix, flag_g = rasterize(pj["xys"], pj["depths"], pj["radii"], pj["conics"], pj["tile_min"], pj["tile_max"], colors, op, H, W, bg4,
-                                             flag_tol=flag_tol)
-    return {"rgb": torch.clamp(img[..., :3], max=1.0), "thermal": torch.clamp(img[..., 3:], max=1.0), "accumulation": alpha[..., None], "raw": img,
-            "xys": pj["xys"], "projection": pj, "flag_pixels": flag_pix, "flag_gaussians": flag_g | (pj["near_clamp"] & pj["ok"]) | (near_sh & pj["ok"])}
+    geom = (pj["xys"], pj["depths"], pj["radii"], pj["conics"], pj["tile_min"], pj["tile_max"])
+    if not with_depth:
+        img, alpha, flag_pix, flag_g = rasterize(*geom, colors, op, H, W, bg4, flag_tol=flag_tol)
+        return {"rgb": torch.clamp(img[..., :3], max=1.0), "thermal": torch.clamp(img[..., 3:], max=1.0), "accumulation": alpha[..., None], "raw": img,
+                "xys": pj["xys"], "projection": pj, "flag_pixels": flag_pix, "flag_gaussians": flag_g | (pj["near_clamp"] & pj["ok"]) | (near_sh & pj["ok"])}
+    with torch.no_grad():
+        st: Dict[str, Tensor] = {}
+        zero1 = torch.zeros(1, dtype=dt)
+        if rasterize_mode == "classic":
+            img5, alpha, flag_pix, flag_g = rasterize(*geom, torch.cat([colors, pj["depths"][:, None]], -1), op, H, W, torch.cat([bg4, zero1]),
+                                                      flag_tol=flag_tol, clamp_channels=4, stats=st)
+            img, depth_raw, pair_used = img5[..., :4], img5[..., 4:], st["pair_used"]
+        else:
+            img, alpha, flag_pix, flag_g = rasterize(*geom, colors, op, H, W, bg4, flag_tol=flag_tol, stats=st)
+            st_d: Dict[str, Tensor] = {}
+            depth_raw, _, fp_d, fg_d = rasterize(*geom, pj["depths"][:, None], op_plain, H, W, zero1, flag_tol=flag_tol, clamp_channels=0, stats=st_d)
+            flag_pix, flag_g, pair_used = flag_pix | fp_d, flag_g | fg_d, st["pair_used"] | st_d["pair_used"]
+        alpha = alpha[..., None]
+        fill = depth_raw.max()
+        depth = torch.where(alpha > 0, depth_raw / alpha, fill)  # splatfacto.py:809
+    return {"rgb": torch.clamp(img[..., :3], max=1.0), "thermal": torch.clamp(img[..., 3:], max=1.0), "accumulation": alpha, "raw": img, "depth": depth,
+            "depth_raw": depth_raw, "depth_fill": fill, "xys": pj["xys"], "projection": pj, "flag_pixels": flag_pix,
+            "flag_gaussians": flag_g | (pj["near_clamp"] & pj["ok"]) | (near_sh & pj["ok"]), "pair_used": pair_used,
+            "contributors_per_tile": pair_used.sum(0), "stopped": st["stopped"], "stopped_fraction": float(st["stopped"].float().mean())}
 
 
 def scene(num: int, seed: int, sh_degree: int, extent: float = 1.0, scale_range=(-3.6, -2.2)) -> Dict[str, Tensor]:
