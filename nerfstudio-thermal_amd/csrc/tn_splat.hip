@@ -22,7 +22,7 @@
 //                      a wave whose 64 pixels are all finished skips the arithmetic; the colour (RGB+T) and depth images come out of ONE
 //                      pass (the reference runs the rasteriser twice; in "antialiased" mode the depth pass uses the uncompensated
 //                      opacity, so that variant carries a second transmittance).  The TRAIN instantiation (tn_splat_raster_train) also
-//                      keeps each pixel's final transmittance and last contributor for the backward at the end of this file.
+//                      keeps each pixel's final transmittance and last contributor for the backward.
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -67,6 +67,12 @@ struct HitsInOrder {  // tiles-per-Gaussian read through the depth order (input 
 
 static size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
+struct Carve {  // hands out the pieces of a workspace, each rounded up to 256 bytes; with a null base it only counts (off = the bytes needed)
+  char* base;
+  size_t off;
+  void* take(size_t bytes) { size_t o = off; off += al256(bytes); return base ? (void*)(base + o) : (void*)nullptr; }
+};
+
 static size_t sort_tmp_bytes(int64_t capacity, int64_t N) {
   size_t a = 0, b = 0, c = 0;
   (void)rocprim::radix_sort_pairs(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (size_t)std::max<int64_t>(capacity, 1 << 20), 0, 32);  // also covers the sort of the tile order (<= 2^20 tiles)
@@ -79,24 +85,22 @@ static size_t sort_tmp_bytes(int64_t capacity, int64_t N) {
 
 static SplatWs splat_layout(void* base, int64_t N, int64_t capacity, int32_t num_tiles, size_t* total) {
   SplatWs w;
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return base ? (void*)(p + o) : (void*)nullptr; };
-  w.recs = (SplatRec*)take(sizeof(SplatRec) * (size_t)N);
-  w.cum = (int32_t*)take(4 * (size_t)N);
-  w.tbox = (int32_t*)take(16 * (size_t)N);
-  w.thits = (int32_t*)take(4 * (size_t)N);
-  w.tile_bins = (int32_t*)take(8 * (size_t)num_tiles);
-  w.depth_max = (uint32_t*)take(256);
-  for (int i = 0; i < 2; ++i) w.lkeys[i] = (uint32_t*)take(4 * (size_t)num_tiles);
-  for (int i = 0; i < 2; ++i) w.lvals[i] = (int32_t*)take(4 * (size_t)num_tiles);
-  w.dkeys = (uint32_t*)take(4 * (size_t)N);
-  w.order = (int32_t*)take(4 * (size_t)N);
-  for (int i = 0; i < 2; ++i) w.keys[i] = (uint32_t*)take(4 * (size_t)capacity);
-  for (int i = 0; i < 2; ++i) w.vals[i] = (int32_t*)take(4 * (size_t)capacity);
+  Carve cv{(char*)base, 0};
+  w.recs = (SplatRec*)cv.take(sizeof(SplatRec) * (size_t)N);
+  w.cum = (int32_t*)cv.take(4 * (size_t)N);
+  w.tbox = (int32_t*)cv.take(16 * (size_t)N);
+  w.thits = (int32_t*)cv.take(4 * (size_t)N);
+  w.tile_bins = (int32_t*)cv.take(8 * (size_t)num_tiles);
+  w.depth_max = (uint32_t*)cv.take(256);
+  for (int i = 0; i < 2; ++i) w.lkeys[i] = (uint32_t*)cv.take(4 * (size_t)num_tiles);
+  for (int i = 0; i < 2; ++i) w.lvals[i] = (int32_t*)cv.take(4 * (size_t)num_tiles);
+  w.dkeys = (uint32_t*)cv.take(4 * (size_t)N);
+  w.order = (int32_t*)cv.take(4 * (size_t)N);
+  for (int i = 0; i < 2; ++i) w.keys[i] = (uint32_t*)cv.take(4 * (size_t)capacity);
+  for (int i = 0; i < 2; ++i) w.vals[i] = (int32_t*)cv.take(4 * (size_t)capacity);
   w.tmp_bytes = sort_tmp_bytes(capacity, N);
-  w.tmp = take(w.tmp_bytes);
-  if (total) *total = off;
+  w.tmp = cv.take(w.tmp_bytes);
+  if (total) *total = cv.off;
   return w;
 }
 
@@ -376,6 +380,30 @@ __global__ void k_splat_tile_len(const int32_t* __restrict__ tile_bins, int num_
 }
 
 // ------------------------------------------------------------------------------------------------ rasteriser
+// The rules k_splat_raster and k_splat_raster_bwd must agree on bit for bit, each written once.  ALL these helpers take and return scalars on
+// purpose: handed a float4 or both axes at once, the compiler packs x and y into v_pk instructions -- the same arithmetic, but no longer the
+// instruction stream the rasteriser was tuned and measured with.  After any change to them, compare both kernels' assembly with the parent's
+// again (profiles/splat_refactor.md).  lane -> pixel: a wave covers one 8x8 QUADRANT of the tile (the squarest 64-pixel footprint: the per-wave
+// culling rejects the most Gaussians for it); 8 lanes = one 128-byte row of the RGBT output.  (qcx, qcy): centre of the quadrant's pixel centres.
+__device__ __forceinline__ bool splat_lane_pixel(int tile_x, int tile_y, int W, int H, int& lane, int& wv, int& ix, int& iy, float& pxf, float& pyf,
+                                                 float& qcx, float& qcy) {
+  lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int qx0 = tile_x * SPLAT_BLOCK + 8 * (wv & 1), qy0 = tile_y * SPLAT_BLOCK + 8 * (wv >> 1);
+  ix = qx0 + (lane & 7), iy = qy0 + (lane >> 3);
+  pxf = (float)ix + 0.5f, pyf = (float)iy + 0.5f;
+  qcx = (float)qx0 + 4.0f, qcy = (float)qy0 + 4.0f;
+  return ix < W && iy < H;  // the pixel is inside the image
+}
+// one axis of the quadrant test: can a Gaussian centred at g with half extent h (k_splat_project's box) reach alpha >= 1/255 around qc?
+__device__ __forceinline__ bool splat_axis_hit(float g, float h, float qc) { return fabsf(g - qc) <= h + 3.5f; }
+// sigma log2(e) at the offset (dx, dy) = centre - pixel; A, B, C as in SplatRec
+__device__ __forceinline__ float splat_power(float A, float B, float Cc, float dx, float dy) { return fmaf(dx, fmaf(A, dx, B * dy), Cc * dy * dy); }
+// alpha before the clamp to 0.999 (the backward passes gradient only where the clamp is inactive); then alpha and the gate on it.  The gate's
+// other half is power >= 0: the forward leaves a lane with power < 0 before the exponential, the backward tests it.
+__device__ __forceinline__ float splat_alpha_raw(float l2op, float power) { return __builtin_amdgcn_exp2f(l2op - power); }
+__device__ __forceinline__ float splat_alpha(float raw) { return fminf(0.999f, raw); }
+__device__ __forceinline__ bool splat_visible(float alpha) { return alpha >= (1.0f / 255.0f); }
+
 // TRAIN: the training variant (tn_splat_raster_train) also leaves what the backward needs per pixel -- the final transmittance and the number
 // of list entries up to and including the last Gaussian that contributed -- and writes the colour BEFORE the clamp to 1 (the caller clamps,
 // so the clamp's gradient mask is the caller's).  TRAIN = false is the eval rasteriser, unchanged.
@@ -389,14 +417,9 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
   __shared__ float smax[4];
   const int tile = tile_order[blockIdx.x];
   const int tile_x = tile % tbx, tile_y = tile / tbx;
-  // lane -> pixel: a wave covers one 8x8 QUADRANT of the tile (the squarest 64-pixel footprint: the per-wave culling below rejects the most
-  // Gaussians for it); 8 lanes = one 128-byte row segment of the RGBT output
-  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int qx0 = tile_x * SPLAT_BLOCK + 8 * (wv & 1), qy0 = tile_y * SPLAT_BLOCK + 8 * (wv >> 1);
-  const int ix = qx0 + (lane & 7), iy = qy0 + (lane >> 3);
-  const bool inside = ix < W && iy < H;
-  const float pxf = (float)ix + 0.5f, pyf = (float)iy + 0.5f;
-  const float qcx = (float)qx0 + 4.0f, qcy = (float)qy0 + 4.0f;  // centre of the quadrant's pixel centres (they span +-3.5 around it)
+  int lane, wv, ix, iy;
+  float pxf, pyf, qcx, qcy;
+  const bool inside = splat_lane_pixel(tile_x, tile_y, W, H, lane, wv, ix, iy, pxf, pyf, qcx, qcy);
   const int begin = tile_bins[2 * tile], end = tile_bins[2 * tile + 1];
   float T = 1.0f, Td = 1.0f;
   f32x2 acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};
@@ -435,7 +458,7 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
       bool keep = false;
       if (kk < n) {
         float4 a = sa[kk], b = sb[kk];
-        keep = fabsf(a.x - qcx) <= b.z + 3.5f && fabsf(a.y - qcy) <= b.w + 3.5f;
+        keep = splat_axis_hit(a.x, b.z, qcx) && splat_axis_hit(a.y, b.w, qcy);
       }
       uint64_t live = __ballot(keep);
       while (live) {
@@ -445,16 +468,17 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
         // measured slower (403 vs 360 us: +11 VALU instructions per Gaussian in a kernel that is VALU-issue bound).
         float4 a = sa[k], b = sb[k];
         float dx = a.x - pxf, dy = a.y - pyf;
-        float power = fmaf(dx, fmaf(a.z, dx, a.w * dy), b.x * dy * dy);  // sigma log2(e)
+        float power = splat_power(a.z, a.w, b.x, dx, dy);
         float ex = b.y - power;
         // nobody in the wave can reach alpha >= 1/255 = 2^-7.994 (or the form is negative): skip the exponential and the blend
         // (antialiased: the depth pass blends with the plain opacity, which is the larger one)
         if (!__any((power >= 0.f && (AA ? sd[k].y - power : ex) >= -8.0f) ? 1 : 0)) continue;
         if (power < 0.f) continue;
-        float alpha = fminf(0.999f, __builtin_amdgcn_exp2f(ex));
-        if (!done && alpha >= (1.0f / 255.0f)) {
+        const float alpha = splat_alpha(splat_alpha_raw(b.y, power));
+        const bool vis_c = splat_visible(alpha);  // (evaluated ahead of the &&: inside it the compiler branches on `done` first)
+        if (!done && vis_c) {
           float nT = fmaf(-alpha, T, T);
-          if (nT <= 1e-4f) done = true;
+          if (nT <= 1e-4f) done = true;  // the pixel stops BEFORE this Gaussian (the backward sees that through `last`)
           else {
             float vis = alpha * T;
             float4 c = sc[k];
@@ -468,8 +492,9 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
         }
         if (AA) {
           float4 d = sd[k];
-          float alpha_d = fminf(0.999f, __builtin_amdgcn_exp2f(d.y - power));
-          if (!done_d && alpha_d >= (1.0f / 255.0f)) {
+          const float alpha_d = splat_alpha(splat_alpha_raw(d.y, power));
+          const bool vis_d = splat_visible(alpha_d);
+          if (!done_d && vis_d) {
             float nT = fmaf(-alpha_d, Td, Td);
             if (nT <= 1e-4f) done_d = true;
             else { dacc = fmaf(alpha_d * Td, d.x, dacc); Td = nT; }
@@ -534,12 +559,10 @@ struct SplatBwdWs {
 
 static SplatBwdWs splat_bwd_layout(void* base, int64_t N, int64_t capacity, size_t* total) {
   SplatBwdWs w;
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return base ? (void*)(p + o) : (void*)nullptr; };
-  w.pair = (float*)take(sizeof(float) * SPLAT_PAIR_GRADS * (size_t)std::max<int64_t>(capacity, 1));
-  w.start = (int32_t*)take(4 * (size_t)std::max<int64_t>(N, 1));
-  if (total) *total = off;
+  Carve cv{(char*)base, 0};
+  w.pair = (float*)cv.take(sizeof(float) * SPLAT_PAIR_GRADS * (size_t)std::max<int64_t>(capacity, 1));
+  w.start = (int32_t*)cv.take(4 * (size_t)std::max<int64_t>(N, 1));
+  if (total) *total = cv.off;
   return w;
 }
 
@@ -569,12 +592,9 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
   __shared__ int s_n;
   const int tile = tile_order[blockIdx.x];
   const int tile_x = tile % tbx, tile_y = tile / tbx;
-  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int qx0 = tile_x * SPLAT_BLOCK + 8 * (wv & 1), qy0 = tile_y * SPLAT_BLOCK + 8 * (wv >> 1);
-  const int ix = qx0 + (lane & 7), iy = qy0 + (lane >> 3);
-  const bool inside = ix < W && iy < H;
-  const float pxf = (float)ix + 0.5f, pyf = (float)iy + 0.5f;
-  const float qcx = (float)qx0 + 4.0f, qcy = (float)qy0 + 4.0f;
+  int lane, wv, ix, iy;
+  float pxf, pyf, qcx, qcy;
+  const bool inside = splat_lane_pixel(tile_x, tile_y, W, H, lane, wv, ix, iy, pxf, pyf, qcx, qcy);
   const int begin = tile_bins[2 * tile];
   // T: transmittance after the Gaussian being visited (starts at the final one); rest: sum over the Gaussians behind it of
   // alpha_j T_j <colour_j, v> plus the background's T_final <bg, v> - T_final d accumulation (accumulation = 1 - T_final)
@@ -619,20 +639,20 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
       bool keep = false;
       if (kk < cnt && lo + kk < begin + wn) {
         float4 a = sa[kk], b = sb[kk];
-        keep = fabsf(a.x - qcx) <= b.z + 3.5f && fabsf(a.y - qcy) <= b.w + 3.5f;
+        keep = splat_axis_hit(a.x, b.z, qcx) && splat_axis_hit(a.y, b.w, qcy);
       }
       uint64_t live = __ballot(keep);
       while (live) {
         const int bit = 63 - __builtin_clzll(live);
         live &= ~(1ull << bit);
         const int k = q * 64 + bit;
-        // the forward's arithmetic, bit for bit: the same set of contributors
+        // the forward's rules (the helpers above): the same set of contributors
         const float4 a = sa[k], b = sb[k];
         const float dx = a.x - pxf, dy = a.y - pyf;
-        const float power = fmaf(dx, fmaf(a.z, dx, a.w * dy), b.x * dy * dy);
-        const float raw = __builtin_amdgcn_exp2f(b.y - power);
-        const float alpha = fminf(0.999f, raw);
-        const bool use = lo + k - begin < n && power >= 0.f && alpha >= (1.0f / 255.0f);
+        const float power = splat_power(a.z, a.w, b.x, dx, dy);
+        const float raw = splat_alpha_raw(b.y, power);
+        const float alpha = splat_alpha(raw);
+        const bool use = lo + k - begin < n && power >= 0.f && splat_visible(alpha);
         if (!__any(use ? 1 : 0)) continue;
         float g[SPLAT_PAIR_GRADS];
 #pragma unroll
@@ -1006,26 +1026,32 @@ extern "C" int tn_splat_bin(const TnSplatCamera* camera, const float* depths, in
   return TN_OK;
 }
 
+// The raster of both entry points below: AA x TRAIN dispatch (TRAIN = the caller wants the transmittance and last-contributor images), then
+// the depth normalisation.  `who` / `who_depth` name the entry point's two launches in error messages.
+static int splat_raster(const char* who, const char* who_depth, const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                        const float* background4, int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, float* out_T, int32_t* out_last,
+                        tn_stream_t stream) {
+  SplatCamK k = make_camk(camera);
+  SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, k.tbx * k.tby, nullptr);
+  float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
+  hipStream_t st = tn_s(stream);
+  auto kernel = antialiased ? (out_T ? k_splat_raster<true, true> : k_splat_raster<true, false>) : (out_T ? k_splat_raster<false, true> : k_splat_raster<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, out_rgbt, out_depth,
+                     out_alpha, ws.depth_max, out_T, out_last);
+  TN_CHECK_LAUNCH(who);
+  int64_t n = (int64_t)k.W * k.H;
+  hipLaunchKernelGGL(k_splat_depth_finalize, dim3((unsigned)tn_cdiv(n, 256)), dim3(256), 0, st, out_depth, out_alpha, ws.depth_max, n);
+  TN_CHECK_LAUNCH(who_depth);
+  return TN_OK;
+}
+
 extern "C" int tn_splat_raster(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections, const float* background4,
                                int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, tn_stream_t stream) {
   int rc = check_cam(camera, "tn_splat_raster");
   if (rc) return rc;
   TN_REQUIRE(workspace && background4 && out_rgbt && out_depth && out_alpha, "tn_splat_raster: null pointer");
-  SplatCamK k = make_camk(camera);
-  SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, k.tbx * k.tby, nullptr);
-  float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
-  hipStream_t st = tn_s(stream);
-  if (antialiased)
-    hipLaunchKernelGGL((k_splat_raster<true, false>), dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, out_rgbt, out_depth,
-                       out_alpha, ws.depth_max, nullptr, nullptr);
-  else
-    hipLaunchKernelGGL((k_splat_raster<false, false>), dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, out_rgbt, out_depth,
-                       out_alpha, ws.depth_max, nullptr, nullptr);
-  TN_CHECK_LAUNCH("tn_splat_raster");
-  int64_t n = (int64_t)k.W * k.H;
-  hipLaunchKernelGGL(k_splat_depth_finalize, dim3((unsigned)tn_cdiv(n, 256)), dim3(256), 0, st, out_depth, out_alpha, ws.depth_max, n);
-  TN_CHECK_LAUNCH("tn_splat_raster(depth)");
-  return TN_OK;
+  return splat_raster("tn_splat_raster", "tn_splat_raster(depth)", camera, num_gaussians, workspace, max_intersections, background4, antialiased, out_rgbt, out_depth, out_alpha, nullptr,
+                      nullptr, stream);
 }
 
 extern "C" int tn_splat_raster_train(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
@@ -1035,21 +1061,8 @@ extern "C" int tn_splat_raster_train(const TnSplatCamera* camera, int64_t num_ga
   if (rc) return rc;
   TN_REQUIRE(workspace && background4 && out_rgbt && out_depth && out_alpha && out_transmittance && out_last, "tn_splat_raster_train: null pointer");
   TN_REQUIRE(num_gaussians >= 0 && max_intersections >= 0, "tn_splat_raster_train: bad sizes");
-  SplatCamK k = make_camk(camera);
-  SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, k.tbx * k.tby, nullptr);
-  float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
-  hipStream_t st = tn_s(stream);
-  if (antialiased)
-    hipLaunchKernelGGL((k_splat_raster<true, true>), dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg,
-                       out_rgbt, out_depth, out_alpha, ws.depth_max, out_transmittance, out_last);
-  else
-    hipLaunchKernelGGL((k_splat_raster<false, true>), dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg,
-                       out_rgbt, out_depth, out_alpha, ws.depth_max, out_transmittance, out_last);
-  TN_CHECK_LAUNCH("tn_splat_raster_train");
-  int64_t n = (int64_t)k.W * k.H;
-  hipLaunchKernelGGL(k_splat_depth_finalize, dim3((unsigned)tn_cdiv(n, 256)), dim3(256), 0, st, out_depth, out_alpha, ws.depth_max, n);
-  TN_CHECK_LAUNCH("tn_splat_raster_train(depth)");
-  return TN_OK;
+  return splat_raster("tn_splat_raster_train", "tn_splat_raster_train(depth)", camera, num_gaussians, workspace, max_intersections, background4, antialiased, out_rgbt, out_depth, out_alpha,
+                      out_transmittance, out_last, stream);
 }
 
 extern "C" int tn_splat_raster_backward(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
@@ -1156,18 +1169,16 @@ struct RefineWs {
 
 static RefineWs refine_layout(void* base, int64_t N, int32_t S, size_t* total) {
   RefineWs w;
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return base ? (void*)(p + o) : (void*)nullptr; };
+  Carve cv{(char*)base, 0};
   const size_t n = (size_t)std::max<int64_t>(N, 1);
-  w.cnt = (RefCnt*)take(sizeof(RefCnt) * n);
-  w.incl = (RefCnt*)take(sizeof(RefCnt) * n);
-  w.map = (int2*)take(sizeof(int2) * n * (size_t)(S + 2));
+  w.cnt = (RefCnt*)cv.take(sizeof(RefCnt) * n);
+  w.incl = (RefCnt*)cv.take(sizeof(RefCnt) * n);
+  w.map = (int2*)cv.take(sizeof(int2) * n * (size_t)(S + 2));
   size_t b = 0;
   (void)rocprim::inclusive_scan(nullptr, b, (const RefCnt*)nullptr, (RefCnt*)nullptr, n, RefCntSum());
   w.tmp_bytes = al256(b) + 256;
-  w.tmp = take(w.tmp_bytes);
-  if (total) *total = off;
+  w.tmp = cv.take(w.tmp_bytes);
+  if (total) *total = cv.off;
   return w;
 }
 

@@ -255,76 +255,91 @@ GROUP_PARAMS = {"xyz": "means", "features_dc": "features_dc", "features_rest": "
                 "rotation": "quats", "features_dc_thermal": "features_dc_thermal", "features_rest_thermal": "features_rest_thermal"}
 
 
+def _param_ptrs(tensors) -> list:
+    """Pointers of eight tensors laid out as the gauss_params, in _PARAM_NAMES order, as the C entry points take them: without higher-order SH
+    coefficients (K == 0) the two features_rest tensors are null, and opacities [N,1] goes in flat."""
+    K = tensors[5].shape[1]
+    pp = [_ptr(t, torch.float32, n) if (K or not n.startswith("features_rest")) else None for t, n in zip(tensors, _PARAM_NAMES)]
+    pp[3] = _ptr(tensors[3].reshape(-1), torch.float32, "opacities")
+    return pp
+
+
+def _project_and_bin(model, cam, params, H: int, W: int, deg: int, aa: int, cap: int, workspace):
+    """One frame's tn_splat_project -> tn_splat_bin into `workspace(N, cap, tiles)`, a buffer for `cap` (Gaussian, tile) pairs: the caller says
+    where it comes from.  A frame with more pairs grows `cap` once and is redone.  Leaves `last_projection` / `last_num_intersections` on the model
+    and returns (projection tensors, workspace, cap, pairs).  No Gaussians: nothing to project, no workspace (None), the frame is the background."""
+    i32 = torch.int32
+    lib = _lib.load()
+    N, K, dev = params[0].shape[0], params[5].shape[1], params[0].device
+    tiles = ((W + BLOCK_WIDTH - 1) // BLOCK_WIDTH) * ((H + BLOCK_WIDTH - 1) // BLOCK_WIDTH)
+    proj = {"xys": torch.empty((N, 2), device=dev), "depths": torch.empty((N,), device=dev), "radii": torch.empty((N,), dtype=i32, device=dev),
+            "conics": torch.empty((N, 3), device=dev), "compensation": torch.empty((N,), device=dev),
+            "num_tiles_hit": torch.empty((N,), dtype=i32, device=dev), "tile_box": torch.empty((N, 4), dtype=i32, device=dev)}
+    ws, total = None, C.c_int64(0)
+    for attempt in range(2 if N > 0 else 0):
+        out_ptrs = [_ptr(t, t.dtype, k) for k, t in proj.items()]
+        ws = workspace(N, cap, tiles)
+        wsp = C.c_void_p(ws.data_ptr())
+        _lib.check(lib.tn_splat_project(C.byref(cam), *_param_ptrs(params), N, K, deg, aa, *out_ptrs, wsp, cap, _stream()), "tn_splat_project")
+        rc = lib.tn_splat_bin(C.byref(cam), out_ptrs[1], N, wsp, cap, C.byref(total), _stream())
+        if rc == 0:
+            break
+        if attempt == 0 and total.value > cap:  # more (Gaussian, tile) pairs than the workspace holds: grow once and redo the frame
+            cap = int(total.value * 1.25) + 1024
+            continue
+        _lib.check(rc, "tn_splat_bin")
+    model.last_projection = proj
+    model.last_num_intersections = int(total.value)
+    return proj, ws, cap, int(total.value)
+
+
+def _outputs(rgb: Tensor, thermal: Tensor, depth: Tensor, accumulation: Tensor, bgl: List[float]) -> Dict[str, Tensor]:
+    dev = rgb.device
+    return {"rgb": rgb, "thermal": thermal, "depth": depth, "accumulation": accumulation, "background": torch.tensor(bgl[:3]).to(dev),
+            "background_thermal": torch.tensor(bgl[3:], device=dev)}
+
+
+def _background_outputs(H: int, W: int, bgl: List[float], dev) -> Dict[str, Tensor]:
+    """Nothing to render (splatfacto.py:759-764): the background, depth 10, no accumulation."""
+    return _outputs(torch.tensor(bgl[:3]).to(dev).repeat(H, W, 1), torch.full((H, W, 1), bgl[3], device=dev), torch.full((H, W, 1), 10.0, device=dev),
+                    torch.zeros((H, W, 1), device=dev), bgl)
+
+
 class _SplatRender(torch.autograd.Function):
     """project -> bin -> training raster; backward = raster backward -> projection backward.  Inputs after `frame` are the gauss_params in
     _PARAM_NAMES order; outputs: colour before the clamp [H,W,4] (RGB + thermal over the background), accumulation [H,W,1], depth [H,W,1]
     (not differentiable)."""
 
     @staticmethod
-    def forward(ctx, frame, means, scales, quats, opacities, features_dc, features_rest, features_dc_thermal, features_rest_thermal):
+    def forward(ctx, frame, *params):
         model, camera = frame["model"], frame["camera"]
         f32, i32 = torch.float32, torch.int32
-        lib = _lib.load()
-        cam, N, H, W = frame["cam"], means.shape[0], int(camera.height), int(camera.width)
-        K, deg, aa, bg4 = features_rest.shape[1], frame["deg"], frame["aa"], frame["bg4"]
-        dev = means.device
-        tiles = ((W + BLOCK_WIDTH - 1) // BLOCK_WIDTH) * ((H + BLOCK_WIDTH - 1) // BLOCK_WIDTH)
-        opac = opacities.reshape(-1)
-        xys = torch.empty((N, 2), device=dev)
-        depths = torch.empty((N,), device=dev)
-        radii = torch.empty((N,), dtype=i32, device=dev)
-        conics = torch.empty((N, 3), device=dev)
-        comp = torch.empty((N,), device=dev)
-        hit = torch.empty((N,), dtype=i32, device=dev)
-        box = torch.empty((N, 4), dtype=i32, device=dev)
-        cap = max(model._train_cap, 1 << 16)
-        total = C.c_int64(0)
-        for attempt in range(2 if N > 0 else 0):  # (no Gaussians: nothing to project, the frame is the background)
-            # a workspace of this frame's own: the backward reads it after other frames may have been rendered
-            need = int(lib.tn_splat_workspace_bytes(N, cap, tiles))
-            if need < 0:
-                raise RuntimeError("tn_splat_workspace_bytes: bad sizes")
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            wsp = C.c_void_p(ws.data_ptr())
-            _lib.check(lib.tn_splat_project(C.byref(cam), _ptr(means, f32, "means"), _ptr(scales, f32, "scales"), _ptr(quats, f32, "quats"),
-                                            _ptr(opac, f32, "opacities"), _ptr(features_dc, f32, "features_dc"),
-                                            _ptr(features_rest, f32, "features_rest") if K else None,
-                                            _ptr(features_dc_thermal, f32, "features_dc_thermal"),
-                                            _ptr(features_rest_thermal, f32, "features_rest_thermal") if K else None, N, K, deg, aa,
-                                            _ptr(xys, f32, "xys"), _ptr(depths, f32, "depths"), _ptr(radii, i32, "radii"), _ptr(conics, f32, "conics"),
-                                            _ptr(comp, f32, "compensation"), _ptr(hit, i32, "num_tiles_hit"), _ptr(box, i32, "tile_box"), wsp, cap, _stream()),
-                       "tn_splat_project")
-            rc = lib.tn_splat_bin(C.byref(cam), _ptr(depths, f32, "depths"), N, wsp, cap, C.byref(total), _stream())
-            if rc == 0:
-                break
-            if attempt == 0 and total.value > cap:  # more (Gaussian, tile) pairs than the workspace holds: grow once and redo the frame
-                cap = int(total.value * 1.25) + 1024
-                continue
-            _lib.check(rc, "tn_splat_bin")
+        cam, N, H, W = frame["cam"], params[0].shape[0], int(camera.height), int(camera.width)
+        aa, bg4, dev = frame["aa"], frame["bg4"], params[0].device
+        # a workspace of this frame's own: the backward reads it after other frames may have been rendered
+        proj, ws, cap, total = _project_and_bin(model, cam, params, H, W, frame["deg"], aa, max(model._train_cap, 1 << 16), model._new_workspace)
         model._train_cap = cap
-        model.last_projection = {"xys": xys, "depths": depths, "radii": radii, "conics": conics, "compensation": comp, "num_tiles_hit": hit, "tile_box": box}
-        model.last_num_intersections = int(total.value)
         # what after_train reads of the training frame (the reference's self.radii / self.last_size); eval renders leave these alone
-        model.last_radii, model.last_size = radii, (H, W)
-        ctx.frame, ctx.empty = frame, total.value == 0
-        if total.value == 0:  # nothing on screen: the background, and zero gradients
+        model.last_radii, model.last_size = proj["radii"], (H, W)
+        ctx.frame, ctx.empty = frame, total == 0
+        if total == 0:  # nothing on screen: the background, and zero gradients
             rgbt = torch.tensor(list(bg4), device=dev).repeat(H, W, 1)
             alpha = torch.zeros((H, W, 1), device=dev)
             depth = torch.full((H, W, 1), 10.0, device=dev)
             ctx.mark_non_differentiable(depth)
-            ctx.save_for_backward(means, scales, quats, opacities, features_dc, features_rest, features_dc_thermal, features_rest_thermal)
+            ctx.save_for_backward(*params)
             return rgbt, alpha, depth
         rgbt = torch.empty((H, W, 4), device=dev)
         depth = torch.empty((H, W, 1), device=dev)
         alpha = torch.empty((H, W, 1), device=dev)
         final_t = torch.empty((H, W), device=dev)
         last = torch.empty((H, W), dtype=i32, device=dev)
-        _lib.check(lib.tn_splat_raster_train(C.byref(cam), N, wsp, cap, bg4, aa, _ptr(rgbt, f32, "rgbt"), _ptr(depth, f32, "depth"), _ptr(alpha, f32, "alpha"),
-                                             _ptr(final_t, f32, "transmittance"), _ptr(last, i32, "last"), _stream()), "tn_splat_raster_train")
+        _lib.check(_lib.load().tn_splat_raster_train(C.byref(cam), N, C.c_void_p(ws.data_ptr()), cap, bg4, aa, _ptr(rgbt, f32, "rgbt"), _ptr(depth, f32, "depth"),
+                                                     _ptr(alpha, f32, "alpha"), _ptr(final_t, f32, "transmittance"), _ptr(last, i32, "last"), _stream()),
+                   "tn_splat_raster_train")
         ctx.mark_non_differentiable(depth)
-        ctx.ws, ctx.cap, ctx.total = ws, cap, int(total.value)
-        ctx.save_for_backward(means, scales, quats, opacities, features_dc, features_rest, features_dc_thermal, features_rest_thermal, radii, conics,
-                              final_t, last)
+        ctx.ws, ctx.cap, ctx.total = ws, cap, total
+        ctx.save_for_backward(*params, proj["radii"], proj["conics"], final_t, last)
         return rgbt, alpha, depth
 
     @staticmethod
@@ -357,14 +372,9 @@ class _SplatRender(torch.autograd.Function):
                                                 _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"), _ptr(v_lnop, f32, "v_log_opacity"), _stream()),
                    "tn_splat_raster_backward")
         grads = [torch.empty_like(p) for p in params]
-        K = params[5].shape[1]
-        names = ("means", "scales", "quats", "opacities", "features_dc", "features_rest", "features_dc_thermal", "features_rest_thermal")
-        pp = [_ptr(p, f32, n) if (K or n not in ("features_rest", "features_rest_thermal")) else None for p, n in zip(params, names)]
-        pp[3] = _ptr(params[3].reshape(-1), f32, "opacities")
-        gp = [_ptr(g, f32, "grad") if (K or n not in ("features_rest", "features_rest_thermal")) else None for g, n in zip(grads, names)]
-        _lib.check(lib.tn_splat_project_backward(C.byref(cam), *pp, N, K, deg, aa, _ptr(radii, torch.int32, "radii"), _ptr(v_xys, f32, "v_xys"),
-                                                 _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"), _ptr(v_lnop, f32, "v_log_opacity"), *gp,
-                                                 _stream()), "tn_splat_project_backward")
+        _lib.check(lib.tn_splat_project_backward(C.byref(cam), *_param_ptrs(params), N, params[5].shape[1], deg, aa, _ptr(radii, torch.int32, "radii"),
+                                                 _ptr(v_xys, f32, "v_xys"), _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"),
+                                                 _ptr(v_lnop, f32, "v_log_opacity"), *_param_ptrs(grads), _stream()), "tn_splat_project_backward")
         model.last_xys_grad = v_xys
         return (None,) + tuple(grads)
 
@@ -486,108 +496,67 @@ class ThermalSplatfactoModel(nn.Module):
         v = 1.0 if cfg.background_color == "white" else 0.0
         return [v, v, v, float(cfg.background_thermal)]
 
-    def _workspace(self, n: int, cap: int, tiles: int) -> Tensor:
+    def _workspace_bytes(self, n: int, cap: int, tiles: int) -> int:
         need = int(_lib.load().tn_splat_workspace_bytes(n, cap, tiles))
         if need < 0:
             raise RuntimeError("tn_splat_workspace_bytes: bad sizes")
+        return need
+
+    def _new_workspace(self, n: int, cap: int, tiles: int) -> Tensor:
+        return torch.empty(self._workspace_bytes(n, cap, tiles), dtype=torch.uint8, device=self.means.device)
+
+    def _workspace(self, n: int, cap: int, tiles: int) -> Tensor:
+        """The eval render's workspace, kept between frames (`_ws`, for `_cap` pairs) while it is large enough."""
+        need = self._workspace_bytes(n, cap, tiles)
         if self._ws is None or self._ws.numel() < need or self._cap != cap:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.means.device)
             self._cap = cap
         return self._ws
 
+    def _frame_settings(self) -> Tuple[int, int]:
+        """(antialiased flag, SH degree at this step) of a frame rendered now (splatfacto.py:772; sh_degree == 0 -> -1: sigmoid of the DC
+        term, :776-777)."""
+        cfg = self.config
+        if cfg.rasterize_mode not in ("classic", "antialiased"):
+            raise ValueError(f"Unknown rasterize_mode: {cfg.rasterize_mode}")
+        return int(cfg.rasterize_mode == "antialiased"), min(self.step // cfg.sh_degree_interval, cfg.sh_degree) if cfg.sh_degree > 0 else -1
+
     @torch.no_grad()
     def get_outputs(self, camera: PinholeCamera) -> Dict[str, Tensor]:
         """splatfacto.py:659-822 (eval mode, no crop box): project -> SH colours -> tile binning -> raster (colour + depth in one pass).
         Returns rgb [H,W,3], thermal [H,W,1], depth [H,W,1], accumulation [H,W,1], background [3], background_thermal [1]."""
-        cfg = self.config
-        lib = _lib.load()
-        gp = self.gauss_params
-        dev = gp["means"].device
+        dev = self.means.device
         N, H, W = self.num_points, int(camera.height), int(camera.width)
-        if cfg.rasterize_mode not in ("classic", "antialiased"):
-            raise ValueError(f"Unknown rasterize_mode: {cfg.rasterize_mode}")
-        aa = int(cfg.rasterize_mode == "antialiased")
+        aa, deg = self._frame_settings()
         bgl = self._background4(training=False)
-        bg = torch.tensor(bgl[:3])
-        bg_th = torch.tensor(bgl[3:], device=dev)
-        if N == 0:  # every Gaussian culled: the background (splatfacto.py:759-764)
-            background = bg.to(dev)
-            return {"rgb": background.repeat(H, W, 1), "thermal": torch.full((H, W, 1), bgl[3], device=dev),
-                    "depth": torch.full((H, W, 1), 10.0, device=dev), "accumulation": torch.zeros((H, W, 1), device=dev), "background": background,
-                    "background_thermal": bg_th}
+        if N == 0:  # every Gaussian culled: the background (splatfacto.py:759-764); last_projection stays what it was
+            return _background_outputs(H, W, bgl, dev)
         cam = camera_struct(camera)
-        tiles = ((W + BLOCK_WIDTH - 1) // BLOCK_WIDTH) * ((H + BLOCK_WIDTH - 1) // BLOCK_WIDTH)
-        K = gp["features_rest"].shape[1]
-        # degree evaluated at this step (splatfacto.py:772); sh_degree == 0 -> sigmoid of the DC term (:776-777)
-        deg = min(self.step // cfg.sh_degree_interval, cfg.sh_degree) if cfg.sh_degree > 0 else -1
-        xys = torch.empty((N, 2), device=dev)
-        depths = torch.empty((N,), device=dev)
-        radii = torch.empty((N,), dtype=torch.int32, device=dev)
-        conics = torch.empty((N, 3), device=dev)
-        comp = torch.empty((N,), device=dev)
-        hit = torch.empty((N,), dtype=torch.int32, device=dev)
-        box = torch.empty((N, 4), dtype=torch.int32, device=dev)
-        cap = max(self._cap, 1 << 16)
-        f32, i32 = torch.float32, torch.int32
-        opac = gp["opacities"].reshape(-1)
-        total = C.c_int64(0)
-        for attempt in range(2):
-            ws = self._workspace(N, cap, tiles)
-            wsp = C.c_void_p(ws.data_ptr())
-            _lib.check(lib.tn_splat_project(C.byref(cam), _ptr(gp["means"], f32, "means"), _ptr(gp["scales"], f32, "scales"), _ptr(gp["quats"], f32, "quats"),
-                                            _ptr(opac, f32, "opacities"), _ptr(gp["features_dc"], f32, "features_dc"),
-                                            _ptr(gp["features_rest"], f32, "features_rest") if K else None,
-                                            _ptr(gp["features_dc_thermal"], f32, "features_dc_thermal"),
-                                            _ptr(gp["features_rest_thermal"], f32, "features_rest_thermal") if K else None, N, K, deg, aa,
-                                            _ptr(xys, f32, "xys"), _ptr(depths, f32, "depths"), _ptr(radii, i32, "radii"), _ptr(conics, f32, "conics"),
-                                            _ptr(comp, f32, "compensation"), _ptr(hit, i32, "num_tiles_hit"), _ptr(box, i32, "tile_box"), wsp, cap, _stream()),
-                       "tn_splat_project")
-            rc = lib.tn_splat_bin(C.byref(cam), _ptr(depths, f32, "depths"), N, wsp, cap, C.byref(total), _stream())
-            if rc == 0:
-                break
-            if attempt == 0 and total.value > cap:  # the workspace was sized for fewer (Gaussian, tile) pairs: grow once and redo the frame
-                cap = int(total.value * 1.25) + 1024
-                continue
-            _lib.check(rc, "tn_splat_bin")
-        self.last_projection = {"xys": xys, "depths": depths, "radii": radii, "conics": conics, "compensation": comp, "num_tiles_hit": hit, "tile_box": box}
-        self.last_num_intersections = int(total.value)
-        background = bg.to(dev)
-        if total.value == 0:  # nothing on screen (splatfacto.py:759-764)
-            return {"rgb": background.repeat(H, W, 1), "thermal": torch.full((H, W, 1), bgl[3], device=dev),
-                    "depth": torch.full((H, W, 1), 10.0, device=dev), "accumulation": torch.zeros((H, W, 1), device=dev), "background": background,
-                    "background_thermal": bg_th}
+        params = [self.gauss_params[k] for k in _PARAM_NAMES]
+        _, ws, cap, total = _project_and_bin(self, cam, params, H, W, deg, aa, max(self._cap, 1 << 16), self._workspace)
+        if total == 0:  # nothing on screen
+            return _background_outputs(H, W, bgl, dev)
+        f32 = torch.float32
         rgbt = torch.empty((H, W, 4), device=dev)
         depth = torch.empty((H, W, 1), device=dev)
         alpha = torch.empty((H, W, 1), device=dev)
-        bg4 = (C.c_float * 4)(float(bg[0]), float(bg[1]), float(bg[2]), bgl[3])
-        _lib.check(lib.tn_splat_raster(C.byref(cam), N, C.c_void_p(self._ws.data_ptr()), cap, bg4, aa, _ptr(rgbt, f32, "rgbt"), _ptr(depth, f32, "depth"),
-                                       _ptr(alpha, f32, "alpha"), _stream()), "tn_splat_raster")
-        return {"rgb": rgbt[..., :3], "thermal": rgbt[..., 3:], "depth": depth, "accumulation": alpha, "background": background,
-                "background_thermal": bg_th}
+        _lib.check(_lib.load().tn_splat_raster(C.byref(cam), N, C.c_void_p(ws.data_ptr()), cap, (C.c_float * 4)(*bgl), aa, _ptr(rgbt, f32, "rgbt"),
+                                               _ptr(depth, f32, "depth"), _ptr(alpha, f32, "alpha"), _stream()), "tn_splat_raster")
+        return _outputs(rgbt[..., :3], rgbt[..., 3:], depth, alpha, bgl)
 
     def get_train_outputs(self, camera: PinholeCamera) -> Dict[str, Tensor]:
         """The render of get_outputs as a differentiable function of every gauss_params tensor (splatfacto.py:659-822 in training, without
         the crop box).  rgb [H,W,3], thermal [H,W,1] and accumulation [H,W,1] carry gradients; depth [H,W,1] is detached.  With a fixed
         background the values equal get_outputs' bit for bit; background_color "random" draws this frame's RGB + thermal background from the
         model's generator (background [3], background_thermal [1]).  After backward(), `last_xys_grad` [N,2] holds dL/d xys per Gaussian."""
-        cfg = self.config
-        if cfg.rasterize_mode not in ("classic", "antialiased"):
-            raise ValueError(f"Unknown rasterize_mode: {cfg.rasterize_mode}")
-        gp = self.gauss_params
-        dev = gp["means"].device
+        aa, deg = self._frame_settings()
         bgl = self._background4(training=True)
-        bg = torch.tensor(bgl[:3])
-        frame = {"model": self, "camera": camera, "cam": camera_struct(camera), "aa": int(cfg.rasterize_mode == "antialiased"),
-                 "deg": min(self.step // cfg.sh_degree_interval, cfg.sh_degree) if cfg.sh_degree > 0 else -1,
-                 "bg4": (C.c_float * 4)(*bgl)}
+        frame = {"model": self, "camera": camera, "cam": camera_struct(camera), "aa": aa, "deg": deg, "bg4": (C.c_float * 4)(*bgl)}
         self.last_xys_grad = None
-        rgbt, alpha, depth = _SplatRender.apply(frame, *(gp[k] for k in _PARAM_NAMES))
-        background, bg_th = bg.to(dev), torch.tensor(bgl[3:], device=dev)
+        rgbt, alpha, depth = _SplatRender.apply(frame, *(self.gauss_params[k] for k in _PARAM_NAMES))
         if self.last_num_intersections == 0:  # the background as get_outputs returns it (no clamp)
-            return {"rgb": rgbt[..., :3], "thermal": rgbt[..., 3:], "depth": depth, "accumulation": alpha, "background": background,
-                    "background_thermal": bg_th}
-        return {"rgb": torch.clamp(rgbt[..., :3], max=1.0), "thermal": torch.clamp(rgbt[..., 3:], max=1.0), "depth": depth, "accumulation": alpha,
-                "background": background, "background_thermal": bg_th}
+            return _outputs(rgbt[..., :3], rgbt[..., 3:], depth, alpha, bgl)
+        return _outputs(torch.clamp(rgbt[..., :3], max=1.0), torch.clamp(rgbt[..., 3:], max=1.0), depth, alpha, bgl)
 
     # ------------------------------------------------------------------------------------------------ loss and metrics (splatfacto.py:824-934)
     def get_gt_img(self, image: Tensor) -> Tensor:
