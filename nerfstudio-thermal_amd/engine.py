@@ -60,6 +60,28 @@ class Branch:
     prop_grad: bool
     fwd_buf: Optional[Tensor] = None  # the one buffer of tn_render_rays_train (fused training forward): what tn_render_rays_train_bwd reads
     prop_enc_saved: bool = False      # ... and it holds the proposal levels' encodings (forward ran with save_prop_enc)
+    d_origins: Optional[Tensor] = None     # [N,3] gradient of the pose-corrected rays, summed by the backward launches (None: no pose to refine)
+    d_directions: Optional[Tensor] = None  # [N,3]
+    pose_done: bool = False                # the pose gradient was finished early (data-parallel schedule, step without a proposal update)
+
+
+@dataclass
+class BranchNets:
+    """What one spectrum branch (suffix "" = RGB / shared, "_thermal") trains and where it lives: every per-branch choice of the step is a
+    lookup here.  The tensors are the engine's own (RenderEngine.props, .field, .pose, ... are aliases of the same objects)."""
+
+    sfx: str
+    props: List["ops.PropNetParams"]
+    field: "ops.FieldParams"
+    pose: Optional[Tensor]       # camera optimiser's pose_adjustment [C,6], None with mode "off"
+    pose_grad: Optional[Tensor]
+    frozen: Tensor               # [C] uint8: cameras this branch's camera optimiser leaves alone
+    cam_opt: object              # CameraOptimizerConfig (penalties of the regulariser)
+    reg_slot: int                # index of the camera regulariser in the loss vector: 11 / 12
+    g_fields: str                # optimiser group names
+    g_props: str
+    g_camera: str
+    table_key: str               # arena key of the main hash table
 
 
 def exp_decay_lr(step: int, lr_init: float, lr_final: float, max_steps: int) -> float:
@@ -87,17 +109,27 @@ class RenderEngine:
         self.device = dev
         self.separate = cfg.density_mode == "separate"
         th = torch.tensor([1 if x != 0 else 0 for x in is_thermal_cam], dtype=torch.uint8)
-        # camera_optimizer: thermal cameras are non-trainable; camera_optimizer_thermal: RGB cameras are (models/thermal_nerfacto.py:132-144)
-        self.frozen_rgb = th.to(dev)
-        self.frozen_thermal = (1 - th).to(dev)
-        self.props = [prop_params(arena, "proposal_networks", i, cfg, with_grads=True) for i in range(2)]
-        self.field = field_params(arena, "field", cfg, with_grads=True)
-        self.props_thermal = [prop_params(arena, "proposal_networks_thermal", i, cfg, with_grads=True) for i in range(2)]
-        self.field_thermal = field_params(arena, "field_thermal", cfg, with_grads=True) if self.separate else None
-        self.pose = arena.view("camera_optimizer.pose_adjustment") if cfg.camera_optimizer.mode != "off" else None
-        self.pose_grad = arena.grad_view("camera_optimizer.pose_adjustment") if self.pose is not None else None
-        self.pose_thermal = arena.view("camera_optimizer_thermal.pose_adjustment") if cfg.camera_optimizer_thermal.mode != "off" else None
-        self.pose_thermal_grad = arena.grad_view("camera_optimizer_thermal.pose_adjustment") if self.pose_thermal is not None else None
+
+        def nets(sfx: str, with_field: bool) -> BranchNets:
+            co = cfg.camera_optimizer_thermal if sfx else cfg.camera_optimizer
+            pose_key = f"camera_optimizer{sfx}.pose_adjustment"
+            pose = arena.view(pose_key) if co.mode != "off" else None
+            return BranchNets(
+                sfx=sfx, props=[prop_params(arena, "proposal_networks" + sfx, i, cfg, with_grads=True) for i in range(2)],
+                field=field_params(arena, "field" + sfx, cfg, with_grads=True) if with_field else None,
+                pose=pose, pose_grad=arena.grad_view(pose_key) if pose is not None else None,
+                # camera_optimizer: thermal cameras are non-trainable; camera_optimizer_thermal: RGB cameras are (models/thermal_nerfacto.py:132-144)
+                frozen=((1 - th) if sfx else th).to(dev), cam_opt=co, reg_slot=12 if sfx else 11,
+                g_fields="fields" + sfx, g_props="proposal_networks" + sfx, g_camera="camera_opt" + sfx,
+                table_key=f"field{sfx}.mlp_base.model.0.hash_table")
+
+        rgb, thermal = nets("", True), nets("_thermal", self.separate)
+        # the branches that exist: shared mode has the thermal proposal networks (the reference builds them) but no thermal branch
+        self.nets: Dict[str, BranchNets] = {"": rgb, "_thermal": thermal} if self.separate else {"": rgb}
+        # the same objects under the names tests, bench.py, parallel.py and model.py read
+        self.props, self.field, self.pose, self.pose_grad, self.frozen_rgb = rgb.props, rgb.field, rgb.pose, rgb.pose_grad, rgb.frozen
+        self.props_thermal, self.field_thermal, self.frozen_thermal = thermal.props, thermal.field, thermal.frozen
+        self.pose_thermal, self.pose_thermal_grad = thermal.pose, thermal.pose_grad
         self.counts = list(cfg.num_proposal_samples_per_ray) + [cfg.num_nerf_samples_per_ray]
         # ProposalNetworkSampler state (model_components/ray_samplers.py:564-575)
         self.anneal = 1.0
@@ -116,18 +148,34 @@ class RenderEngine:
         # the one-call step runs the NEXT iteration's sampling front (pose correction + proposal sampling of the batch the device data manager has
         # handed over) as co-work of its optimiser launch (TnTrainStep.next_sampling); False: every iteration samples in line
         self.next_sampling = True
+        self.last_updated = False  # did the proposal networks of the RGB sampler get gradients in the last forward?
+        self.group_steps: Dict[str, int] = {}  # Adam step count per optimiser group (a group that is skipped keeps its count)
+        self.scatter_events: Optional[list] = None  # measurement hook (bench.py): a list to receive a HIP event pair around every table scatter
+        self._side: Dict[int, object] = {}  # side streams by index (0 / 1: proposal backward, 5: overlap_adam)
+        self._rand = None  # ops.UniformPool, made on first use (see _uniforms)
+        self._nf_cache: dict = {}  # (N, training) -> (nears, fars) of the last batch size
+        self._step_acc = None  # (N, keys, views): the accumulators get_outputs(prealloc_accumulators=True) allocated for loss_and_backward
+        self._small_ranges: Optional[List[Tuple[int, int, int]]] = None  # cache of _small_grad_ranges
+        self._grad_zero_flag = False  # what _set_grad_zero last wrote into the grids
+        self._kflags_scaler = None  # the grad scaler whose found_inf the grids' nonfinite_flag point at (train_step)
+        self._kernel_flags_done = False  # the last backward raised found_inf for every group: optimizer_step need not scan the arena
+        self._bwd_reads_prop_enc = True  # the backward of this step reads the proposal encodings the forward saves (False: data-parallel schedule)
+        self._step_call: Optional["ops.TrainStepCall"] = None  # the one-call step's argument block, per (scaler, gradient arena)
+        self._step_gidx: Dict[str, int] = {}  # ... and its optimiser group -> flag index
+        self._planned: Optional[dict] = None  # the sampling front the last one-call step ran for the next batch
+        self._metric_ones: Optional[Tensor] = None  # dummy loss vector of pose_metrics
+        self._last_losses16, self._last_num_rays = None, 0  # loss vector and ray count of the last train step (train_metrics)
 
     def _side_stream(self, i: int = 0):
-        side = self.__dict__.setdefault("_side", {})
-        if i not in side:
-            side[i] = torch.cuda.Stream(device=self.device)
-        return side[i]
+        if i not in self._side:
+            self._side[i] = torch.cuda.Stream(device=self.device)
+        return self._side[i]
 
     def _uniforms(self) -> "ops.UniformPool":
         """The samplers' per-ray jitter (ray_samplers.py:104-110, 322-330: torch.rand per call), drawn for 32 requests at a time."""
-        pool = self.__dict__.get("_rand")
+        pool = self.__dict__.get("_rand")  # (tolerant: resetting the pool by removing the attribute is supported)
         if pool is None:
-            pool = self.__dict__["_rand"] = ops.UniformPool(self.device)
+            pool = self._rand = ops.UniformPool(self.device)
         return pool
 
     def sync_params(self) -> None:
@@ -172,7 +220,7 @@ class RenderEngine:
             # drop-in path
             r = ops.render_rays_train(props, fld, pose, frozen, origins, directions, cam, nears, fars, self.counts, anneal, jitters, tag=tag,
                                       wait_event=wait_event, zero_fill=zero_fill,
-                                      save_prop_enc=bool(prop_grad) and self.__dict__.get("_bwd_reads_prop_enc", True))
+                                      save_prop_enc=bool(prop_grad) and self._bwd_reads_prop_enc)
             levels = [Level(S=S, s_bins=lv["s_bins"], e_bins=lv["e_bins"], density=lv["density"], weights=lv["weights"], median=lv["median"])
                       for S, lv in zip(self.counts, r["levels"])]
             return Branch(origins=r["origins"], directions=r["directions"], origins_in=o_in, directions_in=d_in, levels=levels,
@@ -224,11 +272,10 @@ class RenderEngine:
     def _nears_fars(self, N: int, training: bool):
         near = self.cfg.near_plane if training else 0.0  # NearFarCollider resets the near plane at inference (scene_colliders.py:186-191)
         key = (N, bool(training))
-        cache = self.__dict__.setdefault("_nf_cache", {})
-        if key not in cache:  # constants: filled once per batch size, not once per step
-            cache.clear()
-            cache[key] = (torch.full((N,), near, device=self.device), torch.full((N,), self.cfg.far_plane, device=self.device))
-        return cache[key]
+        if key not in self._nf_cache:  # constants: filled once per batch size, not once per step
+            self._nf_cache.clear()
+            self._nf_cache[key] = (torch.full((N,), near, device=self.device), torch.full((N,), self.cfg.far_plane, device=self.device))
+        return self._nf_cache[key]
 
     def _zeros_many(self, shapes, fill: bool = True):
         """Zero-initialised tensors carved out of ONE allocation (one fill kernel instead of one per tensor: at 2 ms per step the ~4.5 us
@@ -247,14 +294,13 @@ class RenderEngine:
         """keys and shapes of the zero-initialised accumulators of one training iteration (loss_and_backward): the loss vector and its 64 lines,
         then per branch d comp, d weights of the levels that take a gradient, d origins / d directions."""
         zshapes, zkeys = [(16,), (ops.LOSS_LINES, 16)], [("L", ""), ("Lp", "")]
-        for sfx in [""] + (["_thermal"] if self.separate else []):
-            fld = self.field_thermal if sfx else self.field
-            zkeys.append(("d_comp", sfx)); zshapes.append((N, fld.num_channels))
+        for sfx, bn in self.nets.items():
+            zkeys.append(("d_comp", sfx)); zshapes.append((N, bn.field.num_channels))
             zkeys.append(("dw2", sfx)); zshapes.append((N, self.counts[2]))
             if prop_grads[sfx]:
                 for i in range(2):
                     zkeys.append((f"dw{i}", sfx)); zshapes.append((N, self.counts[i]))
-            if (self.pose_thermal if sfx else self.pose) is not None:
+            if bn.pose is not None:
                 zkeys.append(("d_o", sfx)); zshapes.append((N, 3))
                 zkeys.append(("d_d", sfx)); zshapes.append((N, 3))
         if self.separate and self.cfg.density_loss_mult > 0:  # the density loss's four gradient buffers (tn_l1_loss accumulates into them)
@@ -304,7 +350,7 @@ class RenderEngine:
         else:
             b = self.render_branch(self.props, self.field, self.pose, self.frozen_rgb, origins, directions, cam, nears, fars, training, self.anneal,
                                    jitters, prop_grad=updated, wait_event=wait_ev, zero_fill=zero_fill)
-        self.last_updated = bool(updated)  # did the proposal networks of the RGB sampler get gradients in this forward?
+        self.last_updated = bool(updated)
         if updated:  # eval renders included, as ProposalNetworkSampler.generate_ray_samples does (ray_samplers.py:612-613)
             self.steps_since_update = 0
         out = self._branch_outputs(b, "", training)
@@ -353,46 +399,70 @@ class RenderEngine:
         """get_metrics_dict['distortion'] + get_loss_dict (models/thermal_nerfacto.py:253-388) and the gradient of their sum with respect to
         every parameter, accumulated into the arena's gradient buffer.  (_grads_are_zero: train_step's promise, see _set_grad_zero.)"""
         self._set_grad_zero(_grads_are_zero)
-        c = self.cfg
-        N = image.shape[0]
-        dev = self.device
         self.arena.grads_clean = False  # this call accumulates into the arena's gradient buffer
-        b = branches[""]
-        bt = branches.get("_thermal")
-        C = b.comp.shape[1]
-        # ---- pixel losses -> d comp
-        # every zero-initialised accumulator of the step comes out of one allocation / one fill (see _zeros_many)
-        # L: 0 rgb 1 thermal 2 tv 3 cross 4 (scratch) 8 interlevel 9 distortion 10 density 11 camreg 12 camreg_thermal
-        # Lp: the loss sums spread over LOSS_LINES 64-byte lines (ops.train_losses), added up into L by ops.losses_finish at the end
-        zkeys, zshapes = self._accumulator_spec(N, {sfx: bool(br.prop_grad) for sfx, br in branches.items()} | ({} if self.separate else {"_thermal": False}))
-        pre = self.__dict__.get("_step_acc")
-        self._step_acc = None
-        if pre is not None and pre[0] == N and pre[1] == zkeys:  # allocated by get_outputs(prealloc_accumulators=True), cleared by the forward
-            Z = pre[2]
-        else:
-            Z = dict(zip(zkeys, self._zeros_many(zshapes)))
+        Z = self._step_accumulators(image.shape[0], branches)
         L, Lp = Z[("L", "")], Z[("Lp", "")]
-        d_comp = Z[("d_comp", "")]
+        grads_w = self._enqueue_losses(branches, Z, image, is_thermal)
+        density_loss = self.separate and self.cfg.density_loss_mult > 0
+        d_dens_extra = self._enqueue_density_loss(out, branches, Z) if density_loss else {}
+        # Overlapped data-parallel exchange only where a slice of the arena is final right after its kernel: in separate mode the
+        # cross-evaluated densities scatter into the same tables again later, so everything is exchanged by dp.finish() instead.
+        pipelined = dp is not None and not self.separate
+        for sfx, br in branches.items():
+            bn = self.nets[sfx]
+            if bn.pose is not None:  # (cross-evaluation gradients are added to the same two tensors before the pose backward)
+                br.d_origins, br.d_directions = Z[("d_o", sfx)], Z[("d_d", sfx)]
+            dc, dws, extra = Z[("d_comp", sfx)], grads_w[sfx], d_dens_extra.get(sfx)
+            if pipelined:
+                self._branch_backward_pipelined(bn, br, cam, dc, dws, extra, br.d_origins, br.d_directions, dp, L, Lp)
+            elif _FUSE and _ONE_CALL_BWD and br.fwd_buf is not None and self.scatter_events is None:
+                # the whole backward of the branch as ONE call of the C ABI (tn_render_rays_train_bwd): renderer backward, field backward with
+                # d position and table scatter, both proposal networks on the library's companion streams -- the launches of
+                # branch_backward, enqueued by the library in the same order per stream
+                ops.render_rays_train_bwd(bn.props, bn.field, br.fwd_buf, br.origins, br.directions, cam, self.counts, dc, dws, extra,
+                                          br.d_origins, br.d_directions, tag="main", side_tags=("side0" + sfx, "side1" + sfx),
+                                          prop_enc_saved=br.prop_enc_saved)
+            else:
+                self.branch_backward(bn, br, cam, dc, dws, extra, br.d_origins, br.d_directions, by_seam=not _FUSE, scatter_events=self.scatter_events)
+        if density_loss:
+            self._cross_density_backward(branches, cam, Z, dp)
+        self._pose_finish(branches, cam, L, Lp, dp)
+        self._last_losses16, self._last_num_rays = L, int(image.shape[0])  # (train_metrics)
+        return self._loss_dict(L)
+
+    def _step_accumulators(self, N: int, branches: Dict[str, Branch]) -> Dict[Tuple[str, str], Tensor]:
+        """Every zero-initialised accumulator of the step, out of one allocation / one fill (see _zeros_many), by (name, suffix).
+        L: 0 rgb 1 thermal 2 tv 3 cross 4 (scratch) 8 interlevel 9 distortion 10 density 11 camreg 12 camreg_thermal
+        Lp: the loss sums spread over LOSS_LINES 64-byte lines (ops.train_losses), added up into L by ops.losses_finish at the end"""
+        zkeys, zshapes = self._accumulator_spec(N, {sfx: bool(br.prop_grad) for sfx, br in branches.items()} | ({} if self.separate else {"_thermal": False}))
+        pre, self._step_acc = self._step_acc, None
+        if pre is not None and pre[0] == N and pre[1] == zkeys:  # allocated by get_outputs(prealloc_accumulators=True), cleared by the forward
+            return pre[2]
+        return dict(zip(zkeys, self._zeros_many(zshapes)))
+
+    def _enqueue_losses(self, branches: Dict[str, Branch], Z, image: Tensor, is_thermal: Tensor) -> Dict[str, List[Optional[Tensor]]]:
+        """The pixel losses (-> d comp) and every branch's proposal losses -> per branch the d weights of its three levels (None: a proposal
+        level that takes no gradient this step)."""
+        c = self.cfg
+        L, Lp = Z[("L", "")], Z[("Lp", "")]
+        b, d_comp = branches[""], Z[("d_comp", "")]
         # the pixel terms ride in the first branch's loss launch (ops.train_losses(pixel=...)): one launch instead of two back to back
         if self.separate:
-            d_comp_t = Z[("d_comp", "_thermal")]
-            pixel = (b.comp, bt.comp, image, is_thermal, c.thermal_loss_mult, c.tv_pixel_loss_mult, c.cross_channel_loss_mult, d_comp, d_comp_t)
+            pixel = (b.comp, branches["_thermal"].comp, image, is_thermal, c.thermal_loss_mult, c.tv_pixel_loss_mult, c.cross_channel_loss_mult, d_comp,
+                     Z[("d_comp", "_thermal")])
         else:
             pixel = (b.comp[:, :3], b.comp[:, 3:], image, is_thermal, c.thermal_loss_mult, c.tv_pixel_loss_mult, c.cross_channel_loss_mult,
                      d_comp[:, :3], d_comp[:, 3:])
         if not _FUSE:
             ops.pixel_losses(*pixel[:7], L[0:8], *pixel[7:])
             pixel = None
-        # ---- proposal losses.  NB (models/thermal_nerfacto.py:363-368): metrics_dict["distortion"] is the SUM over suffixes and is added once per
+        # NB (models/thermal_nerfacto.py:363-368): metrics_dict["distortion"] is the SUM over suffixes and is added once per
         # suffix, so in separate mode each branch's distortion enters with 2x distortion_loss_mult.
         nsfx = 2 if self.separate else 1
         grads_w: Dict[str, List[Optional[Tensor]]] = {}
         for sfx, br in branches.items():
             lv = br.levels
-            dws: List[Optional[Tensor]] = [None, None, Z[("dw2", sfx)]]
-            for i in range(2):
-                if br.prop_grad:
-                    dws[i] = Z[(f"dw{i}", sfx)]
+            dws: List[Optional[Tensor]] = [Z[("dw0", sfx)] if br.prop_grad else None, Z[("dw1", sfx)] if br.prop_grad else None, Z[("dw2", sfx)]]
             # distortion + both interlevel terms (+ the pixel terms): one launch
             props_l = [(lv[i].s_bins, lv[i].weights, dws[i]) for i in range(2)]
             if _FUSE:
@@ -401,215 +471,210 @@ class RenderEngine:
                 ops.proposal_losses(lv[2].s_bins, lv[2].weights, props_l, c.distortion_loss_mult * nsfx, c.interlevel_loss_mult, L[9:10], L[8:9], dws[2])
             pixel = None
             grads_w[sfx] = dws
-        # ---- per-branch backward
-        # Overlapped data-parallel exchange only where a slice of the arena is final right after its kernel: in separate mode the
-        # cross-evaluated densities scatter into the same tables again later, so everything is exchanged by dp.finish() instead.
-        pipelined = dp is not None and not self.separate
-        d_dens_extra: Dict[str, Optional[Tensor]] = {"": None, "_thermal": None}
-        if self.separate and c.density_loss_mult > 0:
-            a, bb = c.density_loss_mult, c.rgb_density_loss_mult * c.density_loss_mult
-            d2, d2t = out["density2"].squeeze(-1), out["density2_thermal"].squeeze(-1)
-            dens, dens_t = b.levels[-1].density, bt.levels[-1].density
-            g_d2, g_dt, g_d, g_d2t = Z[("g_d2", "")], Z[("g_dt", "")], Z[("g_d", "")], Z[("g_d2t", "")]  # (zero, from the step's one allocation)
-            # a*|d2.detach - dens_t| + b*|d2 - dens_t.detach|  and  a*|dens.detach - d2t| + b*|dens - d2t.detach|   (:336-344)
-            ops.l1_loss(d2, dens_t, bb, a, L[10:11], g_d2, g_dt)
-            ops.l1_loss(dens, d2t, bb, a, L[10:11], g_d, g_d2t)
-            d_dens_extra[""], d_dens_extra["_thermal"] = g_d, g_dt
-        for sfx, br in branches.items():
-            fld = self.field_thermal if sfx else self.field
-            props = self.props_thermal if sfx else self.props
-            pose = self.pose_thermal if sfx else self.pose
-            pose_grad = self.pose_thermal_grad if sfx else self.pose_grad
-            frozen = self.frozen_thermal if sfx else self.frozen_rgb
-            lv = br.levels
-            want_pos = pose is not None
-            d_o = Z[("d_o", sfx)] if want_pos else None
-            d_d = Z[("d_d", sfx)] if want_pos else None
-            dws = grads_w[sfx]
-            dc = d_comp_t if sfx else d_comp
-            if _FUSE and _ONE_CALL_BWD and not pipelined and br.fwd_buf is not None and getattr(self, "scatter_events", None) is None:
-                # the whole backward of the branch as ONE call of the C ABI (tn_render_rays_train_bwd): renderer backward, field backward with
-                # d position and table scatter, both proposal networks on the library's companion streams -- the launches below, enqueued
-                # by the library in the same order per stream
-                ops.render_rays_train_bwd(props, fld, br.fwd_buf, br.origins, br.directions, cam, self.counts, dc,
-                                          [dws[0] if br.prop_grad else None, dws[1] if br.prop_grad else None, dws[2]], d_dens_extra[sfx], d_o, d_d,
-                                          tag="main", side_tags=("side0" + sfx, "side1" + sfx), prop_enc_saved=br.prop_enc_saved)
-                br._d_o, br._d_d = d_o, d_d
-                continue
-            if _FUSE:
-                d_rgb, d_dens = ops.render_bwd(lv[2].e_bins, lv[2].density, br.rgb_samples, lv[2].weights, dc, dws[2])
-            else:
-                d_rgb = ops.composite_bwd(br.rgb_samples, lv[2].weights, dc, dws[2])
-                d_dens = ops.weights_bwd(lv[2].e_bins, lv[2].density, lv[2].weights, dws[2])
-            if d_dens_extra[sfx] is not None:
-                d_dens += d_dens_extra[sfx]
-            # The proposal networks' backward (own tables, MLPs and scatter; d origins / d directions are accumulated atomically) is
-            # independent of the main field's and runs on side streams.
-            #   plain step: level 0 on one side stream, level 1 on a second one (both beside the field's backward, which also forks d position
-            #   to the library's companion stream) -- measured 1.249 -> 1.216 ms per step against one shared side stream.
-            #   data-parallel schedule: BOTH levels, one after the other, on ONE side stream, and nothing else forks (d position runs in line).
-            #   The step then keeps three streams busy -- main, this one, RCCL's -- so that with the runtime's DEFAULT four hardware queues every
-            #   busy stream has a queue of its own.  Round 4's schedule (side stream + companion stream + level 1 behind the table ranges + two
-            #   communicators) ran at 0.89 ms with GPU_MAX_HW_QUEUES=8 and stalled at 1.8-2.1 ms with 4 / 5 / 7: which streams shared a queue
-            #   decided a factor of two (profiles/r04_experiments.md; sweep of this schedule: profiles/r05_dp_hwq_sweep.json).
-            side = None
-            on_side = (0, 1) if pipelined else (0,)
-            if br.prop_grad:
-                side = self._side_stream()
-                main = torch.cuda.current_stream()
-                side.wait_stream(main)  # dws[i], d_o, d_d are produced/zeroed on the main stream
-                with torch.cuda.stream(side):
-                    for i in on_side:
-                        dd = ops.weights_bwd(lv[i].e_bins, lv[i].density, lv[i].weights, dws[i])
-                        ops.prop_density_bwd(props[i], br.origins, br.directions, lv[i].e_bins, dd, d_o, d_d, tag=f"side{i}")
-            if pipelined:
-                # main table in level ranges: each range's all-reduce runs beside the scatter of the next one
-                ph = ops._lib
-                # (d position in line: one stream less -- see above)
-                ops.field_bwd_phase(fld, br.origins, br.directions, cam, lv[2].e_bins, d_dens, d_rgb, d_o, d_d, ph.TN_BWD_MLP)
-                if _FUSE and pose is not None and not br.prop_grad:
-                    # Nothing else adds to d origins / d directions on a step without a proposal update: the pose gradient (+ the loss sums and
-                    # the camera regulariser) can be finished NOW, and with it everything behind the table in the arena is final -- MLP
-                    # weights, embedding, pose.  Their exchange goes out here, hidden behind the scatter, instead of as one more collective
-                    # behind the last table range (~35-50 us between the last fold and the optimiser, whatever the number of ranks).
-                    co = c.camera_optimizer_thermal if sfx else c.camera_optimizer
-                    ops.pose_bwd_finish(pose, frozen, cam, br.directions_in, d_o, d_d, pose_grad, co.trans_l2_penalty, co.rot_l2_penalty, co.penalty_scale,
-                                        L[12:13] if sfx else L[11:12], Lp, L)
-                    br._pose_done = True
-                    dp.reduce_range(self.arena.layout["field.mlp_base.model.0.hash_table"][0] + self._table_floats(fld), self._camera_hi())
-                T2 = 2 * 2**fld.log2_hashmap_size
-                t0 = self.arena.layout["field.mlp_base.model.0.hash_table"][0]
-                P = N * self.counts[-1]
-                # the coarse levels first, exchanged as dense per-cell sums (their table slice is almost all zeros): the longest prefix of levels
-                # that are all dense-replica levels at this batch size
-                nd = 0
-                while getattr(dp, "dense_exchange", False) and nd < fld.num_levels and ops.field_dense_count(fld, P, 0, nd + 1) > 0:
-                    nd += 1
-                if nd > 0:
-                    cells = ops.field_dense_count(fld, P, 0, nd)
-                    dense = torch.empty((cells, 2), device=dev)
-                    ops.field_bwd_scatter_dense(fld, br.origins, br.directions, lv[2].e_bins, d_o, d_d, 0, nd, dense)
-                    dp.reduce_tensor(dense, (t0, t0 + nd * T2), lambda fld=fld, P=P, nd=nd, dense=dense: ops.field_dense_fold(fld, P, 0, nd, dense))
-                # one bin pass over every level, then one fold per exchanged level range (with the dense exchange of the coarse levels the
-                # remaining levels go range by range through the whole scatter instead: bin + fold per range)
-                two_step = nd == 0
-                if two_step:
-                    ops.field_bwd_phase(fld, br.origins, br.directions, cam, lv[2].e_bins, d_dens, d_rgb, d_o, d_d,
-                                        ph.TN_BWD_SCATTER_BIN | ph.TN_BWD_COUNTERS_CLEAN)  # (the MLP phase above left the bucket counters zeroed)
-                for lb, le in dp.level_ranges(fld.num_levels - nd):
-                    lb, le = lb + nd, le + nd
-                    ops.field_bwd_phase(fld, br.origins, br.directions, cam, lv[2].e_bins, d_dens, d_rgb, d_o, d_d,
-                                        ph.TN_BWD_SCATTER_FOLD if two_step else ph.TN_BWD_SCATTER, lb, le)
-                    dp.reduce_range(t0 + lb * T2, t0 + le * T2)
-                ops.field_bwd_phase(fld, br.origins, br.directions, cam, lv[2].e_bins, d_dens, d_rgb, d_o, d_d, ph.TN_BWD_JOIN)
-            else:
-                # the level-1 network on a second side stream (the package asks the runtime for 8 hardware queues, see __init__.py; with
-                # the default 4 a fifth busy stream shares a queue and serialises).  Measured: 1.249 -> 1.216 ms per step.
-                side1 = None
-                if br.prop_grad:
-                    side1 = self._side_stream(1)
-                    side1.wait_stream(main)
-                    with torch.cuda.stream(side1):
-                        dd = ops.weights_bwd(lv[1].e_bins, lv[1].density, lv[1].weights, dws[1])
-                        ops.prop_density_bwd(props[1], br.origins, br.directions, lv[1].e_bins, dd, d_o, d_d, tag="side1")
-                ev = getattr(self, "scatter_events", None)
-                if ev is not None and not sfx:
-                    # measurement hook (bench.py: roofline.avg_launch_ms_in_step): the same three phases as one tn_field_bwd call, with a HIP
-                    # event pair around the table scatter on the launch stream -- whatever runs beside it in the step still does
-                    ph = ops._lib
-                    ops.field_bwd_phase(fld, br.origins, br.directions, cam, lv[2].e_bins, d_dens, d_rgb, d_o, d_d, ph.TN_BWD_MLP)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    ops.field_bwd_phase(fld, br.origins, br.directions, cam, lv[2].e_bins, d_dens, d_rgb, d_o, d_d,
-                                        ph.TN_BWD_SCATTER | ph.TN_BWD_COUNTERS_CLEAN, 0, fld.num_levels)
-                    e1.record()
-                    ops.field_bwd_phase(fld, br.origins, br.directions, cam, lv[2].e_bins, d_dens, d_rgb, d_o, d_d, ph.TN_BWD_JOIN)
-                    ev.append((e0, e1, bool(br.prop_grad)))
-                else:
-                    ops.field_bwd(fld, br.origins, br.directions, cam, lv[2].e_bins, d_dens, d_rgb, d_o, d_d)
-                if side1 is not None:
-                    torch.cuda.current_stream().wait_stream(side1)
-            if side is not None:
-                torch.cuda.current_stream().wait_stream(side)
-                if pipelined:
-                    # both proposal networks' gradients are final: ONE collective for the group, on the same communicator as the table ranges and
-                    # issued behind them (a communicator runs its collectives in issue order: ahead of the table ranges it would hold them up until
-                    # the whole proposal backward is through, which is why round 4 needed a second communicator)
-                    dp.reduce_range(*self.arena.group_range["proposal_networks"])
-            br._d_o, br._d_d = d_o, d_d  # cross-evaluation gradients are added below before the pose backward
-        if self.separate and c.density_loss_mult > 0:
-            # density2 = field at the thermal branch's samples/rays; density2_thermal = field_thermal at the rgb branch's
-            # density-only backward: the colour head saw these samples with a zero gradient (models/thermal_nerfacto.py:447-458 calls
-            # get_density only), so its backward, its three weight-gradient GEMMs and the embedding rows are skipped
-            ops.field_bwd(self.field, bt.origins, bt.directions, cam, bt.levels[-1].e_bins, g_d2, None, bt._d_o, bt._d_d, tag="cross")
+        return grads_w
+
+    def _enqueue_density_loss(self, out: Dict[str, object], branches: Dict[str, Branch], Z) -> Dict[str, Tensor]:
+        """Separate mode's density loss between each field and the other one evaluated at its samples -> per branch the gradient it adds to
+        the branch's own density (the cross-evaluated densities' gradients stay in Z for _cross_density_backward)."""
+        c = self.cfg
+        a, bb = c.density_loss_mult, c.rgb_density_loss_mult * c.density_loss_mult
+        d2, d2t = out["density2"].squeeze(-1), out["density2_thermal"].squeeze(-1)
+        dens, dens_t = branches[""].levels[-1].density, branches["_thermal"].levels[-1].density
+        g_d2, g_dt, g_d, g_d2t = Z[("g_d2", "")], Z[("g_dt", "")], Z[("g_d", "")], Z[("g_d2t", "")]  # (zero, from the step's one allocation)
+        # a*|d2.detach - dens_t| + b*|d2 - dens_t.detach|  and  a*|dens.detach - d2t| + b*|dens - d2t.detach|   (:336-344)
+        L10 = Z[("L", "")][10:11]
+        ops.l1_loss(d2, dens_t, bb, a, L10, g_d2, g_dt)
+        ops.l1_loss(dens, d2t, bb, a, L10, g_d, g_d2t)
+        return {"": g_d, "_thermal": g_dt}
+
+    def _render_backward(self, br: Branch, d_comp: Tensor, dw2: Tensor, d_dens_extra: Optional[Tensor], by_seam: bool):
+        """renderer + weights backward of the last level (+ the density loss's own gradient) -> d rgb samples, d density"""
+        last = br.levels[2]
+        if by_seam:
+            d_rgb = ops.composite_bwd(br.rgb_samples, last.weights, d_comp, dw2)
+            d_dens = ops.weights_bwd(last.e_bins, last.density, last.weights, dw2)
+        else:
+            d_rgb, d_dens = ops.render_bwd(last.e_bins, last.density, br.rgb_samples, last.weights, d_comp, dw2)
+        if d_dens_extra is not None:
+            d_dens += d_dens_extra
+        return d_rgb, d_dens
+
+    def _proposal_backward(self, bn: BranchNets, br: Branch, levels, d_weights, d_o, d_d, stream: int, main):
+        """weights backward + proposal network backward (own table, MLP and scatter; d origins / d directions are accumulated atomically) of
+        `levels`, one after the other on side stream `stream`, forked from `main` -> the side stream, for the caller to join."""
+        side = self._side_stream(stream)
+        side.wait_stream(main)  # d_weights, d_o, d_d are produced / zeroed on the main stream
+        with torch.cuda.stream(side):
+            for i in levels:
+                lv = br.levels[i]
+                dd = ops.weights_bwd(lv.e_bins, lv.density, lv.weights, d_weights[i])
+                ops.prop_density_bwd(bn.props[i], br.origins, br.directions, lv.e_bins, dd, d_o, d_d, tag=f"side{i}")
+        return side
+
+    def branch_backward(self, bn: BranchNets, br: Branch, cam: Tensor, d_comp: Tensor, d_weights: List[Optional[Tensor]],
+                        d_dens_extra: Optional[Tensor], d_o: Optional[Tensor], d_d: Optional[Tensor], by_seam: bool = False,
+                        scatter_events: Optional[list] = None) -> None:
+        """The backward of one branch launch by launch -- what tn_render_rays_train_bwd enqueues in one call -- for the fused step
+        (TN_ONE_CALL_BWD=0, the measurement hook) and for the autograd node of the model API (model._RenderFn.backward).
+        d_weights = [level 0, level 1, fine]; None for level 0 or 1: that proposal network takes no gradient.  d_dens_extra: added to the
+        fine level's d density.  by_seam: composite_bwd + weights_bwd instead of the fused tn_render_bwd (TN_FUSE_SMALL=0)."""
+        d_rgb, d_dens = self._render_backward(br, d_comp, d_weights[2], d_dens_extra, by_seam)
+        # The proposal networks' backward is independent of the main field's and runs on side streams: level 0 on one, level 1 on a second
+        # one (both beside the field's backward, which also forks d position to the library's companion stream) -- measured
+        # 1.249 -> 1.216 ms per step against one shared side stream.  (The package asks the runtime for 8 hardware queues, see __init__.py;
+        # with the default 4 a fifth busy stream shares a queue and serialises.)
+        sides = []
+        if d_weights[0] is not None or d_weights[1] is not None:
+            main = torch.cuda.current_stream()
+            sides = [self._proposal_backward(bn, br, (i,), d_weights, d_o, d_d, i, main) for i in (0, 1) if d_weights[i] is not None]
+        lv2 = br.levels[2]
+        if scatter_events is not None and not bn.sfx:
+            self._field_backward_timed(bn.field, br, cam, d_dens, d_rgb, d_o, d_d, scatter_events)
+        else:
+            ops.field_bwd(bn.field, br.origins, br.directions, cam, lv2.e_bins, d_dens, d_rgb, d_o, d_d)
+        for side in reversed(sides):
+            main.wait_stream(side)
+
+    def _field_backward_timed(self, fld, br: Branch, cam: Tensor, d_dens: Tensor, d_rgb: Tensor, d_o, d_d, events: list) -> None:
+        """measurement hook (bench.py: roofline.avg_launch_ms_in_step): the same three phases as one tn_field_bwd call, with a HIP
+        event pair around the table scatter on the launch stream -- whatever runs beside it in the step still does"""
+        ph = ops._lib
+        args = (fld, br.origins, br.directions, cam, br.levels[2].e_bins, d_dens, d_rgb, d_o, d_d)
+        ops.field_bwd_phase(*args, ph.TN_BWD_MLP)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ops.field_bwd_phase(*args, ph.TN_BWD_SCATTER | ph.TN_BWD_COUNTERS_CLEAN, 0, fld.num_levels)
+        e1.record()
+        ops.field_bwd_phase(*args, ph.TN_BWD_JOIN)
+        events.append((e0, e1, bool(br.prop_grad)))
+
+    def _branch_backward_pipelined(self, bn: BranchNets, br: Branch, cam: Tensor, d_comp: Tensor, d_weights: List[Optional[Tensor]],
+                                   d_dens_extra: Optional[Tensor], d_o: Optional[Tensor], d_d: Optional[Tensor], dp, L: Tensor, Lp: Tensor) -> None:
+        """branch_backward for the overlapped data-parallel exchange (shared mode): the main table goes out in level ranges, each range's
+        all-reduce beside the scatter of the next one.
+        Schedule: BOTH proposal levels, one after the other, on ONE side stream, and nothing else forks (d position runs in line).
+        The step then keeps three streams busy -- main, this one, RCCL's -- so that with the runtime's DEFAULT four hardware queues every
+        busy stream has a queue of its own.  Round 4's schedule (side stream + companion stream + level 1 behind the table ranges + two
+        communicators) ran at 0.89 ms with GPU_MAX_HW_QUEUES=8 and stalled at 1.8-2.1 ms with 4 / 5 / 7: which streams shared a queue
+        decided a factor of two (profiles/r04_experiments.md; sweep of this schedule: profiles/r05_dp_hwq_sweep.json)."""
+        fld, ph = bn.field, ops._lib
+        d_rgb, d_dens = self._render_backward(br, d_comp, d_weights[2], d_dens_extra, by_seam=not _FUSE)
+        side = self._proposal_backward(bn, br, (0, 1), d_weights, d_o, d_d, 0, torch.cuda.current_stream()) if br.prop_grad else None
+        args = (fld, br.origins, br.directions, cam, br.levels[2].e_bins, d_dens, d_rgb, d_o, d_d)
+        t0 = self.arena.layout[bn.table_key][0]
+        # (d position in line: one stream less -- see above)
+        ops.field_bwd_phase(*args, ph.TN_BWD_MLP)
+        if _FUSE and bn.pose is not None and not br.prop_grad:
+            # Nothing else adds to d origins / d directions on a step without a proposal update: the pose gradient (+ the loss sums and
+            # the camera regulariser) can be finished NOW, and with it everything behind the table in the arena is final -- MLP
+            # weights, embedding, pose.  Their exchange goes out here, hidden behind the scatter, instead of as one more collective
+            # behind the last table range (~35-50 us between the last fold and the optimiser, whatever the number of ranks).
+            self._pose_bwd_finish(bn, br, cam, L, Lp, L)
+            br.pose_done = True
+            # (to the end of the shared-mode live range behind the main table: field embedding + MLPs, then the camera optimiser's pose)
+            dp.reduce_range(t0 + self._table_floats(fld), self.arena.group_range[bn.g_camera][1])
+        T2 = 2 * 2**fld.log2_hashmap_size
+        P = cam.shape[0] * self.counts[-1]
+        # the coarse levels first, exchanged as dense per-cell sums (their table slice is almost all zeros): the longest prefix of levels
+        # that are all dense-replica levels at this batch size
+        nd = 0
+        while getattr(dp, "dense_exchange", False) and nd < fld.num_levels and ops.field_dense_count(fld, P, 0, nd + 1) > 0:
+            nd += 1
+        if nd > 0:
+            cells = ops.field_dense_count(fld, P, 0, nd)
+            dense = torch.empty((cells, 2), device=self.device)
+            ops.field_bwd_scatter_dense(fld, br.origins, br.directions, br.levels[2].e_bins, d_o, d_d, 0, nd, dense)
+            dp.reduce_tensor(dense, (t0, t0 + nd * T2), lambda fld=fld, P=P, nd=nd, dense=dense: ops.field_dense_fold(fld, P, 0, nd, dense))
+        # one bin pass over every level, then one fold per exchanged level range (with the dense exchange of the coarse levels the
+        # remaining levels go range by range through the whole scatter instead: bin + fold per range)
+        two_step = nd == 0
+        if two_step:
+            ops.field_bwd_phase(*args, ph.TN_BWD_SCATTER_BIN | ph.TN_BWD_COUNTERS_CLEAN)  # (the MLP phase above left the bucket counters zeroed)
+        for lb, le in dp.level_ranges(fld.num_levels - nd):
+            lb, le = lb + nd, le + nd
+            ops.field_bwd_phase(*args, ph.TN_BWD_SCATTER_FOLD if two_step else ph.TN_BWD_SCATTER, lb, le)
+            dp.reduce_range(t0 + lb * T2, t0 + le * T2)
+        ops.field_bwd_phase(*args, ph.TN_BWD_JOIN)
+        if side is not None:
+            torch.cuda.current_stream().wait_stream(side)
+            # both proposal networks' gradients are final: ONE collective for the group, on the same communicator as the table ranges and
+            # issued behind them (a communicator runs its collectives in issue order: ahead of the table ranges it would hold them up until
+            # the whole proposal backward is through, which is why round 4 needed a second communicator)
+            dp.reduce_range(*self.arena.group_range[bn.g_props])
+
+    def _cross_density_backward(self, branches: Dict[str, Branch], cam: Tensor, Z, dp) -> None:
+        """Separate mode's density loss, second half: density2 = field at the thermal branch's samples/rays; density2_thermal = field_thermal
+        at the rgb branch's.  Density-only backward: the colour head saw these samples with a zero gradient
+        (models/thermal_nerfacto.py:447-458 calls get_density only), so its backward, its three weight-gradient GEMMs and the embedding
+        rows are skipped."""
+        # Data parallel, separate mode: a table is final after its SECOND scatter (own branch + the cross-evaluated density).  The RGB
+        # field's 64 MB go out right behind its cross backward and travel beside the thermal field's; the thermal table follows it, the rest
+        # at finish().  (DDP's buckets overlap with the backward in every mode: pipelines/base_pipeline.py:281-283.)
+        for sfx, other, g in (("", "_thermal", Z[("g_d2", "")]), ("_thermal", "", Z[("g_d2t", "")])):
+            bn, at = self.nets[sfx], branches[other]  # this field, at the OTHER branch's samples
+            ops.field_bwd(bn.field, at.origins, at.directions, cam, at.levels[-1].e_bins, g, None, at.d_origins, at.d_directions, tag="cross")
             if dp is not None:
-                # Data parallel, separate mode: a table is final after its SECOND scatter (own branch + the cross-evaluated density).  The RGB
-                # field's 64 MB go out here and travel beside the thermal field's cross backward; the thermal table follows it, the rest at
-                # finish().  (DDP's buckets overlap with the backward in every mode: pipelines/base_pipeline.py:281-283.)
-                t0 = self.arena.layout["field.mlp_base.model.0.hash_table"][0]
-                dp.reduce_range(t0, t0 + self._table_floats(self.field))
-            ops.field_bwd(self.field_thermal, b.origins, b.directions, cam, b.levels[-1].e_bins, g_d2t, None, b._d_o, b._d_d, tag="cross")
-            if dp is not None:
-                t0 = self.arena.layout["field_thermal.mlp_base.model.0.hash_table"][0]
-                dp.reduce_range(t0, t0 + self._table_floats(self.field_thermal))
+                t0 = self.arena.layout[bn.table_key][0]
+                dp.reduce_range(t0, t0 + self._table_floats(bn.field))
+
+    def _pose_bwd_finish(self, bn: BranchNets, br: Branch, cam: Tensor, L: Tensor, loss_lines: Optional[Tensor], losses16: Optional[Tensor],
+                         **check) -> None:
+        """pose gradient + camera regulariser (+ the loss sums, when loss_lines / losses16 are given) of one branch in one launch"""
+        co = bn.cam_opt
+        ops.pose_bwd_finish(bn.pose, bn.frozen, cam, br.directions_in, br.d_origins, br.d_directions, bn.pose_grad, co.trans_l2_penalty, co.rot_l2_penalty,
+                            co.penalty_scale, L[bn.reg_slot:bn.reg_slot + 1], loss_lines, losses16, **check)
+
+    def _pose_finish(self, branches: Dict[str, Branch], cam: Tensor, L: Tensor, Lp: Tensor, dp) -> None:
+        """The end of the backward: every camera optimiser's pose gradient and regulariser, and the loss sums Lp added up into L once."""
         finished = not _FUSE
         # GradScaler's found_inf from the kernels that write the gradients (see train_step): the last pose launch of the step also scans the
         # small ranges no scatter sees; the flags count as raised only when every camera group's launch went through this path
-        kscaler = self.__dict__.get("_kflags_scaler") if (dp is None and _FUSE) else None
+        kscaler = self._kflags_scaler if (dp is None and _FUSE) else None
         gidx = {g: i for i, g in enumerate(self.arena.optimised_groups)}
-        todo = [sfx for sfx, br in branches.items() if (self.pose_thermal if sfx else self.pose) is not None and not getattr(br, "_pose_done", False)]
+        todo = [sfx for sfx, br in branches.items() if self.nets[sfx].pose is not None and not br.pose_done]
         handled = set()
         for sfx, br in branches.items():
-            pose = self.pose_thermal if sfx else self.pose
-            if pose is None:
+            bn = self.nets[sfx]
+            if bn.pose is None:
                 continue
-            if getattr(br, "_pose_done", False):  # finished early (data-parallel schedule, step without a proposal update)
+            if br.pose_done:  # finished early (data-parallel schedule, step without a proposal update)
                 finished = True
                 continue
-            pose_grad = self.pose_thermal_grad if sfx else self.pose_grad
-            frozen = self.frozen_thermal if sfx else self.frozen_rgb
-            co = c.camera_optimizer_thermal if sfx else c.camera_optimizer
-            reg = L[12:13] if sfx else L[11:12]
             if _FUSE:  # pose gradient + regulariser (+ the loss sums, once) in one launch
                 extra = {}
-                if kscaler is not None and ("camera_opt" + sfx) in gidx:
+                if kscaler is not None and bn.g_camera in gidx:
                     extra = dict(check_grads=self.arena.grads, check_ranges=self._small_grad_ranges() if sfx == todo[-1] else [],
-                                 found_inf=kscaler.found_inf, pose_flag=gidx["camera_opt" + sfx])
-                    handled.add("camera_opt" + sfx)
-                ops.pose_bwd_finish(pose, frozen, cam, br.directions_in, br._d_o, br._d_d, pose_grad, co.trans_l2_penalty, co.rot_l2_penalty,
-                                    co.penalty_scale, reg, None if finished else Lp, None if finished else L, **extra)
+                                 found_inf=kscaler.found_inf, pose_flag=gidx[bn.g_camera])
+                    handled.add(bn.g_camera)
+                self._pose_bwd_finish(bn, br, cam, L, None if finished else Lp, None if finished else L, **extra)
                 finished = True
             else:
-                ops.pose_apply_bwd(pose, frozen, cam, br.directions_in, br._d_o, br._d_d, pose_grad)
-                ops.camera_reg(pose, co.trans_l2_penalty, co.rot_l2_penalty, co.penalty_scale, reg, pose_grad)
+                ops.pose_apply_bwd(bn.pose, bn.frozen, cam, br.directions_in, br.d_origins, br.d_directions, bn.pose_grad)
+                ops.camera_reg(bn.pose, bn.cam_opt.trans_l2_penalty, bn.cam_opt.rot_l2_penalty, bn.cam_opt.penalty_scale, L[bn.reg_slot:bn.reg_slot + 1], bn.pose_grad)
         if not finished:
             ops.losses_finish(Lp, L)
         self._kernel_flags_done = bool(handled) and handled == {g for g in self.arena.optimised_groups if g.startswith("camera_opt")}
-        self._last_losses16, self._last_num_rays = L, int(image.shape[0])  # (train_metrics)
+
+    def _loss_dict(self, L: Tensor) -> Dict[str, Tensor]:
+        """get_loss_dict's entries as views of the loss vector"""
         losses = {"rgb_loss": L[0], "thermal_loss": L[1], "tv_pixel_loss": L[2], "cross_channel_loss": L[3], "interlevel_loss": L[8],
                   "distortion_loss": L[9]}
-        if self.separate and c.density_loss_mult > 0:
+        if self.separate and self.cfg.density_loss_mult > 0:
             losses["density_loss"] = L[10]
-        if self.pose is not None:
-            losses["camera_opt_regularizer"] = L[11]
-        if self.separate and self.pose_thermal is not None:
-            losses["camera_opt_regularizer_thermal"] = L[12]
+        for sfx, bn in self.nets.items():
+            if bn.pose is not None:
+                losses["camera_opt_regularizer" + sfx] = L[bn.reg_slot]
         return losses
 
     def _table_floats(self, fld) -> int:
         return fld.num_levels * 2 * 2**fld.log2_hashmap_size
 
-    def _camera_hi(self) -> int:
-        """end of the shared-mode live range behind the main table: field embedding + MLPs, then the camera optimiser's pose"""
-        return self.arena.group_range["camera_opt"][1]
-
     # ---------------------------------------------------------------- GradScaler's found_inf raised by the kernels that write the gradients
     def _small_grad_ranges(self) -> List[Tuple[int, int, int]]:
         """(lo, hi, group index) of everything in the optimised groups that is neither a hash table (its scatter raises the group's flag through
         TnGrid.nonfinite_flag) nor a pose (tn_pose_bwd_finish_check sees its contributions): MLP weights, biases, embeddings -- a few 10^4 floats."""
-        hit = self.__dict__.get("_small_ranges")
-        if hit is not None:
-            return hit
+        if self._small_ranges is not None:
+            return self._small_ranges
         a = self.arena
         out: List[Tuple[int, int, int]] = []
         for gi, g in enumerate(a.optimised_groups):
@@ -639,11 +704,10 @@ class RenderEngine:
         gidx = {g: i for i, g in enumerate(self.arena.optimised_groups)}
         def flag(g):
             return None if (scaler is None or g not in gidx) else scaler.found_inf[gidx[g]:gidx[g] + 1]
-        for objs, g in ((self.props, "proposal_networks"), ([self.field], "fields"), (self.props_thermal if self.separate else [], "proposal_networks_thermal"),
-                        ([self.field_thermal] if self.field_thermal is not None else [], "fields_thermal")):
-            for o in objs:
-                if o is not None:
-                    o.__dict__["nonfinite_flag"] = flag(g)
+        for bn in self.nets.values():  # (shared mode: the thermal proposal networks are never evaluated and keep no flag)
+            for o in bn.props:
+                o.nonfinite_flag = flag(bn.g_props)
+            bn.field.nonfinite_flag = flag(bn.g_fields)
 
     def _set_grad_zero(self, flag: bool) -> None:
         """TnGrid.table_grad_is_zero on every grid of the model: the promise that a table's gradient holds zeros when its scatter starts and is
@@ -651,13 +715,12 @@ class RenderEngine:
         gradients are zero when its backward starts, and in shared mode every table sees one scatter.  Everything else (loss_and_backward called
         directly, the autograd nodes of the drop-in path: several backward passes may share one arena) withdraws it."""
         flag = bool(flag) and not self.separate
-        if self.__dict__.get("_grad_zero_flag", False) == flag:
+        if self._grad_zero_flag == flag:
             return
         self._grad_zero_flag = flag
-        for o in list(self.props) + [self.field] + (list(self.props_thermal) if self.separate else []) + (
-                [self.field_thermal] if self.field_thermal is not None else []):
-            if o is not None:
-                o.__dict__["grad_is_zero"] = flag
+        for bn in self.nets.values():  # (shared mode: not the thermal proposal networks, as in _set_kernel_flags)
+            for o in bn.props + [bn.field]:
+                o.grad_is_zero = flag
 
     # ---------------------------------------------------------------- optimiser
     def optimizer_step(self, lr_overrides: Optional[Dict[str, float]] = None, scheduled: bool = True, skip_groups=(), ranges=None,
@@ -672,8 +735,6 @@ class RenderEngine:
         grad_scaler (optim.DeviceGradScaler): GradScaler semantics on the device -- the step is a no-op when the gradients hold an inf / NaN,
         bias corrections and LR schedule are evaluated at (count - skipped steps), the scale is updated (engine/trainer.py:470-495)."""
         self.adam_step_count += 1
-        if not hasattr(self, "group_steps"):
-            self.group_steps = {}
         a = self.arena
         hyper = {}
         for gname in a.optimised_groups:
@@ -696,7 +757,9 @@ class RenderEngine:
             # GradScaler decides per optimiser = per parameter group: one flag per group.  When the kernels that WRITE the gradients have raised the
             # flags already (table scatters through TnGrid.nonfinite_flag, everything else in tn_pose_bwd_finish_check) no pass over the arena is
             # needed; otherwise all groups are checked in one launch.
-            kernel_flags = scaler is not None and self.__dict__.pop("_kernel_flags_done", False)
+            kernel_flags = scaler is not None and self._kernel_flags_done
+            if scaler is not None:
+                self._kernel_flags_done = False  # (one backward's flags serve one optimiser step)
             if scaler is not None and not kernel_flags:
                 scaler.check_ranges(a.grads, [a.group_range[g] for g in names], [gidx[g] for g in names])
             on_device_lr = scaler is not None and scheduled and not lr_overrides
@@ -781,7 +844,7 @@ class RenderEngine:
         parameter of the group in get_param_groups() order.  Plus the sampler's update counters, which the reference loses on resume."""
         self.sync_params()
         a = self.arena
-        steps = getattr(self, "group_steps", {})
+        steps = self.group_steps
         opt, sched = {}, {}
         # With a grad scaler the host counters include the iterations the DEVICE skipped (inf / NaN gradients) and the schedule lag; what the
         # reference Trainer would have written for the same history excludes them (torch's Adam `step` does not advance on a skipped step, the
@@ -839,14 +902,15 @@ class RenderEngine:
         The five-call path stays the reference (TN_TRAIN_STEP_ONE_CALL=0; tests/test_trainer_sequence_gpu.py compares the two)."""
         a, c = self.arena, self.cfg
         N = origins.shape[0]
-        call = self.__dict__.get("_step_call")
+        call = self._step_call
         if call is None or call.scaler is not scaler or call.arena_tensors[1] is not a.grads:
-            co = c.camera_optimizer
+            bn = self.nets[""]
+            co = bn.cam_opt
             gidx = {g: i for i, g in enumerate(a.optimised_groups)}
             call = self._step_call = ops.TrainStepCall(
-                self.props, self.field, self.pose, self.frozen_rgb, self.pose_grad, (co.trans_l2_penalty, co.rot_l2_penalty, co.penalty_scale), self.counts,
+                bn.props, bn.field, bn.pose, bn.frozen, bn.pose_grad, (co.trans_l2_penalty, co.rot_l2_penalty, co.penalty_scale), self.counts,
                 (c.thermal_loss_mult, c.tv_pixel_loss_mult, c.cross_channel_loss_mult, c.distortion_loss_mult, c.interlevel_loss_mult),
-                (a.params, a.grads, a.exp_avg, a.exp_avg_sq), self._small_grad_ranges(), gidx["camera_opt"], scaler)
+                (a.params, a.grads, a.exp_avg, a.exp_avg_sq), self._small_grad_ranges(), gidx[bn.g_camera], scaler)
             self._step_gidx = gidx
         gidx = self._step_gidx
         nears, fars = self._nears_fars(N, True)
@@ -854,7 +918,7 @@ class RenderEngine:
         # The previous call may have run THIS batch's sampling front (pose correction + both proposal levels) in its optimiser launch
         # (TnTrainStep.next_sampling): valid when the batch is the one it was planned for, the sampler's state is what was predicted, and nobody has
         # written the parameters through torch since (our kernels do not move the version counter; copy_ / load_state_dict do).
-        plan, fwd_buf = self.__dict__.pop("_planned", None), None
+        plan, self._planned, fwd_buf = self._planned, None, None
         if plan is not None and jitters is None and plan["call"] is call and plan["N"] == N and plan["step"] == step \
                 and plan["ptrs"] == (origins.data_ptr(), directions.data_ptr(), cam.data_ptr()) and plan["anneal"] == float(self.anneal) \
                 and plan["updated"] == bool(updated) and plan["version"] == a.params._version:
@@ -868,7 +932,7 @@ class RenderEngine:
         # (drawn now: the same sequence of draws, one iteration early), its anneal exponent and whether its proposal networks take a gradient
         next_plan = None
         pend = ops._PENDING_SAMPLE
-        if _NEXT_SAMPLING and self.next_sampling and drew and step is not None and pend is not None and int(pend[0].num_rays) == N and N % 4 == 0:
+        if _NEXT_SAMPLING and self.next_sampling and drew and step is not None and pend is not None and pend.num_rays == N and N % 4 == 0:
             since = (0 if updated else self.steps_since_update) + 1  # (what step_cb leaves behind this iteration)
             n_updated = since > self.update_schedule(step) or step < 10
             next_plan = (list(self._uniforms().take((3, N)).unbind(0)), self.anneal_for_step(step + 1), bool(n_updated))
@@ -879,8 +943,6 @@ class RenderEngine:
         # Worked out on copies and COMMITTED only after the library accepted the call: tn_train_step validates every stage's arguments and
         # workspace sizes before its first launch, so a refused call (TN_EINVAL) has enqueued nothing and must leave the host counters where the
         # device's are.
-        if not hasattr(self, "group_steps"):
-            self.group_steps = {}
         group_steps = dict(self.group_steps)
         ranges = []
         for g in a.optimised_groups:
@@ -900,8 +962,8 @@ class RenderEngine:
         finally:
             self._set_grad_zero(False)  # the promise holds for this call's scatters only -- also when the call was refused
         if next_plan is not None and call.next_buf is not None:
-            o2, d2, c2 = pend[1][3], pend[1][4], pend[1][5]  # (sample_rays_deferred: (u, cameras, cache) + (origins, directions, camera_indices, ...))
-            self._planned = {"call": call, "N": N, "step": step + 1, "ptrs": (o2.data_ptr(), d2.data_ptr(), c2.data_ptr()), "anneal": float(next_plan[1]),
+            ptrs = (pend.origins.data_ptr(), pend.directions.data_ptr(), pend.camera_indices.data_ptr())
+            self._planned = {"call": call, "N": N, "step": step + 1, "ptrs": ptrs, "anneal": float(next_plan[1]),
                              "updated": next_plan[2], "jitters": next_plan[0], "buf": call.next_buf, "version": a.params._version}
         self.adam_step_count += 1
         self.group_steps = group_steps
@@ -911,20 +973,16 @@ class RenderEngine:
             self.steps_since_update = 0
         L = acc["L"]
         self._last_losses16, self._last_num_rays = L, int(N)  # (train_metrics)
-        return {"rgb_loss": L[0], "thermal_loss": L[1], "tv_pixel_loss": L[2], "cross_channel_loss": L[3], "interlevel_loss": L[8],
-                "distortion_loss": L[9], "camera_opt_regularizer": L[11]}
-
-    def _metric_poses(self):
-        return [p for p in ((self.pose, self.pose_thermal) if self.separate else (self.pose,)) if p is not None]
+        return self._loss_dict(L)
 
     def pose_metrics(self) -> Dict[str, Tensor]:
         """camera_opt_translation / camera_opt_rotation (cameras/camera_optimizers.py:197-202) of the CURRENT pose corrections, one small launch.
         The reference's metrics_dict holds them as they are when the forward runs -- before the iteration's optimiser step: take them before
         train_step and hand them to train_metrics."""
-        poses = self._metric_poses()
+        poses = [bn.pose for bn in self.nets.values() if bn.pose is not None]
         out: Dict[str, Tensor] = {}
         if poses:
-            dummy = self.__dict__.get("_metric_ones")
+            dummy = self._metric_ones
             if dummy is None:
                 dummy = self._metric_ones = torch.ones(16, device=poses[0].device)
             m = torch.empty(8, device=poses[0].device)
@@ -937,7 +995,7 @@ class RenderEngine:
         """metrics_dict of the iteration train_step just enqueued (models/thermal_nerfacto.py:253-282): the PSNR per spectrum from the pixel-loss
         sums and the distortion metric -- one small launch (tn_train_metrics) behind the step, no host synchronisation -- plus `pose_metrics`
         (see there).  Call before the next train_step (the loss vector is the step's accumulator)."""
-        L = self.__dict__.get("_last_losses16")
+        L = self._last_losses16
         if L is None:
             raise RuntimeError("train_metrics: no train_step has run")
         c = self.cfg
@@ -963,14 +1021,14 @@ class RenderEngine:
         # found_inf by the kernels that write the gradients -- only when the gradients are final where they are written (no data-parallel exchange
         # behind the backward: with one, an inf on another rank arrives through the all-reduce and the explicit check after it stays)
         kflags = grad_scaler if (grad_scaler is not None and grad_scaler.enabled and grad_hook is None and _FUSE) else None
-        if self.__dict__.get("_kflags_scaler") is not kflags:
+        if self._kflags_scaler is not kflags:
             self._set_kernel_flags(kflags)
             self._kflags_scaler = kflags
         if not self.arena.grads_clean:  # (the previous step's optimiser launch consumed the gradients: nothing to fill)
             self.sync_params()
             self.arena.zero_grad()
         if (_ONE_CALL_STEP and _FUSE and _ONE_CALL_BWD and kflags is not None and scheduled and not self.separate and self.pose is not None
-                and not self.overlap_adam and getattr(self, "scatter_events", None) is None
+                and not self.overlap_adam and self.scatter_events is None
                 and self.field.num_channels == 4 and "camera_opt" in self.arena.optimised_groups):
             losses = self._train_step_one_call(origins, directions, cam, image, is_thermal, jitters, grad_scaler, step)
             self._set_grad_zero(False)  # the promise holds for this iteration's scatters only (anybody may call the ops on these grids next)

@@ -168,70 +168,39 @@ class _RenderFn(torch.autograd.Function):
                     view = arena.grad_view(n)
                     detached[n] = view.clone()
                     view.zero_()
-        d_od = {}
         for sfx, br in branches.items():
             g_comp, g_dens, g_w = per[sfx]
-            fld = eng.field_thermal if sfx else eng.field
-            props = eng.props_thermal if sfx else eng.props
-            pose = eng.pose_thermal if sfx else eng.pose
-            lv = br.levels
-            d_o = torch.zeros((N, 3), device=dev) if pose is not None else None
-            d_d = torch.zeros((N, 3), device=dev) if pose is not None else None
-            dw2 = (g_w[2][..., 0].contiguous() if g_w[2] is not None else z(lv[2].weights))  # read only (tn_render_bwd)
+            bn = eng.nets[sfx]
+            if bn.pose is not None:
+                br.d_origins, br.d_directions = torch.zeros((N, 3), device=dev), torch.zeros((N, 3), device=dev)
+            dw2 = (g_w[2][..., 0].contiguous() if g_w[2] is not None else z(br.levels[2].weights))  # read only (tn_render_bwd)
+            d_comp = g_comp.contiguous() if g_comp is not None else z(br.comp)
             both, neither = g_w[0] is not None and g_w[1] is not None, g_w[0] is None and g_w[1] is None
             if br.fwd_buf is not None and (neither or (both and br.prop_grad)):
                 # the whole backward of the branch as ONE call of the C ABI (tn_render_rays_train_bwd), exactly as the fused step issues it
                 # (engine.loss_and_backward): renderer backward, the density loss's own gradient added, both proposal networks on the
                 # library's companion streams, field backward with d position and table scatter
                 pg = both and br.prop_grad
-                ops.render_rays_train_bwd(props, fld, br.fwd_buf, br.origins, br.directions, cam, eng.counts,
-                                          (g_comp.contiguous() if g_comp is not None else z(br.comp)),
+                ops.render_rays_train_bwd(bn.props, bn.field, br.fwd_buf, br.origins, br.directions, cam, eng.counts, d_comp,
                                           [g_w[0][..., 0].contiguous() if pg else None, g_w[1][..., 0].contiguous() if pg else None, dw2],
-                                          g_dens[..., 0].contiguous() if g_dens is not None else None, d_o, d_d,
+                                          g_dens[..., 0].contiguous() if g_dens is not None else None, br.d_origins, br.d_directions,
                                           tag="main", side_tags=("side0" + sfx, "side1" + sfx), prop_enc_saved=br.prop_enc_saved)
-                d_od[sfx] = (d_o, d_d)
                 continue
-            d_rgb, d_dens = ops.render_bwd(lv[2].e_bins, lv[2].density, br.rgb_samples, lv[2].weights,
-                                           (g_comp.contiguous() if g_comp is not None else z(br.comp)), dw2)
-            if g_dens is not None:
-                d_dens += g_dens[..., 0]
-            # same schedule as the fused step (engine.loss_and_backward): the level-0 proposal network (2/3 of the proposal work) on the side
-            # stream beside the main field's backward, the level-1 network on a second one
-            side = None
-            if br.prop_grad and g_w[0] is not None:
-                g0 = g_w[0][..., 0].contiguous()
-                side = eng._side_stream()
-                side.wait_stream(torch.cuda.current_stream())  # g0, d_o, d_d are produced / zeroed on the main stream
-                with torch.cuda.stream(side):
-                    dd = ops.weights_bwd(lv[0].e_bins, lv[0].density, lv[0].weights, g0)
-                    ops.prop_density_bwd(props[0], br.origins, br.directions, lv[0].e_bins, dd, d_o, d_d, tag="side0")
-            side1 = None
-            if br.prop_grad and g_w[1] is not None:
-                g1 = g_w[1][..., 0].contiguous()
-                side1 = eng._side_stream(1)
-                side1.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side1):
-                    dd = ops.weights_bwd(lv[1].e_bins, lv[1].density, lv[1].weights, g1)
-                    ops.prop_density_bwd(props[1], br.origins, br.directions, lv[1].e_bins, dd, d_o, d_d, tag="side1")
-            ops.field_bwd(fld, br.origins, br.directions, cam, lv[2].e_bins, d_dens, d_rgb, d_o, d_d)
-            for st in (side, side1):
-                if st is not None:
-                    torch.cuda.current_stream().wait_stream(st)
-            d_od[sfx] = (d_o, d_d)
+            # launch by launch, on the fused step's schedule (engine.branch_backward); a proposal level runs only with an incoming gradient
+            dws = [g_w[i][..., 0].contiguous() if (br.prop_grad and g_w[i] is not None) else None for i in range(2)] + [dw2]
+            eng.branch_backward(bn, br, cam, d_comp, dws, g_dens[..., 0] if g_dens is not None else None, br.d_origins, br.d_directions)
         if g_d2 is not None or g_d2t is not None:
             b, bt = branches[""], branches["_thermal"]
             if g_d2 is not None:
-                ops.field_bwd(eng.field, bt.origins, bt.directions, cam, bt.levels[-1].e_bins, g_d2[..., 0].contiguous(), None, *d_od["_thermal"],
+                ops.field_bwd(eng.field, bt.origins, bt.directions, cam, bt.levels[-1].e_bins, g_d2[..., 0].contiguous(), None, bt.d_origins, bt.d_directions,
                               tag="cross")
             if g_d2t is not None:
-                ops.field_bwd(eng.field_thermal, b.origins, b.directions, cam, b.levels[-1].e_bins, g_d2t[..., 0].contiguous(), None, *d_od[""],
+                ops.field_bwd(eng.field_thermal, b.origins, b.directions, cam, b.levels[-1].e_bins, g_d2t[..., 0].contiguous(), None, b.d_origins, b.d_directions,
                               tag="cross")
         for sfx, br in branches.items():
-            pose = eng.pose_thermal if sfx else eng.pose
-            if pose is None:
-                continue
-            ops.pose_apply_bwd(pose, eng.frozen_thermal if sfx else eng.frozen_rgb, cam, br.directions_in, *d_od[sfx],
-                               eng.pose_thermal_grad if sfx else eng.pose_grad)
+            bn = eng.nets[sfx]
+            if bn.pose is not None:
+                ops.pose_apply_bwd(bn.pose, bn.frozen, cam, br.directions_in, br.d_origins, br.d_directions, bn.pose_grad)
         # Hand the arena's gradient views to autograd as the parameters' gradients.  None (= "no gradient", as under the reference's no_grad)
         # for every parameter this step did not differentiate: the proposal networks on iterations where the sampler did not update them
         # (ray_samplers.py:591,605-610) and the thermal twins that shared mode never evaluates -- torch.optim.Adam skips a parameter whose
@@ -243,10 +212,11 @@ class _RenderFn(torch.autograd.Function):
         if hit is None or hit[0] is not ctx.names:  # (positions in ctx.names of the parameters this kind of iteration differentiates)
             live = set()
             for sfx, pgrad in key:
-                live.update(arena.group_keys["fields_thermal" if sfx else "fields"])
-                live.update(arena.group_keys["camera_opt_thermal" if sfx else "camera_opt"])
+                bn = eng.nets[sfx]
+                live.update(arena.group_keys[bn.g_fields])
+                live.update(arena.group_keys[bn.g_camera])
                 if pgrad:
-                    live.update(arena.group_keys["proposal_networks_thermal" if sfx else "proposal_networks"])
+                    live.update(arena.group_keys[bn.g_props])
             hit = cache[key] = (ctx.names, [i for i, n in enumerate(ctx.names) if n in live])
         names, plist = ctx.names, ctx.params
         pg = [None] * len(names)
@@ -489,7 +459,7 @@ class ThermalNerfactoModel(nn.Module):
             pg = bool(outputs.get(f"_prop_grad{s_}", self.training and ws[0].requires_grad))
             branches.append((s_, [r.s_bins for r in outputs[f"ray_samples_list{s_}"]], pg))
             if sep:
-                comp = outputs["rgb_thermal"] if s_ else outputs["rgb"]
+                comp = outputs[f"rgb{s_}"]
             else:
                 comp = outputs["rgbt"] if "rgbt" in outputs else torch.cat([outputs["rgb"], outputs["rgb_thermal"]], -1)
             ts += [comp, *ws]

@@ -18,6 +18,7 @@ from . import _lib
 from ._lib import TnField, TnGrid, TnPropNet, check
 
 TN_MAX_SAMPLES = _lib.TN_MAX_SAMPLES
+LOSS_LINES = _lib.TN_LOSS_LINES  # 64-byte lines the loss sums are spread over (train_losses), added up by losses_finish / pose_bwd_finish
 
 
 def level_resolutions(num_levels: int, min_res: int, max_res: int) -> List[float]:
@@ -92,8 +93,37 @@ def _grid_struct(table: Tensor, grad: Optional[Tensor], num_levels: int, log2_ha
     return g
 
 
+class _NetParams:
+    """What PropNetParams and FieldParams share: the checked C struct of the network, built once and kept until a tensor field is assigned."""
+
+    def __setattr__(self, name, value):  # a new tensor in any field: the checked C struct is rebuilt at the next call
+        if name != "nonfinite_flag" and name != "grad_is_zero":  # (both are part of the cache's key: toggling them per step rebuilds nothing)
+            self.__dict__.pop("_cs", None)
+        object.__setattr__(self, name, value)
+
+    def cstruct(self, need_grad: bool = False):
+        g = self.grads or {}
+        if need_grad and not g:
+            raise ValueError("gradient buffers required")
+        # the parameters are views of the arena: their addresses do not change from step to step, so the checked struct is built once
+        nf = self.nonfinite_flag
+        # (key: the table's addresses stand for all of them -- every tensor is a view of the same arena; assigning a field drops the cached
+        # struct, see __setattr__ -- 25 data_ptr() calls per struct and step were ~10 us each on the path to the two library calls)
+        gt = g.get("table")
+        key = (self.table.data_ptr(), gt.data_ptr() if gt is not None else 0, len(g), nf.data_ptr() if nf is not None else 0, bool(self.grad_is_zero))
+        cache = self.__dict__.get("_cs")
+        if cache is None:
+            cache = self.__dict__["_cs"] = {}
+        s = cache.get(key)
+        if s is None:
+            if len(cache) >= 8:  # (addresses moved, flags toggled: a handful of variants at most)
+                cache.clear()
+            s = cache[key] = self._build_cstruct(g)
+        return s
+
+
 @dataclass
-class PropNetParams:
+class PropNetParams(_NetParams):
     """HashMLPDensityField parameters (fields/density_fields.py:34-118); tensors are views of the caller's storage."""
 
     table: Tensor
@@ -105,36 +135,12 @@ class PropNetParams:
     log2_hashmap_size: int
     res: List[float]
     grads: Optional[dict] = None  # same keys -> gradient tensors
-
-    def __setattr__(self, name, value):  # a new tensor in any field: the checked C struct is rebuilt at the next call
-        self.__dict__.pop("_cs", None)
-        object.__setattr__(self, name, value)
-
-    def cstruct(self, need_grad: bool = False) -> TnPropNet:
-        g = self.grads or {}
-        if need_grad and not g:
-            raise ValueError("gradient buffers required")
-        # the parameters are views of the arena: their addresses do not change from step to step, so the checked struct is built once
-        nf = self.__dict__.get("nonfinite_flag")  # set by the engine: the optimiser group's found_inf entry (DeviceGradScaler), or absent
-        # (key: the table's addresses stand for all of them -- every tensor is a view of the same arena; assigning a field drops the cached
-        # struct, see __setattr__ -- 25 data_ptr() calls per struct and step were ~10 us each on the path to the two library calls)
-        gt = g.get("table")
-        key = (self.table.data_ptr(), gt.data_ptr() if gt is not None else 0, len(g), nf.data_ptr() if nf is not None else 0,
-               bool(self.__dict__.get("grad_is_zero", False)))
-        cache = self.__dict__.get("_cs")
-        if cache is None:
-            cache = self.__dict__["_cs"] = {}
-        s = cache.get(key)
-        if s is None:
-            if len(cache) >= 8:  # (addresses moved, flags toggled: a handful of variants at most)
-                cache.clear()
-            s = cache[key] = self._build_cstruct(g)
-        return s
+    nonfinite_flag: Optional[Tensor] = None  # set by the engine: the optimiser group's found_inf entry (DeviceGradScaler) the table scatter raises
+    grad_is_zero: bool = False  # set by the engine: the promise of TnGrid.table_grad_is_zero
 
     def _build_cstruct(self, g) -> TnPropNet:
         s = TnPropNet()
-        s.grid = _grid_struct(self.table, g.get("table"), self.num_levels, self.log2_hashmap_size, self.res, self.__dict__.get("nonfinite_flag"),
-                              bool(self.__dict__.get("grad_is_zero", False)))
+        s.grid = _grid_struct(self.table, g.get("table"), self.num_levels, self.log2_hashmap_size, self.res, self.nonfinite_flag, bool(self.grad_is_zero))
         H, F = 16, self.num_levels * 2
         s.w0, s.b0 = _f32(self.w0, "w0", (H, F)), _f32(self.b0, "b0", (H,))
         s.w1, s.b1 = _f32(self.w1, "w1", (1, H)), _f32(self.b1, "b1", (1,))
@@ -143,11 +149,8 @@ class PropNetParams:
         return s
 
 
-_FIELD_KEYS = ("w0", "b0", "w1", "b1", "hw0", "hb0", "hw1", "hb1", "hw2", "hb2", "emb")
-
-
 @dataclass
-class FieldParams:
+class FieldParams(_NetParams):
     """ThermalNerfactoField parameters (fields/thermal_nerfacto_field.py:37-99)."""
 
     table: Tensor
@@ -167,6 +170,8 @@ class FieldParams:
     res: List[float]
     num_channels: int
     grads: Optional[dict] = None
+    nonfinite_flag: Optional[Tensor] = None  # (as PropNetParams)
+    grad_is_zero: bool = False
     _ws: dict = field(default_factory=dict, repr=False)
 
     def shapes(self):
@@ -174,34 +179,11 @@ class FieldParams:
         return {"w0": (64, 32), "b0": (64,), "w1": (16, 64), "b1": (16,), "hw0": (64, 63), "hb0": (64,), "hw1": (64, 64),
                 "hb1": (64,), "hw2": (C_, 64), "hb2": (C_,), "emb": (I, 32)}
 
-    def __setattr__(self, name, value):  # a new tensor in any field: the checked C struct is rebuilt at the next call
-        self.__dict__.pop("_cs", None)
-        object.__setattr__(self, name, value)
-
-    def cstruct(self, need_grad: bool = False) -> TnField:
+    def _build_cstruct(self, g) -> TnField:
         if self.num_levels * 2 != 32:
             raise ValueError("the fused main-field kernels are built for 16 levels x 2 features")
-        g = self.grads or {}
-        if need_grad and not g:
-            raise ValueError("gradient buffers required")
-        nf = self.__dict__.get("nonfinite_flag")
-        gt = g.get("table")  # (as PropNetParams.cstruct: the table's addresses stand for the arena's; __setattr__ drops the cache)
-        key = (self.table.data_ptr(), gt.data_ptr() if gt is not None else 0, len(g), nf.data_ptr() if nf is not None else 0,
-               bool(self.__dict__.get("grad_is_zero", False)))
-        cache = self.__dict__.get("_cs")
-        if cache is None:
-            cache = self.__dict__["_cs"] = {}
-        s = cache.get(key)
-        if s is None:
-            if len(cache) >= 8:
-                cache.clear()
-            s = cache[key] = self._build_cstruct(g)
-        return s
-
-    def _build_cstruct(self, g) -> TnField:
         s = TnField()
-        s.grid = _grid_struct(self.table, g.get("table"), self.num_levels, self.log2_hashmap_size, self.res, self.__dict__.get("nonfinite_flag"),
-                              bool(self.__dict__.get("grad_is_zero", False)))
+        s.grid = _grid_struct(self.table, g.get("table"), self.num_levels, self.log2_hashmap_size, self.res, self.nonfinite_flag, bool(self.grad_is_zero))
         for k, shp in self.shapes().items():
             setattr(s, k, _f32(getattr(self, k), k, shp))
             setattr(s, "g" + k, _f32(g.get(k), "g" + k, shp, optional=True))
@@ -273,18 +255,34 @@ class ImageCache:
                           image_idx.to(device, torch.int64).contiguous())
 
 
+def _sample_outputs(cache: ImageCache, num_rays: int, u: Tensor, patch_size: int, camera_indices: bool = True, rays: bool = True):
+    """What the three sampling entry points share: the check of `u` and the uninitialised outputs -> ray_indices [N,3] int64, image [N,3],
+    is_thermal [N], camera_indices [N] int64 (or None), and with rays=True origins, directions [N,3], pixel_area, directions_norm [N,1]."""
+    dev = cache.buffer.device
+    if u.device != dev or u.dtype != torch.float32 or not u.is_contiguous() or tuple(u.shape) != (num_rays // (patch_size * patch_size), 3):
+        raise ValueError(f"u must be a contiguous fp32 [{num_rays // (patch_size * patch_size)}, 3] tensor on {dev}")
+    idx = torch.empty((num_rays, 3), dtype=torch.int64, device=dev)
+    cam = torch.empty((num_rays,), dtype=torch.int64, device=dev) if camera_indices else None
+    img, is_th = torch.empty((num_rays, 3), device=dev), torch.empty((num_rays,), device=dev)
+    if not rays:
+        return idx, img, is_th, cam
+    return (idx, img, is_th, cam, torch.empty((num_rays, 3), device=dev), torch.empty((num_rays, 3), device=dev), torch.empty((num_rays, 1), device=dev),
+            torch.empty((num_rays, 1), device=dev))
+
+
+def _camera_args(cameras: dict):
+    """c2w [C,3,4], fx, fy, cx, cy [C], optional distortion [C,6] of `cameras`, checked, and C: the camera arguments of tn_sample_rays in its order"""
+    Cn = cameras["c2w"].shape[0]
+    return (_f32(cameras["c2w"], "c2w", (Cn, 3, 4)), *(_f32(cameras[k], k, (Cn,)) for k in ("fx", "fy", "cx", "cy")),
+            _f32(cameras.get("distortion"), "distortion", (Cn, 6), optional=True), Cn)
+
+
 def sample_pixels(cache: ImageCache, num_rays: int, u: Tensor, patch_size: int = 2, want_camera_indices: bool = False):
     """PatchPixelSampler.sample + ground-truth gather on the device -> ray_indices [N,3] int64 (camera,row,col), image [N,3], is_thermal [N]
     (+ camera_indices [N] int64 with want_camera_indices=True: ray_indices[:,0] as a contiguous vector).
     u [num_rays / patch^2, 3]: the uniforms the reference would draw with torch.rand, image after image."""
     n_img = cache.offsets.shape[0]
-    dev = cache.buffer.device
-    if u.device != dev or u.dtype != torch.float32 or not u.is_contiguous() or tuple(u.shape) != (num_rays // (patch_size * patch_size), 3):
-        raise ValueError(f"u must be a contiguous fp32 [{num_rays // (patch_size * patch_size)}, 3] tensor on {dev}")
-    idx = torch.empty((num_rays, 3), dtype=torch.int64, device=dev)
-    img = torch.empty((num_rays, 3), dtype=torch.float32, device=dev)
-    is_th = torch.empty((num_rays,), dtype=torch.float32, device=dev)
-    cam = torch.empty((num_rays,), dtype=torch.int64, device=dev) if want_camera_indices else None
+    idx, img, is_th, cam = _sample_outputs(cache, num_rays, u, patch_size, camera_indices=want_camera_indices, rays=False)
     p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     check(_lib.load().tn_sample_pixels(p(cache.buffer), p(cache.offsets), p(cache.heights), p(cache.widths), p(cache.is_thermal), p(cache.image_idx),
                                        n_img, p(u), num_rays, patch_size, p(idx), p(img), p(is_th), p(cam) if cam is not None else None, _stream()),
@@ -298,31 +296,41 @@ def sample_rays(cache: ImageCache, num_rays: int, u: Tensor, cameras: dict, patc
     RayBundle, cameras/cameras.py:904-928).  cameras: c2w [C,3,4], fx, fy, cx, cy [C], optional distortion [C,6].
     want_pixel_area=False: the bundle's pixel_area (which thermal-nerfacto never reads) is not computed -- two of the three undistortions per ray."""
     n_img = cache.offsets.shape[0]
-    dev = cache.buffer.device
-    if u.device != dev or u.dtype != torch.float32 or not u.is_contiguous() or tuple(u.shape) != (num_rays // (patch_size * patch_size), 3):
-        raise ValueError(f"u must be a contiguous fp32 [{num_rays // (patch_size * patch_size)}, 3] tensor on {dev}")
-    idx = torch.empty((num_rays, 3), dtype=torch.int64, device=dev)
-    cam = torch.empty((num_rays,), dtype=torch.int64, device=dev)
-    img, is_th, o, d, area, nrm = (torch.empty((num_rays, 3), device=dev), torch.empty((num_rays,), device=dev), torch.empty((num_rays, 3), device=dev),
-                                   torch.empty((num_rays, 3), device=dev), torch.empty((num_rays, 1), device=dev), torch.empty((num_rays, 1), device=dev))
-    c2w = cameras["c2w"]
-    Cn = c2w.shape[0]
+    idx, img, is_th, cam, o, d, area, nrm = _sample_outputs(cache, num_rays, u, patch_size)
     p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     check(_lib.load().tn_sample_rays(p(cache.buffer), p(cache.offsets), p(cache.heights), p(cache.widths), p(cache.is_thermal), p(cache.image_idx),
-                                     n_img, p(u), num_rays, patch_size, p(idx), p(img), p(is_th), p(cam),
-                                     _f32(c2w, "c2w", (Cn, 3, 4)), _f32(cameras["fx"], "fx", (Cn,)), _f32(cameras["fy"], "fy", (Cn,)),
-                                     _f32(cameras["cx"], "cx", (Cn,)), _f32(cameras["cy"], "cy", (Cn,)),
-                                     _f32(cameras.get("distortion"), "distortion", (Cn, 6), optional=True), Cn, p(o), p(d), p(area) if want_pixel_area else None,
-                                     p(nrm), _stream()),
+                                     n_img, p(u), num_rays, patch_size, p(idx), p(img), p(is_th), p(cam), *_camera_args(cameras), p(o), p(d),
+                                     p(area) if want_pixel_area else None, p(nrm), _stream()),
           "tn_sample_rays")
     if with_bundle_extras:
         return o, d, cam, img, is_th, idx, area, nrm
     return o, d, cam, img, is_th, idx
 
 
-# A batch whose sampling has been handed to the NEXT tn_train_step: that call runs it in co-work blocks of its optimiser launch (TnTrainStep.next_sample);
-# if no such call comes first, flush_pending_sample() launches it as a kernel of its own.  One slot per process: the training loop has one data manager.
-_PENDING_SAMPLE: Optional[tuple] = None
+@dataclass
+class PendingSample:
+    """A batch whose sampling has been handed to the NEXT tn_train_step: that call runs it in co-work blocks of its optimiser launch
+    (TnTrainStep.next_sample); if no such call comes first, flush_pending_sample() launches it as a kernel of its own."""
+
+    args: "_lib.TnSampleRays"  # the argument block the library reads
+    num_rays: int
+    origins: Tensor
+    directions: Tensor
+    camera_indices: Tensor
+    image: Tensor
+    is_thermal: Tensor
+    ray_indices: Tensor
+    pixel_area: Tensor
+    directions_norm: Tensor
+    keep: tuple  # the inputs the block points into (u, cameras, cache): alive until the batch has been sampled
+
+    def outputs(self):
+        """the tensors sample_rays(with_bundle_extras=True) returns, in its order"""
+        return (self.origins, self.directions, self.camera_indices, self.image, self.is_thermal, self.ray_indices, self.pixel_area, self.directions_norm)
+
+
+# One slot per process: the training loop has one data manager.
+_PENDING_SAMPLE: Optional[PendingSample] = None
 
 
 def sample_rays_deferred(cache: ImageCache, num_rays: int, u: Tensor, cameras: dict, patch_size: int = 2):
@@ -332,30 +340,17 @@ def sample_rays_deferred(cache: ImageCache, num_rays: int, u: Tensor, cameras: d
     global _PENDING_SAMPLE
     flush_pending_sample()
     n_img = cache.offsets.shape[0]
-    dev = cache.buffer.device
-    if u.device != dev or u.dtype != torch.float32 or not u.is_contiguous() or tuple(u.shape) != (num_rays // (patch_size * patch_size), 3):
-        raise ValueError(f"u must be a contiguous fp32 [{num_rays // (patch_size * patch_size)}, 3] tensor on {dev}")
-    idx = torch.empty((num_rays, 3), dtype=torch.int64, device=dev)
-    cam = torch.empty((num_rays,), dtype=torch.int64, device=dev)
-    img, is_th, o, d, area, nrm = (torch.empty((num_rays, 3), device=dev), torch.empty((num_rays,), device=dev), torch.empty((num_rays, 3), device=dev),
-                                   torch.empty((num_rays, 3), device=dev), torch.empty((num_rays, 1), device=dev), torch.empty((num_rays, 1), device=dev))
-    c2w = cameras["c2w"]
-    Cn = c2w.shape[0]
+    idx, img, is_th, cam, o, d, area, nrm = _sample_outputs(cache, num_rays, u, patch_size)
     st = _lib.TnSampleRays()
     p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     st.images, st.image_offsets, st.heights, st.widths = p(cache.buffer), p(cache.offsets), p(cache.heights), p(cache.widths)
     st.is_thermal, st.image_idx, st.num_images = p(cache.is_thermal), p(cache.image_idx), n_img
     st.u, st.num_rays, st.patch_size = p(u), num_rays, patch_size
     st.ray_indices, st.image, st.is_thermal_out, st.camera_indices = p(idx), p(img), p(is_th), p(cam)
-    st.c2w = _f32(c2w, "c2w", (Cn, 3, 4))
-    st.fx, st.fy = _f32(cameras["fx"], "fx", (Cn,)), _f32(cameras["fy"], "fy", (Cn,))
-    st.cx, st.cy = _f32(cameras["cx"], "cx", (Cn,)), _f32(cameras["cy"], "cy", (Cn,))
-    st.distortion = _f32(cameras.get("distortion"), "distortion", (Cn, 6), optional=True)
-    st.num_cameras = Cn
+    st.c2w, st.fx, st.fy, st.cx, st.cy, st.distortion, st.num_cameras = _camera_args(cameras)
     st.origins, st.directions, st.pixel_area, st.directions_norm = p(o), p(d), p(area), p(nrm)
-    outs = (o, d, cam, img, is_th, idx, area, nrm)
-    _PENDING_SAMPLE = (st, (u, cameras, cache) + outs)
-    return outs
+    _PENDING_SAMPLE = PendingSample(st, int(num_rays), o, d, cam, img, is_th, idx, area, nrm, keep=(u, cameras, cache))
+    return _PENDING_SAMPLE.outputs()
 
 
 def flush_pending_sample() -> None:
@@ -365,7 +360,7 @@ def flush_pending_sample() -> None:
     if pend is None:
         return
     _PENDING_SAMPLE = None
-    check(_lib.load().tn_sample_rays_args(C.byref(pend[0]), _stream()), "tn_sample_rays_args")
+    check(_lib.load().tn_sample_rays_args(C.byref(pend.args), _stream()), "tn_sample_rays_args")
 
 
 # ------------------------------------------------------------------------------------------------ a1 / a4
@@ -439,7 +434,7 @@ def pose_bwd_finish(pose: Tensor, frozen: Optional[Tensor], cam: Tensor, directi
     check(_lib.load().tn_pose_bwd_finish(_f32(pose, "pose", (Cn, 6)), _u8(frozen, Cn), _i64(cam, "camera_indices", (N,)),
                                          _f32(directions_in, "directions", (N, 3)), _f32(d_o, "d_origins", (N, 3)), _f32(d_d, "d_directions", (N, 3)),
                                          N, Cn, _f32(grad_pose, "grad_pose", (Cn, 6)),
-                                         _f32(loss_lines, "loss_lines", (_lib.TN_LOSS_LINES, 16), optional=True), _f32(losses16, "losses16", optional=True),
+                                         _f32(loss_lines, "loss_lines", (LOSS_LINES, 16), optional=True), _f32(losses16, "losses16", optional=True),
                                          float(trans_pen), float(rot_pen), float(scale), _f32(reg_out, "reg_out"), _stream()), "tn_pose_bwd_finish")
 
 
@@ -545,19 +540,36 @@ def _nbytes(t: Optional[Tensor]) -> int:
     return 0 if t is None else t.numel() * t.element_size()
 
 
-_PROP_WS: dict = {}
+_SCRATCH: dict = {}
+
+
+def _scratch(key: tuple, need: int, dtype, device) -> Tensor:
+    """Device scratch kept between calls and grown on demand.  `key` decides who shares a buffer: calls that may be in flight at the same time
+    (different streams) must not, so every key names its device and a tag or a stream."""
+    t = _SCRATCH.get(key)
+    if t is None or t.numel() < need:
+        t = _SCRATCH[key] = torch.empty(need, dtype=dtype, device=device)
+    return t
+
+
+def _prop_ws(device, num_points: int, tag: str) -> Tensor:
+    return _scratch(("prop", str(device), tag), int(_lib.load().tn_prop_workspace_bytes(num_points)), torch.uint8, device)
+
+
+def _bwd_tmp(device, tag: str, N: int, S0: int, S1: int, S2: int, Cc: int) -> Tensor:
+    return _scratch(("bwd_tmp", str(device), tag), int(_lib.load().tn_render_rays_train_bwd_tmp_floats(N, S0, S1, S2, Cc)), torch.float32, device)
+
+
+def _render_scratch(dev, st) -> Tensor:
+    """per-block min / max of the sample midpoints (contents irrelevant between calls): one buffer per (device, stream)"""
+    return _scratch(("render", dev.index, st.value), _lib.TN_RENDER_SCRATCH_FLOATS, torch.float32, dev)
 
 
 def prop_density_bwd(net: PropNetParams, origins: Tensor, directions: Tensor, e_bins: Tensor, d_density: Tensor,
                      d_origins: Optional[Tensor] = None, d_directions: Optional[Tensor] = None, tag: str = "") -> None:
     """`tag` names the scratch buffer: calls that may be in flight at the same time (different streams) must use different tags."""
     N, S = e_bins.shape[0], e_bins.shape[1] - 1
-    need = int(_lib.load().tn_prop_workspace_bytes(N * S))
-    key = (str(origins.device), tag)
-    ws = _PROP_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=origins.device)
-        _PROP_WS[key] = ws
+    ws = _prop_ws(origins.device, N * S, tag)
     s = net.cstruct(need_grad=True)
     check(_lib.load().tn_prop_density_bwd(C.byref(s), _f32(origins, "origins", (N, 3)), _f32(directions, "directions", (N, 3)),
                                           _f32(e_bins, "e_bins", (N, S + 1)), _f32(d_density, "d_density", (N, S)), N, S, C.c_void_p(ws.data_ptr()), _nbytes(ws),
@@ -654,9 +666,6 @@ def field_dense_fold(fld: FieldParams, num_points: int, level_begin: int, level_
     check(_lib.load().tn_field_dense_fold(C.byref(s), num_points, level_begin, level_end, _f32(dense_sum, "dense_sum"), _stream()), "tn_field_dense_fold")
 
 
-_SCATTER_WS: dict = {}
-
-
 def hash_scatter(table: Tensor, table_grad: Tensor, num_levels: int, log2_hashmap_size: int, res, origins: Tensor, directions: Tensor, e_bins: Tensor,
                  g_enc: Tensor, d_origins: Optional[Tensor] = None, d_directions: Optional[Tensor] = None, use_workspace: bool = True,
                  grad_is_zero: bool = False) -> None:
@@ -670,11 +679,7 @@ def hash_scatter(table: Tensor, table_grad: Tensor, num_levels: int, log2_hashma
     ld = -1 if level_major else g_enc.shape[1]
     ws = None
     if use_workspace:
-        need = int(_lib.load().tn_hash_scatter_workspace_bytes(N * S, num_levels))
-        ws = _SCATTER_WS.get(str(origins.device))
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=origins.device)
-            _SCATTER_WS[str(origins.device)] = ws
+        ws = _scratch(("scatter", str(origins.device)), int(_lib.load().tn_hash_scatter_workspace_bytes(N * S, num_levels)), torch.uint8, origins.device)
     g = _grid_struct(table, table_grad, num_levels, log2_hashmap_size, res, grad_is_zero=grad_is_zero)
     check(_lib.load().tn_hash_scatter(C.byref(g), _f32(origins, "origins", (N, 3)), _f32(directions, "directions", (N, 3)), _f32(e_bins, "e_bins", (N, S + 1)),
                                       _f32(g_enc, "g_enc", None if level_major else (N * S, ld)), ld, N, S, _f32(d_origins, "d_origins", (N, 3), True),
@@ -763,6 +768,17 @@ def render_rays_eval(props: Sequence[PropNetParams], fld: FieldParams, origins: 
 _TRAIN_LAYOUTS: dict = {}
 
 
+def _train_layout(N: int, S0: int, S1: int, S2: int, Cc: int) -> List[int]:
+    """float offsets of the results inside the one buffer of tn_render_rays_train (last entry: its size)"""
+    key = (N, S0, S1, S2, Cc)
+    off = _TRAIN_LAYOUTS.get(key)
+    if off is None:
+        arr = (C.c_int64 * _lib.TN_RENDER_TRAIN_OFFSETS)()
+        check(_lib.load().tn_render_rays_train_layout(N, S0, S1, S2, Cc, arr, _lib.TN_RENDER_TRAIN_OFFSETS), "tn_render_rays_train_layout")
+        off = _TRAIN_LAYOUTS[key] = [int(v) for v in arr]
+    return off
+
+
 def render_rays_train(props: Sequence[PropNetParams], fld: FieldParams, pose: Optional[Tensor], frozen: Optional[Tensor], origins: Tensor,
                       directions: Tensor, cam: Tensor, nears: Tensor, fars: Tensor, counts: Sequence[int], anneal: float,
                       jitters: Optional[Sequence[Optional[Tensor]]] = None, tag: str = "main", wait_event=None, zero_fill: Optional[Tensor] = None,
@@ -779,12 +795,7 @@ def render_rays_train(props: Sequence[PropNetParams], fld: FieldParams, pose: Op
     Cc = fld.num_channels
     dev = origins.device
     lib = _lib.load()
-    key = (N, S0, S1, S2, Cc)
-    off = _TRAIN_LAYOUTS.get(key)
-    if off is None:
-        arr = (C.c_int64 * _lib.TN_RENDER_TRAIN_OFFSETS)()
-        check(lib.tn_render_rays_train_layout(N, S0, S1, S2, Cc, arr, _lib.TN_RENDER_TRAIN_OFFSETS), "tn_render_rays_train_layout")
-        off = _TRAIN_LAYOUTS[key] = [int(v) for v in arr]
+    off = _train_layout(N, S0, S1, S2, Cc)
     buf = torch.empty(off[_lib.TN_RENDER_TRAIN_OFFSETS - 1], device=dev)
     ws = fld.workspace(N * S2, True, tag)
     jit = list(jitters) if jitters is not None else [None, None, None]
@@ -855,21 +866,10 @@ class TrainStepCall:
     def _for_batch(self, N: int, dev) -> None:
         """what depends on the batch size only: layouts, workspaces, sampler tables"""
         st, (S0, S1, S2) = self.st, self.counts
-        lib = _lib.load()
-        key = (N, S0, S1, S2, 4)
-        off = _TRAIN_LAYOUTS.get(key)
-        if off is None:
-            arr = (C.c_int64 * _lib.TN_RENDER_TRAIN_OFFSETS)()
-            check(lib.tn_render_rays_train_layout(N, S0, S1, S2, 4, arr, _lib.TN_RENDER_TRAIN_OFFSETS), "tn_render_rays_train_layout")
-            off = _TRAIN_LAYOUTS[key] = [int(x) for x in arr]
-        self.off = off
+        self.off = _train_layout(N, S0, S1, S2, 4)
         ws = self.fld.workspace(N * S2, True, self.tags[0])
         w0, w1 = _prop_ws(dev, N * S0, self.tags[1]), _prop_ws(dev, N * S1, self.tags[2])
-        need = int(lib.tn_render_rays_train_bwd_tmp_floats(N, S0, S1, S2, 4))
-        tkey = (str(dev), self.tags[0])
-        tmp = _BWD_TMP.get(tkey)
-        if tmp is None or tmp.numel() < need:
-            tmp = _BWD_TMP[tkey] = torch.empty(need, device=dev)
+        tmp = _bwd_tmp(dev, self.tags[0], N, S0, S1, S2, 4)
         lins = (_lin_table("spaced", S0, dev), _lin_table("pdf", S1, dev), _lin_table("pdf", S2, dev))
         st.N = N
         st.field_workspace, st.field_workspace_bytes = C.c_void_p(ws.data_ptr()), _nbytes(ws)
@@ -929,13 +929,13 @@ class TrainStepCall:
         pend = _PENDING_SAMPLE
         taken = C.c_int32(0)
         if pend is not None and len(ranges) > 0:
-            st.next_sample, st.next_sample_taken = C.pointer(pend[0]), C.pointer(taken)
+            st.next_sample, st.next_sample_taken = C.pointer(pend.args), C.pointer(taken)
         else:
             st.next_sample, st.next_sample_taken = C.POINTER(_lib.TnSampleRays)(), C.POINTER(C.c_int32)()
         # the next iteration's sampling front for that batch, in the same co-work blocks
         ns_taken, nxt, next_buf = C.c_int32(0), None, None
         self.next_buf = None
-        if next_plan is not None and pend is not None and len(ranges) > 0 and int(pend[0].num_rays) == N:
+        if next_plan is not None and pend is not None and len(ranges) > 0 and pend.num_rays == N:
             njit, nanneal, nprop = next_plan
             next_buf = torch.empty(total, device=dev)
             nxt = _lib.TnNextSampling()
@@ -954,19 +954,6 @@ class TrainStepCall:
         return buf
 
 
-def _prop_ws(device, num_points: int, tag: str) -> Tensor:
-    need = int(_lib.load().tn_prop_workspace_bytes(num_points))
-    key = (str(device), tag)
-    ws = _PROP_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
-        _PROP_WS[key] = ws
-    return ws
-
-
-_BWD_TMP: dict = {}
-
-
 def render_rays_train_bwd(props: Sequence[PropNetParams], fld: FieldParams, fwd_buf: Tensor, origins: Tensor, directions: Tensor, cam: Tensor,
                           counts: Sequence[int], d_comp: Tensor, d_weights: Sequence[Optional[Tensor]], d_density_extra: Optional[Tensor],
                           d_origins: Optional[Tensor], d_directions: Optional[Tensor], tag: str = "main", side_tags=("side0", "side1"),
@@ -979,11 +966,7 @@ def render_rays_train_bwd(props: Sequence[PropNetParams], fld: FieldParams, fwd_
     Cc = fld.num_channels
     lib = _lib.load()
     dev = origins.device
-    need = int(lib.tn_render_rays_train_bwd_tmp_floats(N, S0, S1, S2, Cc))
-    key = (str(dev), tag)
-    tmp = _BWD_TMP.get(key)
-    if tmp is None or tmp.numel() < need:
-        tmp = _BWD_TMP[key] = torch.empty(need, device=dev)
+    tmp = _bwd_tmp(dev, tag, N, S0, S1, S2, Cc)
     ws = fld.workspace(N * S2, True, tag)
     prop_grad = d_weights[0] is not None
     p0 = props[0].cstruct(need_grad=True) if prop_grad else None
@@ -1001,9 +984,6 @@ def render_rays_train_bwd(props: Sequence[PropNetParams], fld: FieldParams, fwd_
                                        1 if (prop_enc_saved and prop_grad) else 0, _stream()), "tn_render_rays_train_bwd")
 
 
-_RENDER_SCRATCH: dict = {}
-
-
 def render_fwd(e_bins: Tensor, density: Tensor, rgb: Tensor, training: bool, want_depth: bool = True):
     """weights_fwd + composite_fwd (+ depth clip) of the last level in one launch (tn_render_fwd)
     -> weights [N,S], comp [N,C], accumulation [N,1], depth_median [N,1] or None, depth_expected [N,1] or None."""
@@ -1015,13 +995,7 @@ def render_fwd(e_bins: Tensor, density: Tensor, rgb: Tensor, training: bool, wan
     med = torch.empty((N, 1), device=dev) if want_depth else None
     exp = torch.empty((N, 1), device=dev) if want_depth else None
     st = _stream()
-    scratch = None
-    if want_depth:
-        # per-block min / max of the sample midpoints (contents irrelevant between calls): one buffer per (device, stream)
-        key = (dev.index, st.value)
-        scratch = _RENDER_SCRATCH.get(key)
-        if scratch is None:
-            scratch = _RENDER_SCRATCH[key] = torch.empty(_lib.TN_RENDER_SCRATCH_FLOATS, device=dev)
+    scratch = _render_scratch(dev, st) if want_depth else None
     check(_lib.load().tn_render_fwd(_f32(e_bins, "e_bins", (N, S + 1)), _f32(density, "density", (N, S)), _f32(rgb, "rgb", (N, S, Cc)), N, S, Cc,
                                     1 if training else 0, _f32(w, "w"), _f32(comp, "comp"), _f32(acc, "acc"), _f32(med, "med", optional=True),
                                     _f32(exp, "exp", optional=True), _f32(scratch, "scratch", optional=True), st), "tn_render_fwd")
@@ -1082,9 +1056,6 @@ def proposal_losses(s_fine: Tensor, w_fine: Tensor, props, distortion_mult: floa
           "tn_proposal_losses")
 
 
-LOSS_LINES = _lib.TN_LOSS_LINES
-
-
 def train_losses(s_fine: Tensor, w_fine: Tensor, props, distortion_mult: float, interlevel_mult: float, d_w_fine: Optional[Tensor],
                  loss_lines: Tensor, pixel=None) -> None:
     """proposal_losses and (pixel != None: the arguments of pixel_losses() without losses_out) the pixel terms in ONE launch, the sums spread
@@ -1119,10 +1090,7 @@ def render_losses_bwd(e_bins: Tensor, density: Tensor, rgb: Tensor, s_fine: Tens
     d_rgb = torch.empty((N, S, Cc), device=dev)
     dd = torch.empty((N, S), device=dev)
     st = _stream()
-    key = (dev.index, st.value)
-    scratch = _RENDER_SCRATCH.get(key)
-    if scratch is None:
-        scratch = _RENDER_SCRATCH[key] = torch.empty(_lib.TN_RENDER_SCRATCH_FLOATS, device=dev)
+    scratch = _render_scratch(dev, st)
     n, sb, wp, sp, dw = _prop_level_arrays(props, N)
     check(_lib.load().tn_render_losses_bwd(_f32(e_bins, "e_bins", (N, S + 1)), _f32(density, "density", (N, S)), _f32(rgb, "rgb", (N, S, Cc)), N, S, Cc,
                                            _f32(w, "w"), _f32(comp, "comp"), _f32(acc, "acc"), _f32(med, "med"), _f32(exp, "exp"), _f32(scratch, "scratch"),
