@@ -754,6 +754,28 @@ TN_API int64_t tn_image_loss_workspace_bytes(int32_t height, int32_t width, int3
 TN_API int tn_image_loss(const float* pred, int64_t pred_pixel_stride, const float* gt, int64_t gt_pixel_stride, int32_t height, int32_t width,
                          int32_t channels, float ssim_lambda, float weight, void* workspace, int64_t workspace_bytes, float* out_loss, float* out_grad,
                          tn_stream_t stream);
+/* ---- N4 thermal regularisers: ThermalNeRF's two image-space terms on the thermal render of an RGB camera -- tv_pixel_loss and
+ * cross_channel_loss (nerfstudio/model_components/losses.py:602-651, used at models/thermal_nerfacto.py:346-354 on the rays with
+ * is_thermal == 0) -- applied to the batch of all (H-1) x (W-1) overlapping 2 x 2 windows of one frame: stride 1, row-major, each window flattened
+ * as (top-left, top-right, bottom-left, bottom-right).  With p the window of the thermal prediction and q that of the mean over the channels of
+ * the RGB ground truth:
+ *   tv = 0.25 * mean_w(|p0-p1| + |p0-p2| + |p1-p3| + |p2-p3|)
+ *   cc = 0.25 * mean_w(|(p1-p0)-(q1-q0)| + |(p2-p0)-(q2-q0)| + |(p3-p1)-(q3-q1)| + |(p3-p2)-(q3-q2)|)
+ * (the reference samples disjoint patches; stride 1 regularises every adjacent pixel pair of the frame).  One pass over the frame and a finishing
+ * reduction.  Deterministic: no float atomics -- every pixel gathers its gradient from its own edges, the per-block partial sums are added in a
+ * fixed order -- so the same inputs give bit-identical loss and gradient.  No host synchronisation.  A multiplier of exactly 0 skips that term's
+ * arithmetic (and, for cross_mult, every read of gt_rgb): its loss is exactly 0 and it adds nothing to the gradient.
+ *
+ * scratch of tn_thermal_reg: the per-block partial sums; -1 on bad sizes (H or W < 2 or > 32768) */
+TN_API int64_t tn_thermal_reg_workspace_bytes(int32_t height, int32_t width);
+/* pred_thermal: [H,W,*] fp32 whose pixels are pred_pixel_stride floats apart (channel 0 of each pixel is read, so channel 3 of an [H,W,4] render
+ * serves with stride 4); gt_rgb: [H,W,*] fp32, pixels gt_pixel_stride floats apart, channels 0..2 read; rows W strides apart in both.  out_loss:
+ * DEVICE [2] = tv_mult * tv, cross_mult * cc.  out_grad: [H,W] contiguous = d (out_loss[0] + out_loss[1]) / d pred_thermal with sign(0) = 0 (the
+ * ground truth gets none), or NULL for the losses alone.  Refused with TN_EINVAL before any launch: null pointers, H or W < 2 or > 32768, a pixel
+ * stride below the channel count (1 for pred_thermal, 3 for gt_rgb), a short workspace. */
+TN_API int tn_thermal_reg(const float* pred_thermal, int64_t pred_pixel_stride, const float* gt_rgb, int64_t gt_pixel_stride, int32_t height,
+                          int32_t width, float tv_mult, float cross_mult, void* workspace, int64_t workspace_bytes, float* out_loss, float* out_grad,
+                          tn_stream_t stream);
 /* ---- N4 resolution schedule: bilinear resize of one image, what splatfacto's _downscale_if_required does with
  * torchvision.transforms.functional.resize(antialias=None) (nerfstudio/models/splatfacto.py:648-657), i.e. torch.nn.functional.interpolate(
  * mode="bilinear", align_corners=False, antialias=False).  Per axis: scale = (float)in / out, source coordinate scale * (dst + 0.5) - 0.5 clamped

@@ -11,6 +11,13 @@
 //   k_loss_finish one block: the partial sums in a fixed order (double) -> [main_loss, L1, SSIM] on the device.
 //
 // Beside it, the resize of the resolution schedule's ground truth (splatfacto.py:648-657): tn_image_resize, one streaming launch (k_image_resize).
+//
+// And the two image-space regularisers ThermalNeRF puts on the thermal render at the RGB cameras (model_components/losses.py:602-651, used at
+// models/thermal_nerfacto.py:346-354), over every stride-1 2 x 2 window of a frame: tn_thermal_reg.  Two launches, no float atomics:
+//   k_thermal_reg         one block per 64 x 16 tile of the frame: stages the thermal prediction and the ground truth's grey value with a 1-pixel
+//                         halo in LDS; every pixel sums its right and its lower edge into the loss (an edge counts once per window that holds it)
+//                         and GATHERS its gradient from its four edges; one partial sum per term and block.
+//   k_thermal_reg_finish  one block: the partial sums in a fixed order (double) -> [tv_mult * tv, cross_mult * cc] on the device.
 #include "tn_common.h"
 
 namespace {
@@ -364,6 +371,127 @@ void launch_resize_channels(const ResizeK& k, int C, hipStream_t st) {
   }
 }
 
+// ---- tn_thermal_reg.  The windows' terms are edge terms: the window at (y, x) holds the horizontal edges (y, x)-(y, x+1) and (y+1, x)-(y+1, x+1) and
+// the vertical edges (y, x)-(y+1, x) and (y, x+1)-(y+1, x+1), so a horizontal edge of row y is in as many windows as y has window rows around it
+// (rows y - 1 and y: 2 inside the frame, 1 on its first and last row), a vertical edge of column x likewise.  With those multiplicities
+//   sum over windows = sum over pixels of  mh(y) * |right edge| + mv(x) * |lower edge|
+// and a pixel's gradient is a signed count over its four edges: a small integer, exact in fp32 whatever the order, times the term's constant.
+constexpr int RTX = 64;                // tile width (one wave of columns)
+constexpr int RTY = 16;                // tile height
+constexpr int RSX = RTX + 2;           // staged columns (1-pixel halo)
+constexpr int RSY = RTY + 2;           // staged rows
+constexpr int RRO = RTY / (LB / RTX);  // rows per thread (4)
+static_assert(RTY % (LB / RTX) == 0, "tile shape");
+
+struct RegK {
+  const float* pred;  // thermal prediction, pixels ps floats apart
+  const float* gt;    // RGB ground truth, pixels gs floats apart
+  int64_t ps, gs;
+  int H, W;
+  float* grad;     // [H][W] or null
+  float* part_tv;  // one partial sum of the TV edge terms per block
+  float* part_cc;  // one partial sum of the cross-channel edge terms per block
+  float ctv, ccc;  // mult * 0.25 / windows: a term's gradient per unit of its signed edge count
+};
+
+__device__ __forceinline__ float sign0(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }  // sign(0) = 0, as torch.abs' backward
+
+template <bool TV, bool CC>
+__global__ __launch_bounds__(LB) void k_thermal_reg(RegK k) {
+  __shared__ float st[RSY][RSX];           // thermal prediction (zero outside the frame: those edges carry weight 0)
+  __shared__ float sq[CC ? RSY : 1][RSX];  // mean over the channels of the RGB ground truth
+  __shared__ float red_tv[LB / 64], red_cc[LB / 64];
+  const int t = threadIdx.x, tx0 = blockIdx.x * RTX, ty0 = blockIdx.y * RTY;
+  for (int i = t; i < RSY * RSX; i += LB) {
+    const int r = i / RSX, q = i - r * RSX, y = ty0 - 1 + r, x = tx0 - 1 + q;
+    float a = 0.0f, b = 0.0f;
+    if (y >= 0 && y < k.H && x >= 0 && x < k.W) {
+      const int64_t p = (int64_t)y * k.W + x;
+      a = k.pred[p * k.ps];
+      if constexpr (CC) {
+        const float* g = k.gt + p * k.gs;
+        b = (g[0] + g[1] + g[2]) / 3.0f;
+      }
+    }
+    st[r][q] = a;
+    if constexpr (CC) sq[r][q] = b;
+  }
+  __syncthreads();
+  const int col = t & (RTX - 1), r0 = (t / RTX) * RRO;
+  const int px = tx0 + col, lc = col + 1;
+  const float hasL = px > 0 ? 1.0f : 0.0f, hasR = px < k.W - 1 ? 1.0f : 0.0f, mv = hasL + hasR;
+  float ltv = 0.0f, lcc = 0.0f;
+#pragma unroll
+  for (int o = 0; o < RRO; ++o) {
+    const int py = ty0 + r0 + o, lr = r0 + o + 1;
+    if (py < k.H && px < k.W) {
+      const float hasU = py > 0 ? 1.0f : 0.0f, hasD = py < k.H - 1 ? 1.0f : 0.0f, mh = hasU + hasD;
+      const float wL = mh * hasL, wR = mh * hasR, wU = mv * hasU, wD = mv * hasD;  // windows that hold each of the pixel's edges
+      const float t0 = st[lr][lc], tL = st[lr][lc - 1], tR = st[lr][lc + 1], tU = st[lr - 1][lc], tD = st[lr + 1][lc];
+      float g = 0.0f;
+      if constexpr (TV) {  // |p0 - p1|, |p2 - p3| (left - right) and |p0 - p2|, |p1 - p3| (upper - lower)
+        const float eL = tL - t0, eR = t0 - tR, eU = tU - t0, eD = t0 - tD;
+        ltv += wR * fabsf(eR) + wD * fabsf(eD);
+        g = k.ctv * (wR * sign0(eR) - wL * sign0(eL) + wD * sign0(eD) - wU * sign0(eU));
+      }
+      if constexpr (CC) {  // |(p1 - p0) - (q1 - q0)|, ... : the later pixel minus the earlier one, thermal minus grey
+        const float q0 = sq[lr][lc];
+        const float cL = (t0 - tL) - (q0 - sq[lr][lc - 1]), cR = (tR - t0) - (sq[lr][lc + 1] - q0);
+        const float cU = (t0 - tU) - (q0 - sq[lr - 1][lc]), cD = (tD - t0) - (sq[lr + 1][lc] - q0);
+        lcc += wR * fabsf(cR) + wD * fabsf(cD);
+        g += k.ccc * (wL * sign0(cL) - wR * sign0(cR) + wU * sign0(cU) - wD * sign0(cD));
+      }
+      if (k.grad != nullptr) k.grad[(int64_t)py * k.W + px] = g;
+    }
+  }
+  const int b = blockIdx.y * gridDim.x + blockIdx.x;
+  if constexpr (TV) {
+    const float s = block_sum(ltv, red_tv);
+    if (t == 0) k.part_tv[b] = s;
+  }
+  if constexpr (CC) {
+    const float s = block_sum(lcc, red_cc);
+    if (t == 0) k.part_cc[b] = s;
+  }
+}
+
+// a term that is switched off (null partials) is exactly 0
+__global__ __launch_bounds__(LB) void k_thermal_reg_finish(const float* part_tv, const float* part_cc, int n, double stv, double scc, float* out) {
+  __shared__ double r_tv[LB], r_cc[LB];
+  const int t = threadIdx.x;
+  double a = 0.0, b = 0.0;
+  if (part_tv != nullptr)
+    for (int i = t; i < n; i += LB) a += (double)part_tv[i];
+  if (part_cc != nullptr)
+    for (int i = t; i < n; i += LB) b += (double)part_cc[i];
+  r_tv[t] = a;
+  r_cc[t] = b;
+  __syncthreads();
+  for (int s = LB / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      r_tv[t] += r_tv[t + s];
+      r_cc[t] += r_cc[t + s];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    out[0] = part_tv != nullptr ? (float)(stv * r_tv[0]) : 0.0f;
+    out[1] = part_cc != nullptr ? (float)(scc * r_cc[0]) : 0.0f;
+  }
+}
+
+struct RegLayout {
+  int64_t bx, by, off_cc, total;
+};
+
+RegLayout reg_layout(int32_t H, int32_t W) {
+  RegLayout L;
+  L.bx = tn_cdiv(W, RTX), L.by = tn_cdiv(H, RTY);
+  L.off_cc = align256(L.bx * L.by * 4);
+  L.total = 2 * L.off_cc;
+  return L;
+}
+
 }  // namespace
 
 extern "C" int tn_image_resize(const void* in, int32_t in_dtype, int64_t in_pixel_stride, int32_t in_height, int32_t in_width, int32_t channels,
@@ -431,5 +559,52 @@ extern "C" int tn_image_loss(const float* pred, int64_t pred_pixel_stride, const
   hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(LB), 0, st, k.part_s, (int)(L.bx1 * L.by1), k.part_l1, (int)(L.bx2 * L.by2), n_valid, n_all,
                      ssim_lambda, weight, out_loss);
   TN_CHECK_LAUNCH("tn_image_loss(finish)");
+  return TN_OK;
+}
+
+extern "C" int64_t tn_thermal_reg_workspace_bytes(int32_t height, int32_t width) {
+  if (height < 2 || width < 2 || height > kMaxSide || width > kMaxSide) return -1;
+  return reg_layout(height, width).total;
+}
+
+extern "C" int tn_thermal_reg(const float* pred_thermal, int64_t pred_pixel_stride, const float* gt_rgb, int64_t gt_pixel_stride, int32_t height,
+                              int32_t width, float tv_mult, float cross_mult, void* workspace, int64_t workspace_bytes, float* out_loss,
+                              float* out_grad, tn_stream_t stream) {
+  TN_REQUIRE(pred_thermal && gt_rgb && workspace && out_loss, "tn_thermal_reg: null pointer");
+  TN_REQUIRE(height >= 2 && width >= 2, "tn_thermal_reg: %d x %d image, a 2 x 2 window needs at least 2 x 2", height, width);
+  TN_REQUIRE(height <= kMaxSide && width <= kMaxSide, "tn_thermal_reg: %d x %d image is larger than %d on a side", height, width, kMaxSide);
+  TN_REQUIRE(pred_pixel_stride >= 1 && gt_pixel_stride >= 3, "tn_thermal_reg: pixel strides %lld / %lld below the channel counts 1 / 3",
+             (long long)pred_pixel_stride, (long long)gt_pixel_stride);
+  const RegLayout L = reg_layout(height, width);
+  TN_REQUIRE(workspace_bytes >= L.total, "tn_thermal_reg: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)L.total);
+  const bool tv = tv_mult != 0.0f, cc = cross_mult != 0.0f;
+  RegK k;
+  k.pred = pred_thermal, k.gt = gt_rgb, k.ps = pred_pixel_stride, k.gs = gt_pixel_stride;
+  k.H = height, k.W = width, k.grad = out_grad;
+  char* ws = static_cast<char*>(workspace);
+  k.part_tv = tv ? reinterpret_cast<float*>(ws) : nullptr;
+  k.part_cc = cc ? reinterpret_cast<float*>(ws + L.off_cc) : nullptr;
+  const double windows = (double)(height - 1) * (double)(width - 1);
+  const double stv = (double)tv_mult * 0.25 / windows, scc = (double)cross_mult * 0.25 / windows;
+  k.ctv = (float)stv, k.ccc = (float)scc;
+  hipStream_t st = tn_s(stream);
+  const dim3 grid((unsigned)L.bx, (unsigned)L.by);
+  if (tv && cc) {
+    hipLaunchKernelGGL((k_thermal_reg<true, true>), grid, dim3(LB), 0, st, k);
+  } else if (tv) {
+    hipLaunchKernelGGL((k_thermal_reg<true, false>), grid, dim3(LB), 0, st, k);
+  } else if (cc) {
+    hipLaunchKernelGGL((k_thermal_reg<false, true>), grid, dim3(LB), 0, st, k);
+  } else if (out_grad != nullptr) {  // both terms off: no arithmetic, a zero gradient
+    const hipError_t e = hipMemsetAsync(out_grad, 0, (size_t)height * (size_t)width * sizeof(float), st);
+    if (e != hipSuccess) {
+      tn_set_error("tn_thermal_reg: %s", hipGetErrorString(e));
+      return TN_ELAUNCH;
+    }
+  }
+  TN_CHECK_LAUNCH("tn_thermal_reg");
+  hipLaunchKernelGGL(k_thermal_reg_finish, dim3(1), dim3(LB), 0, st, (const float*)k.part_tv, (const float*)k.part_cc, (int)(L.bx * L.by), stv, scc,
+                     out_loss);
+  TN_CHECK_LAUNCH("tn_thermal_reg(finish)");
   return TN_OK;
 }

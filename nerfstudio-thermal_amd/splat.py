@@ -20,7 +20,11 @@ cube of before.  Training can run splatfacto's coarse-to-fine resolution schedul
 training render and its ground truth are at 1 / 2^n of the frame's size for the first `resolution_schedule` steps and double every
 `resolution_schedule` steps after (`downscale_factor`); the camera is rescaled as a copy (`rescaled_camera`), the ground truth -- uint8 or float --
 by one HIP bilinear resize with torchvision's resize(antialias=None) semantics (`resize_image`: tn_image_resize); the eval render is always
-full size.  Masks and camera-pose gradients are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
+full size.  ThermalNeRF's two cross-spectrum regularisers (model_components/losses.py:602-651, used at models/thermal_nerfacto.py:346-354) are there
+for RGB frames: with `tv_pixel_loss_mult` / `cross_channel_loss_mult` above 0 (both default 0: stock splatfacto has neither) `get_loss_dict` adds
+`tv_pixel_loss` -- the 2 x 2-patch total variation of the thermal render at the RGB camera -- and `cross_channel_loss` -- that render's pixel
+differences against those of the RGB ground truth's grey value -- over every stride-1 window of the frame, in one fused HIP call
+(`thermal_regularizers`: tn_thermal_reg), so the thermal channel gets a gradient from RGB frames too.  Masks and camera-pose gradients are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
 tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 """
 from __future__ import annotations
@@ -54,6 +58,9 @@ class ThermalSplatfactoModelConfig:
     use_scale_regularization: bool = False
     max_gauss_ratio: float = 10.0
     thermal_loss_mult: float = 1.0
+    # ThermalNeRF's regularisers of the thermal render on RGB frames (ThermalNerfactoModelConfig's names; the NeRF path runs both at 1e-6); 0 = off
+    tv_pixel_loss_mult: float = 0.0
+    cross_channel_loss_mult: float = 0.0
     # initialisation (splatfacto.py:127-131): random_init ignores the model's seed_points
     random_init: bool = False
     num_random: int = 50000
@@ -75,6 +82,11 @@ class ThermalSplatfactoModelConfig:
     # coarse-to-fine training (splatfacto.py:112-116): 1 / 2^num_downscales of the resolution at first, doubled every resolution_schedule steps
     resolution_schedule: int = 250
     num_downscales: int = 0
+
+    def __post_init__(self):
+        for name in ("tv_pixel_loss_mult", "cross_channel_loss_mult"):
+            if getattr(self, name) < 0:
+                raise ValueError(f"{name} = {getattr(self, name)}: a loss multiplier cannot be negative")
 
 
 @dataclass
@@ -257,7 +269,7 @@ def image_loss(pred: Tensor, gt: Tensor, ssim_lambda: float = 0.2, weight: float
     return out[0], out[1], out[2]
 
 
-MAX_IMAGE_SIDE = 1 << 15  # tn_image_resize's (and tn_image_loss's) largest side
+MAX_IMAGE_SIDE = 1 << 15  # tn_image_resize's (and tn_image_loss's, tn_thermal_reg's) largest side
 
 
 def resize_image(image: Tensor, size: Tuple[int, int]) -> Tensor:
@@ -281,6 +293,74 @@ def resize_image(image: Tensor, size: Tuple[int, int]) -> Tensor:
     _lib.check(_lib.load().tn_image_resize(C.c_void_p(image.data_ptr()), dtype, ps, H, W, Cc, C.c_void_p(out.data_ptr()), h, w, _stream()),
                "tn_image_resize")
     return out
+
+
+class _ThermalRegularizers(torch.autograd.Function):
+    """tn_thermal_reg as an autograd node: forward computes (tv_mult * tv, cross_mult * cc) and the gradient of their sum in one call and saves it;
+    backward scales it.  Summed with one upstream gradient -- a loss dict's sum -- that is all.  Upstream gradients that differ between the two
+    outputs (or reach only one of them while both terms are on) need each term's own gradient: one more call per term, with the other's multiplier 0."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, tv_mult, cross_mult):
+        out, grad = _thermal_reg_call(pred, gt, tv_mult, cross_mult, True)
+        ctx.save_for_backward(grad, pred, gt)
+        ctx.mults = (tv_mult, cross_mult)
+        ctx.set_materialize_grads(False)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_tv, g_cc):
+        grad, pred, gt = ctx.saved_tensors
+        tv_mult, cross_mult = ctx.mults
+        if tv_mult == 0 or cross_mult == 0:  # the saved gradient is the one live term's
+            g = g_cc if tv_mult == 0 else g_tv
+            return (None if g is None else grad * g), None, None, None
+        if g_tv is not None and g_cc is not None and g_tv.shape == g_cc.shape and g_tv.data_ptr() == g_cc.data_ptr():  # one upstream gradient
+            return grad * g_tv, None, None, None
+        total = None
+        for g, mults in ((g_tv, (tv_mult, 0.0)), (g_cc, (0.0, cross_mult))):
+            if g is not None:
+                term = _thermal_reg_call(pred, gt, *mults, True)[1] * g
+                total = term if total is None else total + term
+        return total, None, None, None
+
+
+def _thermal_reg_call(pred: Tensor, gt: Tensor, tv_mult: float, cross_mult: float, want_grad: bool) -> Tuple[Tensor, Optional[Tensor]]:
+    if pred.dim() != 3 or gt.dim() != 3 or pred.shape[2] != 1 or gt.shape[2] != 3 or pred.shape[:2] != gt.shape[:2]:
+        raise ValueError(f"thermal_regularizers takes a thermal prediction [H,W,1] and an RGB ground truth [H,W,3] of one size, got "
+                         f"{tuple(pred.shape)} and {tuple(gt.shape)}")
+    if tv_mult < 0 or cross_mult < 0:
+        raise ValueError(f"thermal_regularizers: multipliers {tv_mult} / {cross_mult}, a loss multiplier cannot be negative")
+    pred, ps = _image_view(pred.detach(), "thermal prediction")
+    gt, gs = _image_view(gt.detach(), "RGB ground truth")
+    H, W, _ = pred.shape
+    if not all(2 <= v <= MAX_IMAGE_SIDE for v in (H, W)):
+        raise ValueError(f"thermal_regularizers: {H} x {W}, every side must be in 2..{MAX_IMAGE_SIDE} (the windows are 2 x 2)")
+    lib = _lib.load()
+    need = int(lib.tn_thermal_reg_workspace_bytes(H, W))
+    if need < 0:
+        raise ValueError(f"tn_thermal_reg_workspace_bytes: bad sizes {H} x {W}")
+    dev = pred.device
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(2, device=dev)
+    grad = torch.empty((H, W, 1), device=dev) if want_grad else None
+    _lib.check(lib.tn_thermal_reg(C.c_void_p(pred.data_ptr()), ps, C.c_void_p(gt.data_ptr()), gs, H, W, float(tv_mult), float(cross_mult),
+                                  C.c_void_p(ws.data_ptr()), need, C.c_void_p(out.data_ptr()), C.c_void_p(grad.data_ptr()) if grad is not None else None,
+                                  _stream()), "tn_thermal_reg")
+    return out, grad
+
+
+def thermal_regularizers(pred_thermal: Tensor, gt_rgb: Tensor, tv_mult: float, cross_mult: float) -> Tuple[Tensor, Tensor]:
+    """ThermalNeRF's regularisers of a thermal render [H,W,1] at an RGB camera with ground truth [H,W,3] (H and W >= 2), on the device and without a
+    host synchronisation: (tv_mult * tv_pixel_loss, cross_mult * cross_channel_loss) of model_components/losses.py:602-651, applied to all
+    (H-1) x (W-1) stride-1 2 x 2 windows of the frame -- the total variation of the prediction, and its pixel differences against those of the mean
+    over gt_rgb's channels.  A multiplier of 0 gives exactly 0 and skips that term.  Views whose pixels are further apart (rgbt[..., 3:],
+    image[..., :3] of an [H,W,4] image) are read in place.  Both entries are differentiable in pred_thermal when gradients are on (sign(0) = 0, as
+    torch.abs has it); gt_rgb gets no gradient."""
+    if torch.is_grad_enabled() and isinstance(pred_thermal, Tensor) and pred_thermal.requires_grad:
+        return _ThermalRegularizers.apply(pred_thermal, gt_rgb, float(tv_mult), float(cross_mult))
+    out, _ = _thermal_reg_call(pred_thermal, gt_rgb, tv_mult, cross_mult, False)
+    return out[0], out[1]
 
 
 def ssim(pred: Tensor, gt: Tensor) -> Tensor:
@@ -657,8 +737,11 @@ class ThermalSplatfactoModel(nn.Module):
 
     def get_loss_dict(self, outputs: Dict[str, Tensor], batch, metrics_dict=None) -> Dict[str, Tensor]:
         """splatfacto.py:863-903 on the frame's spectrum: main_loss = (1 - ssim_lambda) * L1 + ssim_lambda * (1 - SSIM) (one tn_image_loss call,
-        times thermal_loss_mult on a thermal frame) and scale_reg (every 10th step when use_scale_regularization, else 0).  `batch`: image
-        [H,W,3|4], is_thermal."""
+        times thermal_loss_mult on a thermal frame) and scale_reg (every 10th step when use_scale_regularization, else 0).  With
+        tv_pixel_loss_mult / cross_channel_loss_mult above 0 also tv_pixel_loss / cross_channel_loss (the NeRF model's keys,
+        models/thermal_nerfacto.py:346-354): on an RGB frame ThermalNeRF's regularisers of outputs["thermal"] against the main loss's ground truth
+        (one tn_thermal_reg call), on a thermal frame 0 -- the reference keeps both to the RGB rays, and the keys depend on the config alone.
+        `batch`: image [H,W,3|4], is_thermal."""
         if "mask" in batch:
             raise NotImplementedError("masks are not supported by the splat loss (DESIGN.md section 7)")
         cfg = self.config
@@ -671,7 +754,18 @@ class ThermalSplatfactoModel(nn.Module):
             scale_reg = 0.1 * scale_reg.mean()
         else:
             scale_reg = torch.tensor(0.0).to(dev)
-        return {"main_loss": main, "scale_reg": scale_reg}
+        losses = {"main_loss": main, "scale_reg": scale_reg}
+        tv_mult, cross_mult = cfg.tv_pixel_loss_mult, cfg.cross_channel_loss_mult
+        if tv_mult > 0 or cross_mult > 0:
+            if th:
+                tv = cross = torch.tensor(0.0).to(dev)
+            else:
+                tv, cross = thermal_regularizers(outputs["thermal"], gt.float(), tv_mult, cross_mult)
+            if tv_mult > 0:
+                losses["tv_pixel_loss"] = tv
+            if cross_mult > 0:
+                losses["cross_channel_loss"] = cross
+        return losses
 
     @torch.no_grad()
     def get_metrics_dict(self, outputs: Dict[str, Tensor], batch) -> Dict[str, Tensor]:

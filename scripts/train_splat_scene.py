@@ -9,8 +9,11 @@ generated scene also gets a sparse point cloud -- N points on the cube's faces w
 written as the dataset's PLY (transforms.json ply_file_path) -- and the model starts from it as splatfacto does (load_3D_points -> seed_points,
 one Gaussian per point with kNN scales) instead of from --gaussians random ones.  --num-downscales N trains coarse to fine (splatfacto's resolution
 schedule: 1 / 2^N of each frame's size at first, doubled every --resolution-schedule steps); the JSON line lists every stage with its factor, its
-steps and its time per iteration, and the val split is scored in eval mode, at full size."""
+steps and its time per iteration, and the val split is scored in eval mode, at full size.  --tv-pixel-loss-mult / --cross-channel-loss-mult (default 0:
+off) switch on ThermalNeRF's regularisers of the thermal render at the RGB cameras (get_loss_dict's tv_pixel_loss / cross_channel_loss: tn_thermal_reg;
+the NeRF path runs both at 1e-6); the backward goes over the sum of the loss dict."""
 import argparse
+import functools
 import json
 import math
 import os
@@ -68,6 +71,9 @@ def main():
     ap.add_argument("--seed-points", type=int, default=0, help="start from N points sampled on the cube's surface (generated scene only)")
     ap.add_argument("--num-downscales", type=int, default=0, help="train at 1 / 2^N resolution at first (0: full size throughout)")
     ap.add_argument("--resolution-schedule", type=int, default=250, help="steps after which the training resolution doubles")
+    ap.add_argument("--tv-pixel-loss-mult", type=float, default=0.0, help="weight of the thermal render's 2x2 total variation on RGB frames (0: off)")
+    ap.add_argument("--cross-channel-loss-mult", type=float, default=0.0,
+                    help="weight of the thermal render's pixel differences against the RGB ground truth's on RGB frames (0: off)")
     args = ap.parse_args()
     if args.seed_points and args.data is not None:
         ap.error("--seed-points samples the generated scene's cube; a dataset on disk brings its own ply_file_path")
@@ -88,7 +94,8 @@ def main():
         seed_points = (train_out.metadata["points3D_xyz"], train_out.metadata["points3D_rgb"])
     cfg = ThermalSplatfactoModelConfig(num_random=args.gaussians, random_scale=args.init_extent, ssim_lambda=args.ssim_lambda,
                                        background_color=args.background, num_downscales=args.num_downscales,
-                                       resolution_schedule=args.resolution_schedule)
+                                       resolution_schedule=args.resolution_schedule, tv_pixel_loss_mult=args.tv_pixel_loss_mult,
+                                       cross_channel_loss_mult=args.cross_channel_loss_mult)
     model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=len(train), seed_points=seed_points)
     initial = model.num_points
     opts = Optimizers(model.get_param_groups(), SPLAT_OPTIMIZERS, optimizer_cls=HipAdam)
@@ -111,7 +118,7 @@ def main():
             cb.run_callback_at_location(step, TrainingCallbackLocation.BEFORE_TRAIN_ITERATION)
         opts.zero_grad_all()
         loss = model.get_loss_dict(model.get_train_outputs(cam), batch)
-        (loss["main_loss"] + loss["scale_reg"]).backward()
+        functools.reduce(torch.add, loss.values()).backward()
         opts.optimizer_step_all()
         opts.scheduler_step_all()
         for cb in cbs:
@@ -138,7 +145,8 @@ def main():
                       "val_images": len(val), "steps": args.steps, "ssim_lambda": args.ssim_lambda, "background_color": args.background,
                       "initial_gaussians": initial, "seed_points": args.seed_points, "final_gaussians": model.num_points, "train_seconds": train_s,
                       "ms_per_iteration": 1e3 * train_s / max(args.steps, 1), "num_downscales": args.num_downscales,
-                      "resolution_schedule": args.resolution_schedule, "stages": stages, "val_metrics": metrics, "curve": curve}))
+                      "resolution_schedule": args.resolution_schedule, "tv_pixel_loss_mult": args.tv_pixel_loss_mult,
+                      "cross_channel_loss_mult": args.cross_channel_loss_mult, "stages": stages, "val_metrics": metrics, "curve": curve}))
 
 
 if __name__ == "__main__":
