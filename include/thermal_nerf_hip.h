@@ -790,6 +790,27 @@ TN_API int tn_thermal_reg(const float* pred_thermal, int64_t pred_pixel_stride, 
 #define TN_IMAGE_U8 1
 TN_API int tn_image_resize(const void* in, int32_t in_dtype, int64_t in_pixel_stride, int32_t in_height, int32_t in_width, int32_t channels,
                            float* out, int32_t out_height, int32_t out_width, tn_stream_t stream);
+/* ---- N4 undistortion: one distorted training frame resampled into the pinhole frame the rasteriser renders, what the reference's
+ * FullImageDatamanager does once per frame with OpenCV (data/datamanagers/full_images_datamanager.py:351-386).  The distortion model is tn_raygen's
+ * (k = k1 k2 k3 k4 p1 p2, the dataparser's order): with r = x^2 + y^2, d = 1 + r (k1 + r (k2 + r (k3 + r k4))),
+ * x_d = d x + 2 p1 x y + p2 (r + 2 x^2), y_d = d y + 2 p2 x y + p1 (r + 2 y^2); pixel (u, v) has its centre at (u + 0.5, v + 0.5), as in tn_raygen
+ * and the splat rasteriser.  Output pixel (u, v): x = (u + 0.5 - new_cx) / new_fx, y = (v + 0.5 - new_cy) / new_fy, the polynomial above (closed
+ * form, no iteration), source position s = (fx x_d + cx - 0.5, fy y_d + cy - 0.5) clamped to [-1, width] x [-1, height], taps floor(s) and
+ * floor(s) + 1 with their indices clamped to the frame, weight of the second s - floor(s); interpolation along x, then along y, all in fp32.
+ * Deterministic; no workspace, no host synchronisation.  The caller chooses the new intrinsics (splat.undistorted_camera: the largest pinhole frame
+ * of the same size that reads only inside the source). */
+typedef struct TnUndistort {
+  float fx, fy, cx, cy;                 /* the source frame's (distorted) camera */
+  float new_fx, new_fy, new_cx, new_cy; /* the output frame's pinhole camera */
+  float k[6];                           /* k1 k2 k3 k4 p1 p2 */
+} TnUndistort;
+/* in: [height, width, *] of in_dtype whose pixels are in_pixel_stride ELEMENTS apart (rows width strides apart; channels 0..C-1 of each pixel are
+ * read).  A TN_IMAGE_U8 value v enters as (float)v / 255.0f.  out: [height, width, C] of out_dtype, contiguous; a TN_IMAGE_U8 output is
+ * rintf(255 * clamp(value, 0, 1)).  in and out must not overlap.  Refused with TN_EINVAL before any launch: null pointers, an unknown in_dtype or
+ * out_dtype, channels outside 1..4, a pixel stride below the channel count, a side below 1 or above 32768, a focal length that is not finite and
+ * positive, a non-finite principal point or coefficient. */
+TN_API int tn_image_undistort(const void* in, int32_t in_dtype, int64_t in_pixel_stride, int32_t height, int32_t width, int32_t channels, void* out,
+                              int32_t out_dtype, const TnUndistort* params, tn_stream_t stream);
 /* ---- N4 seeding: exact k-nearest-neighbour distances over a point cloud (splatfacto's k_nearest_sklearn, nerfstudio/models/splatfacto.py:272-290,
  * which seeds each Gaussian's log-scale from the mean distance to its 3 nearest neighbours).  Row i of out_dist holds the k smallest distances
  * from point i to the points j != i, ascending; a duplicate of point i is a neighbour at distance 0.  d2 = (dx*dx + dy*dy) + dz*dz with

@@ -6,6 +6,17 @@ There is no CPU fallback: every op raises if the HIP library is missing.
 """
 __version__ = "0.1.0"
 
+_LAZY = {"ThermalFullImageDatamanager": "splat_datamanager", "ThermalFullImageDatamanagerConfig": "splat_datamanager"}
+
+
+def __getattr__(name):
+    """The splat path's full-image datamanager, imported on first use (importing the package itself stays free of torch)."""
+    if name in _LAZY:
+        import importlib
+
+        return getattr(importlib.import_module(f"{__name__}.{_LAZY[name]}"), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
 # Hardware queues.  The ROCm runtime multiplexes a process's HIP streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); streams that
 # share a queue serialise behind each other.  The package does NOT touch the environment (round 4 wrote GPU_MAX_HW_QUEUES=8 into it at import:
 # process-global, silently ignored once HIP is initialised, and the optimum of one particular set of streams).  Instead the schedules fit the

@@ -17,7 +17,7 @@ TN_MAX_SAMPLES = 256
 TN_RENDER_SCRATCH_FLOATS = 4096
 TN_LOSS_LINES = 64
 TN_RENDER_TRAIN_OFFSETS = 25
-TN_IMAGE_F32, TN_IMAGE_U8 = 0, 1  # tn_image_resize's input types
+TN_IMAGE_F32, TN_IMAGE_U8 = 0, 1  # tn_image_resize's input types, tn_image_undistort's input and output types
 TN_BWD_MLP, TN_BWD_SCATTER, TN_BWD_JOIN, TN_BWD_SCATTER_BIN, TN_BWD_SCATTER_FOLD, TN_BWD_FORK_DPOS, TN_BWD_COUNTERS_CLEAN = 1, 2, 4, 8, 16, 32, 64
 
 _p = C.c_void_p
@@ -108,6 +108,11 @@ class TnSplatRefine(C.Structure):
                 ("n_split_samples", _i32), ("continue_cull_post_densification", _i32), ("num_train_data", _i32), ("max_size", _i32)]
 
 
+class TnUndistort(C.Structure):
+    """include/thermal_nerf_hip.h: the source camera, the pinhole camera of the output and k1 k2 k3 k4 p1 p2 (tn_image_undistort)"""
+    _fields_ = [("fx", _f), ("fy", _f), ("cx", _f), ("cy", _f), ("new_fx", _f), ("new_fy", _f), ("new_cx", _f), ("new_cy", _f), ("k", _f * 6)]
+
+
 # name -> (restype, argtypes); must list every symbol include/thermal_nerf_hip.h declares
 SIGNATURES = {
     "tn_last_error": (C.c_char_p, []),
@@ -196,6 +201,7 @@ SIGNATURES = {
     "tn_image_loss_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "tn_image_loss": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _f, _f, _p, _i64, _p, _p, _p]),
     "tn_image_resize": (C.c_int, [_p, _i32, _i64, _i32, _i32, _i32, _p, _i32, _i32, _p]),
+    "tn_image_undistort": (C.c_int, [_p, _i32, _i64, _i32, _i32, _i32, _p, _i32, C.POINTER(TnUndistort), _p]),
     "tn_thermal_reg_workspace_bytes": (_i64, [_i32, _i32]),
     "tn_thermal_reg": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _f, _f, _p, _i64, _p, _p, _p]),
     "tn_knn_workspace_bytes": (_i64, [_i64, _i32]),

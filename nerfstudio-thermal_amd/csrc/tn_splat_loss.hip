@@ -10,7 +10,9 @@
 //                 the transposed ("full") correlation and writes d loss / d pred = L1 term + SSIM term; one partial L1 sum per block.
 //   k_loss_finish one block: the partial sums in a fixed order (double) -> [main_loss, L1, SSIM] on the device.
 //
-// Beside it, the resize of the resolution schedule's ground truth (splatfacto.py:648-657): tn_image_resize, one streaming launch (k_image_resize).
+// Beside it, the resize of the resolution schedule's ground truth (splatfacto.py:648-657): tn_image_resize, one streaming launch (k_image_resize),
+// and the undistortion of a training frame into a pinhole frame (what FullImageDatamanager._undistort_image does with OpenCV,
+// data/datamanagers/full_images_datamanager.py:351-386): tn_image_undistort, one gathering launch (k_image_undistort).
 //
 // And the two image-space regularisers ThermalNeRF puts on the thermal render at the RGB cameras (model_components/losses.py:602-651, used at
 // models/thermal_nerfacto.py:346-354), over every stride-1 2 x 2 window of a frame: tn_thermal_reg.  Two launches, no float atomics:
@@ -371,6 +373,86 @@ void launch_resize_channels(const ResizeK& k, int C, hipStream_t st) {
   }
 }
 
+// ---- tn_image_undistort: output pixel (u, v) of the pinhole camera `n*` looks along (x, y); the distortion polynomial of tn_raygen's model
+// (tn_misc.hip: undistort() inverts it) takes that to the source camera's (x_d, y_d), closed form; the frame is read there bilinearly.  A gather
+// whose source addresses are nearly the destination's: the launch shape of k_image_resize (64 consecutive pixels of a row per wave, 4 rows per
+// block, every channel of a pixel in one thread), no LDS.
+__device__ __forceinline__ void store_value(float* o, float v) { *o = v; }
+__device__ __forceinline__ void store_value(uint8_t* o, float v) { *o = (uint8_t)rintf(255.0f * fminf(fmaxf(v, 0.0f), 1.0f)); }
+
+struct UndistortK {
+  const void* in;
+  void* out;
+  int64_t ps;  // input pixel stride (elements)
+  int H, W;
+  TnUndistort p;
+};
+
+// taps floor(s) and floor(s) + 1 with their indices clamped to the frame, weight of the second = s - floor(s).  s is clamped to [-1, n] first
+// (a NaN becomes -1), so the conversion to int is defined and both indices are in bounds whatever the camera.
+__device__ __forceinline__ void undistort_taps(float s, int n, int& i0, int& i1, float& w1) {
+  s = fminf(fmaxf(s, -1.0f), (float)n);
+  const float f = floorf(s);
+  const int i = (int)f;
+  w1 = s - f;
+  i0 = min(max(i, 0), n - 1);
+  i1 = min(max(i + 1, 0), n - 1);
+}
+
+template <typename T, typename TO, int C, bool VEC>
+__global__ __launch_bounds__(256) void k_image_undistort(UndistortK k) {
+  const int u = blockIdx.x * 64 + threadIdx.x, v = blockIdx.y * 4 + threadIdx.y;
+  if (u >= k.W || v >= k.H) return;
+  const TnUndistort& p = k.p;
+  const float x = ((float)u + 0.5f - p.new_cx) / p.new_fx, y = ((float)v + 0.5f - p.new_cy) / p.new_fy;
+  const float r = x * x + y * y;
+  const float d = 1.0f + r * (p.k[0] + r * (p.k[1] + r * (p.k[2] + r * p.k[3])));
+  const float xd = d * x + 2.0f * p.k[4] * x * y + p.k[5] * (r + 2.0f * x * x);
+  const float yd = d * y + 2.0f * p.k[5] * x * y + p.k[4] * (r + 2.0f * y * y);
+  int x0, x1, y0, y1;
+  float wx, wy;
+  undistort_taps(p.fx * xd + p.cx - 0.5f, k.W, x0, x1, wx);
+  undistort_taps(p.fy * yd + p.cy - 0.5f, k.H, y0, y1, wy);
+  const T* in = static_cast<const T*>(k.in);
+  const int64_t r0 = (int64_t)y0 * k.W, r1 = (int64_t)y1 * k.W;
+  float v00[C], v01[C], v10[C], v11[C];
+  load_tap<T, C, VEC>(in + (r0 + x0) * k.ps, v00);
+  load_tap<T, C, VEC>(in + (r0 + x1) * k.ps, v01);
+  load_tap<T, C, VEC>(in + (r1 + x0) * k.ps, v10);
+  load_tap<T, C, VEC>(in + (r1 + x1) * k.ps, v11);
+  const float ux = 1.0f - wx, uy = 1.0f - wy;
+  TO* o = static_cast<TO*>(k.out) + ((int64_t)v * k.W + u) * C;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {  // along x, then along y
+    const float top = ux * v00[c] + wx * v01[c];
+    const float bot = ux * v10[c] + wx * v11[c];
+    store_value(o + c, uy * top + wy * bot);
+  }
+}
+
+template <typename T, typename TO, int C>
+void launch_undistort(const UndistortK& k, bool vec, hipStream_t st) {
+  const dim3 grid((unsigned)tn_cdiv(k.W, 64), (unsigned)tn_cdiv(k.H, 4)), block(64, 4);
+  if constexpr (C == 2 || C == 4) {
+    if (vec) {
+      hipLaunchKernelGGL((k_image_undistort<T, TO, C, true>), grid, block, 0, st, k);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_image_undistort<T, TO, C, false>), grid, block, 0, st, k);
+}
+
+template <typename T, typename TO>
+void launch_undistort_channels(const UndistortK& k, int C, hipStream_t st) {
+  const bool vec = reinterpret_cast<uintptr_t>(k.in) % (C * sizeof(T)) == 0 && k.ps % C == 0;
+  switch (C) {
+    case 1: launch_undistort<T, TO, 1>(k, vec, st); break;
+    case 2: launch_undistort<T, TO, 2>(k, vec, st); break;
+    case 3: launch_undistort<T, TO, 3>(k, vec, st); break;
+    default: launch_undistort<T, TO, 4>(k, vec, st); break;
+  }
+}
+
 // ---- tn_thermal_reg.  The windows' terms are edge terms: the window at (y, x) holds the horizontal edges (y, x)-(y, x+1) and (y+1, x)-(y+1, x+1) and
 // the vertical edges (y, x)-(y+1, x) and (y, x+1)-(y+1, x+1), so a horizontal edge of row y is in as many windows as y has window rows around it
 // (rows y - 1 and y: 2 inside the frame, 1 on its first and last row), a vertical edge of column x likewise.  With those multiplicities
@@ -513,6 +595,41 @@ extern "C" int tn_image_resize(const void* in, int32_t in_dtype, int64_t in_pixe
   else
     launch_resize_channels<float>(k, channels, tn_s(stream));
   TN_CHECK_LAUNCH("tn_image_resize");
+  return TN_OK;
+}
+
+extern "C" int tn_image_undistort(const void* in, int32_t in_dtype, int64_t in_pixel_stride, int32_t height, int32_t width, int32_t channels,
+                                  void* out, int32_t out_dtype, const TnUndistort* params, tn_stream_t stream) {
+  TN_REQUIRE(in && out && params, "tn_image_undistort: null pointer");
+  TN_REQUIRE(in_dtype == TN_IMAGE_F32 || in_dtype == TN_IMAGE_U8, "tn_image_undistort: input type %d (TN_IMAGE_F32 or TN_IMAGE_U8)", in_dtype);
+  TN_REQUIRE(out_dtype == TN_IMAGE_F32 || out_dtype == TN_IMAGE_U8, "tn_image_undistort: output type %d (TN_IMAGE_F32 or TN_IMAGE_U8)", out_dtype);
+  TN_REQUIRE(channels >= 1 && channels <= 4, "tn_image_undistort: %d channels (1..4)", channels);
+  TN_REQUIRE(in_pixel_stride >= channels, "tn_image_undistort: pixel stride %lld below the channel count %d", (long long)in_pixel_stride, channels);
+  TN_REQUIRE(height >= 1 && width >= 1, "tn_image_undistort: %d x %d image, every side must be positive", height, width);
+  TN_REQUIRE(height <= kMaxSide && width <= kMaxSide, "tn_image_undistort: %d x %d image is larger than %d on a side", height, width, kMaxSide);
+  const TnUndistort& p = *params;
+  TN_REQUIRE(std::isfinite(p.fx) && std::isfinite(p.fy) && std::isfinite(p.new_fx) && std::isfinite(p.new_fy) && p.fx > 0.0f && p.fy > 0.0f &&
+                 p.new_fx > 0.0f && p.new_fy > 0.0f,
+             "tn_image_undistort: focal lengths %g %g -> %g %g must be finite and positive", (double)p.fx, (double)p.fy, (double)p.new_fx,
+             (double)p.new_fy);
+  bool finite = std::isfinite(p.cx) && std::isfinite(p.cy) && std::isfinite(p.new_cx) && std::isfinite(p.new_cy);
+  for (int i = 0; i < 6; ++i) finite = finite && std::isfinite(p.k[i]);
+  TN_REQUIRE(finite, "tn_image_undistort: non-finite principal point or distortion coefficient");
+  UndistortK k;
+  k.in = in, k.out = out, k.ps = in_pixel_stride, k.H = height, k.W = width, k.p = p;
+  hipStream_t st = tn_s(stream);
+  if (in_dtype == TN_IMAGE_U8) {
+    if (out_dtype == TN_IMAGE_U8)
+      launch_undistort_channels<uint8_t, uint8_t>(k, channels, st);
+    else
+      launch_undistort_channels<uint8_t, float>(k, channels, st);
+  } else {
+    if (out_dtype == TN_IMAGE_U8)
+      launch_undistort_channels<float, uint8_t>(k, channels, st);
+    else
+      launch_undistort_channels<float, float>(k, channels, st);
+  }
+  TN_CHECK_LAUNCH("tn_image_undistort");
   return TN_OK;
 }
 

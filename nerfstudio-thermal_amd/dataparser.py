@@ -332,6 +332,17 @@ def load_3D_points(ply_path: str, transform: Tensor, scale: float) -> Dict[str, 
     return {"points3D_xyz": points, "points3D_rgb": torch.from_numpy(rgb)}
 
 
+def load_image_uint8(path: str) -> Tensor:
+    """[H,W,3] uint8 (base_dataset.py:61-77, get_numpy_image: a single-channel image is repeated to three channels; alpha dropped, as
+    load_image_float32 drops it)."""
+    from PIL import Image
+
+    im = np.array(Image.open(path), dtype="uint8")
+    if im.ndim == 2:
+        im = im[:, :, None].repeat(3, axis=2)
+    return torch.from_numpy(np.ascontiguousarray(im[:, :, :3]))
+
+
 def load_image_float32(path: str) -> Tensor:
     """[H,W,3] fp32 in [0,1] (base_dataset.py:61-95: uint8 / 255; a single-channel image is repeated to three channels; alpha dropped)."""
     from PIL import Image

@@ -24,7 +24,12 @@ full size.  ThermalNeRF's two cross-spectrum regularisers (model_components/loss
 for RGB frames: with `tv_pixel_loss_mult` / `cross_channel_loss_mult` above 0 (both default 0: stock splatfacto has neither) `get_loss_dict` adds
 `tv_pixel_loss` -- the 2 x 2-patch total variation of the thermal render at the RGB camera -- and `cross_channel_loss` -- that render's pixel
 differences against those of the RGB ground truth's grey value -- over every stride-1 window of the frame, in one fused HIP call
-(`thermal_regularizers`: tn_thermal_reg), so the thermal channel gets a gradient from RGB frames too.  Masks and camera-pose gradients are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
+(`thermal_regularizers`: tn_thermal_reg), so the thermal channel gets a gradient from RGB frames too.  The rasteriser is strictly pinhole; distorted frames
+are resampled once into pinhole frames, as the reference's FullImageDatamanager does with OpenCV (full_images_datamanager.py:132-225, 351-386):
+`undistorted_camera` is the pinhole camera of a distorted one (the largest frame of the same size that reads only inside the source),
+`undistort_image` the frame it sees (tn_image_undistort, uint8 or fp32 in and out), with tn_raygen's distortion model and pixel convention, so a
+dataset means the same on the NeRF path and here; splat_datamanager.ThermalFullImageDatamanager caches the undistorted frames on the device and
+serves (camera, batch).  Masks and camera-pose gradients are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
 tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 """
 from __future__ import annotations
@@ -269,7 +274,7 @@ def image_loss(pred: Tensor, gt: Tensor, ssim_lambda: float = 0.2, weight: float
     return out[0], out[1], out[2]
 
 
-MAX_IMAGE_SIDE = 1 << 15  # tn_image_resize's (and tn_image_loss's, tn_thermal_reg's) largest side
+MAX_IMAGE_SIDE = 1 << 15  # tn_image_resize's (and tn_image_undistort's, tn_image_loss's, tn_thermal_reg's) largest side
 
 
 def resize_image(image: Tensor, size: Tuple[int, int]) -> Tensor:
@@ -293,6 +298,143 @@ def resize_image(image: Tensor, size: Tuple[int, int]) -> Tensor:
     _lib.check(_lib.load().tn_image_resize(C.c_void_p(image.data_ptr()), dtype, ps, H, W, Cc, C.c_void_p(out.data_ptr()), h, w, _stream()),
                "tn_image_resize")
     return out
+
+
+_NEWTON_ITERS = 50  # undistorted_camera: Newton steps per border pixel, and the residual (normalised coordinates) it must reach
+_NEWTON_TOL = 1e-9
+_SETTLE_ITERS = 100  # ... and the steps and the miss (pixels) of settling the rectangle on the new frame's own border
+_SETTLE_TOL = 1e-9
+
+
+def _distort(x: Tensor, y: Tensor, k: List[float]) -> Tuple[Tensor, Tensor]:
+    k1, k2, k3, k4, p1, p2 = k
+    r = x * x + y * y
+    d = 1 + r * (k1 + r * (k2 + r * (k3 + r * k4)))
+    return d * x + 2 * p1 * x * y + p2 * (r + 2 * x * x), d * y + 2 * p2 * x * y + p1 * (r + 2 * y * y)
+
+
+def _undistort_points(xd: Tensor, yd: Tensor, k: List[float]) -> Tuple[Tensor, Tensor, float]:
+    """Newton from (xd, yd) on _distort(x, y) = (xd, yd), float64, _NEWTON_ITERS steps -> (x, y, the largest residual; inf when not finite)."""
+    k1, k2, k3, k4, p1, p2 = k
+    x, y = xd.clone(), yd.clone()
+    for _ in range(_NEWTON_ITERS):
+        r = x * x + y * y
+        d = 1 + r * (k1 + r * (k2 + r * (k3 + r * k4)))
+        d_r = k1 + r * (2 * k2 + r * (3 * k3 + r * 4 * k4))
+        ex, ey = _distort(x, y, k)
+        ex, ey = ex - xd, ey - yd
+        a, b = d + 2 * x * x * d_r + 2 * p1 * y + 6 * p2 * x, 2 * x * y * d_r + 2 * p1 * x + 2 * p2 * y
+        c, e = 2 * x * y * d_r + 2 * p2 * y + 2 * p1 * x, d + 2 * y * y * d_r + 2 * p2 * x + 6 * p1 * y
+        det = a * e - b * c
+        x, y = x - (ex * e - ey * b) / det, y - (ey * a - ex * c) / det
+    ex, ey = _distort(x, y, k)
+    res = torch.maximum((ex - xd).abs(), (ey - yd).abs())
+    return x, y, (float(res.max()) if bool(torch.isfinite(res).all()) else math.inf)
+
+
+def _coefficients(distortion) -> List[float]:
+    k = [float(v) for v in (distortion.detach().reshape(-1).tolist() if isinstance(distortion, Tensor) else distortion)]  # (floats keep their 64 bits)
+    if len(k) != 6:
+        raise ValueError(f"distortion must hold the six coefficients k1 k2 k3 k4 p1 p2, got {len(k)} values")
+    if not all(math.isfinite(v) for v in k):
+        raise ValueError(f"distortion coefficients {k} are not finite")
+    return k
+
+
+def undistorted_camera(camera: PinholeCamera, distortion) -> PinholeCamera:
+    """The pinhole camera of the frame `undistort_image` makes of a frame of `camera` with `distortion` = (k1, k2, k3, k4, p1, p2), the
+    dataparser's order: the part of cv2.getOptimalNewCameraMatrix(alpha=0) in the reference's _undistort_image
+    (data/datamanagers/full_images_datamanager.py:351-386) -- the largest pinhole frame of the same size that sees only valid source pixels.  Size
+    and pose are the camera's own; with all six coefficients zero the camera itself is returned.  Host side, float64.
+
+    Model: tn_raygen's (and oracle undistort_opencv's): r = x^2 + y^2, d = 1 + r (k1 + r (k2 + r (k3 + r k4))), x_d = d x + 2 p1 x y +
+    p2 (r + 2 x^2), y_d = d y + 2 p2 x y + p1 (r + 2 y^2), so a dataset means the same on the NeRF path and here.  That deviates from the
+    reference, whose OpenCV call reads slot k4 as a rational-model coefficient; datasets written as OPENCV have k4 = 0.  Pixel centres are at
+    (u + 0.5, v + 0.5), x = (u + 0.5 - cx) / fx, the ray generator's and the rasteriser's convention; OpenCV puts centres at integers and the
+    reference hands its K to a half-pixel rasteriser unchanged -- one convention throughout is a deliberate deviation too.
+
+    Rule: the centres of all 2W + 2H - 4 border pixels are mapped to undistorted normalised coordinates by Newton iteration; x0 = the largest x
+    over the left column, x1 = the smallest over the right column, y0 / y1 likewise over the top / bottom row; fx' = (W - 1) / (x1 - x0),
+    cx' = 0.5 - fx' x0, fy' = (H - 1) / (y1 - y0), cy' = 0.5 - fy' y0.  The new frame's rows and columns are not the undistorted positions of the
+    source's border pixels, so at this point its own border pixels still read up to ~1e-3 px outside (or inside) the source frame; the rectangle is
+    then settled on them: each side moves by its miss -- min of the source x over the new column 0, max over column W - 1 minus (W - 1), and
+    the rows likewise, closed form -- over the focal length, until every miss is below 1e-9 px.  Every output pixel's four taps then lie inside
+    the source frame up to rounding and one border pixel per side reads the source's very edge: no region-of-interest pass, no crop.
+
+    ValueError: non-finite coefficients, a distortion Newton cannot invert on the border (residual above 1e-9 after 50 steps), an empty or
+    inverted rectangle, one that does not settle."""
+    k = _coefficients(distortion)
+    if not any(k):
+        return camera
+    W, H = int(camera.width), int(camera.height)
+    fx, fy, cx, cy = float(camera.fx), float(camera.fy), float(camera.cx), float(camera.cy)
+    if W < 2 or H < 2:
+        raise ValueError(f"undistorted_camera: a {W} x {H} frame has no inner rectangle")
+    us, vs = torch.arange(W, dtype=torch.float64), torch.arange(H, dtype=torch.float64)
+    xs, ys = (us + 0.5 - cx) / fx, (vs + 0.5 - cy) / fy
+    left = _undistort_points(xs[0].expand(H), ys, k)
+    right = _undistort_points(xs[-1].expand(H), ys, k)
+    top = _undistort_points(xs, ys[0].expand(W), k)
+    bottom = _undistort_points(xs, ys[-1].expand(W), k)
+    worst = max(s[2] for s in (left, right, top, bottom))
+    if not worst <= _NEWTON_TOL:
+        raise ValueError(f"undistorted_camera: the distortion {k} cannot be inverted on the border of the {W} x {H} frame (residual {worst:.3g})")
+    x0, x1, y0, y1 = float(left[0].max()), float(right[0].min()), float(top[1].max()), float(bottom[1].min())
+    for _ in range(_SETTLE_ITERS):
+        if not (x1 > x0 and y1 > y0):
+            raise ValueError(f"undistorted_camera: the distortion {k} leaves no rectangle inside the {W} x {H} frame "
+                             f"(x {x0:.4g} .. {x1:.4g}, y {y0:.4g} .. {y1:.4g})")
+        nfx, nfy = (W - 1) / (x1 - x0), (H - 1) / (y1 - y0)
+        ncx, ncy = 0.5 - nfx * x0, 0.5 - nfy * y0
+        nx, ny = (us + 0.5 - ncx) / nfx, (vs + 0.5 - ncy) / nfy
+        sx = lambda x, y: fx * _distort(x, y, k)[0] + cx - 0.5  # noqa: E731
+        sy = lambda x, y: fy * _distort(x, y, k)[1] + cy - 0.5  # noqa: E731
+        miss = (float(sx(nx[0].expand(H), ny).min()), float(sx(nx[-1].expand(H), ny).max()) - (W - 1),
+                float(sy(nx, ny[0].expand(W)).min()), float(sy(nx, ny[-1].expand(W)).max()) - (H - 1))
+        if max(abs(m) for m in miss) <= _SETTLE_TOL:
+            return dataclasses.replace(camera, fx=nfx, fy=nfy, cx=ncx, cy=ncy)
+        x0, x1, y0, y1 = x0 - miss[0] / fx, x1 - miss[1] / fx, y0 - miss[2] / fy, y1 - miss[3] / fy
+    raise ValueError(f"undistorted_camera: the inner rectangle of the distortion {k} on the {W} x {H} frame does not settle")
+
+
+def undistort_image(image: Tensor, camera: PinholeCamera, distortion, new_camera: Optional[PinholeCamera] = None,
+                    out_dtype: Optional[torch.dtype] = None) -> Tuple[Tensor, PinholeCamera]:
+    """One frame of `camera` with `distortion` (k1, k2, k3, k4, p1, p2) resampled into the pinhole frame of `new_camera` (default:
+    `undistorted_camera(camera, distortion)`, whose docstring has the model and the pixel convention) -> (image', camera'), in one
+    tn_image_undistort call on the current stream, without a host synchronisation.  image: [H,W,C] uint8 or fp32 on the device, C = 1..4; a view
+    whose pixels are further apart than C (rgbt[..., :3]) is read in place; a uint8 value v enters as float(v) / 255.0f.  image': contiguous
+    [H,W,C] of `out_dtype` (torch.uint8 or torch.float32, default the input's); a uint8 output is rint(255 clamp(value, 0, 1)), so a uint8 cache
+    stays uint8.  Each output pixel is the bilinear interpolation of the source at the distorted position of its viewing direction (taps clamped
+    to the frame).  With all six coefficients zero the input tensor and camera come back themselves and nothing is launched.  No gradient.
+    ValueError when the image's size and the camera's width / height disagree."""
+    k = _coefficients(distortion)
+    image, ps = _image_view(image, "image", (torch.uint8, torch.float32), "a uint8 or fp32")
+    H, W, Cc = image.shape
+    if (H, W) != (int(camera.height), int(camera.width)):
+        raise ValueError(f"undistort_image: the image is {H} x {W}, the camera {camera.height} x {camera.width}")
+    out_dtype = image.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"undistort_image: out_dtype {out_dtype} (torch.uint8 or torch.float32)")
+    if not any(k):
+        return image, camera
+    if not 1 <= Cc <= 4:
+        raise ValueError(f"undistort_image takes 1..4 channels, got {Cc}")
+    if not all(1 <= v <= MAX_IMAGE_SIDE for v in (H, W)):
+        raise ValueError(f"undistort_image: {H} x {W}, every side must be in 1..{MAX_IMAGE_SIDE}")
+    new_camera = undistorted_camera(camera, k) if new_camera is None else new_camera
+    if (int(new_camera.height), int(new_camera.width)) != (H, W):
+        raise ValueError(f"undistort_image: the new camera is {new_camera.height} x {new_camera.width}, the image {H} x {W}")
+    image = image.detach()
+    p = _lib.TnUndistort()
+    p.fx, p.fy, p.cx, p.cy = float(camera.fx), float(camera.fy), float(camera.cx), float(camera.cy)
+    p.new_fx, p.new_fy, p.new_cx, p.new_cy = float(new_camera.fx), float(new_camera.fy), float(new_camera.cx), float(new_camera.cy)
+    for i, v in enumerate(k):
+        p.k[i] = v
+    out = torch.empty((H, W, Cc), dtype=out_dtype, device=image.device)
+    code = {torch.uint8: _lib.TN_IMAGE_U8, torch.float32: _lib.TN_IMAGE_F32}
+    _lib.check(_lib.load().tn_image_undistort(C.c_void_p(image.data_ptr()), code[image.dtype], ps, H, W, Cc, C.c_void_p(out.data_ptr()),
+                                              code[out_dtype], C.byref(p), _stream()), "tn_image_undistort")
+    return out, new_camera
 
 
 class _ThermalRegularizers(torch.autograd.Function):

@@ -1,10 +1,13 @@
 """Splat trainer on the synthetic RGB+T cube scene: ThermalSplatfactoModel trained on whole frames with splatfacto's objective.
 
 The scene is train_eval_scene.py's (write_cube_scene: RGB 640x480 and thermal 160x120 frames on a ring, written to disk as a dataset) read back
-through this package's dataparser.  Training keeps every train frame resident on the device, turns each camera into a PinholeCamera and visits
-the frames in a shuffled order per epoch: get_train_outputs -> get_loss_dict (L1 + SSIM, tn_image_loss) -> backward -> Optimizers(SPLAT_OPTIMIZERS,
+through this package's dataparser by ThermalFullImageDatamanager (splat_datamanager.py): every frame is undistorted once on the device
+(tn_image_undistort) into the pinhole frame the rasteriser renders, with the camera that goes with it, cached as uint8, and served as (camera, batch)
+with every frame seen once per epoch: get_train_outputs -> get_loss_dict (L1 + SSIM, tn_image_loss) -> backward -> Optimizers(SPLAT_OPTIMIZERS,
 HipAdam) -> the model's training callbacks (SH degree, gradient statistics, refinement).  At the end it reports PSNR / SSIM per spectrum on the
-val split and the time per iteration as one JSON line.  (Camera distortion is ignored: the scene's cameras have none.)  With --seed-points N the
+val split and the time per iteration as one JSON line.  The scene's cameras are distorted (synth.synth_cameras: RGB k1 = 0.05, thermal k1 = -0.08,
+both with tangential terms: about 9 px at the corners of the RGB frames); --no-undistort trains on the raw frames with the parser's intrinsics
+instead, the distortion dropped, as this script did before.  Either way the val split is scored on its undistorted frames.  With --seed-points N the
 generated scene also gets a sparse point cloud -- N points on the cube's faces with their texture colours plus jitter (synth.cube_surface_points),
 written as the dataset's PLY (transforms.json ply_file_path) -- and the model starts from it as splatfacto does (load_3D_points -> seed_points,
 one Gaussian per point with kNN scales) instead of from --gaussians random ones.  --num-downscales N trains coarse to fine (splatfacto's resolution
@@ -28,6 +31,7 @@ import torch  # noqa: E402
 
 import nerfstudio_thermal_amd  # noqa: E402,F401
 from nerfstudio_thermal_amd import synth  # noqa: E402
+from nerfstudio_thermal_amd import ThermalFullImageDatamanagerConfig  # noqa: E402
 from nerfstudio_thermal_amd.dataparser import ThermalNerfDataParserConfig, load_image_float32, write_ply  # noqa: E402
 from nerfstudio_thermal_amd.model import TrainingCallbackLocation  # noqa: E402
 from nerfstudio_thermal_amd.optim import SPLAT_OPTIMIZERS, HipAdam, Optimizers  # noqa: E402
@@ -36,7 +40,9 @@ from train_eval_scene import write_cube_scene  # noqa: E402
 
 
 def frames_of(outputs, device):
-    """(PinholeCamera, batch) per image of a dataparser split; images resident on the device"""
+    """(PinholeCamera, batch) per image of a dataparser split as it is on disk: fp32 frames resident on the device, the parser's intrinsics, the
+    distortion dropped.  main() no longer trains on these (ThermalFullImageDatamanager undistorts and serves the frames); tests/test_splat_seed_gpu.py
+    builds its frame list with it."""
     cams = outputs.cameras
     out = []
     for i, path in enumerate(outputs.image_filenames):
@@ -74,6 +80,7 @@ def main():
     ap.add_argument("--tv-pixel-loss-mult", type=float, default=0.0, help="weight of the thermal render's 2x2 total variation on RGB frames (0: off)")
     ap.add_argument("--cross-channel-loss-mult", type=float, default=0.0,
                     help="weight of the thermal render's pixel differences against the RGB ground truth's on RGB frames (0: off)")
+    ap.add_argument("--no-undistort", action="store_true", help="train on the raw frames with the parser's intrinsics (the distortion dropped)")
     args = ap.parse_args()
     if args.seed_points and args.data is not None:
         ap.error("--seed-points samples the generated scene's cube; a dataset on disk brings its own ply_file_path")
@@ -87,21 +94,19 @@ def main():
         if args.seed_points:
             add_seed_points(data, args.seed_points, args.seed)
     pc = ThermalNerfDataParserConfig(data=data, load_3D_points=bool(args.seed_points))
-    train_out = pc.setup().get_dataparser_outputs("train")
-    train, val = frames_of(train_out, dev), frames_of(pc.setup().get_dataparser_outputs("val"), dev)
-    seed_points = None
-    if args.seed_points:
-        seed_points = (train_out.metadata["points3D_xyz"], train_out.metadata["points3D_rgb"])
+    dm = ThermalFullImageDatamanagerConfig(dataparser=pc, undistort=not args.no_undistort, seed=args.seed).setup(device=dev)
+    # the val split is scored on its undistorted frames whatever the training frames were
+    val = dm.fixed_indices_eval_dataloader if not args.no_undistort else \
+        ThermalFullImageDatamanagerConfig(dataparser=pc, seed=args.seed).setup(device=dev).fixed_indices_eval_dataloader
+    seed_points = dm.seed_points if args.seed_points else None
     cfg = ThermalSplatfactoModelConfig(num_random=args.gaussians, random_scale=args.init_extent, ssim_lambda=args.ssim_lambda,
                                        background_color=args.background, num_downscales=args.num_downscales,
                                        resolution_schedule=args.resolution_schedule, tv_pixel_loss_mult=args.tv_pixel_loss_mult,
                                        cross_channel_loss_mult=args.cross_channel_loss_mult)
-    model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=len(train), seed_points=seed_points)
+    model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=dm.num_train_data, seed_points=seed_points)
     initial = model.num_points
     opts = Optimizers(model.get_param_groups(), SPLAT_OPTIMIZERS, optimizer_cls=HipAdam)
     cbs = model.get_training_callbacks(opts)
-    order_gen = torch.Generator().manual_seed(args.seed)
-    order = []
     curve = []
     stages = []  # one entry per run of steps at one downscale factor
     torch.cuda.synchronize()
@@ -111,9 +116,7 @@ def main():
         if not stages or stages[-1]["downscale_factor"] != factor:
             torch.cuda.synchronize()
             stages.append({"downscale_factor": factor, "first_step": step, "t0": time.perf_counter()})
-        if not order:
-            order = torch.randperm(len(train), generator=order_gen).tolist()
-        cam, batch = train[order.pop()]
+        cam, batch = dm.next_train(step)
         for cb in cbs:
             cb.run_callback_at_location(step, TrainingCallbackLocation.BEFORE_TRAIN_ITERATION)
         opts.zero_grad_all()
@@ -141,12 +144,12 @@ def main():
                 sums.setdefault(k, []).append(v)
     model.train()
     metrics = {k: sum(v) / len(v) for k, v in sums.items() if all(math.isfinite(x) for x in v)}
-    print(json.dumps({"dataset": "synthetic cube scene (train_eval_scene.write_cube_scene)" if tmp else data, "train_images": len(train),
+    print(json.dumps({"dataset": "synthetic cube scene (train_eval_scene.write_cube_scene)" if tmp else data, "train_images": dm.num_train_data,
                       "val_images": len(val), "steps": args.steps, "ssim_lambda": args.ssim_lambda, "background_color": args.background,
                       "initial_gaussians": initial, "seed_points": args.seed_points, "final_gaussians": model.num_points, "train_seconds": train_s,
                       "ms_per_iteration": 1e3 * train_s / max(args.steps, 1), "num_downscales": args.num_downscales,
                       "resolution_schedule": args.resolution_schedule, "tv_pixel_loss_mult": args.tv_pixel_loss_mult,
-                      "cross_channel_loss_mult": args.cross_channel_loss_mult, "stages": stages, "val_metrics": metrics, "curve": curve}))
+                      "cross_channel_loss_mult": args.cross_channel_loss_mult, "undistort": not args.no_undistort, "stages": stages, "val_metrics": metrics, "curve": curve}))
 
 
 if __name__ == "__main__":
