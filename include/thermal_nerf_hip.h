@@ -739,6 +739,69 @@ TN_API int tn_splat_refine_apply(const TnSplatRefine* config, int64_t num_gaussi
                                  int64_t workspace_bytes, const int64_t* counts, const float* noise, const float* const* params,
                                  const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params, float* const* new_exp_avg,
                                  float* const* new_exp_avg_sq, tn_stream_t stream);
+
+/* ---- N4 separate thermal opacity (ThermalSplatfactoModelConfig.thermal_opacity_mode = "separate", the splat analogue of thermal-nerfacto's
+ * density_mode "separate"): every Gaussian has a second opacity logit, opacities_thermal [N].  RGB, accumulation and depth composite with
+ * sigmoid(opacities) as above; the thermal channel composites with sigmoid(opacities_thermal) through a transmittance chain of its own over the
+ * same depth-sorted tile lists, with its own stop (a pixel's chain stops before the Gaussian that would take T to 1e-4 or below), and the thermal
+ * background is weighted by that chain's final transmittance.  In antialiased mode both opacities take the same compensation.  Each _sep entry
+ * point is the entry point it is named after plus the thermal-opacity arguments; both share one implementation, and the entry points above keep
+ * their signatures and results.  A frame is one family throughout: tn_splat_project_sep -> tn_splat_bin -> tn_splat_raster_sep, or
+ * -> tn_splat_raster_train_sep -> tn_splat_raster_backward_sep -> tn_splat_project_backward_sep, on the same workspace (a workspace projected
+ * by tn_splat_project holds no thermal opacities).  Same determinism: no float atomics, bit-identical gradients for the same inputs.  Every
+ * refusal below is TN_EINVAL before any launch.
+ *
+ * tn_splat_project_sep: tn_splat_project with opacities_thermal [N] (logits; null is refused for N > 0).  The tight tile box and the half
+ * extents of {alpha >= 1/255} come from the LARGER of the two opacities, so neither chain loses a contributor; radii, num_tiles_hit and
+ * tile_box are gsplat's, as before.  Refuses what tn_splat_project refuses, and a negative max_intersections. */
+TN_API int tn_splat_project_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
+                                const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
+                                const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased,
+                                float* xys, float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box,
+                                void* workspace, int64_t max_intersections, tn_stream_t stream);
+/* tn_splat_raster on a workspace of tn_splat_project_sep: out_rgbt [H,W,4] (thermal from its own chain), out_depth, out_alpha [H,W] (the RGB
+ * chain's accumulation) and out_alpha_thermal [H,W] (the thermal chain's).  Refuses null pointers and negative sizes. */
+TN_API int tn_splat_raster_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections, const float* background4,
+                               int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, float* out_alpha_thermal, tn_stream_t stream);
+/* tn_splat_raster_train likewise: out_transmittance / out_last are the RGB chain's, out_transmittance_thermal [H,W] / out_last_thermal [H,W] int32
+ * the thermal chain's final T and last contributor.  Refuses null pointers and negative sizes. */
+TN_API int tn_splat_raster_train_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                     const float* background4, int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha,
+                                     float* out_alpha_thermal, float* out_transmittance, int32_t* out_last, float* out_transmittance_thermal,
+                                     int32_t* out_last_thermal, tn_stream_t stream);
+/* scratch of tn_splat_raster_backward_sep (one more partial sum per pair than tn_splat_backward_workspace_bytes); -1 on bad sizes */
+TN_API int64_t tn_splat_backward_workspace_bytes_sep(int64_t num_gaussians, int64_t max_intersections);
+/* raster backward of both chains: the arguments of tn_splat_raster_backward plus the thermal chain's transmittance_thermal / last_thermal (from
+ * tn_splat_raster_train_sep) and v_alpha_thermal [H,W] = dL / d thermal accumulation.  v_rgbt's RGB channels and v_alpha feed the RGB chain, its
+ * thermal channel and v_alpha_thermal the thermal chain; v_xys and v_conics are the sums over both chains; v_log_opacity [N] and
+ * v_log_opacity_thermal [N] = dL / d ln(each opacity as the rasteriser used it).  Refuses a bad Gaussian count, num_intersections outside
+ * [0, max_intersections], null pointers (N > 0) and a bwd_workspace_bytes below tn_splat_backward_workspace_bytes_sep. */
+TN_API int tn_splat_raster_backward_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                        int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
+                                        const float* transmittance_thermal, const int32_t* last_thermal, const float* conics, const float* v_rgbt,
+                                        const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace, int64_t bwd_workspace_bytes, float* v_xys,
+                                        float* v_conics, float* v_colors, float* v_log_opacity, float* v_log_opacity_thermal, tn_stream_t stream);
+/* tn_splat_project_backward plus v_opacities_thermal [N] (logits) from v_log_opacity_thermal; in antialiased mode the covariance receives the
+ * compensation's gradient from both opacities.  Refuses what tn_splat_project_backward refuses, and null thermal-opacity pointers. */
+TN_API int tn_splat_project_backward_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
+                                         const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
+                                         const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs,
+                                         int32_t sh_degree, int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics,
+                                         const float* v_colors, const float* v_log_opacity, const float* v_log_opacity_thermal, float* v_means,
+                                         float* v_log_scales, float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest,
+                                         float* v_thermal_dc, float* v_thermal_rest, float* v_opacities_thermal, tn_stream_t stream);
+/* tn_splat_refine_plan with the both-below cull rule: a Gaussian is culled for low opacity only when sigmoid(opacities) AND
+ * sigmoid(opacities_thermal) are below cull_alpha_thresh (one that is visible in either spectrum stays).  Same workspace, counts and refusals,
+ * plus a null opacities_thermal on a step that refines. */
+TN_API int tn_splat_refine_plan_sep(const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities,
+                                    const float* opacities_thermal, const float* grad_norm_sum, const float* vis_counts, const float* max_2d_size,
+                                    int64_t num_gaussians, void* workspace, int64_t workspace_bytes, int64_t* counts_out, tn_stream_t stream);
+/* tn_splat_refine_apply over HOST arrays of 9 device pointers: the eight of tn_splat_refine_apply, then opacities_thermal [N,1], which -- with its
+ * moments -- is carried exactly as the opacities are.  counts and workspace must be those of the tn_splat_refine_plan_sep call on the same inputs. */
+TN_API int tn_splat_refine_apply_sep(const TnSplatRefine* config, int64_t num_gaussians, int32_t num_rest_coeffs, const void* workspace,
+                                     int64_t workspace_bytes, const int64_t* counts, const float* noise, const float* const* params,
+                                     const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params, float* const* new_exp_avg,
+                                     float* const* new_exp_avg_sq, tn_stream_t stream);
 /* ---- N4 training loss: splatfacto's (1 - ssim_lambda) * L1 + ssim_lambda * (1 - SSIM) (nerfstudio/models/splatfacto.py:863-903), SSIM as
  * pytorch_msssim computes it: an 11-tap Gaussian window (sigma 1.5) applied separably as a VALID correlation, C1 = 0.01^2, C2 = 0.03^2 (data
  * range 1), mean over the (H-10) x (W-10) valid pixels and the channels.  L1 = mean |pred - gt| over all H W C values.  Deterministic: no

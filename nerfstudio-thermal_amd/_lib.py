@@ -198,6 +198,15 @@ SIGNATURES = {
     "tn_splat_refine_workspace_bytes": (_i64, [_i64, _i32]),
     "tn_splat_refine_plan": (C.c_int, [C.POINTER(TnSplatRefine), _i32] + [_p] * 5 + [_i64, _p, _i64, _p, _p]),
     "tn_splat_refine_apply": (C.c_int, [C.POINTER(TnSplatRefine), _i64, _i32, _p, _i64, _p, _p] + [_p] * 6 + [_p]),
+    # separate thermal opacity: each entry point above plus the thermal-opacity arguments
+    "tn_splat_project_sep": (C.c_int, [_p] * 10 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, _p]),
+    "tn_splat_raster_sep": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _p, _p, _p, _p]),
+    "tn_splat_raster_train_sep": (C.c_int, [_p, _i64, _p, _i64, _p, _i32] + [_p] * 8 + [_p]),
+    "tn_splat_backward_workspace_bytes_sep": (_i64, [_i64, _i64]),
+    "tn_splat_raster_backward_sep": (C.c_int, [_p, _i64, _p, _i64, _i64] + [_p] * 10 + [_i64] + [_p] * 6),
+    "tn_splat_project_backward_sep": (C.c_int, [_p] * 10 + [_i64, _i32, _i32, _i32] + [_p] * 16),
+    "tn_splat_refine_plan_sep": (C.c_int, [C.POINTER(TnSplatRefine), _i32] + [_p] * 6 + [_i64, _p, _i64, _p, _p]),
+    "tn_splat_refine_apply_sep": (C.c_int, [C.POINTER(TnSplatRefine), _i64, _i32, _p, _i64, _p, _p] + [_p] * 6 + [_p]),
     "tn_image_loss_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "tn_image_loss": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _f, _f, _p, _i64, _p, _p, _p]),
     "tn_image_resize": (C.c_int, [_p, _i32, _i64, _i32, _i32, _i32, _p, _i32, _i32, _p]),

@@ -39,7 +39,8 @@ struct SplatRec {  // 64 bytes per Gaussian
   float4 a;        // x, y, A, B
   float4 b;        // C, l2op (compensated opacity in antialiased mode), hx, hy: half extents of the box around {alpha >= 1/255}
   float4 c;        // r, g, b, thermal
-  float4 d;        // depth, l2op of the plain opacity, -, -
+  float4 d;        // depth, l2op of the plain opacity; separate thermal opacity (SEP): l2op of the plain thermal opacity, l2op of the thermal
+                   // opacity the thermal chain blends with (compensated in antialiased mode); else 0, 0
 };
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -138,6 +139,9 @@ struct SplatCamK {
   int W, H, tbx, tby;
 };
 
+// SEP: the thermal channel has an opacity of its own (opac_th_logit, else unused): its log2 goes into the record's two spare floats, and the box
+// around {alpha >= 1/255} comes from the larger of the two opacities, so neither chain of the rasteriser loses a contributor.
+template <bool SEP>
 __global__ void __launch_bounds__(256) k_splat_project(SplatCamK cam, const float* __restrict__ means, const float* __restrict__ log_scales,
                                                        const float* __restrict__ quats, const float* __restrict__ opac_logit,
                                                        const float* __restrict__ f_dc, const float* __restrict__ f_rest,
@@ -145,7 +149,8 @@ __global__ void __launch_bounds__(256) k_splat_project(SplatCamK cam, const floa
                                                        int rest_coeffs, int antialiased, float2* __restrict__ xys, float* __restrict__ depths,
                                                        int32_t* __restrict__ radii, float* __restrict__ conics, float* __restrict__ comp_out,
                                                        int32_t* __restrict__ tiles_hit, int32_t* __restrict__ tile_box, SplatRec* __restrict__ recs,
-                                                       int32_t* __restrict__ tbox, int32_t* __restrict__ thits) {
+                                                       int32_t* __restrict__ tbox, int32_t* __restrict__ thits,
+                                                       const float* __restrict__ opac_th_logit) {
   // The higher-order SH coefficients of the block's 256 Gaussians (45 + 15 floats each) go through LDS: the block copies its contiguous
   // 46 KB + 15 KB slab with coalesced 16-byte loads, and each thread then reads its own coefficients at stride 45 / 15 floats -- odd strides,
   // so the 64 lanes of a wave hit 64 different banks.  Reading them straight from global memory (each lane its own 180-byte run) cost
@@ -288,7 +293,9 @@ __global__ void __launch_bounds__(256) k_splat_project(SplatCamK cam, const floa
   // Tiles (and, in the rasteriser, 8x8 pixel quadrants) outside that box see nothing of the Gaussian: dropping them is EXACT.  The box is
   // intersected with gsplat's 3-sigma tile box (pixels outside THAT never see the Gaussian in the reference even where alpha >= 1/255).
   // In antialiased mode the depth pass uses the plain opacity (>= the compensated one): the bound uses the larger.
-  float smax = logf(255.0f * op);
+  float op_t = 0.0f;
+  if (SEP) op_t = 1.0f / (1.0f + expf(-opac_th_logit[i]));
+  float smax = logf(255.0f * (SEP ? fmaxf(op, op_t) : op));
   float hx = -1.0f, hy = -1.0f;
   int bx0 = 0, bx1 = 0, by0 = 0, by1 = 0;
   if (smax > 0.0f) {
@@ -309,7 +316,7 @@ __global__ void __launch_bounds__(256) k_splat_project(SplatCamK cam, const floa
   r.a = make_float4(xy.x, xy.y, 0.5f * conic.x * LOG2E, conic.y * LOG2E);
   r.b = make_float4(0.5f * conic.z * LOG2E, log2f(antialiased ? op * cmp : op), hx, hy);
   r.c = make_float4(col[0], col[1], col[2], col[3]);
-  r.d = make_float4(depth, log2f(op), 0.f, 0.f);
+  r.d = SEP ? make_float4(depth, log2f(op), log2f(op_t), log2f(antialiased ? op_t * cmp : op_t)) : make_float4(depth, log2f(op), 0.f, 0.f);
   recs[i] = r;
 }
 
@@ -404,15 +411,28 @@ __device__ __forceinline__ float splat_alpha_raw(float l2op, float power) { retu
 __device__ __forceinline__ float splat_alpha(float raw) { return fminf(0.999f, raw); }
 __device__ __forceinline__ bool splat_visible(float alpha) { return alpha >= (1.0f / 255.0f); }
 
+// The SEP instantiations' extra kernel arguments ride in a parameter pack (empty without SEP), so that the SEP = false kernels keep the argument
+// list -- and with it every kernel-argument offset -- they had before SEP existed: their instruction stream is the parent's, bit for bit.
+template <int I, typename T, typename... R>
+__device__ __forceinline__ auto pack_arg(T t, R... r) {
+  if constexpr (I == 0) return t;
+  else return pack_arg<I - 1>(r...);
+}
+
 // TRAIN: the training variant (tn_splat_raster_train) also leaves what the backward needs per pixel -- the final transmittance and the number
 // of list entries up to and including the last Gaussian that contributed -- and writes the colour BEFORE the clamp to 1 (the caller clamps,
 // so the clamp's gradient mask is the caller's).  TRAIN = false is the eval rasteriser, unchanged.
-template <bool AA, bool TRAIN>
+// SEP: the thermal channel blends with its own opacity (SplatRec::d.w) through a transmittance chain of its own (Tt / done_t, the pattern of the
+// antialiased depth pass) over the same list, with its own 1e-4 stop; RGB, accumulation and depth stay on the first chain.  It writes the
+// thermal accumulation, and in TRAIN the thermal chain's final transmittance and last contributor.  SEP = false is the kernel as it was.
+// sep_args (SEP only): float* out_alpha_th, float* out_T_th, int32_t* out_last_th.
+template <bool AA, bool TRAIN, bool SEP, typename... SepArgs>
 __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict__ recs, const int32_t* __restrict__ sorted_ids,
                                                       const int32_t* __restrict__ tile_bins, const int32_t* __restrict__ tile_order, int W, int H,
                                                       int tbx, float4 background, float* __restrict__ out_rgbt, float* __restrict__ out_depth,
                                                       float* __restrict__ out_alpha, uint32_t* __restrict__ depth_max, float* __restrict__ out_T,
-                                                      int32_t* __restrict__ out_last) {
+                                                      int32_t* __restrict__ out_last, SepArgs... sep_args) {
+  static_assert(sizeof...(SepArgs) == (SEP ? 3 : 0), "SEP takes out_alpha_th, out_T_th, out_last_th");
   __shared__ float4 sa[SPLAT_BATCH], sb[SPLAT_BATCH], sc[SPLAT_BATCH], sd[SPLAT_BATCH];
   __shared__ float smax[4];
   const int tile = tile_order[blockIdx.x];
@@ -421,11 +441,11 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
   float pxf, pyf, qcx, qcy;
   const bool inside = splat_lane_pixel(tile_x, tile_y, W, H, lane, wv, ix, iy, pxf, pyf, qcx, qcy);
   const int begin = tile_bins[2 * tile], end = tile_bins[2 * tile + 1];
-  float T = 1.0f, Td = 1.0f;
+  float T = 1.0f, Td = 1.0f, Tt = 1.0f;
   f32x2 acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};
   float dacc = 0.f;
-  bool done = !inside, done_d = !inside;
-  int last = 0;  // TRAIN: list entries of this tile up to and including the last contributor
+  bool done = !inside, done_d = !inside, done_t = !inside;
+  int last = 0, last_t = 0;  // TRAIN: list entries of this tile up to and including the last contributor (of the thermal chain: last_t)
   // software pipeline: the records of batch i+1 are fetched (two dependent gathers: id, then the 64-byte record) while batch i is blended
   float4 ra, rb, rc, rd;
   ra = rb = rc = rd = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -435,7 +455,7 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
   }
   for (int base = begin; base < end; base += SPLAT_BATCH) {
     // all 256 pixels finished -> nothing left to blend in this tile
-    if (__syncthreads_count((AA ? (done && done_d) : done) ? 1 : 0) == 256) break;
+    if (__syncthreads_count(((AA ? (done && done_d) : done) && (SEP ? done_t : true)) ? 1 : 0) == 256) break;
     sa[threadIdx.x] = ra; sb[threadIdx.x] = rb; sc[threadIdx.x] = rc; sd[threadIdx.x] = rd;
     __syncthreads();
     {
@@ -447,7 +467,7 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
     }
     const int n = min(SPLAT_BATCH, end - base);
     // the whole wave is done: skip the arithmetic of this batch (wave-uniform branch)
-    if (__all((AA ? (done && done_d) : done) ? 1 : 0)) continue;
+    if (__all(((AA ? (done && done_d) : done) && (SEP ? done_t : true)) ? 1 : 0)) continue;
     // Per-wave culling, 64 Gaussians per step: lane l tests Gaussian 64 q + l against this wave's quadrant (box around {alpha >= 1/255},
     // see k_splat_project); the ballot is the list of Gaussians that can touch the quadrant, walked with scalar bit operations.  A
     // Gaussian that misses the quadrant costs 1/64 of a test instead of a full evaluation on all 64 lanes.
@@ -472,7 +492,8 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
         float ex = b.y - power;
         // nobody in the wave can reach alpha >= 1/255 = 2^-7.994 (or the form is negative): skip the exponential and the blend
         // (antialiased: the depth pass blends with the plain opacity, which is the larger one)
-        if (!__any((power >= 0.f && (AA ? sd[k].y - power : ex) >= -8.0f) ? 1 : 0)) continue;
+        // (SEP: the larger of the two plain opacities bounds every chain)
+        if (!__any((power >= 0.f && (SEP ? fmaxf(AA ? sd[k].y : b.y, sd[k].z) - power : (AA ? sd[k].y - power : ex)) >= -8.0f) ? 1 : 0)) continue;
         if (power < 0.f) continue;
         const float alpha = splat_alpha(splat_alpha_raw(b.y, power));
         const bool vis_c = splat_visible(alpha);  // (evaluated ahead of the &&: inside it the compiler branches on `done` first)
@@ -484,7 +505,8 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
             float4 c = sc[k];
             f32x2 v2 = {vis, vis};
             acc01 = __builtin_elementwise_fma(v2, (f32x2){c.x, c.y}, acc01);
-            acc23 = __builtin_elementwise_fma(v2, (f32x2){c.z, c.w}, acc23);
+            if (SEP) acc23.x = fmaf(vis, c.z, acc23.x);
+            else acc23 = __builtin_elementwise_fma(v2, (f32x2){c.z, c.w}, acc23);
             if (!AA) dacc = fmaf(vis, sd[k].x, dacc);
             T = nT;
             if (TRAIN) last = base + k - begin + 1;
@@ -500,6 +522,19 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
             else { dacc = fmaf(alpha_d * Td, d.x, dacc); Td = nT; }
           }
         }
+        if (SEP) {
+          const float alpha_t = splat_alpha(splat_alpha_raw(sd[k].w, power));
+          const bool vis_t = splat_visible(alpha_t);
+          if (!done_t && vis_t) {
+            float nT = fmaf(-alpha_t, Tt, Tt);
+            if (nT <= 1e-4f) done_t = true;  // the thermal chain's own stop, the same rule
+            else {
+              acc23.y = fmaf(alpha_t * Tt, sc[k].w, acc23.y);
+              Tt = nT;
+              if (TRAIN) last_t = base + k - begin + 1;
+            }
+          }
+        }
       }
     }
   }
@@ -507,17 +542,20 @@ __global__ void __launch_bounds__(256) k_splat_raster(const SplatRec* __restrict
   float dmax = 0.f;
   if (inside) {
     int64_t p = (int64_t)iy * W + ix;
+    const float Tw = SEP ? Tt : T;  // what is left for the thermal background
     if (TRAIN) {
       reinterpret_cast<float4*>(out_rgbt)[p] =
-          make_float4(acc[0] + T * background.x, acc[1] + T * background.y, acc[2] + T * background.z, acc[3] + T * background.w);
+          make_float4(acc[0] + T * background.x, acc[1] + T * background.y, acc[2] + T * background.z, acc[3] + Tw * background.w);
       out_T[p] = T;
       out_last[p] = last;
+      if constexpr (SEP) { pack_arg<1>(sep_args...)[p] = Tt; pack_arg<2>(sep_args...)[p] = last_t; }
     } else {
       float4 o = make_float4(fminf(acc[0] + T * background.x, 1.0f), fminf(acc[1] + T * background.y, 1.0f), fminf(acc[2] + T * background.z, 1.0f),
-                             fminf(acc[3] + T * background.w, 1.0f));
+                             fminf(acc[3] + Tw * background.w, 1.0f));
       reinterpret_cast<float4*>(out_rgbt)[p] = o;
     }
     out_alpha[p] = 1.0f - T;
+    if constexpr (SEP) pack_arg<0>(sep_args...)[p] = 1.0f - Tt;
     out_depth[p] = dacc;  // un-normalised: k_splat_depth_finalize divides by alpha
     dmax = dacc;
   }
@@ -551,16 +589,17 @@ __global__ void k_splat_depth_finalize(float* __restrict__ depth, const float* _
 //   k_splat_project_bwd thread = Gaussian: through the EWA projection, the covariance, the quaternion normalisation, SH and sigmoids to the
 //                       parameters, written in their own layouts.
 #define SPLAT_PAIR_GRADS 10  // per pair, summed over pixels: dsigma*dx, dsigma*dy, dsigma*dx^2/2, dsigma*dx*dy, dsigma*dy^2/2, d colour (4), d ln(opacity)
+#define SPLAT_PAIR_GRADS_SEP (SPLAT_PAIR_GRADS + 1)  // separate thermal opacity: one more, d ln(thermal opacity)
 
 struct SplatBwdWs {
-  float* pair;     // [max_intersections][SPLAT_PAIR_GRADS]
+  float* pair;     // [max_intersections][SPLAT_PAIR_GRADS or SPLAT_PAIR_GRADS_SEP]
   int32_t* start;  // [N] first record of each Gaussian's run
 };
 
-static SplatBwdWs splat_bwd_layout(void* base, int64_t N, int64_t capacity, size_t* total) {
+static SplatBwdWs splat_bwd_layout(void* base, int64_t N, int64_t capacity, int pair_grads, size_t* total) {
   SplatBwdWs w;
   Carve cv{(char*)base, 0};
-  w.pair = (float*)cv.take(sizeof(float) * SPLAT_PAIR_GRADS * (size_t)std::max<int64_t>(capacity, 1));
+  w.pair = (float*)cv.take(sizeof(float) * pair_grads * (size_t)std::max<int64_t>(capacity, 1));
   w.start = (int32_t*)cv.take(4 * (size_t)std::max<int64_t>(N, 1));
   if (total) *total = cv.off;
   return w;
@@ -569,7 +608,14 @@ static SplatBwdWs splat_bwd_layout(void* base, int64_t N, int64_t capacity, size
 extern "C" int64_t tn_splat_backward_workspace_bytes(int64_t num_gaussians, int64_t max_intersections) {
   if (num_gaussians < 0 || max_intersections < 0) return -1;
   size_t total = 0;
-  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, &total);
+  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, SPLAT_PAIR_GRADS, &total);
+  return (int64_t)total;
+}
+
+extern "C" int64_t tn_splat_backward_workspace_bytes_sep(int64_t num_gaussians, int64_t max_intersections) {
+  if (num_gaussians < 0 || max_intersections < 0) return -1;
+  size_t total = 0;
+  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, SPLAT_PAIR_GRADS_SEP, &total);
   return (int64_t)total;
 }
 
@@ -582,13 +628,26 @@ __global__ void k_splat_run_start(const int32_t* __restrict__ order, const int32
   start[g] = cum[j] - thits[g];
 }
 
+// SEP (separate thermal opacity): every pixel walks from the larger of its two chains' last contributors and keeps two T / rest pairs.  RGB and
+// v_alpha feed chain 1 (alpha from SplatRec::b.y), the thermal channel and v_alpha_th chain 2 (alpha from SplatRec::d.w); the five geometry sums
+// receive both chains' d_sigma, and the pair record grows by d ln(thermal opacity).  SEP = false is the kernel as it was.
+// sep_args (SEP only): const float* final_T_th, const int32_t* last_th, const float* v_alpha_th.
+template <bool SEP, typename... SepArgs>
 __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __restrict__ recs, const int32_t* __restrict__ sorted_ids,
                                                           const int32_t* __restrict__ tile_bins, const int32_t* __restrict__ tile_order, int W, int H,
                                                           int tbx, float4 background, const float* __restrict__ final_T, const int32_t* __restrict__ last,
                                                           const float* __restrict__ v_rgbt, const float* __restrict__ v_alpha,
-                                                          const int32_t* __restrict__ start, const int32_t* __restrict__ tbox, float* __restrict__ pair) {
+                                                          const int32_t* __restrict__ start, const int32_t* __restrict__ tbox, float* __restrict__ pair,
+                                                          SepArgs... sep_args) {
+  static_assert(sizeof...(SepArgs) == (SEP ? 3 : 0), "SEP takes final_T_th, last_th, v_alpha_th");
+  constexpr int NG = SEP ? SPLAT_PAIR_GRADS_SEP : SPLAT_PAIR_GRADS;
   __shared__ float4 sa[SPLAT_BATCH], sb[SPLAT_BATCH], sc[SPLAT_BATCH];
-  __shared__ float sp[4][SPLAT_PAIR_GRADS][SPLAT_BATCH];  // per wave partial sums of the batch's Gaussians
+  float* l2t = nullptr;  // SEP: l2op of the thermal chain (SplatRec::d.w) of the batch's Gaussians
+  if constexpr (SEP) {
+    __shared__ float s_l2t[SPLAT_BATCH];
+    l2t = s_l2t;
+  }
+  __shared__ float sp[4][NG][SPLAT_BATCH];  // per wave partial sums of the batch's Gaussians (SEP: 57 KB of LDS with the records, 2 blocks per CU as before)
   __shared__ int s_n;
   const int tile = tile_order[blockIdx.x];
   const int tile_x = tile % tbx, tile_y = tile / tbx;
@@ -599,16 +658,24 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
   // T: transmittance after the Gaussian being visited (starts at the final one); rest: sum over the Gaussians behind it of
   // alpha_j T_j <colour_j, v> plus the background's T_final <bg, v> - T_final d accumulation (accumulation = 1 - T_final)
   float T = 1.f, rest = 0.f;
+  float Tt = 1.f, rest_t = 0.f;  // SEP: the thermal chain's
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  int n = 0;
+  int n = 0, nt = 0;
   if (inside) {
     const int64_t p = (int64_t)iy * W + ix;
     T = final_T[p];
     n = last[p];
     v = reinterpret_cast<const float4*>(v_rgbt)[p];
-    rest = T * (v.x * background.x + v.y * background.y + v.z * background.z + v.w * background.w - v_alpha[p]);
+    if constexpr (SEP) {
+      rest = T * (v.x * background.x + v.y * background.y + v.z * background.z - v_alpha[p]);
+      Tt = pack_arg<0>(sep_args...)[p];
+      nt = pack_arg<1>(sep_args...)[p];
+      rest_t = Tt * (v.w * background.w - pack_arg<2>(sep_args...)[p]);
+    } else {
+      rest = T * (v.x * background.x + v.y * background.y + v.z * background.z + v.w * background.w - v_alpha[p]);
+    }
   }
-  int wn = n;
+  int wn = SEP ? max(n, nt) : n;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) wn = max(wn, __shfl_xor(wn, o, 64));
   if (threadIdx.x == 0) s_n = 0;
@@ -624,13 +691,14 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
       const int g = sorted_ids[lo + (int)threadIdx.x];
       const SplatRec* r = recs + g;
       sa[threadIdx.x] = r->a; sb[threadIdx.x] = r->b; sc[threadIdx.x] = r->c;
+      if (SEP) l2t[threadIdx.x] = r->d.w;
       const int4 bx = reinterpret_cast<const int4*>(tbox)[g];
       dst = (int64_t)start[g] + (tile_y - bx.y) * (bx.z - bx.x) + (tile_x - bx.x);
     }
 #pragma unroll
     for (int w = 0; w < 4; ++w)
 #pragma unroll
-      for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) sp[w][c][threadIdx.x] = 0.f;
+      for (int c = 0; c < NG; ++c) sp[w][c][threadIdx.x] = 0.f;
     __syncthreads();
     // back to front; per-wave culling as in the forward (the quadrant test is exact: outside it alpha < 1/255)
 #pragma unroll 1
@@ -653,19 +721,27 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
         const float raw = splat_alpha_raw(b.y, power);
         const float alpha = splat_alpha(raw);
         const bool use = lo + k - begin < n && power >= 0.f && splat_visible(alpha);
-        if (!__any(use ? 1 : 0)) continue;
-        float g[SPLAT_PAIR_GRADS];
+        float raw_t = 0.f, alpha_t = 0.f;
+        bool use_t = false;
+        if (SEP) {
+          raw_t = splat_alpha_raw(l2t[k], power);
+          alpha_t = splat_alpha(raw_t);
+          use_t = lo + k - begin < nt && power >= 0.f && splat_visible(alpha_t);
+        }
+        if (!__any((SEP ? (use || use_t) : use) ? 1 : 0)) continue;
+        float g[NG];
 #pragma unroll
-        for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) g[c] = 0.f;
+        for (int c = 0; c < NG; ++c) g[c] = 0.f;
         if (use) {
           const float om = 1.0f - alpha;
           T = T / om;  // transmittance in front of this Gaussian
           const float4 col = sc[k];
-          const float cv = col.x * v.x + col.y * v.y + col.z * v.z + col.w * v.w;
+          const float cv = SEP ? col.x * v.x + col.y * v.y + col.z * v.z : col.x * v.x + col.y * v.y + col.z * v.z + col.w * v.w;
           const float vis = alpha * T;
           const float d_alpha = T * cv - rest / om;
           rest = fmaf(vis, cv, rest);
-          g[5] = vis * v.x; g[6] = vis * v.y; g[7] = vis * v.z; g[8] = vis * v.w;
+          g[5] = vis * v.x; g[6] = vis * v.y; g[7] = vis * v.z;
+          if (!SEP) g[8] = vis * v.w;
           if (raw <= 0.999f) {  // the clamp passes gradient where torch.clamp's backward does
             const float d_lnop = d_alpha * alpha;  // alpha = opacity exp(-sigma)
             const float d_sigma = -d_lnop;
@@ -674,39 +750,56 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
             g[9] = d_lnop;
           }
         }
+        if (SEP && use_t) {  // the thermal chain: the same derivative with its own alpha, T and rest
+          const float om = 1.0f - alpha_t;
+          Tt = Tt / om;
+          const float cv = sc[k].w * v.w;
+          const float vis = alpha_t * Tt;
+          const float d_alpha = Tt * cv - rest_t / om;
+          rest_t = fmaf(vis, cv, rest_t);
+          g[8] = vis * v.w;
+          if (raw_t <= 0.999f) {
+            const float d_lnop = d_alpha * alpha_t;
+            const float d_sigma = -d_lnop;
+            g[0] += d_sigma * dx; g[1] += d_sigma * dy;
+            g[2] += 0.5f * d_sigma * dx * dx; g[3] += d_sigma * dx * dy; g[4] += 0.5f * d_sigma * dy * dy;
+            g[NG - 1] = d_lnop;
+          }
+        }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1)
 #pragma unroll
-          for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) g[c] += __shfl_xor(g[c], o, 64);
+          for (int c = 0; c < NG; ++c) g[c] += __shfl_xor(g[c], o, 64);
         if (lane == 0) {
 #pragma unroll
-          for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) sp[wv][c][k] = g[c];
+          for (int c = 0; c < NG; ++c) sp[wv][c][k] = g[c];
         }
       }
     }
     __syncthreads();
     if (dst >= 0) {
-      float* o = pair + dst * SPLAT_PAIR_GRADS;
+      float* o = pair + dst * NG;
 #pragma unroll
-      for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) o[c] = ((sp[0][c][threadIdx.x] + sp[1][c][threadIdx.x]) + sp[2][c][threadIdx.x]) + sp[3][c][threadIdx.x];
+      for (int c = 0; c < NG; ++c) o[c] = ((sp[0][c][threadIdx.x] + sp[1][c][threadIdx.x]) + sp[2][c][threadIdx.x]) + sp[3][c][threadIdx.x];
     }
   }
 }
 
+template <int NG>  // SPLAT_PAIR_GRADS, or SPLAT_PAIR_GRADS_SEP: the last sum is d ln(thermal opacity) -> v_lnop_th
 __global__ void k_splat_pair_fold(const float* __restrict__ pair, const int32_t* __restrict__ start, const int32_t* __restrict__ thits,
                                   const float* __restrict__ conics, int64_t N, float* __restrict__ v_xys, float* __restrict__ v_conics,
-                                  float* __restrict__ v_colors, float* __restrict__ v_lnop) {
+                                  float* __restrict__ v_colors, float* __restrict__ v_lnop, float* __restrict__ v_lnop_th) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= N) return;
-  float s[SPLAT_PAIR_GRADS];
+  float s[NG];
 #pragma unroll
-  for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) s[c] = 0.f;
+  for (int c = 0; c < NG; ++c) s[c] = 0.f;
   const int cnt = thits[i];
   if (cnt > 0) {
-    const float* p = pair + (int64_t)start[i] * SPLAT_PAIR_GRADS;
-    for (int j = 0; j < cnt; ++j, p += SPLAT_PAIR_GRADS)
+    const float* p = pair + (int64_t)start[i] * NG;
+    for (int j = 0; j < cnt; ++j, p += NG)
 #pragma unroll
-      for (int c = 0; c < SPLAT_PAIR_GRADS; ++c) s[c] += p[c];
+      for (int c = 0; c < NG; ++c) s[c] += p[c];
   }
   // d sigma / d xy = (cx dx + cy dy, cy dx + cz dy), dx = x - pixel
   const float cx = conics[3 * i], cy = conics[3 * i + 1], cz = conics[3 * i + 2];
@@ -715,6 +808,7 @@ __global__ void k_splat_pair_fold(const float* __restrict__ pair, const int32_t*
   v_conics[3 * i] = s[2]; v_conics[3 * i + 1] = s[3]; v_conics[3 * i + 2] = s[4];
   v_colors[4 * i] = s[5]; v_colors[4 * i + 1] = s[6]; v_colors[4 * i + 2] = s[7]; v_colors[4 * i + 3] = s[8];
   v_lnop[i] = s[9];
+  if (NG > SPLAT_PAIR_GRADS) v_lnop_th[i] = s[NG - 1];
 }
 
 // SH basis of degree <= 3 at the unit direction (x, y, z), the coefficients of sh_eval
@@ -732,6 +826,8 @@ __device__ __forceinline__ void sh_basis(int degree, float x, float y, float z, 
   b[14] = 1.445305721320277f * z * (xx - yy); b[15] = -0.5900435899266435f * x * (xx - 3.0f * yy);
 }
 
+// SEP: also d thermal-opacity logit (g_opac_th) from v_lnop_th = d ln(thermal opacity); in antialiased mode the compensation takes both
+template <bool SEP>
 __global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const float* __restrict__ means, const float* __restrict__ log_scales,
                                                            const float* __restrict__ quats, const float* __restrict__ opac_logit,
                                                            const float* __restrict__ f_dc, const float* __restrict__ f_rest, const float* __restrict__ t_dc,
@@ -740,10 +836,12 @@ __global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const 
                                                            const float* __restrict__ v_conics, const float* __restrict__ v_colors,
                                                            const float* __restrict__ v_lnop, float* __restrict__ g_means, float* __restrict__ g_scales,
                                                            float* __restrict__ g_quats, float* __restrict__ g_opac, float* __restrict__ g_fdc,
-                                                           float* __restrict__ g_frest, float* __restrict__ g_tdc, float* __restrict__ g_trest) {
+                                                           float* __restrict__ g_frest, float* __restrict__ g_tdc, float* __restrict__ g_trest,
+                                                           const float* __restrict__ opac_th_logit, const float* __restrict__ v_lnop_th,
+                                                           float* __restrict__ g_opac_th) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= N) return;
-  float gm[3] = {0.f, 0.f, 0.f}, gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f}, gop = 0.f;
+  float gm[3] = {0.f, 0.f, 0.f}, gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f}, gop = 0.f, gop_t = 0.f;
   float gcol[4] = {0.f, 0.f, 0.f, 0.f};  // d (colour before the clamp / sigmoid argument), per channel
   float basis[16];
   int nb = 0;
@@ -803,14 +901,18 @@ __global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const 
     float vb = vcx * 2.f * b * c * id2 + vcy * (-id - 2.f * b * b * id2) + vcz * 2.f * a * b * id2;
     float vc = vcx * (id - a * c * id2) + vcy * a * b * id2 - vcz * a * a * id2;
     const float dl = v_lnop[i];
+    float dl_t = 0.f;
+    if (SEP) dl_t = v_lnop_th[i];
+    const float dl_c = SEP ? dl + dl_t : dl;  // both compensated opacities carry the compensation
     if (antialiased && det_orig > 0.f) {  // ln compensation = (ln det_orig - ln det) / 2
       const float io = 1.0f / det_orig;
-      va += 0.5f * dl * (c11 * io - c * id);
-      vb += 0.5f * dl * (-2.f * c01 * io + 2.f * b * id);
-      vc += 0.5f * dl * (c00 * io - a * id);
+      va += 0.5f * dl_c * (c11 * io - c * id);
+      vb += 0.5f * dl_c * (-2.f * c01 * io + 2.f * b * id);
+      vc += 0.5f * dl_c * (c00 * io - a * id);
     }
     // opacity = sigmoid(logit): d ln(sigmoid) / d logit = sigmoid(-logit)
     gop = dl / (1.0f + expf(opac_logit[i]));
+    if (SEP) gop_t = dl_t / (1.0f + expf(opac_th_logit[i]));
     // cov2d = T Sigma T^T, T = J W
     float gT0[3], gT1[3];
 #pragma unroll
@@ -899,6 +1001,7 @@ __global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const 
 #pragma unroll
   for (int cc = 0; cc < 4; ++cc) g_quats[4 * i + cc] = gq[cc];
   g_opac[i] = gop;
+  if (SEP) g_opac_th[i] = gop_t;
   const float b0 = nb > 0 ? basis[0] : 1.0f;  // sigmoid path: the DC gradient is gcol itself
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) g_fdc[3 * i + ch] = b0 * gcol[ch];
@@ -930,32 +1033,55 @@ static SplatCamK make_camk(const TnSplatCamera* cam) {
   return k;
 }
 
+// The _sep entry points (separate thermal opacity) share their implementation with the entry points they extend: `sep` picks the SEP
+// instantiation of the kernels, and the thermal-opacity pointers, null in shared mode, are then required.  `who` names the entry point in messages.
+static int splat_project(const char* who, bool sep, const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
+                         const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
+                         const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys,
+                         float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
+                         int64_t max_intersections, tn_stream_t stream) {
+  int rc = check_cam(camera, who);
+  if (rc) return rc;
+  if (num_gaussians == 0) return TN_OK;
+  TN_REQUIRE(means && log_scales && quats && opacities && features_dc && thermal_dc && xys && depths && radii && conics && compensation &&
+                 num_tiles_hit && tile_box && workspace && (!sep || opacities_thermal),
+             "%s: null pointer", who);
+  TN_REQUIRE(num_gaussians > 0 && num_gaussians < (1ll << 31), "%s: bad Gaussian count", who);
+  TN_REQUIRE(max_intersections >= 0 || !sep, "%s: bad workspace capacity", who);
+  TN_REQUIRE(sh_degree >= -1 && sh_degree <= 3, "%s: sh_degree %d unsupported (-1 = sigmoid of the DC term, 0..3)", who, sh_degree);
+  TN_REQUIRE(num_rest_coeffs >= (sh_degree < 1 ? 0 : (sh_degree + 1) * (sh_degree + 1) - 1), "%s: %d higher-order coefficients for degree %d", who,
+             num_rest_coeffs, sh_degree);
+  TN_REQUIRE(num_rest_coeffs == 0 || (features_rest && thermal_rest), "%s: null SH coefficients", who);
+  SplatCamK k = make_camk(camera);
+  SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, k.tbx * k.tby, nullptr);
+  const int PB = 128;  // Gaussians per block: 30 KB of LDS at degree 3 -> 5 blocks per CU (256 per block = 61 KB = 2 blocks: 136 vs 1xx us)
+  const size_t lds = (size_t)PB * num_rest_coeffs * 4 * sizeof(float);
+  TN_REQUIRE(lds <= 65536, "%s: %d higher-order coefficients do not fit the LDS staging", who, num_rest_coeffs);
+  hipLaunchKernelGGL(sep ? k_splat_project<true> : k_splat_project<false>, dim3((unsigned)tn_cdiv(num_gaussians, PB)), dim3(PB), lds, tn_s(stream), k, means,
+                     log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased,
+                     (float2*)xys, depths, radii, conics, compensation, num_tiles_hit, tile_box, ws.recs, ws.tbox, ws.thits, opacities_thermal);
+  TN_CHECK_LAUNCH(who);
+  return TN_OK;
+}
+
 extern "C" int tn_splat_project(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
                                 const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
                                 int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys, float* depths,
                                 int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
                                 int64_t max_intersections, tn_stream_t stream) {
-  int rc = check_cam(camera, "tn_splat_project");
-  if (rc) return rc;
-  if (num_gaussians == 0) return TN_OK;
-  TN_REQUIRE(means && log_scales && quats && opacities && features_dc && thermal_dc && xys && depths && radii && conics && compensation &&
-                 num_tiles_hit && tile_box && workspace,
-             "tn_splat_project: null pointer");
-  TN_REQUIRE(num_gaussians > 0 && num_gaussians < (1ll << 31), "tn_splat_project: bad Gaussian count");
-  TN_REQUIRE(sh_degree >= -1 && sh_degree <= 3, "tn_splat_project: sh_degree %d unsupported (-1 = sigmoid of the DC term, 0..3)", sh_degree);
-  TN_REQUIRE(num_rest_coeffs >= (sh_degree < 1 ? 0 : (sh_degree + 1) * (sh_degree + 1) - 1), "tn_splat_project: %d higher-order coefficients for degree %d",
-             num_rest_coeffs, sh_degree);
-  TN_REQUIRE(num_rest_coeffs == 0 || (features_rest && thermal_rest), "tn_splat_project: null SH coefficients");
-  SplatCamK k = make_camk(camera);
-  SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, k.tbx * k.tby, nullptr);
-  const int PB = 128;  // Gaussians per block: 30 KB of LDS at degree 3 -> 5 blocks per CU (256 per block = 61 KB = 2 blocks: 136 vs 1xx us)
-  const size_t lds = (size_t)PB * num_rest_coeffs * 4 * sizeof(float);
-  TN_REQUIRE(lds <= 65536, "tn_splat_project: %d higher-order coefficients do not fit the LDS staging", num_rest_coeffs);
-  hipLaunchKernelGGL(k_splat_project, dim3((unsigned)tn_cdiv(num_gaussians, PB)), dim3(PB), lds, tn_s(stream), k, means, log_scales, quats, opacities,
-                     features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, (float2*)xys, depths, radii,
-                     conics, compensation, num_tiles_hit, tile_box, ws.recs, ws.tbox, ws.thits);
-  TN_CHECK_LAUNCH("tn_splat_project");
-  return TN_OK;
+  return splat_project("tn_splat_project", false, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, nullptr,
+                       num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation, num_tiles_hit, tile_box, workspace,
+                       max_intersections, stream);
+}
+
+extern "C" int tn_splat_project_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
+                                    const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
+                                    const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased,
+                                    float* xys, float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box,
+                                    void* workspace, int64_t max_intersections, tn_stream_t stream) {
+  return splat_project("tn_splat_project_sep", true, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
+                       opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation, num_tiles_hit,
+                       tile_box, workspace, max_intersections, stream);
 }
 
 extern "C" int tn_splat_bin(const TnSplatCamera* camera, const float* depths, int64_t num_gaussians, void* workspace, int64_t max_intersections,
@@ -1030,14 +1156,22 @@ extern "C" int tn_splat_bin(const TnSplatCamera* camera, const float* depths, in
 // the depth normalisation.  `who` / `who_depth` name the entry point's two launches in error messages.
 static int splat_raster(const char* who, const char* who_depth, const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
                         const float* background4, int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, float* out_T, int32_t* out_last,
-                        tn_stream_t stream) {
+                        float* out_alpha_th, float* out_T_th, int32_t* out_last_th, tn_stream_t stream) {
   SplatCamK k = make_camk(camera);
   SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, k.tbx * k.tby, nullptr);
   float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
   hipStream_t st = tn_s(stream);
-  auto kernel = antialiased ? (out_T ? k_splat_raster<true, true> : k_splat_raster<true, false>) : (out_T ? k_splat_raster<false, true> : k_splat_raster<false, false>);
-  hipLaunchKernelGGL(kernel, dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, out_rgbt, out_depth,
-                     out_alpha, ws.depth_max, out_T, out_last);
+  if (out_alpha_th) {  // the caller is a _sep entry point (separate thermal opacity)
+    auto kernel = antialiased ? (out_T ? k_splat_raster<true, true, true, float*, float*, int32_t*> : k_splat_raster<true, false, true, float*, float*, int32_t*>)
+                              : (out_T ? k_splat_raster<false, true, true, float*, float*, int32_t*> : k_splat_raster<false, false, true, float*, float*, int32_t*>);
+    hipLaunchKernelGGL(kernel, dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, out_rgbt, out_depth,
+                       out_alpha, ws.depth_max, out_T, out_last, out_alpha_th, out_T_th, out_last_th);
+  } else {
+    auto kernel = antialiased ? (out_T ? k_splat_raster<true, true, false> : k_splat_raster<true, false, false>)
+                              : (out_T ? k_splat_raster<false, true, false> : k_splat_raster<false, false, false>);
+    hipLaunchKernelGGL(kernel, dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, out_rgbt, out_depth,
+                       out_alpha, ws.depth_max, out_T, out_last);
+  }
   TN_CHECK_LAUNCH(who);
   int64_t n = (int64_t)k.W * k.H;
   hipLaunchKernelGGL(k_splat_depth_finalize, dim3((unsigned)tn_cdiv(n, 256)), dim3(256), 0, st, out_depth, out_alpha, ws.depth_max, n);
@@ -1051,7 +1185,17 @@ extern "C" int tn_splat_raster(const TnSplatCamera* camera, int64_t num_gaussian
   if (rc) return rc;
   TN_REQUIRE(workspace && background4 && out_rgbt && out_depth && out_alpha, "tn_splat_raster: null pointer");
   return splat_raster("tn_splat_raster", "tn_splat_raster(depth)", camera, num_gaussians, workspace, max_intersections, background4, antialiased, out_rgbt, out_depth, out_alpha, nullptr,
-                      nullptr, stream);
+                      nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int tn_splat_raster_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections, const float* background4,
+                                   int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, float* out_alpha_thermal, tn_stream_t stream) {
+  int rc = check_cam(camera, "tn_splat_raster_sep");
+  if (rc) return rc;
+  TN_REQUIRE(workspace && background4 && out_rgbt && out_depth && out_alpha && out_alpha_thermal, "tn_splat_raster_sep: null pointer");
+  TN_REQUIRE(num_gaussians >= 0 && max_intersections >= 0, "tn_splat_raster_sep: bad sizes");
+  return splat_raster("tn_splat_raster_sep", "tn_splat_raster_sep(depth)", camera, num_gaussians, workspace, max_intersections, background4, antialiased, out_rgbt,
+                      out_depth, out_alpha, nullptr, nullptr, out_alpha_thermal, nullptr, nullptr, stream);
 }
 
 extern "C" int tn_splat_raster_train(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
@@ -1062,7 +1206,66 @@ extern "C" int tn_splat_raster_train(const TnSplatCamera* camera, int64_t num_ga
   TN_REQUIRE(workspace && background4 && out_rgbt && out_depth && out_alpha && out_transmittance && out_last, "tn_splat_raster_train: null pointer");
   TN_REQUIRE(num_gaussians >= 0 && max_intersections >= 0, "tn_splat_raster_train: bad sizes");
   return splat_raster("tn_splat_raster_train", "tn_splat_raster_train(depth)", camera, num_gaussians, workspace, max_intersections, background4, antialiased, out_rgbt, out_depth, out_alpha,
-                      out_transmittance, out_last, stream);
+                      out_transmittance, out_last, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int tn_splat_raster_train_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                         const float* background4, int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha,
+                                         float* out_alpha_thermal, float* out_transmittance, int32_t* out_last, float* out_transmittance_thermal,
+                                         int32_t* out_last_thermal, tn_stream_t stream) {
+  int rc = check_cam(camera, "tn_splat_raster_train_sep");
+  if (rc) return rc;
+  TN_REQUIRE(workspace && background4 && out_rgbt && out_depth && out_alpha && out_alpha_thermal && out_transmittance && out_last &&
+                 out_transmittance_thermal && out_last_thermal,
+             "tn_splat_raster_train_sep: null pointer");
+  TN_REQUIRE(num_gaussians >= 0 && max_intersections >= 0, "tn_splat_raster_train_sep: bad sizes");
+  return splat_raster("tn_splat_raster_train_sep", "tn_splat_raster_train_sep(depth)", camera, num_gaussians, workspace, max_intersections, background4, antialiased,
+                      out_rgbt, out_depth, out_alpha, out_transmittance, out_last, out_alpha_thermal, out_transmittance_thermal, out_last_thermal, stream);
+}
+
+static int splat_raster_backward(const char* who, bool sep, const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                 int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
+                                 const float* transmittance_th, const int32_t* last_th, const float* conics, const float* v_rgbt, const float* v_alpha,
+                                 const float* v_alpha_th, void* bwd_workspace, int64_t bwd_workspace_bytes, float* v_xys, float* v_conics, float* v_colors,
+                                 float* v_log_opacity, float* v_log_opacity_th, tn_stream_t stream) {
+  int rc = check_cam(camera, who);
+  if (rc) return rc;
+  TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31), "%s: bad Gaussian count", who);
+  TN_REQUIRE(max_intersections >= 0 && num_intersections >= 0 && num_intersections <= max_intersections, "%s: %lld intersections for a workspace of %lld", who,
+             (long long)num_intersections, (long long)max_intersections);
+  if (num_gaussians == 0) return TN_OK;
+  TN_REQUIRE(workspace && background4 && transmittance && last && conics && v_rgbt && v_alpha && bwd_workspace && v_xys && v_conics && v_colors &&
+                 v_log_opacity && (!sep || (transmittance_th && last_th && v_alpha_th && v_log_opacity_th)),
+             "%s: null pointer", who);
+  const int ng = sep ? SPLAT_PAIR_GRADS_SEP : SPLAT_PAIR_GRADS;
+  const int64_t need = sep ? tn_splat_backward_workspace_bytes_sep(num_gaussians, max_intersections) : tn_splat_backward_workspace_bytes(num_gaussians, max_intersections);
+  TN_REQUIRE(bwd_workspace_bytes >= need, "%s: backward workspace of %lld bytes, %lld needed", who, (long long)bwd_workspace_bytes, (long long)need);
+  SplatCamK k = make_camk(camera);
+  const int num_tiles = k.tbx * k.tby;
+  SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, num_tiles, nullptr);
+  SplatBwdWs bw = splat_bwd_layout(bwd_workspace, num_gaussians, max_intersections, ng, nullptr);
+  hipStream_t st = tn_s(stream);
+  hipLaunchKernelGGL(k_splat_run_start, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, st, ws.order, ws.cum, ws.thits, num_gaussians, bw.start);
+  TN_CHECK_LAUNCH(who);
+  if (num_intersections > 0) {
+    // pairs behind every pixel's last contributor are not visited: their records stay zero
+    if (hipMemsetAsync(bw.pair, 0, sizeof(float) * ng * (size_t)num_intersections, st) != hipSuccess) {
+      tn_set_error("%s: memset failed", who);
+      return TN_ELAUNCH;
+    }
+    float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
+    if (sep)
+      hipLaunchKernelGGL((k_splat_raster_bwd<true, const float*, const int32_t*, const float*>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins,
+                         ws.lvals[1], k.W, k.H, k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, transmittance_th, last_th, v_alpha_th);
+    else
+      hipLaunchKernelGGL(k_splat_raster_bwd<false>, dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg,
+                         transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair);
+    TN_CHECK_LAUNCH(who);
+  }
+  hipLaunchKernelGGL(sep ? k_splat_pair_fold<SPLAT_PAIR_GRADS_SEP> : k_splat_pair_fold<SPLAT_PAIR_GRADS>, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, st,
+                     bw.pair, bw.start, ws.thits, conics, num_gaussians, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_th);
+  TN_CHECK_LAUNCH(who);
+  return TN_OK;
 }
 
 extern "C" int tn_splat_raster_backward(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
@@ -1070,39 +1273,46 @@ extern "C" int tn_splat_raster_backward(const TnSplatCamera* camera, int64_t num
                                         const float* conics, const float* v_rgbt, const float* v_alpha, void* bwd_workspace,
                                         int64_t bwd_workspace_bytes, float* v_xys, float* v_conics, float* v_colors, float* v_log_opacity,
                                         tn_stream_t stream) {
-  int rc = check_cam(camera, "tn_splat_raster_backward");
+  return splat_raster_backward("tn_splat_raster_backward", false, camera, num_gaussians, workspace, max_intersections, num_intersections, background4, transmittance,
+                               last, nullptr, nullptr, conics, v_rgbt, v_alpha, nullptr, bwd_workspace, bwd_workspace_bytes, v_xys, v_conics, v_colors,
+                               v_log_opacity, nullptr, stream);
+}
+
+extern "C" int tn_splat_raster_backward_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                            int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
+                                            const float* transmittance_thermal, const int32_t* last_thermal, const float* conics, const float* v_rgbt,
+                                            const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace, int64_t bwd_workspace_bytes, float* v_xys,
+                                            float* v_conics, float* v_colors, float* v_log_opacity, float* v_log_opacity_thermal, tn_stream_t stream) {
+  return splat_raster_backward("tn_splat_raster_backward_sep", true, camera, num_gaussians, workspace, max_intersections, num_intersections, background4,
+                               transmittance, last, transmittance_thermal, last_thermal, conics, v_rgbt, v_alpha, v_alpha_thermal, bwd_workspace,
+                               bwd_workspace_bytes, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, stream);
+}
+
+static int splat_project_backward(const char* who, bool sep, const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
+                                  const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
+                                  const float* thermal_rest, const float* opacities_th, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
+                                  int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics, const float* v_colors,
+                                  const float* v_log_opacity, const float* v_log_opacity_th, float* v_means, float* v_log_scales, float* v_quats,
+                                  float* v_opacities, float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest,
+                                  float* v_opacities_th, tn_stream_t stream) {
+  int rc = check_cam(camera, who);
   if (rc) return rc;
-  TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31), "tn_splat_raster_backward: bad Gaussian count");
-  TN_REQUIRE(max_intersections >= 0 && num_intersections >= 0 && num_intersections <= max_intersections,
-             "tn_splat_raster_backward: %lld intersections for a workspace of %lld", (long long)num_intersections, (long long)max_intersections);
   if (num_gaussians == 0) return TN_OK;
-  TN_REQUIRE(workspace && background4 && transmittance && last && conics && v_rgbt && v_alpha && bwd_workspace && v_xys && v_conics && v_colors &&
-                 v_log_opacity,
-             "tn_splat_raster_backward: null pointer");
-  const int64_t need = tn_splat_backward_workspace_bytes(num_gaussians, max_intersections);
-  TN_REQUIRE(bwd_workspace_bytes >= need, "tn_splat_raster_backward: backward workspace of %lld bytes, %lld needed", (long long)bwd_workspace_bytes,
-             (long long)need);
+  TN_REQUIRE(num_gaussians > 0 && num_gaussians < (1ll << 31), "%s: bad Gaussian count", who);
+  TN_REQUIRE(means && log_scales && quats && opacities && features_dc && thermal_dc && radii && v_xys && v_conics && v_colors && v_log_opacity &&
+                 v_means && v_log_scales && v_quats && v_opacities && v_features_dc && v_thermal_dc &&
+                 (!sep || (opacities_th && v_log_opacity_th && v_opacities_th)),
+             "%s: null pointer", who);
+  TN_REQUIRE(sh_degree >= -1 && sh_degree <= 3, "%s: sh_degree %d unsupported (-1 = sigmoid of the DC term, 0..3)", who, sh_degree);
+  TN_REQUIRE(num_rest_coeffs >= (sh_degree < 1 ? 0 : (sh_degree + 1) * (sh_degree + 1) - 1) && num_rest_coeffs <= 15,
+             "%s: %d higher-order coefficients for degree %d", who, num_rest_coeffs, sh_degree);
+  TN_REQUIRE(num_rest_coeffs == 0 || (features_rest && thermal_rest && v_features_rest && v_thermal_rest), "%s: null SH coefficients", who);
   SplatCamK k = make_camk(camera);
-  const int num_tiles = k.tbx * k.tby;
-  SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, num_tiles, nullptr);
-  SplatBwdWs bw = splat_bwd_layout(bwd_workspace, num_gaussians, max_intersections, nullptr);
-  hipStream_t st = tn_s(stream);
-  hipLaunchKernelGGL(k_splat_run_start, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, st, ws.order, ws.cum, ws.thits, num_gaussians, bw.start);
-  TN_CHECK_LAUNCH("tn_splat_raster_backward(runs)");
-  if (num_intersections > 0) {
-    // pairs behind every pixel's last contributor are not visited: their records stay zero
-    if (hipMemsetAsync(bw.pair, 0, sizeof(float) * SPLAT_PAIR_GRADS * (size_t)num_intersections, st) != hipSuccess) {
-      tn_set_error("tn_splat_raster_backward: memset failed");
-      return TN_ELAUNCH;
-    }
-    float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
-    hipLaunchKernelGGL(k_splat_raster_bwd, dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg,
-                       transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair);
-    TN_CHECK_LAUNCH("tn_splat_raster_backward");
-  }
-  hipLaunchKernelGGL(k_splat_pair_fold, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, st, bw.pair, bw.start, ws.thits, conics, num_gaussians,
-                     v_xys, v_conics, v_colors, v_log_opacity);
-  TN_CHECK_LAUNCH("tn_splat_raster_backward(fold)");
+  hipLaunchKernelGGL(sep ? k_splat_project_bwd<true> : k_splat_project_bwd<false>, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, tn_s(stream), k, means,
+                     log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii,
+                     v_xys, v_conics, v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
+                     v_thermal_rest, opacities_th, v_log_opacity_th, v_opacities_th);
+  TN_CHECK_LAUNCH(who);
   return TN_OK;
 }
 
@@ -1112,23 +1322,22 @@ extern "C" int tn_splat_project_backward(const TnSplatCamera* camera, const floa
                                          int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics, const float* v_colors,
                                          const float* v_log_opacity, float* v_means, float* v_log_scales, float* v_quats, float* v_opacities,
                                          float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest, tn_stream_t stream) {
-  int rc = check_cam(camera, "tn_splat_project_backward");
-  if (rc) return rc;
-  if (num_gaussians == 0) return TN_OK;
-  TN_REQUIRE(num_gaussians > 0 && num_gaussians < (1ll << 31), "tn_splat_project_backward: bad Gaussian count");
-  TN_REQUIRE(means && log_scales && quats && opacities && features_dc && thermal_dc && radii && v_xys && v_conics && v_colors && v_log_opacity &&
-                 v_means && v_log_scales && v_quats && v_opacities && v_features_dc && v_thermal_dc,
-             "tn_splat_project_backward: null pointer");
-  TN_REQUIRE(sh_degree >= -1 && sh_degree <= 3, "tn_splat_project_backward: sh_degree %d unsupported (-1 = sigmoid of the DC term, 0..3)", sh_degree);
-  TN_REQUIRE(num_rest_coeffs >= (sh_degree < 1 ? 0 : (sh_degree + 1) * (sh_degree + 1) - 1) && num_rest_coeffs <= 15,
-             "tn_splat_project_backward: %d higher-order coefficients for degree %d", num_rest_coeffs, sh_degree);
-  TN_REQUIRE(num_rest_coeffs == 0 || (features_rest && thermal_rest && v_features_rest && v_thermal_rest), "tn_splat_project_backward: null SH coefficients");
-  SplatCamK k = make_camk(camera);
-  hipLaunchKernelGGL(k_splat_project_bwd, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, tn_s(stream), k, means, log_scales, quats, opacities,
-                     features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii, v_xys, v_conics,
-                     v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc, v_thermal_rest);
-  TN_CHECK_LAUNCH("tn_splat_project_backward");
-  return TN_OK;
+  return splat_project_backward("tn_splat_project_backward", false, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
+                                nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics, v_colors, v_log_opacity, nullptr, v_means,
+                                v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc, v_thermal_rest, nullptr, stream);
+}
+
+extern "C" int tn_splat_project_backward_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
+                                             const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
+                                             const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs,
+                                             int32_t sh_degree, int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics,
+                                             const float* v_colors, const float* v_log_opacity, const float* v_log_opacity_thermal, float* v_means,
+                                             float* v_log_scales, float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest,
+                                             float* v_thermal_dc, float* v_thermal_rest, float* v_opacities_thermal, tn_stream_t stream) {
+  return splat_project_backward("tn_splat_project_backward_sep", true, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
+                                thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics, v_colors,
+                                v_log_opacity, v_log_opacity_thermal, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
+                                v_thermal_rest, v_opacities_thermal, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ refinement
@@ -1215,9 +1424,11 @@ __global__ void k_splat_grad_stats(const float2* __restrict__ xys_grad, const in
 
 __device__ static inline float refine_shrink(float s) { return logf(expf(s) * (1.0f / 1.6f)); }  // log(exp(s) / 1.6), splatfacto.py:555-556
 
+// SEP (separate thermal opacity): a Gaussian is transparent only when BOTH opacities are below the threshold -- one visible in either spectrum stays
+template <bool SEP>
 __global__ void k_refine_classify(const float* __restrict__ log_scales, const float* __restrict__ opacities, const float* __restrict__ grad_norm_sum,
                                   const float* __restrict__ vis_counts, const float* __restrict__ max_2d_size, int64_t N, RefineK k,
-                                  RefCnt* __restrict__ cnt) {
+                                  RefCnt* __restrict__ cnt, const float* __restrict__ opacities_th) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const float s0 = log_scales[3 * i], s1 = log_scales[3 * i + 1], s2 = log_scales[3 * i + 2];
@@ -1232,7 +1443,8 @@ __global__ void k_refine_classify(const float* __restrict__ log_scales, const fl
     if (split) emax_new = fmaxf(fmaxf(expf(refine_shrink(s0)), expf(refine_shrink(s1))), expf(refine_shrink(s2)));
     dup = emax_new <= k.size_thresh && high;  // on the updated scales: a split Gaussian can be duplicated too (splatfacto.py:413)
   }
-  const bool transparent = 1.0f / (1.0f + expf(-opacities[i])) < k.cull_alpha;
+  bool transparent = 1.0f / (1.0f + expf(-opacities[i])) < k.cull_alpha;
+  if (SEP) transparent = transparent && 1.0f / (1.0f + expf(-opacities_th[i])) < k.cull_alpha;
   const bool cull_orig = transparent || split || (k.cull_big && (emax > k.cull_scale || (k.screen && m2d > k.cull_screen)));
   const bool cull_new = transparent || (k.cull_big && (emax_new > k.cull_scale || (k.screen && 0.0f > k.cull_screen)));  // new rows: max_2d_size 0
   cnt[i] = RefCnt{split ? 1 : 0, cull_orig ? 0 : 1, split && !cull_new ? 1 : 0, dup && !cull_new ? 1 : 0};
@@ -1252,23 +1464,25 @@ __global__ void k_refine_map(const RefCnt* __restrict__ cnt, const RefCnt* __res
   if (c.dup) map[(int64_t)tot.orig + (int64_t)S * tot.child + (in.dup - 1)] = make_int2(src, c.split ? -3 : -2);
 }
 
+template <int NT>    // 8, or 9 with the separate thermal opacity (the ninth tensor, copied exactly as the opacities are)
 struct RefTensors {  // the eight parameter tensors (splat.py _PARAM_NAMES order) and their Adam moments; moments may be absent (null)
-  const float* src[8];
-  const float* src_m1[8];
-  const float* src_m2[8];
-  float* dst[8];
-  float* dst_m1[8];
-  float* dst_m2[8];
-  int32_t width[8];
-  int64_t block_begin[9];  // first block of each tensor
+  const float* src[NT];
+  const float* src_m1[NT];
+  const float* src_m2[NT];
+  float* dst[NT];
+  float* dst_m1[NT];
+  float* dst_m2[NT];
+  int32_t width[NT];
+  int64_t block_begin[NT + 1];  // first block of each tensor
 };
 
-__global__ void __launch_bounds__(256) k_refine_gather(RefTensors t, const int2* __restrict__ map, int64_t num_out, const float* __restrict__ noise,
+template <int NT>
+__global__ void __launch_bounds__(256) k_refine_gather(RefTensors<NT> t, const int2* __restrict__ map, int64_t num_out, const float* __restrict__ noise,
                                                        int64_t noise_rows, const float* __restrict__ means, const float* __restrict__ log_scales,
                                                        const float* __restrict__ quats, int64_t N) {
   int k = 0;
 #pragma unroll
-  for (int j = 1; j < 8; ++j) k += (int64_t)blockIdx.x >= t.block_begin[j] ? 1 : 0;  // block-uniform
+  for (int j = 1; j < NT; ++j) k += (int64_t)blockIdx.x >= t.block_begin[j] ? 1 : 0;  // block-uniform
   const int w = t.width[k];
   const float* __restrict__ src = t.src[k];
   const float* __restrict__ m1 = t.src_m1[k];
@@ -1352,37 +1566,99 @@ extern "C" int tn_splat_grad_stats(const float* xys_grad, const int32_t* radii, 
   return TN_OK;
 }
 
-extern "C" int tn_splat_refine_plan(const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities,
-                                    const float* grad_norm_sum, const float* vis_counts, const float* max_2d_size, int64_t num_gaussians,
+static int splat_refine_plan(const char* who, bool sep, const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities,
+                             const float* opacities_th, const float* grad_norm_sum, const float* vis_counts, const float* max_2d_size, int64_t num_gaussians,
                                     void* workspace, int64_t workspace_bytes, int64_t* counts_out, tn_stream_t stream) {
   RefineK k;
   int cull = 0;
-  int rc = refine_k(config, step, "tn_splat_refine_plan", &k, &cull);
+  int rc = refine_k(config, step, who, &k, &cull);
   if (rc) return rc;
-  TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31), "tn_splat_refine_plan: bad Gaussian count");
-  TN_REQUIRE(counts_out != nullptr, "tn_splat_refine_plan: null output");
+  TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31), "%s: bad Gaussian count", who);
+  TN_REQUIRE(counts_out != nullptr, "%s: null output", who);
   const int64_t N = num_gaussians;
   counts_out[0] = 0, counts_out[1] = N, counts_out[2] = 0, counts_out[3] = 0;
   if (N == 0 || !cull) return TN_OK;  // nothing to refine: every Gaussian stays where it is
-  TN_REQUIRE(log_scales && opacities && grad_norm_sum && vis_counts && max_2d_size && workspace, "tn_splat_refine_plan: null pointer");
+  TN_REQUIRE(log_scales && opacities && grad_norm_sum && vis_counts && max_2d_size && workspace && (!sep || opacities_th), "%s: null pointer", who);
   const int64_t need = tn_splat_refine_workspace_bytes(N, config->n_split_samples);
-  TN_REQUIRE(workspace_bytes >= need, "tn_splat_refine_plan: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
+  TN_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", who, (long long)workspace_bytes, (long long)need);
   RefineWs ws = refine_layout(workspace, N, config->n_split_samples, nullptr);
   hipStream_t st = tn_s(stream);
-  hipLaunchKernelGGL(k_refine_classify, dim3((unsigned)tn_cdiv(N, 256)), dim3(256), 0, st, log_scales, opacities, grad_norm_sum, vis_counts, max_2d_size, N,
-                     k, ws.cnt);
-  TN_CHECK_LAUNCH("tn_splat_refine_plan(classify)");
+  hipLaunchKernelGGL(sep ? k_refine_classify<true> : k_refine_classify<false>, dim3((unsigned)tn_cdiv(N, 256)), dim3(256), 0, st, log_scales, opacities, grad_norm_sum,
+                     vis_counts, max_2d_size, N, k, ws.cnt, opacities_th);
+  TN_CHECK_LAUNCH(who);
   size_t tb = ws.tmp_bytes;
   if (rocprim::inclusive_scan(ws.tmp, tb, (const RefCnt*)ws.cnt, ws.incl, (size_t)N, RefCntSum(), st) != hipSuccess) {
-    tn_set_error("tn_splat_refine_plan: scan failed");
+    tn_set_error("%s: scan failed", who);
     return TN_ELAUNCH;
   }
   RefCnt tot;
   if (hipMemcpyAsync(&tot, ws.incl + (N - 1), sizeof(RefCnt), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    tn_set_error("tn_splat_refine_plan: read-back of the counts failed");
+    tn_set_error("%s: read-back of the counts failed", who);
     return TN_ELAUNCH;
   }
   counts_out[0] = tot.split, counts_out[1] = tot.orig, counts_out[2] = (int64_t)tot.child * config->n_split_samples, counts_out[3] = tot.dup;
+  return TN_OK;
+}
+
+extern "C" int tn_splat_refine_plan(const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities,
+                                    const float* grad_norm_sum, const float* vis_counts, const float* max_2d_size, int64_t num_gaussians,
+                                    void* workspace, int64_t workspace_bytes, int64_t* counts_out, tn_stream_t stream) {
+  return splat_refine_plan("tn_splat_refine_plan", false, config, step, log_scales, opacities, nullptr, grad_norm_sum, vis_counts, max_2d_size, num_gaussians,
+                           workspace, workspace_bytes, counts_out, stream);
+}
+
+extern "C" int tn_splat_refine_plan_sep(const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities,
+                                        const float* opacities_thermal, const float* grad_norm_sum, const float* vis_counts, const float* max_2d_size,
+                                        int64_t num_gaussians, void* workspace, int64_t workspace_bytes, int64_t* counts_out, tn_stream_t stream) {
+  return splat_refine_plan("tn_splat_refine_plan_sep", true, config, step, log_scales, opacities, opacities_thermal, grad_norm_sum, vis_counts, max_2d_size,
+                           num_gaussians, workspace, workspace_bytes, counts_out, stream);
+}
+
+template <int NT>
+static int splat_refine_apply(const char* who, const TnSplatRefine* config, int64_t num_gaussians, int32_t num_rest_coeffs, const void* workspace,
+                                     int64_t workspace_bytes, const int64_t* counts, const float* noise, const float* const* params,
+                                     const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params, float* const* new_exp_avg,
+                                     float* const* new_exp_avg_sq, tn_stream_t stream) {
+  TN_REQUIRE(config != nullptr && counts != nullptr, "%s: null pointer", who);
+  const int32_t S = config->n_split_samples;
+  TN_REQUIRE(S >= 1 && S <= REFINE_MAX_SAMPLES, "%s: n_split_samples %d outside [1, %d]", who, S, REFINE_MAX_SAMPLES);
+  TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31), "%s: bad Gaussian count", who);
+  TN_REQUIRE(num_rest_coeffs >= 0 && num_rest_coeffs <= 15, "%s: %d higher-order coefficients", who, num_rest_coeffs);
+  const int64_t N = num_gaussians;
+  TN_REQUIRE(counts[0] >= 0 && counts[0] <= N && counts[1] >= 0 && counts[1] <= N && counts[2] >= 0 && counts[2] <= S * counts[0] &&
+                 counts[2] % S == 0 && counts[3] >= 0 && counts[3] <= N,
+             "%s: counts (%lld, %lld, %lld, %lld) are not a plan of %lld Gaussians", who, (long long)counts[0], (long long)counts[1],
+             (long long)counts[2], (long long)counts[3], (long long)N);
+  const int64_t num_out = counts[1] + counts[2] + counts[3];
+  if (num_out == 0) return TN_OK;  // everything culled (N == 0 included): nothing to write
+  TN_REQUIRE(params && exp_avg && exp_avg_sq && new_params && new_exp_avg && new_exp_avg_sq && workspace, "%s: null pointer", who);
+  TN_REQUIRE(counts[2] == 0 || noise != nullptr, "%s: null noise for %lld split children", who, (long long)counts[2]);
+  const int64_t need = tn_splat_refine_workspace_bytes(N, S);
+  TN_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", who, (long long)workspace_bytes, (long long)need);
+  const int32_t widths[9] = {3, 3, 4, 1, 3, 3 * num_rest_coeffs, 1, num_rest_coeffs, 1};
+  RefTensors<NT> t;
+  int64_t blocks = 0;
+  for (int j = 0; j < NT; ++j) {
+    const bool on = widths[j] > 0;
+    TN_REQUIRE(!on || (params[j] && new_params[j]), "%s: null parameter %d", who, j);
+    TN_REQUIRE((exp_avg[j] == nullptr) == (exp_avg_sq[j] == nullptr) && (exp_avg[j] == nullptr) == (new_exp_avg[j] == nullptr) &&
+                   (exp_avg[j] == nullptr) == (new_exp_avg_sq[j] == nullptr),
+               "%s: moments of parameter %d are partly null", who, j);
+    t.src[j] = params[j], t.src_m1[j] = on ? exp_avg[j] : nullptr, t.src_m2[j] = on ? exp_avg_sq[j] : nullptr;
+    t.dst[j] = new_params[j], t.dst_m1[j] = on ? new_exp_avg[j] : nullptr, t.dst_m2[j] = on ? new_exp_avg_sq[j] : nullptr;
+    t.width[j] = std::max(widths[j], 1);
+    t.block_begin[j] = blocks;
+    blocks += on ? tn_cdiv(num_out * widths[j], REFINE_GATHER_ELEMS) : 0;
+  }
+  t.block_begin[NT] = blocks;
+  TN_REQUIRE(blocks < (1ll << 31), "%s: %lld output rows are too many", who, (long long)num_out);
+  RefineWs ws = refine_layout(const_cast<void*>(workspace), N, S, nullptr);
+  hipStream_t st = tn_s(stream);
+  hipLaunchKernelGGL(k_refine_map, dim3((unsigned)tn_cdiv(N, 256)), dim3(256), 0, st, ws.cnt, ws.incl, N, S, ws.map);
+  TN_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(k_refine_gather<NT>, dim3((unsigned)blocks), dim3(256), 0, st, t, ws.map, num_out, noise, (int64_t)counts[0] * S, params[0], params[1],
+                     params[2], N);
+  TN_CHECK_LAUNCH(who);
   return TN_OK;
 }
 
@@ -1390,45 +1666,14 @@ extern "C" int tn_splat_refine_apply(const TnSplatRefine* config, int64_t num_ga
                                      int64_t workspace_bytes, const int64_t* counts, const float* noise, const float* const* params,
                                      const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params, float* const* new_exp_avg,
                                      float* const* new_exp_avg_sq, tn_stream_t stream) {
-  TN_REQUIRE(config != nullptr && counts != nullptr, "tn_splat_refine_apply: null pointer");
-  const int32_t S = config->n_split_samples;
-  TN_REQUIRE(S >= 1 && S <= REFINE_MAX_SAMPLES, "tn_splat_refine_apply: n_split_samples %d outside [1, %d]", S, REFINE_MAX_SAMPLES);
-  TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31), "tn_splat_refine_apply: bad Gaussian count");
-  TN_REQUIRE(num_rest_coeffs >= 0 && num_rest_coeffs <= 15, "tn_splat_refine_apply: %d higher-order coefficients", num_rest_coeffs);
-  const int64_t N = num_gaussians;
-  TN_REQUIRE(counts[0] >= 0 && counts[0] <= N && counts[1] >= 0 && counts[1] <= N && counts[2] >= 0 && counts[2] <= S * counts[0] &&
-                 counts[2] % S == 0 && counts[3] >= 0 && counts[3] <= N,
-             "tn_splat_refine_apply: counts (%lld, %lld, %lld, %lld) are not a plan of %lld Gaussians", (long long)counts[0], (long long)counts[1],
-             (long long)counts[2], (long long)counts[3], (long long)N);
-  const int64_t num_out = counts[1] + counts[2] + counts[3];
-  if (num_out == 0) return TN_OK;  // everything culled (N == 0 included): nothing to write
-  TN_REQUIRE(params && exp_avg && exp_avg_sq && new_params && new_exp_avg && new_exp_avg_sq && workspace, "tn_splat_refine_apply: null pointer");
-  TN_REQUIRE(counts[2] == 0 || noise != nullptr, "tn_splat_refine_apply: null noise for %lld split children", (long long)counts[2]);
-  const int64_t need = tn_splat_refine_workspace_bytes(N, S);
-  TN_REQUIRE(workspace_bytes >= need, "tn_splat_refine_apply: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
-  const int32_t widths[8] = {3, 3, 4, 1, 3, 3 * num_rest_coeffs, 1, num_rest_coeffs};
-  RefTensors t;
-  int64_t blocks = 0;
-  for (int j = 0; j < 8; ++j) {
-    const bool on = widths[j] > 0;
-    TN_REQUIRE(!on || (params[j] && new_params[j]), "tn_splat_refine_apply: null parameter %d", j);
-    TN_REQUIRE((exp_avg[j] == nullptr) == (exp_avg_sq[j] == nullptr) && (exp_avg[j] == nullptr) == (new_exp_avg[j] == nullptr) &&
-                   (exp_avg[j] == nullptr) == (new_exp_avg_sq[j] == nullptr),
-               "tn_splat_refine_apply: moments of parameter %d are partly null", j);
-    t.src[j] = params[j], t.src_m1[j] = on ? exp_avg[j] : nullptr, t.src_m2[j] = on ? exp_avg_sq[j] : nullptr;
-    t.dst[j] = new_params[j], t.dst_m1[j] = on ? new_exp_avg[j] : nullptr, t.dst_m2[j] = on ? new_exp_avg_sq[j] : nullptr;
-    t.width[j] = std::max(widths[j], 1);
-    t.block_begin[j] = blocks;
-    blocks += on ? tn_cdiv(num_out * widths[j], REFINE_GATHER_ELEMS) : 0;
-  }
-  t.block_begin[8] = blocks;
-  TN_REQUIRE(blocks < (1ll << 31), "tn_splat_refine_apply: %lld output rows are too many", (long long)num_out);
-  RefineWs ws = refine_layout(const_cast<void*>(workspace), N, S, nullptr);
-  hipStream_t st = tn_s(stream);
-  hipLaunchKernelGGL(k_refine_map, dim3((unsigned)tn_cdiv(N, 256)), dim3(256), 0, st, ws.cnt, ws.incl, N, S, ws.map);
-  TN_CHECK_LAUNCH("tn_splat_refine_apply(map)");
-  hipLaunchKernelGGL(k_refine_gather, dim3((unsigned)blocks), dim3(256), 0, st, t, ws.map, num_out, noise, (int64_t)counts[0] * S, params[0], params[1],
-                     params[2], N);
-  TN_CHECK_LAUNCH("tn_splat_refine_apply(gather)");
-  return TN_OK;
+  return splat_refine_apply<8>("tn_splat_refine_apply", config, num_gaussians, num_rest_coeffs, workspace, workspace_bytes, counts, noise, params, exp_avg,
+                               exp_avg_sq, new_params, new_exp_avg, new_exp_avg_sq, stream);
+}
+
+extern "C" int tn_splat_refine_apply_sep(const TnSplatRefine* config, int64_t num_gaussians, int32_t num_rest_coeffs, const void* workspace,
+                                         int64_t workspace_bytes, const int64_t* counts, const float* noise, const float* const* params,
+                                         const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params, float* const* new_exp_avg,
+                                         float* const* new_exp_avg_sq, tn_stream_t stream) {
+  return splat_refine_apply<9>("tn_splat_refine_apply_sep", config, num_gaussians, num_rest_coeffs, workspace, workspace_bytes, counts, noise, params, exp_avg,
+                               exp_avg_sq, new_params, new_exp_avg, new_exp_avg_sq, stream);
 }

@@ -239,6 +239,8 @@ class HipAdam(torch.optim.Adam):
 
 # splatfacto's optimisers (configs/method_configs.py:655-703) in the (lr, lr_final, max_steps) format Optimizers reads; the thermal SH groups
 # take the rates of their RGB counterparts.  The constant groups run a schedule from lr to lr (the same rate to within a double's last bit).
+# opacities_thermal: the group of thermal_opacity_mode "separate" (the opacity group's rate and schedule); in shared mode the model has no such
+# group and Optimizers, which walks the model's groups, never reads the entry.
 SPLAT_OPTIMIZERS = {
     "xyz": (1.6e-4, 1.6e-6, 30000),
     "features_dc": (0.0025, 0.0025, 30000),
@@ -248,6 +250,7 @@ SPLAT_OPTIMIZERS = {
     "rotation": (0.001, 0.001, 30000),
     "features_dc_thermal": (0.0025, 0.0025, 30000),
     "features_rest_thermal": (0.0025 / 20, 0.0025 / 20, 30000),
+    "opacities_thermal": (0.05, 0.05, 30000),
 }
 
 

@@ -3,7 +3,16 @@
 The reference has no thermal-splatfacto method; the boundary mirrored here is stock `SplatfactoModel.get_outputs(camera)`
 (nerfstudio/models/splatfacto.py:659-822) with the parameter names of its `gauss_params` (means, scales, quats, opacities, features_dc,
 features_rest) plus a second set of SH coefficients with one channel (features_dc_thermal / features_rest_thermal) rendered through the
-same rasteriser -- the splat analogue of thermal-nerfacto's shared density.  The three gsplat calls (project_gaussians,
+same rasteriser -- the splat analogue of thermal-nerfacto's shared density (`thermal_opacity_mode` "shared", the default).  With
+`thermal_opacity_mode` "separate" -- the analogue of ThermalNerfactoModelConfig.density_mode "separate", the reference's default -- every
+Gaussian also has `opacities_thermal` [N,1] (logits, started at logit(0.1) like `opacities`, its own optimiser group): RGB, accumulation and
+depth composite with sigmoid(opacities), the thermal channel with sigmoid(opacities_thermal) through a transmittance chain of its own over the
+same depth-sorted tile lists (its own 1e-4 stop, its background weighted by its own final transmittance; `accumulation_thermal` [H,W,1] is its
+accumulation), so glass can be clear in RGB and opaque in thermal.  That mode runs the _sep family of entry points (tn_splat_project_sep ...
+tn_splat_refine_apply_sep: the same kernels instantiated with the second chain); its backward is as exact and bit-reproducible, `last_xys_grad`
+sums both chains; refinement culls a Gaussian for low opacity only when BOTH opacities are below `cull_alpha_thresh`, and carries, copies and
+resets the thermal logits exactly as the opacities.  `opacity_loss_mult` > 0 adds the NeRF model's `density_loss`
+(models/thermal_nerfacto.py:328-344) on the two opacities.  The three gsplat calls (project_gaussians,
 spherical_harmonics, rasterize_gaussians x2) run as tn_splat_project / tn_splat_bin / tn_splat_raster of libthermal_nerf_hip.so.
 `get_outputs` is the eval render.  `get_train_outputs` is the same render as a differentiable function of every `gauss_params` tensor: its
 backward (tn_splat_raster_backward / tn_splat_project_backward) is the exact, bit-reproducible derivative of the forward this file computes,
@@ -66,6 +75,12 @@ class ThermalSplatfactoModelConfig:
     # ThermalNeRF's regularisers of the thermal render on RGB frames (ThermalNerfactoModelConfig's names; the NeRF path runs both at 1e-6); 0 = off
     tv_pixel_loss_mult: float = 0.0
     cross_channel_loss_mult: float = 0.0
+    # "shared": one opacity blends RGB and thermal; "separate": the thermal channel has opacities_thermal and a transmittance chain of its own
+    # (ThermalNerfactoModelConfig.density_mode's two values).  density_loss (thermal_nerfacto.py:328-344, separate mode, 0 = off) =
+    # opacity_loss_mult * (mean|o_th - o.detach()| + rgb_opacity_loss_mult * mean|o - o_th.detach()|) on the sigmoids
+    thermal_opacity_mode: str = "shared"
+    opacity_loss_mult: float = 0.0
+    rgb_opacity_loss_mult: float = 0.01
     # initialisation (splatfacto.py:127-131): random_init ignores the model's seed_points
     random_init: bool = False
     num_random: int = 50000
@@ -89,9 +104,11 @@ class ThermalSplatfactoModelConfig:
     num_downscales: int = 0
 
     def __post_init__(self):
-        for name in ("tv_pixel_loss_mult", "cross_channel_loss_mult"):
+        for name in ("tv_pixel_loss_mult", "cross_channel_loss_mult", "opacity_loss_mult", "rgb_opacity_loss_mult"):
             if getattr(self, name) < 0:
                 raise ValueError(f"{name} = {getattr(self, name)}: a loss multiplier cannot be negative")
+        if self.thermal_opacity_mode not in ("shared", "separate"):
+            raise ValueError(f'thermal_opacity_mode = {self.thermal_opacity_mode!r}: "shared" or "separate"')
 
 
 @dataclass
@@ -505,6 +522,15 @@ def thermal_regularizers(pred_thermal: Tensor, gt_rgb: Tensor, tv_mult: float, c
     return out[0], out[1]
 
 
+def opacity_density_loss(opacities: Tensor, opacities_thermal: Tensor, opacity_loss_mult: float, rgb_opacity_loss_mult: float) -> Tensor:
+    """ThermalNeRF's density_loss (models/thermal_nerfacto.py:328-344) on the two opacity logits [N,1] of the separate mode:
+    opacity_loss_mult * (mean|s(o_th) - s(o).detach()| + rgb_opacity_loss_mult * mean|s(o) - s(o_th).detach()|), s = sigmoid.  The first term pulls
+    the thermal opacity towards the RGB one, the second (weaker) the RGB one towards the thermal: each term's gradient reaches only its own tensor.
+    Elementwise on [N,1], plain torch."""
+    o, o_th = torch.sigmoid(opacities), torch.sigmoid(opacities_thermal)
+    return opacity_loss_mult * ((o_th - o.detach()).abs().mean() + rgb_opacity_loss_mult * (o - o_th.detach()).abs().mean())
+
+
 def ssim(pred: Tensor, gt: Tensor) -> Tensor:
     """pytorch_msssim's SSIM(data_range=1) of two [H,W,C] images (mean over channels), a device scalar; no gradient."""
     return image_loss(pred.detach(), gt, 1.0, 1.0)[2]
@@ -524,14 +550,24 @@ _PARAM_NAMES = ("means", "scales", "quats", "opacities", "features_dc", "feature
 # optimiser group -> gauss_params entry (splatfacto.py:620-628, plus the thermal SH coefficients)
 GROUP_PARAMS = {"xyz": "means", "features_dc": "features_dc", "features_rest": "features_rest", "opacity": "opacities", "scaling": "scales",
                 "rotation": "quats", "features_dc_thermal": "features_dc_thermal", "features_rest_thermal": "features_rest_thermal"}
+# thermal_opacity_mode "separate": the thermal opacity logits come ninth, in a group of their own
+_PARAM_NAMES_SEP = _PARAM_NAMES + ("opacities_thermal",)
+GROUP_PARAMS_SEP = {**GROUP_PARAMS, "opacities_thermal": "opacities_thermal"}
+
+
+def param_names(mode: str) -> Tuple[str, ...]:
+    """The gauss_params entries of a thermal_opacity_mode, in the order the C entry points take them."""
+    return _PARAM_NAMES_SEP if mode == "separate" else _PARAM_NAMES
 
 
 def _param_ptrs(tensors) -> list:
     """Pointers of eight tensors laid out as the gauss_params, in _PARAM_NAMES order, as the C entry points take them: without higher-order SH
-    coefficients (K == 0) the two features_rest tensors are null, and opacities [N,1] goes in flat."""
+    coefficients (K == 0) the two features_rest tensors are null, and opacities [N,1] goes in flat.  Nine tensors (separate thermal opacity):
+    opacities_thermal [N,1] follows, flat too, where the _sep entry points take it."""
     K = tensors[5].shape[1]
-    pp = [_ptr(t, torch.float32, n) if (K or not n.startswith("features_rest")) else None for t, n in zip(tensors, _PARAM_NAMES)]
-    pp[3] = _ptr(tensors[3].reshape(-1), torch.float32, "opacities")
+    pp = [_ptr(t, torch.float32, n) if (K or not n.startswith("features_rest")) else None for t, n in zip(tensors, _PARAM_NAMES_SEP)]
+    for j in (3, 8)[:len(tensors) - 7]:
+        pp[j] = _ptr(tensors[j].reshape(-1), torch.float32, _PARAM_NAMES_SEP[j])
     return pp
 
 
@@ -551,7 +587,10 @@ def _project_and_bin(model, cam, params, H: int, W: int, deg: int, aa: int, cap:
         out_ptrs = [_ptr(t, t.dtype, k) for k, t in proj.items()]
         ws = workspace(N, cap, tiles)
         wsp = C.c_void_p(ws.data_ptr())
-        _lib.check(lib.tn_splat_project(C.byref(cam), *_param_ptrs(params), N, K, deg, aa, *out_ptrs, wsp, cap, _stream()), "tn_splat_project")
+        if len(params) == 9:  # separate thermal opacity
+            _lib.check(lib.tn_splat_project_sep(C.byref(cam), *_param_ptrs(params), N, K, deg, aa, *out_ptrs, wsp, cap, _stream()), "tn_splat_project_sep")
+        else:
+            _lib.check(lib.tn_splat_project(C.byref(cam), *_param_ptrs(params), N, K, deg, aa, *out_ptrs, wsp, cap, _stream()), "tn_splat_project")
         rc = lib.tn_splat_bin(C.byref(cam), out_ptrs[1], N, wsp, cap, C.byref(total), _stream())
         if rc == 0:
             break
@@ -564,22 +603,26 @@ def _project_and_bin(model, cam, params, H: int, W: int, deg: int, aa: int, cap:
     return proj, ws, cap, int(total.value)
 
 
-def _outputs(rgb: Tensor, thermal: Tensor, depth: Tensor, accumulation: Tensor, bgl: List[float]) -> Dict[str, Tensor]:
+def _outputs(rgb: Tensor, thermal: Tensor, depth: Tensor, accumulation: Tensor, bgl: List[float], accumulation_thermal: Optional[Tensor] = None) -> Dict[str, Tensor]:
     dev = rgb.device
-    return {"rgb": rgb, "thermal": thermal, "depth": depth, "accumulation": accumulation, "background": torch.tensor(bgl[:3]).to(dev),
-            "background_thermal": torch.tensor(bgl[3:], device=dev)}
+    out = {"rgb": rgb, "thermal": thermal, "depth": depth, "accumulation": accumulation, "background": torch.tensor(bgl[:3]).to(dev),
+           "background_thermal": torch.tensor(bgl[3:], device=dev)}
+    if accumulation_thermal is not None:  # separate thermal opacity: the thermal chain's accumulation
+        out["accumulation_thermal"] = accumulation_thermal
+    return out
 
 
-def _background_outputs(H: int, W: int, bgl: List[float], dev) -> Dict[str, Tensor]:
+def _background_outputs(H: int, W: int, bgl: List[float], dev, sep: bool = False) -> Dict[str, Tensor]:
     """Nothing to render (splatfacto.py:759-764): the background, depth 10, no accumulation."""
     return _outputs(torch.tensor(bgl[:3]).to(dev).repeat(H, W, 1), torch.full((H, W, 1), bgl[3], device=dev), torch.full((H, W, 1), 10.0, device=dev),
-                    torch.zeros((H, W, 1), device=dev), bgl)
+                    torch.zeros((H, W, 1), device=dev), bgl, torch.zeros((H, W, 1), device=dev) if sep else None)
 
 
 class _SplatRender(torch.autograd.Function):
     """project -> bin -> training raster; backward = raster backward -> projection backward.  Inputs after `frame` are the gauss_params in
     _PARAM_NAMES order; outputs: colour before the clamp [H,W,4] (RGB + thermal over the background), accumulation [H,W,1], depth [H,W,1]
-    (not differentiable)."""
+    (not differentiable).  Nine parameters (separate thermal opacity, opacities_thermal last): the _sep entry points, and a fourth output,
+    the thermal chain's accumulation [H,W,1]."""
 
     @staticmethod
     def forward(ctx, frame, *params):
@@ -587,6 +630,7 @@ class _SplatRender(torch.autograd.Function):
         f32, i32 = torch.float32, torch.int32
         cam, N, H, W = frame["cam"], params[0].shape[0], int(camera.height), int(camera.width)
         aa, bg4, dev = frame["aa"], frame["bg4"], params[0].device
+        sep = len(params) == 9
         # a workspace of this frame's own: the backward reads it after other frames may have been rendered
         proj, ws, cap, total = _project_and_bin(model, cam, params, H, W, frame["deg"], aa, max(model._train_cap, 1 << 16), model._new_workspace)
         model._train_cap = cap
@@ -599,12 +643,24 @@ class _SplatRender(torch.autograd.Function):
             depth = torch.full((H, W, 1), 10.0, device=dev)
             ctx.mark_non_differentiable(depth)
             ctx.save_for_backward(*params)
-            return rgbt, alpha, depth
+            return (rgbt, alpha, depth, torch.zeros((H, W, 1), device=dev)) if sep else (rgbt, alpha, depth)
         rgbt = torch.empty((H, W, 4), device=dev)
         depth = torch.empty((H, W, 1), device=dev)
         alpha = torch.empty((H, W, 1), device=dev)
         final_t = torch.empty((H, W), device=dev)
         last = torch.empty((H, W), dtype=i32, device=dev)
+        if sep:
+            alpha_th = torch.empty((H, W, 1), device=dev)
+            final_t_th = torch.empty((H, W), device=dev)
+            last_th = torch.empty((H, W), dtype=i32, device=dev)
+            _lib.check(_lib.load().tn_splat_raster_train_sep(C.byref(cam), N, C.c_void_p(ws.data_ptr()), cap, bg4, aa, _ptr(rgbt, f32, "rgbt"), _ptr(depth, f32, "depth"),
+                                                             _ptr(alpha, f32, "alpha"), _ptr(alpha_th, f32, "alpha_thermal"), _ptr(final_t, f32, "transmittance"),
+                                                             _ptr(last, i32, "last"), _ptr(final_t_th, f32, "transmittance_thermal"),
+                                                             _ptr(last_th, i32, "last_thermal"), _stream()), "tn_splat_raster_train_sep")
+            ctx.mark_non_differentiable(depth)
+            ctx.ws, ctx.cap, ctx.total = ws, cap, total
+            ctx.save_for_backward(*params, proj["radii"], proj["conics"], final_t, last, final_t_th, last_th)
+            return rgbt, alpha, depth, alpha_th
         _lib.check(_lib.load().tn_splat_raster_train(C.byref(cam), N, C.c_void_p(ws.data_ptr()), cap, bg4, aa, _ptr(rgbt, f32, "rgbt"), _ptr(depth, f32, "depth"),
                                                      _ptr(alpha, f32, "alpha"), _ptr(final_t, f32, "transmittance"), _ptr(last, i32, "last"), _stream()),
                    "tn_splat_raster_train")
@@ -614,29 +670,49 @@ class _SplatRender(torch.autograd.Function):
         return rgbt, alpha, depth
 
     @staticmethod
-    def backward(ctx, v_rgbt, v_alpha, _v_depth):
+    def backward(ctx, v_rgbt, v_alpha, _v_depth, v_alpha_th=None):
         frame = ctx.frame
         model = frame["model"]
         saved = ctx.saved_tensors
-        params = saved[:8]
+        P = frame["num_params"]
+        sep = P == 9
+        params = saved[:P]
         means = params[0]
         N, dev = means.shape[0], means.device
         if ctx.empty:
             model.last_xys_grad = torch.zeros((N, 2), device=dev)
             return (None,) + tuple(torch.zeros_like(p) for p in params)
-        radii, conics, final_t, last = saved[8:]
+        radii, conics, final_t, last = saved[P:P + 4]
         lib = _lib.load()
         f32 = torch.float32
         cam, deg, aa, bg4 = frame["cam"], frame["deg"], frame["aa"], frame["bg4"]
         H, W = final_t.shape
         v_rgbt = torch.zeros((H, W, 4), device=dev) if v_rgbt is None else v_rgbt.float().contiguous()
         v_alpha = torch.zeros((H, W, 1), device=dev) if v_alpha is None else v_alpha.float().contiguous()
-        need = int(lib.tn_splat_backward_workspace_bytes(N, ctx.cap))
+        need = int((lib.tn_splat_backward_workspace_bytes_sep if sep else lib.tn_splat_backward_workspace_bytes)(N, ctx.cap))
         bws = torch.empty(need, dtype=torch.uint8, device=dev)
         v_xys = torch.empty((N, 2), device=dev)
         v_conics = torch.empty((N, 3), device=dev)
         v_colors = torch.empty((N, 4), device=dev)
         v_lnop = torch.empty((N,), device=dev)
+        if sep:
+            final_t_th, last_th = saved[P + 4:]
+            v_alpha_th = torch.zeros((H, W, 1), device=dev) if v_alpha_th is None else v_alpha_th.float().contiguous()
+            v_lnop_th = torch.empty((N,), device=dev)
+            _lib.check(lib.tn_splat_raster_backward_sep(C.byref(cam), N, C.c_void_p(ctx.ws.data_ptr()), ctx.cap, ctx.total, bg4, _ptr(final_t, f32, "transmittance"),
+                                                        _ptr(last, torch.int32, "last"), _ptr(final_t_th, f32, "transmittance_thermal"),
+                                                        _ptr(last_th, torch.int32, "last_thermal"), _ptr(conics, f32, "conics"), _ptr(v_rgbt, f32, "v_rgbt"),
+                                                        _ptr(v_alpha, f32, "v_alpha"), _ptr(v_alpha_th, f32, "v_alpha_thermal"), C.c_void_p(bws.data_ptr()), need,
+                                                        _ptr(v_xys, f32, "v_xys"), _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"),
+                                                        _ptr(v_lnop, f32, "v_log_opacity"), _ptr(v_lnop_th, f32, "v_log_opacity_thermal"), _stream()),
+                       "tn_splat_raster_backward_sep")
+            grads = [torch.empty_like(p) for p in params]
+            _lib.check(lib.tn_splat_project_backward_sep(C.byref(cam), *_param_ptrs(params), N, params[5].shape[1], deg, aa, _ptr(radii, torch.int32, "radii"),
+                                                         _ptr(v_xys, f32, "v_xys"), _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"),
+                                                         _ptr(v_lnop, f32, "v_log_opacity"), _ptr(v_lnop_th, f32, "v_log_opacity_thermal"), *_param_ptrs(grads),
+                                                         _stream()), "tn_splat_project_backward_sep")
+            model.last_xys_grad = v_xys
+            return (None,) + tuple(grads)
         _lib.check(lib.tn_splat_raster_backward(C.byref(cam), N, C.c_void_p(ctx.ws.data_ptr()), ctx.cap, ctx.total, bg4, _ptr(final_t, f32, "transmittance"),
                                                 _ptr(last, torch.int32, "last"), _ptr(conics, f32, "conics"), _ptr(v_rgbt, f32, "v_rgbt"),
                                                 _ptr(v_alpha, f32, "v_alpha"), C.c_void_p(bws.data_ptr()), need, _ptr(v_xys, f32, "v_xys"),
@@ -692,6 +768,8 @@ class ThermalSplatfactoModel(nn.Module):
                 "features_dc_thermal": nn.Parameter(torch.rand((n, 1), generator=g).to(dev)),
                 "features_rest_thermal": nn.Parameter(torch.zeros((n, dim_sh - 1, 1), device=dev)),
             })
+        if self.separate:  # the thermal opacity logits start exactly as the opacities do
+            self.gauss_params["opacities_thermal"] = nn.Parameter(torch.logit(0.1 * torch.ones(self.gauss_params["means"].shape[0], 1)).to(dev))
         self.step = 0
         self._ws: Optional[Tensor] = None
         self._cap = 0
@@ -743,6 +821,19 @@ class ThermalSplatfactoModel(nn.Module):
             "features_rest_thermal": nn.Parameter(torch.zeros((n, dim_sh - 1, 1), device=dev)),
         })
 
+    @property
+    def separate(self) -> bool:
+        """thermal_opacity_mode == "separate": gauss_params holds opacities_thermal and the _sep entry points run."""
+        return self.config.thermal_opacity_mode == "separate"
+
+    @property
+    def param_names(self) -> Tuple[str, ...]:
+        return param_names(self.config.thermal_opacity_mode)
+
+    @property
+    def group_params(self) -> Dict[str, str]:
+        return GROUP_PARAMS_SEP if self.separate else GROUP_PARAMS
+
     # the reference's accessors
     @property
     def num_points(self) -> int:
@@ -753,7 +844,13 @@ class ThermalSplatfactoModel(nn.Module):
         return self.gauss_params["means"]
 
     def load_gaussians(self, params: Dict[str, Tensor]) -> None:
+        """Replace the Gaussians by `params`.  In separate mode a dict without opacities_thermal starts the thermal logits as a copy of the
+        opacities; shared mode has no such entry and refuses it."""
         dev = self.means.device
+        if self.separate and "opacities_thermal" not in params:
+            params = {**params, "opacities_thermal": params["opacities"].clone()}
+        if not self.separate and "opacities_thermal" in params:
+            raise ValueError('load_gaussians: opacities_thermal belongs to thermal_opacity_mode "separate"')
         self.gauss_params = nn.ParameterDict({k: nn.Parameter(v.detach().float().contiguous().to(dev)) for k, v in params.items()})
 
     def _background4(self, training: bool) -> List[float]:
@@ -795,22 +892,29 @@ class ThermalSplatfactoModel(nn.Module):
     @torch.no_grad()
     def get_outputs(self, camera: PinholeCamera) -> Dict[str, Tensor]:
         """splatfacto.py:659-822 (eval mode, no crop box): project -> SH colours -> tile binning -> raster (colour + depth in one pass).
-        Returns rgb [H,W,3], thermal [H,W,1], depth [H,W,1], accumulation [H,W,1], background [3], background_thermal [1]."""
+        Returns rgb [H,W,3], thermal [H,W,1], depth [H,W,1], accumulation [H,W,1], background [3], background_thermal [1]; in separate mode also
+        accumulation_thermal [H,W,1], the thermal chain's accumulation (accumulation is the RGB chain's)."""
         dev = self.means.device
         N, H, W = self.num_points, int(camera.height), int(camera.width)
         aa, deg = self._frame_settings()
         bgl = self._background4(training=False)
         if N == 0:  # every Gaussian culled: the background (splatfacto.py:759-764); last_projection stays what it was
-            return _background_outputs(H, W, bgl, dev)
+            return _background_outputs(H, W, bgl, dev, self.separate)
         cam = camera_struct(camera)
-        params = [self.gauss_params[k] for k in _PARAM_NAMES]
+        params = [self.gauss_params[k] for k in self.param_names]
         _, ws, cap, total = _project_and_bin(self, cam, params, H, W, deg, aa, max(self._cap, 1 << 16), self._workspace)
         if total == 0:  # nothing on screen
-            return _background_outputs(H, W, bgl, dev)
+            return _background_outputs(H, W, bgl, dev, self.separate)
         f32 = torch.float32
         rgbt = torch.empty((H, W, 4), device=dev)
         depth = torch.empty((H, W, 1), device=dev)
         alpha = torch.empty((H, W, 1), device=dev)
+        if self.separate:
+            alpha_th = torch.empty((H, W, 1), device=dev)
+            _lib.check(_lib.load().tn_splat_raster_sep(C.byref(cam), N, C.c_void_p(ws.data_ptr()), cap, (C.c_float * 4)(*bgl), aa, _ptr(rgbt, f32, "rgbt"),
+                                                       _ptr(depth, f32, "depth"), _ptr(alpha, f32, "alpha"), _ptr(alpha_th, f32, "alpha_thermal"), _stream()),
+                       "tn_splat_raster_sep")
+            return _outputs(rgbt[..., :3], rgbt[..., 3:], depth, alpha, bgl, alpha_th)
         _lib.check(_lib.load().tn_splat_raster(C.byref(cam), N, C.c_void_p(ws.data_ptr()), cap, (C.c_float * 4)(*bgl), aa, _ptr(rgbt, f32, "rgbt"),
                                                _ptr(depth, f32, "depth"), _ptr(alpha, f32, "alpha"), _stream()), "tn_splat_raster")
         return _outputs(rgbt[..., :3], rgbt[..., 3:], depth, alpha, bgl)
@@ -831,12 +935,14 @@ class ThermalSplatfactoModel(nn.Module):
             camera = rescaled_camera(camera, d)
         aa, deg = self._frame_settings()
         bgl = self._background4(training=True)
-        frame = {"model": self, "camera": camera, "cam": camera_struct(camera), "aa": aa, "deg": deg, "bg4": (C.c_float * 4)(*bgl)}
+        names = self.param_names
+        frame = {"model": self, "camera": camera, "cam": camera_struct(camera), "aa": aa, "deg": deg, "bg4": (C.c_float * 4)(*bgl), "num_params": len(names)}
         self.last_xys_grad = None
-        rgbt, alpha, depth = _SplatRender.apply(frame, *(self.gauss_params[k] for k in _PARAM_NAMES))
+        rgbt, alpha, depth, *alpha_th = _SplatRender.apply(frame, *(self.gauss_params[k] for k in names))
+        alpha_th = alpha_th[0] if alpha_th else None  # separate mode: the thermal chain's accumulation (differentiable)
         if self.last_num_intersections == 0:  # the background as get_outputs returns it (no clamp)
-            return _outputs(rgbt[..., :3], rgbt[..., 3:], depth, alpha, bgl)
-        return _outputs(torch.clamp(rgbt[..., :3], max=1.0), torch.clamp(rgbt[..., 3:], max=1.0), depth, alpha, bgl)
+            return _outputs(rgbt[..., :3], rgbt[..., 3:], depth, alpha, bgl, alpha_th)
+        return _outputs(torch.clamp(rgbt[..., :3], max=1.0), torch.clamp(rgbt[..., 3:], max=1.0), depth, alpha, bgl, alpha_th)
 
     # ------------------------------------------------------------------------------------------------ loss and metrics (splatfacto.py:824-934)
     def get_gt_img(self, image: Tensor) -> Tensor:
@@ -883,7 +989,8 @@ class ThermalSplatfactoModel(nn.Module):
         tv_pixel_loss_mult / cross_channel_loss_mult above 0 also tv_pixel_loss / cross_channel_loss (the NeRF model's keys,
         models/thermal_nerfacto.py:346-354): on an RGB frame ThermalNeRF's regularisers of outputs["thermal"] against the main loss's ground truth
         (one tn_thermal_reg call), on a thermal frame 0 -- the reference keeps both to the RGB rays, and the keys depend on the config alone.
-        `batch`: image [H,W,3|4], is_thermal."""
+        In separate mode with opacity_loss_mult > 0 also density_loss = opacity_loss_mult * (mean|s(o_th) - s(o).detach()| + rgb_opacity_loss_mult *
+        mean|s(o) - s(o_th).detach()|), s = sigmoid (plain torch on [N,1]).  `batch`: image [H,W,3|4], is_thermal."""
         if "mask" in batch:
             raise NotImplementedError("masks are not supported by the splat loss (DESIGN.md section 7)")
         cfg = self.config
@@ -907,6 +1014,9 @@ class ThermalSplatfactoModel(nn.Module):
                 losses["tv_pixel_loss"] = tv
             if cross_mult > 0:
                 losses["cross_channel_loss"] = cross
+        if self.separate and cfg.opacity_loss_mult > 0:
+            losses["density_loss"] = opacity_density_loss(self.gauss_params["opacities"], self.gauss_params["opacities_thermal"], cfg.opacity_loss_mult,
+                                                          cfg.rgb_opacity_loss_mult)
         return losses
 
     @torch.no_grad()
@@ -937,8 +1047,8 @@ class ThermalSplatfactoModel(nn.Module):
         self.step = step
 
     def get_gaussian_param_groups(self) -> Dict[str, List[nn.Parameter]]:
-        """splatfacto.py:620-628: the reference's six groups plus the thermal SH coefficients."""
-        return {g: [self.gauss_params[k]] for g, k in GROUP_PARAMS.items()}
+        """splatfacto.py:620-628: the reference's six groups plus the thermal SH coefficients (and, in separate mode, opacities_thermal)."""
+        return {g: [self.gauss_params[k]] for g, k in self.group_params.items()}
 
     def get_param_groups(self) -> Dict[str, List[nn.Parameter]]:
         return self.get_gaussian_param_groups()
@@ -960,7 +1070,7 @@ class ThermalSplatfactoModel(nn.Module):
         self.step = 30000
         n = state_dict["gauss_params.means"].shape[0]
         dev = self.means.device
-        self.gauss_params = nn.ParameterDict({k: nn.Parameter(torch.zeros((n,) + tuple(self.gauss_params[k].shape[1:]), device=dev)) for k in _PARAM_NAMES})
+        self.gauss_params = nn.ParameterDict({k: nn.Parameter(torch.zeros((n,) + tuple(self.gauss_params[k].shape[1:]), device=dev)) for k in self.param_names})
         self.xys_grad_norm = self.vis_counts = self.max_2Dsize = None
         return super().load_state_dict(state_dict, strict=strict, **kwargs)
 
@@ -1016,14 +1126,15 @@ class ThermalSplatfactoModel(nn.Module):
                 raise RuntimeError("refinement_after: densification needs after_train statistics")
             self._refine(optimizers, opts, densify)
         if self.step < cfg.stop_split_at and self.step % reset_interval == cfg.refine_every:
-            op = self.gauss_params["opacities"]
             reset_value = cfg.cull_alpha_thresh * 2.0
-            op.data = torch.clamp(op.data, max=torch.logit(torch.tensor(reset_value, device=op.device)).item())
-            o = opts.get("opacity")
-            if o is not None and o.state.get(op):
-                st = o.state[op]
-                st["exp_avg"] = torch.zeros_like(st["exp_avg"])
-                st["exp_avg_sq"] = torch.zeros_like(st["exp_avg_sq"])
+            for group, key in (("opacity", "opacities"), ("opacities_thermal", "opacities_thermal"))[:2 if self.separate else 1]:
+                op = self.gauss_params[key]
+                op.data = torch.clamp(op.data, max=torch.logit(torch.tensor(reset_value, device=op.device)).item())
+                o = opts.get(group)
+                if o is not None and o.state.get(op):
+                    st = o.state[op]
+                    st["exp_avg"] = torch.zeros_like(st["exp_avg"])
+                    st["exp_avg_sq"] = torch.zeros_like(st["exp_avg_sq"])
         self.xys_grad_norm = self.vis_counts = self.max_2Dsize = None
 
     def _refine(self, optimizers, opts, densify: bool) -> None:
@@ -1041,9 +1152,11 @@ class ThermalSplatfactoModel(nn.Module):
         if stats[0] is None:  # cull only, straight after a reset: no screen sizes recorded
             stats = [torch.ones(N, device=dev), torch.ones(N, device=dev), torch.zeros(N, device=dev)]
         counts = (C.c_int64 * 4)()
-        _lib.check(lib.tn_splat_refine_plan(C.byref(rs), int(self.step), _ptr(gp["scales"], f32, "scales"), _ptr(gp["opacities"].reshape(-1), f32, "opacities"),
-                                            _ptr(stats[0], f32, "grad_norm_sum"), _ptr(stats[1], f32, "vis_counts"), _ptr(stats[2], f32, "max_2d_size"), N,
-                                            C.c_void_p(ws.data_ptr()), need, counts, _stream()), "tn_splat_refine_plan")
+        names, sep = self.param_names, self.separate
+        op_ptrs = [_ptr(gp[k].reshape(-1), f32, k) for k in (("opacities", "opacities_thermal") if sep else ("opacities",))]
+        plan, plan_name = (lib.tn_splat_refine_plan_sep, "tn_splat_refine_plan_sep") if sep else (lib.tn_splat_refine_plan, "tn_splat_refine_plan")
+        _lib.check(plan(C.byref(rs), int(self.step), _ptr(gp["scales"], f32, "scales"), *op_ptrs, _ptr(stats[0], f32, "grad_norm_sum"),
+                        _ptr(stats[1], f32, "vis_counts"), _ptr(stats[2], f32, "max_2d_size"), N, C.c_void_p(ws.data_ptr()), need, counts, _stream()), plan_name)
         n_split, n_orig, n_child, n_dup = (int(c) for c in counts)
         # the reference's noise: randn((n_split_samples * n_split, 3)), sample-major (splatfacto.py:541)
         noise = torch.randn((S * n_split, 3), device=dev, generator=self.noise_generator) if densify else None
@@ -1051,25 +1164,26 @@ class ThermalSplatfactoModel(nn.Module):
         if n_orig == N and n_child == 0 and n_dup == 0:
             return  # nothing split, duplicated or culled: every tensor stays as it is
         M = n_orig + n_child + n_dup
-        old = {k: gp[k] for k in _PARAM_NAMES}
-        group_of = {v: g for g, v in GROUP_PARAMS.items()}
+        old = {k: gp[k] for k in names}
+        group_of = {v: g for g, v in self.group_params.items()}
         moments = {}
-        for k in _PARAM_NAMES:
+        for k in names:
             o = opts.get(group_of[k])
             st = o.state.get(old[k]) if o is not None else None
             if st and "exp_avg" in st:
                 moments[k] = (st["exp_avg"].contiguous(), st["exp_avg_sq"].contiguous())
-        new = {k: torch.empty((M,) + tuple(old[k].shape[1:]), device=dev) for k in _PARAM_NAMES}
+        new = {k: torch.empty((M,) + tuple(old[k].shape[1:]), device=dev) for k in names}
         new_m = {k: (torch.empty_like(new[k]), torch.empty_like(new[k])) for k in moments}
-        arr = lambda ts: (C.c_void_p * 8)(*[t.data_ptr() if t is not None and t.numel() else None for t in ts])  # noqa: E731
-        _lib.check(lib.tn_splat_refine_apply(C.byref(rs), N, K, C.c_void_p(ws.data_ptr()), need, counts,
+        arr = lambda ts: (C.c_void_p * len(names))(*[t.data_ptr() if t is not None and t.numel() else None for t in ts])  # noqa: E731
+        apply, apply_name = (lib.tn_splat_refine_apply_sep, "tn_splat_refine_apply_sep") if sep else (lib.tn_splat_refine_apply, "tn_splat_refine_apply")
+        _lib.check(apply(C.byref(rs), N, K, C.c_void_p(ws.data_ptr()), need, counts,
                                              _ptr(noise, f32, "noise") if noise is not None and noise.numel() else None,
-                                             arr([old[k].detach() for k in _PARAM_NAMES]), arr([moments[k][0] if k in moments else None for k in _PARAM_NAMES]),
-                                             arr([moments[k][1] if k in moments else None for k in _PARAM_NAMES]), arr([new[k] for k in _PARAM_NAMES]),
-                                             arr([new_m[k][0] if k in new_m else None for k in _PARAM_NAMES]),
-                                             arr([new_m[k][1] if k in new_m else None for k in _PARAM_NAMES]), _stream()), "tn_splat_refine_apply")
-        self.gauss_params = nn.ParameterDict({k: nn.Parameter(new[k]) for k in _PARAM_NAMES})
-        for k in _PARAM_NAMES:  # dup_in_optim / remove_from_optim (splatfacto.py:292-344)
+                                             arr([old[k].detach() for k in names]), arr([moments[k][0] if k in moments else None for k in names]),
+                                             arr([moments[k][1] if k in moments else None for k in names]), arr([new[k] for k in names]),
+                                             arr([new_m[k][0] if k in new_m else None for k in names]),
+                                             arr([new_m[k][1] if k in new_m else None for k in names]), _stream()), apply_name)
+        self.gauss_params = nn.ParameterDict({k: nn.Parameter(new[k]) for k in names})
+        for k in names:  # dup_in_optim / remove_from_optim (splatfacto.py:292-344)
             g = group_of[k]
             o = opts.get(g)
             if o is None:

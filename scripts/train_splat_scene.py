@@ -80,6 +80,9 @@ def main():
     ap.add_argument("--tv-pixel-loss-mult", type=float, default=0.0, help="weight of the thermal render's 2x2 total variation on RGB frames (0: off)")
     ap.add_argument("--cross-channel-loss-mult", type=float, default=0.0,
                     help="weight of the thermal render's pixel differences against the RGB ground truth's on RGB frames (0: off)")
+    ap.add_argument("--thermal-opacity-mode", default="shared", choices=("shared", "separate"),
+                    help='"separate": the thermal channel has an opacity per Gaussian of its own (opacities_thermal)')
+    ap.add_argument("--opacity-loss-mult", type=float, default=0.0, help="weight of density_loss between the two opacities (separate mode; 0: off)")
     ap.add_argument("--no-undistort", action="store_true", help="train on the raw frames with the parser's intrinsics (the distortion dropped)")
     args = ap.parse_args()
     if args.seed_points and args.data is not None:
@@ -102,7 +105,8 @@ def main():
     cfg = ThermalSplatfactoModelConfig(num_random=args.gaussians, random_scale=args.init_extent, ssim_lambda=args.ssim_lambda,
                                        background_color=args.background, num_downscales=args.num_downscales,
                                        resolution_schedule=args.resolution_schedule, tv_pixel_loss_mult=args.tv_pixel_loss_mult,
-                                       cross_channel_loss_mult=args.cross_channel_loss_mult)
+                                       cross_channel_loss_mult=args.cross_channel_loss_mult, thermal_opacity_mode=args.thermal_opacity_mode,
+                                       opacity_loss_mult=args.opacity_loss_mult)
     model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=dm.num_train_data, seed_points=seed_points)
     initial = model.num_points
     opts = Optimizers(model.get_param_groups(), SPLAT_OPTIMIZERS, optimizer_cls=HipAdam)
@@ -144,12 +148,18 @@ def main():
                 sums.setdefault(k, []).append(v)
     model.train()
     metrics = {k: sum(v) / len(v) for k, v in sums.items() if all(math.isfinite(x) for x in v)}
+    extra = {}
+    if model.separate:  # the share of Gaussians whose two opacities ended more than 0.5 apart
+        gp = model.gauss_params
+        gap = (torch.sigmoid(gp["opacities"]) - torch.sigmoid(gp["opacities_thermal"])).abs()
+        extra["opacity_gap_above_0.5_share"] = float((gap > 0.5).float().mean()) if gap.numel() else 0.0
     print(json.dumps({"dataset": "synthetic cube scene (train_eval_scene.write_cube_scene)" if tmp else data, "train_images": dm.num_train_data,
                       "val_images": len(val), "steps": args.steps, "ssim_lambda": args.ssim_lambda, "background_color": args.background,
                       "initial_gaussians": initial, "seed_points": args.seed_points, "final_gaussians": model.num_points, "train_seconds": train_s,
                       "ms_per_iteration": 1e3 * train_s / max(args.steps, 1), "num_downscales": args.num_downscales,
                       "resolution_schedule": args.resolution_schedule, "tv_pixel_loss_mult": args.tv_pixel_loss_mult,
-                      "cross_channel_loss_mult": args.cross_channel_loss_mult, "undistort": not args.no_undistort, "stages": stages, "val_metrics": metrics, "curve": curve}))
+                      "cross_channel_loss_mult": args.cross_channel_loss_mult, "undistort": not args.no_undistort, "thermal_opacity_mode": args.thermal_opacity_mode,
+                      "opacity_loss_mult": args.opacity_loss_mult, **extra, "stages": stages, "val_metrics": metrics, "curve": curve}))
 
 
 if __name__ == "__main__":
