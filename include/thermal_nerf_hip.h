@@ -763,6 +763,18 @@ TN_API int tn_splat_project_sep(const TnSplatCamera* camera, const float* means,
  * chain's accumulation) and out_alpha_thermal [H,W] (the thermal chain's).  Refuses null pointers and negative sizes. */
 TN_API int tn_splat_raster_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections, const float* background4,
                                int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, float* out_alpha_thermal, tn_stream_t stream);
+/* ThermalNeRF's removal renders (models/thermal_nerfacto.py:460-487, with opacities for densities): the frame composited only from the
+ * Gaussians on which the two spectra agree.  One more launch over the tile lists of a frame, after tn_splat_project_sep and tn_splat_bin on the
+ * same workspace (before or after tn_splat_raster_sep; it reads the workspace only).  With o = sigmoid(opacities), ot = sigmoid(opacities_thermal)
+ * and thr = min_opacity_diff: out_removal [H,W,4] holds in .xyz the RGB colour composited as tn_splat_raster_sep's RGB chain does, except that a
+ * Gaussian with |o - ot| < thr * o false has alpha 0, over background4.xyz with this chain's own final transmittance; in .w the thermal colour
+ * likewise with ot's chain, |ot - o| < thr * ot, and background4.w; both clamped to <= 1.  The comparisons are strict and use the plain
+ * opacities (in antialiased mode the chains blend with the compensated ones, as the workspace holds them): thr = 0 keeps nothing -- the
+ * background --, thr = inf everything -- tn_splat_raster_sep's out_rgbt bit for bit.  No float atomics: two calls give identical bits.
+ * num_gaussians == 0 is TN_OK: tn_splat_bin left every tile list empty, and every pixel receives background4 (clamped to <= 1).  Refuses a null
+ * pointer, a bad camera, a num_gaussians outside [0, 2^31), a negative max_intersections and a min_opacity_diff that is negative or NaN. */
+TN_API int tn_splat_raster_removal_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                       const float* background4, float min_opacity_diff, float* out_removal, tn_stream_t stream);
 /* tn_splat_raster_train likewise: out_transmittance / out_last are the RGB chain's, out_transmittance_thermal [H,W] / out_last_thermal [H,W] int32
  * the thermal chain's final T and last contributor.  Refuses null pointers and negative sizes. */
 TN_API int tn_splat_raster_train_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,

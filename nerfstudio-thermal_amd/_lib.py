@@ -201,6 +201,7 @@ SIGNATURES = {
     # separate thermal opacity: each entry point above plus the thermal-opacity arguments
     "tn_splat_project_sep": (C.c_int, [_p] * 10 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, _p]),
     "tn_splat_raster_sep": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _p, _p, _p, _p]),
+    "tn_splat_raster_removal_sep": (C.c_int, [_p, _i64, _p, _i64, _p, _f, _p, _p]),
     "tn_splat_raster_train_sep": (C.c_int, [_p, _i64, _p, _i64, _p, _i32] + [_p] * 8 + [_p]),
     "tn_splat_backward_workspace_bytes_sep": (_i64, [_i64, _i64]),
     "tn_splat_raster_backward_sep": (C.c_int, [_p, _i64, _p, _i64, _i64] + [_p] * 10 + [_i64] + [_p] * 6),

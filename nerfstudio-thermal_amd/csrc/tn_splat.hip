@@ -577,6 +577,112 @@ __global__ void k_splat_depth_finalize(float* __restrict__ depth, const float* _
   depth[i] = a > 0.f ? depth[i] / a : __uint_as_float(*depth_max);
 }
 
+// The removal renders of the separate thermal opacity (ThermalNeRF's, models/thermal_nerfacto.py:460-487, opacities for densities): the frame
+// composited only from the Gaussians on which the two spectra agree.  With o, ot the plain opacities: keep_rgb = |o - ot| < thr o,
+// keep_th = |ot - o| < thr ot (strict: thr = 0 keeps nothing).  Eval only, a sibling of k_splat_raster<*, false, true> over the same lists: the
+// same tile order, lane -> pixel map, batches, pipelined gather, quadrant ballot and whole-wave skip, and its two chains' rules -- but only the
+// two removal chains, no depth, no accumulation.  The thread that stages a record decides both keeps from exp2 of SplatRec::d.y / d.z and stores
+// the two log-opacities the chains blend with (b.y, d.w) as they are, or as -inf when masked: a masked Gaussian then fails the 1/255 gate like any
+// faint one, and the inner loop holds no test of its own for it.  A chain that keeps everything therefore does k_splat_raster's arithmetic in
+// k_splat_raster's order: its image is that kernel's, bit for bit.  AA needs no instantiation here: b.y and d.w already hold what each mode blends
+// with, and the compensation cancels in the comparison.  out: [H][W][4] = removal RGB over background.xyz, removal thermal over background.w.
+__global__ void __launch_bounds__(256) k_splat_raster_removal(const SplatRec* __restrict__ recs, const int32_t* __restrict__ sorted_ids,
+                                                              const int32_t* __restrict__ tile_bins, const int32_t* __restrict__ tile_order, int W, int H,
+                                                              int tbx, float4 background, float thr, float* __restrict__ out) {
+  __shared__ float4 sa[SPLAT_BATCH], sb[SPLAT_BATCH], sc[SPLAT_BATCH];
+  __shared__ float sl2t[SPLAT_BATCH];  // l2op the thermal chain blends with (sb[].y is the RGB chain's), -inf when masked
+  const int tile = tile_order[blockIdx.x];
+  const int tile_x = tile % tbx, tile_y = tile / tbx;
+  int lane, wv, ix, iy;
+  float pxf, pyf, qcx, qcy;
+  const bool inside = splat_lane_pixel(tile_x, tile_y, W, H, lane, wv, ix, iy, pxf, pyf, qcx, qcy);
+  const int begin = tile_bins[2 * tile], end = tile_bins[2 * tile + 1];
+  float T = 1.0f, Tt = 1.0f;
+  f32x2 acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};
+  bool done = !inside, done_t = !inside;
+  float4 ra, rb, rc, rd;
+  ra = rb = rc = rd = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (begin + (int)threadIdx.x < end) {
+    const SplatRec* r = recs + sorted_ids[begin + (int)threadIdx.x];
+    ra = r->a; rb = r->b; rc = r->c; rd = r->d;
+  }
+  for (int base = begin; base < end; base += SPLAT_BATCH) {
+    if (__syncthreads_count((done && done_t) ? 1 : 0) == 256) break;
+    {
+      const float o = __builtin_amdgcn_exp2f(rd.y), ot = __builtin_amdgcn_exp2f(rd.z);
+      const float diff = fabsf(o - ot);
+      const float ninf = -__builtin_inff();
+      sa[threadIdx.x] = ra;
+      sb[threadIdx.x] = make_float4(rb.x, diff < thr * o ? rb.y : ninf, rb.z, rb.w);
+      sc[threadIdx.x] = rc;
+      sl2t[threadIdx.x] = diff < thr * ot ? rd.w : ninf;
+    }
+    __syncthreads();
+    {
+      int nidx = base + SPLAT_BATCH + (int)threadIdx.x;
+      if (nidx < end) {
+        const SplatRec* r = recs + sorted_ids[nidx];
+        ra = r->a; rb = r->b; rc = r->c; rd = r->d;
+      }
+    }
+    const int n = min(SPLAT_BATCH, end - base);
+    if (__all((done && done_t) ? 1 : 0)) continue;
+#pragma unroll 1
+    for (int q = 0; q < SPLAT_BATCH / 64; ++q) {
+      if (q * 64 >= n) break;
+      const int kk = q * 64 + lane;
+      bool keep = false;
+      if (kk < n) {
+        float4 a = sa[kk], b = sb[kk];
+        // (a Gaussian masked in both chains leaves the walk here, before any lane evaluates it)
+        keep = splat_axis_hit(a.x, b.z, qcx) && splat_axis_hit(a.y, b.w, qcy) && fmaxf(b.y, sl2t[kk]) >= -8.0f;
+      }
+      uint64_t live = __ballot(keep);
+      while (live) {
+        const int k = q * 64 + __builtin_ctzll(live);
+        live &= live - 1;
+        float4 a = sa[k], b = sb[k];
+        const float l2t = sl2t[k];
+        float dx = a.x - pxf, dy = a.y - pyf;
+        float power = splat_power(a.z, a.w, b.x, dx, dy);
+        // nobody in the wave can reach alpha >= 1/255 in either chain: the larger of the two masked opacities bounds both
+        if (!__any((power >= 0.f && fmaxf(b.y, l2t) - power >= -8.0f) ? 1 : 0)) continue;
+        if (power < 0.f) continue;
+        const float alpha = splat_alpha(splat_alpha_raw(b.y, power));
+        const bool vis_c = splat_visible(alpha);
+        if (!done && vis_c) {
+          float nT = fmaf(-alpha, T, T);
+          if (nT <= 1e-4f) done = true;
+          else {
+            float vis = alpha * T;
+            float4 c = sc[k];
+            f32x2 v2 = {vis, vis};
+            acc01 = __builtin_elementwise_fma(v2, (f32x2){c.x, c.y}, acc01);
+            acc23.x = fmaf(vis, c.z, acc23.x);
+            T = nT;
+          }
+        }
+        const float alpha_t = splat_alpha(splat_alpha_raw(l2t, power));
+        const bool vis_t = splat_visible(alpha_t);
+        if (!done_t && vis_t) {
+          float nT = fmaf(-alpha_t, Tt, Tt);
+          if (nT <= 1e-4f) done_t = true;
+          else {
+            acc23.y = fmaf(alpha_t * Tt, sc[k].w, acc23.y);
+            Tt = nT;
+          }
+        }
+      }
+    }
+  }
+  if (inside) {
+    const float acc[4] = {acc01.x, acc01.y, acc23.x, acc23.y};
+    reinterpret_cast<float4*>(out)[(int64_t)iy * W + ix] =
+        make_float4(fminf(acc[0] + T * background.x, 1.0f), fminf(acc[1] + T * background.y, 1.0f), fminf(acc[2] + T * background.z, 1.0f),
+                    fminf(acc[3] + Tt * background.w, 1.0f));
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ backward
 // The exact derivative of the forward above (rgb, thermal, accumulation; depth is not differentiated).  Three steps, no float atomics, so
 // the gradients are bit-reproducible:
@@ -1196,6 +1302,23 @@ extern "C" int tn_splat_raster_sep(const TnSplatCamera* camera, int64_t num_gaus
   TN_REQUIRE(num_gaussians >= 0 && max_intersections >= 0, "tn_splat_raster_sep: bad sizes");
   return splat_raster("tn_splat_raster_sep", "tn_splat_raster_sep(depth)", camera, num_gaussians, workspace, max_intersections, background4, antialiased, out_rgbt,
                       out_depth, out_alpha, nullptr, nullptr, out_alpha_thermal, nullptr, nullptr, stream);
+}
+
+extern "C" int tn_splat_raster_removal_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                           const float* background4, float min_opacity_diff, float* out_removal, tn_stream_t stream) {
+  const char* who = "tn_splat_raster_removal_sep";
+  int rc = check_cam(camera, who);
+  if (rc) return rc;
+  TN_REQUIRE(workspace && background4 && out_removal, "%s: null pointer", who);
+  TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31) && max_intersections >= 0, "%s: bad sizes", who);
+  TN_REQUIRE(min_opacity_diff >= 0.f, "%s: min_opacity_diff %g must be a number >= 0", who, (double)min_opacity_diff);  // (false for NaN too)
+  SplatCamK k = make_camk(camera);
+  SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, k.tbx * k.tby, nullptr);
+  float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
+  hipLaunchKernelGGL(k_splat_raster_removal, dim3(k.tbx * k.tby), dim3(256), 0, tn_s(stream), ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx,
+                     bg, min_opacity_diff, out_removal);
+  TN_CHECK_LAUNCH(who);
+  return TN_OK;
 }
 
 extern "C" int tn_splat_raster_train(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,

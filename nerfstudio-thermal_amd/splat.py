@@ -12,7 +12,12 @@ accumulation), so glass can be clear in RGB and opaque in thermal.  That mode ru
 tn_splat_refine_apply_sep: the same kernels instantiated with the second chain); its backward is as exact and bit-reproducible, `last_xys_grad`
 sums both chains; refinement culls a Gaussian for low opacity only when BOTH opacities are below `cull_alpha_thresh`, and carries, copies and
 resets the thermal logits exactly as the opacities.  `opacity_loss_mult` > 0 adds the NeRF model's `density_loss`
-(models/thermal_nerfacto.py:328-344) on the two opacities.  The three gsplat calls (project_gaussians,
+(models/thermal_nerfacto.py:328-344) on the two opacities.  With `removal_min_opacity_diff` = thr set (separate mode only; None = off) the eval
+render also returns ThermalNeRF's removal renders (models/thermal_nerfacto.py:460-487, scripts/render.py:737-765, opacities for densities):
+`removal` [H,W,3], the RGB colour composited only from the Gaussians with |o - o_th| < thr * o, and `removal_thermal` [H,W,1], the thermal colour
+from those with |o_th - o| < thr * o_th (o, o_th the two sigmoids; strict, so thr = 0 is the background), each with a transmittance chain, stop
+and background weight of its own -- what sits behind glass or an IR-transparent cover -- from ONE more rasteriser launch
+(tn_splat_raster_removal_sep) over the tile lists the frame already has; training renders never carry them.  The three gsplat calls (project_gaussians,
 spherical_harmonics, rasterize_gaussians x2) run as tn_splat_project / tn_splat_bin / tn_splat_raster of libthermal_nerf_hip.so.
 `get_outputs` is the eval render.  `get_train_outputs` is the same render as a differentiable function of every `gauss_params` tensor: its
 backward (tn_splat_raster_backward / tn_splat_project_backward) is the exact, bit-reproducible derivative of the forward this file computes,
@@ -81,6 +86,9 @@ class ThermalSplatfactoModelConfig:
     thermal_opacity_mode: str = "shared"
     opacity_loss_mult: float = 0.0
     rgb_opacity_loss_mult: float = 0.01
+    # removal renders in eval (thermal_nerfacto.py:460-487; render.py's removal_min_density_diff): a Gaussian stays in `removal` while
+    # |o - o_th| < removal_min_opacity_diff * o, in `removal_thermal` while |o_th - o| < removal_min_opacity_diff * o_th.  None = off; separate mode only
+    removal_min_opacity_diff: Optional[float] = None
     # initialisation (splatfacto.py:127-131): random_init ignores the model's seed_points
     random_init: bool = False
     num_random: int = 50000
@@ -109,6 +117,11 @@ class ThermalSplatfactoModelConfig:
                 raise ValueError(f"{name} = {getattr(self, name)}: a loss multiplier cannot be negative")
         if self.thermal_opacity_mode not in ("shared", "separate"):
             raise ValueError(f'thermal_opacity_mode = {self.thermal_opacity_mode!r}: "shared" or "separate"')
+        if self.removal_min_opacity_diff is not None:
+            if self.thermal_opacity_mode != "separate":
+                raise ValueError('removal_min_opacity_diff needs thermal_opacity_mode "separate": the removal renders compare the two opacities')
+            if not self.removal_min_opacity_diff >= 0:
+                raise ValueError(f"removal_min_opacity_diff = {self.removal_min_opacity_diff}: a number >= 0, or None for no removal renders")
 
 
 @dataclass
@@ -612,10 +625,13 @@ def _outputs(rgb: Tensor, thermal: Tensor, depth: Tensor, accumulation: Tensor, 
     return out
 
 
-def _background_outputs(H: int, W: int, bgl: List[float], dev, sep: bool = False) -> Dict[str, Tensor]:
-    """Nothing to render (splatfacto.py:759-764): the background, depth 10, no accumulation."""
-    return _outputs(torch.tensor(bgl[:3]).to(dev).repeat(H, W, 1), torch.full((H, W, 1), bgl[3], device=dev), torch.full((H, W, 1), 10.0, device=dev),
-                    torch.zeros((H, W, 1), device=dev), bgl, torch.zeros((H, W, 1), device=dev) if sep else None)
+def _background_outputs(H: int, W: int, bgl: List[float], dev, sep: bool = False, removal: bool = False) -> Dict[str, Tensor]:
+    """Nothing to render (splatfacto.py:759-764): the background, depth 10, no accumulation; removal: the removal renders are the background too."""
+    out = _outputs(torch.tensor(bgl[:3]).to(dev).repeat(H, W, 1), torch.full((H, W, 1), bgl[3], device=dev), torch.full((H, W, 1), 10.0, device=dev),
+                   torch.zeros((H, W, 1), device=dev), bgl, torch.zeros((H, W, 1), device=dev) if sep else None)
+    if removal:
+        out["removal"], out["removal_thermal"] = out["rgb"].clone(), out["thermal"].clone()
+    return out
 
 
 class _SplatRender(torch.autograd.Function):
@@ -893,18 +909,20 @@ class ThermalSplatfactoModel(nn.Module):
     def get_outputs(self, camera: PinholeCamera) -> Dict[str, Tensor]:
         """splatfacto.py:659-822 (eval mode, no crop box): project -> SH colours -> tile binning -> raster (colour + depth in one pass).
         Returns rgb [H,W,3], thermal [H,W,1], depth [H,W,1], accumulation [H,W,1], background [3], background_thermal [1]; in separate mode also
-        accumulation_thermal [H,W,1], the thermal chain's accumulation (accumulation is the RGB chain's)."""
+        accumulation_thermal [H,W,1], the thermal chain's accumulation (accumulation is the RGB chain's); with removal_min_opacity_diff set also
+        removal [H,W,3] and removal_thermal [H,W,1], from one more launch over the frame's tile lists."""
         dev = self.means.device
+        thr = self.config.removal_min_opacity_diff
         N, H, W = self.num_points, int(camera.height), int(camera.width)
         aa, deg = self._frame_settings()
         bgl = self._background4(training=False)
         if N == 0:  # every Gaussian culled: the background (splatfacto.py:759-764); last_projection stays what it was
-            return _background_outputs(H, W, bgl, dev, self.separate)
+            return _background_outputs(H, W, bgl, dev, self.separate, thr is not None)
         cam = camera_struct(camera)
         params = [self.gauss_params[k] for k in self.param_names]
         _, ws, cap, total = _project_and_bin(self, cam, params, H, W, deg, aa, max(self._cap, 1 << 16), self._workspace)
         if total == 0:  # nothing on screen
-            return _background_outputs(H, W, bgl, dev, self.separate)
+            return _background_outputs(H, W, bgl, dev, self.separate, thr is not None)
         f32 = torch.float32
         rgbt = torch.empty((H, W, 4), device=dev)
         depth = torch.empty((H, W, 1), device=dev)
@@ -914,7 +932,13 @@ class ThermalSplatfactoModel(nn.Module):
             _lib.check(_lib.load().tn_splat_raster_sep(C.byref(cam), N, C.c_void_p(ws.data_ptr()), cap, (C.c_float * 4)(*bgl), aa, _ptr(rgbt, f32, "rgbt"),
                                                        _ptr(depth, f32, "depth"), _ptr(alpha, f32, "alpha"), _ptr(alpha_th, f32, "alpha_thermal"), _stream()),
                        "tn_splat_raster_sep")
-            return _outputs(rgbt[..., :3], rgbt[..., 3:], depth, alpha, bgl, alpha_th)
+            out = _outputs(rgbt[..., :3], rgbt[..., 3:], depth, alpha, bgl, alpha_th)
+            if thr is not None:  # the removal renders: one more walk over the same lists
+                rem = torch.empty((H, W, 4), device=dev)
+                _lib.check(_lib.load().tn_splat_raster_removal_sep(C.byref(cam), N, C.c_void_p(ws.data_ptr()), cap, (C.c_float * 4)(*bgl), float(thr),
+                                                                   _ptr(rem, f32, "removal"), _stream()), "tn_splat_raster_removal_sep")
+                out["removal"], out["removal_thermal"] = rem[..., :3], rem[..., 3:]
+            return out
         _lib.check(_lib.load().tn_splat_raster(C.byref(cam), N, C.c_void_p(ws.data_ptr()), cap, (C.c_float * 4)(*bgl), aa, _ptr(rgbt, f32, "rgbt"),
                                                _ptr(depth, f32, "depth"), _ptr(alpha, f32, "alpha"), _stream()), "tn_splat_raster")
         return _outputs(rgbt[..., :3], rgbt[..., 3:], depth, alpha, bgl)
@@ -1028,7 +1052,8 @@ class ThermalSplatfactoModel(nn.Module):
     @torch.no_grad()
     def get_image_metrics_and_images(self, outputs: Dict[str, Tensor], batch) -> Tuple[Dict[str, float], Dict[str, Tensor]]:
         """splatfacto.py:917-934 with ThermalNerfactoModel's keys: psnr_rgb / ssim_rgb or psnr_thermal / ssim_thermal of the frame's spectrum
-        (SSIM = the loss's, tn_image_loss), and the ground truth beside both renders.  Scored in training mode under the resolution schedule
+        (SSIM = the loss's, tn_image_loss), and the ground truth beside both renders; `removal` / `removal_thermal` join the images when the
+        outputs hold them.  Scored in training mode under the resolution schedule
         (factor above 1), full-size renders are resized to the ground truth's size, as the reference does (:931-938).  LPIPS is left out, as
         elsewhere in this project."""
         th, pred, gt = self._frame_pred_gt(outputs, batch, resize_pred=True)
@@ -1040,6 +1065,9 @@ class ThermalSplatfactoModel(nn.Module):
             rgb, thermal = resize_image(rgb, gt.shape[:2]), resize_image(thermal, gt.shape[:2])
         images = {"img": torch.cat([gt3, rgb, thermal.expand(-1, -1, 3)], dim=1), "accumulation": outputs["accumulation"],
                   "depth": outputs["depth"]}
+        for k in ("removal", "removal_thermal"):  # the removal renders, at the ground truth's size like rgb and thermal
+            if k in outputs:
+                images[k] = outputs[k] if outputs[k].shape[:2] == gt.shape[:2] else resize_image(outputs[k], gt.shape[:2])
         return metrics, images
 
     # ------------------------------------------------------------------------------------------------ training (splatfacto.py:258-628)

@@ -83,10 +83,15 @@ def main():
     ap.add_argument("--thermal-opacity-mode", default="shared", choices=("shared", "separate"),
                     help='"separate": the thermal channel has an opacity per Gaussian of its own (opacities_thermal)')
     ap.add_argument("--opacity-loss-mult", type=float, default=0.0, help="weight of density_loss between the two opacities (separate mode; 0: off)")
+    ap.add_argument("--removal-min-opacity-diff", type=float, default=None,
+                    help="separate mode: eval renders add `removal` / `removal_thermal`, composited from the Gaussians whose two opacities differ by "
+                         "less than this share of the spectrum's own (ThermalNeRF's removal_min_density_diff); the line reports the shares removed")
     ap.add_argument("--no-undistort", action="store_true", help="train on the raw frames with the parser's intrinsics (the distortion dropped)")
     args = ap.parse_args()
     if args.seed_points and args.data is not None:
         ap.error("--seed-points samples the generated scene's cube; a dataset on disk brings its own ply_file_path")
+    if args.removal_min_opacity_diff is not None and args.thermal_opacity_mode != "separate":
+        ap.error("--removal-min-opacity-diff compares the two opacities: it needs --thermal-opacity-mode separate")
     dev = torch.device("cuda", 0)
     tmp = None
     data = args.data
@@ -106,7 +111,7 @@ def main():
                                        background_color=args.background, num_downscales=args.num_downscales,
                                        resolution_schedule=args.resolution_schedule, tv_pixel_loss_mult=args.tv_pixel_loss_mult,
                                        cross_channel_loss_mult=args.cross_channel_loss_mult, thermal_opacity_mode=args.thermal_opacity_mode,
-                                       opacity_loss_mult=args.opacity_loss_mult)
+                                       opacity_loss_mult=args.opacity_loss_mult, removal_min_opacity_diff=args.removal_min_opacity_diff)
     model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=dm.num_train_data, seed_points=seed_points)
     initial = model.num_points
     opts = Optimizers(model.get_param_groups(), SPLAT_OPTIMIZERS, optimizer_cls=HipAdam)
@@ -153,6 +158,12 @@ def main():
         gp = model.gauss_params
         gap = (torch.sigmoid(gp["opacities"]) - torch.sigmoid(gp["opacities_thermal"])).abs()
         extra["opacity_gap_above_0.5_share"] = float((gap > 0.5).float().mean()) if gap.numel() else 0.0
+        thr = args.removal_min_opacity_diff
+        if thr is not None:  # the share of Gaussians the removal renders leave out of each spectrum
+            o, ot = torch.sigmoid(gp["opacities"]), torch.sigmoid(gp["opacities_thermal"])
+            extra["removal_min_opacity_diff"] = thr
+            extra["removed_from_rgb_share"] = float((~(gap < thr * o)).float().mean()) if gap.numel() else 0.0
+            extra["removed_from_thermal_share"] = float((~(gap < thr * ot)).float().mean()) if gap.numel() else 0.0
     print(json.dumps({"dataset": "synthetic cube scene (train_eval_scene.write_cube_scene)" if tmp else data, "train_images": dm.num_train_data,
                       "val_images": len(val), "steps": args.steps, "ssim_lambda": args.ssim_lambda, "background_color": args.background,
                       "initial_gaussians": initial, "seed_points": args.seed_points, "final_gaussians": model.num_points, "train_seconds": train_s,
