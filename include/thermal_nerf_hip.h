@@ -814,6 +814,38 @@ TN_API int tn_splat_refine_apply_sep(const TnSplatRefine* config, int64_t num_ga
                                      int64_t workspace_bytes, const int64_t* counts, const float* noise, const float* const* params,
                                      const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params, float* const* new_exp_avg,
                                      float* const* new_exp_avg_sq, tn_stream_t stream);
+
+/* ---- N4 crop box: the oriented box of the eval render (SplatfactoModel.crop_box / get_outputs_for_camera, nerfstudio/models/splatfacto.py:
+ * 374-376, 690-698, 904-915; OrientedBox.within, nerfstudio/data/scene_box.py:82-114).  The reference gathers the six parameter tensors
+ * through a boolean index before projecting; here the test sits inside the projection kernel.  world_to_box = rows of the 3x4 matrix
+ * inverse([R|T]) (the caller inverts, once, in float64, and rounds to fp32); half_extent = S / 2.  A point p is inside iff
+ * |q_i| < half_extent[i] for i = 0, 1, 2 -- strict on both sides, so a point exactly on a face is outside, a non-positive extent keeps nothing,
+ * and a NaN keeps nothing -- where, in fp32 with every product and sum rounded on its own (no fused multiply-add) and in this order,
+ *   q_i = ((world_to_box[4i] * p.x + world_to_box[4i+1] * p.y) + world_to_box[4i+2] * p.z) + world_to_box[4i+3]. */
+typedef struct TnSplatCrop {
+  float world_to_box[12];
+  float half_extent[3];
+} TnSplatCrop;
+/* tn_splat_project / tn_splat_project_sep with a crop box (a HOST pointer, read before the launch; null is refused): the crop instantiation
+ * of the same kernel.  The box test on the mean comes first; a Gaussian outside leaves exactly as one behind the clip plane does (radius 0, no
+ * tiles, zeros in every output), a Gaussian inside goes through the same arithmetic as without the box, and a block whose Gaussians are all outside
+ * does not read its higher-order SH coefficients.  No new workspace: tn_splat_bin and every raster entry point run unchanged on what this
+ * leaves, so the frame is the frame of the Gaussians inside, bit for bit.  Refuses what the entry point without _crop refuses. */
+TN_API int tn_splat_project_crop(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
+                                 const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
+                                 int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys, float* depths,
+                                 int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
+                                 int64_t max_intersections, const TnSplatCrop* crop, tn_stream_t stream);
+TN_API int tn_splat_project_crop_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
+                                     const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
+                                     const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs,
+                                     int32_t sh_degree, int32_t antialiased, float* xys, float* depths, int32_t* radii, float* conics, float* compensation,
+                                     int32_t* num_tiles_hit, int32_t* tile_box, void* workspace, int64_t max_intersections, const TnSplatCrop* crop,
+                                     tn_stream_t stream);
+/* the same box test on a bare point list: means [n,3] fp32 -> mask [n] uint8 (1 inside, 0 outside).  n == 0 is TN_OK; refuses a null box, null
+ * pointers for n > 0 and n outside [0, 2^31). */
+TN_API int tn_splat_crop_mask(const TnSplatCrop* crop, const float* means, int64_t n, uint8_t* mask, tn_stream_t stream);
+
 /* ---- N4 training loss: splatfacto's (1 - ssim_lambda) * L1 + ssim_lambda * (1 - SSIM) (nerfstudio/models/splatfacto.py:863-903), SSIM as
  * pytorch_msssim computes it: an 11-tap Gaussian window (sigma 1.5) applied separably as a VALID correlation, C1 = 0.01^2, C2 = 0.03^2 (data
  * range 1), mean over the (H-10) x (W-10) valid pixels and the channels.  L1 = mean |pred - gt| over all H W C values.  Deterministic: no

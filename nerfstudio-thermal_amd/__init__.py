@@ -6,11 +6,11 @@ There is no CPU fallback: every op raises if the HIP library is missing.
 """
 __version__ = "0.1.0"
 
-_LAZY = {"ThermalFullImageDatamanager": "splat_datamanager", "ThermalFullImageDatamanagerConfig": "splat_datamanager"}
+_LAZY = {"ThermalFullImageDatamanager": "splat_datamanager", "ThermalFullImageDatamanagerConfig": "splat_datamanager", "OrientedBox": "splat"}
 
 
 def __getattr__(name):
-    """The splat path's full-image datamanager, imported on first use (importing the package itself stays free of torch)."""
+    """The splat path's full-image datamanager and crop box, imported on first use (importing the package itself stays free of torch)."""
     if name in _LAZY:
         import importlib
 

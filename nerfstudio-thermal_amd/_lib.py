@@ -108,6 +108,11 @@ class TnSplatRefine(C.Structure):
                 ("n_split_samples", _i32), ("continue_cull_post_densification", _i32), ("num_train_data", _i32), ("max_size", _i32)]
 
 
+class TnSplatCrop(C.Structure):
+    """include/thermal_nerf_hip.h: the crop box of the eval render, rows of the 3x4 world -> box matrix and S / 2 (tn_splat_project_crop, tn_splat_crop_mask)"""
+    _fields_ = [("world_to_box", _f * 12), ("half_extent", _f * 3)]
+
+
 class TnUndistort(C.Structure):
     """include/thermal_nerf_hip.h: the source camera, the pinhole camera of the output and k1 k2 k3 k4 p1 p2 (tn_image_undistort)"""
     _fields_ = [("fx", _f), ("fy", _f), ("cx", _f), ("cy", _f), ("new_fx", _f), ("new_fy", _f), ("new_cx", _f), ("new_cy", _f), ("k", _f * 6)]
@@ -208,6 +213,10 @@ SIGNATURES = {
     "tn_splat_project_backward_sep": (C.c_int, [_p] * 10 + [_i64, _i32, _i32, _i32] + [_p] * 16),
     "tn_splat_refine_plan_sep": (C.c_int, [C.POINTER(TnSplatRefine), _i32] + [_p] * 6 + [_i64, _p, _i64, _p, _p]),
     "tn_splat_refine_apply_sep": (C.c_int, [C.POINTER(TnSplatRefine), _i64, _i32, _p, _i64, _p, _p] + [_p] * 6 + [_p]),
+    # crop box of the eval render: the projection entry points plus the box, and the box test on a point list
+    "tn_splat_project_crop": (C.c_int, [_p] * 9 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, C.POINTER(TnSplatCrop), _p]),
+    "tn_splat_project_crop_sep": (C.c_int, [_p] * 10 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, C.POINTER(TnSplatCrop), _p]),
+    "tn_splat_crop_mask": (C.c_int, [C.POINTER(TnSplatCrop), _p, _i64, _p, _p]),
     "tn_image_loss_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "tn_image_loss": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _f, _f, _p, _i64, _p, _p, _p]),
     "tn_image_resize": (C.c_int, [_p, _i32, _i64, _i32, _i32, _i32, _p, _i32, _i32, _p]),

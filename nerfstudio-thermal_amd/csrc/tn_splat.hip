@@ -139,9 +139,40 @@ struct SplatCamK {
   int W, H, tbx, tby;
 };
 
+// Extra kernel arguments of an instantiation ride in a parameter pack that is empty in the others, which so keep their argument list and every
+// kernel-argument offset: pack_arg<I> is the I-th of them.
+template <int I, typename T, typename... R>
+__device__ __forceinline__ auto pack_arg(T t, R... r) {
+  if constexpr (I == 0) return t;
+  else return pack_arg<I - 1>(r...);
+}
+
+// The crop box of the eval render (OrientedBox: splatfacto.py:690-698, scene_box.py:82-114): m = rows of the 3x4 world -> box matrix
+// inverse([R|T]), h = S / 2.  A point p is inside iff |q_i| < h_i on all three axes (strict on both sides; h_i <= 0 or a NaN keeps nothing) with
+//   q_i = ((m[4i] * p.x + m[4i+1] * p.y) + m[4i+2] * p.z) + m[4i+3]
+// in fp32, every product and every sum rounded to nearest on its own (no fused multiply-add), in exactly this order: the float64 restatement
+// of the tests names its near-boundary band from the rounding of these seven operations.
+struct SplatCropK {
+  float m[12];
+  float h[3];
+};
+__device__ __forceinline__ bool splat_in_crop(const SplatCropK& c, float x, float y, float z) {
+  bool in = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float q = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.m[4 * a], x), __fmul_rn(c.m[4 * a + 1], y)), __fmul_rn(c.m[4 * a + 2], z)), c.m[4 * a + 3]);
+    in = in && fabsf(q) < c.h[a];
+  }
+  return in;
+}
+
 // SEP: the thermal channel has an opacity of its own (opac_th_logit, else unused): its log2 goes into the record's two spare floats, and the box
 // around {alpha >= 1/255} comes from the larger of the two opacities, so neither chain of the rasteriser loses a contributor.
-template <bool SEP>
+// Crop (one SplatCropK, or nothing): the crop instantiation tests every mean against the box FIRST.  A Gaussian outside leaves exactly as one behind
+// the clip plane does -- radius 0, no tiles, zeros -- and never reaches the sort; a block whose Gaussians are ALL outside (one block-wide vote, taken
+// by every thread before the barrier below, so the decision is uniform there) does not stage its SH slab -- 240 of the 300 bytes a Gaussian has at
+// degree 3.  Without the pack the kernel is the one it was.
+template <bool SEP, typename... Crop>
 __global__ void __launch_bounds__(256) k_splat_project(SplatCamK cam, const float* __restrict__ means, const float* __restrict__ log_scales,
                                                        const float* __restrict__ quats, const float* __restrict__ opac_logit,
                                                        const float* __restrict__ f_dc, const float* __restrict__ f_rest,
@@ -150,7 +181,9 @@ __global__ void __launch_bounds__(256) k_splat_project(SplatCamK cam, const floa
                                                        int32_t* __restrict__ radii, float* __restrict__ conics, float* __restrict__ comp_out,
                                                        int32_t* __restrict__ tiles_hit, int32_t* __restrict__ tile_box, SplatRec* __restrict__ recs,
                                                        int32_t* __restrict__ tbox, int32_t* __restrict__ thits,
-                                                       const float* __restrict__ opac_th_logit) {
+                                                       const float* __restrict__ opac_th_logit, Crop... crop_arg) {
+  static_assert(sizeof...(Crop) <= 1, "the crop instantiation takes one SplatCropK");
+  constexpr bool CROP = sizeof...(Crop) == 1;
   // The higher-order SH coefficients of the block's 256 Gaussians (45 + 15 floats each) go through LDS: the block copies its contiguous
   // 46 KB + 15 KB slab with coalesced 16-byte loads, and each thread then reads its own coefficients at stride 45 / 15 floats -- odd strides,
   // so the 64 lanes of a wave hit 64 different banks.  Reading them straight from global memory (each lane its own 180-byte run) cost
@@ -158,10 +191,20 @@ __global__ void __launch_bounds__(256) k_splat_project(SplatCamK cam, const floa
   extern __shared__ float sh_lds[];
   float* s_rest = sh_lds;
   float* s_trest = sh_lds + (int)blockDim.x * rest_coeffs * 3;
+  [[maybe_unused]] bool in_box = true;
   {
     const int64_t g0 = blockIdx.x * (int64_t)blockDim.x;
     const int cnt = (int)min((int64_t)blockDim.x, N - g0);
-    if (rest_coeffs > 0 && sh_degree >= 1) {
+    bool stage = rest_coeffs > 0 && sh_degree >= 1;
+    if constexpr (CROP) {
+      const SplatCropK crop = pack_arg<0>(crop_arg...);
+      const int64_t g = g0 + threadIdx.x;
+      in_box = g < N && splat_in_crop(crop, means[3 * g], means[3 * g + 1], means[3 * g + 2]);
+      // The vote: one block-wide OR, a barrier that hands every thread the same answer, so `stage` is uniform over the block before the staging
+      // barrier below.  Every thread of the block gets here (the tail's threads too: the early return for i >= N comes after both barriers).
+      stage = __syncthreads_or(in_box ? 1 : 0) != 0 && stage;
+    }
+    if (stage) {
       const int n3 = cnt * rest_coeffs * 3, n1 = cnt * rest_coeffs;
       const float* src3 = f_rest + g0 * rest_coeffs * 3;
       const float* src1 = t_rest + g0 * rest_coeffs;
@@ -186,6 +229,7 @@ __global__ void __launch_bounds__(256) k_splat_project(SplatCamK cam, const floa
   float py = V[4] * mx + V[5] * my + V[6] * mz + V[7];
   float pz = V[8] * mx + V[9] * my + V[10] * mz + V[11];
   bool ok = pz > cam.clip;
+  if constexpr (CROP) ok = ok && in_box;
   if (ok) {
     // Sigma = (R S)(R S)^T
     float qw = quats[4 * i], qx = quats[4 * i + 1], qy = quats[4 * i + 2], qz = quats[4 * i + 3];
@@ -411,14 +455,9 @@ __device__ __forceinline__ float splat_alpha_raw(float l2op, float power) { retu
 __device__ __forceinline__ float splat_alpha(float raw) { return fminf(0.999f, raw); }
 __device__ __forceinline__ bool splat_visible(float alpha) { return alpha >= (1.0f / 255.0f); }
 
-// The SEP instantiations' extra kernel arguments ride in a parameter pack (empty without SEP), so that the SEP = false kernels keep the argument
-// list -- and with it every kernel-argument offset -- they had before SEP existed: their instruction stream is the parent's, bit for bit.
-template <int I, typename T, typename... R>
-__device__ __forceinline__ auto pack_arg(T t, R... r) {
-  if constexpr (I == 0) return t;
-  else return pack_arg<I - 1>(r...);
-}
-
+// The SEP instantiations' extra kernel arguments ride in a parameter pack (empty without SEP; pack_arg, above k_splat_project), so that the
+// SEP = false kernels keep the argument list -- and with it every kernel-argument offset -- they had before SEP existed: their instruction stream
+// is the parent's, bit for bit.
 // TRAIN: the training variant (tn_splat_raster_train) also leaves what the backward needs per pixel -- the final transmittance and the number
 // of list entries up to and including the last Gaussian that contributed -- and writes the colour BEFORE the clamp to 1 (the caller clamps,
 // so the clamp's gradient mask is the caller's).  TRAIN = false is the eval rasteriser, unchanged.
@@ -1139,13 +1178,20 @@ static SplatCamK make_camk(const TnSplatCamera* cam) {
   return k;
 }
 
+static SplatCropK make_cropk(const TnSplatCrop* crop) {
+  SplatCropK c;
+  for (int i = 0; i < 12; ++i) c.m[i] = crop->world_to_box[i];
+  for (int i = 0; i < 3; ++i) c.h[i] = crop->half_extent[i];
+  return c;
+}
+
 // The _sep entry points (separate thermal opacity) share their implementation with the entry points they extend: `sep` picks the SEP
 // instantiation of the kernels, and the thermal-opacity pointers, null in shared mode, are then required.  `who` names the entry point in messages.
-static int splat_project(const char* who, bool sep, const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
-                         const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
-                         const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys,
-                         float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
-                         int64_t max_intersections, tn_stream_t stream) {
+static int splat_project(const char* who, bool sep, const TnSplatCrop* crop, const TnSplatCamera* camera, const float* means, const float* log_scales,
+                         const float* quats, const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
+                         const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
+                         int32_t antialiased, float* xys, float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit,
+                         int32_t* tile_box, void* workspace, int64_t max_intersections, tn_stream_t stream) {
   int rc = check_cam(camera, who);
   if (rc) return rc;
   if (num_gaussians == 0) return TN_OK;
@@ -1162,7 +1208,15 @@ static int splat_project(const char* who, bool sep, const TnSplatCamera* camera,
   SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, k.tbx * k.tby, nullptr);
   const int PB = 128;  // Gaussians per block: 30 KB of LDS at degree 3 -> 5 blocks per CU (256 per block = 61 KB = 2 blocks: 136 vs 1xx us)
   const size_t lds = (size_t)PB * num_rest_coeffs * 4 * sizeof(float);
-  TN_REQUIRE(lds <= 65536, "%s: %d higher-order coefficients do not fit the LDS staging", who, num_rest_coeffs);
+  TN_REQUIRE(lds <= (crop ? 65536 - 256 : 65536), "%s: %d higher-order coefficients do not fit the LDS staging", who, num_rest_coeffs);  // 256 B of static LDS: the words of __syncthreads_or
+  if (crop) {  // the crop instantiation: the same launch plus the box
+    hipLaunchKernelGGL((sep ? k_splat_project<true, SplatCropK> : k_splat_project<false, SplatCropK>), dim3((unsigned)tn_cdiv(num_gaussians, PB)), dim3(PB), lds,
+                       tn_s(stream), k, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree,
+                       num_rest_coeffs, antialiased, (float2*)xys, depths, radii, conics, compensation, num_tiles_hit, tile_box, ws.recs, ws.tbox, ws.thits,
+                       opacities_thermal, make_cropk(crop));
+    TN_CHECK_LAUNCH(who);
+    return TN_OK;
+  }
   hipLaunchKernelGGL(sep ? k_splat_project<true> : k_splat_project<false>, dim3((unsigned)tn_cdiv(num_gaussians, PB)), dim3(PB), lds, tn_s(stream), k, means,
                      log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased,
                      (float2*)xys, depths, radii, conics, compensation, num_tiles_hit, tile_box, ws.recs, ws.tbox, ws.thits, opacities_thermal);
@@ -1175,9 +1229,9 @@ extern "C" int tn_splat_project(const TnSplatCamera* camera, const float* means,
                                 int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys, float* depths,
                                 int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
                                 int64_t max_intersections, tn_stream_t stream) {
-  return splat_project("tn_splat_project", false, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, nullptr,
-                       num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation, num_tiles_hit, tile_box, workspace,
-                       max_intersections, stream);
+  return splat_project("tn_splat_project", false, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
+                       nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation, num_tiles_hit, tile_box,
+                       workspace, max_intersections, stream);
 }
 
 extern "C" int tn_splat_project_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
@@ -1185,9 +1239,51 @@ extern "C" int tn_splat_project_sep(const TnSplatCamera* camera, const float* me
                                     const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased,
                                     float* xys, float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box,
                                     void* workspace, int64_t max_intersections, tn_stream_t stream) {
-  return splat_project("tn_splat_project_sep", true, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
-                       opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation, num_tiles_hit,
-                       tile_box, workspace, max_intersections, stream);
+  return splat_project("tn_splat_project_sep", true, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
+                       thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation,
+                       num_tiles_hit, tile_box, workspace, max_intersections, stream);
+}
+
+// The crop entry points: the entry point each is named after, with the crop instantiation of the projection kernel.  A null box is refused (the
+// uncropped frame is the entry point without _crop).
+extern "C" int tn_splat_project_crop(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
+                                     const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
+                                     int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys, float* depths,
+                                     int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
+                                     int64_t max_intersections, const TnSplatCrop* crop, tn_stream_t stream) {
+  TN_REQUIRE(crop != nullptr, "tn_splat_project_crop: null crop box");
+  return splat_project("tn_splat_project_crop", false, crop, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
+                       nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation, num_tiles_hit, tile_box,
+                       workspace, max_intersections, stream);
+}
+
+extern "C" int tn_splat_project_crop_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
+                                         const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
+                                         const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs,
+                                         int32_t sh_degree, int32_t antialiased, float* xys, float* depths, int32_t* radii, float* conics, float* compensation,
+                                         int32_t* num_tiles_hit, int32_t* tile_box, void* workspace, int64_t max_intersections, const TnSplatCrop* crop,
+                                         tn_stream_t stream) {
+  TN_REQUIRE(crop != nullptr, "tn_splat_project_crop_sep: null crop box");
+  return splat_project("tn_splat_project_crop_sep", true, crop, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
+                       thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation,
+                       num_tiles_hit, tile_box, workspace, max_intersections, stream);
+}
+
+// the box test of the crop projection on a bare point list: mask[i] = 1 where means[i] is inside, else 0
+__global__ void __launch_bounds__(256) k_splat_crop_mask(SplatCropK crop, const float* __restrict__ means, int64_t n, uint8_t* __restrict__ mask) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  mask[i] = splat_in_crop(crop, means[3 * i], means[3 * i + 1], means[3 * i + 2]) ? 1 : 0;
+}
+
+extern "C" int tn_splat_crop_mask(const TnSplatCrop* crop, const float* means, int64_t n, uint8_t* mask, tn_stream_t stream) {
+  TN_REQUIRE(crop != nullptr, "tn_splat_crop_mask: null crop box");
+  TN_REQUIRE(n >= 0 && n < (1ll << 31), "tn_splat_crop_mask: bad point count");
+  if (n == 0) return TN_OK;
+  TN_REQUIRE(means && mask, "tn_splat_crop_mask: null pointer");
+  hipLaunchKernelGGL(k_splat_crop_mask, dim3((unsigned)tn_cdiv(n, 256)), dim3(256), 0, tn_s(stream), make_cropk(crop), means, n, mask);
+  TN_CHECK_LAUNCH("tn_splat_crop_mask");
+  return TN_OK;
 }
 
 extern "C" int tn_splat_bin(const TnSplatCamera* camera, const float* depths, int64_t num_gaussians, void* workspace, int64_t max_intersections,

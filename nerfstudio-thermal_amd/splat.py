@@ -43,7 +43,15 @@ are resampled once into pinhole frames, as the reference's FullImageDatamanager 
 `undistorted_camera` is the pinhole camera of a distorted one (the largest frame of the same size that reads only inside the source),
 `undistort_image` the frame it sees (tn_image_undistort, uint8 or fp32 in and out), with tn_raygen's distortion model and pixel convention, so a
 dataset means the same on the NeRF path and here; splat_datamanager.ThermalFullImageDatamanager caches the undistorted frames on the device and
-serves (camera, batch).  Masks and camera-pose gradients are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
+serves (camera, batch).  The eval render takes splatfacto's crop box (splatfacto.py:374-376, 690-698, 904-915): `OrientedBox` (R, T, S as
+nerfstudio/data/scene_box.py:82-114; `from_params(pos, rpy, scale)`, `within(pts)`), `set_crop(box)` / `crop_box` and
+`get_outputs_for_camera(camera, obb_box)`, the door of the viewer, ns-render and the exporter.  With a box set `get_outputs` renders only the
+Gaussians whose mean is strictly inside it, bit for bit the frame of a model holding those alone -- rgb, thermal, depth, the accumulations and the
+removal renders.  The reference gathers six parameter tensors through a boolean index per frame; here the box test is the first thing the
+projection kernel does (tn_splat_project_crop / _crop_sep): a Gaussian outside leaves with radius 0 and no tiles, as one behind the camera, a
+block of Gaussians that are all outside never reads its SH coefficients, and nothing is copied, allocated or read back.  The training render never
+crops (the reference crops only outside training), and the box is neither a parameter nor in the state dict.  Masks and camera-pose gradients are
+not built.  Parity is unpinned (gsplat is a third-party package outside the reference
 tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 """
 from __future__ import annotations
@@ -136,6 +144,88 @@ class PinholeCamera:
     cy: float
     width: int
     height: int
+
+
+def _rotation_rpy(roll: float, pitch: float, yaw: float) -> Tensor:
+    """Rz(yaw) Ry(pitch) Rx(roll) [3,3] in float64 (radians): what viser's SO3.from_rpy_radians(roll, pitch, yaw).as_matrix() gives."""
+    cr, sr, cp, sp, cy, sy = math.cos(roll), math.sin(roll), math.cos(pitch), math.sin(pitch), math.cos(yaw), math.sin(yaw)
+    rz = torch.tensor([[cy, -sy, 0.0], [sy, cy, 0.0], [0.0, 0.0, 1.0]], dtype=torch.float64)
+    ry = torch.tensor([[cp, 0.0, sp], [0.0, 1.0, 0.0], [-sp, 0.0, cp]], dtype=torch.float64)
+    rx = torch.tensor([[1.0, 0.0, 0.0], [0.0, cr, -sr], [0.0, sr, cr]], dtype=torch.float64)
+    return rz @ ry @ rx
+
+
+@dataclass
+class OrientedBox:
+    """The reference's oriented box (nerfstudio/data/scene_box.py:82-114): box coordinates -> world is p = R q + T, and the box is
+    |q_i| < S_i / 2.  R [3,3] may be any invertible matrix (a rotation from `from_params`), T [3] is the centre, S [3] the full extents.
+
+    `within(pts)`: q = inverse([R|T]) [p, 1]; inside iff -S_i/2 < q_i < S_i/2 on all three axes, strictly on both sides -- a point exactly on
+    a face is outside and a non-positive S_i keeps nothing.  The 3x4 world -> box matrix is computed once per call on the host in float64 and
+    rounded to fp32 (`world_to_box`; a singular R is a ValueError); q_i = ((m_i0 x + m_i1 y) + m_i2 z) + m_i3 is then evaluated in the points'
+    precision, every product and sum rounded on its own.  float32 HIP tensors go through tn_splat_crop_mask, the device function the cropped
+    projection itself uses; anything else runs the same rule in torch."""
+
+    R: Tensor
+    T: Tensor
+    S: Tensor
+
+    @staticmethod
+    def from_params(pos: Tuple[float, float, float], rpy: Tuple[float, float, float], scale: Tuple[float, float, float]) -> "OrientedBox":
+        """Centre `pos`, extents `scale`, R = Rz(yaw) Ry(pitch) Rx(roll) with rpy = (roll, pitch, yaw) in radians (scene_box.py:100-114)."""
+        return OrientedBox(R=_rotation_rpy(*(float(a) for a in rpy)).float(), T=torch.tensor([float(v) for v in pos], dtype=torch.float32),
+                           S=torch.tensor([float(v) for v in scale], dtype=torch.float32))
+
+    def _world_to_box_rows(self) -> List[List[float]]:
+        """inverse([R|T]) = [R^-1 | -R^-1 T], three rows of four, in float64 (Python floats: the adjugate over the determinant -- no tensor
+        work, this runs once per cropped frame)."""
+        R, T, S = (torch.as_tensor(v).detach() for v in (self.R, self.T, self.S))
+        if R.shape != (3, 3) or T.shape != (3,) or S.shape != (3,):
+            raise ValueError(f"OrientedBox: R [3,3], T [3] and S [3] expected, got {tuple(R.shape)}, {tuple(T.shape)} and {tuple(S.shape)}")
+        (a, b, c), (d, e, f), (g, h, i) = R.tolist()
+        t = T.tolist()
+        adj = [[e * i - f * h, c * h - b * i, b * f - c * e], [f * g - d * i, a * i - c * g, c * d - a * f], [d * h - e * g, b * g - a * h, a * e - b * d]]
+        det = a * adj[0][0] + b * adj[1][0] + c * adj[2][0]
+        size = math.sqrt(a * a + b * b + c * c) * math.sqrt(d * d + e * e + f * f) * math.sqrt(g * g + h * h + i * i)  # |det| <= this (Hadamard)
+        if not (math.isfinite(det) and math.isfinite(size)) or abs(det) <= 1e-12 * size:
+            raise ValueError("OrientedBox: R is singular, the box has no world -> box transform")
+        rows = [[v / det for v in row] for row in adj]
+        return [row + [-(row[0] * t[0] + row[1] * t[1] + row[2] * t[2])] for row in rows]
+
+    def world_to_box(self) -> Tensor:
+        """inverse([R|T]) as [3,4] fp32 on the host, inverted in float64 and rounded once."""
+        return torch.tensor(self._world_to_box_rows(), dtype=torch.float64).float()
+
+    def crop_struct(self) -> _lib.TnSplatCrop:
+        """The box as the C entry points take it: rows of `world_to_box` and S / 2."""
+        rows = self._world_to_box_rows()
+        c = _lib.TnSplatCrop()
+        c.world_to_box[:] = [v for row in rows for v in row]  # ctypes rounds the float64 values to fp32
+        c.half_extent[:] = [0.5 * v for v in torch.as_tensor(self.S).detach().float().tolist()]
+        return c
+
+    def within(self, pts: Tensor) -> Tensor:
+        """bool [n] for pts [n,3]: which points are strictly inside the box."""
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError(f"OrientedBox.within: pts must be [n,3], got {tuple(pts.shape)}")
+        if pts.is_cuda and pts.dtype == torch.float32:
+            p = pts.detach().contiguous()
+            mask = torch.empty((p.shape[0],), dtype=torch.uint8, device=p.device)
+            crop = self.crop_struct()
+            _lib.check(_lib.load().tn_splat_crop_mask(C.byref(crop), _ptr(p, torch.float32, "pts"), p.shape[0], C.c_void_p(mask.data_ptr()), _stream()),
+                       "tn_splat_crop_mask")
+            return mask.bool()
+        p = pts.detach()
+        if not p.is_floating_point():
+            p = p.float()
+        m = self.world_to_box().to(device=p.device, dtype=p.dtype)
+        h = (0.5 * torch.as_tensor(self.S).detach().to("cpu", torch.float32)).to(device=p.device, dtype=p.dtype)
+        x, y, z = p[:, 0], p[:, 1], p[:, 2]
+        inside = torch.ones(p.shape[0], dtype=torch.bool, device=p.device)
+        for i in range(3):
+            q = ((m[i, 0] * x + m[i, 1] * y) + m[i, 2] * z) + m[i, 3]
+            inside &= q.abs() < h[i]
+        return inside
 
 
 def downscale_factor(step: int, num_downscales: int, resolution_schedule: int, training: bool) -> int:
@@ -584,9 +674,9 @@ def _param_ptrs(tensors) -> list:
     return pp
 
 
-def _project_and_bin(model, cam, params, H: int, W: int, deg: int, aa: int, cap: int, workspace):
+def _project_and_bin(model, cam, params, H: int, W: int, deg: int, aa: int, cap: int, workspace, crop: Optional[_lib.TnSplatCrop] = None):
     """One frame's tn_splat_project -> tn_splat_bin into `workspace(N, cap, tiles)`, a buffer for `cap` (Gaussian, tile) pairs: the caller says
-    where it comes from.  A frame with more pairs grows `cap` once and is redone.  Leaves `last_projection` / `last_num_intersections` on the model
+    where it comes from.  With `crop` the projection is tn_splat_project_crop / _crop_sep: Gaussians outside the box leave with radius 0.  A frame with more pairs grows `cap` once and is redone.  Leaves `last_projection` / `last_num_intersections` on the model
     and returns (projection tensors, workspace, cap, pairs).  No Gaussians: nothing to project, no workspace (None), the frame is the background."""
     i32 = torch.int32
     lib = _lib.load()
@@ -600,7 +690,10 @@ def _project_and_bin(model, cam, params, H: int, W: int, deg: int, aa: int, cap:
         out_ptrs = [_ptr(t, t.dtype, k) for k, t in proj.items()]
         ws = workspace(N, cap, tiles)
         wsp = C.c_void_p(ws.data_ptr())
-        if len(params) == 9:  # separate thermal opacity
+        if crop is not None:  # the eval render's crop box: the same launch with the box test in front
+            name = "tn_splat_project_crop_sep" if len(params) == 9 else "tn_splat_project_crop"
+            _lib.check(getattr(lib, name)(C.byref(cam), *_param_ptrs(params), N, K, deg, aa, *out_ptrs, wsp, cap, C.byref(crop), _stream()), name)
+        elif len(params) == 9:  # separate thermal opacity
             _lib.check(lib.tn_splat_project_sep(C.byref(cam), *_param_ptrs(params), N, K, deg, aa, *out_ptrs, wsp, cap, _stream()), "tn_splat_project_sep")
         else:
             _lib.check(lib.tn_splat_project(C.byref(cam), *_param_ptrs(params), N, K, deg, aa, *out_ptrs, wsp, cap, _stream()), "tn_splat_project")
@@ -795,6 +888,8 @@ class ThermalSplatfactoModel(nn.Module):
         self.last_num_intersections = 0
         self.last_radii: Optional[Tensor] = None  # radii [N] and (H, W) of the last TRAINING frame
         self.last_size: Optional[Tuple[int, int]] = None
+        # the eval render's crop box (splatfacto.py:374-376): plain attributes, neither parameters nor in the state dict
+        self.crop_box: Optional[OrientedBox] = None
         # refinement statistics (after_train); None = the next after_train is the first after a reset
         self.xys_grad_norm: Optional[Tensor] = None
         self.vis_counts: Optional[Tensor] = None
@@ -905,12 +1000,31 @@ class ThermalSplatfactoModel(nn.Module):
             raise ValueError(f"Unknown rasterize_mode: {cfg.rasterize_mode}")
         return int(cfg.rasterize_mode == "antialiased"), min(self.step // cfg.sh_degree_interval, cfg.sh_degree) if cfg.sh_degree > 0 else -1
 
+    def set_crop(self, crop_box: Optional[OrientedBox]) -> None:
+        """splatfacto.py:374-376: the box `get_outputs` crops to from now on; None clears it.  The box is read anew by every cropped frame (its
+        world -> box matrix is inverted on the host, a few dozen float operations), so a box changed afterwards, in place or not, is seen; a
+        singular R is the ValueError of that frame, raised before any launch."""
+        if crop_box is not None and not isinstance(crop_box, OrientedBox):
+            raise TypeError(f"set_crop: an OrientedBox or None expected, got {type(crop_box).__name__}")
+        self.crop_box = crop_box
+
+    def _crop(self) -> Optional[_lib.TnSplatCrop]:
+        """The C struct of `crop_box` as it is now (also when the attribute was assigned without set_crop, as the reference's viewer does)."""
+        return None if self.crop_box is None else self.crop_box.crop_struct()
+
+    def get_outputs_for_camera(self, camera: PinholeCamera, obb_box: Optional[OrientedBox] = None) -> Dict[str, Tensor]:
+        """splatfacto.py:904-915: the eval render cropped to `obb_box`; as in the reference, None clears an earlier crop."""
+        self.set_crop(obb_box)
+        return self.get_outputs(camera)
+
     @torch.no_grad()
     def get_outputs(self, camera: PinholeCamera) -> Dict[str, Tensor]:
-        """splatfacto.py:659-822 (eval mode, no crop box): project -> SH colours -> tile binning -> raster (colour + depth in one pass).
+        """splatfacto.py:659-822 (eval mode): project -> SH colours -> tile binning -> raster (colour + depth in one pass).
         Returns rgb [H,W,3], thermal [H,W,1], depth [H,W,1], accumulation [H,W,1], background [3], background_thermal [1]; in separate mode also
         accumulation_thermal [H,W,1], the thermal chain's accumulation (accumulation is the RGB chain's); with removal_min_opacity_diff set also
-        removal [H,W,3] and removal_thermal [H,W,1], from one more launch over the frame's tile lists."""
+        removal [H,W,3] and removal_thermal [H,W,1], from one more launch over the frame's tile lists.  With `crop_box` set the projection is the
+        crop instantiation: every output is that of the Gaussians strictly inside the box alone, `last_projection` holds radius 0 for the others, and
+        a box that keeps nothing gives the background (splatfacto.py:690-698, 759-764)."""
         dev = self.means.device
         thr = self.config.removal_min_opacity_diff
         N, H, W = self.num_points, int(camera.height), int(camera.width)
@@ -920,7 +1034,7 @@ class ThermalSplatfactoModel(nn.Module):
             return _background_outputs(H, W, bgl, dev, self.separate, thr is not None)
         cam = camera_struct(camera)
         params = [self.gauss_params[k] for k in self.param_names]
-        _, ws, cap, total = _project_and_bin(self, cam, params, H, W, deg, aa, max(self._cap, 1 << 16), self._workspace)
+        _, ws, cap, total = _project_and_bin(self, cam, params, H, W, deg, aa, max(self._cap, 1 << 16), self._workspace, self._crop())
         if total == 0:  # nothing on screen
             return _background_outputs(H, W, bgl, dev, self.separate, thr is not None)
         f32 = torch.float32
@@ -948,8 +1062,8 @@ class ThermalSplatfactoModel(nn.Module):
         return downscale_factor(self.step, self.config.num_downscales, self.config.resolution_schedule, self.training)
 
     def get_train_outputs(self, camera: PinholeCamera) -> Dict[str, Tensor]:
-        """The render of get_outputs as a differentiable function of every gauss_params tensor (splatfacto.py:659-822 in training, without
-        the crop box).  rgb [H,W,3], thermal [H,W,1] and accumulation [H,W,1] carry gradients; depth [H,W,1] is detached.  With a fixed
+        """The render of get_outputs as a differentiable function of every gauss_params tensor (splatfacto.py:659-822 in training: `crop_box`
+        is not read, the reference crops only outside training).  rgb [H,W,3], thermal [H,W,1] and accumulation [H,W,1] carry gradients; depth [H,W,1] is detached.  With a fixed
         background the values equal get_outputs' bit for bit; background_color "random" draws this frame's RGB + thermal background from the
         model's generator (background [3], background_thermal [1]).  After backward(), `last_xys_grad` [N,2] holds dL/d xys per Gaussian.
         Under the resolution schedule the frame is that of `rescaled_camera(camera, d)` (splatfacto.py:699-700): its size is what `last_size`,

@@ -14,7 +14,11 @@ one Gaussian per point with kNN scales) instead of from --gaussians random ones.
 schedule: 1 / 2^N of each frame's size at first, doubled every --resolution-schedule steps); the JSON line lists every stage with its factor, its
 steps and its time per iteration, and the val split is scored in eval mode, at full size.  --tv-pixel-loss-mult / --cross-channel-loss-mult (default 0:
 off) switch on ThermalNeRF's regularisers of the thermal render at the RGB cameras (get_loss_dict's tv_pixel_loss / cross_channel_loss: tn_thermal_reg;
-the NeRF path runs both at 1e-6); the backward goes over the sum of the loss dict."""
+the NeRF path runs both at 1e-6); the backward goes over the sum of the loss dict.  --crop-pos / --crop-rpy / --crop-scale (three floats each, all
+three or none: centre, roll pitch yaw in radians, extents) give the eval render an oriented crop box (OrientedBox.from_params): after the val
+split is scored on the whole scene, its frames are rendered again through get_outputs_for_camera(camera, box) and written as PNGs to --crop-out
+(rgb_*.png, thermal_*.png; in separate mode with --removal-min-opacity-diff also removal_*.png and removal_thermal_*.png), and the line reports
+the share of Gaussians the box keeps."""
 import argparse
 import functools
 import json
@@ -35,7 +39,7 @@ from nerfstudio_thermal_amd import ThermalFullImageDatamanagerConfig  # noqa: E4
 from nerfstudio_thermal_amd.dataparser import ThermalNerfDataParserConfig, load_image_float32, write_ply  # noqa: E402
 from nerfstudio_thermal_amd.model import TrainingCallbackLocation  # noqa: E402
 from nerfstudio_thermal_amd.optim import SPLAT_OPTIMIZERS, HipAdam, Optimizers  # noqa: E402
-from nerfstudio_thermal_amd.splat import PinholeCamera, ThermalSplatfactoModel, ThermalSplatfactoModelConfig, downscale_factor  # noqa: E402
+from nerfstudio_thermal_amd.splat import OrientedBox, PinholeCamera, ThermalSplatfactoModel, ThermalSplatfactoModelConfig, downscale_factor  # noqa: E402
 from train_eval_scene import write_cube_scene  # noqa: E402
 
 
@@ -64,6 +68,23 @@ def add_seed_points(data: str, num: int, seed: int) -> None:
         json.dump(meta, f, indent=4)
 
 
+def write_cropped_frames(model, val, box, out_dir: str) -> int:
+    """The val frames through get_outputs_for_camera(camera, box), one PNG per image output; returns the number of frames."""
+    from PIL import Image
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = 0
+    with torch.no_grad():
+        for n, (cam, _) in enumerate(val, 1):
+            out = model.get_outputs_for_camera(cam, box)
+            for key in ("rgb", "thermal", "removal", "removal_thermal"):
+                if key in out:
+                    u8 = (out[key].clamp(0.0, 1.0) * 255.0).round().to(torch.uint8).cpu().numpy()
+                    Image.fromarray(u8[:, :, 0] if u8.shape[2] == 1 else u8).save(os.path.join(out_dir, f"{key}_{n:05d}.png"))
+    model.set_crop(None)
+    return n
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", default=None)
@@ -86,12 +107,20 @@ def main():
     ap.add_argument("--removal-min-opacity-diff", type=float, default=None,
                     help="separate mode: eval renders add `removal` / `removal_thermal`, composited from the Gaussians whose two opacities differ by "
                          "less than this share of the spectrum's own (ThermalNeRF's removal_min_density_diff); the line reports the shares removed")
+    ap.add_argument("--crop-pos", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="centre of the eval render's crop box")
+    ap.add_argument("--crop-rpy", type=float, nargs=3, default=None, metavar=("ROLL", "PITCH", "YAW"), help="its orientation, radians")
+    ap.add_argument("--crop-scale", type=float, nargs=3, default=None, metavar=("SX", "SY", "SZ"), help="its extents")
+    ap.add_argument("--crop-out", default="out/crop", help="where the cropped eval frames are written")
     ap.add_argument("--no-undistort", action="store_true", help="train on the raw frames with the parser's intrinsics (the distortion dropped)")
     args = ap.parse_args()
     if args.seed_points and args.data is not None:
         ap.error("--seed-points samples the generated scene's cube; a dataset on disk brings its own ply_file_path")
     if args.removal_min_opacity_diff is not None and args.thermal_opacity_mode != "separate":
         ap.error("--removal-min-opacity-diff compares the two opacities: it needs --thermal-opacity-mode separate")
+    crop_args = (args.crop_pos, args.crop_rpy, args.crop_scale)
+    if any(a is not None for a in crop_args) and not all(a is not None for a in crop_args):
+        ap.error("--crop-pos, --crop-rpy and --crop-scale go together")
+    crop_box = OrientedBox.from_params(*crop_args) if crop_args[0] is not None else None
     dev = torch.device("cuda", 0)
     tmp = None
     data = args.data
@@ -151,9 +180,13 @@ def main():
             metrics, _ = model.get_image_metrics_and_images(model.get_outputs(cam), batch)
             for k, v in metrics.items():
                 sums.setdefault(k, []).append(v)
+    extra = {}
+    if crop_box is not None:  # the same frames cropped to the box, written out; the whole-scene metrics above are untouched
+        frames = write_cropped_frames(model, val, crop_box, args.crop_out)
+        extra["crop"] = {"pos": args.crop_pos, "rpy": args.crop_rpy, "scale": args.crop_scale, "frames_written": frames, "out": args.crop_out,
+                         "gaussians_kept_share": float(crop_box.within(model.means.detach()).float().mean()) if model.num_points else 0.0}
     model.train()
     metrics = {k: sum(v) / len(v) for k, v in sums.items() if all(math.isfinite(x) for x in v)}
-    extra = {}
     if model.separate:  # the share of Gaussians whose two opacities ended more than 0.5 apart
         gp = model.gauss_params
         gap = (torch.sigmoid(gp["opacities"]) - torch.sigmoid(gp["opacities_thermal"])).abs()
