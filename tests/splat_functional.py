@@ -187,5 +187,29 @@ def scene(num: int, seed: int, sh_degree: int, extent: float = 1.0, scale_range=
     return p
 
 
+def separate_depths(means: Tensor, c2w: Tensor, min_gap: float = 2.5e-5, fixed: Optional[Tensor] = None) -> Tensor:
+    """`means` (float32) moved along the camera's optical axis until every float64 view-space depth exceeds its predecessor's, in sorted
+    order, by at least `min_gap`: about a hundred float32 ulps of a depth near 2, so that float32 and float64 composite in the same order.
+    fixed [N] bool: Gaussians that stay where they are (bit-equal means: tied depths); the others also keep `min_gap` from those.  The
+    rounding of the moved means to float32 costs a few 1e-7 of depth, which is why tests ask the result for 2e-5 only."""
+    viewmat, _ = so.camera_matrices(c2w, 1.0, 1.0, 2, 2)
+    Rv, tv = viewmat[:3, :3].double(), viewmat[:3, 3].double()
+    m = means.double()
+    d = (m @ Rv.T + tv)[:, 2]
+    fixed = torch.zeros(d.shape[0], dtype=torch.bool) if fixed is None else fixed
+    walls = sorted(d[fixed].tolist())
+    new, prev = d.clone(), -math.inf
+    for i in torch.argsort(d, stable=True).tolist():
+        if bool(fixed[i]):
+            prev = max(prev, float(d[i]))
+            continue
+        t = max(float(d[i]), prev + min_gap)
+        for f in walls:  # ascending, and t only grows: one pass
+            if abs(t - f) < min_gap:
+                t = f + min_gap
+        new[i] = prev = t
+    return (m + (new - d)[:, None] * Rv[2]).float()
+
+
 def fov_focal(W: int, fov_deg: float = 60.0) -> float:
     return 0.5 * W / math.tan(math.radians(0.5 * fov_deg))

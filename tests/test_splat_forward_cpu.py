@@ -33,8 +33,8 @@ def _with(p, **kw):
     return p
 
 
-def _ragged(deg):
-    return sf.scene(1500, 21, deg, scale_range=(-4.0, -2.6))
+def _ragged(deg, num=1500):
+    return sf.scene(num, 21, deg, scale_range=(-4.0, -2.6))
 
 
 def _sliver(deg):
@@ -45,14 +45,14 @@ def _subtile(deg):
     return sf.scene(200, 23, deg, extent=0.4, scale_range=(-3.0, -2.0))
 
 
-def _deep(deg):
-    p = sf.scene(2500, 24, deg, extent=0.6, scale_range=(-2.2, -1.4))
+def _deep(deg, num=2500, extent=0.6):
+    p = sf.scene(num, 24, deg, extent=extent, scale_range=(-2.2, -1.4))
     g = torch.Generator().manual_seed(24)
     return _with(p, opacities=torch.rand(p["opacities"].shape, generator=g) * 1.0 - 4.8)  # sigmoid: 0.008 .. 0.022, all above 1/255
 
 
-def _opaque(deg):
-    p = sf.scene(4500, 21, deg, extent=0.6, scale_range=(-2.6, -1.6))
+def _opaque(deg, num=4500):
+    p = sf.scene(num, 21, deg, extent=0.6, scale_range=(-2.6, -1.6))
     return _with(p, opacities=p["opacities"] * 0.0 + 3.0)
 
 
@@ -155,9 +155,9 @@ def case_scene(case, deg):
     return CASES[case][0](deg)
 
 
-def case_camera(case):
-    """c2w, fx, fy, cx, cy, W, H"""
-    _, W, H, fov, (cx, cy), eye = CASES[case]
+def case_camera(case, cases=None):
+    """c2w, fx, fy, cx, cy, W, H of a row of `cases` (default: CASES)"""
+    _, W, H, fov, (cx, cy), eye = (CASES if cases is None else cases)[case]
     fx = sf.fov_focal(W, fov)
     return so.look_at_camera(eye), fx, fx * 0.97, cx, cy, W, H
 
