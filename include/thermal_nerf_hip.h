@@ -846,6 +846,59 @@ TN_API int tn_splat_project_crop_sep(const TnSplatCamera* camera, const float* m
  * pointers for n > 0 and n outside [0, 2^31). */
 TN_API int tn_splat_crop_mask(const TnSplatCrop* crop, const float* means, int64_t n, uint8_t* mask, tn_stream_t stream);
 
+/* ---- N4 pose refinement: camera-pose gradients of the training render (CameraOptimizer, nerfstudio/cameras/camera_optimizers.py:89-213, as
+ * ThermalNerfactoModel uses it for both spectra, models/thermal_nerfacto.py:132-144).  A pose row p = (t, w) in R^6 -- translation, then the so(3)
+ * vector -- gives A(p) = [R(w) | t] = exp_map_SO3xR3 (cameras/lie_groups.py:24-58, theta = sqrt(clamp(|w|^2, 1e-4))), applied as
+ * c2w' = c2w [A(p); 0 0 0 1] (apply_to_camera, :178-186).  With F = diag(1, -1, -1) and V0 = camera->viewmat that is view' = D V0 with the rigid
+ * D = F A(p)^-1 F.  The pose stays on the device: tn_splat_pose_camera writes the corrected camera into a record of
+ * TN_SPLAT_POSE_CAMERA_FLOATS floats, the _pose entry points read their camera from it.  Record: [0..11] view' (3x4 rows), [12..27] proj' (4x4
+ * rows; row 2 is not read and is 0), [28..30] position' = c2w'[:3, 3] (the SH view directions; a value, no gradient: splatfacto.py:770),
+ * [31] proj_x, [32] proj_y, the rest 0.  Everything additive: no other entry point changes.
+ *
+ * tn_splat_pose_camera: camera = the frame's camera as without a pose; proj_x, proj_y = entries [0][0] and [1][1] of
+ * projection_matrix(0.001, 1000, fovx, fovy) (the intrinsic part of camera->projmat: proj' rows 0, 1, 3 = proj_x view'[0], proj_y view'[1],
+ * view'[2]); pose_row [6] and pose_camera [TN_SPLAT_POSE_CAMERA_FLOATS] are DEVICE pointers.  One launch, nothing read back.  With a zero row every
+ * number of the record equals the corresponding number of `camera` (D is exactly the identity and zero terms are skipped, not added). */
+#define TN_SPLAT_POSE_CAMERA_FLOATS 40
+TN_API int tn_splat_pose_camera(const TnSplatCamera* camera, float proj_x, float proj_y, const float* pose_row, float* pose_camera, tn_stream_t stream);
+/* tn_splat_project / tn_splat_project_sep with view, projection rows and position taken from pose_camera (the pose instantiation of the same
+ * kernel; camera still gives the intrinsics, the clip threshold and the image size).  crop: a box as tn_splat_project_crop takes it, or null. */
+TN_API int tn_splat_project_pose(const TnSplatCamera* camera, const float* pose_camera, const float* means, const float* log_scales, const float* quats,
+                                 const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
+                                 const float* thermal_rest, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased,
+                                 float* xys, float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box,
+                                 void* workspace, int64_t max_intersections, const TnSplatCrop* crop, tn_stream_t stream);
+TN_API int tn_splat_project_pose_sep(const TnSplatCamera* camera, const float* pose_camera, const float* means, const float* log_scales,
+                                     const float* quats, const float* opacities, const float* features_dc, const float* features_rest,
+                                     const float* thermal_dc, const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians,
+                                     int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys, float* depths, int32_t* radii,
+                                     float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
+                                     int64_t max_intersections, const TnSplatCrop* crop, tn_stream_t stream);
+/* scratch of the pose backward: one partial sum of dL/d view' (12 doubles) per block of 256 Gaussians; -1 on a bad count */
+TN_API int64_t tn_splat_pose_workspace_bytes(int64_t num_gaussians);
+/* tn_splat_project_backward / _sep for a frame projected with tn_splat_project_pose / _sep (the same record, and the row it was made from), plus
+ * the pose gradient: every Gaussian with radii > 0 contributes to dL/d view' through its view-space point (frustum clamp included), the
+ * covariance's T = J W and the projection rows xys reads; the 12 sums are reduced per wave, per block (double) and over the blocks in block
+ * order -- no float atomics, bit-reproducible -- and chained through D to the row.  The result is ADDED to grad_pose_row [6] (the caller's row
+ * of a zeroed or accumulating grad_pose [C,6]); dview_out [12] (may be null) receives dL/d view'.  workspace: tn_splat_pose_workspace_bytes. */
+TN_API int tn_splat_project_backward_pose(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
+                                          const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
+                                          const float* features_rest, const float* thermal_dc, const float* thermal_rest, int64_t num_gaussians,
+                                          int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, const int32_t* radii, const float* v_xys,
+                                          const float* v_conics, const float* v_colors, const float* v_log_opacity, float* v_means, float* v_log_scales,
+                                          float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest, float* v_thermal_dc,
+                                          float* v_thermal_rest, void* workspace, int64_t workspace_bytes, float* grad_pose_row, float* dview_out,
+                                          tn_stream_t stream);
+TN_API int tn_splat_project_backward_pose_sep(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
+                                              const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
+                                              const float* features_rest, const float* thermal_dc, const float* thermal_rest,
+                                              const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
+                                              int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics,
+                                              const float* v_colors, const float* v_log_opacity, const float* v_log_opacity_thermal, float* v_means,
+                                              float* v_log_scales, float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest,
+                                              float* v_thermal_dc, float* v_thermal_rest, float* v_opacities_thermal, void* workspace,
+                                              int64_t workspace_bytes, float* grad_pose_row, float* dview_out, tn_stream_t stream);
+
 /* ---- N4 training loss: splatfacto's (1 - ssim_lambda) * L1 + ssim_lambda * (1 - SSIM) (nerfstudio/models/splatfacto.py:863-903), SSIM as
  * pytorch_msssim computes it: an 11-tap Gaussian window (sigma 1.5) applied separably as a VALID correlation, C1 = 0.01^2, C2 = 0.03^2 (data
  * range 1), mean over the (H-10) x (W-10) valid pixels and the channels.  L1 = mean |pred - gt| over all H W C values.  Deterministic: no

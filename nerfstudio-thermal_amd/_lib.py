@@ -17,6 +17,7 @@ TN_MAX_SAMPLES = 256
 TN_RENDER_SCRATCH_FLOATS = 4096
 TN_LOSS_LINES = 64
 TN_RENDER_TRAIN_OFFSETS = 25
+TN_SPLAT_POSE_CAMERA_FLOATS = 40  # the corrected-camera record of tn_splat_pose_camera
 TN_IMAGE_F32, TN_IMAGE_U8 = 0, 1  # tn_image_resize's input types, tn_image_undistort's input and output types
 TN_BWD_MLP, TN_BWD_SCATTER, TN_BWD_JOIN, TN_BWD_SCATTER_BIN, TN_BWD_SCATTER_FOLD, TN_BWD_FORK_DPOS, TN_BWD_COUNTERS_CLEAN = 1, 2, 4, 8, 16, 32, 64
 
@@ -217,6 +218,13 @@ SIGNATURES = {
     "tn_splat_project_crop": (C.c_int, [_p] * 9 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, C.POINTER(TnSplatCrop), _p]),
     "tn_splat_project_crop_sep": (C.c_int, [_p] * 10 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, C.POINTER(TnSplatCrop), _p]),
     "tn_splat_crop_mask": (C.c_int, [C.POINTER(TnSplatCrop), _p, _i64, _p, _p]),
+    # pose refinement: the corrected camera as a device record, the projection entry points that read it, the pose gradient
+    "tn_splat_pose_camera": (C.c_int, [_p, _f, _f, _p, _p, _p]),
+    "tn_splat_project_pose": (C.c_int, [_p] * 10 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, C.POINTER(TnSplatCrop), _p]),
+    "tn_splat_project_pose_sep": (C.c_int, [_p] * 11 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, C.POINTER(TnSplatCrop), _p]),
+    "tn_splat_pose_workspace_bytes": (_i64, [_i64]),
+    "tn_splat_project_backward_pose": (C.c_int, [_p] * 11 + [_i64, _i32, _i32, _i32] + [_p] * 14 + [_i64, _p, _p, _p]),
+    "tn_splat_project_backward_pose_sep": (C.c_int, [_p] * 12 + [_i64, _i32, _i32, _i32] + [_p] * 16 + [_i64, _p, _p, _p]),
     "tn_image_loss_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "tn_image_loss": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _f, _f, _p, _i64, _p, _p, _p]),
     "tn_image_resize": (C.c_int, [_p, _i32, _i64, _i32, _i32, _i32, _p, _i32, _i32, _p]),

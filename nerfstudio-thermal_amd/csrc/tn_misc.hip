@@ -413,30 +413,7 @@ extern "C" int tn_sample_rays_args(const TnSampleRays* s, tn_stream_t stream) {
 }
 
 // ------------------------------------------------------------------------------------------------ pose correction
-struct Pose {
-  float R[9];
-  float t[3];
-};
-// exp_map_SO3xR3 (cameras/lie_groups.py:24-58)
-__device__ __forceinline__ Pose pose_exp(const float* __restrict__ p) {
-  Pose o;
-  float v0 = p[3], v1 = p[4], v2 = p[5];
-  float n = v0 * v0 + v1 * v1 + v2 * v2;
-  float ang = sqrtf(fmaxf(n, 1e-4f));
-  float inv = 1.0f / ang;
-  float f1 = inv * sinf(ang);
-  float f2 = inv * inv * (1.0f - cosf(ang));
-  float K[9] = {0.f, -v2, v1, v2, 0.f, -v0, -v1, v0, 0.f};
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      float kk = K[i * 3 + 0] * K[0 * 3 + j] + K[i * 3 + 1] * K[1 * 3 + j] + K[i * 3 + 2] * K[2 * 3 + j];
-      o.R[i * 3 + j] = f1 * K[i * 3 + j] + f2 * kk + (i == j ? 1.0f : 0.0f);
-    }
-  o.t[0] = p[0]; o.t[1] = p[1]; o.t[2] = p[2];
-  return o;
-}
+// (Pose, pose_exp -- exp_map_SO3xR3 -- and its derivative pose_exp_bwd: tn_pose_finish.h)
 
 // one ray: prow = the camera's pose row, is_frozen = a non-trainable camera (identity)
 __device__ __forceinline__ void pose_apply_ray(const float (&prow)[6], bool is_frozen, float ox, float oy, float oz, float dx, float dy, float dz,

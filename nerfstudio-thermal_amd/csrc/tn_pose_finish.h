@@ -5,9 +5,69 @@
 #pragma once
 #include "tn_common.h"
 
+// The pose map and its derivative, each written once: the ray path (tn_misc.hip, below) and the splat path (tn_splat.hip) both call them.
+struct Pose {
+  float R[9];
+  float t[3];
+};
+// exp_map_SO3xR3 (cameras/lie_groups.py:24-58)
+__device__ __forceinline__ Pose pose_exp(const float* __restrict__ p) {
+  Pose o;
+  float v0 = p[3], v1 = p[4], v2 = p[5];
+  float n = v0 * v0 + v1 * v1 + v2 * v2;
+  float ang = sqrtf(fmaxf(n, 1e-4f));
+  float inv = 1.0f / ang;
+  float f1 = inv * sinf(ang);
+  float f2 = inv * inv * (1.0f - cosf(ang));
+  float K[9] = {0.f, -v2, v1, v2, 0.f, -v0, -v1, v0, 0.f};
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      float kk = K[i * 3 + 0] * K[0 * 3 + j] + K[i * 3 + 1] * K[1 * 3 + j] + K[i * 3 + 2] * K[2 * 3 + j];
+      o.R[i * 3 + j] = f1 * K[i * 3 + j] + f2 * kk + (i == j ? 1.0f : 0.0f);
+    }
+  o.t[0] = p[0]; o.t[1] = p[1]; o.t[2] = p[2];
+  return o;
+}
+
 // backward:  R = I + f1 K + f2 K^2, K = skew(v), K^2 = v v^T - |v|^2 I, theta = sqrt(clamp(|v|^2, 1e-4))
-//   G = g_d (outer) d_in ;  dL/dt = g_o
+//   G = dL/dR (the ray path: g_d (outer) d_in) ;  dL/dt = g_o
 //   dL/dv_m = f1 * skewpart(G)_m + f2 * ((G + G^T) v - 2 v tr G)_m + (<G,K> f1' + <G,K^2> f2') * dtheta/dn * 2 v_m
+// PoseExpFactors: what the derivative needs of w alone; pose_exp_bwd: v = the so(3) part of the pose row, G = dL/dR row-major -> out = dL/dv
+struct PoseExpFactors {
+  float n, f1, f2, df1, df2, dth_dn;
+};
+__device__ __forceinline__ PoseExpFactors pose_exp_factors(const float (&v)[3]) {
+  float n = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+  float th = sqrtf(fmaxf(n, 1e-4f));
+  float sn = sinf(th), cs = cosf(th);
+  float f1 = sn / th, f2 = (1.0f - cs) / (th * th);
+  float df1 = (th * cs - sn) / (th * th);
+  float df2 = (th * sn - 2.0f * (1.0f - cs)) / (th * th * th);
+  float dth_dn = (n >= 1e-4f) ? 0.5f / th : 0.0f;
+  return PoseExpFactors{n, f1, f2, df1, df2, dth_dn};
+}
+__device__ __forceinline__ void pose_exp_bwd(const float (&v)[3], const PoseExpFactors& e, const float (&G)[9], float (&out)[3]) {
+  const float n = e.n, f1 = e.f1, f2 = e.f2, df1 = e.df1, df2 = e.df2, dth_dn = e.dth_dn;
+  float K[9] = {0.f, -v[2], v[1], v[2], 0.f, -v[0], -v[1], v[0], 0.f};
+  float GK = 0.f, GK2 = 0.f, tr = G[0] + G[4] + G[8];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      GK += G[a * 3 + b] * K[a * 3 + b];
+      GK2 += G[a * 3 + b] * (v[a] * v[b] - (a == b ? n : 0.0f));
+    }
+  float sk[3] = {G[2 * 3 + 1] - G[1 * 3 + 2], G[0 * 3 + 2] - G[2 * 3 + 0], G[1 * 3 + 0] - G[0 * 3 + 1]};
+  float common = (GK * df1 + GK2 * df2) * dth_dn * 2.0f;
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    float Gv = G[m * 3] * v[0] + G[m * 3 + 1] * v[1] + G[m * 3 + 2] * v[2];
+    float Gtv = G[m] * v[0] + G[3 + m] * v[1] + G[6 + m] * v[2];
+    out[m] = f1 * sk[m] + f2 * (Gv + Gtv - 2.0f * v[m] * tr) + common * v[m];
+  }
+}
 __device__ __forceinline__ void pose_bwd_body(const float* __restrict__ pose, const uint8_t* __restrict__ frozen, const int64_t* __restrict__ cam_idx,
                                               const float* __restrict__ d_in, const float* __restrict__ g_o, const float* __restrict__ g_d, int64_t N,
                                               int C, float* __restrict__ grad_pose, int bid, int nblk, float* __restrict__ nonfinite = nullptr) {
@@ -25,13 +85,7 @@ __device__ __forceinline__ void pose_bwd_body(const float* __restrict__ pose, co
     if (live && !(frozen != nullptr && frozen[cam])) {
       const float* p = pose + cam * 6;
       float v[3] = {p[3], p[4], p[5]};
-      float n = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-      float th = sqrtf(fmaxf(n, 1e-4f));
-      float sn = sinf(th), cs = cosf(th);
-      float f1 = sn / th, f2 = (1.0f - cs) / (th * th);
-      float df1 = (th * cs - sn) / (th * th);
-      float df2 = (th * sn - 2.0f * (1.0f - cs)) / (th * th * th);
-      float dth_dn = (n >= 1e-4f) ? 0.5f / th : 0.0f;
+      const PoseExpFactors e = pose_exp_factors(v);
       float gd[3] = {g_d[ii * 3], g_d[ii * 3 + 1], g_d[ii * 3 + 2]};
       float dd[3] = {d_in[ii * 3], d_in[ii * 3 + 1], d_in[ii * 3 + 2]};
       float G[9];
@@ -39,22 +93,11 @@ __device__ __forceinline__ void pose_bwd_body(const float* __restrict__ pose, co
       for (int a = 0; a < 3; ++a)
 #pragma unroll
         for (int b = 0; b < 3; ++b) G[a * 3 + b] = gd[a] * dd[b];
-      float K[9] = {0.f, -v[2], v[1], v[2], 0.f, -v[0], -v[1], v[0], 0.f};
-      float GK = 0.f, GK2 = 0.f, tr = G[0] + G[4] + G[8];
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-          GK += G[a * 3 + b] * K[a * 3 + b];
-          GK2 += G[a * 3 + b] * (v[a] * v[b] - (a == b ? n : 0.0f));
-        }
-      float sk[3] = {G[2 * 3 + 1] - G[1 * 3 + 2], G[0 * 3 + 2] - G[2 * 3 + 0], G[1 * 3 + 0] - G[0 * 3 + 1]};
-      float common = (GK * df1 + GK2 * df2) * dth_dn * 2.0f;
+      float dv[3];
+      pose_exp_bwd(v, e, G, dv);
 #pragma unroll
       for (int m = 0; m < 3; ++m) {
-        float Gv = G[m * 3] * v[0] + G[m * 3 + 1] * v[1] + G[m * 3 + 2] * v[2];
-        float Gtv = G[m] * v[0] + G[3 + m] * v[1] + G[6 + m] * v[2];
-        out[3 + m] = f1 * sk[m] + f2 * (Gv + Gtv - 2.0f * v[m] * tr) + common * v[m];
+        out[3 + m] = dv[m];
         out[m] = g_o[ii * 3 + m];
       }
     }

@@ -24,10 +24,12 @@
 //                      opacity, so that variant carries a second transmittance).  The TRAIN instantiation (tn_splat_raster_train) also
 //                      keeps each pixel's final transmittance and last contributor for the backward.
 #include <cstring>
+#include <type_traits>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
 #include "tn_common.h"
+#include "tn_pose_finish.h"  // pose_exp / pose_exp_bwd: the pose map and its derivative, shared with the ray path
 
 #define SPLAT_BLOCK 16
 #define SPLAT_BATCH 256
@@ -147,6 +149,41 @@ __device__ __forceinline__ auto pack_arg(T t, R... r) {
   else return pack_arg<I - 1>(r...);
 }
 
+// pack_has<T> / pack_get<T>: whether the pack holds an argument of type T, and that argument.
+template <typename T, typename... R>
+inline constexpr bool pack_has = (std::is_same_v<T, R> || ...);
+template <typename T, typename A, typename... R>
+__device__ __forceinline__ T pack_get(A a, R... r) {
+  if constexpr (std::is_same_v<T, A>) return a;
+  else return pack_get<T>(r...);
+}
+
+// Pose refinement (CameraOptimizer.apply_to_camera, cameras/camera_optimizers.py:178-186: c2w' = c2w [A(p); 0 0 0 1], A = exp_map_SO3xR3).  In the
+// rasteriser's convention (F = diag(1, -1, -1), V0 = the view matrix of the TnSplatCamera) that is V' = D V0 with the rigid D = F A(p)^-1 F.
+// k_splat_pose_camera writes the corrected camera as a RECORD of SPLAT_POSE_REC floats in device memory -- laid out as SplatCamK begins -- and the
+// pose instantiations of the projection kernels (a SplatPoseK / SplatPoseBwdK in their trailing pack) read their camera from it instead of from
+// their by-value SplatCamK: the pose never travels to the host.
+//   [0..11] view' (3x4 rows)   [12..27] proj' (4x4 rows; row 2 is not read and stays 0)   [28..30] position'   [31] proj_x   [32] proj_y
+// proj_x / proj_y: the two entries of the intrinsic part of projection_matrix the kernels' rows depend on (row 0 = proj_x view'[0], row 1 =
+// proj_y view'[1], row 3 = view'[2]: one product each).
+#define SPLAT_POSE_REC 40
+static_assert(SPLAT_POSE_REC == TN_SPLAT_POSE_CAMERA_FLOATS, "the header documents the record's size");
+struct SplatPoseK {
+  const float* rec;
+};
+struct SplatPoseBwdK {
+  const float* rec;
+  double* partial;  // [blocks][12]: every block's sum of dL/d view'
+};
+__device__ __forceinline__ void splat_pose_load(SplatCamK& cam, const float* __restrict__ rec) {
+#pragma unroll
+  for (int i = 0; i < 12; ++i) cam.view[i] = rec[i];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) cam.proj[i] = rec[12 + i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) cam.pos[i] = rec[28 + i];
+}
+
 // The crop box of the eval render (OrientedBox: splatfacto.py:690-698, scene_box.py:82-114): m = rows of the 3x4 world -> box matrix
 // inverse([R|T]), h = S / 2.  A point p is inside iff |q_i| < h_i on all three axes (strict on both sides; h_i <= 0 or a NaN keeps nothing) with
 //   q_i = ((m[4i] * p.x + m[4i+1] * p.y) + m[4i+2] * p.z) + m[4i+3]
@@ -172,6 +209,7 @@ __device__ __forceinline__ bool splat_in_crop(const SplatCropK& c, float x, floa
 // the clip plane does -- radius 0, no tiles, zeros -- and never reaches the sort; a block whose Gaussians are ALL outside (one block-wide vote, taken
 // by every thread before the barrier below, so the decision is uniform there) does not stage its SH slab -- 240 of the 300 bytes a Gaussian has at
 // degree 3.  Without the pack the kernel is the one it was.
+// Pose (one SplatPoseK, or nothing; with or without the box): view, projection rows and position come from the device record (uniform loads).
 template <bool SEP, typename... Crop>
 __global__ void __launch_bounds__(256) k_splat_project(SplatCamK cam, const float* __restrict__ means, const float* __restrict__ log_scales,
                                                        const float* __restrict__ quats, const float* __restrict__ opac_logit,
@@ -182,8 +220,9 @@ __global__ void __launch_bounds__(256) k_splat_project(SplatCamK cam, const floa
                                                        int32_t* __restrict__ tiles_hit, int32_t* __restrict__ tile_box, SplatRec* __restrict__ recs,
                                                        int32_t* __restrict__ tbox, int32_t* __restrict__ thits,
                                                        const float* __restrict__ opac_th_logit, Crop... crop_arg) {
-  static_assert(sizeof...(Crop) <= 1, "the crop instantiation takes one SplatCropK");
-  constexpr bool CROP = sizeof...(Crop) == 1;
+  constexpr bool CROP = pack_has<SplatCropK, Crop...>, POSE = pack_has<SplatPoseK, Crop...>;
+  static_assert(sizeof...(Crop) == (CROP ? 1 : 0) + (POSE ? 1 : 0), "the pack takes one SplatCropK, one SplatPoseK, or both");
+  if constexpr (POSE) splat_pose_load(cam, pack_get<SplatPoseK>(crop_arg...).rec);
   // The higher-order SH coefficients of the block's 256 Gaussians (45 + 15 floats each) go through LDS: the block copies its contiguous
   // 46 KB + 15 KB slab with coalesced 16-byte loads, and each thread then reads its own coefficients at stride 45 / 15 floats -- odd strides,
   // so the 64 lanes of a wave hit 64 different banks.  Reading them straight from global memory (each lane its own 180-byte run) cost
@@ -197,7 +236,7 @@ __global__ void __launch_bounds__(256) k_splat_project(SplatCamK cam, const floa
     const int cnt = (int)min((int64_t)blockDim.x, N - g0);
     bool stage = rest_coeffs > 0 && sh_degree >= 1;
     if constexpr (CROP) {
-      const SplatCropK crop = pack_arg<0>(crop_arg...);
+      const SplatCropK crop = pack_get<SplatCropK>(crop_arg...);
       const int64_t g = g0 + threadIdx.x;
       in_box = g < N && splat_in_crop(crop, means[3 * g], means[3 * g + 1], means[3 * g + 2]);
       // The vote: one block-wide OR, a barrier that hands every thread the same answer, so `stage` is uniform over the block before the staging
@@ -971,8 +1010,30 @@ __device__ __forceinline__ void sh_basis(int degree, float x, float y, float z, 
   b[14] = 1.445305721320277f * z * (xx - yy); b[15] = -0.5900435899266435f * x * (xx - 3.0f * yy);
 }
 
+// The sums over a wave of 16 values per lane with 17 exchanges instead of 16 x 6: a butterfly that halves what a lane holds at each of the first
+// four steps -- the lane whose bit `o` is clear keeps the lower half of its values and hands the upper half to its partner, which keeps that half
+// -- so after offsets 32, 16, 8, 4 a lane holds ONE component, k = lane >> 2, summed over the 16 lanes that share its two low bits; offsets 2 and
+// 1 finish it.  Returns component lane >> 2 (in all four lanes of a quad).  A fixed tree: the same inputs give the same bits.
+__device__ __forceinline__ double splat_wave_sum16(double (&v)[16], int lane) {
+#pragma unroll
+  for (int h = 8, o = 32; h >= 1; h >>= 1, o >>= 1) {
+    const bool up = (lane & o) != 0;
+#pragma unroll
+    for (int j = 0; j < h; ++j) {
+      const double keep = up ? v[h + j] : v[j], send = up ? v[j] : v[h + j];
+      v[j] = keep + __shfl_xor(send, o, 64);
+    }
+  }
+  v[0] += __shfl_xor(v[0], 2, 64);
+  v[0] += __shfl_xor(v[0], 1, 64);
+  return v[0];
+}
+
 // SEP: also d thermal-opacity logit (g_opac_th) from v_lnop_th = d ln(thermal opacity); in antialiased mode the compensation takes both
-template <bool SEP>
+// Pose (one SplatPoseBwdK, or nothing -- then the kernel is the one it was): the camera comes from the device record, and every Gaussian with
+// radii > 0 also contributes to dL/d view' [3,4] through the view-space point (gpx, gpy, gpz, frustum-clamp branches included), T = J W and the
+// projection rows xys reads.  The 12 numbers are summed per wave (splat_wave_sum16) and per block (LDS) in double and leave as ONE partial per block; no atomics.
+template <bool SEP, typename... Pose>
 __global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const float* __restrict__ means, const float* __restrict__ log_scales,
                                                            const float* __restrict__ quats, const float* __restrict__ opac_logit,
                                                            const float* __restrict__ f_dc, const float* __restrict__ f_rest, const float* __restrict__ t_dc,
@@ -983,14 +1044,28 @@ __global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const 
                                                            float* __restrict__ g_quats, float* __restrict__ g_opac, float* __restrict__ g_fdc,
                                                            float* __restrict__ g_frest, float* __restrict__ g_tdc, float* __restrict__ g_trest,
                                                            const float* __restrict__ opac_th_logit, const float* __restrict__ v_lnop_th,
-                                                           float* __restrict__ g_opac_th) {
+                                                           float* __restrict__ g_opac_th, Pose... pose_arg) {
+  constexpr bool POSE = pack_has<SplatPoseBwdK, Pose...>;
+  static_assert(sizeof...(Pose) == (POSE ? 1 : 0), "the pose instantiation takes one SplatPoseBwdK");
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= N) return;
+  [[maybe_unused]] const bool live = i < N;  // (pose: the tail's threads stay for the block's reduction)
+  [[maybe_unused]] float dV[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  [[maybe_unused]] float proj_x = 0.f, proj_y = 0.f;
+  if constexpr (POSE) {
+    const float* rec = pack_get<SplatPoseBwdK>(pose_arg...).rec;
+    splat_pose_load(cam, rec);
+    proj_x = rec[31]; proj_y = rec[32];
+  } else {
+    if (i >= N) return;
+  }
   float gm[3] = {0.f, 0.f, 0.f}, gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f}, gop = 0.f, gop_t = 0.f;
   float gcol[4] = {0.f, 0.f, 0.f, 0.f};  // d (colour before the clamp / sigmoid argument), per channel
   float basis[16];
   int nb = 0;
-  if (radii[i] > 0) {  // Gaussians the forward culled get no gradient
+  bool visible;
+  if constexpr (POSE) visible = live && radii[i] > 0;
+  else visible = radii[i] > 0;
+  if (visible) {  // Gaussians the forward culled get no gradient
     const float mx = means[3 * i], my = means[3 * i + 1], mz = means[3 * i + 2];
     const float* V = cam.view;
     const float px = V[0] * mx + V[1] * my + V[2] * mz + V[3];
@@ -1097,6 +1172,22 @@ __global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const 
     const float g_hw = -(vx * 0.5f * (float)cam.W * hx + vy * 0.5f * (float)cam.H * hy) * rw * rw;
 #pragma unroll
     for (int cc = 0; cc < 3; ++cc) gm[cc] += P[cc] * g_hx + P[4 + cc] * g_hy + P[12 + cc] * g_hw;
+    if constexpr (POSE) {
+      const float mh[4] = {mx, my, mz, 1.0f};
+      const float ax = proj_x * g_hx, ay = proj_y * g_hy;  // proj row 0 = proj_x view'[0], row 1 = proj_y view'[1], row 3 = view'[2]
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc) {
+        dV[cc] = gpx * mh[cc] + ax * mh[cc];
+        dV[4 + cc] = gpy * mh[cc] + ay * mh[cc];
+        dV[8 + cc] = gpz * mh[cc] + g_hw * mh[cc];
+      }
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc) {  // T = J W: T0 = J0[0] W[0] + J0[2] W[2], T1 = J1[1] W[1] + J1[2] W[2]
+        dV[cc] += gT0[cc] * J0[0];
+        dV[4 + cc] += gT1[cc] * J1[1];
+        dV[8 + cc] += gT0[cc] * J0[2] + gT1[cc] * J1[2];
+      }
+    }
     // Sigma = M M^T, M = R diag(s): d M = (G + G^T) M
     float gR[9];
 #pragma unroll
@@ -1141,6 +1232,20 @@ __global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const 
       gcol[3] = vcol[3] * sg * (1.0f - sg);
     }
   }
+  if constexpr (POSE) {
+    __shared__ double s_part[4][12];  // blockDim.x == 256: four waves
+    const int lane = tn_lane(), wv = threadIdx.x >> 6;
+    double v[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = k < 12 ? (double)dV[k] : 0.0;
+    const double w = splat_wave_sum16(v, lane);
+    if ((lane & 3) == 0 && lane < 48) s_part[wv][lane >> 2] = w;
+    __syncthreads();
+    if (threadIdx.x < 12)
+      pack_get<SplatPoseBwdK>(pose_arg...).partial[(int64_t)blockIdx.x * 12 + threadIdx.x] =
+          ((s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + s_part[2][threadIdx.x]) + s_part[3][threadIdx.x];
+    if (!live) return;
+  }
 #pragma unroll
   for (int cc = 0; cc < 3; ++cc) { g_means[3 * i + cc] = gm[cc]; g_scales[3 * i + cc] = gs[cc]; }
 #pragma unroll
@@ -1156,6 +1261,113 @@ __global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const 
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) g_frest[(i * rest_coeffs + (k - 1)) * 3 + ch] = bk * gcol[ch];
     g_trest[i * rest_coeffs + (k - 1)] = bk * gcol[3];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ pose refinement
+// sum of the terms c_k x_k (+ add) whose coefficient c_k (add) is not zero, first term first: with the coefficients of an identity transform the
+// result IS the one x_k (or add) that remains, bit for bit -- no 1 * x + 0 * y + 0 * z, whose zero products can still flip the sign of a zero.
+__device__ __forceinline__ float pose_dot_skip0(float c0, float x0, float c1, float x1, float c2, float x2, float add) {
+  float acc = 0.0f;
+  bool have = false;
+  const float c[3] = {c0, c1, c2}, x[3] = {x0, x1, x2};
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    if (c[k] != 0.0f) {
+      const float t = c[k] * x[k];
+      acc = have ? acc + t : t;
+      have = true;
+    }
+  if (add != 0.0f) acc = have ? acc + add : add;
+  return acc;
+}
+
+// The corrected camera of one frame: cam = the frame's camera as the host built it (view V0, position), pose = the frame's row (t, w) on the
+// device -> rec (layout above SplatPoseK).  One thread; A(p) = [R | t] = pose_exp.  D = F A^-1 F = [D_R | D_t], D_R[i][j] = f_i f_j R[j][i],
+// D_t[i] = -f_i sum_j R[j][i] t[j]; view' = [D_R R0 | D_R T0 + D_t]; position' = c2w' [:3, 3] = Rc t + position with Rc[i][j] = f_j R0[j][i].
+// With a zero row D is exactly the identity and every number written equals the host struct's (its projmat rows being single products too).
+__global__ void k_splat_pose_camera(SplatCamK cam, float proj_x, float proj_y, const float* __restrict__ pose, float* __restrict__ rec) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const Pose a = pose_exp(pose);
+  const float f[3] = {1.0f, -1.0f, -1.0f};
+  float DR[9], Dt[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) DR[3 * i + j] = f[i] * f[j] * a.R[3 * j + i];
+    Dt[i] = -f[i] * pose_dot_skip0(a.t[0], a.R[i], a.t[1], a.R[3 + i], a.t[2], a.R[6 + i], 0.0f);
+  }
+  const float* V0 = cam.view;
+  float V[12];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      V[4 * i + j] = pose_dot_skip0(DR[3 * i], V0[j], DR[3 * i + 1], V0[4 + j], DR[3 * i + 2], V0[8 + j], j == 3 ? Dt[i] : 0.0f);
+#pragma unroll
+  for (int j = 0; j < 12; ++j) rec[j] = V[j];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    rec[12 + j] = proj_x * V[j];
+    rec[16 + j] = proj_y * V[4 + j];
+    rec[20 + j] = 0.0f;
+    rec[24 + j] = V[8 + j];
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    rec[28 + i] = pose_dot_skip0(a.t[0], f[0] * V0[i], a.t[1], f[1] * V0[4 + i], a.t[2], f[2] * V0[8 + i], cam.pos[i]);
+  rec[31] = proj_x; rec[32] = proj_y;
+#pragma unroll
+  for (int j = 33; j < SPLAT_POSE_REC; ++j) rec[j] = 0.0f;
+}
+
+// Ends the pose backward: one block.  12 components x SPLAT_POSE_SEGS segments of consecutive blocks are folded in block order, the segment sums in
+// segment order (double; the association depends on the block count alone), then thread 0 chains dL/d view' -> dL/dD -> dL/d(t, w):
+//   dD_R = dV'_R R0^T + dV'_t T0^T, dD_t = dV'_t;  G = dL/dR: G[j][i] = f_i f_j dD_R[i][j] - f_i dD_t[i] t[j];  dL/dt[j] = -sum_i f_i dD_t[i] R[j][i];
+//   dL/dw = pose_exp_bwd(w, G), the derivative the ray path uses.  The result is ADDED to grad_row[6]; dview_out [12] (optional) gets dL/d view'.
+#define SPLAT_POSE_SEGS 16
+__global__ void __launch_bounds__(12 * SPLAT_POSE_SEGS) k_splat_pose_finish(SplatCamK cam, const float* __restrict__ pose, const double* __restrict__ partial,
+                                                                            int nblk, float* __restrict__ grad_row, float* __restrict__ dview_out) {
+  __shared__ double s_seg[SPLAT_POSE_SEGS][12];
+  __shared__ double s_dv[12];
+  const int k = threadIdx.x % 12, seg = threadIdx.x / 12;
+  const int per = (nblk + SPLAT_POSE_SEGS - 1) / SPLAT_POSE_SEGS;
+  const int b0 = seg * per, b1 = min(nblk, b0 + per);
+  double acc = 0.0;
+  for (int b = b0; b < b1; ++b) acc += partial[(int64_t)b * 12 + k];
+  s_seg[seg][k] = acc;
+  __syncthreads();
+  if (threadIdx.x < 12) {
+    double t = 0.0;
+    for (int q = 0; q < SPLAT_POSE_SEGS; ++q) t += s_seg[q][threadIdx.x];
+    s_dv[threadIdx.x] = t;
+    if (dview_out != nullptr) dview_out[threadIdx.x] = (float)t;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const Pose a = pose_exp(pose);
+  const double f[3] = {1.0, -1.0, -1.0};
+  const float* V0 = cam.view;
+  float G[9];
+  double dt[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double dDt = s_dv[4 * i + 3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double dDR = ((s_dv[4 * i] * (double)V0[4 * j] + s_dv[4 * i + 1] * (double)V0[4 * j + 1]) + s_dv[4 * i + 2] * (double)V0[4 * j + 2]) +
+                         dDt * (double)V0[4 * j + 3];
+      G[3 * j + i] = (float)(f[i] * f[j] * dDR - f[i] * dDt * (double)a.t[j]);
+      dt[j] -= f[i] * dDt * (double)a.R[3 * j + i];
+    }
+  }
+  const float w[3] = {pose[3], pose[4], pose[5]};
+  float dw[3];
+  pose_exp_bwd(w, pose_exp_factors(w), G, dw);
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    grad_row[m] += (float)dt[m];
+    grad_row[3 + m] += dw[m];
   }
 }
 
@@ -1187,7 +1399,7 @@ static SplatCropK make_cropk(const TnSplatCrop* crop) {
 
 // The _sep entry points (separate thermal opacity) share their implementation with the entry points they extend: `sep` picks the SEP
 // instantiation of the kernels, and the thermal-opacity pointers, null in shared mode, are then required.  `who` names the entry point in messages.
-static int splat_project(const char* who, bool sep, const TnSplatCrop* crop, const TnSplatCamera* camera, const float* means, const float* log_scales,
+static int splat_project(const char* who, bool sep, const TnSplatCrop* crop, const float* pose_rec, const TnSplatCamera* camera, const float* means, const float* log_scales,
                          const float* quats, const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
                          const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
                          int32_t antialiased, float* xys, float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit,
@@ -1209,6 +1421,20 @@ static int splat_project(const char* who, bool sep, const TnSplatCrop* crop, con
   const int PB = 128;  // Gaussians per block: 30 KB of LDS at degree 3 -> 5 blocks per CU (256 per block = 61 KB = 2 blocks: 136 vs 1xx us)
   const size_t lds = (size_t)PB * num_rest_coeffs * 4 * sizeof(float);
   TN_REQUIRE(lds <= (crop ? 65536 - 256 : 65536), "%s: %d higher-order coefficients do not fit the LDS staging", who, num_rest_coeffs);  // 256 B of static LDS: the words of __syncthreads_or
+  if (pose_rec) {  // the pose instantiations: the camera comes from the device record (with or without the box)
+    const SplatPoseK pk{pose_rec};
+    auto launch = [&](auto kernel, auto... extra) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)tn_cdiv(num_gaussians, PB)), dim3(PB), lds, tn_s(stream), k, means, log_scales, quats, opacities, features_dc,
+                         features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, (float2*)xys, depths, radii, conics,
+                         compensation, num_tiles_hit, tile_box, ws.recs, ws.tbox, ws.thits, opacities_thermal, extra...);
+    };
+    if (crop && sep) launch(k_splat_project<true, SplatCropK, SplatPoseK>, make_cropk(crop), pk);
+    else if (crop) launch(k_splat_project<false, SplatCropK, SplatPoseK>, make_cropk(crop), pk);
+    else if (sep) launch(k_splat_project<true, SplatPoseK>, pk);
+    else launch(k_splat_project<false, SplatPoseK>, pk);
+    TN_CHECK_LAUNCH(who);
+    return TN_OK;
+  }
   if (crop) {  // the crop instantiation: the same launch plus the box
     hipLaunchKernelGGL((sep ? k_splat_project<true, SplatCropK> : k_splat_project<false, SplatCropK>), dim3((unsigned)tn_cdiv(num_gaussians, PB)), dim3(PB), lds,
                        tn_s(stream), k, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree,
@@ -1229,7 +1455,7 @@ extern "C" int tn_splat_project(const TnSplatCamera* camera, const float* means,
                                 int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys, float* depths,
                                 int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
                                 int64_t max_intersections, tn_stream_t stream) {
-  return splat_project("tn_splat_project", false, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
+  return splat_project("tn_splat_project", false, nullptr, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
                        nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation, num_tiles_hit, tile_box,
                        workspace, max_intersections, stream);
 }
@@ -1239,7 +1465,7 @@ extern "C" int tn_splat_project_sep(const TnSplatCamera* camera, const float* me
                                     const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased,
                                     float* xys, float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box,
                                     void* workspace, int64_t max_intersections, tn_stream_t stream) {
-  return splat_project("tn_splat_project_sep", true, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
+  return splat_project("tn_splat_project_sep", true, nullptr, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
                        thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation,
                        num_tiles_hit, tile_box, workspace, max_intersections, stream);
 }
@@ -1252,7 +1478,7 @@ extern "C" int tn_splat_project_crop(const TnSplatCamera* camera, const float* m
                                      int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
                                      int64_t max_intersections, const TnSplatCrop* crop, tn_stream_t stream) {
   TN_REQUIRE(crop != nullptr, "tn_splat_project_crop: null crop box");
-  return splat_project("tn_splat_project_crop", false, crop, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
+  return splat_project("tn_splat_project_crop", false, crop, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
                        nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation, num_tiles_hit, tile_box,
                        workspace, max_intersections, stream);
 }
@@ -1264,12 +1490,47 @@ extern "C" int tn_splat_project_crop_sep(const TnSplatCamera* camera, const floa
                                          int32_t* num_tiles_hit, int32_t* tile_box, void* workspace, int64_t max_intersections, const TnSplatCrop* crop,
                                          tn_stream_t stream) {
   TN_REQUIRE(crop != nullptr, "tn_splat_project_crop_sep: null crop box");
-  return splat_project("tn_splat_project_crop_sep", true, crop, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
+  return splat_project("tn_splat_project_crop_sep", true, crop, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
                        thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation,
                        num_tiles_hit, tile_box, workspace, max_intersections, stream);
 }
 
 // the box test of the crop projection on a bare point list: mask[i] = 1 where means[i] is inside, else 0
+// The pose entry points.  tn_splat_pose_camera: the frame's camera and one pose row (device) -> the corrected camera record (device), one launch,
+// nothing read back.  tn_splat_project_pose / _sep: tn_splat_project / _sep with the camera taken from that record (camera still gives the
+// intrinsics, the clip threshold and the image size); crop may be null.
+extern "C" int tn_splat_pose_camera(const TnSplatCamera* camera, float proj_x, float proj_y, const float* pose_row, float* pose_camera, tn_stream_t stream) {
+  int rc = check_cam(camera, "tn_splat_pose_camera");
+  if (rc) return rc;
+  TN_REQUIRE(pose_row && pose_camera, "tn_splat_pose_camera: null pointer");
+  hipLaunchKernelGGL(k_splat_pose_camera, dim3(1), dim3(64), 0, tn_s(stream), make_camk(camera), proj_x, proj_y, pose_row, pose_camera);
+  TN_CHECK_LAUNCH("tn_splat_pose_camera");
+  return TN_OK;
+}
+
+extern "C" int tn_splat_project_pose(const TnSplatCamera* camera, const float* pose_camera, const float* means, const float* log_scales, const float* quats,
+                                     const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
+                                     const float* thermal_rest, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased,
+                                     float* xys, float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box,
+                                     void* workspace, int64_t max_intersections, const TnSplatCrop* crop, tn_stream_t stream) {
+  TN_REQUIRE(pose_camera != nullptr, "tn_splat_project_pose: null pose camera record");
+  return splat_project("tn_splat_project_pose", false, crop, pose_camera, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
+                       thermal_rest, nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation, num_tiles_hit,
+                       tile_box, workspace, max_intersections, stream);
+}
+
+extern "C" int tn_splat_project_pose_sep(const TnSplatCamera* camera, const float* pose_camera, const float* means, const float* log_scales,
+                                         const float* quats, const float* opacities, const float* features_dc, const float* features_rest,
+                                         const float* thermal_dc, const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians,
+                                         int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys, float* depths, int32_t* radii,
+                                         float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
+                                         int64_t max_intersections, const TnSplatCrop* crop, tn_stream_t stream) {
+  TN_REQUIRE(pose_camera != nullptr, "tn_splat_project_pose_sep: null pose camera record");
+  return splat_project("tn_splat_project_pose_sep", true, crop, pose_camera, camera, means, log_scales, quats, opacities, features_dc, features_rest,
+                       thermal_dc, thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics,
+                       compensation, num_tiles_hit, tile_box, workspace, max_intersections, stream);
+}
+
 __global__ void __launch_bounds__(256) k_splat_crop_mask(SplatCropK crop, const float* __restrict__ means, int64_t n, uint8_t* __restrict__ mask) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1507,7 +1768,20 @@ extern "C" int tn_splat_raster_backward_sep(const TnSplatCamera* camera, int64_t
                                bwd_workspace_bytes, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, stream);
 }
 
-static int splat_project_backward(const char* who, bool sep, const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
+struct PoseBwdArgs {  // what the pose entry points add to the projection backward (null: the entry points without _pose)
+  const float* rec;
+  const float* pose_row;
+  void* workspace;
+  int64_t workspace_bytes;
+  float* grad_pose_row;
+  float* dview_out;
+};
+extern "C" int64_t tn_splat_pose_workspace_bytes(int64_t num_gaussians) {
+  if (num_gaussians < 0 || num_gaussians >= (1ll << 31)) return -1;
+  return (int64_t)al256((size_t)std::max<int64_t>(tn_cdiv(num_gaussians, 256), 1) * 12 * sizeof(double));
+}
+
+static int splat_project_backward(const char* who, bool sep, const PoseBwdArgs* pose, const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
                                   const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
                                   const float* thermal_rest, const float* opacities_th, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
                                   int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics, const float* v_colors,
@@ -1527,6 +1801,29 @@ static int splat_project_backward(const char* who, bool sep, const TnSplatCamera
              "%s: %d higher-order coefficients for degree %d", who, num_rest_coeffs, sh_degree);
   TN_REQUIRE(num_rest_coeffs == 0 || (features_rest && thermal_rest && v_features_rest && v_thermal_rest), "%s: null SH coefficients", who);
   SplatCamK k = make_camk(camera);
+  if (pose) {  // the pose instantiation, then the launch that folds the blocks' partials and chains them to the pose row
+    TN_REQUIRE(pose->rec && pose->pose_row && pose->workspace && pose->grad_pose_row, "%s: null pointer", who);
+    const int64_t need = tn_splat_pose_workspace_bytes(num_gaussians);
+    TN_REQUIRE(pose->workspace_bytes >= need, "%s: workspace of %lld bytes, tn_splat_pose_workspace_bytes asks for %lld", who,
+               (long long)pose->workspace_bytes, (long long)need);
+    const int nblk = (int)tn_cdiv(num_gaussians, 256);
+    const SplatPoseBwdK pk{pose->rec, (double*)pose->workspace};
+    if (sep)
+      hipLaunchKernelGGL((k_splat_project_bwd<true, SplatPoseBwdK>), dim3((unsigned)nblk), dim3(256), 0, tn_s(stream), k, means, log_scales, quats, opacities,
+                         features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii, v_xys, v_conics,
+                         v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc, v_thermal_rest,
+                         opacities_th, v_log_opacity_th, v_opacities_th, pk);
+    else
+      hipLaunchKernelGGL((k_splat_project_bwd<false, SplatPoseBwdK>), dim3((unsigned)nblk), dim3(256), 0, tn_s(stream), k, means, log_scales, quats, opacities,
+                         features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii, v_xys, v_conics,
+                         v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc, v_thermal_rest,
+                         opacities_th, v_log_opacity_th, v_opacities_th, pk);
+    TN_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(k_splat_pose_finish, dim3(1), dim3(12 * SPLAT_POSE_SEGS), 0, tn_s(stream), k, pose->pose_row, (const double*)pose->workspace, nblk,
+                       pose->grad_pose_row, pose->dview_out);
+    TN_CHECK_LAUNCH(who);
+    return TN_OK;
+  }
   hipLaunchKernelGGL(sep ? k_splat_project_bwd<true> : k_splat_project_bwd<false>, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, tn_s(stream), k, means,
                      log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii,
                      v_xys, v_conics, v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
@@ -1541,7 +1838,7 @@ extern "C" int tn_splat_project_backward(const TnSplatCamera* camera, const floa
                                          int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics, const float* v_colors,
                                          const float* v_log_opacity, float* v_means, float* v_log_scales, float* v_quats, float* v_opacities,
                                          float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest, tn_stream_t stream) {
-  return splat_project_backward("tn_splat_project_backward", false, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
+  return splat_project_backward("tn_splat_project_backward", false, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
                                 nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics, v_colors, v_log_opacity, nullptr, v_means,
                                 v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc, v_thermal_rest, nullptr, stream);
 }
@@ -1553,10 +1850,44 @@ extern "C" int tn_splat_project_backward_sep(const TnSplatCamera* camera, const 
                                              const float* v_colors, const float* v_log_opacity, const float* v_log_opacity_thermal, float* v_means,
                                              float* v_log_scales, float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest,
                                              float* v_thermal_dc, float* v_thermal_rest, float* v_opacities_thermal, tn_stream_t stream) {
-  return splat_project_backward("tn_splat_project_backward_sep", true, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
+  return splat_project_backward("tn_splat_project_backward_sep", true, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
                                 thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics, v_colors,
                                 v_log_opacity, v_log_opacity_thermal, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
                                 v_thermal_rest, v_opacities_thermal, stream);
+}
+
+// The pose backward: tn_splat_project_backward / _sep with the camera of the forward's record, plus dL/d(pose row): pose_camera and pose_row as
+// tn_splat_pose_camera took and wrote them; workspace of tn_splat_pose_workspace_bytes(num_gaussians); the gradient is ADDED to grad_pose_row [6]
+// (the caller's row of grad_pose [C,6]); dview_out [12] (may be null) receives dL/d view'.  With zero Gaussians nothing is launched.
+extern "C" int tn_splat_project_backward_pose(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
+                                              const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
+                                              const float* features_rest, const float* thermal_dc, const float* thermal_rest, int64_t num_gaussians,
+                                              int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, const int32_t* radii, const float* v_xys,
+                                              const float* v_conics, const float* v_colors, const float* v_log_opacity, float* v_means, float* v_log_scales,
+                                              float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest, float* v_thermal_dc,
+                                              float* v_thermal_rest, void* workspace, int64_t workspace_bytes, float* grad_pose_row, float* dview_out,
+                                              tn_stream_t stream) {
+  const PoseBwdArgs pa{pose_camera, pose_row, workspace, workspace_bytes, grad_pose_row, dview_out};
+  return splat_project_backward("tn_splat_project_backward_pose", false, &pa, camera, means, log_scales, quats, opacities, features_dc, features_rest,
+                                thermal_dc, thermal_rest, nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics, v_colors,
+                                v_log_opacity, nullptr, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
+                                v_thermal_rest, nullptr, stream);
+}
+
+extern "C" int tn_splat_project_backward_pose_sep(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
+                                                  const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
+                                                  const float* features_rest, const float* thermal_dc, const float* thermal_rest,
+                                                  const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
+                                                  int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics,
+                                                  const float* v_colors, const float* v_log_opacity, const float* v_log_opacity_thermal, float* v_means,
+                                                  float* v_log_scales, float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest,
+                                                  float* v_thermal_dc, float* v_thermal_rest, float* v_opacities_thermal, void* workspace,
+                                                  int64_t workspace_bytes, float* grad_pose_row, float* dview_out, tn_stream_t stream) {
+  const PoseBwdArgs pa{pose_camera, pose_row, workspace, workspace_bytes, grad_pose_row, dview_out};
+  return splat_project_backward("tn_splat_project_backward_pose_sep", true, &pa, camera, means, log_scales, quats, opacities, features_dc, features_rest,
+                                thermal_dc, thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics,
+                                v_colors, v_log_opacity, v_log_opacity_thermal, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest,
+                                v_thermal_dc, v_thermal_rest, v_opacities_thermal, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ refinement

@@ -252,6 +252,12 @@ SPLAT_OPTIMIZERS = {
     "features_rest_thermal": (0.0025 / 20, 0.0025 / 20, 30000),
     "opacities_thermal": (0.05, 0.05, 30000),
 }
+# The pose optimisers of the splat model (ThermalSplatfactoModelConfig.camera_optimizer / camera_optimizer_thermal), with the NeRF path's rates
+# (engine.py OPTIMIZERS): groups the model has only when a mode is on -- pass {**SPLAT_OPTIMIZERS, **SPLAT_CAMERA_OPTIMIZERS} to Optimizers then.
+SPLAT_CAMERA_OPTIMIZERS = {
+    "camera_opt": (1e-3, 1e-4, 5000),
+    "camera_opt_thermal": (1e-3, 1e-4, 5000),
+}
 
 
 def _cut_launches(work: list, max_ranges: int = 8) -> List[list]:

@@ -50,8 +50,14 @@ Gaussians whose mean is strictly inside it, bit for bit the frame of a model hol
 removal renders.  The reference gathers six parameter tensors through a boolean index per frame; here the box test is the first thing the
 projection kernel does (tn_splat_project_crop / _crop_sep): a Gaussian outside leaves with radius 0 and no tiles, as one behind the camera, a
 block of Gaussians that are all outside never reads its SH coefficients, and nothing is copied, allocated or read back.  The training render never
-crops (the reference crops only outside training), and the box is neither a parameter nor in the state dict.  Masks and camera-pose gradients are
-not built.  Parity is unpinned (gsplat is a third-party package outside the reference
+crops (the reference crops only outside training), and the box is neither a parameter nor in the state dict.  Camera poses can be refined as on
+the NeRF path (ThermalNerfactoModelConfig's camera_optimizer / camera_optimizer_thermal, cameras/camera_optimizers.py): with
+`camera_optimizer` / `camera_optimizer_thermal` in mode "SO3xR3" (a row per training frame, training renders only) or "shared_SO3xR3" (one row per
+spectrum -- a mis-registered thermal rig -- eval renders too) a frame reads the row (t, w) its PinholeCamera.cam_idx / is_thermal names,
+c2w' = c2w [A(p); 0 0 0 1] with A = exp_map_SO3xR3, and `get_train_outputs` is differentiable in it: the corrected camera is built on the device
+(tn_splat_pose_camera), the pose instantiations of the projection kernels read it (tn_splat_project_pose / tn_splat_project_backward_pose), and
+the backward reduces dL/d view' over the Gaussians without atomics, bit-reproducibly; the SH view directions take the corrected position as a
+value (splatfacto.py:770).  Both modes default to "off", which changes nothing.  Masks are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
 tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 """
 from __future__ import annotations
@@ -59,16 +65,18 @@ from __future__ import annotations
 import ctypes as C
 import dataclasses
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor, nn
 
 from . import _lib
+from .config import CameraOptimizerConfig
 from .ops import _stream
 
 BLOCK_WIDTH = 16  # splatfacto.py:738
+CAMERA_OPTIMIZER_MODES = ("off", "SO3xR3", "shared_SO3xR3")  # "SE3" is not built
 
 
 @dataclass
@@ -118,8 +126,17 @@ class ThermalSplatfactoModelConfig:
     # coarse-to-fine training (splatfacto.py:112-116): 1 / 2^num_downscales of the resolution at first, doubled every resolution_schedule steps
     resolution_schedule: int = 250
     num_downscales: int = 0
+    # pose refinement (ThermalNerfactoModelConfig's camera_optimizer / camera_optimizer_thermal; cameras/camera_optimizers.py:39-56): "off",
+    # "SO3xR3" (a row per training frame, training renders only) or "shared_SO3xR3" (one row for the whole spectrum, the rig extrinsic, eval
+    # renders too).  RGB frames read camera_optimizer, thermal frames camera_optimizer_thermal; penalty_scale < 0 also means off
+    camera_optimizer: CameraOptimizerConfig = field(default_factory=CameraOptimizerConfig)
+    camera_optimizer_thermal: CameraOptimizerConfig = field(default_factory=CameraOptimizerConfig)
 
     def __post_init__(self):
+        for name in ("camera_optimizer", "camera_optimizer_thermal"):
+            mode = getattr(self, name).mode
+            if mode not in CAMERA_OPTIMIZER_MODES:
+                raise ValueError(f'{name}.mode = {mode!r}: the splat path refines poses with "SO3xR3" or "shared_SO3xR3" ("off": not at all)')
         for name in ("tv_pixel_loss_mult", "cross_channel_loss_mult", "opacity_loss_mult", "rgb_opacity_loss_mult"):
             if getattr(self, name) < 0:
                 raise ValueError(f"{name} = {getattr(self, name)}: a loss multiplier cannot be negative")
@@ -144,6 +161,8 @@ class PinholeCamera:
     cy: float
     width: int
     height: int
+    cam_idx: Optional[int] = None  # the frame's index among the training frames: the row of a per-frame pose optimiser (None: no row)
+    is_thermal: bool = False  # the spectrum, which picks the pose optimiser (camera_optimizer / camera_optimizer_thermal)
 
 
 def _rotation_rpy(roll: float, pitch: float, yaw: float) -> Tensor:
@@ -286,6 +305,26 @@ def _ptr(t: Optional[Tensor], dtype, name: str):
     if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
         raise ValueError(f"{name} must be a contiguous {dtype} HIP tensor (the splat path has no CPU fallback)")
     return C.c_void_p(t.data_ptr())
+
+
+def _pose_row_ptr(pose: Tensor, row: int, name: str = "pose_adjustment"):
+    """Device pointer of row `row` of a contiguous fp32 [C,6] tensor (a host offset: nothing is read)."""
+    _ptr(pose, torch.float32, name)
+    if pose.dim() != 2 or pose.shape[1] != 6 or not 0 <= row < pose.shape[0]:
+        raise ValueError(f"{name} must be [C,6] with the frame's row {row} inside, got {tuple(pose.shape)}")
+    return C.c_void_p(pose.data_ptr() + 24 * row)
+
+
+def pose_camera_record(camera: PinholeCamera, cam: _lib.TnSplatCamera, pose: Tensor, row: int) -> Tensor:
+    """The camera corrected by row `row` of `pose` [C,6] (c2w' = c2w [A(p); 0 0 0 1], camera_optimizers.py:178-186) as the device record the
+    _pose entry points read (tn_splat_pose_camera: one launch, the pose is never read on the host).  [TN_SPLAT_POSE_CAMERA_FLOATS] fp32: view'
+    [0:12], proj' [12:28], position' [28:31], the two intrinsic projection entries [31:33].  With a zero row it holds `cam`'s own numbers."""
+    fovx, fovy = 2 * math.atan(camera.width / (2 * camera.fx)), 2 * math.atan(camera.height / (2 * camera.fy))
+    P = projection_matrix(0.001, 1000, fovx, fovy)  # camera_struct's: projmat = P @ viewmat, rows 0, 1, 3 one product each
+    rec = torch.empty(_lib.TN_SPLAT_POSE_CAMERA_FLOATS, device=pose.device)
+    _lib.check(_lib.load().tn_splat_pose_camera(C.byref(cam), float(P[0, 0]), float(P[1, 1]), _pose_row_ptr(pose, row), _ptr(rec, torch.float32, "pose camera"),
+                                                _stream()), "tn_splat_pose_camera")
+    return rec
 
 
 KNN_MAX_K = 8  # tn_knn's largest k
@@ -674,9 +713,11 @@ def _param_ptrs(tensors) -> list:
     return pp
 
 
-def _project_and_bin(model, cam, params, H: int, W: int, deg: int, aa: int, cap: int, workspace, crop: Optional[_lib.TnSplatCrop] = None):
+def _project_and_bin(model, cam, params, H: int, W: int, deg: int, aa: int, cap: int, workspace, crop: Optional[_lib.TnSplatCrop] = None,
+                     pose_rec: Optional[Tensor] = None):
     """One frame's tn_splat_project -> tn_splat_bin into `workspace(N, cap, tiles)`, a buffer for `cap` (Gaussian, tile) pairs: the caller says
-    where it comes from.  With `crop` the projection is tn_splat_project_crop / _crop_sep: Gaussians outside the box leave with radius 0.  A frame with more pairs grows `cap` once and is redone.  Leaves `last_projection` / `last_num_intersections` on the model
+    where it comes from.  With `crop` the projection is tn_splat_project_crop / _crop_sep: Gaussians outside the box leave with radius 0.  With
+    `pose_rec` (pose_camera_record) it is tn_splat_project_pose / _pose_sep, which reads the corrected camera from that record (and takes the box too).  A frame with more pairs grows `cap` once and is redone.  Leaves `last_projection` / `last_num_intersections` on the model
     and returns (projection tensors, workspace, cap, pairs).  No Gaussians: nothing to project, no workspace (None), the frame is the background."""
     i32 = torch.int32
     lib = _lib.load()
@@ -690,7 +731,11 @@ def _project_and_bin(model, cam, params, H: int, W: int, deg: int, aa: int, cap:
         out_ptrs = [_ptr(t, t.dtype, k) for k, t in proj.items()]
         ws = workspace(N, cap, tiles)
         wsp = C.c_void_p(ws.data_ptr())
-        if crop is not None:  # the eval render's crop box: the same launch with the box test in front
+        if pose_rec is not None:  # a refined pose: the camera comes from the device record
+            name = "tn_splat_project_pose_sep" if len(params) == 9 else "tn_splat_project_pose"
+            _lib.check(getattr(lib, name)(C.byref(cam), _ptr(pose_rec, torch.float32, "pose camera"), *_param_ptrs(params), N, K, deg, aa, *out_ptrs, wsp, cap,
+                                          C.byref(crop) if crop is not None else None, _stream()), name)
+        elif crop is not None:  # the eval render's crop box: the same launch with the box test in front
             name = "tn_splat_project_crop_sep" if len(params) == 9 else "tn_splat_project_crop"
             _lib.check(getattr(lib, name)(C.byref(cam), *_param_ptrs(params), N, K, deg, aa, *out_ptrs, wsp, cap, C.byref(crop), _stream()), name)
         elif len(params) == 9:  # separate thermal opacity
@@ -727,21 +772,49 @@ def _background_outputs(H: int, W: int, bgl: List[float], dev, sep: bool = False
     return out
 
 
+def _project_backward_pose(model, entry, name: str, cam, rec: Tensor, pose: Tensor, row: int, params, grads, N: int, deg: int, aa: int, radii: Tensor,
+                           upstream) -> Tensor:
+    """The pose instantiation of the projection backward (tn_splat_project_backward_pose / _pose_sep): fills `grads` as the entry point without
+    _pose does and returns dL/d pose [C,6] -- zeros but for the frame's row, which the finishing kernel adds into.  dL/d view' [3,4] is left in
+    `model.last_view_grad`.  The partials' workspace is this call's own; nothing is read back."""
+    f32, dev = torch.float32, pose.device
+    need = int(_lib.load().tn_splat_pose_workspace_bytes(N))
+    if need < 0:
+        raise RuntimeError("tn_splat_pose_workspace_bytes: bad Gaussian count")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    g_pose = torch.zeros_like(pose)
+    dview = torch.empty((3, 4), device=dev)
+    names = ("v_xys", "v_conics", "v_colors", "v_log_opacity", "v_log_opacity_thermal")
+    _lib.check(entry(C.byref(cam), _ptr(rec, f32, "pose camera"), _pose_row_ptr(pose, row), *_param_ptrs(params), N, params[5].shape[1], deg, aa,
+                     _ptr(radii, torch.int32, "radii"), *(_ptr(t, f32, n) for t, n in zip(upstream, names)), *_param_ptrs(grads), C.c_void_p(ws.data_ptr()), need,
+                     _pose_row_ptr(g_pose, row, "grad_pose"), _ptr(dview, f32, "dview"), _stream()), name)
+    model.last_view_grad = dview
+    return g_pose
+
+
 class _SplatRender(torch.autograd.Function):
     """project -> bin -> training raster; backward = raster backward -> projection backward.  Inputs after `frame` are the gauss_params in
     _PARAM_NAMES order; outputs: colour before the clamp [H,W,4] (RGB + thermal over the background), accumulation [H,W,1], depth [H,W,1]
     (not differentiable).  Nine parameters (separate thermal opacity, opacities_thermal last): the _sep entry points, and a fourth output,
-    the thermal chain's accumulation [H,W,1]."""
+    the thermal chain's accumulation [H,W,1].  A frame with a pose row (frame["pose_row"]) passes its optimiser's pose_adjustment [C,6] as one
+    more input behind the parameters: the camera is corrected on the device (pose_camera_record), the _pose entry points run, and the backward
+    also returns dL/d pose_adjustment [C,6], zero outside the frame's row, and leaves dL/d view' [3,4] in `last_view_grad`."""
 
     @staticmethod
     def forward(ctx, frame, *params):
+        row = frame.get("pose_row")
+        pose = None
+        if row is not None:
+            params, pose = params[:-1], params[-1].detach().contiguous()
+        ctx.pose, ctx.rec = pose, (pose_camera_record(frame["camera"], frame["cam"], pose, row) if pose is not None else None)
         model, camera = frame["model"], frame["camera"]
         f32, i32 = torch.float32, torch.int32
         cam, N, H, W = frame["cam"], params[0].shape[0], int(camera.height), int(camera.width)
         aa, bg4, dev = frame["aa"], frame["bg4"], params[0].device
         sep = len(params) == 9
         # a workspace of this frame's own: the backward reads it after other frames may have been rendered
-        proj, ws, cap, total = _project_and_bin(model, cam, params, H, W, frame["deg"], aa, max(model._train_cap, 1 << 16), model._new_workspace)
+        proj, ws, cap, total = _project_and_bin(model, cam, params, H, W, frame["deg"], aa, max(model._train_cap, 1 << 16), model._new_workspace,
+                                                pose_rec=ctx.rec)
         model._train_cap = cap
         # what after_train reads of the training frame (the reference's self.radii / self.last_size); eval renders leave these alone
         model.last_radii, model.last_size = proj["radii"], (H, W)
@@ -788,9 +861,10 @@ class _SplatRender(torch.autograd.Function):
         params = saved[:P]
         means = params[0]
         N, dev = means.shape[0], means.device
+        pose, row = ctx.pose, frame.get("pose_row")
         if ctx.empty:
             model.last_xys_grad = torch.zeros((N, 2), device=dev)
-            return (None,) + tuple(torch.zeros_like(p) for p in params)
+            return (None,) + tuple(torch.zeros_like(p) for p in params) + ((torch.zeros_like(pose),) if pose is not None else ())
         radii, conics, final_t, last = saved[P:P + 4]
         lib = _lib.load()
         f32 = torch.float32
@@ -816,6 +890,11 @@ class _SplatRender(torch.autograd.Function):
                                                         _ptr(v_lnop, f32, "v_log_opacity"), _ptr(v_lnop_th, f32, "v_log_opacity_thermal"), _stream()),
                        "tn_splat_raster_backward_sep")
             grads = [torch.empty_like(p) for p in params]
+            if pose is not None:
+                g_pose = _project_backward_pose(model, lib.tn_splat_project_backward_pose_sep, "tn_splat_project_backward_pose_sep", cam, ctx.rec, pose, row,
+                                                params, grads, N, deg, aa, radii, (v_xys, v_conics, v_colors, v_lnop, v_lnop_th))
+                model.last_xys_grad = v_xys
+                return (None,) + tuple(grads) + (g_pose,)
             _lib.check(lib.tn_splat_project_backward_sep(C.byref(cam), *_param_ptrs(params), N, params[5].shape[1], deg, aa, _ptr(radii, torch.int32, "radii"),
                                                          _ptr(v_xys, f32, "v_xys"), _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"),
                                                          _ptr(v_lnop, f32, "v_log_opacity"), _ptr(v_lnop_th, f32, "v_log_opacity_thermal"), *_param_ptrs(grads),
@@ -828,11 +907,80 @@ class _SplatRender(torch.autograd.Function):
                                                 _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"), _ptr(v_lnop, f32, "v_log_opacity"), _stream()),
                    "tn_splat_raster_backward")
         grads = [torch.empty_like(p) for p in params]
+        if pose is not None:
+            g_pose = _project_backward_pose(model, lib.tn_splat_project_backward_pose, "tn_splat_project_backward_pose", cam, ctx.rec, pose, row, params,
+                                            grads, N, deg, aa, radii, (v_xys, v_conics, v_colors, v_lnop))
+            model.last_xys_grad = v_xys
+            return (None,) + tuple(grads) + (g_pose,)
         _lib.check(lib.tn_splat_project_backward(C.byref(cam), *_param_ptrs(params), N, params[5].shape[1], deg, aa, _ptr(radii, torch.int32, "radii"),
                                                  _ptr(v_xys, f32, "v_xys"), _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"),
                                                  _ptr(v_lnop, f32, "v_log_opacity"), *_param_ptrs(grads), _stream()), "tn_splat_project_backward")
         model.last_xys_grad = v_xys
         return (None,) + tuple(grads)
+
+
+class SplatCameraOptimizer(nn.Module):
+    """The reference's CameraOptimizer (cameras/camera_optimizers.py:89-213) for one spectrum of the splat model: `pose_adjustment` [C,6] (mode
+    "SO3xR3", a row (t, w) per training frame) or [1,6] ("shared_SO3xR3", one row for the whole spectrum), zeros at the start; mode "off" (or
+    penalty_scale < 0) holds no parameter at all.  As in ThermalNerfactoModel (models/thermal_nerfacto.py:132-144) the optimiser of each
+    spectrum is sized to ALL training frames and the other spectrum's rows are non-trainable (`non_trainable_camera_indices`, the frozen mask):
+    a frame reads a row only from its own spectrum's optimiser, so those rows never receive a gradient.  `row(camera, training)` is the row a
+    frame reads, decided on the host from camera.cam_idx / camera.is_thermal alone: a per-frame row in training only
+    (thermal_nerfacto.py:410-412), the shared row always; None renders the camera as it is."""
+
+    def __init__(self, config: CameraOptimizerConfig, num_cameras: int, device, thermal: bool = False,
+                 non_trainable_camera_indices: Optional[Tensor] = None):
+        super().__init__()
+        if config.mode not in CAMERA_OPTIMIZER_MODES:
+            raise ValueError(f'camera optimiser mode {config.mode!r}: the splat path refines poses with "SO3xR3" or "shared_SO3xR3" ("off": not at all)')
+        self.config = config
+        self.mode = "off" if config.penalty_scale < 0 else config.mode
+        self.thermal = bool(thermal)
+        self.suffix = "_thermal" if thermal else ""
+        self.group = "camera_opt" + self.suffix
+        self.num_cameras = int(num_cameras)
+        frozen = torch.zeros(max(self.num_cameras, 0), dtype=torch.uint8)
+        if non_trainable_camera_indices is not None and self.num_cameras > 0:
+            frozen[torch.as_tensor(non_trainable_camera_indices, dtype=torch.long)] = 1
+        self._frozen_rows = frozenset(int(i) for i in frozen.nonzero().reshape(-1).tolist())  # the host's copy: what row() reads
+        self.register_buffer("_frozen", frozen.to(device), persistent=False)
+        if self.mode == "SO3xR3" and self.num_cameras < 1:
+            raise ValueError('camera optimiser mode "SO3xR3" needs num_train_data: a pose row per training frame')
+        if self.mode != "off":
+            self.pose_adjustment = nn.Parameter(torch.zeros((1 if self.shared else self.num_cameras, 6), device=device))
+
+    @property
+    def shared(self) -> bool:
+        return self.mode == "shared_SO3xR3"
+
+    def row(self, camera: PinholeCamera, training: bool) -> Optional[int]:
+        if self.mode == "off" or bool(camera.is_thermal) != self.thermal:
+            return None
+        if self.shared:
+            return 0
+        idx = camera.cam_idx
+        if not training or idx is None or idx in self._frozen_rows:
+            return None
+        if not 0 <= int(idx) < self.num_cameras:
+            raise ValueError(f"camera.cam_idx = {idx}: {self.group} has {self.num_cameras} rows")
+        return int(idx)
+
+    def get_loss_dict(self, loss_dict: dict) -> None:
+        if self.mode != "off":
+            from .autograd_ops import CameraRegularizer
+
+            loss_dict[f"camera_opt_regularizer{self.suffix}"] = CameraRegularizer.apply(
+                self.pose_adjustment, self.config.trans_l2_penalty, self.config.rot_l2_penalty, self.config.penalty_scale)
+
+    def get_metrics_dict(self, metrics_dict: dict) -> None:
+        if self.mode != "off":
+            pa = self.pose_adjustment.detach()
+            metrics_dict[f"camera_opt_translation{self.suffix}"] = pa[:, :3].norm()
+            metrics_dict[f"camera_opt_rotation{self.suffix}"] = pa[:, 3:].norm()
+
+    def get_param_groups(self, param_groups: dict) -> None:
+        if self.mode != "off":
+            param_groups[self.group] = [self.pose_adjustment]
 
 
 class ThermalSplatfactoModel(nn.Module):
@@ -851,7 +999,7 @@ class ThermalSplatfactoModel(nn.Module):
     which this model deliberately does not, to keep that start unchanged."""
 
     def __init__(self, config: Optional[ThermalSplatfactoModelConfig] = None, num_points: Optional[int] = None, device="cuda", seed: int = 0,
-                 num_train_data: int = 0, seed_points: Optional[Tuple[Tensor, Tensor]] = None):
+                 num_train_data: int = 0, seed_points: Optional[Tuple[Tensor, Tensor]] = None, train_is_thermal: Optional[List[bool]] = None):
         super().__init__()
         self.config = config or ThermalSplatfactoModelConfig()
         self.num_train_data = num_train_data
@@ -879,6 +1027,17 @@ class ThermalSplatfactoModel(nn.Module):
             })
         if self.separate:  # the thermal opacity logits start exactly as the opacities do
             self.gauss_params["opacities_thermal"] = nn.Parameter(torch.logit(0.1 * torch.ones(self.gauss_params["means"].shape[0], 1)).to(dev))
+        # pose refinement: one optimiser per spectrum, both sized to all training frames; the other spectrum's rows are non-trainable
+        # (`train_is_thermal`, one flag per training frame, names them; without it no row is marked and the routing by camera.is_thermal alone
+        # keeps a frame off the other optimiser).  Mode "off" adds no parameter, no state-dict entry and no optimiser group.
+        flags = None if train_is_thermal is None else torch.tensor([bool(t) for t in train_is_thermal], dtype=torch.bool)
+        if flags is not None and flags.numel() != num_train_data:
+            raise ValueError(f"train_is_thermal has {flags.numel()} flags for num_train_data = {num_train_data}")
+        self.camera_optimizer = SplatCameraOptimizer(self.config.camera_optimizer, num_train_data, dev, False,
+                                                     None if flags is None else flags.nonzero().reshape(-1))
+        self.camera_optimizer_thermal = SplatCameraOptimizer(self.config.camera_optimizer_thermal, num_train_data, dev, True,
+                                                             None if flags is None else (~flags).nonzero().reshape(-1))
+        self.last_view_grad: Optional[Tensor] = None  # dL/d view' [3,4] of the last training frame that read a pose row
         self.step = 0
         self._ws: Optional[Tensor] = None
         self._cap = 0
@@ -1034,7 +1193,9 @@ class ThermalSplatfactoModel(nn.Module):
             return _background_outputs(H, W, bgl, dev, self.separate, thr is not None)
         cam = camera_struct(camera)
         params = [self.gauss_params[k] for k in self.param_names]
-        _, ws, cap, total = _project_and_bin(self, cam, params, H, W, deg, aa, max(self._cap, 1 << 16), self._workspace, self._crop())
+        pose, row = self._pose_row(camera, training=False)  # a shared row corrects eval renders of its spectrum too; per-frame rows never do
+        rec = pose_camera_record(camera, cam, pose.detach(), row) if row is not None else None
+        _, ws, cap, total = _project_and_bin(self, cam, params, H, W, deg, aa, max(self._cap, 1 << 16), self._workspace, self._crop(), rec)
         if total == 0:  # nothing on screen
             return _background_outputs(H, W, bgl, dev, self.separate, thr is not None)
         f32 = torch.float32
@@ -1057,6 +1218,12 @@ class ThermalSplatfactoModel(nn.Module):
                                                _ptr(depth, f32, "depth"), _ptr(alpha, f32, "alpha"), _stream()), "tn_splat_raster")
         return _outputs(rgbt[..., :3], rgbt[..., 3:], depth, alpha, bgl)
 
+    def _pose_row(self, camera: PinholeCamera, training: bool) -> Tuple[Optional[Tensor], Optional[int]]:
+        """(pose_adjustment, row) the frame of `camera` reads -- its spectrum's optimiser, at most one row of one tensor -- or (None, None)."""
+        opt = self.camera_optimizer_thermal if camera.is_thermal else self.camera_optimizer
+        row = opt.row(camera, training)
+        return (opt.pose_adjustment, row) if row is not None else (None, None)
+
     def _get_downscale_factor(self) -> int:
         """splatfacto.py:639-646: the resolution schedule's factor at this step while the module is in training mode, else 1."""
         return downscale_factor(self.step, self.config.num_downscales, self.config.resolution_schedule, self.training)
@@ -1076,7 +1243,12 @@ class ThermalSplatfactoModel(nn.Module):
         names = self.param_names
         frame = {"model": self, "camera": camera, "cam": camera_struct(camera), "aa": aa, "deg": deg, "bg4": (C.c_float * 4)(*bgl), "num_params": len(names)}
         self.last_xys_grad = None
-        rgbt, alpha, depth, *alpha_th = _SplatRender.apply(frame, *(self.gauss_params[k] for k in names))
+        pose, row = self._pose_row(camera, training=True)
+        if row is not None:  # the frame's pose row: one more differentiable input
+            frame["pose_row"] = row
+            rgbt, alpha, depth, *alpha_th = _SplatRender.apply(frame, *(self.gauss_params[k] for k in names), pose)
+        else:
+            rgbt, alpha, depth, *alpha_th = _SplatRender.apply(frame, *(self.gauss_params[k] for k in names))
         alpha_th = alpha_th[0] if alpha_th else None  # separate mode: the thermal chain's accumulation (differentiable)
         if self.last_num_intersections == 0:  # the background as get_outputs returns it (no clamp)
             return _outputs(rgbt[..., :3], rgbt[..., 3:], depth, alpha, bgl, alpha_th)
@@ -1155,13 +1327,18 @@ class ThermalSplatfactoModel(nn.Module):
         if self.separate and cfg.opacity_loss_mult > 0:
             losses["density_loss"] = opacity_density_loss(self.gauss_params["opacities"], self.gauss_params["opacities_thermal"], cfg.opacity_loss_mult,
                                                           cfg.rgb_opacity_loss_mult)
+        self.camera_optimizer.get_loss_dict(losses)  # camera_opt_regularizer / _thermal (tn_camera_reg), only when the mode is on
+        self.camera_optimizer_thermal.get_loss_dict(losses)
         return losses
 
     @torch.no_grad()
     def get_metrics_dict(self, outputs: Dict[str, Tensor], batch) -> Dict[str, Tensor]:
         """splatfacto.py:848-861 on the frame's spectrum: psnr (data range 1, a device scalar) and gaussian_count."""
         _, pred, gt = self._frame_pred_gt(outputs, batch)
-        return {"psnr": _psnr(pred, gt), "gaussian_count": self.num_points}
+        metrics = {"psnr": _psnr(pred, gt), "gaussian_count": self.num_points}
+        self.camera_optimizer.get_metrics_dict(metrics)  # camera_opt_translation / camera_opt_rotation (+ _thermal), only when the mode is on
+        self.camera_optimizer_thermal.get_metrics_dict(metrics)
+        return metrics
 
     @torch.no_grad()
     def get_image_metrics_and_images(self, outputs: Dict[str, Tensor], batch) -> Tuple[Dict[str, float], Dict[str, Tensor]]:
@@ -1193,7 +1370,11 @@ class ThermalSplatfactoModel(nn.Module):
         return {g: [self.gauss_params[k]] for g, k in self.group_params.items()}
 
     def get_param_groups(self) -> Dict[str, List[nn.Parameter]]:
-        return self.get_gaussian_param_groups()
+        """The Gaussian groups and, for each pose optimiser that is on, camera_opt / camera_opt_thermal (optim.SPLAT_CAMERA_OPTIMIZERS)."""
+        groups = self.get_gaussian_param_groups()
+        self.camera_optimizer.get_param_groups(groups)
+        self.camera_optimizer_thermal.get_param_groups(groups)
+        return groups
 
     def get_training_callbacks(self, training_callback_attributes) -> List["TrainingCallback"]:
         """splatfacto.py:595-617.  `training_callback_attributes` carries the `Optimizers` as `.optimizers` (or is the `Optimizers`); the

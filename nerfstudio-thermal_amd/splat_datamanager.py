@@ -11,6 +11,7 @@ one seed see one order.  A batch is a new dict over the cached tensor (the refer
 to a batch's image).  Masks, depth images and fisheye cameras are not built."""
 from __future__ import annotations
 
+import dataclasses
 import random
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
@@ -62,7 +63,7 @@ class ThermalFullImageDatamanager:
         self.dataparser = config.dataparser.setup()
         self.train_dataparser_outputs = self.dataparser.get_dataparser_outputs("train")
         self.eval_dataparser_outputs = self.dataparser.get_dataparser_outputs(config.eval_split)
-        self.cached_train, self.train_cameras = self._cache(self.train_dataparser_outputs)
+        self.cached_train, self.train_cameras = self._cache(self.train_dataparser_outputs, train=True)
         self.cached_eval, self.eval_cameras = self._cache(self.eval_dataparser_outputs)
         if not self.cached_train:
             raise ValueError("No data found in dataset")
@@ -71,20 +72,28 @@ class ThermalFullImageDatamanager:
         self.eval_unseen_cameras = list(range(len(self.cached_eval)))
         self._last_pixels = 0
 
-    def _cache(self, outputs: DataparserOutputs) -> Tuple[List[Batch], List[PinholeCamera]]:
+    def _cache(self, outputs: DataparserOutputs, train: bool = False) -> Tuple[List[Batch], List[PinholeCamera]]:
+        """Every camera carries its spectrum (is_thermal); a training camera also its index among the training frames (cam_idx), the row of a
+        per-frame pose optimiser."""
         load = load_image_uint8 if self.config.cache_images_type == "uint8" else load_image_float32
         cached, cameras = [], []
         for i, path in enumerate(outputs.image_filenames):
             image, camera = load(path).to(self.device), parsed_camera(outputs, i)
             if self.config.undistort:
                 image, camera = undistort_image(image, camera, outputs.cameras["distortion"][i])
-            cached.append({"image": image, "is_thermal": bool(outputs.metadata["is_thermal"][i]), "image_idx": i})
-            cameras.append(camera)
+            is_thermal = bool(outputs.metadata["is_thermal"][i])
+            cached.append({"image": image, "is_thermal": is_thermal, "image_idx": i})
+            cameras.append(dataclasses.replace(camera, cam_idx=i if train else None, is_thermal=is_thermal))
         return cached, cameras
 
     @property
     def num_train_data(self) -> int:
         return len(self.cached_train)
+
+    @property
+    def train_is_thermal(self) -> List[bool]:
+        """One flag per training frame: what ThermalSplatfactoModel(train_is_thermal=...) marks the other spectrum's pose rows with."""
+        return [bool(b["is_thermal"]) for b in self.cached_train]
 
     @property
     def seed_points(self) -> Optional[Tuple[Tensor, Tensor]]:

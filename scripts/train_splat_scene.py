@@ -38,7 +38,8 @@ from nerfstudio_thermal_amd import synth  # noqa: E402
 from nerfstudio_thermal_amd import ThermalFullImageDatamanagerConfig  # noqa: E402
 from nerfstudio_thermal_amd.dataparser import ThermalNerfDataParserConfig, load_image_float32, write_ply  # noqa: E402
 from nerfstudio_thermal_amd.model import TrainingCallbackLocation  # noqa: E402
-from nerfstudio_thermal_amd.optim import SPLAT_OPTIMIZERS, HipAdam, Optimizers  # noqa: E402
+from nerfstudio_thermal_amd.config import CameraOptimizerConfig  # noqa: E402
+from nerfstudio_thermal_amd.optim import SPLAT_CAMERA_OPTIMIZERS, SPLAT_OPTIMIZERS, HipAdam, Optimizers  # noqa: E402
 from nerfstudio_thermal_amd.splat import OrientedBox, PinholeCamera, ThermalSplatfactoModel, ThermalSplatfactoModelConfig, downscale_factor  # noqa: E402
 from train_eval_scene import write_cube_scene  # noqa: E402
 
@@ -111,6 +112,10 @@ def main():
     ap.add_argument("--crop-rpy", type=float, nargs=3, default=None, metavar=("ROLL", "PITCH", "YAW"), help="its orientation, radians")
     ap.add_argument("--crop-scale", type=float, nargs=3, default=None, metavar=("SX", "SY", "SZ"), help="its extents")
     ap.add_argument("--crop-out", default="out/crop", help="where the cropped eval frames are written")
+    ap.add_argument("--camera-optimizer", default="off", choices=("off", "SO3xR3", "shared_SO3xR3"),
+                    help="refine the RGB frames' poses: a row per training frame, or one shared row (also applied to eval renders)")
+    ap.add_argument("--camera-optimizer-thermal", default="off", choices=("off", "SO3xR3", "shared_SO3xR3"),
+                    help="the same for the thermal frames (shared_SO3xR3: a mis-registered thermal rig)")
     ap.add_argument("--no-undistort", action="store_true", help="train on the raw frames with the parser's intrinsics (the distortion dropped)")
     args = ap.parse_args()
     if args.seed_points and args.data is not None:
@@ -140,10 +145,13 @@ def main():
                                        background_color=args.background, num_downscales=args.num_downscales,
                                        resolution_schedule=args.resolution_schedule, tv_pixel_loss_mult=args.tv_pixel_loss_mult,
                                        cross_channel_loss_mult=args.cross_channel_loss_mult, thermal_opacity_mode=args.thermal_opacity_mode,
-                                       opacity_loss_mult=args.opacity_loss_mult, removal_min_opacity_diff=args.removal_min_opacity_diff)
-    model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=dm.num_train_data, seed_points=seed_points)
+                                       opacity_loss_mult=args.opacity_loss_mult, removal_min_opacity_diff=args.removal_min_opacity_diff,
+                                       camera_optimizer=CameraOptimizerConfig(mode=args.camera_optimizer),
+                                       camera_optimizer_thermal=CameraOptimizerConfig(mode=args.camera_optimizer_thermal))
+    model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=dm.num_train_data, seed_points=seed_points,
+                                   train_is_thermal=dm.train_is_thermal)
     initial = model.num_points
-    opts = Optimizers(model.get_param_groups(), SPLAT_OPTIMIZERS, optimizer_cls=HipAdam)
+    opts = Optimizers(model.get_param_groups(), {**SPLAT_OPTIMIZERS, **SPLAT_CAMERA_OPTIMIZERS}, optimizer_cls=HipAdam)
     cbs = model.get_training_callbacks(opts)
     curve = []
     stages = []  # one entry per run of steps at one downscale factor
@@ -187,6 +195,10 @@ def main():
                          "gaussians_kept_share": float(crop_box.within(model.means.detach()).float().mean()) if model.num_points else 0.0}
     model.train()
     metrics = {k: sum(v) / len(v) for k, v in sums.items() if all(math.isfinite(x) for x in v)}
+    pose_norms = {}
+    model.camera_optimizer.get_metrics_dict(pose_norms)
+    model.camera_optimizer_thermal.get_metrics_dict(pose_norms)
+    extra.update({k: float(v) for k, v in pose_norms.items()})  # the refined poses' translation / rotation norms, when a mode is on
     if model.separate:  # the share of Gaussians whose two opacities ended more than 0.5 apart
         gp = model.gauss_params
         gap = (torch.sigmoid(gp["opacities"]) - torch.sigmoid(gp["opacities_thermal"])).abs()
@@ -203,7 +215,8 @@ def main():
                       "ms_per_iteration": 1e3 * train_s / max(args.steps, 1), "num_downscales": args.num_downscales,
                       "resolution_schedule": args.resolution_schedule, "tv_pixel_loss_mult": args.tv_pixel_loss_mult,
                       "cross_channel_loss_mult": args.cross_channel_loss_mult, "undistort": not args.no_undistort, "thermal_opacity_mode": args.thermal_opacity_mode,
-                      "opacity_loss_mult": args.opacity_loss_mult, **extra, "stages": stages, "val_metrics": metrics, "curve": curve}))
+                      "opacity_loss_mult": args.opacity_loss_mult, "camera_optimizer": args.camera_optimizer,
+                      "camera_optimizer_thermal": args.camera_optimizer_thermal, **extra, "stages": stages, "val_metrics": metrics, "curve": curve}))
 
 
 if __name__ == "__main__":
