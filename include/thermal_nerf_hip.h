@@ -793,6 +793,26 @@ TN_API int tn_splat_raster_backward_sep(const TnSplatCamera* camera, int64_t num
                                         const float* transmittance_thermal, const int32_t* last_thermal, const float* conics, const float* v_rgbt,
                                         const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace, int64_t bwd_workspace_bytes, float* v_xys,
                                         float* v_conics, float* v_colors, float* v_log_opacity, float* v_log_opacity_thermal, tn_stream_t stream);
+/* ---- N4 absgrad (AbsGS; gsplat's `absgrad`, splatfacto's `use_absgrad`): the raster backwards above plus the densification statistic
+ * v_xys_abs [N,2] = sum over the pixels p a Gaussian blends of (|J_p.x|, |J_p.y|), where J_p = d sigma_p * (cx dx + cy dy, cy dx + cz dy) is the
+ * pixel's term of v_xys (v_xys = sum_p J_p; in separate mode d sigma_p is the sum of both chains' terms, taken before the absolute value).  A
+ * blend on the 0.999 clamp contributes nothing, a Gaussian without a pair gets (0, 0).  No atomics: bit-reproducible.  Nothing is chained
+ * through v_xys_abs, so the projection backward is unchanged; every other output is bit-equal to the entry point without _abs.  The pair record
+ * grows by two sums: the scratch is sized by the _abs functions below (-1 on bad sizes).  Refusals as tn_splat_raster_backward / _sep, plus a
+ * null v_xys_abs and a bwd_workspace_bytes below the _abs size. */
+TN_API int64_t tn_splat_backward_workspace_bytes_abs(int64_t num_gaussians, int64_t max_intersections);
+TN_API int64_t tn_splat_backward_workspace_bytes_abs_sep(int64_t num_gaussians, int64_t max_intersections);
+TN_API int tn_splat_raster_backward_abs(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                        int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
+                                        const float* conics, const float* v_rgbt, const float* v_alpha, void* bwd_workspace,
+                                        int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors,
+                                        float* v_log_opacity, tn_stream_t stream);
+TN_API int tn_splat_raster_backward_abs_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                            int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
+                                            const float* transmittance_thermal, const int32_t* last_thermal, const float* conics,
+                                            const float* v_rgbt, const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace,
+                                            int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors,
+                                            float* v_log_opacity, float* v_log_opacity_thermal, tn_stream_t stream);
 /* tn_splat_project_backward plus v_opacities_thermal [N] (logits) from v_log_opacity_thermal; in antialiased mode the covariance receives the
  * compensation's gradient from both opacities.  Refuses what tn_splat_project_backward refuses, and null thermal-opacity pointers. */
 TN_API int tn_splat_project_backward_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,

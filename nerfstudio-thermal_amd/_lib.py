@@ -211,6 +211,10 @@ SIGNATURES = {
     "tn_splat_raster_train_sep": (C.c_int, [_p, _i64, _p, _i64, _p, _i32] + [_p] * 8 + [_p]),
     "tn_splat_backward_workspace_bytes_sep": (_i64, [_i64, _i64]),
     "tn_splat_raster_backward_sep": (C.c_int, [_p, _i64, _p, _i64, _i64] + [_p] * 10 + [_i64] + [_p] * 6),
+    "tn_splat_backward_workspace_bytes_abs": (_i64, [_i64, _i64]),
+    "tn_splat_backward_workspace_bytes_abs_sep": (_i64, [_i64, _i64]),
+    "tn_splat_raster_backward_abs": (C.c_int, [_p, _i64, _p, _i64, _i64] + [_p] * 7 + [_i64] + [_p] * 6),
+    "tn_splat_raster_backward_abs_sep": (C.c_int, [_p, _i64, _p, _i64, _i64] + [_p] * 10 + [_i64] + [_p] * 7),
     "tn_splat_project_backward_sep": (C.c_int, [_p] * 10 + [_i64, _i32, _i32, _i32] + [_p] * 16),
     "tn_splat_refine_plan_sep": (C.c_int, [C.POINTER(TnSplatRefine), _i32] + [_p] * 6 + [_i64, _p, _i64, _p, _p]),
     "tn_splat_refine_apply_sep": (C.c_int, [C.POINTER(TnSplatRefine), _i64, _i32, _p, _i64, _p, _p] + [_p] * 6 + [_p]),

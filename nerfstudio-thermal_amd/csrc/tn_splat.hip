@@ -774,9 +774,14 @@ __global__ void __launch_bounds__(256) k_splat_raster_removal(const SplatRec* __
 //                       parameters, written in their own layouts.
 #define SPLAT_PAIR_GRADS 10  // per pair, summed over pixels: dsigma*dx, dsigma*dy, dsigma*dx^2/2, dsigma*dx*dy, dsigma*dy^2/2, d colour (4), d ln(opacity)
 #define SPLAT_PAIR_GRADS_SEP (SPLAT_PAIR_GRADS + 1)  // separate thermal opacity: one more, d ln(thermal opacity)
+// ABS (absgrad, the densification statistic of AbsGS / gsplat): two more slots at the END of the record (after d ln(thermal opacity) in SEP),
+// sum over pixels of |J.x|, |J.y| with J = dsigma * (cx dx + cy dy, cy dx + cz dy) the pixel's term of d xys, both chains added BEFORE the
+// absolute value.  The rasteriser holds the conic only in splat_power's scaled form (A, B, C) = (cx / 2, cy, cz / 2) log2(e), so the slots carry
+// log2(e) |J| = |dsigma (2A dx + B dy)|, |dsigma (B dx + 2C dy)| (the doubling is exact) and k_splat_pair_fold multiplies the sum by ln 2.
+#define SPLAT_PAIR_ABS 2
 
 struct SplatBwdWs {
-  float* pair;     // [max_intersections][SPLAT_PAIR_GRADS or SPLAT_PAIR_GRADS_SEP]
+  float* pair;     // [max_intersections][SPLAT_PAIR_GRADS or SPLAT_PAIR_GRADS_SEP (+ SPLAT_PAIR_ABS)]
   int32_t* start;  // [N] first record of each Gaussian's run
 };
 
@@ -803,6 +808,20 @@ extern "C" int64_t tn_splat_backward_workspace_bytes_sep(int64_t num_gaussians, 
   return (int64_t)total;
 }
 
+extern "C" int64_t tn_splat_backward_workspace_bytes_abs(int64_t num_gaussians, int64_t max_intersections) {
+  if (num_gaussians < 0 || max_intersections < 0) return -1;
+  size_t total = 0;
+  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, SPLAT_PAIR_GRADS + SPLAT_PAIR_ABS, &total);
+  return (int64_t)total;
+}
+
+extern "C" int64_t tn_splat_backward_workspace_bytes_abs_sep(int64_t num_gaussians, int64_t max_intersections) {
+  if (num_gaussians < 0 || max_intersections < 0) return -1;
+  size_t total = 0;
+  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, SPLAT_PAIR_GRADS_SEP + SPLAT_PAIR_ABS, &total);
+  return (int64_t)total;
+}
+
 // start of Gaussian order[j]'s run of pairs: cum is the inclusive scan of the tight tile counts in depth order
 __global__ void k_splat_run_start(const int32_t* __restrict__ order, const int32_t* __restrict__ cum, const int32_t* __restrict__ thits, int64_t N,
                                   int32_t* __restrict__ start) {
@@ -816,7 +835,9 @@ __global__ void k_splat_run_start(const int32_t* __restrict__ order, const int32
 // v_alpha feed chain 1 (alpha from SplatRec::b.y), the thermal channel and v_alpha_th chain 2 (alpha from SplatRec::d.w); the five geometry sums
 // receive both chains' d_sigma, and the pair record grows by d ln(thermal opacity).  SEP = false is the kernel as it was.
 // sep_args (SEP only): const float* final_T_th, const int32_t* last_th, const float* v_alpha_th.
-template <bool SEP, typename... SepArgs>
+// ABS: the record grows by the SPLAT_PAIR_ABS slots, which take the path of the others (lane, butterfly, sp, four waves in order, one write).
+// ABS = false is the kernel as it was.  Static LDS: 61 440 B, SEP 66 560 B (gfx950 has 160 KB per CU: two blocks per CU as before).
+template <bool SEP, bool ABS, typename... SepArgs>
 __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __restrict__ recs, const int32_t* __restrict__ sorted_ids,
                                                           const int32_t* __restrict__ tile_bins, const int32_t* __restrict__ tile_order, int W, int H,
                                                           int tbx, float4 background, const float* __restrict__ final_T, const int32_t* __restrict__ last,
@@ -824,7 +845,8 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
                                                           const int32_t* __restrict__ start, const int32_t* __restrict__ tbox, float* __restrict__ pair,
                                                           SepArgs... sep_args) {
   static_assert(sizeof...(SepArgs) == (SEP ? 3 : 0), "SEP takes final_T_th, last_th, v_alpha_th");
-  constexpr int NG = SEP ? SPLAT_PAIR_GRADS_SEP : SPLAT_PAIR_GRADS;
+  constexpr int NG = (SEP ? SPLAT_PAIR_GRADS_SEP : SPLAT_PAIR_GRADS) + (ABS ? SPLAT_PAIR_ABS : 0);
+  constexpr int TH = SEP ? SPLAT_PAIR_GRADS : NG - 1;  // SEP: the slot of d ln(thermal opacity)
   __shared__ float4 sa[SPLAT_BATCH], sb[SPLAT_BATCH], sc[SPLAT_BATCH];
   float* l2t = nullptr;  // SEP: l2op of the thermal chain (SplatRec::d.w) of the batch's Gaussians
   if constexpr (SEP) {
@@ -947,8 +969,12 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
             const float d_sigma = -d_lnop;
             g[0] += d_sigma * dx; g[1] += d_sigma * dy;
             g[2] += 0.5f * d_sigma * dx * dx; g[3] += d_sigma * dx * dy; g[4] += 0.5f * d_sigma * dy * dy;
-            g[NG - 1] = d_lnop;
+            g[TH] = d_lnop;
           }
+        }
+        if constexpr (ABS) {  // g[0], g[1] = dsigma dx, dsigma dy of this pixel, both chains added (0 on the clamp and for a lane that does not blend)
+          g[NG - 2] = fabsf((a.z + a.z) * g[0] + a.w * g[1]);
+          g[NG - 1] = fabsf(a.w * g[0] + (b.x + b.x) * g[1]);
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1)
@@ -969,10 +995,15 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
   }
 }
 
-template <int NG>  // SPLAT_PAIR_GRADS, or SPLAT_PAIR_GRADS_SEP: the last sum is d ln(thermal opacity) -> v_lnop_th
+// NG = SPLAT_PAIR_GRADS, or SPLAT_PAIR_GRADS_SEP: the sum after the ten is d ln(thermal opacity) -> v_lnop_th.  abs_args (ABS only, NG is then
+// SPLAT_PAIR_ABS larger): float* v_xys_abs [N,2], the record's last two sums times ln 2 (see SPLAT_PAIR_ABS).  Without it the kernel as it was.
+template <int NG, typename... AbsArgs>
 __global__ void k_splat_pair_fold(const float* __restrict__ pair, const int32_t* __restrict__ start, const int32_t* __restrict__ thits,
                                   const float* __restrict__ conics, int64_t N, float* __restrict__ v_xys, float* __restrict__ v_conics,
-                                  float* __restrict__ v_colors, float* __restrict__ v_lnop, float* __restrict__ v_lnop_th) {
+                                  float* __restrict__ v_colors, float* __restrict__ v_lnop, float* __restrict__ v_lnop_th, AbsArgs... abs_args) {
+  constexpr bool ABS = sizeof...(AbsArgs) == 1;
+  static_assert(sizeof...(AbsArgs) <= 1 && (NG - (ABS ? SPLAT_PAIR_ABS : 0) == SPLAT_PAIR_GRADS || NG - (ABS ? SPLAT_PAIR_ABS : 0) == SPLAT_PAIR_GRADS_SEP),
+                "ABS takes v_xys_abs and SPLAT_PAIR_ABS more sums");
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= N) return;
   float s[NG];
@@ -992,7 +1023,13 @@ __global__ void k_splat_pair_fold(const float* __restrict__ pair, const int32_t*
   v_conics[3 * i] = s[2]; v_conics[3 * i + 1] = s[3]; v_conics[3 * i + 2] = s[4];
   v_colors[4 * i] = s[5]; v_colors[4 * i + 1] = s[6]; v_colors[4 * i + 2] = s[7]; v_colors[4 * i + 3] = s[8];
   v_lnop[i] = s[9];
-  if (NG > SPLAT_PAIR_GRADS) v_lnop_th[i] = s[NG - 1];
+  constexpr bool SEP = NG - (ABS ? SPLAT_PAIR_ABS : 0) > SPLAT_PAIR_GRADS;
+  if (SEP) v_lnop_th[i] = s[SEP ? SPLAT_PAIR_GRADS : NG - 1];
+  if constexpr (ABS) {
+    float* v_xys_abs = pack_arg<0>(abs_args...);
+    v_xys_abs[2 * i] = s[NG - 2] * 0.6931471805599453f;
+    v_xys_abs[2 * i + 1] = s[NG - 1] * 0.6931471805599453f;
+  }
 }
 
 // SH basis of degree <= 3 at the unit direction (x, y, z), the coefficients of sh_eval
@@ -1703,11 +1740,11 @@ extern "C" int tn_splat_raster_train_sep(const TnSplatCamera* camera, int64_t nu
                       out_rgbt, out_depth, out_alpha, out_transmittance, out_last, out_alpha_thermal, out_transmittance_thermal, out_last_thermal, stream);
 }
 
-static int splat_raster_backward(const char* who, bool sep, const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+static int splat_raster_backward(const char* who, bool sep, bool absgrad, const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
                                  int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
                                  const float* transmittance_th, const int32_t* last_th, const float* conics, const float* v_rgbt, const float* v_alpha,
-                                 const float* v_alpha_th, void* bwd_workspace, int64_t bwd_workspace_bytes, float* v_xys, float* v_conics, float* v_colors,
-                                 float* v_log_opacity, float* v_log_opacity_th, tn_stream_t stream) {
+                                 const float* v_alpha_th, void* bwd_workspace, int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics,
+                                 float* v_colors, float* v_log_opacity, float* v_log_opacity_th, tn_stream_t stream) {
   int rc = check_cam(camera, who);
   if (rc) return rc;
   TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31), "%s: bad Gaussian count", who);
@@ -1715,10 +1752,12 @@ static int splat_raster_backward(const char* who, bool sep, const TnSplatCamera*
              (long long)num_intersections, (long long)max_intersections);
   if (num_gaussians == 0) return TN_OK;
   TN_REQUIRE(workspace && background4 && transmittance && last && conics && v_rgbt && v_alpha && bwd_workspace && v_xys && v_conics && v_colors &&
-                 v_log_opacity && (!sep || (transmittance_th && last_th && v_alpha_th && v_log_opacity_th)),
+                 v_log_opacity && (!sep || (transmittance_th && last_th && v_alpha_th && v_log_opacity_th)) && (!absgrad || v_xys_abs),
              "%s: null pointer", who);
-  const int ng = sep ? SPLAT_PAIR_GRADS_SEP : SPLAT_PAIR_GRADS;
-  const int64_t need = sep ? tn_splat_backward_workspace_bytes_sep(num_gaussians, max_intersections) : tn_splat_backward_workspace_bytes(num_gaussians, max_intersections);
+  const int ng = (sep ? SPLAT_PAIR_GRADS_SEP : SPLAT_PAIR_GRADS) + (absgrad ? SPLAT_PAIR_ABS : 0);
+  size_t need_sz = 0;
+  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, ng, &need_sz);
+  const int64_t need = (int64_t)need_sz;
   TN_REQUIRE(bwd_workspace_bytes >= need, "%s: backward workspace of %lld bytes, %lld needed", who, (long long)bwd_workspace_bytes, (long long)need);
   SplatCamK k = make_camk(camera);
   const int num_tiles = k.tbx * k.tby;
@@ -1734,16 +1773,29 @@ static int splat_raster_backward(const char* who, bool sep, const TnSplatCamera*
       return TN_ELAUNCH;
     }
     float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
-    if (sep)
-      hipLaunchKernelGGL((k_splat_raster_bwd<true, const float*, const int32_t*, const float*>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins,
-                         ws.lvals[1], k.W, k.H, k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, transmittance_th, last_th, v_alpha_th);
+    if (sep && absgrad)
+      hipLaunchKernelGGL((k_splat_raster_bwd<true, true, const float*, const int32_t*, const float*>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1],
+                         ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, transmittance_th, last_th,
+                         v_alpha_th);
+    else if (sep)
+      hipLaunchKernelGGL((k_splat_raster_bwd<true, false, const float*, const int32_t*, const float*>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1],
+                         ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, transmittance_th, last_th,
+                         v_alpha_th);
+    else if (absgrad)
+      hipLaunchKernelGGL((k_splat_raster_bwd<false, true>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg,
+                         transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair);
     else
-      hipLaunchKernelGGL(k_splat_raster_bwd<false>, dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg,
+      hipLaunchKernelGGL((k_splat_raster_bwd<false, false>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg,
                          transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair);
     TN_CHECK_LAUNCH(who);
   }
-  hipLaunchKernelGGL(sep ? k_splat_pair_fold<SPLAT_PAIR_GRADS_SEP> : k_splat_pair_fold<SPLAT_PAIR_GRADS>, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, st,
-                     bw.pair, bw.start, ws.thits, conics, num_gaussians, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_th);
+  const dim3 fold_grid((unsigned)tn_cdiv(num_gaussians, 256));
+  if (absgrad)
+    hipLaunchKernelGGL((sep ? k_splat_pair_fold<SPLAT_PAIR_GRADS_SEP + SPLAT_PAIR_ABS, float*> : k_splat_pair_fold<SPLAT_PAIR_GRADS + SPLAT_PAIR_ABS, float*>), fold_grid,
+                       dim3(256), 0, st, bw.pair, bw.start, ws.thits, conics, num_gaussians, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_th, v_xys_abs);
+  else
+    hipLaunchKernelGGL(sep ? k_splat_pair_fold<SPLAT_PAIR_GRADS_SEP> : k_splat_pair_fold<SPLAT_PAIR_GRADS>, fold_grid, dim3(256), 0, st, bw.pair, bw.start, ws.thits,
+                       conics, num_gaussians, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_th);
   TN_CHECK_LAUNCH(who);
   return TN_OK;
 }
@@ -1753,8 +1805,8 @@ extern "C" int tn_splat_raster_backward(const TnSplatCamera* camera, int64_t num
                                         const float* conics, const float* v_rgbt, const float* v_alpha, void* bwd_workspace,
                                         int64_t bwd_workspace_bytes, float* v_xys, float* v_conics, float* v_colors, float* v_log_opacity,
                                         tn_stream_t stream) {
-  return splat_raster_backward("tn_splat_raster_backward", false, camera, num_gaussians, workspace, max_intersections, num_intersections, background4, transmittance,
-                               last, nullptr, nullptr, conics, v_rgbt, v_alpha, nullptr, bwd_workspace, bwd_workspace_bytes, v_xys, v_conics, v_colors,
+  return splat_raster_backward("tn_splat_raster_backward", false, false, camera, num_gaussians, workspace, max_intersections, num_intersections, background4, transmittance,
+                               last, nullptr, nullptr, conics, v_rgbt, v_alpha, nullptr, bwd_workspace, bwd_workspace_bytes, v_xys, nullptr, v_conics, v_colors,
                                v_log_opacity, nullptr, stream);
 }
 
@@ -1763,9 +1815,32 @@ extern "C" int tn_splat_raster_backward_sep(const TnSplatCamera* camera, int64_t
                                             const float* transmittance_thermal, const int32_t* last_thermal, const float* conics, const float* v_rgbt,
                                             const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace, int64_t bwd_workspace_bytes, float* v_xys,
                                             float* v_conics, float* v_colors, float* v_log_opacity, float* v_log_opacity_thermal, tn_stream_t stream) {
-  return splat_raster_backward("tn_splat_raster_backward_sep", true, camera, num_gaussians, workspace, max_intersections, num_intersections, background4,
+  return splat_raster_backward("tn_splat_raster_backward_sep", true, false, camera, num_gaussians, workspace, max_intersections, num_intersections, background4,
                                transmittance, last, transmittance_thermal, last_thermal, conics, v_rgbt, v_alpha, v_alpha_thermal, bwd_workspace,
-                               bwd_workspace_bytes, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, stream);
+                               bwd_workspace_bytes, v_xys, nullptr, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, stream);
+}
+
+// The two entry points above with the absgrad statistic: v_xys_abs [N,2] = sum over pixels of |the pixel's term of v_xys|, per component
+// (SPLAT_PAIR_ABS).  The workspace is tn_splat_backward_workspace_bytes_abs / _abs_sep; every other output is bit-equal to the entry point without _abs.
+extern "C" int tn_splat_raster_backward_abs(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                            int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
+                                            const float* conics, const float* v_rgbt, const float* v_alpha, void* bwd_workspace,
+                                            int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors,
+                                            float* v_log_opacity, tn_stream_t stream) {
+  return splat_raster_backward("tn_splat_raster_backward_abs", false, true, camera, num_gaussians, workspace, max_intersections, num_intersections, background4,
+                               transmittance, last, nullptr, nullptr, conics, v_rgbt, v_alpha, nullptr, bwd_workspace, bwd_workspace_bytes, v_xys, v_xys_abs, v_conics,
+                               v_colors, v_log_opacity, nullptr, stream);
+}
+
+extern "C" int tn_splat_raster_backward_abs_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                                int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
+                                                const float* transmittance_thermal, const int32_t* last_thermal, const float* conics, const float* v_rgbt,
+                                                const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace, int64_t bwd_workspace_bytes,
+                                                float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors, float* v_log_opacity,
+                                                float* v_log_opacity_thermal, tn_stream_t stream) {
+  return splat_raster_backward("tn_splat_raster_backward_abs_sep", true, true, camera, num_gaussians, workspace, max_intersections, num_intersections, background4,
+                               transmittance, last, transmittance_thermal, last_thermal, conics, v_rgbt, v_alpha, v_alpha_thermal, bwd_workspace,
+                               bwd_workspace_bytes, v_xys, v_xys_abs, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, stream);
 }
 
 struct PoseBwdArgs {  // what the pose entry points add to the projection backward (null: the entry points without _pose)

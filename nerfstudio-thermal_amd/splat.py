@@ -117,6 +117,12 @@ class ThermalSplatfactoModelConfig:
     continue_cull_post_densification: bool = True
     reset_alpha_every: int = 30
     densify_grad_thresh: float = 0.0002
+    # AbsGS's statistic (gsplat's `absgrad`, splatfacto's `use_absgrad`): densify on the norm of sum over pixels |d L_p / d xys| per component
+    # instead of |sum over pixels d L_p / d xys|, whose pixel terms cancel on a large Gaussian over fine structure (tn_splat_raster_backward_abs;
+    # `last_xys_absgrad`).  The absolute statistic is several times the signed one (a median 3.5 to 12.5 times on the backward test scenes), so
+    # densify_grad_thresh wants raising with it: gsplat's documentation advises about 0.0008 with absgrad where 0.0002 is used without.  The
+    # default above is NOT changed by the flag, and no scene has been trained here to pick a value.
+    use_absgrad: bool = False
     densify_size_thresh: float = 0.01
     n_split_samples: int = 2
     cull_screen_size: float = 0.15
@@ -862,8 +868,10 @@ class _SplatRender(torch.autograd.Function):
         means = params[0]
         N, dev = means.shape[0], means.device
         pose, row = ctx.pose, frame.get("pose_row")
+        absgrad = bool(model.config.use_absgrad)  # the _abs entry points: the same gradients plus last_xys_absgrad, the densification statistic
         if ctx.empty:
             model.last_xys_grad = torch.zeros((N, 2), device=dev)
+            model.last_xys_absgrad = torch.zeros((N, 2), device=dev) if absgrad else None
             return (None,) + tuple(torch.zeros_like(p) for p in params) + ((torch.zeros_like(pose),) if pose is not None else ())
         radii, conics, final_t, last = saved[P:P + 4]
         lib = _lib.load()
@@ -872,9 +880,15 @@ class _SplatRender(torch.autograd.Function):
         H, W = final_t.shape
         v_rgbt = torch.zeros((H, W, 4), device=dev) if v_rgbt is None else v_rgbt.float().contiguous()
         v_alpha = torch.zeros((H, W, 1), device=dev) if v_alpha is None else v_alpha.float().contiguous()
-        need = int((lib.tn_splat_backward_workspace_bytes_sep if sep else lib.tn_splat_backward_workspace_bytes)(N, ctx.cap))
+        if absgrad:
+            need = int((lib.tn_splat_backward_workspace_bytes_abs_sep if sep else lib.tn_splat_backward_workspace_bytes_abs)(N, ctx.cap))
+        else:
+            need = int((lib.tn_splat_backward_workspace_bytes_sep if sep else lib.tn_splat_backward_workspace_bytes)(N, ctx.cap))
         bws = torch.empty(need, dtype=torch.uint8, device=dev)
         v_xys = torch.empty((N, 2), device=dev)
+        v_xys_abs = torch.empty((N, 2), device=dev) if absgrad else None
+        model.last_xys_absgrad = v_xys_abs
+        xys_ptrs = (_ptr(v_xys, f32, "v_xys"),) + ((_ptr(v_xys_abs, f32, "v_xys_abs"),) if absgrad else ())
         v_conics = torch.empty((N, 3), device=dev)
         v_colors = torch.empty((N, 4), device=dev)
         v_lnop = torch.empty((N,), device=dev)
@@ -882,13 +896,13 @@ class _SplatRender(torch.autograd.Function):
             final_t_th, last_th = saved[P + 4:]
             v_alpha_th = torch.zeros((H, W, 1), device=dev) if v_alpha_th is None else v_alpha_th.float().contiguous()
             v_lnop_th = torch.empty((N,), device=dev)
-            _lib.check(lib.tn_splat_raster_backward_sep(C.byref(cam), N, C.c_void_p(ctx.ws.data_ptr()), ctx.cap, ctx.total, bg4, _ptr(final_t, f32, "transmittance"),
-                                                        _ptr(last, torch.int32, "last"), _ptr(final_t_th, f32, "transmittance_thermal"),
-                                                        _ptr(last_th, torch.int32, "last_thermal"), _ptr(conics, f32, "conics"), _ptr(v_rgbt, f32, "v_rgbt"),
-                                                        _ptr(v_alpha, f32, "v_alpha"), _ptr(v_alpha_th, f32, "v_alpha_thermal"), C.c_void_p(bws.data_ptr()), need,
-                                                        _ptr(v_xys, f32, "v_xys"), _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"),
-                                                        _ptr(v_lnop, f32, "v_log_opacity"), _ptr(v_lnop_th, f32, "v_log_opacity_thermal"), _stream()),
-                       "tn_splat_raster_backward_sep")
+            name = "tn_splat_raster_backward_abs_sep" if absgrad else "tn_splat_raster_backward_sep"
+            _lib.check(getattr(lib, name)(C.byref(cam), N, C.c_void_p(ctx.ws.data_ptr()), ctx.cap, ctx.total, bg4, _ptr(final_t, f32, "transmittance"),
+                                          _ptr(last, torch.int32, "last"), _ptr(final_t_th, f32, "transmittance_thermal"),
+                                          _ptr(last_th, torch.int32, "last_thermal"), _ptr(conics, f32, "conics"), _ptr(v_rgbt, f32, "v_rgbt"),
+                                          _ptr(v_alpha, f32, "v_alpha"), _ptr(v_alpha_th, f32, "v_alpha_thermal"), C.c_void_p(bws.data_ptr()), need,
+                                          *xys_ptrs, _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"),
+                                          _ptr(v_lnop, f32, "v_log_opacity"), _ptr(v_lnop_th, f32, "v_log_opacity_thermal"), _stream()), name)
             grads = [torch.empty_like(p) for p in params]
             if pose is not None:
                 g_pose = _project_backward_pose(model, lib.tn_splat_project_backward_pose_sep, "tn_splat_project_backward_pose_sep", cam, ctx.rec, pose, row,
@@ -901,11 +915,11 @@ class _SplatRender(torch.autograd.Function):
                                                          _stream()), "tn_splat_project_backward_sep")
             model.last_xys_grad = v_xys
             return (None,) + tuple(grads)
-        _lib.check(lib.tn_splat_raster_backward(C.byref(cam), N, C.c_void_p(ctx.ws.data_ptr()), ctx.cap, ctx.total, bg4, _ptr(final_t, f32, "transmittance"),
-                                                _ptr(last, torch.int32, "last"), _ptr(conics, f32, "conics"), _ptr(v_rgbt, f32, "v_rgbt"),
-                                                _ptr(v_alpha, f32, "v_alpha"), C.c_void_p(bws.data_ptr()), need, _ptr(v_xys, f32, "v_xys"),
-                                                _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"), _ptr(v_lnop, f32, "v_log_opacity"), _stream()),
-                   "tn_splat_raster_backward")
+        name = "tn_splat_raster_backward_abs" if absgrad else "tn_splat_raster_backward"
+        _lib.check(getattr(lib, name)(C.byref(cam), N, C.c_void_p(ctx.ws.data_ptr()), ctx.cap, ctx.total, bg4, _ptr(final_t, f32, "transmittance"),
+                                      _ptr(last, torch.int32, "last"), _ptr(conics, f32, "conics"), _ptr(v_rgbt, f32, "v_rgbt"),
+                                      _ptr(v_alpha, f32, "v_alpha"), C.c_void_p(bws.data_ptr()), need, *xys_ptrs,
+                                      _ptr(v_conics, f32, "v_conics"), _ptr(v_colors, f32, "v_colors"), _ptr(v_lnop, f32, "v_log_opacity"), _stream()), name)
         grads = [torch.empty_like(p) for p in params]
         if pose is not None:
             g_pose = _project_backward_pose(model, lib.tn_splat_project_backward_pose, "tn_splat_project_backward_pose", cam, ctx.rec, pose, row, params,
@@ -1043,6 +1057,7 @@ class ThermalSplatfactoModel(nn.Module):
         self._cap = 0
         self._train_cap = 0  # intersection capacity the training render last needed (each training frame has a workspace of its own)
         self.last_xys_grad: Optional[Tensor] = None
+        self.last_xys_absgrad: Optional[Tensor] = None  # use_absgrad: sum over pixels of |the pixel's term of last_xys_grad| [N,2]; else None
         self.last_projection: Dict[str, Tensor] = {}
         self.last_num_intersections = 0
         self.last_radii: Optional[Tensor] = None  # radii [N] and (H, W) of the last TRAINING frame
@@ -1232,7 +1247,8 @@ class ThermalSplatfactoModel(nn.Module):
         """The render of get_outputs as a differentiable function of every gauss_params tensor (splatfacto.py:659-822 in training: `crop_box`
         is not read, the reference crops only outside training).  rgb [H,W,3], thermal [H,W,1] and accumulation [H,W,1] carry gradients; depth [H,W,1] is detached.  With a fixed
         background the values equal get_outputs' bit for bit; background_color "random" draws this frame's RGB + thermal background from the
-        model's generator (background [3], background_thermal [1]).  After backward(), `last_xys_grad` [N,2] holds dL/d xys per Gaussian.
+        model's generator (background [3], background_thermal [1]).  After backward(), `last_xys_grad` [N,2] holds dL/d xys per Gaussian
+        (and, with config.use_absgrad, `last_xys_absgrad` [N,2] the sum of its per-pixel terms' absolute values).
         Under the resolution schedule the frame is that of `rescaled_camera(camera, d)` (splatfacto.py:699-700): its size is what `last_size`,
         `last_radii`, `last_xys_grad` and the refinement statistics refer to; `camera` is not modified."""
         d = self._get_downscale_factor()
@@ -1243,6 +1259,7 @@ class ThermalSplatfactoModel(nn.Module):
         names = self.param_names
         frame = {"model": self, "camera": camera, "cam": camera_struct(camera), "aa": aa, "deg": deg, "bg4": (C.c_float * 4)(*bgl), "num_params": len(names)}
         self.last_xys_grad = None
+        self.last_xys_absgrad = None
         pose, row = self._pose_row(camera, training=True)
         if row is not None:  # the frame's pose row: one more differentiable input
             frame["pose_row"] = row
@@ -1412,14 +1429,16 @@ class ThermalSplatfactoModel(nn.Module):
 
     @torch.no_grad()
     def after_train(self, step: int) -> None:
-        """splatfacto.py:346-372 on the last training frame (its radii, size and, after backward(), last_xys_grad): tn_splat_grad_stats."""
+        """splatfacto.py:346-372 on the last training frame (its radii, size and, after backward(), last_xys_grad): tn_splat_grad_stats.
+        With config.use_absgrad the statistic accumulated is the norm of last_xys_absgrad instead."""
         assert step == self.step
         if self.step >= self.config.stop_split_at:
             return
-        if self.last_xys_grad is None or self.last_radii is None or self.last_size is None:
+        xys_grad = self.last_xys_absgrad if self.config.use_absgrad else self.last_xys_grad
+        if xys_grad is None or self.last_radii is None or self.last_size is None:
             raise RuntimeError("after_train needs a get_train_outputs() frame and its backward()")
         N, dev = self.num_points, self.means.device
-        if self.last_radii.shape[0] != N or self.last_xys_grad.shape[0] != N:
+        if self.last_radii.shape[0] != N or xys_grad.shape[0] != N:
             raise RuntimeError("after_train: the Gaussians changed since the last training frame")
         first = self.xys_grad_norm is None
         if first:
@@ -1427,7 +1446,7 @@ class ThermalSplatfactoModel(nn.Module):
             self.vis_counts = torch.empty(N, device=dev)
             self.max_2Dsize = torch.empty(N, device=dev)
         f32 = torch.float32
-        _lib.check(_lib.load().tn_splat_grad_stats(_ptr(self.last_xys_grad.contiguous(), f32, "xys_grad"), _ptr(self.last_radii, torch.int32, "radii"), N,
+        _lib.check(_lib.load().tn_splat_grad_stats(_ptr(xys_grad.contiguous(), f32, "xys_grad"), _ptr(self.last_radii, torch.int32, "radii"), N,
                                                    max(self.last_size), int(first), _ptr(self.xys_grad_norm, f32, "grad_norm_sum"),
                                                    _ptr(self.vis_counts, f32, "vis_counts"), _ptr(self.max_2Dsize, f32, "max_2d_size"), _stream()),
                    "tn_splat_grad_stats")

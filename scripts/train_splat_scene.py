@@ -116,6 +116,9 @@ def main():
                     help="refine the RGB frames' poses: a row per training frame, or one shared row (also applied to eval renders)")
     ap.add_argument("--camera-optimizer-thermal", default="off", choices=("off", "SO3xR3", "shared_SO3xR3"),
                     help="the same for the thermal frames (shared_SO3xR3: a mis-registered thermal rig)")
+    ap.add_argument("--use-absgrad", action="store_true",
+                    help="densify on the absolute 2D-mean gradients (AbsGS); raise --densify-grad-thresh with it (gsplat advises about 0.0008)")
+    ap.add_argument("--densify-grad-thresh", type=float, default=0.0002)
     ap.add_argument("--no-undistort", action="store_true", help="train on the raw frames with the parser's intrinsics (the distortion dropped)")
     args = ap.parse_args()
     if args.seed_points and args.data is not None:
@@ -147,7 +150,8 @@ def main():
                                        cross_channel_loss_mult=args.cross_channel_loss_mult, thermal_opacity_mode=args.thermal_opacity_mode,
                                        opacity_loss_mult=args.opacity_loss_mult, removal_min_opacity_diff=args.removal_min_opacity_diff,
                                        camera_optimizer=CameraOptimizerConfig(mode=args.camera_optimizer),
-                                       camera_optimizer_thermal=CameraOptimizerConfig(mode=args.camera_optimizer_thermal))
+                                       camera_optimizer_thermal=CameraOptimizerConfig(mode=args.camera_optimizer_thermal), use_absgrad=args.use_absgrad,
+                                       densify_grad_thresh=args.densify_grad_thresh)
     model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=dm.num_train_data, seed_points=seed_points,
                                    train_is_thermal=dm.train_is_thermal)
     initial = model.num_points
