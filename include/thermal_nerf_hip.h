@@ -1003,6 +1003,46 @@ TN_API int64_t tn_knn_workspace_bytes(int64_t n, int32_t k);
  * TN_EINVAL before any launch: k outside 1..8, n < 0 or n > INT32_MAX, null pointers, n < k + 1, a short workspace. */
 TN_API int tn_knn(const float* points, int64_t n, int32_t k, float* out_dist, int32_t* out_index, void* workspace, int64_t workspace_bytes,
                   tn_stream_t stream);
+
+/* ---- N4 training, MCMC strategy (ThermalSplatfactoModelConfig.strategy = "mcmc": "3D Gaussian Splatting as Markov Chain Monte Carlo", gsplat's
+ * MCMCStrategy): a fixed budget of Gaussians; dead ones are moved onto live ones, the population grows to its cap, and position noise keeps the
+ * faint ones exploring.  tests/splat_mcmc_functional.py restates both operations in float64.
+ *
+ * tn_splat_mcmc_relocate: num_draws draws (src_idx[j] -> dst_idx[j]; both DEVICE int64 [num_draws]) on tensors of num_rows rows, in place.
+ * params / exp_avg / exp_avg_sq: HOST arrays of 8 device pointers in tn_splat_refine_apply's order (K = num_rest_coeffs; the two rest entries are
+ * ignored when K = 0); a parameter's two moment pointers are both null (no Adam state) or both set.  With ratio r = min(1 + the number of times a
+ * source row was drawn, 51), o = sigmoid(opacity) and s = exp(log-scale) of the source BEFORE the call:
+ *   o' = clamp(1 - (1 - o)^(1/r), min_opacity, 1 - FLT_EPSILON), stored as log(o' / (1 - o'));
+ *   p' = 1 - (1 - o)^(1/r) unclamped, denom = sum_{i=1..r} sum_{k=0..i-1} binom(i-1, k) (-1)^k p'^(k+1) / sqrt(k+1), s' = (o / denom) s, stored as
+ *   log s', on all three axes -- evaluated in double from the fp32 inputs and rounded once (r = 1: the identity up to the clamp).
+ * Every drawn source row takes (o', s') once, however often it was drawn, and both Adam moments of that row become zero in every tensor.  Every
+ * destination row becomes a copy of its source's row in every tensor, with (o', s'); its moments stay what they were.  Rows not named are
+ * untouched.  The caller's rule: no destination is also a source, no destination repeats (relocation: the dead rows; growth: rows appended with
+ * zero moments before the call).  A draw with an index outside [0, num_rows) is skipped.  The draw counts use integer atomics on the zeroed
+ * workspace, so the result is bit-reproducible.  No host synchronisation.  num_draws == 0 launches nothing.  Refused with TN_EINVAL before any
+ * launch: num_rows or num_draws negative or above INT32_MAX, draws on no rows, K outside 0..15, min_opacity outside (0, 1), null pointers, partly
+ * null moments, a short workspace.
+ *
+ * scratch of tn_splat_mcmc_relocate (a counter and five values per row, a flag per draw); -1 on bad sizes */
+TN_API int64_t tn_splat_mcmc_workspace_bytes(int64_t num_rows, int64_t num_draws);
+TN_API int tn_splat_mcmc_relocate(int64_t num_rows, int32_t num_rest_coeffs, const int64_t* src_idx, const int64_t* dst_idx, int64_t num_draws,
+                                  float min_opacity, float* const* params, float* const* exp_avg, float* const* exp_avg_sq, void* workspace,
+                                  int64_t workspace_bytes, tn_stream_t stream);
+/* the same over HOST arrays of 9 device pointers (tn_splat_refine_apply_sep's order: opacities_thermal [N,1] last): the thermal opacity takes its own
+ * o_th' by the same rule, and the scale follows the larger of the two opacities (a tie goes to o) */
+TN_API int tn_splat_mcmc_relocate_sep(int64_t num_rows, int32_t num_rest_coeffs, const int64_t* src_idx, const int64_t* dst_idx, int64_t num_draws,
+                                      float min_opacity, float* const* params, float* const* exp_avg, float* const* exp_avg_sq, void* workspace,
+                                      int64_t workspace_bytes, tn_stream_t stream);
+/* The position noise of one training step, in place: means [N,3] += Sigma (randn * g * scaler) with Sigma = R diag(exp(log_scales)^2) R^T,
+ * R the rotation of quats / |quats| (w x y z, the projection's convention), g = 1 / (1 + exp(-100 ((1 - o) - 0.995))), o = sigmoid(opacities),
+ * randn [N,3] standard normal draws, scaler = noise_lr times the means' learning rate.  One launch, one thread per Gaussian, fp32, no [N,3,3]
+ * temporary; memory-bound at 68 bytes per Gaussian.  quats must be 16-byte aligned.  num_gaussians == 0 launches nothing.  Refused with TN_EINVAL
+ * before any launch: a count that is negative or above INT32_MAX, null pointers, a scaler that is negative or not finite. */
+TN_API int tn_splat_mcmc_noise(float* means, const float* log_scales, const float* quats, const float* opacities, const float* randn,
+                               int64_t num_gaussians, float scaler, tn_stream_t stream);
+/* the same with o = max(sigmoid(opacities), sigmoid(opacities_thermal)): a Gaussian visible in either spectrum is left in place */
+TN_API int tn_splat_mcmc_noise_sep(float* means, const float* log_scales, const float* quats, const float* opacities, const float* opacities_thermal,
+                                   const float* randn, int64_t num_gaussians, float scaler, tn_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

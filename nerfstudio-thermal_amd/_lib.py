@@ -237,6 +237,12 @@ SIGNATURES = {
     "tn_thermal_reg": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _f, _f, _p, _i64, _p, _p, _p]),
     "tn_knn_workspace_bytes": (_i64, [_i64, _i32]),
     "tn_knn": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _i64, _p]),
+    # MCMC strategy: relocation / growth in place (8 or 9 tensors with their moments) and the per-step position noise
+    "tn_splat_mcmc_workspace_bytes": (_i64, [_i64, _i64]),
+    "tn_splat_mcmc_relocate": (C.c_int, [_i64, _i32, _p, _p, _i64, _f, _p, _p, _p, _p, _i64, _p]),
+    "tn_splat_mcmc_relocate_sep": (C.c_int, [_i64, _i32, _p, _p, _i64, _f, _p, _p, _p, _p, _i64, _p]),
+    "tn_splat_mcmc_noise": (C.c_int, [_p] * 5 + [_i64, _f, _p]),
+    "tn_splat_mcmc_noise_sep": (C.c_int, [_p] * 6 + [_i64, _f, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

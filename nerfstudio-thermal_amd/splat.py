@@ -57,7 +57,18 @@ spectrum -- a mis-registered thermal rig -- eval renders too) a frame reads the 
 c2w' = c2w [A(p); 0 0 0 1] with A = exp_map_SO3xR3, and `get_train_outputs` is differentiable in it: the corrected camera is built on the device
 (tn_splat_pose_camera), the pose instantiations of the projection kernels read it (tn_splat_project_pose / tn_splat_project_backward_pose), and
 the backward reduces dL/d view' over the Gaussians without atomics, bit-reproducibly; the SH view directions take the corrected position as a
-value (splatfacto.py:770).  Both modes default to "off", which changes nothing.  Masks are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
+value (splatfacto.py:770).  Both modes default to "off", which changes nothing.  Densification has a second strategy,
+`strategy` = "mcmc" ("3D Gaussian Splatting as Markov Chain Monte Carlo": gsplat's MCMCStrategy, current splatfacto's strategy "mcmc" with
+`max_gs_num`): a fixed budget of Gaussians instead of gradient thresholds.  Every `refine_every` steps (between warmup_length and stop_split_at)
+the refinement callback relocates the dead Gaussians -- visible opacity (the larger of the two sigmoids in separate mode) <= `mcmc_min_opacity` --
+onto live ones drawn with probability proportional to their visible opacity (torch.multinomial of the model's noise_generator), correcting the
+opacity and the scale of source and copies so that the render is preserved, then grows the population by `mcmc_grow_factor` up to `max_gs_num`
+in the same way; both go through tn_splat_mcmc_relocate / _sep, in place on every parameter tensor and both Adam moments (source rows lose their
+moments, as in gsplat), with the relocation values evaluated in double.  One more callback adds position noise after every step,
+means += Sigma (randn * g * noise_lr * lr of the means), g = sigmoid(100 ((1 - o_vis) - 0.995)), in one tn_splat_mcmc_noise / _sep launch, and
+`get_loss_dict` adds `mcmc_opacity_reg` * mean(sigmoid(opacities)) (+ the thermal mean in separate mode) and `mcmc_scale_reg` * mean(exp(scales)).
+No gradient statistics, no cull, no opacity reset; `last_refine_counts` = (dead, relocated, added).  "default" (the default) takes the code path
+of before, untouched.  Whether "mcmc" trains thermal scenes better is not established (profiles/splat_mcmc.md).  Masks are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
 tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 """
 from __future__ import annotations
@@ -77,6 +88,8 @@ from .ops import _stream
 
 BLOCK_WIDTH = 16  # splatfacto.py:738
 CAMERA_OPTIMIZER_MODES = ("off", "SO3xR3", "shared_SO3xR3")  # "SE3" is not built
+STRATEGIES = ("default", "mcmc")  # densification: splatfacto's gradient-threshold refinement, or gsplat's MCMCStrategy
+MCMC_N_MAX = 51  # the relocation ratio's cap (gsplat's n_max; tn_splat_mcmc_relocate's)
 
 
 @dataclass
@@ -129,6 +142,19 @@ class ThermalSplatfactoModelConfig:
     split_screen_size: float = 0.05
     stop_screen_size_at: int = 4000
     stop_split_at: int = 15000
+    # densification strategy (current splatfacto's `strategy`): "default" is the gradient-threshold refinement above; "mcmc" is gsplat's MCMCStrategy
+    # ("3D Gaussian Splatting as Markov Chain Monte Carlo"): a budget of max_gs_num Gaussians, every refine_every steps the dead ones (visible
+    # opacity <= mcmc_min_opacity) are relocated onto live ones and the population grows by mcmc_grow_factor up to the budget, every step the means
+    # take noise of noise_lr x their learning rate shaped by each Gaussian's covariance, and the loss adds mcmc_opacity_reg * mean(opacity) and
+    # mcmc_scale_reg * mean(exp(scales)).  No gradient statistics, no threshold, no cull, no opacity reset.  Whether it trains thermal scenes better
+    # than "default" has not been established here.
+    strategy: str = "default"
+    max_gs_num: int = 1_000_000
+    noise_lr: float = 5e5
+    mcmc_opacity_reg: float = 0.01
+    mcmc_scale_reg: float = 0.01
+    mcmc_min_opacity: float = 0.005
+    mcmc_grow_factor: float = 1.05
     # coarse-to-fine training (splatfacto.py:112-116): 1 / 2^num_downscales of the resolution at first, doubled every resolution_schedule steps
     resolution_schedule: int = 250
     num_downscales: int = 0
@@ -148,6 +174,17 @@ class ThermalSplatfactoModelConfig:
                 raise ValueError(f"{name} = {getattr(self, name)}: a loss multiplier cannot be negative")
         if self.thermal_opacity_mode not in ("shared", "separate"):
             raise ValueError(f'thermal_opacity_mode = {self.thermal_opacity_mode!r}: "shared" or "separate"')
+        if self.strategy not in STRATEGIES:
+            raise ValueError(f'strategy = {self.strategy!r}: "default" or "mcmc"')
+        if not self.max_gs_num >= 1:
+            raise ValueError(f"max_gs_num = {self.max_gs_num}: the budget holds at least one Gaussian")
+        for name in ("noise_lr", "mcmc_opacity_reg", "mcmc_scale_reg"):
+            if not getattr(self, name) >= 0:
+                raise ValueError(f"{name} = {getattr(self, name)}: a number >= 0")
+        if not 0 < self.mcmc_min_opacity < 1:
+            raise ValueError(f"mcmc_min_opacity = {self.mcmc_min_opacity}: an opacity inside (0, 1)")
+        if not self.mcmc_grow_factor >= 1:
+            raise ValueError(f"mcmc_grow_factor = {self.mcmc_grow_factor}: a factor >= 1")
         if self.removal_min_opacity_diff is not None:
             if self.thermal_opacity_mode != "separate":
                 raise ValueError('removal_min_opacity_diff needs thermal_opacity_mode "separate": the removal renders compare the two opacities')
@@ -1039,6 +1076,8 @@ class ThermalSplatfactoModel(nn.Module):
                 "features_dc_thermal": nn.Parameter(torch.rand((n, 1), generator=g).to(dev)),
                 "features_rest_thermal": nn.Parameter(torch.zeros((n, dim_sh - 1, 1), device=dev)),
             })
+        if self.mcmc and self.gauss_params["means"].shape[0] > self.config.max_gs_num:
+            raise ValueError(f'strategy "mcmc": {self.gauss_params["means"].shape[0]} initial Gaussians are above the budget max_gs_num = {self.config.max_gs_num}')
         if self.separate:  # the thermal opacity logits start exactly as the opacities do
             self.gauss_params["opacities_thermal"] = nn.Parameter(torch.logit(0.1 * torch.ones(self.gauss_params["means"].shape[0], 1)).to(dev))
         # pose refinement: one optimiser per spectrum, both sized to all training frames; the other spectrum's rows are non-trainable
@@ -1110,6 +1149,11 @@ class ThermalSplatfactoModel(nn.Module):
     def separate(self) -> bool:
         """thermal_opacity_mode == "separate": gauss_params holds opacities_thermal and the _sep entry points run."""
         return self.config.thermal_opacity_mode == "separate"
+
+    @property
+    def mcmc(self) -> bool:
+        """strategy == "mcmc": the refinement callback relocates and grows, one more callback adds the position noise."""
+        return self.config.strategy == "mcmc"
 
     @property
     def param_names(self) -> Tuple[str, ...]:
@@ -1317,7 +1361,9 @@ class ThermalSplatfactoModel(nn.Module):
         models/thermal_nerfacto.py:346-354): on an RGB frame ThermalNeRF's regularisers of outputs["thermal"] against the main loss's ground truth
         (one tn_thermal_reg call), on a thermal frame 0 -- the reference keeps both to the RGB rays, and the keys depend on the config alone.
         In separate mode with opacity_loss_mult > 0 also density_loss = opacity_loss_mult * (mean|s(o_th) - s(o).detach()| + rgb_opacity_loss_mult *
-        mean|s(o) - s(o_th).detach()|), s = sigmoid (plain torch on [N,1]).  `batch`: image [H,W,3|4], is_thermal."""
+        mean|s(o) - s(o_th).detach()|), s = sigmoid (plain torch on [N,1]).  Under strategy "mcmc" also mcmc_opacity_reg = mcmc_opacity_reg *
+        mean(s(o)) (+ mean(s(o_th)) in separate mode) and mcmc_scale_reg = mcmc_scale_reg * mean(exp(scales)) (plain torch).  `batch`: image [H,W,3|4],
+        is_thermal."""
         if "mask" in batch:
             raise NotImplementedError("masks are not supported by the splat loss (DESIGN.md section 7)")
         cfg = self.config
@@ -1344,6 +1390,12 @@ class ThermalSplatfactoModel(nn.Module):
         if self.separate and cfg.opacity_loss_mult > 0:
             losses["density_loss"] = opacity_density_loss(self.gauss_params["opacities"], self.gauss_params["opacities_thermal"], cfg.opacity_loss_mult,
                                                           cfg.rgb_opacity_loss_mult)
+        if self.mcmc:  # gsplat's MCMC regularisers: few and small Gaussians (elementwise on [N,1] and [N,3], plain torch)
+            o_mean = torch.sigmoid(self.gauss_params["opacities"]).mean()
+            if self.separate:
+                o_mean = o_mean + torch.sigmoid(self.gauss_params["opacities_thermal"]).mean()
+            losses["mcmc_opacity_reg"] = cfg.mcmc_opacity_reg * o_mean
+            losses["mcmc_scale_reg"] = cfg.mcmc_scale_reg * torch.exp(self.gauss_params["scales"]).mean()
         self.camera_optimizer.get_loss_dict(losses)  # camera_opt_regularizer / _thermal (tn_camera_reg), only when the mode is on
         self.camera_optimizer_thermal.get_loss_dict(losses)
         return losses
@@ -1395,15 +1447,19 @@ class ThermalSplatfactoModel(nn.Module):
 
     def get_training_callbacks(self, training_callback_attributes) -> List["TrainingCallback"]:
         """splatfacto.py:595-617.  `training_callback_attributes` carries the `Optimizers` as `.optimizers` (or is the `Optimizers`); the
-        refinement callback reaches them through a closure."""
+        refinement callback reaches them through a closure.  Strategy "mcmc": the same three (after_train does nothing, the refinement callback
+        relocates and grows) and a fourth that adds the position noise after every iteration."""
         from .model import TrainingCallback, TrainingCallbackLocation
 
         opts = training_callback_attributes
         if not isinstance(getattr(opts, "optimizers", None), dict):
             opts = opts.optimizers
         after = [TrainingCallbackLocation.AFTER_TRAIN_ITERATION]
-        return [TrainingCallback([TrainingCallbackLocation.BEFORE_TRAIN_ITERATION], self.step_cb), TrainingCallback(after, self.after_train),
-                TrainingCallback(after, lambda step: self.refinement_after(opts, step), update_every_num_iters=self.config.refine_every)]
+        cbs = [TrainingCallback([TrainingCallbackLocation.BEFORE_TRAIN_ITERATION], self.step_cb), TrainingCallback(after, self.after_train),
+               TrainingCallback(after, lambda step: self.refinement_after(opts, step), update_every_num_iters=self.config.refine_every)]
+        if self.mcmc:  # the position noise: every step, after the optimiser step and after the refinement of a refine step
+            cbs.append(TrainingCallback(after, lambda step: self.mcmc_noise_after(opts, step)))
+        return cbs
 
     def load_state_dict(self, state_dict, strict: bool = True, **kwargs):
         """splatfacto.py:258-271: resize the Gaussians to the checkpoint's count, then load (and, as the reference, step = 30000: every SH degree on)."""
@@ -1432,7 +1488,7 @@ class ThermalSplatfactoModel(nn.Module):
         """splatfacto.py:346-372 on the last training frame (its radii, size and, after backward(), last_xys_grad): tn_splat_grad_stats.
         With config.use_absgrad the statistic accumulated is the norm of last_xys_absgrad instead."""
         assert step == self.step
-        if self.step >= self.config.stop_split_at:
+        if self.mcmc or self.step >= self.config.stop_split_at:  # the MCMC strategy keeps no gradient statistics
             return
         xys_grad = self.last_xys_absgrad if self.config.use_absgrad else self.last_xys_grad
         if xys_grad is None or self.last_radii is None or self.last_size is None:
@@ -1455,12 +1511,18 @@ class ThermalSplatfactoModel(nn.Module):
     def refinement_after(self, optimizers, step: int) -> None:
         """splatfacto.py:381-498: densify (split + duplicate) and cull, or cull only after stop_split_at; then the opacity reset and a reset of
         the statistics.  `optimizers`: an `Optimizers` (or a dict group -> torch.optim optimiser, or None); every optimiser's parameter is
-        replaced by the model's new one, surviving Gaussians keep their Adam moments, new ones start at zero, step counts are kept."""
+        replaced by the model's new one, surviving Gaussians keep their Adam moments, new ones start at zero, step counts are kept.
+        Strategy "mcmc": when warmup_length < step < stop_split_at and step % refine_every == 0, relocate the dead Gaussians and grow towards
+        max_gs_num (`_mcmc_refine`); nothing else."""
         assert step == self.step
         cfg = self.config
         if self.step <= cfg.warmup_length:
             return
         opts = getattr(optimizers, "optimizers", optimizers) or {}
+        if self.mcmc:  # relocate the dead, grow to the budget: no cull, no opacity reset, no statistics
+            if self.step < cfg.stop_split_at and self.step % cfg.refine_every == 0:
+                self._mcmc_refine(optimizers, opts)
+            return
         reset_interval = cfg.reset_alpha_every * cfg.refine_every
         densify = self.step < cfg.stop_split_at and self.step % reset_interval > self.num_train_data + cfg.refine_every
         if densify or (self.step >= cfg.stop_split_at and cfg.continue_cull_post_densification):
@@ -1539,3 +1601,157 @@ class ThermalSplatfactoModel(nn.Module):
                 o.state[p] = st
             if isinstance(getattr(optimizers, "parameters", None), dict) and g in optimizers.parameters:
                 optimizers.parameters[g] = [p]
+
+    # ------------------------------------------------------------------------------------------------ MCMC strategy (gsplat's MCMCStrategy)
+    def _visible_opacity(self) -> Tensor:
+        """o_vis [N]: sigmoid(opacities), in separate mode the larger of the two sigmoids -- the cull's "visible in either spectrum" rule."""
+        o = torch.sigmoid(self.gauss_params["opacities"].detach()).reshape(-1)
+        if self.separate:
+            o = torch.maximum(o, torch.sigmoid(self.gauss_params["opacities_thermal"].detach()).reshape(-1))
+        return o
+
+    def _adam_moments(self, opts) -> Dict[str, Tuple[Tensor, Tensor]]:
+        """gauss_params entry -> (exp_avg, exp_avg_sq) of its optimiser, contiguous and the state's own tensors (written in place); entries
+        without Adam state are left out."""
+        group_of = {v: g for g, v in self.group_params.items()}
+        moments = {}
+        for k in self.param_names:
+            o = opts.get(group_of[k])
+            st = o.state.get(self.gauss_params[k]) if o is not None else None
+            if st and "exp_avg" in st:
+                st["exp_avg"], st["exp_avg_sq"] = st["exp_avg"].contiguous(), st["exp_avg_sq"].contiguous()
+                moments[k] = (st["exp_avg"], st["exp_avg_sq"])
+        return moments
+
+    def _mcmc_grow(self, optimizers, opts, n_add: int) -> None:
+        """Append n_add zero rows to every parameter and both moments, and hand the new parameters to the optimisers as `_refine` does: existing
+        rows keep their values, moments and step counts."""
+        names = self.param_names
+        old = {k: self.gauss_params[k] for k in names}
+        moments = self._adam_moments(opts)
+        grown = lambda t: torch.cat([t.detach(), torch.zeros((n_add,) + tuple(t.shape[1:]), device=t.device)], dim=0)  # noqa: E731
+        self.gauss_params = nn.ParameterDict({k: nn.Parameter(grown(old[k])) for k in names})
+        group_of = {v: g for g, v in self.group_params.items()}
+        for k in names:
+            g = group_of[k]
+            o = opts.get(g)
+            if o is None:
+                continue
+            st = o.state.pop(old[k], None)
+            p = self.gauss_params[k]
+            o.param_groups[0]["params"] = [p]
+            if st is not None:
+                if k in moments:
+                    st["exp_avg"], st["exp_avg_sq"] = grown(moments[k][0]), grown(moments[k][1])
+                o.state[p] = st
+            if isinstance(getattr(optimizers, "parameters", None), dict) and g in optimizers.parameters:
+                optimizers.parameters[g] = [p]
+
+    def _mcmc_refine(self, optimizers, opts) -> None:
+        """One MCMC refinement: relocate the dead Gaussians onto live ones, then grow towards the budget (each: one torch.multinomial draw of the
+        model's noise_generator on the device and one tn_splat_mcmc_relocate call).  One host synchronisation: the number of dead Gaussians."""
+        cfg = self.config
+        N = self.num_points
+        n_dead = n_relocated = 0
+        if N > 0:
+            o_vis = self._visible_opacity()
+            dead = o_vis <= cfg.mcmc_min_opacity
+            dst = dead.nonzero().reshape(-1)
+            n_dead = int(dst.numel())
+            if 0 < n_dead < N:
+                alive = (~dead).nonzero().reshape(-1)
+                src = alive[torch.multinomial(o_vis[alive], n_dead, replacement=True, generator=self.noise_generator)]
+                self._mcmc_relocate(opts, src, dst)
+                n_relocated = n_dead
+        n_add = mcmc_num_added(N, cfg.max_gs_num, cfg.mcmc_grow_factor)
+        if n_add > 0:
+            src = torch.multinomial(self._visible_opacity(), n_add, replacement=True, generator=self.noise_generator)  # on the relocated values
+            self._mcmc_grow(optimizers, opts, n_add)
+            self._mcmc_relocate(opts, src, torch.arange(N, N + n_add, device=src.device))
+        self.last_refine_counts = (n_dead, n_relocated, n_add)
+        if n_relocated or n_add:  # what the last training frame left refers to other Gaussians now
+            self.last_radii = None
+            self.last_xys_grad = self.last_xys_absgrad = None
+        self.xys_grad_norm = self.vis_counts = self.max_2Dsize = None
+
+    def _mcmc_relocate(self, opts, src: Tensor, dst: Tensor) -> None:
+        names = self.param_names
+        moments = self._adam_moments(opts)
+        mcmc_relocate([self.gauss_params[k].data for k in names], [moments[k][0] if k in moments else None for k in names],
+                      [moments[k][1] if k in moments else None for k in names], src, dst, self.config.mcmc_min_opacity)
+
+    @torch.no_grad()
+    def mcmc_noise_after(self, optimizers, step: int) -> None:
+        """The MCMC position noise of one iteration (while step < stop_split_at): means += Sigma (randn * g * noise_lr * lr), lr the "xyz"
+        optimiser's current learning rate, randn [N,3] from the model's noise_generator, in one tn_splat_mcmc_noise call; Adam state untouched."""
+        assert step == self.step
+        if not self.mcmc or self.step >= self.config.stop_split_at or self.num_points == 0:
+            return
+        opts = getattr(optimizers, "optimizers", optimizers) or {}
+        if "xyz" not in opts:
+            raise RuntimeError('mcmc_noise_after: the noise is scaled by the learning rate of the "xyz" optimiser, which is missing')
+        lr = float(opts["xyz"].param_groups[0]["lr"])
+        gp = self.gauss_params
+        z = torch.randn((self.num_points, 3), device=self.means.device, generator=self.noise_generator)
+        mcmc_noise(gp["means"].data, gp["scales"].data, gp["quats"].data, gp["opacities"].data, z, self.config.noise_lr * lr,
+                   gp["opacities_thermal"].data if self.separate else None)
+
+
+def mcmc_num_added(n: int, max_gs_num: int, grow_factor: float) -> int:
+    """How many Gaussians an MCMC refinement adds to n of them: max(0, min(max_gs_num, int(grow_factor * n)) - n)."""
+    return max(0, min(int(max_gs_num), int(grow_factor * n)) - n)
+
+
+def mcmc_relocate(params: List[Tensor], exp_avg: List[Optional[Tensor]], exp_avg_sq: List[Optional[Tensor]], src_idx: Tensor, dst_idx: Tensor,
+                  min_opacity: float) -> None:
+    """tn_splat_mcmc_relocate / _sep in place on the current stream, without a host synchronisation.  params: the 8 (9: separate thermal opacity)
+    gauss_params tensors in param_names order, contiguous fp32 on the device, all with the same number of rows; exp_avg / exp_avg_sq: per tensor
+    its Adam moments or None (both); src_idx / dst_idx: int64 [M] on the device.  Row dst_idx[j] becomes a copy of row src_idx[j] with gsplat's
+    relocation opacity and scale (ratio = 1 + how often the source was drawn, capped at 51; evaluated in double), every drawn source takes that
+    opacity and scale once and loses its moments; destination moments and every row not named stay.  No destination may be a source or repeat."""
+    if len(params) not in (8, 9):
+        raise ValueError(f"mcmc_relocate takes the 8 or 9 gauss_params tensors, got {len(params)}")
+    if len(exp_avg) != len(params) or len(exp_avg_sq) != len(params):
+        raise ValueError("mcmc_relocate: one exp_avg and one exp_avg_sq entry (a tensor or None) per parameter")
+    rows, K = params[0].shape[0], params[5].shape[1]
+    for t, m1, m2, n in zip(params, exp_avg, exp_avg_sq, _PARAM_NAMES_SEP):
+        if t.shape[0] != rows:
+            raise ValueError(f"mcmc_relocate: {n} has {t.shape[0]} rows, means {rows}")
+        if (m1 is None) != (m2 is None) or (m1 is not None and (m1.shape != t.shape or m2.shape != t.shape)):
+            raise ValueError(f"mcmc_relocate: the moments of {n} must both be None or both have its shape")
+    if src_idx.shape != dst_idx.shape or src_idx.dim() != 1:
+        raise ValueError(f"mcmc_relocate: src_idx and dst_idx must be [M], got {tuple(src_idx.shape)} and {tuple(dst_idx.shape)}")
+    M = src_idx.shape[0]
+    if M == 0:
+        return
+    lib = _lib.load()
+    pp = _param_ptrs(params)  # checks device, dtype and contiguity; the two features_rest entries are null without higher-order coefficients
+
+    def arr(ts, what):  # a HOST array of device pointers; an entry is null where the tensor is None or the parameter itself is
+        return (C.c_void_p * len(params))(*[_ptr(t, torch.float32, what).value if t is not None and p is not None else None for t, p in zip(ts, pp)])
+
+    need = int(lib.tn_splat_mcmc_workspace_bytes(rows, M))
+    if need < 0:
+        raise RuntimeError("tn_splat_mcmc_workspace_bytes: bad sizes")
+    ws = torch.empty(need, dtype=torch.uint8, device=params[0].device)
+    name = "tn_splat_mcmc_relocate_sep" if len(params) == 9 else "tn_splat_mcmc_relocate"
+    _lib.check(getattr(lib, name)(rows, K, _ptr(src_idx, torch.int64, "src_idx"), _ptr(dst_idx, torch.int64, "dst_idx"), M, float(min_opacity),
+                                  arr(params, "params"), arr(exp_avg, "exp_avg"), arr(exp_avg_sq, "exp_avg_sq"), C.c_void_p(ws.data_ptr()), need,
+                                  _stream()), name)
+
+
+def mcmc_noise(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor, randn: Tensor, scaler: float,
+               opacities_thermal: Optional[Tensor] = None) -> None:
+    """tn_splat_mcmc_noise / _sep: means [N,3] += Sigma (randn * g * scaler) in place, one launch on the current stream, fp32.  Sigma =
+    R diag(exp(scales)^2) R^T with R the rotation of quats / |quats|; g = 1 / (1 + exp(-100 ((1 - o_vis) - 0.995))), o_vis = sigmoid(opacities)
+    or, with opacities_thermal, the larger of the two sigmoids: a Gaussian anyone can see stays where it is.  Contiguous fp32 device tensors."""
+    N = means.shape[0]
+    if means.shape != (N, 3) or scales.shape != (N, 3) or quats.shape != (N, 4) or randn.shape != (N, 3) or opacities.numel() != N or \
+            (opacities_thermal is not None and opacities_thermal.numel() != N):
+        raise ValueError("mcmc_noise: means, scales, randn [N,3], quats [N,4], opacities [N,1] of one N expected")
+    f32 = torch.float32
+    args = [_ptr(means, f32, "means"), _ptr(scales, f32, "scales"), _ptr(quats, f32, "quats"), _ptr(opacities.reshape(-1), f32, "opacities")]
+    if opacities_thermal is not None:
+        args.append(_ptr(opacities_thermal.reshape(-1), f32, "opacities_thermal"))
+    name = "tn_splat_mcmc_noise_sep" if opacities_thermal is not None else "tn_splat_mcmc_noise"
+    _lib.check(getattr(_lib.load(), name)(*args, _ptr(randn, f32, "randn"), N, float(scaler), _stream()), name)

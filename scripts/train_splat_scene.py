@@ -18,7 +18,9 @@ the NeRF path runs both at 1e-6); the backward goes over the sum of the loss dic
 three or none: centre, roll pitch yaw in radians, extents) give the eval render an oriented crop box (OrientedBox.from_params): after the val
 split is scored on the whole scene, its frames are rendered again through get_outputs_for_camera(camera, box) and written as PNGs to --crop-out
 (rgb_*.png, thermal_*.png; in separate mode with --removal-min-opacity-diff also removal_*.png and removal_thermal_*.png), and the line reports
-the share of Gaussians the box keeps."""
+the share of Gaussians the box keeps.  --strategy mcmc trains with gsplat's MCMC strategy instead of splatfacto's gradient-threshold refinement: a budget of
+--max-gs-num Gaussians, relocation and growth every refine_every steps (tn_splat_mcmc_relocate), position noise of --noise-lr times the means' learning
+rate after every step (tn_splat_mcmc_noise), and the two MCMC regularisers in the loss."""
 import argparse
 import functools
 import json
@@ -119,6 +121,10 @@ def main():
     ap.add_argument("--use-absgrad", action="store_true",
                     help="densify on the absolute 2D-mean gradients (AbsGS); raise --densify-grad-thresh with it (gsplat advises about 0.0008)")
     ap.add_argument("--densify-grad-thresh", type=float, default=0.0002)
+    ap.add_argument("--strategy", default="default", choices=("default", "mcmc"),
+                    help='"mcmc": a budget of --max-gs-num Gaussians, dead ones relocated onto live ones, position noise every step (gsplat\'s MCMCStrategy)')
+    ap.add_argument("--max-gs-num", type=int, default=1_000_000, help="the MCMC strategy's budget of Gaussians")
+    ap.add_argument("--noise-lr", type=float, default=5e5, help="the MCMC strategy's position noise, in units of the means' learning rate")
     ap.add_argument("--no-undistort", action="store_true", help="train on the raw frames with the parser's intrinsics (the distortion dropped)")
     args = ap.parse_args()
     if args.seed_points and args.data is not None:
@@ -151,7 +157,8 @@ def main():
                                        opacity_loss_mult=args.opacity_loss_mult, removal_min_opacity_diff=args.removal_min_opacity_diff,
                                        camera_optimizer=CameraOptimizerConfig(mode=args.camera_optimizer),
                                        camera_optimizer_thermal=CameraOptimizerConfig(mode=args.camera_optimizer_thermal), use_absgrad=args.use_absgrad,
-                                       densify_grad_thresh=args.densify_grad_thresh)
+                                       densify_grad_thresh=args.densify_grad_thresh, strategy=args.strategy, max_gs_num=args.max_gs_num,
+                                       noise_lr=args.noise_lr)
     model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=dm.num_train_data, seed_points=seed_points,
                                    train_is_thermal=dm.train_is_thermal)
     initial = model.num_points
@@ -220,7 +227,8 @@ def main():
                       "resolution_schedule": args.resolution_schedule, "tv_pixel_loss_mult": args.tv_pixel_loss_mult,
                       "cross_channel_loss_mult": args.cross_channel_loss_mult, "undistort": not args.no_undistort, "thermal_opacity_mode": args.thermal_opacity_mode,
                       "opacity_loss_mult": args.opacity_loss_mult, "camera_optimizer": args.camera_optimizer,
-                      "camera_optimizer_thermal": args.camera_optimizer_thermal, **extra, "stages": stages, "val_metrics": metrics, "curve": curve}))
+                      "camera_optimizer_thermal": args.camera_optimizer_thermal, "strategy": args.strategy, "max_gs_num": args.max_gs_num,
+                      "noise_lr": args.noise_lr, **extra, "stages": stages, "val_metrics": metrics, "curve": curve}))
 
 
 if __name__ == "__main__":
