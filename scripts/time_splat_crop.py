@@ -20,7 +20,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 import nerfstudio_thermal_amd  # noqa: E402,F401
-from nerfstudio_thermal_amd import _lib, splat, synth  # noqa: E402
+from nerfstudio_thermal_amd import _lib, splat, splat_calls, synth  # noqa: E402
 from nerfstudio_thermal_amd.ops import _stream  # noqa: E402
 from nerfstudio_thermal_amd.splat import PinholeCamera, ThermalSplatfactoModel, ThermalSplatfactoModelConfig, camera_struct  # noqa: E402
 
@@ -107,7 +107,7 @@ for order in ("random", "morton"):
     # the launches alone, on the eval workspace and the projection tensors the last frame left
     cs, ws, cap = camera_struct(cam), m._ws, m._cap
     proj = m.last_projection
-    pp = splat._param_ptrs([m.gauss_params[k] for k in m.param_names])
+    pp = splat_calls._param_ptrs([m.gauss_params[k] for k in m.param_names])
     K = m.gauss_params["features_rest"].shape[1]
     outs = [ptr(proj[k]) for k in ("xys", "depths", "radii", "conics", "compensation", "num_tiles_hit", "tile_box")]
     total = C.c_int64(0)

@@ -20,7 +20,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 import nerfstudio_thermal_amd  # noqa: E402,F401
-from nerfstudio_thermal_amd import _lib, splat, synth  # noqa: E402
+from nerfstudio_thermal_amd import _lib, splat_calls, synth  # noqa: E402
 from nerfstudio_thermal_amd.ops import _stream  # noqa: E402
 from nerfstudio_thermal_amd.splat import PinholeCamera, ThermalSplatfactoModel, ThermalSplatfactoModelConfig, camera_struct, pose_camera_record  # noqa: E402
 
@@ -63,7 +63,7 @@ def outputs():
             torch.empty(N, device=dev), torch.empty(N, dtype=i32, device=dev), torch.empty((N, 4), dtype=i32, device=dev)]
 
 
-pp = splat._param_ptrs(params)
+pp = splat_calls._param_ptrs(params)
 pose = torch.zeros((2, 6), device=dev)
 pose[1] = torch.tensor([0.02, -0.015, 0.01, 0.012, -0.02, 0.015])
 sfx = "_sep" if sep else ""
@@ -84,7 +84,7 @@ gen = torch.Generator(device=dev).manual_seed(3)
 up = [torch.randn((N, 2), device=dev, generator=gen), torch.randn((N, 3), device=dev, generator=gen), torch.randn((N, 4), device=dev, generator=gen),
       torch.randn(N, device=dev, generator=gen)] + ([torch.randn(N, device=dev, generator=gen)] if sep else [])
 grads = [torch.empty_like(t) for t in params]
-gp = splat._param_ptrs(grads)
+gp = splat_calls._param_ptrs(grads)
 need = int(lib.tn_splat_pose_workspace_bytes(N))
 pws = torch.empty(need, dtype=torch.uint8, device=dev)
 g_pose = torch.zeros((2, 6), device=dev)
