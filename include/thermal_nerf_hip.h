@@ -919,6 +919,45 @@ TN_API int tn_splat_project_backward_pose_sep(const TnSplatCamera* camera, const
                                               float* v_thermal_dc, float* v_thermal_rest, float* v_opacities_thermal, void* workspace,
                                               int64_t workspace_bytes, float* grad_pose_row, float* dview_out, tn_stream_t stream);
 
+/* ---- N4 depth gradient: the training render's depth image as a differentiable output (splatfacto's training depth carries gradients,
+ * nerfstudio/models/splatfacto.py:805-820).  Classic mode only.  There depth = D / A where A = accumulation > 0, with D = sum alpha_i T_i z_i on
+ * the RGB chain (in separate mode too) and z_i = depths[i]; elsewhere depth is the frame's maximum of D, a value without gradient (the reference's
+ * .detach().max()).  With v_depth [H,W] = dL / d depth, per pixel vD = v_depth / A (0 where A == 0): z rides the RGB chain's walk as a fifth colour
+ * channel with upstream vD and no background term, and v_alpha becomes v_alpha - vD * depth.  The pair record grows by one sum, d z, reduced as the
+ * others are (lane, fixed butterfly, LDS, four waves in order, one write): no float atomics, bit-reproducible.  In antialiased mode the depth is
+ * blended by a chain of its own with the uncompensated opacity, whose final transmittance and last contributor the training forward does not keep:
+ * both entry points refuse antialiased != 0.
+ *
+ * scratch of tn_depth_splat_raster_backward: one more partial sum per pair than the entry point without it (sep, absgrad: 0 or 1); -1 on bad sizes */
+TN_API int64_t tn_splat_depth_backward_workspace_bytes(int64_t num_gaussians, int64_t max_intersections, int32_t sep, int32_t absgrad);
+/* The arguments of tn_splat_raster_backward_abs_sep, `antialiased` (must be 0) behind background4, and at the end depth [H,W] (the normalised image
+ * tn_splat_raster_train / _sep wrote), v_depth [H,W] and v_depths [N] = dL / d depths (out).  The thermal group (transmittance_thermal, last_thermal,
+ * v_alpha_thermal, v_log_opacity_thermal) all null selects shared mode, a null v_xys_abs no absgrad; every other output is what the entry point of
+ * that mode computes from v_alpha - vD * depth and the fifth channel.  Refuses what that entry point refuses, null depth pointers (N > 0),
+ * antialiased != 0 and a bwd_workspace_bytes below tn_splat_depth_backward_workspace_bytes. */
+TN_API int tn_depth_splat_raster_backward(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                          int64_t num_intersections, const float* background4, int32_t antialiased, const float* transmittance,
+                                          const int32_t* last, const float* transmittance_thermal, const int32_t* last_thermal, const float* conics,
+                                          const float* v_rgbt, const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace,
+                                          int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors,
+                                          float* v_log_opacity, float* v_log_opacity_thermal, const float* depth, const float* v_depth,
+                                          float* v_depths, tn_stream_t stream);
+/* The arguments of tn_splat_project_backward_pose_sep plus v_depths [N] (behind v_log_opacity_thermal): depths[i] is the view-space z of the mean,
+ * so every Gaussian with radii > 0 adds v_depths[i] * view[2, :3] to v_means, and with a pose v_depths[i] * (mean, 1) to row 2 of dL/d view' before
+ * the double-precision sums.  A null pose_camera means no pose (pose_row, workspace, grad_pose_row and dview_out are then not read); the thermal
+ * opacity pointers (opacities_thermal, v_log_opacity_thermal, v_opacities_thermal) all null select shared mode.  Refuses what the entry point of
+ * that mode refuses, a null v_depths (N > 0) and antialiased != 0. */
+TN_API int tn_depth_splat_project_backward(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
+                                           const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
+                                           const float* features_rest, const float* thermal_dc, const float* thermal_rest,
+                                           const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
+                                           int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics,
+                                           const float* v_colors, const float* v_log_opacity, const float* v_log_opacity_thermal,
+                                           const float* v_depths, float* v_means, float* v_log_scales, float* v_quats, float* v_opacities,
+                                           float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest,
+                                           float* v_opacities_thermal, void* workspace, int64_t workspace_bytes, float* grad_pose_row,
+                                           float* dview_out, tn_stream_t stream);
+
 /* ---- N4 training loss: splatfacto's (1 - ssim_lambda) * L1 + ssim_lambda * (1 - SSIM) (nerfstudio/models/splatfacto.py:863-903), SSIM as
  * pytorch_msssim computes it: an 11-tap Gaussian window (sigma 1.5) applied separably as a VALID correlation, C1 = 0.01^2, C2 = 0.03^2 (data
  * range 1), mean over the (H-10) x (W-10) valid pixels and the channels.  L1 = mean |pred - gt| over all H W C values.  Deterministic: no
@@ -956,6 +995,24 @@ TN_API int64_t tn_thermal_reg_workspace_bytes(int32_t height, int32_t width);
 TN_API int tn_thermal_reg(const float* pred_thermal, int64_t pred_pixel_stride, const float* gt_rgb, int64_t gt_pixel_stride, int32_t height,
                           int32_t width, float tv_mult, float cross_mult, void* workspace, int64_t workspace_bytes, float* out_loss, float* out_grad,
                           tn_stream_t stream);
+/* ---- N4 depth losses: two geometric priors on the depth render, both only where the render is covered (accumulation > 0):
+ *   depth_loss    = mean |depth - depth_image| over the pixels with accumulation > 0 and a finite, positive depth_image (a sensor depth in scene
+ *                   units, nerfstudio's DepthDataset key); 0 without such a pixel, and with a null depth_image
+ *   depth_tv_loss = the 2 x 2 total variation above, 0.25 * mean_w(|p0-p1| + |p0-p2| + |p1-p3| + |p2-p3|), of the depth over the stride-1 windows
+ *                   whose four pixels all have accumulation > 0 (an uncovered pixel holds the frame's fill value: it would put an edge on every
+ *                   silhouette); 0 without such a window
+ * The two normalisations are data, so the gradient's constants exist only after the sums: a pass of partial sums and counts, a finishing reduction
+ * (double, fixed order), and -- with out_grad -- a second pass in which every pixel gathers its gradient.  Deterministic: no float atomics.  No host
+ * synchronisation.  A multiplier of exactly 0 skips its term: the loss is exactly 0 and adds nothing to the gradient.
+ *
+ * scratch of tn_depth_loss: per-block partial sums and counts, and the two gradient constants; -1 on bad sizes (H or W < 2 or > 32768) */
+TN_API int64_t tn_depth_loss_workspace_bytes(int32_t height, int32_t width);
+/* depth, accumulation: [H,W] fp32 contiguous; depth_image: [H,W] fp32 contiguous or NULL.  out_loss: DEVICE [2] = depth_mult * depth_loss,
+ * tv_mult * depth_tv_loss.  out_grad: [H,W] contiguous = d (out_loss[0] + out_loss[1]) / d depth with sign(0) = 0 (accumulation and depth_image get
+ * none), or NULL for the losses alone.  Refused with TN_EINVAL before any launch: null pointers, H or W < 2 or > 32768, a negative multiplier, a
+ * short workspace. */
+TN_API int tn_depth_loss(const float* depth, const float* accumulation, const float* depth_image, int32_t height, int32_t width, float depth_mult,
+                         float tv_mult, void* workspace, int64_t workspace_bytes, float* out_loss, float* out_grad, tn_stream_t stream);
 /* ---- N4 resolution schedule: bilinear resize of one image, what splatfacto's _downscale_if_required does with
  * torchvision.transforms.functional.resize(antialias=None) (nerfstudio/models/splatfacto.py:648-657), i.e. torch.nn.functional.interpolate(
  * mode="bilinear", align_corners=False, antialias=False).  Per axis: scale = (float)in / out, source coordinate scale * (dst + 0.5) - 0.5 clamped

@@ -229,12 +229,18 @@ SIGNATURES = {
     "tn_splat_pose_workspace_bytes": (_i64, [_i64]),
     "tn_splat_project_backward_pose": (C.c_int, [_p] * 11 + [_i64, _i32, _i32, _i32] + [_p] * 14 + [_i64, _p, _p, _p]),
     "tn_splat_project_backward_pose_sep": (C.c_int, [_p] * 12 + [_i64, _i32, _i32, _i32] + [_p] * 16 + [_i64, _p, _p, _p]),
+    # depth gradient (classic mode): the raster and projection backwards with v_depth / v_depths; thermal, absgrad and pose groups are nullable
+    "tn_splat_depth_backward_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "tn_depth_splat_raster_backward": (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _i32] + [_p] * 9 + [_i64] + [_p] * 10),
+    "tn_depth_splat_project_backward": (C.c_int, [_p] * 12 + [_i64, _i32, _i32, _i32] + [_p] * 17 + [_i64, _p, _p, _p]),
     "tn_image_loss_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "tn_image_loss": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _f, _f, _p, _i64, _p, _p, _p]),
     "tn_image_resize": (C.c_int, [_p, _i32, _i64, _i32, _i32, _i32, _p, _i32, _i32, _p]),
     "tn_image_undistort": (C.c_int, [_p, _i32, _i64, _i32, _i32, _i32, _p, _i32, C.POINTER(TnUndistort), _p]),
     "tn_thermal_reg_workspace_bytes": (_i64, [_i32, _i32]),
     "tn_thermal_reg": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _f, _f, _p, _i64, _p, _p, _p]),
+    "tn_depth_loss_workspace_bytes": (_i64, [_i32, _i32]),
+    "tn_depth_loss": (C.c_int, [_p, _p, _p, _i32, _i32, _f, _f, _p, _i64, _p, _p, _p]),
     "tn_knn_workspace_bytes": (_i64, [_i64, _i32]),
     "tn_knn": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _i64, _p]),
     # MCMC strategy: relocation / growth in place (8 or 9 tensors with their moments) and the per-step position noise

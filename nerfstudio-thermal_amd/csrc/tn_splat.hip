@@ -762,8 +762,8 @@ __global__ void __launch_bounds__(256) k_splat_raster_removal(const SplatRec* __
 }
 
 // ------------------------------------------------------------------------------------------------ backward
-// The exact derivative of the forward above (rgb, thermal, accumulation; depth is not differentiated).  Three steps, no float atomics, so
-// the gradients are bit-reproducible:
+// The exact derivative of the forward above (rgb, thermal, accumulation; depth only through the DEPTH instantiations below, which the
+// tn_depth_splat_* entry points run).  Three steps, no float atomics, so the gradients are bit-reproducible:
 //   k_splat_raster_bwd  block = one tile, same lane -> pixel map as the forward.  Every pixel walks its list from the last contributor back
 //                       to the front, recomputing alpha under the forward's rules and the transmittance before each Gaussian as T / (1 - alpha).
 //                       The SPLAT_PAIR_GRADS partial sums of a (tile, Gaussian) pair are reduced over the wave (fixed butterfly), then over the
@@ -779,9 +779,23 @@ __global__ void __launch_bounds__(256) k_splat_raster_removal(const SplatRec* __
 // absolute value.  The rasteriser holds the conic only in splat_power's scaled form (A, B, C) = (cx / 2, cy, cz / 2) log2(e), so the slots carry
 // log2(e) |J| = |dsigma (2A dx + B dy)|, |dsigma (B dx + 2C dy)| (the doubling is exact) and k_splat_pair_fold multiplies the sum by ln 2.
 #define SPLAT_PAIR_ABS 2
+// DEPTH (an upstream gradient of the depth image, classic mode): depth = D / A with D = sum alpha_i T_i z_i on chain 1 (the RGB chain, in SEP too)
+// and A = 1 - T_final > 0; elsewhere depth is the frame's maximum of D, a value without gradient.  With v_depth = dL / d depth that is a fifth
+// colour channel without a background term plus a correction of v_alpha, per pixel
+//   vD = v_depth / A (0 where A == 0),   v_alpha_eff = v_alpha - vD * depth   (d depth / d A = -D / A^2 = -depth / A)
+// so inside the walk of chain 1 cv gains z_k vD (z_k = SplatRec::d.x), `rest` starts from v_alpha_eff, and the pair record gains ONE slot,
+// d z = vis * vD, behind d ln(thermal opacity) and before the SPLAT_PAIR_ABS slots; k_splat_pair_fold sums it into v_depths [N] = dL / d depths.
+#define SPLAT_PAIR_DEPTH 1
+struct SplatDepthBwdK {  // the DEPTH instantiations' extra kernel argument (last in the pack)
+  const float* depth;    // [H,W] the forward's normalised depth image
+  const float* v_depth;  // [H,W] dL / d depth
+};
+struct SplatDepthFoldK {  // k_splat_pair_fold's
+  float* v_depths;  // [N]
+};
 
 struct SplatBwdWs {
-  float* pair;     // [max_intersections][SPLAT_PAIR_GRADS or SPLAT_PAIR_GRADS_SEP (+ SPLAT_PAIR_ABS)]
+  float* pair;     // [max_intersections][SPLAT_PAIR_GRADS or SPLAT_PAIR_GRADS_SEP (+ SPLAT_PAIR_DEPTH) (+ SPLAT_PAIR_ABS)]
   int32_t* start;  // [N] first record of each Gaussian's run
 };
 
@@ -822,6 +836,17 @@ extern "C" int64_t tn_splat_backward_workspace_bytes_abs_sep(int64_t num_gaussia
   return (int64_t)total;
 }
 
+static int splat_pair_grads(bool sep, bool absgrad, bool depth) {
+  return (sep ? SPLAT_PAIR_GRADS_SEP : SPLAT_PAIR_GRADS) + (depth ? SPLAT_PAIR_DEPTH : 0) + (absgrad ? SPLAT_PAIR_ABS : 0);
+}
+
+extern "C" int64_t tn_splat_depth_backward_workspace_bytes(int64_t num_gaussians, int64_t max_intersections, int32_t sep, int32_t absgrad) {
+  if (num_gaussians < 0 || max_intersections < 0) return -1;
+  size_t total = 0;
+  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, splat_pair_grads(sep != 0, absgrad != 0, true), &total);
+  return (int64_t)total;
+}
+
 // start of Gaussian order[j]'s run of pairs: cum is the inclusive scan of the tight tile counts in depth order
 __global__ void k_splat_run_start(const int32_t* __restrict__ order, const int32_t* __restrict__ cum, const int32_t* __restrict__ thits, int64_t N,
                                   int32_t* __restrict__ start) {
@@ -837,6 +862,9 @@ __global__ void k_splat_run_start(const int32_t* __restrict__ order, const int32
 // sep_args (SEP only): const float* final_T_th, const int32_t* last_th, const float* v_alpha_th.
 // ABS: the record grows by the SPLAT_PAIR_ABS slots, which take the path of the others (lane, butterfly, sp, four waves in order, one write).
 // ABS = false is the kernel as it was.  Static LDS: 61 440 B, SEP 66 560 B (gfx950 has 160 KB per CU: two blocks per CU as before).
+// DEPTH (one SplatDepthBwdK behind the SEP arguments, see SPLAT_PAIR_DEPTH): the record grows by d z, which takes the path of the others, and the
+// batch's z_k sit in one more float[SPLAT_BATCH].  Without it the kernel is the one it was.  Static LDS of the largest instantiation (SEP + ABS +
+// DEPTH: 14 sums): 71 684 B, below the 80 KB that keep two blocks per CU.
 template <bool SEP, bool ABS, typename... SepArgs>
 __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __restrict__ recs, const int32_t* __restrict__ sorted_ids,
                                                           const int32_t* __restrict__ tile_bins, const int32_t* __restrict__ tile_order, int W, int H,
@@ -844,14 +872,21 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
                                                           const float* __restrict__ v_rgbt, const float* __restrict__ v_alpha,
                                                           const int32_t* __restrict__ start, const int32_t* __restrict__ tbox, float* __restrict__ pair,
                                                           SepArgs... sep_args) {
-  static_assert(sizeof...(SepArgs) == (SEP ? 3 : 0), "SEP takes final_T_th, last_th, v_alpha_th");
-  constexpr int NG = (SEP ? SPLAT_PAIR_GRADS_SEP : SPLAT_PAIR_GRADS) + (ABS ? SPLAT_PAIR_ABS : 0);
+  constexpr bool DEPTH = pack_has<SplatDepthBwdK, SepArgs...>;
+  static_assert(sizeof...(SepArgs) == (SEP ? 3 : 0) + (DEPTH ? 1 : 0), "SEP takes final_T_th, last_th, v_alpha_th; DEPTH one SplatDepthBwdK behind them");
+  constexpr int NG = (SEP ? SPLAT_PAIR_GRADS_SEP : SPLAT_PAIR_GRADS) + (DEPTH ? SPLAT_PAIR_DEPTH : 0) + (ABS ? SPLAT_PAIR_ABS : 0);
   constexpr int TH = SEP ? SPLAT_PAIR_GRADS : NG - 1;  // SEP: the slot of d ln(thermal opacity)
+  constexpr int DZ = SEP ? SPLAT_PAIR_GRADS_SEP : SPLAT_PAIR_GRADS;  // DEPTH: the slot of d z
   __shared__ float4 sa[SPLAT_BATCH], sb[SPLAT_BATCH], sc[SPLAT_BATCH];
   float* l2t = nullptr;  // SEP: l2op of the thermal chain (SplatRec::d.w) of the batch's Gaussians
   if constexpr (SEP) {
     __shared__ float s_l2t[SPLAT_BATCH];
     l2t = s_l2t;
+  }
+  [[maybe_unused]] float* sz = nullptr;  // DEPTH: view-space depth (SplatRec::d.x) of the batch's Gaussians
+  if constexpr (DEPTH) {
+    __shared__ float s_z[SPLAT_BATCH];
+    sz = s_z;
   }
   __shared__ float sp[4][NG][SPLAT_BATCH];  // per wave partial sums of the batch's Gaussians (SEP: 57 KB of LDS with the records, 2 blocks per CU as before)
   __shared__ int s_n;
@@ -866,19 +901,27 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
   float T = 1.f, rest = 0.f;
   float Tt = 1.f, rest_t = 0.f;  // SEP: the thermal chain's
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  [[maybe_unused]] float vD = 0.f;  // DEPTH: v_depth / accumulation
   int n = 0, nt = 0;
   if (inside) {
     const int64_t p = (int64_t)iy * W + ix;
     T = final_T[p];
     n = last[p];
     v = reinterpret_cast<const float4*>(v_rgbt)[p];
+    float va = v_alpha[p];
+    if constexpr (DEPTH) {  // v_alpha_eff; the depth channel has no background term
+      const SplatDepthBwdK dk = pack_get<SplatDepthBwdK>(sep_args...);
+      const float acc = 1.0f - T;  // the accumulation as the forward wrote it
+      vD = acc > 0.f ? dk.v_depth[p] / acc : 0.f;
+      va = va - vD * dk.depth[p];
+    }
     if constexpr (SEP) {
-      rest = T * (v.x * background.x + v.y * background.y + v.z * background.z - v_alpha[p]);
+      rest = T * (v.x * background.x + v.y * background.y + v.z * background.z - va);
       Tt = pack_arg<0>(sep_args...)[p];
       nt = pack_arg<1>(sep_args...)[p];
       rest_t = Tt * (v.w * background.w - pack_arg<2>(sep_args...)[p]);
     } else {
-      rest = T * (v.x * background.x + v.y * background.y + v.z * background.z + v.w * background.w - v_alpha[p]);
+      rest = T * (v.x * background.x + v.y * background.y + v.z * background.z + v.w * background.w - va);
     }
   }
   int wn = SEP ? max(n, nt) : n;
@@ -898,6 +941,7 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
       const SplatRec* r = recs + g;
       sa[threadIdx.x] = r->a; sb[threadIdx.x] = r->b; sc[threadIdx.x] = r->c;
       if (SEP) l2t[threadIdx.x] = r->d.w;
+      if constexpr (DEPTH) sz[threadIdx.x] = r->d.x;
       const int4 bx = reinterpret_cast<const int4*>(tbox)[g];
       dst = (int64_t)start[g] + (tile_y - bx.y) * (bx.z - bx.x) + (tile_x - bx.x);
     }
@@ -942,12 +986,14 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
           const float om = 1.0f - alpha;
           T = T / om;  // transmittance in front of this Gaussian
           const float4 col = sc[k];
-          const float cv = SEP ? col.x * v.x + col.y * v.y + col.z * v.z : col.x * v.x + col.y * v.y + col.z * v.z + col.w * v.w;
+          float cv = SEP ? col.x * v.x + col.y * v.y + col.z * v.z : col.x * v.x + col.y * v.y + col.z * v.z + col.w * v.w;
+          if constexpr (DEPTH) cv += sz[k] * vD;  // the fifth channel
           const float vis = alpha * T;
           const float d_alpha = T * cv - rest / om;
           rest = fmaf(vis, cv, rest);
           g[5] = vis * v.x; g[6] = vis * v.y; g[7] = vis * v.z;
           if (!SEP) g[8] = vis * v.w;
+          if constexpr (DEPTH) g[DZ] = vis * vD;
           if (raw <= 0.999f) {  // the clamp passes gradient where torch.clamp's backward does
             const float d_lnop = d_alpha * alpha;  // alpha = opacity exp(-sigma)
             const float d_sigma = -d_lnop;
@@ -997,13 +1043,15 @@ __global__ void __launch_bounds__(256) k_splat_raster_bwd(const SplatRec* __rest
 
 // NG = SPLAT_PAIR_GRADS, or SPLAT_PAIR_GRADS_SEP: the sum after the ten is d ln(thermal opacity) -> v_lnop_th.  abs_args (ABS only, NG is then
 // SPLAT_PAIR_ABS larger): float* v_xys_abs [N,2], the record's last two sums times ln 2 (see SPLAT_PAIR_ABS).  Without it the kernel as it was.
+// DEPTH (one SplatDepthFoldK in the pack, NG SPLAT_PAIR_DEPTH larger): the sum behind d ln(thermal opacity) -> v_depths [N].
 template <int NG, typename... AbsArgs>
 __global__ void k_splat_pair_fold(const float* __restrict__ pair, const int32_t* __restrict__ start, const int32_t* __restrict__ thits,
                                   const float* __restrict__ conics, int64_t N, float* __restrict__ v_xys, float* __restrict__ v_conics,
                                   float* __restrict__ v_colors, float* __restrict__ v_lnop, float* __restrict__ v_lnop_th, AbsArgs... abs_args) {
-  constexpr bool ABS = sizeof...(AbsArgs) == 1;
-  static_assert(sizeof...(AbsArgs) <= 1 && (NG - (ABS ? SPLAT_PAIR_ABS : 0) == SPLAT_PAIR_GRADS || NG - (ABS ? SPLAT_PAIR_ABS : 0) == SPLAT_PAIR_GRADS_SEP),
-                "ABS takes v_xys_abs and SPLAT_PAIR_ABS more sums");
+  constexpr bool ABS = pack_has<float*, AbsArgs...>, DEPTH = pack_has<SplatDepthFoldK, AbsArgs...>;
+  constexpr int BASE = NG - (ABS ? SPLAT_PAIR_ABS : 0) - (DEPTH ? SPLAT_PAIR_DEPTH : 0);
+  static_assert(sizeof...(AbsArgs) == (ABS ? 1 : 0) + (DEPTH ? 1 : 0) && (BASE == SPLAT_PAIR_GRADS || BASE == SPLAT_PAIR_GRADS_SEP),
+                "ABS takes v_xys_abs and SPLAT_PAIR_ABS more sums, DEPTH a SplatDepthFoldK and SPLAT_PAIR_DEPTH more");
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= N) return;
   float s[NG];
@@ -1023,10 +1071,11 @@ __global__ void k_splat_pair_fold(const float* __restrict__ pair, const int32_t*
   v_conics[3 * i] = s[2]; v_conics[3 * i + 1] = s[3]; v_conics[3 * i + 2] = s[4];
   v_colors[4 * i] = s[5]; v_colors[4 * i + 1] = s[6]; v_colors[4 * i + 2] = s[7]; v_colors[4 * i + 3] = s[8];
   v_lnop[i] = s[9];
-  constexpr bool SEP = NG - (ABS ? SPLAT_PAIR_ABS : 0) > SPLAT_PAIR_GRADS;
+  constexpr bool SEP = BASE > SPLAT_PAIR_GRADS;
   if (SEP) v_lnop_th[i] = s[SEP ? SPLAT_PAIR_GRADS : NG - 1];
+  if constexpr (DEPTH) pack_get<SplatDepthFoldK>(abs_args...).v_depths[i] = s[BASE];
   if constexpr (ABS) {
-    float* v_xys_abs = pack_arg<0>(abs_args...);
+    float* v_xys_abs = pack_get<float*>(abs_args...);
     v_xys_abs[2 * i] = s[NG - 2] * 0.6931471805599453f;
     v_xys_abs[2 * i + 1] = s[NG - 1] * 0.6931471805599453f;
   }
@@ -1070,6 +1119,11 @@ __device__ __forceinline__ double splat_wave_sum16(double (&v)[16], int lane) {
 // Pose (one SplatPoseBwdK, or nothing -- then the kernel is the one it was): the camera comes from the device record, and every Gaussian with
 // radii > 0 also contributes to dL/d view' [3,4] through the view-space point (gpx, gpy, gpz, frustum-clamp branches included), T = J W and the
 // projection rows xys reads.  The 12 numbers are summed per wave (splat_wave_sum16) and per block (LDS) in double and leave as ONE partial per block; no atomics.
+// Depth (one SplatDepthProjK, or nothing -- then the kernel is the one it was): depths[i] is the view-space z of the mean, so v_depths[i] = dL / d
+// depths[i] adds v_depths[i] view[2, :3] to d mean, and in the pose instantiation v_depths[i] (mean, 1) to row 2 of dL/d view' before the sums above.
+struct SplatDepthProjK {
+  const float* v_depths;  // [N]
+};
 template <bool SEP, typename... Pose>
 __global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const float* __restrict__ means, const float* __restrict__ log_scales,
                                                            const float* __restrict__ quats, const float* __restrict__ opac_logit,
@@ -1082,8 +1136,8 @@ __global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const 
                                                            float* __restrict__ g_frest, float* __restrict__ g_tdc, float* __restrict__ g_trest,
                                                            const float* __restrict__ opac_th_logit, const float* __restrict__ v_lnop_th,
                                                            float* __restrict__ g_opac_th, Pose... pose_arg) {
-  constexpr bool POSE = pack_has<SplatPoseBwdK, Pose...>;
-  static_assert(sizeof...(Pose) == (POSE ? 1 : 0), "the pose instantiation takes one SplatPoseBwdK");
+  constexpr bool POSE = pack_has<SplatPoseBwdK, Pose...>, DEPTH = pack_has<SplatDepthProjK, Pose...>;
+  static_assert(sizeof...(Pose) == (POSE ? 1 : 0) + (DEPTH ? 1 : 0), "the pack takes one SplatPoseBwdK, one SplatDepthProjK, or both");
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   [[maybe_unused]] const bool live = i < N;  // (pose: the tail's threads stay for the block's reduction)
   [[maybe_unused]] float dV[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -1209,6 +1263,12 @@ __global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const 
     const float g_hw = -(vx * 0.5f * (float)cam.W * hx + vy * 0.5f * (float)cam.H * hy) * rw * rw;
 #pragma unroll
     for (int cc = 0; cc < 3; ++cc) gm[cc] += P[cc] * g_hx + P[4 + cc] * g_hy + P[12 + cc] * g_hw;
+    [[maybe_unused]] float vz = 0.f;
+    if constexpr (DEPTH) {  // depths = view[2] . (mean, 1)
+      vz = pack_get<SplatDepthProjK>(pose_arg...).v_depths[i];
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc) gm[cc] += V[8 + cc] * vz;
+    }
     if constexpr (POSE) {
       const float mh[4] = {mx, my, mz, 1.0f};
       const float ax = proj_x * g_hx, ay = proj_y * g_hy;  // proj row 0 = proj_x view'[0], row 1 = proj_y view'[1], row 3 = view'[2]
@@ -1223,6 +1283,10 @@ __global__ void __launch_bounds__(256) k_splat_project_bwd(SplatCamK cam, const 
         dV[cc] += gT0[cc] * J0[0];
         dV[4 + cc] += gT1[cc] * J1[1];
         dV[8 + cc] += gT0[cc] * J0[2] + gT1[cc] * J1[2];
+      }
+      if constexpr (DEPTH) {
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) dV[8 + cc] += vz * mh[cc];
       }
     }
     // Sigma = M M^T, M = R diag(s): d M = (G + G^T) M
@@ -1744,17 +1808,20 @@ static int splat_raster_backward(const char* who, bool sep, bool absgrad, const 
                                  int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
                                  const float* transmittance_th, const int32_t* last_th, const float* conics, const float* v_rgbt, const float* v_alpha,
                                  const float* v_alpha_th, void* bwd_workspace, int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics,
-                                 float* v_colors, float* v_log_opacity, float* v_log_opacity_th, tn_stream_t stream) {
+                                 float* v_colors, float* v_log_opacity, float* v_log_opacity_th, const float* depth, const float* v_depth, float* v_depths,
+                                 tn_stream_t stream) {
   int rc = check_cam(camera, who);
   if (rc) return rc;
+  const bool with_depth = depth || v_depth || v_depths;  // the DEPTH instantiations (tn_depth_splat_raster_backward)
   TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31), "%s: bad Gaussian count", who);
   TN_REQUIRE(max_intersections >= 0 && num_intersections >= 0 && num_intersections <= max_intersections, "%s: %lld intersections for a workspace of %lld", who,
              (long long)num_intersections, (long long)max_intersections);
   if (num_gaussians == 0) return TN_OK;
   TN_REQUIRE(workspace && background4 && transmittance && last && conics && v_rgbt && v_alpha && bwd_workspace && v_xys && v_conics && v_colors &&
-                 v_log_opacity && (!sep || (transmittance_th && last_th && v_alpha_th && v_log_opacity_th)) && (!absgrad || v_xys_abs),
+                 v_log_opacity && (!sep || (transmittance_th && last_th && v_alpha_th && v_log_opacity_th)) && (!absgrad || v_xys_abs) &&
+                 (!with_depth || (depth && v_depth && v_depths)),
              "%s: null pointer", who);
-  const int ng = (sep ? SPLAT_PAIR_GRADS_SEP : SPLAT_PAIR_GRADS) + (absgrad ? SPLAT_PAIR_ABS : 0);
+  const int ng = splat_pair_grads(sep, absgrad, with_depth);
   size_t need_sz = 0;
   (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, ng, &need_sz);
   const int64_t need = (int64_t)need_sz;
@@ -1773,7 +1840,22 @@ static int splat_raster_backward(const char* who, bool sep, bool absgrad, const 
       return TN_ELAUNCH;
     }
     float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
-    if (sep && absgrad)
+    const SplatDepthBwdK dk{depth, v_depth};
+    if (with_depth && sep && absgrad)
+      hipLaunchKernelGGL((k_splat_raster_bwd<true, true, const float*, const int32_t*, const float*, SplatDepthBwdK>), dim3(num_tiles), dim3(256), 0, st, ws.recs,
+                         ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, transmittance_th,
+                         last_th, v_alpha_th, dk);
+    else if (with_depth && sep)
+      hipLaunchKernelGGL((k_splat_raster_bwd<true, false, const float*, const int32_t*, const float*, SplatDepthBwdK>), dim3(num_tiles), dim3(256), 0, st, ws.recs,
+                         ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, transmittance_th,
+                         last_th, v_alpha_th, dk);
+    else if (with_depth && absgrad)
+      hipLaunchKernelGGL((k_splat_raster_bwd<false, true, SplatDepthBwdK>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H,
+                         k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, dk);
+    else if (with_depth)
+      hipLaunchKernelGGL((k_splat_raster_bwd<false, false, SplatDepthBwdK>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H,
+                         k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, dk);
+    else if (sep && absgrad)
       hipLaunchKernelGGL((k_splat_raster_bwd<true, true, const float*, const int32_t*, const float*>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1],
                          ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, transmittance_th, last_th,
                          v_alpha_th);
@@ -1790,7 +1872,16 @@ static int splat_raster_backward(const char* who, bool sep, bool absgrad, const 
     TN_CHECK_LAUNCH(who);
   }
   const dim3 fold_grid((unsigned)tn_cdiv(num_gaussians, 256));
-  if (absgrad)
+  const SplatDepthFoldK fk{v_depths};
+  if (with_depth && absgrad)
+    hipLaunchKernelGGL((sep ? k_splat_pair_fold<SPLAT_PAIR_GRADS_SEP + SPLAT_PAIR_DEPTH + SPLAT_PAIR_ABS, float*, SplatDepthFoldK>
+                            : k_splat_pair_fold<SPLAT_PAIR_GRADS + SPLAT_PAIR_DEPTH + SPLAT_PAIR_ABS, float*, SplatDepthFoldK>),
+                       fold_grid, dim3(256), 0, st, bw.pair, bw.start, ws.thits, conics, num_gaussians, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_th,
+                       v_xys_abs, fk);
+  else if (with_depth)
+    hipLaunchKernelGGL((sep ? k_splat_pair_fold<SPLAT_PAIR_GRADS_SEP + SPLAT_PAIR_DEPTH, SplatDepthFoldK> : k_splat_pair_fold<SPLAT_PAIR_GRADS + SPLAT_PAIR_DEPTH, SplatDepthFoldK>),
+                       fold_grid, dim3(256), 0, st, bw.pair, bw.start, ws.thits, conics, num_gaussians, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_th, fk);
+  else if (absgrad)
     hipLaunchKernelGGL((sep ? k_splat_pair_fold<SPLAT_PAIR_GRADS_SEP + SPLAT_PAIR_ABS, float*> : k_splat_pair_fold<SPLAT_PAIR_GRADS + SPLAT_PAIR_ABS, float*>), fold_grid,
                        dim3(256), 0, st, bw.pair, bw.start, ws.thits, conics, num_gaussians, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_th, v_xys_abs);
   else
@@ -1807,7 +1898,7 @@ extern "C" int tn_splat_raster_backward(const TnSplatCamera* camera, int64_t num
                                         tn_stream_t stream) {
   return splat_raster_backward("tn_splat_raster_backward", false, false, camera, num_gaussians, workspace, max_intersections, num_intersections, background4, transmittance,
                                last, nullptr, nullptr, conics, v_rgbt, v_alpha, nullptr, bwd_workspace, bwd_workspace_bytes, v_xys, nullptr, v_conics, v_colors,
-                               v_log_opacity, nullptr, stream);
+                               v_log_opacity, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int tn_splat_raster_backward_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
@@ -1817,7 +1908,7 @@ extern "C" int tn_splat_raster_backward_sep(const TnSplatCamera* camera, int64_t
                                             float* v_conics, float* v_colors, float* v_log_opacity, float* v_log_opacity_thermal, tn_stream_t stream) {
   return splat_raster_backward("tn_splat_raster_backward_sep", true, false, camera, num_gaussians, workspace, max_intersections, num_intersections, background4,
                                transmittance, last, transmittance_thermal, last_thermal, conics, v_rgbt, v_alpha, v_alpha_thermal, bwd_workspace,
-                               bwd_workspace_bytes, v_xys, nullptr, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, stream);
+                               bwd_workspace_bytes, v_xys, nullptr, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, nullptr, nullptr, nullptr, stream);
 }
 
 // The two entry points above with the absgrad statistic: v_xys_abs [N,2] = sum over pixels of |the pixel's term of v_xys|, per component
@@ -1829,7 +1920,7 @@ extern "C" int tn_splat_raster_backward_abs(const TnSplatCamera* camera, int64_t
                                             float* v_log_opacity, tn_stream_t stream) {
   return splat_raster_backward("tn_splat_raster_backward_abs", false, true, camera, num_gaussians, workspace, max_intersections, num_intersections, background4,
                                transmittance, last, nullptr, nullptr, conics, v_rgbt, v_alpha, nullptr, bwd_workspace, bwd_workspace_bytes, v_xys, v_xys_abs, v_conics,
-                               v_colors, v_log_opacity, nullptr, stream);
+                               v_colors, v_log_opacity, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int tn_splat_raster_backward_abs_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
@@ -1840,7 +1931,26 @@ extern "C" int tn_splat_raster_backward_abs_sep(const TnSplatCamera* camera, int
                                                 float* v_log_opacity_thermal, tn_stream_t stream) {
   return splat_raster_backward("tn_splat_raster_backward_abs_sep", true, true, camera, num_gaussians, workspace, max_intersections, num_intersections, background4,
                                transmittance, last, transmittance_thermal, last_thermal, conics, v_rgbt, v_alpha, v_alpha_thermal, bwd_workspace,
-                               bwd_workspace_bytes, v_xys, v_xys_abs, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, stream);
+                               bwd_workspace_bytes, v_xys, v_xys_abs, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, nullptr, nullptr, nullptr, stream);
+}
+
+// The raster backward with an upstream gradient of the depth image (SPLAT_PAIR_DEPTH; classic mode only: in antialiased mode the depth is blended by a
+// chain of its own whose final transmittance and last contributor the training forward does not keep).  The arguments of
+// tn_splat_raster_backward_abs_sep plus `antialiased`, depth (the forward's normalised image), v_depth and v_depths; a null thermal group selects
+// shared mode, a null v_xys_abs no absgrad.  Workspace: tn_splat_depth_backward_workspace_bytes.
+extern "C" int tn_depth_splat_raster_backward(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                              int64_t num_intersections, const float* background4, int32_t antialiased, const float* transmittance,
+                                              const int32_t* last, const float* transmittance_thermal, const int32_t* last_thermal, const float* conics,
+                                              const float* v_rgbt, const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace,
+                                              int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors,
+                                              float* v_log_opacity, float* v_log_opacity_thermal, const float* depth, const float* v_depth,
+                                              float* v_depths, tn_stream_t stream) {
+  TN_REQUIRE(antialiased == 0, "tn_depth_splat_raster_backward: the depth gradient exists in classic mode only (antialiased depth rides a chain of its own)");
+  const bool sep = transmittance_thermal || last_thermal || v_alpha_thermal || v_log_opacity_thermal;
+  TN_REQUIRE(num_gaussians == 0 || (depth && v_depth && v_depths), "tn_depth_splat_raster_backward: null pointer");
+  return splat_raster_backward("tn_depth_splat_raster_backward", sep, v_xys_abs != nullptr, camera, num_gaussians, workspace, max_intersections, num_intersections,
+                               background4, transmittance, last, transmittance_thermal, last_thermal, conics, v_rgbt, v_alpha, v_alpha_thermal, bwd_workspace,
+                               bwd_workspace_bytes, v_xys, v_xys_abs, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, depth, v_depth, v_depths, stream);
 }
 
 struct PoseBwdArgs {  // what the pose entry points add to the projection backward (null: the entry points without _pose)
@@ -1862,7 +1972,7 @@ static int splat_project_backward(const char* who, bool sep, const PoseBwdArgs* 
                                   int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics, const float* v_colors,
                                   const float* v_log_opacity, const float* v_log_opacity_th, float* v_means, float* v_log_scales, float* v_quats,
                                   float* v_opacities, float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest,
-                                  float* v_opacities_th, tn_stream_t stream) {
+                                  float* v_opacities_th, const float* v_depths, tn_stream_t stream) {
   int rc = check_cam(camera, who);
   if (rc) return rc;
   if (num_gaussians == 0) return TN_OK;
@@ -1883,7 +1993,18 @@ static int splat_project_backward(const char* who, bool sep, const PoseBwdArgs* 
                (long long)pose->workspace_bytes, (long long)need);
     const int nblk = (int)tn_cdiv(num_gaussians, 256);
     const SplatPoseBwdK pk{pose->rec, (double*)pose->workspace};
-    if (sep)
+    const SplatDepthProjK zk{v_depths};
+    if (v_depths && sep)
+      hipLaunchKernelGGL((k_splat_project_bwd<true, SplatPoseBwdK, SplatDepthProjK>), dim3((unsigned)nblk), dim3(256), 0, tn_s(stream), k, means, log_scales, quats,
+                         opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii, v_xys,
+                         v_conics, v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
+                         v_thermal_rest, opacities_th, v_log_opacity_th, v_opacities_th, pk, zk);
+    else if (v_depths)
+      hipLaunchKernelGGL((k_splat_project_bwd<false, SplatPoseBwdK, SplatDepthProjK>), dim3((unsigned)nblk), dim3(256), 0, tn_s(stream), k, means, log_scales, quats,
+                         opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii, v_xys,
+                         v_conics, v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
+                         v_thermal_rest, opacities_th, v_log_opacity_th, v_opacities_th, pk, zk);
+    else if (sep)
       hipLaunchKernelGGL((k_splat_project_bwd<true, SplatPoseBwdK>), dim3((unsigned)nblk), dim3(256), 0, tn_s(stream), k, means, log_scales, quats, opacities,
                          features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii, v_xys, v_conics,
                          v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc, v_thermal_rest,
@@ -1899,10 +2020,16 @@ static int splat_project_backward(const char* who, bool sep, const PoseBwdArgs* 
     TN_CHECK_LAUNCH(who);
     return TN_OK;
   }
-  hipLaunchKernelGGL(sep ? k_splat_project_bwd<true> : k_splat_project_bwd<false>, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, tn_s(stream), k, means,
-                     log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii,
-                     v_xys, v_conics, v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
-                     v_thermal_rest, opacities_th, v_log_opacity_th, v_opacities_th);
+  if (v_depths)
+    hipLaunchKernelGGL((sep ? k_splat_project_bwd<true, SplatDepthProjK> : k_splat_project_bwd<false, SplatDepthProjK>), dim3((unsigned)tn_cdiv(num_gaussians, 256)),
+                       dim3(256), 0, tn_s(stream), k, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree,
+                       num_rest_coeffs, antialiased, radii, v_xys, v_conics, v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc,
+                       v_features_rest, v_thermal_dc, v_thermal_rest, opacities_th, v_log_opacity_th, v_opacities_th, SplatDepthProjK{v_depths});
+  else
+    hipLaunchKernelGGL(sep ? k_splat_project_bwd<true> : k_splat_project_bwd<false>, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, tn_s(stream), k, means,
+                       log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii,
+                       v_xys, v_conics, v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
+                       v_thermal_rest, opacities_th, v_log_opacity_th, v_opacities_th);
   TN_CHECK_LAUNCH(who);
   return TN_OK;
 }
@@ -1915,7 +2042,7 @@ extern "C" int tn_splat_project_backward(const TnSplatCamera* camera, const floa
                                          float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest, tn_stream_t stream) {
   return splat_project_backward("tn_splat_project_backward", false, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
                                 nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics, v_colors, v_log_opacity, nullptr, v_means,
-                                v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc, v_thermal_rest, nullptr, stream);
+                                v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc, v_thermal_rest, nullptr, nullptr, stream);
 }
 
 extern "C" int tn_splat_project_backward_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
@@ -1928,7 +2055,7 @@ extern "C" int tn_splat_project_backward_sep(const TnSplatCamera* camera, const 
   return splat_project_backward("tn_splat_project_backward_sep", true, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
                                 thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics, v_colors,
                                 v_log_opacity, v_log_opacity_thermal, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
-                                v_thermal_rest, v_opacities_thermal, stream);
+                                v_thermal_rest, v_opacities_thermal, nullptr, stream);
 }
 
 // The pose backward: tn_splat_project_backward / _sep with the camera of the forward's record, plus dL/d(pose row): pose_camera and pose_row as
@@ -1946,7 +2073,7 @@ extern "C" int tn_splat_project_backward_pose(const TnSplatCamera* camera, const
   return splat_project_backward("tn_splat_project_backward_pose", false, &pa, camera, means, log_scales, quats, opacities, features_dc, features_rest,
                                 thermal_dc, thermal_rest, nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics, v_colors,
                                 v_log_opacity, nullptr, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
-                                v_thermal_rest, nullptr, stream);
+                                v_thermal_rest, nullptr, nullptr, stream);
 }
 
 extern "C" int tn_splat_project_backward_pose_sep(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
@@ -1962,7 +2089,29 @@ extern "C" int tn_splat_project_backward_pose_sep(const TnSplatCamera* camera, c
   return splat_project_backward("tn_splat_project_backward_pose_sep", true, &pa, camera, means, log_scales, quats, opacities, features_dc, features_rest,
                                 thermal_dc, thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics,
                                 v_colors, v_log_opacity, v_log_opacity_thermal, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest,
-                                v_thermal_dc, v_thermal_rest, v_opacities_thermal, stream);
+                                v_thermal_dc, v_thermal_rest, v_opacities_thermal, nullptr, stream);
+}
+
+// The projection backward with dL / d depths (SplatDepthProjK): the arguments of tn_splat_project_backward_pose_sep plus v_depths [N].  A null pose group
+// (pose_camera) means no pose, null thermal-opacity pointers select shared mode.  Classic mode only, as tn_depth_splat_raster_backward.
+extern "C" int tn_depth_splat_project_backward(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
+                                               const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
+                                               const float* features_rest, const float* thermal_dc, const float* thermal_rest,
+                                               const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
+                                               int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics,
+                                               const float* v_colors, const float* v_log_opacity, const float* v_log_opacity_thermal,
+                                               const float* v_depths, float* v_means, float* v_log_scales, float* v_quats, float* v_opacities,
+                                               float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest,
+                                               float* v_opacities_thermal, void* workspace, int64_t workspace_bytes, float* grad_pose_row,
+                                               float* dview_out, tn_stream_t stream) {
+  TN_REQUIRE(antialiased == 0, "tn_depth_splat_project_backward: the depth gradient exists in classic mode only (antialiased depth rides a chain of its own)");
+  TN_REQUIRE(num_gaussians == 0 || v_depths, "tn_depth_splat_project_backward: null pointer");
+  const bool sep = opacities_thermal || v_log_opacity_thermal || v_opacities_thermal;
+  const PoseBwdArgs pa{pose_camera, pose_row, workspace, workspace_bytes, grad_pose_row, dview_out};
+  return splat_project_backward("tn_depth_splat_project_backward", sep, pose_camera ? &pa : nullptr, camera, means, log_scales, quats, opacities, features_dc,
+                                features_rest, thermal_dc, thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys,
+                                v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest,
+                                v_thermal_dc, v_thermal_rest, v_opacities_thermal, v_depths, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ refinement

@@ -20,6 +20,13 @@
 //                         halo in LDS; every pixel sums its right and its lower edge into the loss (an edge counts once per window that holds it)
 //                         and GATHERS its gradient from its four edges; one partial sum per term and block.
 //   k_thermal_reg_finish  one block: the partial sums in a fixed order (double) -> [tv_mult * tv, cross_mult * cc] on the device.
+//
+// And the two geometric priors on the depth render (tn_depth_loss): the L1 distance to a sensor depth and the 2 x 2 total variation of the depth,
+// both only where the render is covered (accumulation > 0).  Their normalisations -- the number of valid pixels and of covered windows -- are data, so
+// the gradient's constants exist only after the sums: three launches, no float atomics:
+//   k_depth_loss<false>   one block per 64 x 16 tile: stages depth and coverage with a 1-pixel halo; one partial sum and one partial count per term.
+//   k_depth_loss_finish   one block: sums and counts in a fixed order (double) -> the two losses and the two gradient constants on the device.
+//   k_depth_loss<true>    the same tiles again (gradient requested): every pixel GATHERS its gradient from its own term and its four edges.
 #include "tn_common.h"
 
 namespace {
@@ -562,6 +569,131 @@ __global__ __launch_bounds__(LB) void k_thermal_reg_finish(const float* part_tv,
   }
 }
 
+// ---- tn_depth_loss.  depth_loss = mean |depth - sensor| over the pixels with accumulation > 0 and a finite, positive sensor depth; depth_tv_loss =
+// the total variation above (0.25 * mean of the four absolute differences) over the stride-1 2 x 2 windows whose FOUR pixels have accumulation > 0 --
+// an uncovered pixel holds the frame's fill value, which would put an edge on every silhouette.  Either is 0 without a pixel / window to average over.
+// As edge terms: a horizontal edge sits in the window above and the window below it, a vertical edge in the window left and right of it, and it counts
+// once per COVERED window among the two; a pixel's windows are the four it is a corner of (NW, NE, SW, SE by the window's position around the pixel).
+struct DepthLossK {
+  const float* depth;   // [H][W]
+  const float* alpha;   // [H][W] accumulation
+  const float* sensor;  // [H][W] or null (no depth_loss)
+  int H, W;
+  int tv;               // the TV term is on
+  float* grad;          // GRAD: [H][W]
+  float* part;          // [4][blocks]: sum |depth - sensor|, its pixels, sum of the TV edge terms, covered windows
+  int64_t part_stride;  // floats between the four
+  const float* scale;   // GRAD: [2] on the device: depth_mult / pixels, tv_mult * 0.25 / windows (0 where there are none)
+};
+
+template <bool GRAD>
+__global__ __launch_bounds__(LB) void k_depth_loss(DepthLossK k) {
+  __shared__ float sd[RSY][RSX];    // depth (0 outside the frame)
+  __shared__ float scv[RSY][RSX];   // 1 where the pixel is inside the frame and covered, else 0
+  __shared__ float red[4][LB / 64];
+  const int t = threadIdx.x, tx0 = blockIdx.x * RTX, ty0 = blockIdx.y * RTY;
+  for (int i = t; i < RSY * RSX; i += LB) {
+    const int r = i / RSX, q = i - r * RSX, y = ty0 - 1 + r, x = tx0 - 1 + q;
+    float a = 0.0f, c = 0.0f;
+    if (y >= 0 && y < k.H && x >= 0 && x < k.W) {
+      const int64_t p = (int64_t)y * k.W + x;
+      a = k.depth[p];
+      c = k.alpha[p] > 0.0f ? 1.0f : 0.0f;
+    }
+    sd[r][q] = a;
+    scv[r][q] = c;
+  }
+  __syncthreads();
+  float c_d = 0.0f, c_tv = 0.0f;
+  if constexpr (GRAD) c_d = k.scale[0], c_tv = k.scale[1];
+  const int col = t & (RTX - 1), r0 = (t / RTX) * RRO;
+  const int px = tx0 + col, lc = col + 1;
+  float l_d = 0.0f, n_d = 0.0f, l_tv = 0.0f, n_tv = 0.0f;
+#pragma unroll
+  for (int o = 0; o < RRO; ++o) {
+    const int py = ty0 + r0 + o, lr = r0 + o + 1;
+    if (py < k.H && px < k.W) {
+      const int64_t p = (int64_t)py * k.W + px;
+      const float t0 = sd[lr][lc];
+      float g = 0.0f;
+      if (k.sensor != nullptr) {
+        const float s = k.sensor[p];
+        if (scv[lr][lc] > 0.0f && s > 0.0f && s <= 3.402823466e38f) {  // covered, and the sensor depth finite and positive (a NaN fails both)
+          const float e = t0 - s;
+          l_d += fabsf(e);
+          n_d += 1.0f;
+          g = c_d * sign0(e);
+        }
+      }
+      if (k.tv) {
+        // the four windows around the pixel; a window is covered when its four pixels are (one outside the frame is not)
+        const float cN = scv[lr - 1][lc] * scv[lr][lc], cS = scv[lr][lc] * scv[lr + 1][lc];
+        const float nw = cN * scv[lr - 1][lc - 1] * scv[lr][lc - 1], ne = cN * scv[lr - 1][lc + 1] * scv[lr][lc + 1];
+        const float sw = cS * scv[lr][lc - 1] * scv[lr + 1][lc - 1], se = cS * scv[lr][lc + 1] * scv[lr + 1][lc + 1];
+        const float wL = nw + sw, wR = ne + se, wU = nw + ne, wD = sw + se;  // covered windows that hold each of the pixel's edges
+        const float eL = sd[lr][lc - 1] - t0, eR = t0 - sd[lr][lc + 1], eU = sd[lr - 1][lc] - t0, eD = t0 - sd[lr + 1][lc];
+        if constexpr (GRAD) {
+          g += c_tv * (wR * sign0(eR) - wL * sign0(eL) + wD * sign0(eD) - wU * sign0(eU));
+        } else {
+          l_tv += wR * fabsf(eR) + wD * fabsf(eD);  // (an edge of weight 0 joins finite values: the fill value is finite)
+          n_tv += se;                               // the window whose top-left pixel this is
+        }
+      }
+      if constexpr (GRAD) k.grad[p] = g;
+    }
+  }
+  if constexpr (!GRAD) {
+    const int b = blockIdx.y * gridDim.x + blockIdx.x;
+    const float v[4] = {l_d, n_d, l_tv, n_tv};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float sum = block_sum(v[j], red[j]);
+      if (t == 0) k.part[j * k.part_stride + b] = sum;
+    }
+  }
+}
+
+// out = [depth_mult * depth_loss, tv_mult * depth_tv_loss]; scale = the gradient's two constants.  A term without pixels / windows is exactly 0.
+__global__ __launch_bounds__(LB) void k_depth_loss_finish(const float* part, int64_t part_stride, int n, double depth_mult, double tv_mult, float* out,
+                                                          float* scale) {
+  __shared__ double r[4][LB];
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    double a = 0.0;
+    for (int i = t; i < n; i += LB) a += (double)part[j * part_stride + i];
+    r[j][t] = a;
+  }
+  __syncthreads();
+  for (int s = LB / 2; s > 0; s >>= 1) {
+    if (t < s) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) r[j][t] += r[j][t + s];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    const double cd = r[1][0] > 0.0 ? depth_mult / r[1][0] : 0.0, ctv = r[3][0] > 0.0 ? tv_mult * 0.25 / r[3][0] : 0.0;
+    out[0] = (float)(cd * r[0][0]);
+    out[1] = (float)(ctv * r[2][0]);
+    scale[0] = (float)cd;
+    scale[1] = (float)ctv;
+  }
+}
+
+struct DepthLossLayout {
+  int64_t bx, by, part_stride, off_scale, total;
+};
+
+DepthLossLayout depth_loss_layout(int32_t H, int32_t W) {
+  DepthLossLayout L;
+  L.bx = tn_cdiv(W, RTX), L.by = tn_cdiv(H, RTY);
+  L.part_stride = align256(L.bx * L.by * 4) / 4;
+  L.off_scale = 4 * L.part_stride * 4;
+  L.total = L.off_scale + 256;
+  return L;
+}
+
 struct RegLayout {
   int64_t bx, by, off_cc, total;
 };
@@ -723,5 +855,40 @@ extern "C" int tn_thermal_reg(const float* pred_thermal, int64_t pred_pixel_stri
   hipLaunchKernelGGL(k_thermal_reg_finish, dim3(1), dim3(LB), 0, st, (const float*)k.part_tv, (const float*)k.part_cc, (int)(L.bx * L.by), stv, scc,
                      out_loss);
   TN_CHECK_LAUNCH("tn_thermal_reg(finish)");
+  return TN_OK;
+}
+
+extern "C" int64_t tn_depth_loss_workspace_bytes(int32_t height, int32_t width) {
+  if (height < 2 || width < 2 || height > kMaxSide || width > kMaxSide) return -1;
+  return depth_loss_layout(height, width).total;
+}
+
+extern "C" int tn_depth_loss(const float* depth, const float* accumulation, const float* depth_image, int32_t height, int32_t width, float depth_mult,
+                             float tv_mult, void* workspace, int64_t workspace_bytes, float* out_loss, float* out_grad, tn_stream_t stream) {
+  TN_REQUIRE(depth && accumulation && workspace && out_loss, "tn_depth_loss: null pointer");
+  TN_REQUIRE(height >= 2 && width >= 2, "tn_depth_loss: %d x %d image, a 2 x 2 window needs at least 2 x 2", height, width);
+  TN_REQUIRE(height <= kMaxSide && width <= kMaxSide, "tn_depth_loss: %d x %d image is larger than %d on a side", height, width, kMaxSide);
+  TN_REQUIRE(depth_mult >= 0.0f && tv_mult >= 0.0f, "tn_depth_loss: multipliers %g / %g, a loss multiplier cannot be negative", (double)depth_mult, (double)tv_mult);
+  const DepthLossLayout L = depth_loss_layout(height, width);
+  TN_REQUIRE(workspace_bytes >= L.total, "tn_depth_loss: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)L.total);
+  DepthLossK k;
+  k.depth = depth, k.alpha = accumulation;
+  k.sensor = depth_mult != 0.0f ? depth_image : nullptr;  // a multiplier of 0 (or no sensor depth) skips the term: exactly 0
+  k.H = height, k.W = width, k.tv = tv_mult != 0.0f ? 1 : 0;
+  k.grad = out_grad;
+  k.part = static_cast<float*>(workspace), k.part_stride = L.part_stride;
+  float* scale = reinterpret_cast<float*>(static_cast<char*>(workspace) + L.off_scale);
+  k.scale = scale;
+  hipStream_t st = tn_s(stream);
+  const dim3 grid((unsigned)L.bx, (unsigned)L.by);
+  hipLaunchKernelGGL(k_depth_loss<false>, grid, dim3(LB), 0, st, k);
+  TN_CHECK_LAUNCH("tn_depth_loss");
+  hipLaunchKernelGGL(k_depth_loss_finish, dim3(1), dim3(LB), 0, st, (const float*)k.part, k.part_stride, (int)(L.bx * L.by), (double)depth_mult, (double)tv_mult,
+                     out_loss, scale);
+  TN_CHECK_LAUNCH("tn_depth_loss(finish)");
+  if (out_grad != nullptr) {
+    hipLaunchKernelGGL(k_depth_loss<true>, grid, dim3(LB), 0, st, k);
+    TN_CHECK_LAUNCH("tn_depth_loss(gradient)");
+  }
   return TN_OK;
 }

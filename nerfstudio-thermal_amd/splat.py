@@ -20,7 +20,12 @@ and background weight of its own -- what sits behind glass or an IR-transparent 
 `get_outputs` is the eval render.  `get_train_outputs` is the same render as a differentiable function of every `gauss_params` tensor: its
 backward (tn_splat_raster_backward / tn_splat_project_backward) is the exact, bit-reproducible derivative of the forward this file computes,
 and it leaves dL/d xys per Gaussian in `last_xys_grad` (what splatfacto's densification reads as `self.xys.grad`, splatfacto.py:355).
-Depth is returned detached.  Training follows splatfacto's refinement (splatfacto.py:346-498): `after_train` accumulates the gradient
+Depth is returned detached unless `differentiable_depth` is on (classic mode): then `depth` [H,W,1] carries gradients too -- depth = D / accumulation
+where the pixel is covered, D riding the RGB chain as a fifth channel; the fill value elsewhere takes none -- through tn_depth_splat_raster_backward /
+tn_depth_splat_project_backward, as exact and atomic-free as the rest; a backward whose loss never touched depth runs the entry points of before and
+gives their bits.  `depth_loss_mult` / `depth_tv_loss_mult` above 0 (both default 0) add `depth_loss` -- the L1 distance to the batch's `depth_image`, a
+sensor depth -- and `depth_tv_loss` -- the depth's 2 x 2 total variation -- over the covered pixels, on RGB and thermal frames alike (`depth_losses`:
+tn_depth_loss).  Training follows splatfacto's refinement (splatfacto.py:346-498): `after_train` accumulates the gradient
 statistics (tn_splat_grad_stats), `refinement_after` splits, duplicates and culls the Gaussians (tn_splat_refine_plan / tn_splat_refine_apply)
 and carries every optimiser's parameter and Adam moments along, and resets the opacities now and then.  The objective is splatfacto's
 (splatfacto.py:848-903): `get_loss_dict` takes the image loss of the frame's spectrum; `background_color = "random"` draws
@@ -53,7 +58,7 @@ tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 
 splat_calls.py: the C entry points, their names and argument order, the workspaces, `knn_distances`, `mcmc_relocate`, `mcmc_noise`.
 splat_camera.py: `PinholeCamera`, `camera_struct`, the resolution schedule's camera, `undistorted_camera`, `OrientedBox`, the pose optimiser.
-splat_image.py: `image_loss`, `resize_image`, `undistort_image`, `thermal_regularizers`, `ssim`.
+splat_image.py: `image_loss`, `resize_image`, `undistort_image`, `thermal_regularizers`, `depth_losses`, `ssim`.
 """
 from __future__ import annotations
 
@@ -70,7 +75,7 @@ from .config import CameraOptimizerConfig
 from .splat_calls import KNN_MAX_K, _PARAM_NAMES, knn_distances, mcmc_noise, mcmc_relocate, param_names  # noqa: F401
 from .splat_camera import (CAMERA_OPTIMIZER_MODES, OrientedBox, PinholeCamera, SplatCameraOptimizer, camera_struct, downscale_factor,  # noqa: F401
                            pose_camera_record, projection_matrix, rescaled_camera, undistorted_camera)
-from .splat_image import MAX_IMAGE_SIDE, _psnr, image_loss, resize_image, ssim, thermal_regularizers, undistort_image  # noqa: F401
+from .splat_image import MAX_IMAGE_SIDE, _psnr, depth_losses, image_loss, resize_image, ssim, thermal_regularizers, undistort_image  # noqa: F401
 
 BLOCK_WIDTH = 16  # splatfacto.py:738
 STRATEGIES = ("default", "mcmc")  # densification: splatfacto's gradient-threshold refinement, or gsplat's MCMCStrategy
@@ -94,6 +99,13 @@ class ThermalSplatfactoModelConfig:
     # ThermalNeRF's regularisers of the thermal render on RGB frames (ThermalNerfactoModelConfig's names; the NeRF path runs both at 1e-6); 0 = off
     tv_pixel_loss_mult: float = 0.0
     cross_channel_loss_mult: float = 0.0
+    # the training render's depth as a differentiable output (splatfacto's is: splatfacto.py:805-820); classic mode only -- in antialiased mode the
+    # depth is blended by a chain of its own whose final transmittance and last contributor the training forward does not keep.  Off: depth is detached
+    differentiable_depth: bool = False
+    # geometric priors on the depth render over its covered pixels (need differentiable_depth; 0 = off): depth_loss = mean |depth - batch["depth_image"]|
+    # (a sensor depth [H,W,1] in scene units, nerfstudio's DepthDataset key; 0 for a batch without one), depth_tv_loss = the depth's 2 x 2 total variation
+    depth_loss_mult: float = 0.0
+    depth_tv_loss_mult: float = 0.0
     # "shared": one opacity blends RGB and thermal; "separate": the thermal channel has opacities_thermal and a transmittance chain of its own
     # (ThermalNerfactoModelConfig.density_mode's two values).  density_loss (thermal_nerfacto.py:328-344, separate mode, 0 = off) =
     # opacity_loss_mult * (mean|o_th - o.detach()| + rgb_opacity_loss_mult * mean|o - o_th.detach()|) on the sigmoids
@@ -154,9 +166,15 @@ class ThermalSplatfactoModelConfig:
             mode = getattr(self, name).mode
             if mode not in CAMERA_OPTIMIZER_MODES:
                 raise ValueError(f'{name}.mode = {mode!r}: the splat path refines poses with "SO3xR3" or "shared_SO3xR3" ("off": not at all)')
-        for name in ("tv_pixel_loss_mult", "cross_channel_loss_mult", "opacity_loss_mult", "rgb_opacity_loss_mult"):
+        for name in ("tv_pixel_loss_mult", "cross_channel_loss_mult", "opacity_loss_mult", "rgb_opacity_loss_mult", "depth_loss_mult", "depth_tv_loss_mult"):
             if getattr(self, name) < 0:
                 raise ValueError(f"{name} = {getattr(self, name)}: a loss multiplier cannot be negative")
+        if self.differentiable_depth and self.rasterize_mode == "antialiased":
+            raise ValueError('differentiable_depth needs rasterize_mode "classic": antialiased depth is blended with the uncompensated opacity in a chain of '
+                             "its own, whose final transmittance and last contributor the training forward does not keep for a backward")
+        for name in ("depth_loss_mult", "depth_tv_loss_mult"):
+            if getattr(self, name) > 0 and not self.differentiable_depth:
+                raise ValueError(f"{name} = {getattr(self, name)} needs differentiable_depth: with a detached depth the loss would train nothing")
         if self.thermal_opacity_mode not in ("shared", "separate"):
             raise ValueError(f'thermal_opacity_mode = {self.thermal_opacity_mode!r}: "shared" or "separate"')
         if self.strategy not in STRATEGIES:
@@ -254,7 +272,8 @@ def _background_outputs(H: int, W: int, bgl: List[float], dev, sep: bool = False
 class _SplatRender(torch.autograd.Function):
     """project -> bin -> training raster; backward = raster backward -> projection backward.  Inputs after `frame` are the gauss_params in
     _PARAM_NAMES order; outputs: colour before the clamp [H,W,4] (RGB + thermal over the background), accumulation [H,W,1], depth [H,W,1]
-    (not differentiable).  Nine parameters (separate thermal opacity, opacities_thermal last): the _sep entry points, and a fourth output,
+    (not differentiable, unless frame["depth_grad"]: then a backward that receives a gradient for it runs the tn_depth_splat_* entry points, and one
+    that does not runs the others).  Nine parameters (separate thermal opacity, opacities_thermal last): the _sep entry points, and a fourth output,
     the thermal chain's accumulation [H,W,1].  A frame with a pose row (frame["pose_row"]) passes its optimiser's pose_adjustment [C,6] as one
     more input behind the parameters: the camera is corrected on the device (pose_camera_record), the _pose entry points run, and the backward
     also returns dL/d pose_adjustment [C,6], zero outside the frame's row, and leaves dL/d view' [3,4] in `last_view_grad`."""
@@ -277,24 +296,29 @@ class _SplatRender(torch.autograd.Function):
         # what after_train reads of the training frame (the reference's self.radii / self.last_size); eval renders leave these alone
         model.last_radii, model.last_size = proj["radii"], (H, W)
         ctx.frame, ctx.empty = frame, total == 0
+        depth_grad = bool(frame.get("depth_grad"))
+        if depth_grad:  # an output the loss never touched arrives as None in the backward: that is how it tells a depth upstream from none
+            ctx.set_materialize_grads(False)
         if total == 0:  # nothing on screen: the background, and zero gradients
             rgbt = torch.tensor(list(bg4), device=dev).repeat(H, W, 1)
             alpha = torch.zeros((H, W, 1), device=dev)
             depth = torch.full((H, W, 1), 10.0, device=dev)
-            ctx.mark_non_differentiable(depth)
+            if not depth_grad:
+                ctx.mark_non_differentiable(depth)
             ctx.save_for_backward(*params)
             return (rgbt, alpha, depth, torch.zeros((H, W, 1), device=dev)) if sep else (rgbt, alpha, depth)
         image = lambda *c, dtype=torch.float32: torch.empty((H, W) + c, dtype=dtype, device=dev)  # noqa: E731
         rgbt, depth, alpha, final_t, last = image(4), image(1), image(1), image(), image(dtype=torch.int32)
         thermal = (image(1), image(), image(dtype=torch.int32)) if sep else ()  # the thermal chain's accumulation, final transmittance and last index
         splat_calls.raster_train(cam, N, ws, cap, bg4, aa, rgbt, depth, alpha, final_t, last, *thermal)
-        ctx.mark_non_differentiable(depth)
+        if not depth_grad:
+            ctx.mark_non_differentiable(depth)
         ctx.ws, ctx.cap, ctx.total = ws, cap, total
-        ctx.save_for_backward(*params, proj["radii"], proj["conics"], final_t, last, *thermal[1:])
+        ctx.save_for_backward(*params, proj["radii"], proj["conics"], final_t, last, *thermal[1:], *([depth] if depth_grad else []))
         return (rgbt, alpha, depth) + thermal[:1]
 
     @staticmethod
-    def backward(ctx, v_rgbt, v_alpha, _v_depth, v_alpha_th=None):
+    def backward(ctx, v_rgbt, v_alpha, v_depth, v_alpha_th=None):
         frame = ctx.frame
         model = frame["model"]
         P = frame["num_params"]
@@ -316,13 +340,16 @@ class _SplatRender(torch.autograd.Function):
         th = {}  # separate thermal opacity: the second chain's saved tensors, its upstream gradient and its opacity gradient
         if P == 9:
             th = {"final_t_th": rest[4], "last_th": rest[5], "v_alpha_th": upstream(v_alpha_th, 1), "v_lnop_th": per_gaussian()}
+        dz = {}  # a depth upstream (differentiable_depth, and the loss read depth): the forward's depth image, dL / d depth, and dL / d depths [N] to fill
+        if v_depth is not None and frame.get("depth_grad"):
+            dz = {"aa": frame["aa"], "depth": rest[-1], "v_depth": upstream(v_depth, 1), "v_depths": per_gaussian()}
         splat_calls.raster_backward(frame["cam"], N, ctx.ws, ctx.cap, ctx.total, frame["bg4"], final_t, last, conics, v_rgbt, v_alpha, v_xys, v_conics,
-                                    v_colors, v_lnop, v_xys_abs=v_xys_abs, **th)
+                                    v_colors, v_lnop, v_xys_abs=v_xys_abs, **th, **dz)
         grads = [torch.empty_like(p) for p in params]
         # a pose row: dL/d pose [C,6], zeros but for the frame's row, which the finishing kernel adds into, and dL/d view' [3,4]
         g_pose, dview = (torch.zeros_like(pose), torch.empty((3, 4), device=dev)) if pose is not None else (None, None)
         splat_calls.project_backward(frame["cam"], params, frame["deg"], frame["aa"], radii, v_xys, v_conics, v_colors, v_lnop, grads, th.get("v_lnop_th"),
-                                     ctx.rec, pose, row, g_pose, dview)
+                                     ctx.rec, pose, row, g_pose, dview, v_depths=dz.get("v_depths"))
         model.last_xys_grad, model.last_xys_absgrad = v_xys, v_xys_abs
         if pose is not None:
             model.last_view_grad = dview
@@ -571,7 +598,8 @@ class ThermalSplatfactoModel(nn.Module):
 
     def get_train_outputs(self, camera: PinholeCamera) -> Dict[str, Tensor]:
         """The render of get_outputs as a differentiable function of every gauss_params tensor (splatfacto.py:659-822 in training: `crop_box`
-        is not read, the reference crops only outside training).  rgb [H,W,3], thermal [H,W,1] and accumulation [H,W,1] carry gradients; depth [H,W,1] is detached.  With a fixed
+        is not read, the reference crops only outside training).  rgb [H,W,3], thermal [H,W,1] and accumulation [H,W,1] carry gradients; depth [H,W,1] is
+        detached, or with config.differentiable_depth carries them too (where accumulation > 0; the fill value elsewhere takes none).  With a fixed
         background the values equal get_outputs' bit for bit; background_color "random" draws this frame's RGB + thermal background from the
         model's generator (background [3], background_thermal [1]).  After backward(), `last_xys_grad` [N,2] holds dL/d xys per Gaussian
         (and, with config.use_absgrad, `last_xys_absgrad` [N,2] the sum of its per-pixel terms' absolute values).
@@ -584,6 +612,10 @@ class ThermalSplatfactoModel(nn.Module):
         bgl = self._background4(training=True)
         names = self.param_names
         frame = {"model": self, "camera": camera, "cam": camera_struct(camera), "aa": aa, "deg": deg, "bg4": (C.c_float * 4)(*bgl), "num_params": len(names)}
+        if self.config.differentiable_depth:
+            if aa:  # (the config refuses the combination; a rasterize_mode assigned afterwards must not reach the kernels)
+                raise ValueError('differentiable_depth needs rasterize_mode "classic"')
+            frame["depth_grad"] = True
         self.last_xys_grad = None
         self.last_xys_absgrad = None
         pose, row = self._pose_row(camera, training=True)
@@ -642,8 +674,11 @@ class ThermalSplatfactoModel(nn.Module):
         (one tn_thermal_reg call), on a thermal frame 0 -- the reference keeps both to the RGB rays, and the keys depend on the config alone.
         In separate mode with opacity_loss_mult > 0 also density_loss = opacity_loss_mult * (mean|s(o_th) - s(o).detach()| + rgb_opacity_loss_mult *
         mean|s(o) - s(o_th).detach()|), s = sigmoid (plain torch on [N,1]).  Under strategy "mcmc" also mcmc_opacity_reg = mcmc_opacity_reg *
-        mean(s(o)) (+ mean(s(o_th)) in separate mode) and mcmc_scale_reg = mcmc_scale_reg * mean(exp(scales)) (plain torch).  `batch`: image [H,W,3|4],
-        is_thermal."""
+        mean(s(o)) (+ mean(s(o_th)) in separate mode) and mcmc_scale_reg = mcmc_scale_reg * mean(exp(scales)) (plain torch).  With depth_loss_mult /
+        depth_tv_loss_mult above 0 also depth_loss / depth_tv_loss of outputs["depth"] over its covered pixels (one tn_depth_loss call), on RGB and thermal
+        frames alike; depth_loss is 0 for a batch without `depth_image`, and the keys depend on the config alone.  `batch`: image [H,W,3|4], is_thermal,
+        optionally depth_image [H,W,1] float32 in scene units (full size: under the resolution schedule it is taken as depth_image[::d, ::d], cut to the
+        frame -- depth is not interpolated)."""
         if "mask" in batch:
             raise NotImplementedError("masks are not supported by the splat loss (DESIGN.md section 7)")
         cfg = self.config
@@ -667,6 +702,22 @@ class ThermalSplatfactoModel(nn.Module):
                 losses["tv_pixel_loss"] = tv
             if cross_mult > 0:
                 losses["cross_channel_loss"] = cross
+        if cfg.depth_loss_mult > 0 or cfg.depth_tv_loss_mult > 0:
+            depth = outputs["depth"]
+            sensor = batch.get("depth_image") if cfg.depth_loss_mult > 0 else None
+            if sensor is not None:
+                sensor = sensor.to(dev).float()
+                if sensor.shape[:2] != depth.shape[:2]:  # the resolution schedule: every d-th pixel, never an interpolated depth
+                    d = self._get_downscale_factor()
+                    sensor = sensor[::d, ::d][:depth.shape[0], :depth.shape[1]]
+                if sensor.shape != depth.shape:
+                    raise ValueError(f"depth_image is {tuple(batch['depth_image'].shape)}, the depth render {tuple(depth.shape)} (downscale factor "
+                                     f"{self._get_downscale_factor()})")
+            d_loss, d_tv = depth_losses(depth, outputs["accumulation"], sensor, cfg.depth_loss_mult, cfg.depth_tv_loss_mult)
+            if cfg.depth_loss_mult > 0:
+                losses["depth_loss"] = d_loss
+            if cfg.depth_tv_loss_mult > 0:
+                losses["depth_tv_loss"] = d_tv
         if self.separate and cfg.opacity_loss_mult > 0:
             losses["density_loss"] = opacity_density_loss(self.gauss_params["opacities"], self.gauss_params["opacities_thermal"], cfg.opacity_loss_mult,
                                                           cfg.rgb_opacity_loss_mult)

@@ -1,10 +1,11 @@
-"""The call layer of the splat path: the one module that names the tn_splat_* / tn_knn / tn_image_* / tn_thermal_reg entry points of
+"""The call layer of the splat path: the one module that names the tn_splat_* / tn_knn / tn_image_* / tn_thermal_reg / tn_depth_loss entry points of
 libthermal_nerf_hip.so and knows their argument order (include/thermal_nerf_hip.h).  The three gsplat calls (project_gaussians,
 spherical_harmonics, rasterize_gaussians x2) run as tn_splat_project / tn_splat_bin / tn_splat_raster of libthermal_nerf_hip.so; separate thermal
 opacity runs the _sep family (tn_splat_project_sep ... tn_splat_refine_apply_sep: the same kernels instantiated with the second chain), and _crop,
 _pose and _abs are instantiations too.  A variant takes the arguments of its base, in the same order, with the optional ones inserted at fixed
 places, so every stage here is ONE call whose argument list is built from segments; which optional tensors the caller passes picks the variant
-(`entry` composes its name).  The caller decides which tensors exist: nothing is allocated here but workspaces.  Everything goes to the current
+(`entry` composes its name).  The depth gradient is the exception: its three entry points have fixed names and take the thermal-chain, absgrad and
+pose arguments as nullable pointers, so `raster_backward` / `project_backward` switch to them when `v_depth` / `v_depths` are given.  The caller decides which tensors exist: nothing is allocated here but workspaces.  Everything goes to the current
 stream; nothing but refine_plan's counts is read back.
 """
 from __future__ import annotations
@@ -149,10 +150,20 @@ def raster_removal(cam, N, ws, cap, bg4, thr, rem) -> None:
 
 
 def raster_backward(cam, N, ws, cap, total, bg4, final_t, last, conics, v_rgbt, v_alpha, v_xys, v_conics, v_colors, v_lnop, final_t_th=None, last_th=None,
-                    v_alpha_th=None, v_lnop_th=None, v_xys_abs=None) -> None:
-    """tn_splat_raster_backward over the training frame's workspace `ws`: _sep with the thermal chain's four tensors, _abs with `v_xys_abs`.  The
-    backward's own workspace is this call's."""
+                    v_alpha_th=None, v_lnop_th=None, v_xys_abs=None, aa=0, depth=None, v_depth=None, v_depths=None) -> None:
+    """tn_splat_raster_backward over the training frame's workspace `ws`: _sep with the thermal chain's four tensors, _abs with `v_xys_abs`.  With
+    `v_depth` (dL / d depth [H,W,1]; then also `depth`, the forward's normalised image, `v_depths` [N] to fill, and the frame's `aa` flag) it is
+    tn_depth_splat_raster_backward, which takes the thermal chain's tensors and `v_xys_abs` as nullable pointers.  The backward's own workspace is
+    this call's."""
     sep, absgrad = final_t_th is not None, v_xys_abs is not None
+    if v_depth is not None:
+        bws = workspace("tn_splat_depth_backward_workspace_bytes", N, cap, int(sep), int(absgrad), device=v_xys.device)
+        _call("tn_depth_splat_raster_backward", C.byref(cam), N, _raw(ws), cap, total, bg4, int(aa), *_f32(transmittance=final_t), _ptr(last, I32, "last"),
+              *_f32(transmittance_thermal=final_t_th), _ptr(last_th, I32, "last_thermal"), *_f32(conics=conics, v_rgbt=v_rgbt, v_alpha=v_alpha,
+                                                                                              v_alpha_thermal=v_alpha_th), _raw(bws), bws.numel(),
+              *_f32(v_xys=v_xys, v_xys_abs=v_xys_abs, v_conics=v_conics, v_colors=v_colors, v_log_opacity=v_lnop, v_log_opacity_thermal=v_lnop_th, depth=depth,
+                    v_depth=v_depth, v_depths=v_depths))
+        return
     bws = workspace(entry("tn_splat_backward_workspace_bytes", abs=absgrad, sep=sep), N, cap, device=v_xys.device)
     _call(entry("tn_splat_raster_backward", abs=absgrad, sep=sep), C.byref(cam), N, _raw(ws), cap, total, bg4, *_f32(transmittance=final_t),
           _ptr(last, I32, "last"), *(_f32(transmittance_thermal=final_t_th) + [_ptr(last_th, I32, "last_thermal")] if sep else []),
@@ -162,16 +173,24 @@ def raster_backward(cam, N, ws, cap, total, bg4, final_t, last, conics, v_rgbt, 
 
 
 def project_backward(cam, params, deg, aa, radii, v_xys, v_conics, v_colors, v_lnop, grads, v_lnop_th=None, pose_rec=None, pose=None, row=None,
-                     g_pose=None, dview=None) -> None:
+                     g_pose=None, dview=None, v_depths=None) -> None:
     """tn_splat_project_backward: fills `grads` (laid out as `params`; _sep with nine of each and `v_lnop_th`).  With `pose_rec` the pose
     instantiation (tn_splat_project_backward_pose / _pose_sep), which reads the corrected camera and row `row` of `pose` [C,6], adds dL/d pose into
-    that row of `g_pose` through its finishing kernel and leaves dL/d view' in `dview` [3,4].  The partials' workspace is this call's own."""
+    that row of `g_pose` through its finishing kernel and leaves dL/d view' in `dview` [3,4].  With `v_depths` (dL / d depths [N], what the depth raster
+    backward left) it is tn_depth_splat_project_backward, which takes the pose group and the thermal opacities as nullable pointers.  The partials'
+    workspace is this call's own."""
     N, sep, posed = params[0].shape[0], len(params) == 9, pose_rec is not None
     head = tail = []
     if posed:
         pws = workspace("tn_splat_pose_workspace_bytes", N, device=pose.device, what="bad Gaussian count")
         head = [_ptr(pose_rec, F32, "pose camera"), _pose_row_ptr(pose, row)]
         tail = [_raw(pws), pws.numel(), _pose_row_ptr(g_pose, row, "grad_pose"), *_f32(dview=dview)]
+    if v_depths is not None:  # fixed argument list: null pose group / thermal pointers where the frame has none
+        pp, gg = _param_ptrs(params) + [None] * (9 - len(params)), _param_ptrs(grads) + [None] * (9 - len(grads))
+        _call("tn_depth_splat_project_backward", C.byref(cam), *(head or [None, None]), *pp, N, params[5].shape[1], deg, aa, _ptr(radii, I32, "radii"),
+              *_f32(v_xys=v_xys, v_conics=v_conics, v_colors=v_colors, v_log_opacity=v_lnop, v_log_opacity_thermal=v_lnop_th, v_depths=v_depths), *gg,
+              *(tail or [None, 0, None, None]))
+        return
     _call(entry("tn_splat_project_backward", pose=posed, sep=sep), C.byref(cam), *head, *_param_ptrs(params), N, params[5].shape[1], deg, aa,
           _ptr(radii, I32, "radii"), *_f32(v_xys=v_xys, v_conics=v_conics, v_colors=v_colors, v_log_opacity=v_lnop),
           *(_f32(v_log_opacity_thermal=v_lnop_th) if sep else []), *_param_ptrs(grads), *tail)
@@ -300,6 +319,14 @@ def thermal_reg(pred, ps, gt, gs, H, W, tv_mult, cross_mult, out, grad) -> None:
     """tn_thermal_reg: (tv_mult * tv, cross_mult * cc) into `out` [2] and, with `grad`, the gradient of their sum in pred."""
     ws = workspace("tn_thermal_reg_workspace_bytes", H, W, device=pred.device, what=f"bad sizes {H} x {W}", exc=ValueError)
     _call("tn_thermal_reg", _raw(pred), ps, _raw(gt), gs, H, W, float(tv_mult), float(cross_mult), _raw(ws), ws.numel(), _raw(out), _raw(grad))
+
+
+def depth_loss(depth, alpha, depth_image, H, W, depth_mult, tv_mult, out, grad) -> None:
+    """tn_depth_loss: (depth_mult * depth_loss, tv_mult * depth_tv_loss) into `out` [2] and, with `grad`, the gradient of their sum in depth;
+    `depth_image` (the sensor depth) may be None."""
+    ws = workspace("tn_depth_loss_workspace_bytes", H, W, device=depth.device, what=f"bad sizes {H} x {W}", exc=ValueError)
+    _call("tn_depth_loss", *_f32(depth=depth, accumulation=alpha, depth_image=depth_image), H, W, float(depth_mult), float(tv_mult), _raw(ws), ws.numel(),
+          _raw(out), _raw(grad))
 
 
 def _image_code(t) -> int:

@@ -5,7 +5,8 @@ truth -- uint8 or float -- is shrunk by one HIP bilinear resize with torchvision
 ThermalNeRF's two cross-spectrum regularisers (model_components/losses.py:602-651, used at models/thermal_nerfacto.py:346-354) are there for RGB
 frames: `tv_pixel_loss` -- the 2 x 2-patch total variation of the thermal render at the RGB camera -- and `cross_channel_loss` -- that render's pixel
 differences against those of the RGB ground truth's grey value -- over every stride-1 window of the frame, in one fused HIP call
-(`thermal_regularizers`: tn_thermal_reg), so the thermal channel gets a gradient from RGB frames too.  Distorted frames are resampled once into
+(`thermal_regularizers`: tn_thermal_reg), so the thermal channel gets a gradient from RGB frames too.  Two geometric priors act on the depth render
+where it is covered (`depth_losses`: tn_depth_loss): the L1 distance to a sensor depth and the 2 x 2 total variation of the depth.  Distorted frames are resampled once into
 pinhole frames: `undistort_image` is the frame `splat_camera.undistorted_camera` sees (tn_image_undistort, uint8 or fp32 in and out);
 splat_datamanager.ThermalFullImageDatamanager caches the undistorted frames on the device and serves (camera, batch).
 """
@@ -197,6 +198,72 @@ def thermal_regularizers(pred_thermal: Tensor, gt_rgb: Tensor, tv_mult: float, c
     if torch.is_grad_enabled() and isinstance(pred_thermal, Tensor) and pred_thermal.requires_grad:
         return _ThermalRegularizers.apply(pred_thermal, gt_rgb, float(tv_mult), float(cross_mult))
     out, _ = _thermal_reg_call(pred_thermal, gt_rgb, tv_mult, cross_mult, False)
+    return out[0], out[1]
+
+
+class _DepthLosses(torch.autograd.Function):
+    """tn_depth_loss as an autograd node, built as _ThermalRegularizers is: forward computes (depth_mult * depth_loss, tv_mult * depth_tv_loss) and
+    the gradient of their sum in depth in one call and saves it; backward scales it, or -- for upstream gradients that differ between the two
+    outputs -- asks for each term's own gradient with the other's multiplier 0.  Accumulation and sensor depth get no gradient."""
+
+    @staticmethod
+    def forward(ctx, depth, accumulation, depth_image, depth_mult, tv_mult):
+        out, grad = _depth_loss_call(depth, accumulation, depth_image, depth_mult, tv_mult, True)
+        ctx.save_for_backward(grad, depth, accumulation, *([depth_image] if depth_image is not None else []))
+        ctx.mults = (depth_mult, tv_mult)
+        ctx.set_materialize_grads(False)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_d, g_tv):
+        grad, depth, accumulation, *sensor = ctx.saved_tensors
+        sensor = sensor[0] if sensor else None
+        depth_mult, tv_mult = ctx.mults
+        if depth_mult == 0 or tv_mult == 0 or sensor is None:  # the saved gradient is the one live term's
+            g = g_tv if (depth_mult == 0 or sensor is None) else g_d
+            return (None if g is None else grad * g), None, None, None, None
+        if g_d is not None and g_tv is not None and g_d.shape == g_tv.shape and g_d.data_ptr() == g_tv.data_ptr():  # one upstream gradient
+            return grad * g_d, None, None, None, None
+        total = None
+        for g, mults in ((g_d, (depth_mult, 0.0)), (g_tv, (0.0, tv_mult))):
+            if g is not None:
+                term = _depth_loss_call(depth, accumulation, sensor, *mults, True)[1] * g
+                total = term if total is None else total + term
+        return total, None, None, None, None
+
+
+def _depth_loss_call(depth: Tensor, accumulation: Tensor, depth_image: Optional[Tensor], depth_mult: float, tv_mult: float,
+                     want_grad: bool) -> Tuple[Tensor, Optional[Tensor]]:
+    maps = [("depth", depth), ("accumulation", accumulation)] + ([("depth_image", depth_image)] if depth_image is not None else [])
+    for name, t in maps:
+        if not isinstance(t, Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise ValueError(f"depth_losses: {name} must be an fp32 HIP tensor (the splat path has no CPU fallback)")
+        if t.dim() != 3 or t.shape[2] != 1 or t.shape != depth.shape:
+            raise ValueError(f"depth_losses takes depth, accumulation and depth_image [H,W,1] of one size, got {name} {tuple(t.shape)} for depth {tuple(depth.shape)}")
+    if depth_mult < 0 or tv_mult < 0:
+        raise ValueError(f"depth_losses: multipliers {depth_mult} / {tv_mult}, a loss multiplier cannot be negative")
+    H, W, _ = depth.shape
+    if not all(2 <= v <= MAX_IMAGE_SIDE for v in (H, W)):
+        raise ValueError(f"depth_losses: {H} x {W}, every side must be in 2..{MAX_IMAGE_SIDE} (the windows are 2 x 2)")
+    dev = depth.device
+    out = torch.empty(2, device=dev)
+    grad = torch.empty((H, W, 1), device=dev) if want_grad else None
+    splat_calls.depth_loss(depth.detach().contiguous(), accumulation.detach().contiguous(), None if depth_image is None else depth_image.detach().contiguous(),
+                           H, W, depth_mult, tv_mult, out, grad)
+    return out, grad
+
+
+def depth_losses(depth: Tensor, accumulation: Tensor, depth_image: Optional[Tensor], depth_mult: float, tv_mult: float) -> Tuple[Tensor, Tensor]:
+    """Two geometric priors on a depth render [H,W,1] with its accumulation [H,W,1] (H and W >= 2), on the device and without a host synchronisation,
+    in one fused call (tn_depth_loss): (depth_mult * depth_loss, tv_mult * depth_tv_loss).  depth_loss = mean |depth - depth_image| over the pixels
+    with accumulation > 0 and a finite, positive depth_image [H,W,1] (a sensor depth in scene units; None, or no such pixel: 0).  depth_tv_loss =
+    0.25 * mean of the four absolute differences of every stride-1 2 x 2 window of the depth whose four pixels all have accumulation > 0 (no such
+    window: 0) -- uncovered pixels hold the frame's fill value, which would otherwise put an edge on every silhouette.  A multiplier of 0 gives
+    exactly 0 and skips that term.  Both entries are differentiable in `depth` when gradients are on (sign(0) = 0); the accumulation only selects, and
+    like depth_image gets no gradient."""
+    if torch.is_grad_enabled() and isinstance(depth, Tensor) and depth.requires_grad:
+        return _DepthLosses.apply(depth, accumulation, depth_image, float(depth_mult), float(tv_mult))
+    out, _ = _depth_loss_call(depth, accumulation, depth_image, depth_mult, tv_mult, False)
     return out[0], out[1]
 
 

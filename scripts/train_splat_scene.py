@@ -14,7 +14,10 @@ one Gaussian per point with kNN scales) instead of from --gaussians random ones.
 schedule: 1 / 2^N of each frame's size at first, doubled every --resolution-schedule steps); the JSON line lists every stage with its factor, its
 steps and its time per iteration, and the val split is scored in eval mode, at full size.  --tv-pixel-loss-mult / --cross-channel-loss-mult (default 0:
 off) switch on ThermalNeRF's regularisers of the thermal render at the RGB cameras (get_loss_dict's tv_pixel_loss / cross_channel_loss: tn_thermal_reg;
-the NeRF path runs both at 1e-6); the backward goes over the sum of the loss dict.  --crop-pos / --crop-rpy / --crop-scale (three floats each, all
+the NeRF path runs both at 1e-6); the backward goes over the sum of the loss dict.  --differentiable-depth lets the training render's depth carry
+gradients (classic mode), and --depth-tv-loss-mult / --depth-loss-mult (default 0: off; either switches the flag on) add get_loss_dict's depth_tv_loss
+/ depth_loss over the covered pixels (tn_depth_loss); depth_loss needs a depth_image in the batch, which no dataparser here reads yet, and is 0
+without one.  --crop-pos / --crop-rpy / --crop-scale (three floats each, all
 three or none: centre, roll pitch yaw in radians, extents) give the eval render an oriented crop box (OrientedBox.from_params): after the val
 split is scored on the whole scene, its frames are rendered again through get_outputs_for_camera(camera, box) and written as PNGs to --crop-out
 (rgb_*.png, thermal_*.png; in separate mode with --removal-min-opacity-diff also removal_*.png and removal_thermal_*.png), and the line reports
@@ -102,6 +105,9 @@ def main():
     ap.add_argument("--num-downscales", type=int, default=0, help="train at 1 / 2^N resolution at first (0: full size throughout)")
     ap.add_argument("--resolution-schedule", type=int, default=250, help="steps after which the training resolution doubles")
     ap.add_argument("--tv-pixel-loss-mult", type=float, default=0.0, help="weight of the thermal render's 2x2 total variation on RGB frames (0: off)")
+    ap.add_argument("--differentiable-depth", action="store_true", help="let the training render's depth carry gradients (classic mode)")
+    ap.add_argument("--depth-loss-mult", type=float, default=0.0, help="weight of the L1 distance of the depth render to the batch's depth_image (0: off)")
+    ap.add_argument("--depth-tv-loss-mult", type=float, default=0.0, help="weight of the depth render's 2x2 total variation over its covered pixels (0: off)")
     ap.add_argument("--cross-channel-loss-mult", type=float, default=0.0,
                     help="weight of the thermal render's pixel differences against the RGB ground truth's on RGB frames (0: off)")
     ap.add_argument("--thermal-opacity-mode", default="shared", choices=("shared", "separate"),
@@ -153,6 +159,8 @@ def main():
     cfg = ThermalSplatfactoModelConfig(num_random=args.gaussians, random_scale=args.init_extent, ssim_lambda=args.ssim_lambda,
                                        background_color=args.background, num_downscales=args.num_downscales,
                                        resolution_schedule=args.resolution_schedule, tv_pixel_loss_mult=args.tv_pixel_loss_mult,
+                                       differentiable_depth=args.differentiable_depth or args.depth_loss_mult > 0 or args.depth_tv_loss_mult > 0,
+                                       depth_loss_mult=args.depth_loss_mult, depth_tv_loss_mult=args.depth_tv_loss_mult,
                                        cross_channel_loss_mult=args.cross_channel_loss_mult, thermal_opacity_mode=args.thermal_opacity_mode,
                                        opacity_loss_mult=args.opacity_loss_mult, removal_min_opacity_diff=args.removal_min_opacity_diff,
                                        camera_optimizer=CameraOptimizerConfig(mode=args.camera_optimizer),
@@ -225,6 +233,7 @@ def main():
                       "initial_gaussians": initial, "seed_points": args.seed_points, "final_gaussians": model.num_points, "train_seconds": train_s,
                       "ms_per_iteration": 1e3 * train_s / max(args.steps, 1), "num_downscales": args.num_downscales,
                       "resolution_schedule": args.resolution_schedule, "tv_pixel_loss_mult": args.tv_pixel_loss_mult,
+                      "differentiable_depth": cfg.differentiable_depth, "depth_loss_mult": args.depth_loss_mult, "depth_tv_loss_mult": args.depth_tv_loss_mult,
                       "cross_channel_loss_mult": args.cross_channel_loss_mult, "undistort": not args.no_undistort, "thermal_opacity_mode": args.thermal_opacity_mode,
                       "opacity_loss_mult": args.opacity_loss_mult, "camera_optimizer": args.camera_optimizer,
                       "camera_optimizer_thermal": args.camera_optimizer_thermal, "strategy": args.strategy, "max_gs_num": args.max_gs_num,
