@@ -1100,6 +1100,50 @@ TN_API int tn_splat_mcmc_noise(float* means, const float* log_scales, const floa
 /* the same with o = max(sigmoid(opacities), sigmoid(opacities_thermal)): a Gaussian visible in either spectrum is left in place */
 TN_API int tn_splat_mcmc_noise_sep(float* means, const float* log_scales, const float* quats, const float* opacities, const float* opacities_thermal,
                                    const float* randn, int64_t num_gaussians, float scaler, tn_stream_t stream);
+
+/* ---- point-cloud export of the NeRF (ns-export pointcloud: nerfstudio/scripts/exporter.py:90-186, nerfstudio/exporter/exporter_utils.py:83-260,
+ * generate_point_cloud): rendered rays are back-projected by their depth, the opaque ones inside a box are kept, statistical outliers are
+ * removed.  Every point carries the rendered colour and the rendered thermal value.  Both entry points run on the caller's stream without a host
+ * synchronisation and use no float atomics: the same inputs give the same bytes.  tests/cloud_functional.py restates both.
+ *
+ * tn_cloud_append: one batch of num_rays rendered rays.  origins, directions [num_rays,3], depth, accumulation [num_rays] fp32, contiguous;
+ * rgb: channels 0..2 of ray r at rgb[r * rgb_stride], thermal: the value of ray r at thermal[r * thermal_stride] (strides in ELEMENTS, so both can
+ * be read in place from one [num_rays,4] rgbt buffer: rgb = buffer, thermal = buffer + 3, both strides 4).  Ray r is kept iff
+ *   accumulation[r] > alpha_thresh (strict), and
+ *   p = o + d * depth[r] is finite in all three coordinates (fp32, the product and the sum each rounded on its own), and
+ *   box is null, or p is inside it exactly as tn_splat_crop_mask tests it (strict on both sides; a NaN keeps nothing).
+ * count: DEVICE int64[1], the rows the output holds already (read as clamped to 0..cap).  The kept rays' p, rgb and thermal are written in ray
+ * order to rows count, count + 1, ... of out_xyz [cap,3], out_rgb [cap,3], out_thermal [cap]; rows at or beyond cap are dropped, nothing is
+ * written there; afterwards count = min(cap, count + kept).  box is a HOST pointer, read before the launch.  The outputs must not overlap the
+ * inputs.  num_rays == 0 is TN_OK and touches nothing.  Refused with TN_EINVAL before any launch: num_rays negative or at or above 2^31, a negative cap,
+ * null pointers (box may be null, and so may the three outputs when cap is 0), an rgb stride below 3 or a thermal stride below 1, a short workspace.
+ *
+ * scratch of tn_cloud_append (a count and an offset per block of 256 rays); -1 for num_rays outside [0, 2^31) */
+TN_API int64_t tn_cloud_append_workspace_bytes(int64_t num_rays);
+TN_API int tn_cloud_append(const float* origins, const float* directions, const float* depth, const float* accumulation, const float* rgb,
+                           int64_t rgb_stride, const float* thermal, int64_t thermal_stride, int64_t num_rays, float alpha_thresh,
+                           const TnSplatCrop* box, float* out_xyz, float* out_rgb, float* out_thermal, int64_t cap, int64_t* count, void* workspace,
+                           int64_t workspace_bytes, tn_stream_t stream);
+/* tn_cloud_remove_outliers: Open3D's remove_statistical_outlier(nb_neighbors, std_ratio) (the reference calls it with nb_neighbors = 20) over
+ * xyz [n,3], rgb [n,3], thermal [n] fp32.  The rule:
+ *   mean_i = (the sum of the distances from point i to its nb_neighbors - 1 nearest OTHER points, ascending, accumulated in double) / nb_neighbors
+ *            -- Open3D's search returns the query itself at distance 0 as the first of the nb_neighbors; the distances are tn_knn's:
+ *            d2 = (dx*dx + dy*dy) + dz*dz in fp32, sqrtf(d2), ties to the smaller index, exact;
+ *   over the V points with mean_i > 0, in double: m = their mean, s = sqrt(sum (mean_i - m)^2 / (V - 1)), thr = m + std_ratio * s
+ *            (V == 0 makes m, and V == 1 makes s, 0 / 0: the NaN keeps nothing);
+ *   point i is kept iff mean_i > 0 && mean_i < thr.
+ * The kept points' rows go to out_xyz / out_rgb / out_thermal (room for n rows each; they must not overlap the inputs) compacted in their original
+ * order, their number to out_count (DEVICE int64[1]), stats = [m, s, thr] (DEVICE double[3]); unless null, mean [n] double receives every mean_i
+ * and keep [n] uint8 the mask.  The sums are folded in a fixed order.  The neighbour search is the wide form of tn_knn's query on the same tree
+ * (lists of 7, 15, 19 or 31 in registers); it writes mean_i only, no [n,k] table.  Refused with TN_EINVAL before any launch: nb_neighbors outside
+ * 2..32, n < nb_neighbors, n at or above 2^31, null pointers (mean and keep may be null), a short workspace.
+ *
+ * scratch of tn_cloud_remove_outliers (tn_knn's tree, the means, the partial sums, a count and an offset per block); -1 on sizes the call refuses or
+ * when the sort's scratch cannot be sized (no device) */
+TN_API int64_t tn_cloud_remove_outliers_workspace_bytes(int64_t n, int32_t nb_neighbors);
+TN_API int tn_cloud_remove_outliers(const float* xyz, const float* rgb, const float* thermal, int64_t n, int32_t nb_neighbors, double std_ratio,
+                                    float* out_xyz, float* out_rgb, float* out_thermal, int64_t* out_count, double* stats, double* mean, uint8_t* keep,
+                                    void* workspace, int64_t workspace_bytes, tn_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,11 @@ SIGNATURES = {
     "tn_splat_mcmc_relocate_sep": (C.c_int, [_i64, _i32, _p, _p, _i64, _f, _p, _p, _p, _p, _i64, _p]),
     "tn_splat_mcmc_noise": (C.c_int, [_p] * 5 + [_i64, _f, _p]),
     "tn_splat_mcmc_noise_sep": (C.c_int, [_p] * 6 + [_i64, _f, _p]),
+    # point-cloud export of the NeRF: stable append of a rendered batch, statistical outlier removal
+    "tn_cloud_append_workspace_bytes": (_i64, [_i64]),
+    "tn_cloud_append": (C.c_int, [_p] * 5 + [_i64, _p, _i64, _i64, _f, C.POINTER(TnSplatCrop), _p, _p, _p, _i64, _p, _p, _i64, _p]),
+    "tn_cloud_remove_outliers_workspace_bytes": (_i64, [_i64, _i32]),
+    "tn_cloud_remove_outliers": (C.c_int, [_p, _p, _p, _i64, _i32, C.c_double] + [_p] * 8 + [_i64, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

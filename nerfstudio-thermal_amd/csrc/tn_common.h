@@ -76,7 +76,41 @@ int tn_field_fwd_ex(const TnField* field, const float* origins, const float* dir
                     int32_t training, void* workspace, int64_t workspace_bytes, float* density, float* rgb, float* density_pre, int pack_first, void* zero,
                     int64_t zero_bytes, tn_stream_t stream);
 
+// The neighbour means of Open3D's statistical outlier rule over the Morton tree of tn_knn (tn_splat_init.hip): mean[i] = the sum of the distances
+// from point i to its nb_neighbors - 1 nearest OTHER points (tn_knn's d2, sqrtf and tie rule), ascending, accumulated in double, divided by
+// nb_neighbors (Open3D's search counts the query itself, at distance 0, among the nb_neighbors).  points [n,3] fp32 -> mean [n] double, no
+// [n,k] table.  The caller has checked 2 <= nb_neighbors <= 32 and nb_neighbors <= n <= INT32_MAX; the scratch is the tree's.
+int64_t tn_knn_tree_workspace_bytes(int64_t n);  // -1 when rocprim cannot size its sort
+int tn_knn_neighbor_means(const float* points, int64_t n, int32_t nb_neighbors, double* mean, void* workspace, int64_t workspace_bytes,
+                          hipStream_t stream);
+
 // ---------------------------------------------------------------- device side
+// The crop box of the splat eval render and of the point-cloud export (OrientedBox: splatfacto.py:690-698, scene_box.py:82-114): m = rows of the
+// 3x4 world -> box matrix inverse([R|T]), h = S / 2.  A point p is inside iff |q_i| < h_i on all three axes (strict on both sides; h_i <= 0 or a
+// NaN keeps nothing) with
+//   q_i = ((m[4i] * p.x + m[4i+1] * p.y) + m[4i+2] * p.z) + m[4i+3]
+// in fp32, every product and every sum rounded to nearest on its own (no fused multiply-add), in exactly this order: the float64 restatement
+// of the tests names its near-boundary band from the rounding of these seven operations.
+struct SplatCropK {
+  float m[12];
+  float h[3];
+};
+__device__ __forceinline__ bool splat_in_crop(const SplatCropK& c, float x, float y, float z) {
+  bool in = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float q = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.m[4 * a], x), __fmul_rn(c.m[4 * a + 1], y)), __fmul_rn(c.m[4 * a + 2], z)), c.m[4 * a + 3]);
+    in = in && fabsf(q) < c.h[a];
+  }
+  return in;
+}
+static inline SplatCropK make_cropk(const TnSplatCrop* crop) {
+  SplatCropK c;
+  for (int i = 0; i < 12; ++i) c.m[i] = crop->world_to_box[i];
+  for (int i = 0; i < 3; ++i) c.h[i] = crop->half_extent[i];
+  return c;
+}
+
 #define TN_PRIME_Y 2654435761u
 #define TN_PRIME_Z 805459861u
 

@@ -184,24 +184,7 @@ __device__ __forceinline__ void splat_pose_load(SplatCamK& cam, const float* __r
   for (int i = 0; i < 3; ++i) cam.pos[i] = rec[28 + i];
 }
 
-// The crop box of the eval render (OrientedBox: splatfacto.py:690-698, scene_box.py:82-114): m = rows of the 3x4 world -> box matrix
-// inverse([R|T]), h = S / 2.  A point p is inside iff |q_i| < h_i on all three axes (strict on both sides; h_i <= 0 or a NaN keeps nothing) with
-//   q_i = ((m[4i] * p.x + m[4i+1] * p.y) + m[4i+2] * p.z) + m[4i+3]
-// in fp32, every product and every sum rounded to nearest on its own (no fused multiply-add), in exactly this order: the float64 restatement
-// of the tests names its near-boundary band from the rounding of these seven operations.
-struct SplatCropK {
-  float m[12];
-  float h[3];
-};
-__device__ __forceinline__ bool splat_in_crop(const SplatCropK& c, float x, float y, float z) {
-  bool in = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float q = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.m[4 * a], x), __fmul_rn(c.m[4 * a + 1], y)), __fmul_rn(c.m[4 * a + 2], z)), c.m[4 * a + 3]);
-    in = in && fabsf(q) < c.h[a];
-  }
-  return in;
-}
+// (the crop box of the eval render -- SplatCropK, splat_in_crop, make_cropk -- lives in tn_common.h: the point-cloud export tests its points with it too)
 
 // SEP: the thermal channel has an opacity of its own (opac_th_logit, else unused): its log2 goes into the record's two spare floats, and the box
 // around {alpha >= 1/255} comes from the larger of the two opacities, so neither chain of the rasteriser loses a contributor.
@@ -1489,13 +1472,6 @@ static SplatCamK make_camk(const TnSplatCamera* cam) {
   k.tbx = (cam->width + SPLAT_BLOCK - 1) / SPLAT_BLOCK;
   k.tby = (cam->height + SPLAT_BLOCK - 1) / SPLAT_BLOCK;
   return k;
-}
-
-static SplatCropK make_cropk(const TnSplatCrop* crop) {
-  SplatCropK c;
-  for (int i = 0; i < 12; ++i) c.m[i] = crop->world_to_box[i];
-  for (int i = 0; i < 3; ++i) c.h[i] = crop->half_extent[i];
-  return c;
 }
 
 // The _sep entry points (separate thermal opacity) share their implementation with the entry points they extend: `sep` picks the SEP

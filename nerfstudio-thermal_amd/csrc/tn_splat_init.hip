@@ -16,6 +16,9 @@
 //   k_knn_query<K>    one thread per sorted point: the k-best list (registers, insertion unrolled for the compile-time K) is seeded from the
 //                     point's own leaf, then a stackless near-child-first traversal (one trail bit per level) visits every node that can
 //                     still hold a better (d2, j); the row is written at the point's original index.
+//   k_knn_query_mean<K>  the same search (knn_search) with a wide list, K in {7, 15, 19, 31}, for the statistical outlier rule of the point-cloud
+//                     export (tn_knn_neighbor_means, called by tn_cloud_remove_outliers): it writes one double per point, no [n,k] table.
+// knn_build_tree builds the tree for both; tn_knn itself stays at k = 1..8.
 //
 // Pruning is exact: the box distance uses the point formula on the box's nearest coordinate, and correctly rounded subtraction, squaring
 // and addition are monotone, so it is a lower bound of every computed d2 inside the box.  A node is skipped when that bound exceeds the
@@ -195,14 +198,10 @@ struct KBest {
   }
 };
 
+// the exact K best (d2, j) over j != the point at sorted position s, into `best`
 template <int K>
-__global__ void __launch_bounds__(KB) k_knn_query(const float4* __restrict__ sp, int64_t n, const KNode* __restrict__ nodes, int64_t num_padded,
-                                                  float* __restrict__ out_dist, int32_t* __restrict__ out_index) {
-  const int64_t s = (int64_t)blockIdx.x * KB + threadIdx.x;
-  if (s >= n) return;
-  const float4 q = sp[s];
-  const int32_t self = __float_as_int(q.w);
-  KBest<K> best;
+__device__ inline void knn_search(const float4* __restrict__ sp, int64_t n, const KNode* __restrict__ nodes, int64_t num_padded, int64_t s, const float4 q,
+                                  KBest<K>& best) {
   best.init();
   const int64_t own = s / KL;
   {
@@ -243,6 +242,17 @@ __global__ void __launch_bounds__(KB) k_knn_query(const float4* __restrict__ sp,
     node ^= 1;
     trail |= 1u << depth;
   }
+}
+
+template <int K>
+__global__ void __launch_bounds__(KB) k_knn_query(const float4* __restrict__ sp, int64_t n, const KNode* __restrict__ nodes, int64_t num_padded,
+                                                  float* __restrict__ out_dist, int32_t* __restrict__ out_index) {
+  const int64_t s = (int64_t)blockIdx.x * KB + threadIdx.x;
+  if (s >= n) return;
+  const float4 q = sp[s];
+  const int32_t self = __float_as_int(q.w);
+  KBest<K> best;
+  knn_search<K>(sp, n, nodes, num_padded, s, q, best);
   const int64_t row = (int64_t)self * K;
 #pragma unroll
   for (int m = 0; m < K; ++m) out_dist[row + m] = sqrtf(best.d[m]);
@@ -250,6 +260,28 @@ __global__ void __launch_bounds__(KB) k_knn_query(const float4* __restrict__ sp,
 #pragma unroll
     for (int m = 0; m < K; ++m) out_index[row + m] = best.j[m];
   }
+}
+
+// The wide query of the statistical outlier rule (tn_cloud_remove_outliers): the exact K >= used nearest, of which the first `used` -- they are
+// the exact `used` nearest -- are summed as distances, ascending, in double, and divided by `divisor`; nothing but mean[self] is written.
+// Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; the list is 2 K registers held at constant indices, and the unrolled insertion
+// keeps old and new values of a slot alive side by side):
+//   K = 7: 58 VGPRs, 8 waves / SIMD;  K = 15: 91, 5;  K = 19: 112, 4;  K = 31: 172, 2 -- no scratch and no spills in any of them.
+// The block size stays KB = 256 (4 waves): at K = 19, the reference's nb_neighbors = 20, a CU holds 16 waves = 4 whole blocks, and at K = 31 8 waves
+// = 2 whole blocks, so no register file is left partly empty by the block granularity; a smaller block would only add launches of the same waves.
+template <int K>
+__global__ void __launch_bounds__(KB) k_knn_query_mean(const float4* __restrict__ sp, int64_t n, const KNode* __restrict__ nodes, int64_t num_padded,
+                                                       int used, double divisor, double* __restrict__ mean) {
+  const int64_t s = (int64_t)blockIdx.x * KB + threadIdx.x;
+  if (s >= n) return;
+  const float4 q = sp[s];
+  KBest<K> best;
+  knn_search<K>(sp, n, nodes, num_padded, s, q, best);
+  double sum = 0.0;
+#pragma unroll
+  for (int m = 0; m < K; ++m)
+    if (m < used) sum += (double)sqrtf(best.d[m]);
+  mean[__float_as_int(q.w)] = sum / divisor;
 }
 
 constexpr int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
@@ -285,6 +317,55 @@ KnnLayout knn_layout(int64_t n) {
   return L;
 }
 
+struct KnnTree {
+  KBox *box, *partial;
+  uint64_t *codes, *codes_sorted;
+  int32_t* order;
+  float4* sp;
+  KNode* nodes;
+  void* tmp;
+};
+
+KnnTree knn_tree_views(void* workspace, const KnnLayout& L) {
+  char* ws = static_cast<char*>(workspace);
+  return KnnTree{reinterpret_cast<KBox*>(ws + L.box),       reinterpret_cast<KBox*>(ws + L.partial),  reinterpret_cast<uint64_t*>(ws + L.codes),
+                 reinterpret_cast<uint64_t*>(ws + L.codes_sorted), reinterpret_cast<int32_t*>(ws + L.order), reinterpret_cast<float4*>(ws + L.points),
+                 reinterpret_cast<KNode*>(ws + L.nodes),    ws + L.tmp};
+}
+
+// box, Morton codes, sort, sorted points, leaves, levels: the tree both tn_knn and tn_knn_neighbor_means query (n >= 1, a workspace of L.total bytes)
+int knn_build_tree(const float* points, int64_t n, const KnnLayout& L, const KnnTree& T, hipStream_t st) {
+  const int nbox = (int)std::min<int64_t>(tn_cdiv(n, KB * 8), KBOX_BLOCKS);
+  hipLaunchKernelGGL(k_knn_box_partial, dim3(nbox), dim3(KB), 0, st, points, n, T.partial);
+  TN_CHECK_LAUNCH("tn_knn(box_partial)");
+  hipLaunchKernelGGL(k_knn_box_final, dim3(1), dim3(KB), 0, st, T.partial, nbox, T.box);
+  TN_CHECK_LAUNCH("tn_knn(box_final)");
+  const unsigned gn = (unsigned)tn_cdiv(n, KB);
+  hipLaunchKernelGGL(k_knn_morton, dim3(gn), dim3(KB), 0, st, points, n, T.box, T.codes);
+  TN_CHECK_LAUNCH("tn_knn(morton)");
+  size_t tb = (size_t)L.tmp_bytes;
+  if (rocprim::radix_sort_pairs(T.tmp, tb, T.codes, T.codes_sorted, rocprim::counting_iterator<int32_t>(0), T.order, (size_t)n, 0, 63, st) != hipSuccess) {
+    tn_set_error("tn_knn: rocprim::radix_sort_pairs failed");
+    return TN_ELAUNCH;
+  }
+  hipLaunchKernelGGL(k_knn_gather, dim3(gn), dim3(KB), 0, st, points, n, T.order, T.sp);
+  TN_CHECK_LAUNCH("tn_knn(gather)");
+  const int64_t P = padded_leaves(n);
+  hipLaunchKernelGGL(k_knn_leaves, dim3((unsigned)tn_cdiv(P, KB)), dim3(KB), 0, st, T.sp, n, P, T.nodes);
+  TN_CHECK_LAUNCH("tn_knn(leaves)");
+  for (int64_t first = P >> 1; first >= 1; first >>= 1) {
+    hipLaunchKernelGGL(k_knn_level, dim3((unsigned)tn_cdiv(first, KB)), dim3(KB), 0, st, first, T.nodes);
+    TN_CHECK_LAUNCH("tn_knn(level)");
+  }
+  return TN_OK;
+}
+
+template <int K>
+void launch_query_mean(const KnnTree& T, int64_t n, int used, int32_t nb, double* mean, hipStream_t st) {
+  hipLaunchKernelGGL(k_knn_query_mean<K>, dim3((unsigned)tn_cdiv(n, KB)), dim3(KB), 0, st, (const float4*)T.sp, n, (const KNode*)T.nodes, padded_leaves(n), used,
+                     (double)nb, mean);
+}
+
 template <int K>
 void launch_query(const float4* sp, int64_t n, const KNode* nodes, int64_t P, float* out_dist, int32_t* out_index, hipStream_t st) {
   hipLaunchKernelGGL(k_knn_query<K>, dim3((unsigned)tn_cdiv(n, KB)), dim3(KB), 0, st, sp, n, nodes, P, out_dist, out_index);
@@ -312,38 +393,12 @@ extern "C" int tn_knn(const float* points, int64_t n, int32_t k, float* out_dist
     return TN_ELAUNCH;
   }
   TN_REQUIRE(workspace_bytes >= L.total, "tn_knn: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)L.total);
-  char* ws = static_cast<char*>(workspace);
-  KBox* box = reinterpret_cast<KBox*>(ws + L.box);
-  KBox* partial = reinterpret_cast<KBox*>(ws + L.partial);
-  uint64_t* codes = reinterpret_cast<uint64_t*>(ws + L.codes);
-  uint64_t* codes_sorted = reinterpret_cast<uint64_t*>(ws + L.codes_sorted);
-  int32_t* order = reinterpret_cast<int32_t*>(ws + L.order);
-  float4* sp = reinterpret_cast<float4*>(ws + L.points);
-  KNode* nodes = reinterpret_cast<KNode*>(ws + L.nodes);
-  void* tmp = ws + L.tmp;
   hipStream_t st = tn_s(stream);
-  const int nbox = (int)std::min<int64_t>(tn_cdiv(n, KB * 8), KBOX_BLOCKS);
-  hipLaunchKernelGGL(k_knn_box_partial, dim3(nbox), dim3(KB), 0, st, points, n, partial);
-  TN_CHECK_LAUNCH("tn_knn(box_partial)");
-  hipLaunchKernelGGL(k_knn_box_final, dim3(1), dim3(KB), 0, st, partial, nbox, box);
-  TN_CHECK_LAUNCH("tn_knn(box_final)");
-  const unsigned gn = (unsigned)tn_cdiv(n, KB);
-  hipLaunchKernelGGL(k_knn_morton, dim3(gn), dim3(KB), 0, st, points, n, box, codes);
-  TN_CHECK_LAUNCH("tn_knn(morton)");
-  size_t tb = (size_t)L.tmp_bytes;
-  if (rocprim::radix_sort_pairs(tmp, tb, codes, codes_sorted, rocprim::counting_iterator<int32_t>(0), order, (size_t)n, 0, 63, st) != hipSuccess) {
-    tn_set_error("tn_knn: rocprim::radix_sort_pairs failed");
-    return TN_ELAUNCH;
-  }
-  hipLaunchKernelGGL(k_knn_gather, dim3(gn), dim3(KB), 0, st, points, n, order, sp);
-  TN_CHECK_LAUNCH("tn_knn(gather)");
+  const KnnTree T = knn_tree_views(workspace, L);
+  if (const int rc = knn_build_tree(points, n, L, T, st)) return rc;
+  const float4* sp = T.sp;
+  const KNode* nodes = T.nodes;
   const int64_t P = padded_leaves(n);
-  hipLaunchKernelGGL(k_knn_leaves, dim3((unsigned)tn_cdiv(P, KB)), dim3(KB), 0, st, sp, n, P, nodes);
-  TN_CHECK_LAUNCH("tn_knn(leaves)");
-  for (int64_t first = P >> 1; first >= 1; first >>= 1) {
-    hipLaunchKernelGGL(k_knn_level, dim3((unsigned)tn_cdiv(first, KB)), dim3(KB), 0, st, first, nodes);
-    TN_CHECK_LAUNCH("tn_knn(level)");
-  }
   switch (k) {
     case 1: launch_query<1>(sp, n, nodes, P, out_dist, out_index, st); break;
     case 2: launch_query<2>(sp, n, nodes, P, out_dist, out_index, st); break;
@@ -355,5 +410,30 @@ extern "C" int tn_knn(const float* points, int64_t n, int32_t k, float* out_dist
     default: launch_query<8>(sp, n, nodes, P, out_dist, out_index, st); break;
   }
   TN_CHECK_LAUNCH("tn_knn(query)");
+  return TN_OK;
+}
+
+// ---- internal (tn_common.h): the neighbour means of the statistical outlier rule, for tn_cloud_remove_outliers (tn_cloud.hip)
+int64_t tn_knn_tree_workspace_bytes(int64_t n) {
+  if (n < 1 || n > INT32_MAX) return -1;
+  const KnnLayout L = knn_layout(n);
+  return L.ok ? L.total : -1;
+}
+
+int tn_knn_neighbor_means(const float* points, int64_t n, int32_t nb_neighbors, double* mean, void* workspace, int64_t workspace_bytes, hipStream_t st) {
+  const KnnLayout L = knn_layout(n);
+  if (!L.ok) {
+    tn_set_error("tn_cloud_remove_outliers: rocprim could not size its scratch for %lld points", (long long)n);
+    return TN_ELAUNCH;
+  }
+  TN_REQUIRE(workspace_bytes >= L.total, "tn_cloud_remove_outliers: tree workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)L.total);
+  const KnnTree T = knn_tree_views(workspace, L);
+  if (const int rc = knn_build_tree(points, n, L, T, st)) return rc;
+  const int used = nb_neighbors - 1;  // 1..31; n - 1 >= used other points exist, so the first `used` slots of a longer list are all real
+  if (used <= 7) launch_query_mean<7>(T, n, used, nb_neighbors, mean, st);
+  else if (used <= 15) launch_query_mean<15>(T, n, used, nb_neighbors, mean, st);
+  else if (used <= 19) launch_query_mean<19>(T, n, used, nb_neighbors, mean, st);
+  else launch_query_mean<31>(T, n, used, nb_neighbors, mean, st);
+  TN_CHECK_LAUNCH("tn_cloud_remove_outliers(query)");
   return TN_OK;
 }

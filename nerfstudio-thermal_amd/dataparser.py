@@ -219,6 +219,26 @@ def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray]:
     nerfstudio_dataparser.py:461 computes them; clipped to 0..255 first).  Other vertex properties and the elements after `vertex` are
     ignored; fixed-size elements before it are skipped.  ValueError: big-endian or unknown formats, a missing x, y or z, a list property at or
     before the vertices, a truncated body."""
+    xyz, rgb, _ = _read_ply_vertices(path)
+    return xyz, rgb
+
+
+def read_ply_thermal(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+    """read_ply plus the vertices' `thermal` property -> (xyz, rgb, thermal [M,1] uint8, or None when the file has no such property): the rendered
+    temperature a NeRF point cloud carries (cloud.py).  uchar as stored; float / double as the colours are read, (t * 255).astype(uint8) after
+    clipping to 0..255."""
+    return _read_ply_vertices(path)
+
+
+def _ply_u8(path: str, values: np.ndarray, what: str) -> np.ndarray:
+    if values.dtype == np.uint8:
+        return values.copy()
+    if values.dtype.kind == "f":
+        return np.clip(values.astype(np.float64) * 255, 0, 255).astype(np.uint8)
+    raise ValueError(f"{path}: {what} of type {values.dtype} (uchar, float or double are read)")
+
+
+def _read_ply_vertices(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
     with open(path, "rb") as f:
         data = f.read()
     if not data.startswith(b"ply"):
@@ -279,19 +299,16 @@ def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray]:
         arr = np.frombuffer(data, dtype=dt, count=count, offset=off)
         cols = {p: arr[p] for p in pnames}
     xyz = np.stack([cols[a].astype(np.float64) for a in ("x", "y", "z")], -1).astype(np.float32)
+    thermal = _ply_u8(path, np.asarray(cols["thermal"]), "vertex thermal values").reshape(-1, 1) if "thermal" in pnames else None
     if not all(c in pnames for c in ("red", "green", "blue")):
-        return xyz, np.zeros((0, 3), dtype=np.uint8)
-    rgb = np.stack([cols[c] for c in ("red", "green", "blue")], -1)
-    if rgb.dtype == np.uint8:
-        return xyz, rgb.copy()
-    if rgb.dtype.kind == "f":
-        return xyz, np.clip(rgb.astype(np.float64) * 255, 0, 255).astype(np.uint8)
-    raise ValueError(f"{path}: vertex colours of type {rgb.dtype} (uchar, float or double are read)")
+        return xyz, np.zeros((0, 3), dtype=np.uint8), thermal
+    return xyz, _ply_u8(path, np.stack([cols[c] for c in ("red", "green", "blue")], -1), "vertex colours"), thermal
 
 
-def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, binary: bool = True) -> str:
+def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, binary: bool = True, thermal: Optional[np.ndarray] = None) -> str:
     """xyz [M,3] (float32 or float64 -> float / double properties) and optional rgb [M,3] (uint8 -> uchar, float -> float / double) as one
-    PLY vertex element, binary little-endian or ascii."""
+    PLY vertex element, binary little-endian or ascii.  With `thermal` ([M] or [M,1] uint8) one more property, `uchar thermal`, follows; without
+    it the file is byte for byte what it was before the property existed."""
     xyz = np.asarray(xyz)
     if xyz.dtype not in (np.float32, np.float64):
         xyz = xyz.astype(np.float32)
@@ -302,6 +319,11 @@ def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, bina
         if rgb.dtype not in ptype:
             raise ValueError(f"write_ply: colours of type {rgb.dtype} (uint8, float32 or float64)")
         fields += [(c, rgb.dtype) for c in ("red", "green", "blue")]
+    if thermal is not None:
+        thermal = np.asarray(thermal).reshape(-1)
+        if thermal.dtype != np.uint8 or thermal.shape[0] != xyz.shape[0]:
+            raise ValueError(f"write_ply: thermal must be {xyz.shape[0]} uint8 values, got {thermal.shape[0]} of type {thermal.dtype}")
+        fields.append(("thermal", thermal.dtype))
     head = ["ply", f"format {'binary_little_endian' if binary else 'ascii'} 1.0", f"element vertex {xyz.shape[0]}"]
     head += [f"property {ptype[np.dtype(t)]} {n}" for n, t in fields] + ["end_header"]
     rec = np.empty(xyz.shape[0], dtype=[(n, np.dtype(t).newbyteorder("<")) for n, t in fields])
@@ -310,6 +332,8 @@ def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, bina
     if rgb is not None:
         for i, c in enumerate(("red", "green", "blue")):
             rec[c] = rgb[:, i]
+    if thermal is not None:
+        rec["thermal"] = thermal
     with open(path, "wb") as f:
         f.write(("\n".join(head) + "\n").encode("ascii"))
         if binary:
@@ -322,14 +346,18 @@ def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, bina
 
 def load_3D_points(ply_path: str, transform: Tensor, scale: float) -> Dict[str, Tensor]:
     """nerfstudio_dataparser.py:429-466: the cloud in the dataparser's frame, points3D_xyz = cat(xyz, 1) @ transform.T * scale (transform =
-    auto_orient_and_center_poses' [3,4], scale = the final scale, applied_scale included), and points3D_rgb uint8.  No keys for an empty cloud."""
-    xyz, rgb = read_ply(ply_path)
+    auto_orient_and_center_poses' [3,4], scale = the final scale, applied_scale included), and points3D_rgb uint8.  A file with a `thermal` vertex property (a NeRF point cloud, cloud.py) adds points3D_thermal uint8 [M,1]; a
+    file without it adds no such key.  No keys for an empty cloud."""
+    xyz, rgb, thermal = read_ply_thermal(ply_path)
     if xyz.shape[0] == 0:
         return {}
     points = torch.from_numpy(xyz)
     points = torch.cat((points, torch.ones_like(points[..., :1])), -1) @ transform.T
     points *= scale
-    return {"points3D_xyz": points, "points3D_rgb": torch.from_numpy(rgb)}
+    out = {"points3D_xyz": points, "points3D_rgb": torch.from_numpy(rgb)}
+    if thermal is not None:
+        out["points3D_thermal"] = torch.from_numpy(thermal)
+    return out
 
 
 def load_image_uint8(path: str) -> Tensor:

@@ -365,14 +365,16 @@ class ThermalSplatfactoModel(nn.Module):
     reference's torch ops); quats = a normalised Gaussian draw of the model's seeded CPU generator (uniform on S^3, like random_quat_tensor);
     opacities = logit(0.1); features_dc = RGB2SH(rgb / 255) for sh_degree > 0, or logit(rgb / 255, eps=1e-10) for sh_degree 0 -- evaluated in
     float64 and cast to float32, a deviation from the reference, whose fp32 logit is +inf for a channel value of 255 (float64 gives +-23.03);
-    random features_dc when rgb has no rows (the reference's "colors without points"); features_rest zero.  The cloud carries no thermal
+    random features_dc when rgb has no rows (the reference's "colors without points"); features_rest zero.  A 2-tuple carries no thermal
     values, so features_dc_thermal and features_rest_thermal start at zero: mid-grey in thermal under both colour modes (this project's rule).
+    A 3-tuple (xyz, rgb, thermal [M,1] or [M] uint8: a NeRF point cloud, cloud.py) seeds features_dc_thermal by the colours' rule,
+    RGB2SH(thermal / 255) or the float64 logit; features_rest_thermal stays zero.
     Fewer than 4 seed points is a ValueError (the kNN needs 3 neighbours).  Without seeds, or with `random_init`, construction is this model's
     random cube as before, with the constant log-scale log(0.01 * random_scale): the reference would give the random start kNN scales too,
     which this model deliberately does not, to keep that start unchanged."""
 
     def __init__(self, config: Optional[ThermalSplatfactoModelConfig] = None, num_points: Optional[int] = None, device="cuda", seed: int = 0,
-                 num_train_data: int = 0, seed_points: Optional[Tuple[Tensor, Tensor]] = None, train_is_thermal: Optional[List[bool]] = None):
+                 num_train_data: int = 0, seed_points: Optional[Tuple[Tensor, ...]] = None, train_is_thermal: Optional[List[bool]] = None):
         super().__init__()
         self.config = config or ThermalSplatfactoModelConfig()
         self.num_train_data = num_train_data
@@ -433,9 +435,12 @@ class ThermalSplatfactoModel(nn.Module):
         self.noise_generator.manual_seed(seed)
         self.background_generator = torch.Generator().manual_seed(seed)  # background_color "random": host draws, no synchronisation
 
-    def _seeded_params(self, seed_points: Tuple[Tensor, Tensor], g: torch.Generator, dim_sh: int, dev: torch.device) -> nn.ParameterDict:
+    def _seeded_params(self, seed_points: Tuple[Tensor, ...], g: torch.Generator, dim_sh: int, dev: torch.device) -> nn.ParameterDict:
         """populate_modules with seed points (splatfacto.py:190-225); the rules are in the class docstring."""
-        xyz, rgb = seed_points
+        if len(seed_points) not in (2, 3):
+            raise ValueError(f"seed_points must be (xyz, rgb) or (xyz, rgb, thermal), got {len(seed_points)} entries")
+        xyz, rgb = seed_points[:2]
+        thermal = seed_points[2] if len(seed_points) == 3 else None
         if xyz.dim() != 2 or xyz.shape[1] != 3 or rgb.dim() != 2 or rgb.shape[1] != 3:
             raise ValueError(f"seed_points must be (xyz [M,3], rgb [M,3]), got {tuple(xyz.shape)} and {tuple(rgb.shape)}")
         n = xyz.shape[0]
@@ -443,6 +448,11 @@ class ThermalSplatfactoModel(nn.Module):
             raise ValueError(f"seed_points: {n} points, the kNN scales need at least 4")
         if rgb.shape[0] not in (0, n):
             raise ValueError(f"seed_points: {rgb.shape[0]} colours for {n} points")
+        if thermal is not None:
+            if thermal.dim() not in (1, 2) or (thermal.dim() == 2 and thermal.shape[1] != 1):
+                raise ValueError(f"seed_points: thermal must be [M,1] or [M], got {tuple(thermal.shape)}")
+            if thermal.shape[0] != n:
+                raise ValueError(f"seed_points: {thermal.shape[0]} thermal values for {n} points")
         means = xyz.detach().to(device=dev, dtype=torch.float32).contiguous()
         distances = knn_distances(means, 3)
         avg_dist = distances.mean(dim=-1, keepdim=True)
@@ -456,6 +466,11 @@ class ThermalSplatfactoModel(nn.Module):
                 dc = torch.logit(c.double() / 255, eps=1e-10).float()
         else:
             dc = torch.rand((n, 3), generator=g).to(dev)
+        if thermal is not None:
+            t = thermal.detach().to(device=dev).reshape(n, 1)
+            dc_thermal = RGB2SH(t / 255) if self.config.sh_degree > 0 else torch.logit(t.double() / 255, eps=1e-10).float()
+        else:
+            dc_thermal = torch.zeros((n, 1), device=dev)
         return nn.ParameterDict({
             "means": nn.Parameter(means),
             "scales": nn.Parameter(scales),
@@ -463,7 +478,7 @@ class ThermalSplatfactoModel(nn.Module):
             "opacities": nn.Parameter(torch.logit(0.1 * torch.ones(n, 1)).to(dev)),
             "features_dc": nn.Parameter(dc.float().contiguous()),
             "features_rest": nn.Parameter(torch.zeros((n, dim_sh - 1, 3), device=dev)),
-            "features_dc_thermal": nn.Parameter(torch.zeros((n, 1), device=dev)),
+            "features_dc_thermal": nn.Parameter(dc_thermal.float().contiguous()),
             "features_rest_thermal": nn.Parameter(torch.zeros((n, dim_sh - 1, 1), device=dev)),
         })
 

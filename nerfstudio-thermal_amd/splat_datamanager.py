@@ -96,11 +96,14 @@ class ThermalFullImageDatamanager:
         return [bool(b["is_thermal"]) for b in self.cached_train]
 
     @property
-    def seed_points(self) -> Optional[Tuple[Tensor, Tensor]]:
-        """The dataparser's (points3D_xyz, points3D_rgb) (config.dataparser.load_3D_points), or None when the dataset has no cloud."""
+    def seed_points(self) -> Optional[Tuple[Tensor, ...]]:
+        """The dataparser's (points3D_xyz, points3D_rgb) (config.dataparser.load_3D_points), or None when the dataset has no cloud.  A cloud with
+        thermal values (points3D_thermal: a PLY with the `thermal` property, as cloud.py exports it) comes as the 3-tuple (xyz, rgb, thermal)."""
         meta = self.train_dataparser_outputs.metadata
         if "points3D_xyz" not in meta:
             return None
+        if "points3D_thermal" in meta:
+            return meta["points3D_xyz"], meta["points3D_rgb"], meta["points3D_thermal"]
         return meta["points3D_xyz"], meta["points3D_rgb"]
 
     def _serve(self, cached: List[Batch], cameras: List[PinholeCamera], idx: int) -> Tuple[PinholeCamera, Batch]:

@@ -102,6 +102,9 @@ def main():
     ap.add_argument("--background", default="random")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--seed-points", type=int, default=0, help="start from N points sampled on the cube's surface (generated scene only)")
+    ap.add_argument("--seed-from-dataset", action="store_true",
+                    help="start from the cloud the dataset's transforms.json names as ply_file_path (--data only); a cloud with a thermal property, "
+                         "as scripts/export_point_cloud.py writes it, seeds the thermal features too")
     ap.add_argument("--num-downscales", type=int, default=0, help="train at 1 / 2^N resolution at first (0: full size throughout)")
     ap.add_argument("--resolution-schedule", type=int, default=250, help="steps after which the training resolution doubles")
     ap.add_argument("--tv-pixel-loss-mult", type=float, default=0.0, help="weight of the thermal render's 2x2 total variation on RGB frames (0: off)")
@@ -135,6 +138,8 @@ def main():
     args = ap.parse_args()
     if args.seed_points and args.data is not None:
         ap.error("--seed-points samples the generated scene's cube; a dataset on disk brings its own ply_file_path")
+    if args.seed_from_dataset and args.data is None:
+        ap.error("--seed-from-dataset reads the ply_file_path of a dataset on disk: it needs --data")
     if args.removal_min_opacity_diff is not None and args.thermal_opacity_mode != "separate":
         ap.error("--removal-min-opacity-diff compares the two opacities: it needs --thermal-opacity-mode separate")
     crop_args = (args.crop_pos, args.crop_rpy, args.crop_scale)
@@ -150,12 +155,15 @@ def main():
         write_cube_scene(data, args.frames, dev)
         if args.seed_points:
             add_seed_points(data, args.seed_points, args.seed)
-    pc = ThermalNerfDataParserConfig(data=data, load_3D_points=bool(args.seed_points))
+    seeded = bool(args.seed_points) or args.seed_from_dataset
+    pc = ThermalNerfDataParserConfig(data=data, load_3D_points=seeded)
     dm = ThermalFullImageDatamanagerConfig(dataparser=pc, undistort=not args.no_undistort, seed=args.seed).setup(device=dev)
     # the val split is scored on its undistorted frames whatever the training frames were
     val = dm.fixed_indices_eval_dataloader if not args.no_undistort else \
         ThermalFullImageDatamanagerConfig(dataparser=pc, seed=args.seed).setup(device=dev).fixed_indices_eval_dataloader
-    seed_points = dm.seed_points if args.seed_points else None
+    seed_points = dm.seed_points if seeded else None
+    if args.seed_from_dataset and seed_points is None:
+        ap.error(f"--seed-from-dataset: {data} names no point cloud (ply_file_path)")
     cfg = ThermalSplatfactoModelConfig(num_random=args.gaussians, random_scale=args.init_extent, ssim_lambda=args.ssim_lambda,
                                        background_color=args.background, num_downscales=args.num_downscales,
                                        resolution_schedule=args.resolution_schedule, tv_pixel_loss_mult=args.tv_pixel_loss_mult,
@@ -230,7 +238,8 @@ def main():
             extra["removed_from_thermal_share"] = float((~(gap < thr * ot)).float().mean()) if gap.numel() else 0.0
     print(json.dumps({"dataset": "synthetic cube scene (train_eval_scene.write_cube_scene)" if tmp else data, "train_images": dm.num_train_data,
                       "val_images": len(val), "steps": args.steps, "ssim_lambda": args.ssim_lambda, "background_color": args.background,
-                      "initial_gaussians": initial, "seed_points": args.seed_points, "final_gaussians": model.num_points, "train_seconds": train_s,
+                      "initial_gaussians": initial, "seed_points": args.seed_points,
+                      "seed_from_dataset": args.seed_from_dataset, "thermal_seeds": seed_points is not None and len(seed_points) == 3, "final_gaussians": model.num_points, "train_seconds": train_s,
                       "ms_per_iteration": 1e3 * train_s / max(args.steps, 1), "num_downscales": args.num_downscales,
                       "resolution_schedule": args.resolution_schedule, "tv_pixel_loss_mult": args.tv_pixel_loss_mult,
                       "differentiable_depth": cfg.differentiable_depth, "depth_loss_mult": args.depth_loss_mult, "depth_tv_loss_mult": args.depth_tv_loss_mult,
