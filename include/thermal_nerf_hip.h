@@ -1013,6 +1013,39 @@ TN_API int64_t tn_depth_loss_workspace_bytes(int32_t height, int32_t width);
  * short workspace. */
 TN_API int tn_depth_loss(const float* depth, const float* accumulation, const float* depth_image, int32_t height, int32_t width, float depth_mult,
                          float tv_mult, void* workspace, int64_t workspace_bytes, float* out_loss, float* out_grad, tn_stream_t stream);
+/* ---- N4 per-frame colour correction: bilateral grids ("Bilateral Guided Radiance Field Processing"; gsplat's bil_grids, current splatfacto's
+ * use_bilateral_grid).  grids: [F, K, L, GH, GW] fp32 contiguous, one row per frame, K = C (C + 1): for C = 3 a row-major 3 x 4 affine matrix
+ * [A | b] per vertex, for C = 1 a gain and an offset.  Pixel (i, j) of an [H,W,C] image reads row `row` at
+ *   x = (j + 0.5) / W,  y = (i + 0.5) / H,  g = 0.299 r + 0.587 g + 0.114 b  (C = 1: the value itself)
+ * with grid coordinates (x (GW - 1), y (GH - 1), g (L - 1)), each clamped to [0, size - 1], cell = floor, the upper neighbour's index clamped to
+ * size - 1 -- torch's grid_sample(mode="bilinear", padding_mode="border", align_corners=True) at 2 (x, y, g) - 1 -- the K coefficients interpolated
+ * trilinearly as nested lerps a + t (b - a) (x, then y, then g; uncontracted), and out = A pixel + b.  A grid constant over a cell is reproduced
+ * exactly: the identity grid returns the image's bits.  The backward gives d / d image -- A^T v plus the path through g: the coefficients' slope
+ * along the third axis times L - 1 (0 where g (L - 1) is at or beyond the clamp, grid_sample's rule) times the luma weights -- and the WHOLE
+ * gradient of the one grid row, every entry, exact zeros where no pixel reaches: a gather, one block per vertex, row slice and 8 levels, summed in
+ * a fixed order.  Deterministic: no float atomics, the same inputs give identical bits.  No host synchronisation.
+ * Sizes: C is 1 or 3; every grid side in 2..256; image sides in 1..32768; 1 <= F <= 2^20.
+ *
+ * scratch of tn_bilagrid_slice_backward: the row slices' partial grid gradients; -1 on sizes outside those ranges */
+TN_API int64_t tn_bilagrid_workspace_bytes(int32_t channels, int32_t grid_w, int32_t grid_h, int32_t grid_l, int32_t height, int32_t width);
+/* image: [H,W,*] fp32 whose pixels are pixel_stride floats apart (rows W strides apart; channels 0..C-1 of each pixel are read, so rgbt[..., :3] and
+ * rgbt[..., 3:] of an [H,W,4] render are read in place).  out: [H,W,C] contiguous.  Refused with TN_EINVAL before any launch: null pointers, sizes
+ * outside the ranges above, row outside 0..F-1, a pixel stride below the channel count. */
+TN_API int tn_bilagrid_slice(const float* grids, int32_t num_frames, int32_t row, int32_t channels, int32_t grid_w, int32_t grid_h, int32_t grid_l,
+                             const float* image, int64_t pixel_stride, int32_t height, int32_t width, float* out, tn_stream_t stream);
+/* v_out: [H,W,C] contiguous, d loss / d out.  v_image: [H,W,C] contiguous.  v_grid: [K,L,GH,GW], the gradient of row `row` alone (the other rows'
+ * is zero and is not written here).  Refused as above, and for a short workspace. */
+TN_API int tn_bilagrid_slice_backward(const float* grids, int32_t num_frames, int32_t row, int32_t channels, int32_t grid_w, int32_t grid_h,
+                                      int32_t grid_l, const float* image, int64_t pixel_stride, int32_t height, int32_t width, const float* v_out,
+                                      void* workspace, int64_t workspace_bytes, float* v_image, float* v_grid, tn_stream_t stream);
+/* The grids' total variation, gsplat's total_variation_loss: for each of the three grid axes the sum of squared first differences along it divided
+ * by the number of entries of ONE frame's difference tensor (K L GH (GW - 1) for x), the three terms added and divided by F.
+ * scratch of tn_bilagrid_tv: one partial sum per block; -1 on bad sizes (sides as above, 1..64 coefficients, at most 2^34 entries in all) */
+TN_API int64_t tn_bilagrid_tv_workspace_bytes(int32_t num_frames, int32_t coefficients, int32_t grid_w, int32_t grid_h, int32_t grid_l);
+/* out: DEVICE [1] = mult * tv.  out_grad: [F,K,L,GH,GW] = d out / d grids, written in the same call, or NULL for the value alone.  Every entry gathers
+ * its six neighbours; partial sums are added in a fixed order (double).  Constant grids give exactly 0. */
+TN_API int tn_bilagrid_tv(const float* grids, int32_t num_frames, int32_t coefficients, int32_t grid_w, int32_t grid_h, int32_t grid_l, float mult,
+                          void* workspace, int64_t workspace_bytes, float* out, float* out_grad, tn_stream_t stream);
 /* ---- N4 resolution schedule: bilinear resize of one image, what splatfacto's _downscale_if_required does with
  * torchvision.transforms.functional.resize(antialias=None) (nerfstudio/models/splatfacto.py:648-657), i.e. torch.nn.functional.interpolate(
  * mode="bilinear", align_corners=False, antialias=False).  Per axis: scale = (float)in / out, source coordinate scale * (dst + 0.5) - 0.5 clamped

@@ -241,6 +241,12 @@ SIGNATURES = {
     "tn_thermal_reg": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _f, _f, _p, _i64, _p, _p, _p]),
     "tn_depth_loss_workspace_bytes": (_i64, [_i32, _i32]),
     "tn_depth_loss": (C.c_int, [_p, _p, _p, _i32, _i32, _f, _f, _p, _i64, _p, _p, _p]),
+    # bilateral grids: slice-and-apply of one frame's grid, its backward (image and the whole grid row), the grids' total variation
+    "tn_bilagrid_workspace_bytes": (_i64, [_i32] * 6),
+    "tn_bilagrid_slice": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i64, _i32, _i32, _p, _p]),
+    "tn_bilagrid_slice_backward": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i64, _i32, _i32, _p, _p, _i64, _p, _p, _p]),
+    "tn_bilagrid_tv_workspace_bytes": (_i64, [_i32] * 5),
+    "tn_bilagrid_tv": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _f, _p, _i64, _p, _p, _p]),
     "tn_knn_workspace_bytes": (_i64, [_i64, _i32]),
     "tn_knn": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _i64, _p]),
     # MCMC strategy: relocation / growth in place (8 or 9 tensors with their moments) and the per-step position noise

@@ -258,6 +258,13 @@ SPLAT_CAMERA_OPTIMIZERS = {
     "camera_opt": (1e-3, 1e-4, 5000),
     "camera_opt_thermal": (1e-3, 1e-4, 5000),
 }
+# The bilateral grids of the splat model (ThermalSplatfactoModelConfig.use_bilateral_grid), with splatfacto's rates for its bilateral_grid group
+# (2e-3 decaying to 1e-4 over 30000 steps); splatfacto also warms the group up over 1000 steps, which ExponentialDecayLR here does not do.  Adam is
+# dense over all frames' rows, as in gsplat: a frame's moments keep acting between its visits.
+SPLAT_BILAGRID_OPTIMIZERS = {
+    "bilateral_grid": (2e-3, 1e-4, 30000),
+    "bilateral_grid_thermal": (2e-3, 1e-4, 30000),
+}
 
 
 def _cut_launches(work: list, max_ranges: int = 8) -> List[list]:

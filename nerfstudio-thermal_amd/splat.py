@@ -53,12 +53,22 @@ moments, as in gsplat), with the relocation values evaluated in double.  One mor
 means += Sigma (randn * g * noise_lr * lr of the means), g = sigmoid(100 ((1 - o_vis) - 0.995)), in one tn_splat_mcmc_noise / _sep launch, and
 `get_loss_dict` adds `mcmc_opacity_reg` * mean(sigmoid(opacities)) (+ the thermal mean in separate mode) and `mcmc_scale_reg` * mean(exp(scales)).
 No gradient statistics, no cull, no opacity reset; `last_refine_counts` = (dead, relocated, added).  "default" (the default) takes the code path
-of before, untouched.  Whether "mcmc" trains thermal scenes better is not established (profiles/splat_mcmc.md).  Masks are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
+of before, untouched.  Whether "mcmc" trains thermal scenes better is not established (profiles/splat_mcmc.md).  With `use_bilateral_grid` every training frame has a bilateral grid
+("Bilateral Guided Radiance Field Processing"; gsplat's bil_grids, current splatfacto's use_bilateral_grid / grid_shape / tv_loss): a small 3-D grid
+of affine colour transforms, indexed by pixel position and brightness, that `get_train_outputs` applies to the render of the frame's spectrum
+after the clamp (`bilateral_slice`: tn_bilagrid_slice, its backward a gather without atomics) and `get_loss_dict` regularises by its total
+variation (`tv_loss`, `bilateral_grid_tv`: tn_bilagrid_tv), so that gain, offset and vignetting that drift from frame to frame -- a thermal
+camera's automatic gain control and flat-field corrections, an RGB camera's auto-exposure -- go into the grid instead of into floaters.
+`bil_grids` [F_rgb,12,L,GH,GW] holds 3 x 4 matrices for the RGB frames, `bil_grids_thermal` [F_th,2,L,GH,GW] a gain and an offset for the thermal
+ones (this project's addition), both the identity at first, which returns the render bit for bit; their groups are bilateral_grid /
+bilateral_grid_thermal (optim.SPLAT_BILAGRID_OPTIMIZERS, splatfacto's rates; its 1000-step warm-up of the group is not built:
+ExponentialDecayLR has none).  Eval renders are never corrected.  What the grid is worth on a drifting scene is an observation in
+profiles/splat_bilagrid.md, not a claim.  Masks are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
 tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 
 splat_calls.py: the C entry points, their names and argument order, the workspaces, `knn_distances`, `mcmc_relocate`, `mcmc_noise`.
 splat_camera.py: `PinholeCamera`, `camera_struct`, the resolution schedule's camera, `undistorted_camera`, `OrientedBox`, the pose optimiser.
-splat_image.py: `image_loss`, `resize_image`, `undistort_image`, `thermal_regularizers`, `depth_losses`, `ssim`.
+splat_image.py: `image_loss`, `resize_image`, `undistort_image`, `thermal_regularizers`, `depth_losses`, `bilateral_slice`, `bilateral_grid_tv`, `ssim`.
 """
 from __future__ import annotations
 
@@ -75,7 +85,8 @@ from .config import CameraOptimizerConfig
 from .splat_calls import KNN_MAX_K, _PARAM_NAMES, knn_distances, mcmc_noise, mcmc_relocate, param_names  # noqa: F401
 from .splat_camera import (CAMERA_OPTIMIZER_MODES, OrientedBox, PinholeCamera, SplatCameraOptimizer, camera_struct, downscale_factor,  # noqa: F401
                            pose_camera_record, projection_matrix, rescaled_camera, undistorted_camera)
-from .splat_image import MAX_IMAGE_SIDE, _psnr, depth_losses, image_loss, resize_image, ssim, thermal_regularizers, undistort_image  # noqa: F401
+from .splat_image import (MAX_IMAGE_SIDE, _psnr, bilateral_grid_tv, bilateral_slice, depth_losses, image_loss, resize_image, ssim,  # noqa: F401
+                          thermal_regularizers, undistort_image)
 
 BLOCK_WIDTH = 16  # splatfacto.py:738
 STRATEGIES = ("default", "mcmc")  # densification: splatfacto's gradient-threshold refinement, or gsplat's MCMCStrategy
@@ -160,8 +171,21 @@ class ThermalSplatfactoModelConfig:
     # renders too).  RGB frames read camera_optimizer, thermal frames camera_optimizer_thermal; penalty_scale < 0 also means off
     camera_optimizer: CameraOptimizerConfig = field(default_factory=CameraOptimizerConfig)
     camera_optimizer_thermal: CameraOptimizerConfig = field(default_factory=CameraOptimizerConfig)
+    # per-frame colour correction (current splatfacto's use_bilateral_grid / grid_shape; gsplat's bilateral grids): every training frame has a grid
+    # of affine colour transforms, grid_shape = (GW, GH, L) -- indexed by pixel position and brightness -- applied to its training render only and
+    # regularised by tv_loss = bilateral_grid_tv_mult * total variation (10: splatfacto's constant).  RGB frames have 3 x 4 matrices (bil_grids),
+    # thermal frames a gain and an offset (bil_grids_thermal: this project's).  Every side of the grid is in 2..256.  Off: no parameter, no group
+    use_bilateral_grid: bool = False
+    grid_shape: Tuple[int, int, int] = (16, 16, 8)
+    bilateral_grid_tv_mult: float = 10.0
 
     def __post_init__(self):
+        shape = tuple(self.grid_shape) if isinstance(self.grid_shape, (tuple, list)) else ()
+        if len(shape) != 3 or not all(isinstance(v, int) and not isinstance(v, bool) and 2 <= v <= splat_calls.BILAGRID_MAX_SIDE for v in shape):
+            raise ValueError(f"grid_shape = {self.grid_shape!r}: (GW, GH, L), three integers in 2..{splat_calls.BILAGRID_MAX_SIDE}")
+        self.grid_shape = shape
+        if not self.bilateral_grid_tv_mult >= 0:
+            raise ValueError(f"bilateral_grid_tv_mult = {self.bilateral_grid_tv_mult}: a loss multiplier cannot be negative")
         for name in ("camera_optimizer", "camera_optimizer_thermal"):
             mode = getattr(self, name).mode
             if mode not in CAMERA_OPTIMIZER_MODES:
@@ -213,6 +237,15 @@ def opacity_density_loss(opacities: Tensor, opacities_thermal: Tensor, opacity_l
     Elementwise on [N,1], plain torch."""
     o, o_th = torch.sigmoid(opacities), torch.sigmoid(opacities_thermal)
     return opacity_loss_mult * ((o_th - o.detach()).abs().mean() + rgb_opacity_loss_mult * (o - o_th.detach()).abs().mean())
+
+
+def identity_bilateral_grids(num_frames: int, channels: int, grid_shape: Tuple[int, int, int], device=None) -> Tensor:
+    """[F, C (C + 1), L, GH, GW] grids of the identity transform (gsplat's initialisation): the matrix's diagonal -- for one channel the gain --
+    is 1, every other entry 0.  grid_shape = (GW, GH, L)."""
+    GW, GH, L = grid_shape
+    eye = torch.eye(channels, channels + 1).reshape(1, channels * (channels + 1), 1, 1, 1)
+    grids = eye.repeat(num_frames, 1, L, GH, GW).contiguous()
+    return grids if device is None else grids.to(device)
 
 
 def _is_thermal_frame(batch) -> bool:
@@ -415,6 +448,23 @@ class ThermalSplatfactoModel(nn.Module):
         self.camera_optimizer_thermal = SplatCameraOptimizer(self.config.camera_optimizer_thermal, num_train_data, dev, True,
                                                              None if flags is None else (~flags).nonzero().reshape(-1))
         self.last_view_grad: Optional[Tensor] = None  # dL/d view' [3,4] of the last training frame that read a pose row
+        # per-frame bilateral grids, identity at the start.  With `train_is_thermal` each tensor has a row per training frame of its spectrum, in
+        # cam_idx order (`_bil_rows`: cam_idx -> row, a host list); without, both have num_train_data rows and the row is cam_idx.  A spectrum
+        # without a training frame has no tensor.  Switch off: no parameter, no state-dict entry, no optimiser group.
+        self._bil_rows: Optional[List[int]] = None
+        if self.config.use_bilateral_grid:
+            n_rgb = n_th = num_train_data
+            if flags is not None:
+                seen = [0, 0]
+                self._bil_rows = []
+                for t in flags.tolist():
+                    self._bil_rows.append(seen[t])
+                    seen[t] += 1
+                n_rgb, n_th = seen
+            if n_rgb > 0:
+                self.bil_grids = nn.Parameter(identity_bilateral_grids(n_rgb, 3, self.config.grid_shape, dev))
+            if n_th > 0:
+                self.bil_grids_thermal = nn.Parameter(identity_bilateral_grids(n_th, 1, self.config.grid_shape, dev))
         self.step = 0
         self._ws: Optional[Tensor] = None
         self._cap = 0
@@ -607,6 +657,18 @@ class ThermalSplatfactoModel(nn.Module):
         row = opt.row(camera, training)
         return (opt.pose_adjustment, row) if row is not None else (None, None)
 
+    def _bilateral_grid(self, camera: PinholeCamera) -> Tuple[Optional[Tensor], Optional[int]]:
+        """(grids, row) that correct the training render of `camera` -- its spectrum's tensor and, on the host, the frame's row -- or (None, None):
+        the switch is off, or the camera has no cam_idx."""
+        idx = camera.cam_idx
+        if not self.config.use_bilateral_grid or idx is None:
+            return None, None
+        grids = getattr(self, "bil_grids_thermal" if camera.is_thermal else "bil_grids", None)
+        if not 0 <= int(idx) < self.num_train_data or grids is None:
+            raise ValueError(f"camera.cam_idx = {idx} (is_thermal = {bool(camera.is_thermal)}): the model has no bilateral grid for that training frame")
+        row = int(idx) if self._bil_rows is None else self._bil_rows[int(idx)]
+        return grids, row
+
     def _get_downscale_factor(self) -> int:
         """splatfacto.py:639-646: the resolution schedule's factor at this step while the module is in training mode, else 1."""
         return downscale_factor(self.step, self.config.num_downscales, self.config.resolution_schedule, self.training)
@@ -619,7 +681,10 @@ class ThermalSplatfactoModel(nn.Module):
         model's generator (background [3], background_thermal [1]).  After backward(), `last_xys_grad` [N,2] holds dL/d xys per Gaussian
         (and, with config.use_absgrad, `last_xys_absgrad` [N,2] the sum of its per-pixel terms' absolute values).
         Under the resolution schedule the frame is that of `rescaled_camera(camera, d)` (splatfacto.py:699-700): its size is what `last_size`,
-        `last_radii`, `last_xys_grad` and the refinement statistics refer to; `camera` is not modified."""
+        `last_radii`, `last_xys_grad` and the refinement statistics refer to; `camera` is not modified.  With config.use_bilateral_grid and a
+        camera.cam_idx the frame's bilateral grid corrects the render of the camera's spectrum after the clamp (rgb by bil_grids[row] on an RGB
+        frame, thermal by bil_grids_thermal[row] on a thermal one; `bilateral_slice`): that output then also carries gradients to the grid, it is
+        not clamped again, and the other spectrum's render passes through as it is.  `get_outputs` never applies a grid."""
         d = self._get_downscale_factor()
         if d > 1:
             camera = rescaled_camera(camera, d)
@@ -639,8 +704,16 @@ class ThermalSplatfactoModel(nn.Module):
         rgbt, alpha, depth, *alpha_th = _SplatRender.apply(frame, *(self.gauss_params[k] for k in names), *([pose] if row is not None else []))
         alpha_th = alpha_th[0] if alpha_th else None  # separate mode: the thermal chain's accumulation (differentiable)
         if self.last_num_intersections == 0:  # the background as get_outputs returns it (no clamp)
-            return _outputs(rgbt[..., :3], rgbt[..., 3:], depth, alpha, bgl, alpha_th)
-        return _outputs(torch.clamp(rgbt[..., :3], max=1.0), torch.clamp(rgbt[..., 3:], max=1.0), depth, alpha, bgl, alpha_th)
+            rgb, thermal = rgbt[..., :3], rgbt[..., 3:]
+        else:
+            rgb, thermal = torch.clamp(rgbt[..., :3], max=1.0), torch.clamp(rgbt[..., 3:], max=1.0)
+        grids, row = self._bilateral_grid(camera)
+        if grids is not None:  # the frame's colour correction, on its own spectrum; the result is not clamped again
+            if camera.is_thermal:
+                thermal = bilateral_slice(grids, row, thermal)
+            else:
+                rgb = bilateral_slice(grids, row, rgb)
+        return _outputs(rgb, thermal, depth, alpha, bgl, alpha_th)
 
     # ------------------------------------------------------------------------------------------------ loss and metrics (splatfacto.py:824-934)
     def get_gt_img(self, image: Tensor) -> Tensor:
@@ -691,7 +764,8 @@ class ThermalSplatfactoModel(nn.Module):
         mean|s(o) - s(o_th).detach()|), s = sigmoid (plain torch on [N,1]).  Under strategy "mcmc" also mcmc_opacity_reg = mcmc_opacity_reg *
         mean(s(o)) (+ mean(s(o_th)) in separate mode) and mcmc_scale_reg = mcmc_scale_reg * mean(exp(scales)) (plain torch).  With depth_loss_mult /
         depth_tv_loss_mult above 0 also depth_loss / depth_tv_loss of outputs["depth"] over its covered pixels (one tn_depth_loss call), on RGB and thermal
-        frames alike; depth_loss is 0 for a batch without `depth_image`, and the keys depend on the config alone.  `batch`: image [H,W,3|4], is_thermal,
+        frames alike; depth_loss is 0 for a batch without `depth_image`, and the keys depend on the config alone.  With use_bilateral_grid also tv_loss
+        (splatfacto's key) = bilateral_grid_tv_mult * (tv(bil_grids) + tv(bil_grids_thermal)), `bilateral_grid_tv`.  `batch`: image [H,W,3|4], is_thermal,
         optionally depth_image [H,W,1] float32 in scene units (full size: under the resolution schedule it is taken as depth_image[::d, ::d], cut to the
         frame -- depth is not interpolated)."""
         if "mask" in batch:
@@ -742,6 +816,12 @@ class ThermalSplatfactoModel(nn.Module):
                 o_mean = o_mean + torch.sigmoid(self.gauss_params["opacities_thermal"]).mean()
             losses["mcmc_opacity_reg"] = cfg.mcmc_opacity_reg * o_mean
             losses["mcmc_scale_reg"] = cfg.mcmc_scale_reg * torch.exp(self.gauss_params["scales"]).mean()
+        if cfg.use_bilateral_grid:  # the grids' total variation, over every frame's grid of both spectra (tn_bilagrid_tv)
+            tv_loss = torch.zeros((), device=dev)
+            for name in ("bil_grids", "bil_grids_thermal"):
+                if hasattr(self, name):
+                    tv_loss = tv_loss + bilateral_grid_tv(getattr(self, name), cfg.bilateral_grid_tv_mult)
+            losses["tv_loss"] = tv_loss
         self.camera_optimizer.get_loss_dict(losses)  # camera_opt_regularizer / _thermal (tn_camera_reg), only when the mode is on
         self.camera_optimizer_thermal.get_loss_dict(losses)
         return losses
@@ -785,10 +865,14 @@ class ThermalSplatfactoModel(nn.Module):
         return {g: [self.gauss_params[k]] for g, k in self.group_params.items()}
 
     def get_param_groups(self) -> Dict[str, List[nn.Parameter]]:
-        """The Gaussian groups and, for each pose optimiser that is on, camera_opt / camera_opt_thermal (optim.SPLAT_CAMERA_OPTIMIZERS)."""
+        """The Gaussian groups, for each pose optimiser that is on camera_opt / camera_opt_thermal (optim.SPLAT_CAMERA_OPTIMIZERS), and with
+        use_bilateral_grid bilateral_grid / bilateral_grid_thermal (optim.SPLAT_BILAGRID_OPTIMIZERS)."""
         groups = self.get_gaussian_param_groups()
         self.camera_optimizer.get_param_groups(groups)
         self.camera_optimizer_thermal.get_param_groups(groups)
+        for group, name in (("bilateral_grid", "bil_grids"), ("bilateral_grid_thermal", "bil_grids_thermal")):
+            if hasattr(self, name):
+                groups[group] = [getattr(self, name)]
         return groups
 
     def get_training_callbacks(self, training_callback_attributes) -> List["TrainingCallback"]:

@@ -1,4 +1,4 @@
-"""The call layer of the splat path: the one module that names the tn_splat_* / tn_knn / tn_image_* / tn_thermal_reg / tn_depth_loss entry points of
+"""The call layer of the splat path: the one module that names the tn_splat_* / tn_knn / tn_image_* / tn_thermal_reg / tn_depth_loss / tn_bilagrid_* entry points of
 libthermal_nerf_hip.so and knows their argument order (include/thermal_nerf_hip.h).  The three gsplat calls (project_gaussians,
 spherical_harmonics, rasterize_gaussians x2) run as tn_splat_project / tn_splat_bin / tn_splat_raster of libthermal_nerf_hip.so; separate thermal
 opacity runs the _sep family (tn_splat_project_sep ... tn_splat_refine_apply_sep: the same kernels instantiated with the second chain), and _crop,
@@ -341,3 +341,41 @@ def image_resize(image, ps, out) -> None:
 def image_undistort(image, ps, out, p) -> None:
     """tn_image_undistort of an [H,W,C] uint8 or fp32 image with pixel stride ps into `out` [H,W,C] (uint8 or fp32) by the TnUndistort `p`."""
     _call("tn_image_undistort", _raw(image), _image_code(image), ps, *image.shape, _raw(out), _image_code(out), C.byref(p))
+
+
+# ---------------------------------------------------------------------------------------------------- bilateral grids
+BILAGRID_MAX_SIDE = 256  # every side of a bilateral grid is 2..256 (tn_bilagrid_*)
+
+
+def _bilagrid_sizes(grids: Tensor, what: str) -> Tuple[int, int, int, int, int]:
+    """(F, K, L, GH, GW) of a grids tensor [F,K,L,GH,GW]; a ValueError for another shape or a side outside 2..BILAGRID_MAX_SIDE."""
+    if grids.dim() != 5:
+        raise ValueError(f"{what}: grids must be [F, K, L, GH, GW], got {tuple(grids.shape)}")
+    F, K, L, GH, GW = (int(v) for v in grids.shape)
+    if F < 1 or not all(2 <= v <= BILAGRID_MAX_SIDE for v in (L, GH, GW)):
+        raise ValueError(f"{what}: {F} grids of {GW} x {GH} x {L}, every side must be in 2..{BILAGRID_MAX_SIDE}")
+    return F, K, L, GH, GW
+
+
+def bilagrid_slice(grids, row, image, ps, out) -> None:
+    """tn_bilagrid_slice: row `row` of `grids` [F,C(C+1),L,GH,GW] applied to `image` [H,W,C] (pixel stride ps) into `out` [H,W,C]."""
+    F, K, L, GH, GW = _bilagrid_sizes(grids, "bilagrid_slice")
+    H, W, Cc = image.shape
+    _call("tn_bilagrid_slice", *_f32(grids=grids), F, int(row), Cc, GW, GH, L, _raw(image), ps, H, W, *_f32(out=out))
+
+
+def bilagrid_slice_backward(grids, row, image, ps, v_out, v_image, v_grid) -> None:
+    """tn_bilagrid_slice_backward: `v_image` [H,W,C] and `v_grid` [K,L,GH,GW], the whole gradient of row `row`; the workspace is this call's."""
+    F, K, L, GH, GW = _bilagrid_sizes(grids, "bilagrid_slice_backward")
+    H, W, Cc = image.shape
+    ws = workspace("tn_bilagrid_workspace_bytes", Cc, GW, GH, L, H, W, device=grids.device, what=f"bad sizes {H} x {W} x {Cc}, grid {GW} x {GH} x {L}",
+                   exc=ValueError)
+    _call("tn_bilagrid_slice_backward", *_f32(grids=grids), F, int(row), Cc, GW, GH, L, _raw(image), ps, H, W, *_f32(v_out=v_out), _raw(ws), ws.numel(),
+          *_f32(v_image=v_image, v_grid=v_grid))
+
+
+def bilagrid_tv(grids, mult, out, grad) -> None:
+    """tn_bilagrid_tv: mult * total variation of `grids` [F,K,L,GH,GW] into `out` [1] and, with `grad`, its gradient in the same call."""
+    F, K, L, GH, GW = _bilagrid_sizes(grids, "bilagrid_tv")
+    ws = workspace("tn_bilagrid_tv_workspace_bytes", F, K, GW, GH, L, device=grids.device, what=f"bad sizes {F} x {K} x {L} x {GH} x {GW}", exc=ValueError)
+    _call("tn_bilagrid_tv", *_f32(grids=grids), F, K, GW, GH, L, float(mult), _raw(ws), ws.numel(), *_f32(out=out, grad=grad))

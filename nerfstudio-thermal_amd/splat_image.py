@@ -8,7 +8,9 @@ differences against those of the RGB ground truth's grey value -- over every str
 (`thermal_regularizers`: tn_thermal_reg), so the thermal channel gets a gradient from RGB frames too.  Two geometric priors act on the depth render
 where it is covered (`depth_losses`: tn_depth_loss): the L1 distance to a sensor depth and the 2 x 2 total variation of the depth.  Distorted frames are resampled once into
 pinhole frames: `undistort_image` is the frame `splat_camera.undistorted_camera` sees (tn_image_undistort, uint8 or fp32 in and out);
-splat_datamanager.ThermalFullImageDatamanager caches the undistorted frames on the device and serves (camera, batch).
+splat_datamanager.ThermalFullImageDatamanager caches the undistorted frames on the device and serves (camera, batch).  Per-frame colour correction
+is gsplat's bilateral grid: `bilateral_slice` applies one frame's grid of affine colour transforms to a training render (tn_bilagrid_slice, its
+backward a gather without atomics) and `bilateral_grid_tv` is the grids' total-variation regulariser (tn_bilagrid_tv).
 """
 from __future__ import annotations
 
@@ -265,6 +267,98 @@ def depth_losses(depth: Tensor, accumulation: Tensor, depth_image: Optional[Tens
         return _DepthLosses.apply(depth, accumulation, depth_image, float(depth_mult), float(tv_mult))
     out, _ = _depth_loss_call(depth, accumulation, depth_image, depth_mult, tv_mult, False)
     return out[0], out[1]
+
+
+class _BilateralSlice(torch.autograd.Function):
+    """tn_bilagrid_slice as an autograd node: forward applies row `row` of `grids` to the image; backward is one tn_bilagrid_slice_backward call --
+    the image's gradient and a dense gradient for `grids`, the row's own entries from the kernel's gather and zeros in every other row."""
+
+    @staticmethod
+    def forward(ctx, grids, row, image):
+        out, g, img = _bilateral_slice_call(grids, row, image)
+        ctx.save_for_backward(g, img)
+        ctx.row = row
+        return out
+
+    @staticmethod
+    def backward(ctx, v_out):
+        g, img = ctx.saved_tensors
+        img, ps = _image_view(img, "image")
+        v_image = torch.empty(tuple(img.shape), device=img.device)
+        v_grids = torch.zeros_like(g) if g.shape[0] > 1 else torch.empty_like(g)
+        splat_calls.bilagrid_slice_backward(g, ctx.row, img, ps, v_out.float().contiguous(), v_image, v_grids[ctx.row])
+        return (v_grids if ctx.needs_input_grad[0] else None), None, (v_image if ctx.needs_input_grad[2] else None)
+
+
+def _bilateral_check(grids: Tensor, what: str) -> Tensor:
+    if not isinstance(grids, Tensor) or not grids.is_cuda or grids.dtype != torch.float32:
+        raise ValueError(f"{what}: grids must be an fp32 HIP tensor (the splat path has no CPU fallback)")
+    splat_calls._bilagrid_sizes(grids, what)
+    return grids.detach().contiguous()
+
+
+def _bilateral_slice_call(grids: Tensor, row: int, image: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    g = _bilateral_check(grids, "bilateral_slice")
+    img, ps = _image_view(image.detach() if isinstance(image, Tensor) else image, "image")
+    H, W, Cc = img.shape
+    if Cc not in (1, 3) or g.shape[1] != Cc * (Cc + 1):
+        raise ValueError(f"bilateral_slice: an image of {Cc} channels and grids of {g.shape[1]} coefficients; RGB [H,W,3] takes 12, thermal [H,W,1] takes 2")
+    if not 0 <= int(row) < g.shape[0]:
+        raise ValueError(f"bilateral_slice: row {row} of {g.shape[0]} grids")
+    if not all(1 <= v <= MAX_IMAGE_SIDE for v in (H, W)):
+        raise ValueError(f"bilateral_slice: {H} x {W}, every side must be in 1..{MAX_IMAGE_SIDE}")
+    out = torch.empty((H, W, Cc), device=img.device)
+    splat_calls.bilagrid_slice(g, int(row), img, ps, out)
+    return out, g, img
+
+
+def bilateral_slice(grids: Tensor, row: int, image: Tensor) -> Tensor:
+    """Bilateral-grid colour correction of one frame ("Bilateral Guided Radiance Field Processing", gsplat's bil_grids): row `row` (a host int) of
+    `grids` [F,K,L,GH,GW] applied to `image` [H,W,C] -> [H,W,C], one tn_bilagrid_slice call on the current stream, without a host synchronisation.
+    C = 3 with K = 12 (a row-major 3 x 4 affine matrix [A | b] per vertex) or C = 1 with K = 2 (gain, offset).  Pixel (i, j) reads the grid at
+    ((j + 0.5) / W, (i + 0.5) / H, g), g = 0.299 r + 0.587 g + 0.114 b (C = 1: the value), trilinearly, as
+    F.grid_sample(mode="bilinear", padding_mode="border", align_corners=True) does at 2 (x, y, g) - 1; out = A pixel + b.  The interpolation is
+    nested lerps, so the identity grid returns the image bit for bit.  Every grid side is in 2..256.  A view whose pixels are further apart than C
+    (rgbt[..., :3], rgbt[..., 3:]) is read in place.  Differentiable in `grids` (dense: zeros in the other rows) and in `image` (both paths: A^T v
+    and the guidance coordinate; 0 through the clamp at g (L - 1) <= 0 or >= L - 1), bit-reproducibly, without float atomics."""
+    if torch.is_grad_enabled() and ((isinstance(grids, Tensor) and grids.requires_grad) or (isinstance(image, Tensor) and image.requires_grad)):
+        _bilateral_check(grids, "bilateral_slice")
+        return _BilateralSlice.apply(grids, int(row), image)
+    return _bilateral_slice_call(grids, row, image)[0]
+
+
+class _BilateralTV(torch.autograd.Function):
+    """tn_bilagrid_tv as an autograd node: value and gradient come from the one forward call; backward scales the saved gradient."""
+
+    @staticmethod
+    def forward(ctx, grids, mult):
+        out, grad = _bilateral_tv_call(grids, mult, True)
+        ctx.save_for_backward(grad)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None
+
+
+def _bilateral_tv_call(grids: Tensor, mult: float, want_grad: bool) -> Tuple[Tensor, Optional[Tensor]]:
+    g = _bilateral_check(grids, "bilateral_grid_tv")
+    out = torch.empty(1, device=g.device)
+    grad = torch.empty_like(g) if want_grad else None
+    splat_calls.bilagrid_tv(g, float(mult), out, grad)
+    return out[0], grad
+
+
+def bilateral_grid_tv(grids: Tensor, mult: float = 1.0) -> Tensor:
+    """mult * the total variation of bilateral grids [F,K,L,GH,GW] (gsplat's total_variation_loss), a device scalar from one tn_bilagrid_tv call
+    without a host synchronisation: for each of the three grid axes the sum of squared first differences along it over the entries of one frame's
+    difference tensor, the three added and divided by F.  Constant grids give exactly 0.  Differentiable in `grids` (the gradient is written by the
+    same call)."""
+    if torch.is_grad_enabled() and isinstance(grids, Tensor) and grids.requires_grad:
+        _bilateral_check(grids, "bilateral_grid_tv")
+        return _BilateralTV.apply(grids, float(mult))
+    return _bilateral_tv_call(grids, mult, False)[0]
 
 
 def ssim(pred: Tensor, gt: Tensor) -> Tensor:

@@ -23,7 +23,13 @@ split is scored on the whole scene, its frames are rendered again through get_ou
 (rgb_*.png, thermal_*.png; in separate mode with --removal-min-opacity-diff also removal_*.png and removal_thermal_*.png), and the line reports
 the share of Gaussians the box keeps.  --strategy mcmc trains with gsplat's MCMC strategy instead of splatfacto's gradient-threshold refinement: a budget of
 --max-gs-num Gaussians, relocation and growth every refine_every steps (tn_splat_mcmc_relocate), position noise of --noise-lr times the means' learning
-rate after every step (tn_splat_mcmc_noise), and the two MCMC regularisers in the loss."""
+rate after every step (tn_splat_mcmc_noise), and the two MCMC regularisers in the loss.  --use-bilateral-grid gives every training frame a bilateral
+grid of affine colour transforms (current splatfacto's use_bilateral_grid: tn_bilagrid_slice on the training render, tv_loss in the loss, the groups
+bilateral_grid / bilateral_grid_thermal with optim.SPLAT_BILAGRID_OPTIMIZERS); --frame-drift X simulates an automatic gain control on the generated
+scene: every TRAINING frame is multiplied by a gain drawn uniformly in [1 - X, 1 + X] and shifted by an offset in [-X / 2, X / 2] (seeded by --seed,
+clamped to [0, 1]); the held-out frames are left alone, so the val metrics say what the drift did to the scene itself.  Eval renders are never
+corrected by a grid, so the line also reports psnr_rgb_affine_fit / psnr_thermal_affine_fit: each held-out frame's PSNR
+after the least-squares affine colour map of its render onto its ground truth (a diagnostic of this script, plain torch)."""
 import argparse
 import functools
 import json
@@ -44,7 +50,7 @@ from nerfstudio_thermal_amd import ThermalFullImageDatamanagerConfig  # noqa: E4
 from nerfstudio_thermal_amd.dataparser import ThermalNerfDataParserConfig, load_image_float32, write_ply  # noqa: E402
 from nerfstudio_thermal_amd.model import TrainingCallbackLocation  # noqa: E402
 from nerfstudio_thermal_amd.config import CameraOptimizerConfig  # noqa: E402
-from nerfstudio_thermal_amd.optim import SPLAT_CAMERA_OPTIMIZERS, SPLAT_OPTIMIZERS, HipAdam, Optimizers  # noqa: E402
+from nerfstudio_thermal_amd.optim import SPLAT_BILAGRID_OPTIMIZERS, SPLAT_CAMERA_OPTIMIZERS, SPLAT_OPTIMIZERS, HipAdam, Optimizers  # noqa: E402
 from nerfstudio_thermal_amd.splat import OrientedBox, PinholeCamera, ThermalSplatfactoModel, ThermalSplatfactoModelConfig, downscale_factor  # noqa: E402
 from train_eval_scene import write_cube_scene  # noqa: E402
 
@@ -72,6 +78,35 @@ def add_seed_points(data: str, num: int, seed: int) -> None:
     meta["ply_file_path"] = "sparse_pc.ply"
     with open(path, "w", encoding="utf-8") as f:
         json.dump(meta, f, indent=4)
+
+
+def apply_frame_drift(cached_train, drift: float, seed: int):
+    """A simulated automatic gain control: every cached training frame becomes clamp(gain * frame + offset, 0, 1), gain uniform in
+    [1 - drift, 1 + drift], offset uniform in [-drift / 2, drift / 2], one pair per frame from a generator seeded by `seed`; uint8 frames stay
+    uint8.  Returns the (gain, offset) pairs."""
+    g = torch.Generator().manual_seed(seed + 7919)
+    pairs = []
+    for batch in cached_train:
+        gain = 1.0 + drift * (2.0 * float(torch.rand((), generator=g)) - 1.0)
+        offset = 0.5 * drift * (2.0 * float(torch.rand((), generator=g)) - 1.0)
+        image = batch["image"]
+        if image.dtype == torch.uint8:
+            batch["image"] = ((image.float() / 255.0 * gain + offset).clamp(0.0, 1.0) * 255.0).round().to(torch.uint8)
+        else:
+            batch["image"] = (image * gain + offset).clamp(0.0, 1.0)
+        pairs.append((gain, offset))
+    return pairs
+
+
+def affine_fit_psnr(pred: torch.Tensor, gt: torch.Tensor) -> float:
+    """PSNR of an [H,W,C] render against its ground truth after the least-squares affine colour map pred -> gt of that frame (a C x (C + 1)
+    matrix): what is left once a global gain, offset and colour mix are taken out.  A diagnostic of this script -- eval renders are never
+    corrected by a bilateral grid --; plain torch."""
+    C_ = pred.shape[2]
+    x = torch.cat([pred.reshape(-1, C_), torch.ones((pred.shape[0] * pred.shape[1], 1), device=pred.device)], dim=1).double()
+    y = gt.reshape(-1, C_).double()
+    fit = x @ torch.linalg.lstsq(x, y).solution
+    return float(-10.0 * torch.log10(torch.mean((fit - y) ** 2)))
 
 
 def write_cropped_frames(model, val, box, out_dir: str) -> int:
@@ -134,10 +169,18 @@ def main():
                     help='"mcmc": a budget of --max-gs-num Gaussians, dead ones relocated onto live ones, position noise every step (gsplat\'s MCMCStrategy)')
     ap.add_argument("--max-gs-num", type=int, default=1_000_000, help="the MCMC strategy's budget of Gaussians")
     ap.add_argument("--noise-lr", type=float, default=5e5, help="the MCMC strategy's position noise, in units of the means' learning rate")
+    ap.add_argument("--use-bilateral-grid", action="store_true",
+                    help="a bilateral grid of affine colour transforms per training frame, applied to its training render (tv_loss regularises it)")
+    ap.add_argument("--frame-drift", type=float, default=0.0, metavar="X",
+                    help="generated scene only: training frames times a per-frame gain in [1-X, 1+X] plus an offset in [-X/2, X/2]; val frames untouched")
     ap.add_argument("--no-undistort", action="store_true", help="train on the raw frames with the parser's intrinsics (the distortion dropped)")
     args = ap.parse_args()
     if args.seed_points and args.data is not None:
         ap.error("--seed-points samples the generated scene's cube; a dataset on disk brings its own ply_file_path")
+    if args.frame_drift and args.data is not None:
+        ap.error("--frame-drift drifts the generated scene's training frames; a dataset on disk is trained as it is")
+    if not 0.0 <= args.frame_drift < 1.0:
+        ap.error("--frame-drift takes X in [0, 1)")
     if args.seed_from_dataset and args.data is None:
         ap.error("--seed-from-dataset reads the ply_file_path of a dataset on disk: it needs --data")
     if args.removal_min_opacity_diff is not None and args.thermal_opacity_mode != "separate":
@@ -161,6 +204,8 @@ def main():
     # the val split is scored on its undistorted frames whatever the training frames were
     val = dm.fixed_indices_eval_dataloader if not args.no_undistort else \
         ThermalFullImageDatamanagerConfig(dataparser=pc, seed=args.seed).setup(device=dev).fixed_indices_eval_dataloader
+    if args.frame_drift:
+        apply_frame_drift(dm.cached_train, args.frame_drift, args.seed)
     seed_points = dm.seed_points if seeded else None
     if args.seed_from_dataset and seed_points is None:
         ap.error(f"--seed-from-dataset: {data} names no point cloud (ply_file_path)")
@@ -174,11 +219,11 @@ def main():
                                        camera_optimizer=CameraOptimizerConfig(mode=args.camera_optimizer),
                                        camera_optimizer_thermal=CameraOptimizerConfig(mode=args.camera_optimizer_thermal), use_absgrad=args.use_absgrad,
                                        densify_grad_thresh=args.densify_grad_thresh, strategy=args.strategy, max_gs_num=args.max_gs_num,
-                                       noise_lr=args.noise_lr)
+                                       noise_lr=args.noise_lr, use_bilateral_grid=args.use_bilateral_grid)
     model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=dm.num_train_data, seed_points=seed_points,
                                    train_is_thermal=dm.train_is_thermal)
     initial = model.num_points
-    opts = Optimizers(model.get_param_groups(), {**SPLAT_OPTIMIZERS, **SPLAT_CAMERA_OPTIMIZERS}, optimizer_cls=HipAdam)
+    opts = Optimizers(model.get_param_groups(), {**SPLAT_OPTIMIZERS, **SPLAT_CAMERA_OPTIMIZERS, **SPLAT_BILAGRID_OPTIMIZERS}, optimizer_cls=HipAdam)
     cbs = model.get_training_callbacks(opts)
     curve = []
     stages = []  # one entry per run of steps at one downscale factor
@@ -212,7 +257,10 @@ def main():
     model.eval()  # the val split is scored at full size whatever the schedule's factor at the last step
     with torch.no_grad():
         for cam, batch in val:
-            metrics, _ = model.get_image_metrics_and_images(model.get_outputs(cam), batch)
+            outputs = model.get_outputs(cam)
+            metrics, _ = model.get_image_metrics_and_images(outputs, batch)
+            th, pred, gt = model._frame_pred_gt(outputs, batch, resize_pred=True)  # the same frame after a per-frame affine colour fit
+            metrics["psnr_thermal_affine_fit" if th else "psnr_rgb_affine_fit"] = affine_fit_psnr(pred, gt.float())
             for k, v in metrics.items():
                 sums.setdefault(k, []).append(v)
     extra = {}
@@ -246,7 +294,7 @@ def main():
                       "cross_channel_loss_mult": args.cross_channel_loss_mult, "undistort": not args.no_undistort, "thermal_opacity_mode": args.thermal_opacity_mode,
                       "opacity_loss_mult": args.opacity_loss_mult, "camera_optimizer": args.camera_optimizer,
                       "camera_optimizer_thermal": args.camera_optimizer_thermal, "strategy": args.strategy, "max_gs_num": args.max_gs_num,
-                      "noise_lr": args.noise_lr, **extra, "stages": stages, "val_metrics": metrics, "curve": curve}))
+                      "noise_lr": args.noise_lr, "use_bilateral_grid": args.use_bilateral_grid, "frame_drift": args.frame_drift, **extra, "stages": stages, "val_metrics": metrics, "curve": curve}))
 
 
 if __name__ == "__main__":
