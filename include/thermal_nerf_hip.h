@@ -1177,6 +1177,61 @@ TN_API int64_t tn_cloud_remove_outliers_workspace_bytes(int64_t n, int32_t nb_ne
 TN_API int tn_cloud_remove_outliers(const float* xyz, const float* rgb, const float* thermal, int64_t n, int32_t nb_neighbors, double std_ratio,
                                     float* out_xyz, float* out_rgb, float* out_thermal, int64_t* out_count, double* stats, double* mean, uint8_t* keep,
                                     void* workspace, int64_t workspace_bytes, tn_stream_t stream);
+
+/* ---- TSDF mesh export (ns-export tsdf: nerfstudio/exporter/tsdf_utils.py, TSDF.integrate_tsdf and get_mesh): rendered depth frames are fused into
+ * a truncated signed distance volume with an RGB+thermal value per voxel, and the zero level of the volume is extracted as an indexed triangle mesh.
+ * All three entry points run on the caller's stream without a host synchronisation and without atomics: the same inputs give the same bytes.
+ * tests/tsdf_functional.py restates them.
+ *
+ * The volume: values [X,Y,Z] (the reference starts it at -1), weights [X,Y,Z] (at 0) and rgbt [X,Y,Z,4] (16-byte aligned), fp32, z fastest.  Voxel
+ * (i, j, k) sits at origin + (i, j, k) * voxel (the product and the sum each rounded on its own).  X * Y * Z is below 2^31.
+ *
+ * tn_tsdf_integrate: num_frames frames in ONE launch, a thread per voxel, the frames in the order given.  depth [B,H,W], frame_rgbt [B,H,W,4]
+ * (channel-last, 16-byte aligned), accumulation [B,H,W] or null, cameras [B,16] on the DEVICE: the rows of the 3x4 world -> camera matrix
+ * (nerfstudio's camera: x right, y up, z back), then fx fy cx cy.  Per frame, in fp32 with every operation rounded on its own:
+ *   (x, y, z) = M [p, 1] with y and z negated; a voxel with z <= 0 is skipped (the reference divides by that z and mirrors the voxel into the image);
+ *   voxel depth vd = sqrt((x x + y y) + z z) with ray_depth 1 (the reference's rule, the depth of a NeRF), z with ray_depth 0 (a rasteriser's depth);
+ *   pixel column = rint(fx (x / z) + cx - 0.5), row = rint(fy (y / z) + cy - 0.5), half to even: the nearest-pixel sample of
+ *   grid_sample(mode="nearest", align_corners=False, padding_mode="zeros"); outside the image the sample is 0;
+ *   with accumulation, a pixel whose accumulation < min_accumulation counts as depth 0;
+ *   dist = depth - vd; the sample is valid iff vd > 0, depth > 0 and dist > -truncation; tsdf = clamp(dist / truncation, -1, 1);
+ *   where valid: value = (value w + tsdf) / (w + 1), the same for the four rgbt channels, then w = min(w + 1, max_weight).
+ * max_weight 1 is the reference (a running half-and-half average that depends on the frame order), a large one the running mean.  A voxel no frame
+ * of the call observes is neither read nor written, so splitting the frames over several calls gives the same bits.  num_frames == 0 is TN_OK and
+ * touches nothing.  Refused with TN_EINVAL before any launch: sizes outside the above (H, W in 1..32768), an origin that is not finite, a voxel size
+ * or truncation that is not positive and finite, max_weight <= 0, ray_depth other than 0 or 1, null pointers (accumulation may be null), misaligned
+ * rgbt arrays. */
+TN_API int tn_tsdf_integrate(float* values, float* weights, float* rgbt, int32_t X, int32_t Y, int32_t Z, float origin_x, float origin_y,
+                             float origin_z, float voxel_x, float voxel_y, float voxel_z, float truncation, float max_weight, const float* depth,
+                             const float* frame_rgbt, const float* accumulation, float min_accumulation, const float* cameras, int32_t num_frames,
+                             int32_t height, int32_t width, int32_t ray_depth, tn_stream_t stream);
+/* Surface extraction at level 0 of v = clamp(values, -1, 1) by marching tetrahedra on the Freudenthal split of each cell: with the corners of a cell
+ * numbered dx + 2 dy + 4 dz, the tetrahedra (0, a, a + b, 7) for the six orders (a, b, c) of the axes x = 1, y = 2, z = 4 in lexicographic order.
+ * Their edges are the seven kinds +x +y +z +xy +yz +xz +xyz (in this order) per lattice point, the split is the same in every cell, so neighbours
+ * agree on shared faces and a closed level set gives a closed mesh.  v < 0 is inside (a NaN is outside).  The mesh is indexed:
+ *   a vertex belongs to a lattice edge whose ends differ in sign; vertices are numbered by the exclusive prefix sum of the edge flags in
+ *   (voxel linear index, edge kind) order; faces come in (cell linear index, tetrahedron, triangle) order, wound so that the normal points to the
+ *   positive values.  With observed_only a cell with a corner of weight 0 emits nothing, and an edge none of whose cells is emitted has no vertex;
+ *   a dimension of 1 has no cells.
+ * tn_mesh_count writes totals = [vertices, faces] (DEVICE int64[2]) and leaves the flags and the scanned block counts in the workspace;
+ * tn_mesh_emit, called with the SAME workspace, volume and observed_only, writes, for the edge from lattice point p = (i, j, k) along e with a = v(p),
+ * b = v(p + e), t = a / (a - b):
+ *   vertices [V,3] = origin + ((i, j, k) + t e) * voxel;
+ *   normals [V,3] = g / |g|, g = g(p) + t (g(p + e) - g(p)), g(q) = the central difference of v at q (one-sided at the volume's border, 0 along an
+ *   axis of one point) over the voxel size, |g| = sqrt((gx gx + gy gy) + gz gz); a zero g stays the zero vector;
+ *   out_rgbt [V,4] = rgbt of p if t <= 0.5, else of p + e; if that end has weight 0, of the other;
+ *   faces [F,3] int32.
+ * Rows at or beyond num_vertices / num_faces are not written.  Refused with TN_EINVAL before any launch: dimensions below 1 or 2^31 points and
+ * more, null pointers (the outputs may be null when their count is 0), more than 2^31 - 1 vertices, misaligned rgbt arrays, a short workspace.
+ *
+ * scratch of the two (a flag byte and a first-vertex index per lattice point, two counts and two offsets per block of 256); -1 for refused sizes */
+TN_API int64_t tn_mesh_workspace_bytes(int32_t X, int32_t Y, int32_t Z);
+TN_API int tn_mesh_count(const float* values, const float* weights, int32_t X, int32_t Y, int32_t Z, int32_t observed_only, int64_t* totals,
+                         void* workspace, int64_t workspace_bytes, tn_stream_t stream);
+TN_API int tn_mesh_emit(const float* values, const float* weights, const float* rgbt, int32_t X, int32_t Y, int32_t Z, int32_t observed_only,
+                        float origin_x, float origin_y, float origin_z, float voxel_x, float voxel_y, float voxel_z, float* vertices, float* normals,
+                        float* out_rgbt, int64_t num_vertices, int32_t* faces, int64_t num_faces, void* workspace, int64_t workspace_bytes,
+                        tn_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -260,6 +260,10 @@ SIGNATURES = {
     "tn_cloud_append": (C.c_int, [_p] * 5 + [_i64, _p, _i64, _i64, _f, C.POINTER(TnSplatCrop), _p, _p, _p, _i64, _p, _p, _i64, _p]),
     "tn_cloud_remove_outliers_workspace_bytes": (_i64, [_i64, _i32]),
     "tn_cloud_remove_outliers": (C.c_int, [_p, _p, _p, _i64, _i32, C.c_double] + [_p] * 8 + [_i64, _p]),
+    "tn_tsdf_integrate": (C.c_int, [_p, _p, _p, _i32, _i32, _i32] + [_f] * 8 + [_p, _p, _p, _f, _p, _i32, _i32, _i32, _i32, _p]),
+    "tn_mesh_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "tn_mesh_count": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _i64, _p]),
+    "tn_mesh_emit": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32] + [_f] * 6 + [_p, _p, _p, _i64, _p, _i64, _p, _i64, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

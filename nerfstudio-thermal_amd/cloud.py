@@ -8,8 +8,8 @@ with `write_cloud_ply` and named as a dataset's `ply_file_path` seeds thermal sp
 -> ThermalFullImageDatamanager.seed_points -> ThermalSplatfactoModel(seed_points=(xyz, rgb, thermal))).
 
 The raw calls of the two entry points are `append_call` and `remove_outliers_call`, the only places that know their argument order
-(include/thermal_nerf_hip.h).  Everything runs on torch's current stream; there is no CPU fallback.  Normals, view directions and meshes are not
-exported.
+(include/thermal_nerf_hip.h).  Everything runs on torch's current stream; there is no CPU fallback.  Normals and view directions are not exported
+with the cloud; a mesh with normals, colours and temperatures per vertex is mesh.py's (the counterpart of `ns-export tsdf`).
 """
 from __future__ import annotations
 
