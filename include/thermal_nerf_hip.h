@@ -37,6 +37,13 @@
  *                                 extra blocks of the table scatter's bin launch
  *      TN_POSE_FINISH_COWORK=0    (read per call) tn_train_step's last backward launch (tn_pose_bwd_finish_check) always as a launch of its own instead of
  *                                 the first blocks of the main grid's fold launch on iterations without a proposal update
+ *      TN_FOLD_ADAM=0             tn_train_step: the main grid's fold never steps its own table (A/B timing, tests).  By default the fold block that has
+ *                                 summed a bucket's gradient in LDS applies Adam to the bucket's slots itself -- the table gradient is neither stored,
+ *                                 read back nor zeroed, the Adam launch skips the table -- whenever the segmented scatter runs with one fold block per
+ *                                 bucket (<= 524288 field samples), table_grad_is_zero holds, the d position pass rides in the bin launch and one
+ *                                 optimiser range contains the table; and, decided on the device every iteration, max |d enc| <= FLT_MAX / (8 P).  Same
+ *                                 results; slots 12..15 of losses16 then hold max |d enc|, the decision (0 not armed, 1 fused, 2 fell back), and the
+ *                                 step's two scalars
  *      TN_FUSE_RENDER=1           (read per call) tn_train_step with tn_render_fwd / tn_train_losses / tn_render_bwd as ONE launch,
  *                                 tn_render_losses_bwd -- a measured experiment that is correct and not faster (profiles/r05_experiments.md)
  *      TN_NEXT_SAMPLING=0|2|3|4   (read per call) tn_train_step's next_sampling: 0 = never taken (every iteration samples in line); 2 = the chain as a launch

@@ -400,6 +400,8 @@ __device__ __forceinline__ void tn_patch_order(int64_t i, int64_t N, int S, int6
 #endif
 #define TN_BIN_MAX_SLICES 256
 #define TN_BIN_COUNT_STRIDE 16  // words reserved per bucket counter (one 64-B line each)
+// The segmented path (seg_plan) lays its records (8.5 per sample and level), its headers and TN_MAX_LEVELS x (bin blocks) x 8 words of per-wave
+// maxima (a fold that steps its table: tn_adam.h) out inside the same bytes, and checks that they fit: shrinking this formula means revisiting it.
 static inline int64_t tn_bin_level_records(int64_t P) { return 16 * P + TN_BIN_MAX_SLICES * 1032; }
 static inline int64_t tn_bin_bytes(int64_t P, int num_levels) {
   return 256 + (int64_t)num_levels * TN_BIN_MAX_SLICES * 4 * TN_BIN_COUNT_STRIDE + (int64_t)num_levels * tn_bin_level_records(P) * (2 + 8);
@@ -446,7 +448,8 @@ int tn_adam_step_ranges_amp_update_cw(float* params, const float* grads, float* 
                                       float* found_inf, const int32_t* flag_index, int32_t num_flags, int32_t* skipped, int32_t lag_index,
                                       int32_t count_skip, int32_t zero_grads, float* scale, int32_t* growth_tracker, uint32_t* done_counter,
                                       double growth_factor, double backoff_factor, int32_t growth_interval, const TnSampleRays* next, bool* next_taken,
-                                      tn_stream_t stream, const TnNextSamplingHost* chain = nullptr, bool su_update = true);
+                                      tn_stream_t stream, const TnNextSamplingHost* chain = nullptr, bool su_update = true,
+                                      const float* cond_word = nullptr, int cond_range = -1);  // (cond_*: AdamRangesAmp::cond_word, tn_misc.hip)
 // whether the chain supports these sample counts (the lane layouts of the default sampler: 4 / 2 samples per lane on the proposal levels)
 static inline bool tn_next_sampling_supported(int S0, int S1, int S2) { return S0 > 128 && S0 <= 256 && S1 > 64 && S1 <= 128 && S2 >= 1 && S2 <= 256; }
 // internal variants of tn_render_fwd / tn_train_losses for tn_train_step: the batch-wide clip of depth_expected not as a launch of its own behind
@@ -463,17 +466,23 @@ int tn_train_losses_clip(const float* s_bins_fine, const float* weights_fine, in
 // cowork: NULL, or the main field's d position pass (tn_field_dpos.h) to run in extra blocks of the bin launch -- only where
 // tn_grid_scatter_takes_cowork says so (the segmented path, no d position of the scatter's own)
 // fold_cowork: NULL, or the launch that ends an iteration's backward (tn_pose_finish.h) to run in the first blocks of the FOLD launch (same condition)
+// fold_adam: NULL, or the fold steps the grid's table itself (tn_adam.h; tn_train_step, the main grid): the bin pass records max |d enc|, a small
+// launch between bin and fold checks the group's small ranges, decides and writes the step's scalars, the fold reads the decision.  Only where
+// tn_fold_adam_takes says so (segmented path, one fold block per bucket, table_grad_is_zero).
 struct DposArgs;
 struct PoseFinishArgs;
+struct FoldAdamHost;
 int tn_grid_scatter_launch(const TnGrid& grid, const float* origins, const float* directions, const float* e_bins, const float* g_enc, int ld,
                            int64_t N, int S, float* d_origins, float* d_directions, void* scratch, hipStream_t stream, float* dense_sum = nullptr,
-                           bool counters_zeroed = false, const DposArgs* cowork = nullptr, const PoseFinishArgs* fold_cowork = nullptr);
+                           bool counters_zeroed = false, const DposArgs* cowork = nullptr, const PoseFinishArgs* fold_cowork = nullptr,
+                           const FoldAdamHost* fold_adam = nullptr);
 bool tn_grid_scatter_takes_cowork(const TnGrid& grid, int64_t P, void* scratch);
+bool tn_fold_adam_takes(const TnGrid& grid, int64_t P, void* scratch);
 // tn_field_bwd_phase with the fold's co-work (tn_train_step); *fold_cowork_taken says whether the fold launch carried it (else the caller launches it)
 int tn_field_bwd_phase_ex(const TnField* field, const float* origins, const float* directions, const int64_t* camera_indices, const float* e_bins,
                           const float* d_density, const float* d_rgb, int64_t N, int32_t S, void* workspace, int64_t workspace_bytes, float* d_origins,
                           float* d_directions, int32_t phases, int32_t level_begin, int32_t level_end, const PoseFinishArgs* fold_cowork,
-                          bool* fold_cowork_taken, tn_stream_t stream);
+                          bool* fold_cowork_taken, tn_stream_t stream, const FoldAdamHost* fold_adam = nullptr);
 int tn_pose_finish_args(const float* pose_adjustment, const uint8_t* frozen, const int64_t* camera_indices, const float* directions_in,
                         const float* d_origins, const float* d_directions, int64_t N, int32_t num_cameras, float* grad_pose, const float* loss_lines,
                         float* losses16, float trans_pen, float rot_pen, float scale, float* reg_out, const float* grads, int32_t num_ranges,
@@ -492,8 +501,8 @@ __device__ __forceinline__ void tn_zero_words(uint32_t* __restrict__ p, int word
 bool tn_grid_scatter_is_binned(const TnGrid& grid, int64_t P, const void* scratch);
 int tn_grid_scatter_bin(const TnGrid& grid, const float* origins, const float* directions, const float* e_bins, const float* g_enc, int ld, int64_t N,
                         int S, float* d_origins, float* d_directions, void* scratch, hipStream_t stream, bool counters_zeroed = false,
-                        const DposArgs* cowork = nullptr);
+                        const DposArgs* cowork = nullptr, const FoldAdamHost* fold_adam = nullptr);
 int tn_grid_scatter_fold(const TnGrid& grid, int64_t P, void* scratch, int level_begin, int level_end, hipStream_t stream,
-                         const PoseFinishArgs* cowork = nullptr);
+                         const PoseFinishArgs* cowork = nullptr, const FoldAdamHost* fold_adam = nullptr);
 int64_t tn_grid_dense_count(const TnGrid& grid, int64_t P);
 int tn_grid_dense_fold(const TnGrid& grid, int64_t P, const float* dense_sum, hipStream_t stream);

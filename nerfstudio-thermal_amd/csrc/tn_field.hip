@@ -1466,7 +1466,7 @@ extern "C" int tn_field_bwd_phase(const TnField* field, const float* origins, co
 int tn_field_bwd_phase_ex(const TnField* field, const float* origins, const float* directions, const int64_t* camera_indices, const float* e_bins,
                           const float* d_density, const float* d_rgb, int64_t N, int32_t S, void* workspace, int64_t workspace_bytes, float* d_origins,
                           float* d_directions, int32_t phases, int32_t level_begin, int32_t level_end, const PoseFinishArgs* fold_cowork,
-                          bool* fold_cowork_taken, tn_stream_t stream) {
+                          bool* fold_cowork_taken, tn_stream_t stream, const FoldAdamHost* fold_adam) {
   if (fold_cowork_taken) *fold_cowork_taken = false;
   if (N == 0) return TN_OK;  // empty batches are valid and touch nothing
   int rc = check_field(field, "tn_field_bwd", true);
@@ -1555,8 +1555,11 @@ int tn_field_bwd_phase_ex(const TnField* field, const float* origins, const floa
     const bool cz = (phases & (TN_BWD_MLP | TN_BWD_COUNTERS_CLEAN)) && level_begin == 0 && level_end == field->grid.num_levels;
     // (the fold's co-work rides only where the d position pass does: the whole segmented scatter in this call)
     const PoseFinishArgs* fcw = (fold_cowork != nullptr && dpos_cowork) ? fold_cowork : nullptr;
+    // (the fold steps the table only where the group's small ranges are final before it: the embedding's finishing jobs ride with the d position
+    // co-work in the bin launch)
+    const FoldAdamHost* fad = (fold_adam != nullptr && dpos_cowork) ? fold_adam : nullptr;
     rc = tn_grid_scatter_launch(sub, origins, directions, e_bins, ws.g_enc + (int64_t)level_begin * 2 * P, TN_LD_LEVEL_MAJOR, N, S, sc_do, sc_dd, ws.scatter, st,
-                                nullptr, cz, dpos_cowork ? &dpos_args : nullptr, fcw);
+                                nullptr, cz, dpos_cowork ? &dpos_args : nullptr, fcw, fad);
     if (fold_cowork_taken && rc == TN_OK) *fold_cowork_taken = fcw != nullptr;
   }
   if (phases & (TN_BWD_SCATTER_BIN | TN_BWD_SCATTER_FOLD)) {

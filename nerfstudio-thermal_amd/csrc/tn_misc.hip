@@ -914,6 +914,10 @@ struct AdamRangesAmp {
   int32_t max_steps[TN_ADAM_MAX_RANGES];  //   lr = exp(lerp(log lr_init, log lr_final, clip((sched_step - lag) / max_steps, 0, 1)))
   int32_t sched_step;                     // scheduler steps on the host's count
   int32_t num_flags, lag_index;           // entries of found_inf; index of the schedule lag in skipped (-1: none)
+  // tn_train_step with the main grid's fold stepping its own table (tn_adam.h): range cond_range is walked only while *cond_word (a device word
+  // written by an earlier launch) does not say TN_FOLD_ADAM_FUSED.  NULL: every range is walked.
+  const float* cond_word;
+  int32_t cond_range;
 };
 // GradScaler.update() by the LAST block of the Adam launch to finish (tn_adam_step_ranges_amp_update): every block has read found_inf and the
 // schedule lag by the time it counts itself done, so the block that sees the full count may rewrite them -- one launch (4.6 us on the serial
@@ -974,6 +978,7 @@ __device__ __forceinline__ void adam_block_done(const ScalerUpdate& su, float* f
 }
 struct SampleCoWork { SamplePixelsArgs a; RaygenArgs g; int blocks; };
 #include "tn_next_sampling.h"
+#include "tn_adam.h"
 // block `bid` of the `nblk` blocks that walk range k of the launch (grid-stride)
 __device__ __forceinline__ void adam_range_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                 const AdamRangesAmp& r, double beta1, double beta2, float eps, const float* __restrict__ inv_scale,
@@ -985,51 +990,38 @@ __device__ __forceinline__ void adam_range_body(float* __restrict__ p, const flo
   const int lag = (skipped != nullptr && r.lag_index >= 0) ? skipped[r.lag_index] : 0;
   const int64_t off = r.off[k], n = r.cnt[k], n4 = n / 4;
   const int64_t stride = (int64_t)nblk * blockDim.x;
+  // (the fold has stepped this range already and stored no gradient for it: uniform over the launch)
+  const bool stepped_by_fold = r.cond_word != nullptr && k == r.cond_range && *r.cond_word == TN_FOLD_ADAM_FUSED;
   if (found_inf != nullptr && found_inf[fl] != 0.0f) {  // uniform over the range's blocks
     if (count_skip && skipped != nullptr && bid == 0 && threadIdx.x == 0) {
       bool first = true;  // ONE count per group and launch, however many ranges of the launch carry the group's flag
       for (int j = 0; j < k; ++j) first = first && r.flag[j] != fl;
       if (first) atomicAdd(&skipped[fl], 1);
     }
-    if (zero_g) {  // the skipped step still consumes its (non-finite) gradients
+    if (zero_g && !stepped_by_fold) {  // the skipped step still consumes its (non-finite) gradients
       for (int64_t i = bid * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride)
         reinterpret_cast<float4*>(gz + off)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (bid == 0 && (int64_t)threadIdx.x < n - n4 * 4) gz[off + n4 * 4 + threadIdx.x] = 0.0f;
     }
     return;
   }
+  if (stepped_by_fold) return;
   if ((int64_t)bid * blockDim.x >= n4 && bid != 0) return;
   __shared__ float s_ns, s_bc;
   __syncthreads();  // (a block that walks several ranges: the previous range's readers are done with s_ns / s_bc)
-  if (threadIdx.x == 0) {
-    const int sk = skipped ? skipped[fl] : 0;
-    const int eff = r.step[k] - sk;
-    const double bc1 = 1.0 - pow(beta1, (double)(eff < 1 ? 1 : eff)), bc2 = 1.0 - pow(beta2, (double)(eff < 1 ? 1 : eff));
-    double lr = r.lr[k];
-    if (r.max_steps[k] > 0) {
-      double t = (double)(r.sched_step - lag) / (double)r.max_steps[k];
-      t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
-      lr = exp(log(r.lr[k]) * (1.0 - t) + log(r.lr_final[k]) * t);
-    }
-    s_ns = (float)(-(lr / bc1));
-    s_bc = (float)sqrt(bc2);
-  }
+  if (threadIdx.x == 0) adam_step_scalars(r.step[k], skipped ? skipped[fl] : 0, r.lr[k], r.lr_final[k], r.max_steps[k], r.sched_step, lag, beta1, beta2, s_ns, s_bc);
   __syncthreads();
-  const float neg_step = s_ns, bc2_sqrt = s_bc, b1 = (float)beta1, b2 = (float)beta2, omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
+  const AdamCoef coef = adam_coef(s_ns, s_bc, beta1, beta2, eps);
   const float is = inv_scale ? *inv_scale : 1.0f;
   float4* p4 = reinterpret_cast<float4*>(p + off);
   const float4* g4 = reinterpret_cast<const float4*>(g + off);
   float4* m4 = reinterpret_cast<float4*>(m + off);
   float4* v4 = reinterpret_cast<float4*>(v + off);
-#define ADAM1(P, G, M, V)                         \
-  {                                               \
-    float g_ = inv_scale ? (G) * is : (G);        \
-    float m_new_ = M * b1 + g_ * omb1;            \
-    float v_new_ = V * b2 + (omb2 * g_) * g_;     \
-    float den_ = sqrtf(v_new_) / bc2_sqrt + eps;  \
-    P = P + neg_step * (m_new_ / den_);           \
-    M = m_new_;                                   \
-    V = v_new_;                                   \
+#define ADAM1(P, G, M, V)                               \
+  {                                                     \
+    float p_ = P, m_ = M, v_ = V;                       \
+    adam1(p_, inv_scale ? (G) * is : (G), m_, v_, coef); \
+    P = p_; M = m_; V = v_;                             \
   }
   typedef float v4f __attribute__((ext_vector_type(4)));
   typedef uint32_t v4u __attribute__((ext_vector_type(4)));
@@ -1122,7 +1114,8 @@ static int adam_ranges_amp_impl(float* params, const float* grads, float* exp_av
                                const int32_t* sched_max_steps, int32_t sched_step, double beta1, double beta2, double eps,
                                const float* inv_scale, const float* found_inf, const int32_t* flag_index, int32_t num_flags, int32_t* skipped,
                                int32_t lag_index, int32_t count_skip, int32_t zero_grads, ScalerUpdate su, tn_stream_t stream,
-                               const TnSampleRays* next = nullptr, bool* next_taken = nullptr, const TnNextSamplingHost* chain = nullptr) {
+                               const TnSampleRays* next = nullptr, bool* next_taken = nullptr, const TnNextSamplingHost* chain = nullptr,
+                               const float* cond_word = nullptr, int cond_range = -1) {
   if (next_taken) *next_taken = false;
   if (num_ranges == 0) return TN_OK;
   TN_REQUIRE(params && grads && exp_avg && exp_avg_sq && offsets && counts && steps && lrs, "tn_adam_step_ranges_amp: null pointer");
@@ -1139,6 +1132,7 @@ static int adam_ranges_amp_impl(float* params, const float* grads, float* exp_av
     const int fl = flag_index ? flag_index[k] : 0;
     TN_REQUIRE(fl >= 0 && fl < num_flags, "tn_adam_step_ranges_amp: flag index %d of range %d outside [0, %d)", fl, k, num_flags);
     if (counts[k] == 0) continue;
+    if (cond_word != nullptr && k == cond_range) { r.cond_word = cond_word; r.cond_range = n; }
     r.off[n] = offsets[k]; r.cnt[n] = counts[k]; r.step[n] = steps[k]; r.lr[n] = lrs[k]; r.flag[n] = fl;
     r.lr_final[n] = lr_finals ? lr_finals[k] : lrs[k];
     r.max_steps[n] = (lr_finals && sched_max_steps) ? sched_max_steps[k] : 0;
@@ -1220,7 +1214,7 @@ static int adam_ranges_amp_impl(float* params, const float* grads, float* exp_av
       return TN_OK;
     }
     FusedAdam fa{};
-    if (mode && mode[0] == '4' && n == 1 && inv_scale == nullptr) {
+    if (mode && mode[0] == '4' && n == 1 && inv_scale == nullptr && r.cond_word == nullptr) {
       // the chain's waves step the head of the (one) range: as many 256-float batches as their service points can take; the range row the rest
       const int64_t nb = r.cnt[0] / 256, W = (int64_t)ns.blocks * 4, trips = tn_cdiv(chain->N, W);
       const char* fs = getenv("TN_FUSED_SITES");  // (tuning aid: batches per ray the host hands to the chain's waves; default = what their stages take)
@@ -1278,13 +1272,13 @@ int tn_adam_step_ranges_amp_update_cw(float* params, const float* grads, float* 
                                       float* found_inf, const int32_t* flag_index, int32_t num_flags, int32_t* skipped, int32_t lag_index,
                                       int32_t count_skip, int32_t zero_grads, float* scale, int32_t* growth_tracker, uint32_t* done_counter,
                                       double growth_factor, double backoff_factor, int32_t growth_interval, const TnSampleRays* next, bool* next_taken,
-                                      tn_stream_t stream, const TnNextSamplingHost* chain, bool su_update) {
+                                      tn_stream_t stream, const TnNextSamplingHost* chain, bool su_update, const float* cond_word, int cond_range) {
   TN_REQUIRE(found_inf && scale && growth_tracker && done_counter && growth_interval >= 1, "tn_adam_step_ranges_amp_update: bad scaler arguments");
   TN_REQUIRE(num_ranges > 0, "tn_adam_step_ranges_amp_update: the fused scale update needs at least one range (use tn_grad_scaler_update otherwise)");
   ScalerUpdate su{scale, growth_tracker, done_counter, (float)growth_factor, (float)backoff_factor, (int32_t)growth_interval};
   return adam_ranges_amp_impl(params, grads, exp_avg, exp_avg_sq, num_ranges, offsets, counts, steps, lrs, lr_finals, sched_max_steps, sched_step, beta1, beta2,
                               eps, inv_scale, found_inf, flag_index, num_flags, skipped, lag_index, count_skip, zero_grads, su_update ? su : ScalerUpdate{}, stream,
-                              next, next_taken, chain);
+                              next, next_taken, chain, cond_word, cond_range);
 }
 
 // GradScaler.update() (torch/amp/grad_scaler.py -> amp_update_scale_cuda_kernel) for the fused step, one thread: backoff when any of the

@@ -4,6 +4,7 @@
 // Every stage is the entry point a caller could also invoke on its own (same kernels, same results, bit for bit).
 #include "tn_common.h"
 #include "tn_pose_finish.h"
+#include "tn_adam.h"
 
 namespace {
 struct EvalWs {
@@ -200,7 +201,8 @@ static int render_rays_train_bwd_impl(const TnPropNet* prop0, const TnPropNet* p
                                       const float* d_weights1, const float* d_weights2, const float* d_density_extra, void* field_workspace,
                                       int64_t field_workspace_bytes, void* prop_workspace0, int64_t prop_workspace_bytes0, void* prop_workspace1,
                                       int64_t prop_workspace_bytes1, float* tmp, float* d_origins, float* d_directions, int32_t prop_enc_saved,
-                                      bool render_bwd_done, const PoseFinishArgs* fold_cowork, bool* fold_cowork_taken, tn_stream_t stream) {
+                                      bool render_bwd_done, const PoseFinishArgs* fold_cowork, bool* fold_cowork_taken, tn_stream_t stream,
+                                      const FoldAdamHost* fold_adam = nullptr) {
   if (fold_cowork_taken) *fold_cowork_taken = false;
   if (N == 0) return TN_OK;
   TN_REQUIRE(field && origins && directions && camera_indices && fwd_out && d_comp && d_weights2 && field_workspace && tmp,
@@ -249,7 +251,7 @@ static int render_rays_train_bwd_impl(const TnPropNet* prop0, const TnPropNet* p
   // (the fold's co-work only on iterations without the proposal networks' backward: their contributions to d origins / d directions arrive with the join below)
   rc = tn_field_bwd_phase_ex(field, o, d, camera_indices, at(TRO_E2), d_dens, d_rgb, N, S2, field_workspace, field_workspace_bytes, d_origins, d_directions,
                              TN_BWD_MLP | TN_BWD_SCATTER | TN_BWD_JOIN | (prop_grad ? TN_BWD_FORK_DPOS : 0), 0, field->grid.num_levels,
-                             prop_grad ? nullptr : fold_cowork, fold_cowork_taken, stream);
+                             prop_grad ? nullptr : fold_cowork, fold_cowork_taken, stream, fold_adam);
   if (prop_grad) { tn_join_n(st, 1); tn_join_n(st, 2); }
   return rc ? rc : (rc0 ? rc0 : rc1);
 }
@@ -356,6 +358,74 @@ extern "C" int tn_train_step(const TnTrainStep* a, tn_stream_t stream) {
     // pixel terms on the RGB columns / the thermal column of the one RGBT composite (models/thermal_nerfacto.py:425-428)
     return rc;
   }
+  // The optimiser ranges as the Adam launches take them: the caller's -- or, where the main grid's fold steps its own table (tn_adam.h; TN_FOLD_ADAM=0:
+  // never), the range that holds the table cut into [before | table | after], the table's piece walked by the Adam launch only when the device-side
+  // decision word says the fold did not.  The range is found by address interval: a table that lies across a range's end is left to the Adam launch.
+  int nr = a->num_ranges, fa_range = -1;
+  int64_t r_off[TN_TRAIN_STEP_MAX_RANGES + 2], r_cnt[TN_TRAIN_STEP_MAX_RANGES + 2];
+  int32_t r_step[TN_TRAIN_STEP_MAX_RANGES + 2], r_ms[TN_TRAIN_STEP_MAX_RANGES + 2], r_fl[TN_TRAIN_STEP_MAX_RANGES + 2];
+  double r_lr[TN_TRAIN_STEP_MAX_RANGES + 2], r_lf[TN_TRAIN_STEP_MAX_RANGES + 2];
+  for (int k = 0; k < nr; ++k) {
+    r_off[k] = a->offsets[k]; r_cnt[k] = a->counts[k]; r_step[k] = a->steps[k]; r_ms[k] = a->sched_max_steps[k]; r_fl[k] = a->flag_index[k];
+    r_lr[k] = a->lrs[k]; r_lf[k] = a->lr_finals[k];
+  }
+  FoldAdamHost fad{};
+  static const bool fold_adam_on = [] { const char* e = getenv("TN_FOLD_ADAM"); return !(e && e[0] == '0'); }();
+  // (field_workspace stands in for the scatter scratch inside it: the plan only asks whether there is one)
+  if (fold_adam_on && nr > 0 && tn_fold_adam_takes(a->field->grid, a->N * (int64_t)a->S2, a->field_workspace)) {
+    const TnGrid& g = a->field->grid;
+    const int64_t tfl = (int64_t)g.num_levels * (2ll << g.log2_hashmap_size);
+    const int64_t tlo = g.table - a->params, thi = tlo + tfl;
+    int holder = -1, touching = 0;
+    for (int k = 0; k < nr; ++k) {
+      const int64_t lo = a->offsets[k], hi = lo + a->counts[k];
+      if (lo < thi && tlo < hi) { ++touching; if (lo <= tlo && thi <= hi) holder = k; }
+    }
+    // (a range that also holds a tensor the next iteration's sampling front reads is stepped in the FIRST Adam launch as a whole: cut, its pieces
+    // would go to both launches and the group's skip would be counted twice -- left unfused)
+    bool holds_chain_read = false;
+    if (holder >= 0) {
+      const float *lo = a->params + a->offsets[holder], *hi = lo + a->counts[holder];
+      const float* reads[] = {a->prop0->grid.table, a->prop0->w0, a->prop0->b0, a->prop0->w1, a->prop0->b1, a->prop1->grid.table, a->prop1->w0,
+                              a->prop1->b0, a->prop1->w1, a->prop1->b1, a->pose_adjustment};
+      for (const float* q : reads) holds_chain_read = holds_chain_read || (q >= lo && q < hi);
+    }
+    int pieces = 0;
+    if (holder >= 0) pieces = (a->offsets[holder] < tlo ? 1 : 0) + (thi < a->offsets[holder] + a->counts[holder] ? 1 : 0);
+    const bool ok = holder >= 0 && touching == 1 && !holds_chain_read && tlo % 4 == 0 && g.table_grad == a->grads + tlo && a->flag_index[holder] >= 0 &&
+                    a->flag_index[holder] < a->num_flags && g.nonfinite_flag == a->found_inf + a->flag_index[holder] && nr + pieces <= TN_TRAIN_STEP_MAX_RANGES &&
+                    a->steps[holder] >= 1;
+    if (ok) {
+      const int h = holder;
+      const int64_t lo = a->offsets[h], hi = lo + a->counts[h];
+      int n = 0;
+      auto put = [&](int src, int64_t o, int64_t c) {
+        r_off[n] = o; r_cnt[n] = c; r_step[n] = a->steps[src]; r_ms[n] = a->sched_max_steps[src]; r_fl[n] = a->flag_index[src];
+        r_lr[n] = a->lrs[src]; r_lf[n] = a->lr_finals[src];
+        ++n;
+      };
+      for (int k = 0; k < a->num_ranges; ++k) {
+        if (k != h) { put(k, a->offsets[k], a->counts[k]); continue; }
+        if (lo < tlo) put(k, lo, tlo - lo);
+        fa_range = n;
+        put(k, tlo, tfl);
+        if (thi < hi) put(k, thi, hi - thi);
+      }
+      nr = n;
+      fad.p = a->params + tlo; fad.m = a->exp_avg + tlo; fad.v = a->exp_avg_sq + tlo;
+      fad.state = a->losses16 + TN_FOLD_ADAM_STATE_SLOT;
+      fad.found_inf = a->found_inf; fad.flag = a->flag_index[h];
+      fad.skipped = a->skipped; fad.lag_index = a->lag_index;
+      fad.step = a->steps[h]; fad.max_steps = a->sched_max_steps[h]; fad.sched_step = a->sched_step;
+      fad.lr = a->lrs[h]; fad.lr_final = a->lr_finals[h]; fad.beta1 = a->beta1; fad.beta2 = a->beta2; fad.eps = (float)a->eps;
+      fad.grads = a->grads;
+      for (int k = 0; k < a->num_check; ++k)
+        if (a->check_flags[k] == fad.flag && a->check_counts[k] > 0) { fad.check_off[fad.ncheck] = a->check_offsets[k]; fad.check_cnt[fad.ncheck] = a->check_counts[k]; ++fad.ncheck; }
+    }
+  }
+  const FoldAdamHost* fold_adam = fa_range >= 0 ? &fad : nullptr;
+  // (the word stays TN_FOLD_ADAM_NONE -- the accumulator block starts from zero -- when the backward below does not arm the fold after all)
+  const float* cond_word = fold_adam ? fad.state + 1 : nullptr;
   // The launch that ends the backward (pose gradient, loss sums, regulariser, GradScaler's check of the small ranges) rides in the first blocks of
   // the main grid's fold launch on iterations without a proposal update (TN_POSE_FINISH_COWORK=0: always a launch of its own)
   PoseFinishArgs pf;
@@ -373,7 +443,7 @@ extern "C" int tn_train_step(const TnTrainStep* a, tn_stream_t stream) {
                                        a->field_workspace, a->field_workspace_bytes, a->prop_grad ? a->prop_workspace0 : nullptr,
                                        a->prop_grad ? a->prop_workspace_bytes0 : 0, a->prop_grad ? a->prop_workspace1 : nullptr,
                                        a->prop_grad ? a->prop_workspace_bytes1 : 0, a->bwd_tmp, a->d_origins, a->d_directions, a->prop_grad ? 1 : 0,
-                                       fuse_render, pf_cowork ? &pf : nullptr, &pf_taken, stream)))
+                                       fuse_render, pf_cowork ? &pf : nullptr, &pf_taken, stream, fold_adam)))
     return rc;
   if (!pf_taken) {
     if ((rc = tn_pose_bwd_finish_check(a->pose_adjustment, a->frozen, a->camera_indices, a->directions_in, a->d_origins, a->d_directions, a->N,
@@ -390,40 +460,44 @@ extern "C" int tn_train_step(const TnTrainStep* a, tn_stream_t stream) {
   const char* nse = getenv("TN_NEXT_SAMPLING");
   bool chain = nx != nullptr && a->next_sample != nullptr && a->next_sample->num_rays == a->N && a->next_sample->camera_indices != nullptr && a->N % 4 == 0 &&
                tn_next_sampling_supported(a->S0, a->S1, a->S2) && !(nse && nse[0] == '0');
-  int first[TN_TRAIN_STEP_MAX_RANGES], nfirst = 0, rest[TN_TRAIN_STEP_MAX_RANGES], nrest = 0;
+  int first[TN_TRAIN_STEP_MAX_RANGES + 2], nfirst = 0, rest[TN_TRAIN_STEP_MAX_RANGES + 2], nrest = 0;
   if (chain) {
     const float* reads[] = {a->prop0->grid.table, a->prop0->w0, a->prop0->b0, a->prop0->w1, a->prop0->b1, a->prop1->grid.table, a->prop1->w0,
                             a->prop1->b0, a->prop1->w1, a->prop1->b1, a->pose_adjustment};
-    for (int k = 0; k < a->num_ranges; ++k) {
-      const float *lo = a->params + a->offsets[k], *hi = lo + a->counts[k];
+    for (int k = 0; k < nr; ++k) {
+      const float *lo = a->params + r_off[k], *hi = lo + r_cnt[k];
       bool hit = false;
       for (const float* q : reads) hit = hit || (q >= lo && q < hi);
-      if (hit) first[nfirst++] = k; else if (a->counts[k] > 0) rest[nrest++] = k;
+      if (hit) first[nfirst++] = k; else if (r_cnt[k] > 0) rest[nrest++] = k;
     }
     chain = nrest > 0 && nfirst > 0;  // (nothing left to run beside, or nothing to step first: one launch, no chain)
   }
   if (!chain) {
-    rc = tn_adam_step_ranges_amp_update_cw(a->params, a->grads, a->exp_avg, a->exp_avg_sq, a->num_ranges, a->offsets, a->counts, a->steps, a->lrs, a->lr_finals,
-                                           a->sched_max_steps, a->sched_step, a->beta1, a->beta2, a->eps, nullptr, a->found_inf, a->flag_index, a->num_flags,
-                                           a->skipped, a->lag_index, 1, 1, a->scale, a->growth_tracker, a->done_counter, a->growth_factor, a->backoff_factor,
-                                           a->growth_interval, a->next_sample, &taken, stream);
+    rc = tn_adam_step_ranges_amp_update_cw(a->params, a->grads, a->exp_avg, a->exp_avg_sq, nr, r_off, r_cnt, r_step, r_lr, r_lf, r_ms, a->sched_step, a->beta1,
+                                           a->beta2, a->eps, nullptr, a->found_inf, r_fl, a->num_flags, a->skipped, a->lag_index, 1, 1, a->scale,
+                                           a->growth_tracker, a->done_counter, a->growth_factor, a->backoff_factor, a->growth_interval, a->next_sample, &taken,
+                                           stream, nullptr, true, cond_word, fa_range);
   } else {
+    int cond_at = -1;  // (where the table's piece landed in the launch's list)
     auto sub = [&](const int* idx, int n, int64_t* o, int64_t* c, int32_t* s, double* l, double* lf, int32_t* ms, int32_t* fl) {
+      cond_at = -1;
       for (int i = 0; i < n; ++i) {
         const int k = idx[i];
-        o[i] = a->offsets[k]; c[i] = a->counts[k]; s[i] = a->steps[k]; l[i] = a->lrs[k]; lf[i] = a->lr_finals[k]; ms[i] = a->sched_max_steps[k]; fl[i] = a->flag_index[k];
+        o[i] = r_off[k]; c[i] = r_cnt[k]; s[i] = r_step[k]; l[i] = r_lr[k]; lf[i] = r_lf[k]; ms[i] = r_ms[k]; fl[i] = r_fl[k];
+        if (k == fa_range) cond_at = i;
       }
     };
-    int64_t o[TN_TRAIN_STEP_MAX_RANGES], c[TN_TRAIN_STEP_MAX_RANGES];
-    int32_t s[TN_TRAIN_STEP_MAX_RANGES], ms[TN_TRAIN_STEP_MAX_RANGES], fl[TN_TRAIN_STEP_MAX_RANGES];
-    double l[TN_TRAIN_STEP_MAX_RANGES], lf[TN_TRAIN_STEP_MAX_RANGES];
+    int64_t o[TN_TRAIN_STEP_MAX_RANGES + 2], c[TN_TRAIN_STEP_MAX_RANGES + 2];
+    int32_t s[TN_TRAIN_STEP_MAX_RANGES + 2], ms[TN_TRAIN_STEP_MAX_RANGES + 2], fl[TN_TRAIN_STEP_MAX_RANGES + 2];
+    double l[TN_TRAIN_STEP_MAX_RANGES + 2], lf[TN_TRAIN_STEP_MAX_RANGES + 2];
     rc = TN_OK;
     // (the first launch reads found_inf / the schedule lag like the second; GradScaler.update() comes with the second.  It also carries the batch's
     // pixel sampling + ray generation in its co-work row, as the one optimiser launch of other iterations does)
     sub(first, nfirst, o, c, s, l, lf, ms, fl);
     rc = tn_adam_step_ranges_amp_update_cw(a->params, a->grads, a->exp_avg, a->exp_avg_sq, nfirst, o, c, s, l, lf, ms, a->sched_step, a->beta1, a->beta2, a->eps,
                                            nullptr, a->found_inf, fl, a->num_flags, a->skipped, a->lag_index, 1, 1, a->scale, a->growth_tracker, a->done_counter,
-                                           a->growth_factor, a->backoff_factor, a->growth_interval, a->next_sample, &taken, stream, nullptr, false);
+                                           a->growth_factor, a->backoff_factor, a->growth_interval, a->next_sample, &taken, stream, nullptr, false,
+                                           cond_at >= 0 ? cond_word : nullptr, cond_at);
     if (!rc && !taken) rc = tn_sample_rays_args(a->next_sample, stream);  // (no range of the first launch was live: the batch as a launch of its own)
     if (!rc) {
       taken = true;
@@ -441,7 +515,8 @@ extern "C" int tn_train_step(const TnTrainStep* a, tn_stream_t stream) {
       sub(rest, nrest, o, c, s, l, lf, ms, fl);
       rc = tn_adam_step_ranges_amp_update_cw(a->params, a->grads, a->exp_avg, a->exp_avg_sq, nrest, o, c, s, l, lf, ms, a->sched_step, a->beta1, a->beta2, a->eps,
                                              nullptr, a->found_inf, fl, a->num_flags, a->skipped, a->lag_index, 1, 1, a->scale, a->growth_tracker, a->done_counter,
-                                             a->growth_factor, a->backoff_factor, a->growth_interval, nullptr, nullptr, stream, &h, true);
+                                             a->growth_factor, a->backoff_factor, a->growth_interval, nullptr, nullptr, stream, &h, true,
+                                             cond_at >= 0 ? cond_word : nullptr, cond_at);
       if (!rc && a->next_sampling_taken) *a->next_sampling_taken = 1;
     }
   }

@@ -16,6 +16,8 @@
 #include "tn_common.h"
 #include "tn_field_dpos.h"
 #include "tn_pose_finish.h"
+#include "tn_adam.h"
+#include <float.h>
 #include <stdlib.h>
 #include <stdio.h>
 #include <vector>
@@ -735,7 +737,33 @@ struct SegK {
   uint32_t merge_mask;
   uint32_t segc;    // segments (bin blocks) per fold block
   uint32_t chunks;  // fold blocks per bucket = ceil(NB / segc)
+  uint32_t* wmax;   // [TN_MAX_LEVELS][NB][BIN_THREADS / 64] bit pattern of max |d enc| per wave of the bin launch (the fold's overflow guard, tn_adam.h)
 };
+// The step's scalars for a fold that steps its table (tn_adam.h): one extra block of the bin launch evaluates them beside the pass -- 15 us of
+// double-precision pow / log / exp in one lane, ~8 us with the four terms on four waves, which as a launch of its own would stand on the serial chain.
+struct FoldAdamScal {
+  float* state;  // NULL: no such block
+  const int32_t* skipped;
+  int flag, lag_index, step, max_steps, sched_step;
+  double lr, lr_final, beta1, beta2;
+};
+__device__ __forceinline__ void fold_adam_scalars_block(const FoldAdamScal& a, double* s_term /* 4 doubles of LDS */) {
+  if ((threadIdx.x & 63) == 0 && threadIdx.x < 256) {
+    const int w = threadIdx.x >> 6;
+    const int sk = a.skipped ? a.skipped[a.flag] : 0;
+    const int lag = (a.skipped != nullptr && a.lag_index >= 0) ? a.skipped[a.lag_index] : 0;
+    const double t = a.max_steps > 0 ? adam_sched_t(a.max_steps, a.sched_step, lag) : 0.0;
+    if (w < 2) s_term[w] = adam_bias_correction(w == 0 ? a.beta1 : a.beta2, a.step, sk);
+    else if (a.max_steps > 0) s_term[w] = adam_log_lr_term(w == 2 ? a.lr : a.lr_final, w == 2 ? 1.0 - t : t);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float ns, bc;
+    adam_scalars_finish(s_term[0], s_term[1], a.max_steps > 0 ? exp(s_term[2] + s_term[3]) : a.lr, ns, bc);  // (adam_step_scalars, term by term)
+    a.state[2] = ns;
+    a.state[3] = bc;
+  }
+}
 #define SEG_CAP (BIN_THREADS * 8)
 // a block's region of a level: its records, every bucket's run at an EVEN offset (one unused slot behind an odd run) -- the fold reads PAIRS
 #define SEG_REGION (SEG_CAP + TN_BIN_MAX_SLICES)
@@ -747,7 +775,7 @@ template <bool WANT_DPOS>
 __global__ void __launch_bounds__(BIN_THREADS, 4) k_seg_bin(GridK g, const float* __restrict__ origins, const float* __restrict__ directions,
                                                          const float* __restrict__ e_bins, const float* __restrict__ g_enc, int ld, int64_t N, int S,
                                                          float* __restrict__ d_origins, float* __restrict__ d_directions, int level_groups, SegK sk,
-                                                         DposArgs cw, int cw_blocks) {
+                                                         DposArgs cw, int cw_blocks, FoldAdamScal fs) {
   __shared__ uint32_t s_cnt[TN_BIN_MAX_SLICES];      // records per bucket of the level being ranked (zero between levels)
   __shared__ uint32_t s_off[TN_BIN_MAX_SLICES + 1];  // exclusive prefix; [nslices] = the level's record count
   __shared__ __attribute__((aligned(16))) uint16_t s_i16[SEG_REGION];
@@ -757,6 +785,10 @@ __global__ void __launch_bounds__(BIN_THREADS, 4) k_seg_bin(GridK g, const float
   // queue costs an iteration more than the pass takes (tn_field.hip).  (Spread evenly through the rows instead: no gain at all, 0.623 vs
   // 0.616-0.622 ms per step without; at the row ends 0.6115 vs 0.6239.)
   const unsigned bx = blockIdx.x;
+  if (!WANT_DPOS && bx >= sk.NB + (unsigned)cw_blocks) {  // (one block behind the co-work blocks of every row, when fs.state is set)
+    if (blockIdx.y == 0) fold_adam_scalars_block(fs, reinterpret_cast<double*>(s_val));
+    return;
+  }
   if (!WANT_DPOS && bx >= sk.NB) {
     field_dpos_body(cw, blockIdx.y * (unsigned)cw_blocks + (bx - sk.NB), (unsigned)cw_blocks * gridDim.y, reinterpret_cast<float*>(s_val),
                     reinterpret_cast<int*>(s_cnt));
@@ -790,6 +822,7 @@ __global__ void __launch_bounds__(BIN_THREADS, 4) k_seg_bin(GridK g, const float
   __syncthreads();
   const uint32_t smask = (1u << sk.slice_log2) - 1u;
   float dpx = 0.f, dpy = 0.f, dpz = 0.f;
+  uint32_t gmax = 0u;  // enc_max: bit pattern of max |d enc| over the live samples this thread reads (tn_adam.h: the fold's overflow guard)
 #pragma unroll 1
   for (int li = 0; li < nlev; ++li) {
     const int l = blockIdx.y + li * level_groups;
@@ -838,6 +871,7 @@ __global__ void __launch_bounds__(BIN_THREADS, 4) k_seg_bin(GridK g, const float
     } else if (live) {
       gv = *reinterpret_cast<const float2*>(ld > 0 ? g_enc + p * ld + 2 * l : g_enc + (int64_t)l * 2 * P + 2 * p);
     }
+    if (!WANT_DPOS && fs.state != nullptr) gmax = max(gmax, max(__float_as_uint(gv.x) & 0x7fffffffu, __float_as_uint(gv.y) & 0x7fffffffu));
     if (WANT_DPOS) {
       // d enc / d position from the corner values: s_k = <g, table[corner k]>, then the three one-sided differences of the trilinear form
       const float2* tb = g.table + (size_t)l * g.tsize;
@@ -892,6 +926,13 @@ __global__ void __launch_bounds__(BIN_THREADS, 4) k_seg_bin(GridK g, const float
     // (no barrier here: the next level's ranking touches s_cnt only, which the prefix wave left zeroed before the barrier above; its staging
     // waits behind two more barriers, which nobody passes before everybody has finished this copy)
   }
+  if (!WANT_DPOS && fs.state != nullptr) {
+    // one word per wave, reduced by the launch behind this one: an atomic max on ONE word (12 k waves, same-address atomics execute one after the
+    // other) made this launch 15 us longer
+#pragma unroll
+    for (int o2 = 32; o2 >= 1; o2 >>= 1) gmax = max(gmax, (uint32_t)__shfl_xor((int)gmax, o2, 64));
+    if (lane == 0) sk.wmax[((size_t)blockIdx.y * sk.NB + bx) * (BIN_THREADS / 64) + wv] = gmax;
+  }
   if (WANT_DPOS) {
     float wxg, wyg, wzg;
     tn_contract_bwd(c, dpx, dpy, dpz, wxg, wyg, wzg);
@@ -923,8 +964,25 @@ __global__ void __launch_bounds__(BIN_THREADS, 4) k_seg_bin(GridK g, const float
 // waves walk the segments -- PACK segments per wave and iteration (64 / PACK lanes each: a segment of a fine main-grid level holds ~32 records,
 // of a proposal grid ~60, of a merged coarse level a handful; PACK follows the block's average), lane = record, two loads per record, two
 // double-precision LDS adds (see k_grid_fold) -- and the bucket's image goes to the table gradient as in k_grid_fold.
+//
+// ADAM (tn_train_step's main grid, tn_adam.h): the block that has folded a bucket holds the final gradient of its slots in LDS, so it steps them
+// itself -- the gradient never goes to HBM (stored here, read back and zeroed by the Adam launch: 3 x 67 MB per iteration at 16 x 2^19 slots), and
+// the streaming of p / m / v of one resident block runs beside the LDS adds of the other.  Whether it does is decided on the device, by the launch
+// between bin and fold (k_fold_adam_prepare): fa.state[1] is what this launch and the Adam launch both read.  Anything but FUSED: every line below
+// is the unfused fold's.  FUSED with found_inf raised (final by now: prepare has checked the group's other ranges, and no finite batch within the
+// guard gives a non-finite slot): the iteration is skipped, nothing to fold.  A bucket without records still decays its moments.
+struct FoldAdamK {
+  float2 *p, *m, *v;       // [L][tsize], as g.grad
+  const float* state;      // tn_adam.h
+  const float* found_inf;  // the table's group's entry
+  float b1, b2, omb1, omb2, eps;
+};
+#ifndef FOLD_ADAM_BATCH
+#define FOLD_ADAM_BATCH 2  // slot PAIRS (16 bytes of p, m and v each) in flight per thread: the kernel stays at 64 registers (two blocks per CU)
+#endif
+template <bool ADAM>
 __global__ void __launch_bounds__(FOLD_THREADS, 8) k_seg_fold(GridK g, SegK sk, uint32_t level_begin, uint32_t grad_zero_promise, PoseFinishArgs pf,
-                                                           uint32_t pf_blocks) {
+                                                           uint32_t pf_blocks, FoldAdamK fa) {
   extern __shared__ __attribute__((aligned(16))) float s_mem[];  // [slots] double x, [slots] double y, then [segc] headers, [segc] running counts, 16 words
   // co-work blocks (the FIRST pf_blocks, a multiple of 8 so that the fold blocks keep their XCDs): the launch that ends the iteration's backward
   // (tn_pose_finish.h) -- short latency chains beside a pass that is bound by its LDS adds, instead of 9 us in line behind it
@@ -932,6 +990,8 @@ __global__ void __launch_bounds__(FOLD_THREADS, 8) k_seg_fold(GridK g, SegK sk, 
     if ((int)blockIdx.x < pf.total_blocks) pose_finish_body(pf, (int)blockIdx.x);
     return;
   }
+  const bool fused = ADAM && fa.state[1] == TN_FOLD_ADAM_FUSED;  // (uniform over the launch)
+  if (fused && *fa.found_inf != 0.0f) return;
   const uint32_t fb = blockIdx.x - pf_blocks;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t ns = (uint32_t)sk.nslices, per_level = ns * sk.chunks;
@@ -969,7 +1029,7 @@ __global__ void __launch_bounds__(FOLD_THREADS, 8) k_seg_fold(GridK g, SegK sk, 
   uint32_t total = 0;  // pairs
 #pragma unroll
   for (int w = 0; w < FOLD_THREADS / 64; ++w) total += s_tot[w];
-  if (total == 0) return;  // whole block leaves together
+  if (total == 0 && !fused) return;  // whole block leaves together
   const bool split = sk.chunks > 1;
   const bool store = grad_zero_promise && !split;
   // The LDS adds are what this kernel's time is made of, and a ds_add_f64 costs the same with 20 lanes enabled as with 64 (one segment per wave
@@ -979,7 +1039,7 @@ __global__ void __launch_bounds__(FOLD_THREADS, 8) k_seg_fold(GridK g, SegK sk, 
   // one 16-byte value pair per lane), stepping over segment boundaries in the middle of a step (per lane: segment, offset inside it; a boundary
   // costs the lane one header read from LDS).  Equal shares in RECORDS: with equal shares in segments the slowest of the 64 groups had ~17 % more
   // than the mean.  Pairs: the walk (~40 vector instructions per step) was a quarter of the kernel with one record per lane and step.
-  const uint32_t avg = 2u * total / nseg;
+  const uint32_t avg = 2u * total / max(nseg, 1u);
   const int gw_log2 = avg >= 256 ? 6 : (avg >= 96 ? 5 : 4);
   const uint32_t gw = 1u << gw_log2, ngroups = FOLD_THREADS >> gw_log2;
   const uint32_t share = (((total + ngroups - 1) / ngroups) + gw - 1) & ~(gw - 1);
@@ -1066,6 +1126,51 @@ __global__ void __launch_bounds__(FOLD_THREADS, 8) k_seg_fold(GridK g, SegK sk, 
 #if SEG_FOLD_ABLATE & 4  // (timing experiments: no flush)
   if (total != 0xffffffffu) return;
 #endif
+  if (fused) {
+    // adam_range_body's walk over the bucket's slots, two slots (16 bytes) per lane, with the gradient taken from the image: g = (float)double sum
+    // exactly as the flush below forms it; an entry with g | m | v == 0 is not written; p cached, the moments non-temporal.
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    const AdamCoef coef{fa.state[2], fa.state[3], fa.b1, fa.b2, fa.omb1, fa.omb2, fa.eps};
+    const size_t tb = (size_t)l * g.tsize + ((size_t)sl << sk.slice_log2);  // (even: a bucket holds at least two slots)
+    float4* p4 = reinterpret_cast<float4*>(fa.p + tb);
+    v4f* m4 = reinterpret_cast<v4f*>(fa.m + tb);
+    v4f* v4 = reinterpret_cast<v4f*>(fa.v + tb);
+    const uint32_t pairs = slots >> 1;
+    for (uint32_t q0 = 0; q0 < pairs; q0 += FOLD_THREADS * FOLD_ADAM_BATCH) {
+      v4f gg[FOLD_ADAM_BATCH], mm[FOLD_ADAM_BATCH], vv[FOLD_ADAM_BATCH];
+      float4 pq[FOLD_ADAM_BATCH];
+#pragma unroll
+      for (int u = 0; u < FOLD_ADAM_BATCH; ++u) {  // every load first, then the arithmetic and the stores
+        const uint32_t q = q0 + u * FOLD_THREADS + tid;
+        if (q < pairs) {
+          // (the parameters with the moments, not behind the test below: one round trip per block instead of two, while the other resident block
+          // of the CU is still in its walk -- read, never written, for entries that turn out untouched)
+          pq[u] = p4[q];
+          mm[u] = __builtin_nontemporal_load(m4 + q);
+          vv[u] = __builtin_nontemporal_load(v4 + q);
+          gg[u] = v4f{(float)ax[2 * q], (float)ay[2 * q], (float)ax[2 * q + 1], (float)ay[2 * q + 1]};
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < FOLD_ADAM_BATCH; ++u) {
+        const uint32_t q = q0 + u * FOLD_THREADS + tid;
+        if (q >= pairs) continue;
+        const v4u zb = __builtin_bit_cast(v4u, gg[u]) | __builtin_bit_cast(v4u, mm[u]) | __builtin_bit_cast(v4u, vv[u]);
+        if ((zb.x | zb.y | zb.z | zb.w) == 0u) continue;
+        float4 pp = pq[u];
+        float m0 = mm[u].x, m1 = mm[u].y, m2 = mm[u].z, m3 = mm[u].w, v0 = vv[u].x, v1 = vv[u].y, v2 = vv[u].z, v3 = vv[u].w;
+        adam1(pp.x, gg[u].x, m0, v0, coef);
+        adam1(pp.y, gg[u].y, m1, v1, coef);
+        adam1(pp.z, gg[u].z, m2, v2, coef);
+        adam1(pp.w, gg[u].w, m3, v3, coef);
+        p4[q] = pp;
+        __builtin_nontemporal_store(v4f{m0, m1, m2, m3}, m4 + q);
+        __builtin_nontemporal_store(v4f{v0, v1, v2, v3}, v4 + q);
+      }
+    }
+    return;
+  }
   float2* dst = g.grad + (size_t)l * g.tsize + ((size_t)sl << sk.slice_log2);
   for (uint32_t tt = 0; tt < slots; tt += FOLD_THREADS * 8) {
     float2 w[8], cv[8];
@@ -1094,6 +1199,69 @@ __global__ void __launch_bounds__(FOLD_THREADS, 8) k_seg_fold(GridK g, SegK sk, 
         if (g.nonfinite != nullptr && ((w[u].x - w[u].x) + (w[u].y - w[u].y)) != 0.0f) *g.nonfinite = 1.0f;
       }
     }
+  }
+}
+
+// The launch between the bin pass and a fold that may step its table (one block): what has to be FINAL before the fold starts, since nothing
+// inside a launch orders one block behind another.
+//  - GradScaler's check of the group's other ranges (MLP weights, embedding: a few 10^4 floats, final when the bin launch has ended) raises
+//    found_inf[flag] -- the table itself cannot make the group's gradient non-finite on a fused iteration (next point).
+//  - The decision.  A slot's final value is a sum of at most 8 P records w * d enc with 0 <= w <= 1, so max |d enc| <= FLT_MAX / (8 P) (limit)
+//    keeps every slot inside float range; a NaN or an inf among the values fails the comparison too.  Then the iteration takes the unfused
+//    launches, which check the final values.
+//  - neg_step / bc2_sqrt of the table's range, from the expressions adam_range_body's thread 0 evaluates (skipped[] and the schedule lag change
+//    only in the Adam launch behind the fold).
+struct FoldAdamPrep {
+  const float* grads;
+  int ncheck;
+  int64_t off[TN_TRAIN_STEP_MAX_RANGES], cnt[TN_TRAIN_STEP_MAX_RANGES];
+  float* found_inf_flag;  // the group's entry
+  float* state;
+  float limit;
+  const uint32_t* wmax;  // the bin launch's per-wave maxima (SegK::wmax: rows of NB x waves words, `rows` level groups written)
+  uint32_t row_words, row_stride, rows;
+};
+__global__ void __launch_bounds__(1024) k_fold_adam_prepare(FoldAdamPrep a) {
+  __shared__ int s_bad;
+  __shared__ uint32_t s_max;
+  if (threadIdx.x == 0) { s_bad = 0; s_max = 0u; }
+  __syncthreads();
+  // (one block, so the loads of a thread go out eight at a time: one at a time the ~25 round trips made this launch 11-18 us)
+  bool bad = false;
+  for (int k = 0; k < a.ncheck; ++k) {
+    const float* base = a.grads + a.off[k];
+    for (int64_t i0 = threadIdx.x; i0 < a.cnt[k]; i0 += 8 * (int64_t)blockDim.x) {
+      float x[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { const int64_t i = i0 + u * (int64_t)blockDim.x; x[u] = i < a.cnt[k] ? base[i] : 0.0f; }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) bad = bad || ((x[u] - x[u]) != 0.0f);
+    }
+  }
+  uint32_t mx = 0u;
+  for (uint32_t r = 0; r < a.rows; ++r) {
+    const uint32_t* row = a.wmax + (size_t)r * a.row_stride;
+    for (uint32_t i0 = threadIdx.x; i0 < a.row_words; i0 += 8 * blockDim.x) {
+      uint32_t w[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { const uint32_t i = i0 + u * blockDim.x; w[u] = i < a.row_words ? row[i] : 0u; }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) mx = max(mx, w[u]);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
+  const bool wave_bad = __any(bad);  // (the vote with every lane active: inside the branch below only lane 0 would be asked)
+  if ((threadIdx.x & 63) == 0) {
+    if (wave_bad) s_bad = 1;
+    atomicMax(&s_max, mx);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (s_bad) *a.found_inf_flag = 1.0f;
+    const float enc_max = __uint_as_float(s_max);
+    a.state[0] = enc_max;
+    a.state[1] = (enc_max <= a.limit) ? TN_FOLD_ADAM_FUSED : TN_FOLD_ADAM_FELL_BACK;
   }
 }
 
@@ -1160,7 +1328,11 @@ static int seg_plan(const TnGrid& grid, int64_t P, void* scratch, SegK& sk) {
   sk.val = reinterpret_cast<float2*>(base);
   sk.idx = reinterpret_cast<uint16_t*>(base + recs * 8);
   sk.hdr = reinterpret_cast<uint32_t*>(base + recs * 10);
-  TN_REQUIRE(256 + recs * 10 + (int64_t)L * sk.nslices * NB * 4 <= tn_scatter_scratch_bytes(P, L), "tn_grid_scatter: segmented layout exceeds the scatter scratch");
+  // (the per-wave maxima of a bin launch whose fold steps its table sit behind the headers, sized for one row per level: a few KB.  Everything
+  // here lives inside tn_scatter_scratch_bytes(P, L), which is sized for the binned path's 16 records per sample and level -- see there)
+  const int64_t hdr_end = 256 + recs * 10 + (int64_t)L * sk.nslices * NB * 4, wmax_bytes = (int64_t)TN_MAX_LEVELS * NB * (BIN_THREADS / 64) * 4;
+  sk.wmax = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(scratch) + hdr_end);
+  TN_REQUIRE(hdr_end + wmax_bytes <= tn_scatter_scratch_bytes(P, L), "tn_grid_scatter: segmented layout exceeds the scatter scratch");
   for (int l = 0; l < L; ++l)
     if (grid.res[l] <= (float)merge_res()) sk.merge_mask |= 1u << l;
   // fold blocks: a bucket's bin blocks are cut into chunks of `segc` (<= 1024 = FOLD_THREADS: one header per thread).  A grid with many buckets
@@ -1173,6 +1345,13 @@ static int seg_plan(const TnGrid& grid, int64_t P, void* scratch, SegK& sk) {
   sk.segc = (uint32_t)segc;
   sk.chunks = (uint32_t)tn_cdiv(NB, segc);
   return TN_OK;
+}
+// rows of the segmented bin launch: enough resident work for every CU -- the levels are split over blockIdx.y while the batch alone gives fewer
+// than ~6 blocks per CU
+static int seg_level_groups(int L, uint32_t NB) {
+  int level_groups = 1;
+  while (level_groups < L && (int64_t)NB * level_groups < 256 * 6) level_groups *= 2;
+  return std::min(level_groups, L);
 }
 static int fold_chunk_sparse() { static int r = env_int("TN_SCATTER_SPARSE_CHUNK", 16384, 1024, 32768) & ~1023; return r; }
 // Same-cell runs of consecutive samples are summed before they are written (bin_run_sums) on every level whose resolution is at most this.
@@ -1229,22 +1408,22 @@ void tn_grid_scatter_counters(const TnGrid& grid, int64_t P, void* scratch, uint
 }
 
 int tn_grid_scatter_bin(const TnGrid& grid, const float* origins, const float* directions, const float* e_bins, const float* g_enc, int ld, int64_t N,
-                        int S, float* d_origins, float* d_directions, void* scratch, hipStream_t stream, bool counters_zeroed, const DposArgs* cowork) {
+                        int S, float* d_origins, float* d_directions, void* scratch, hipStream_t stream, bool counters_zeroed, const DposArgs* cowork,
+                        const FoldAdamHost* fold_adam) {
   const int64_t P = N * (int64_t)S;
   const int L = grid.num_levels;
+  TN_REQUIRE(fold_adam == nullptr || (d_origins == nullptr && tn_fold_adam_takes(grid, P, scratch)), "tn_grid_scatter: the fold does not step this table (tn_fold_adam_takes)");
   if (seg_mode()) {
     SegK sk;
     int rc = seg_plan(grid, P, scratch, sk);
     if (rc) return rc;
     GridK gk = make_gridk(grid);
     const int blocks = (int)sk.NB;
-    int level_groups = 1;  // enough resident work for every CU: split the levels over blockIdx.y while the batch alone gives fewer than ~6 blocks per CU
-    while (level_groups < L && (int64_t)blocks * level_groups < 256 * 6) level_groups *= 2;
-    level_groups = std::min(level_groups, L);
+    const int level_groups = seg_level_groups(L, sk.NB);
     TN_REQUIRE(cowork == nullptr || d_origins == nullptr, "tn_grid_scatter: co-work only beside a bin pass without a d position path of its own");
     if (d_origins != nullptr) {
       hipLaunchKernelGGL(k_seg_bin<true>, dim3(blocks, level_groups), dim3(BIN_THREADS), 0, stream, gk, origins, directions, e_bins, g_enc, ld, N, S, d_origins,
-                         d_directions, level_groups, sk, DposArgs{}, 0);
+                         d_directions, level_groups, sk, DposArgs{}, 0, FoldAdamScal{});
     } else {
       // co-work: one tile of 32 samples per wave, BIN_THREADS / 64 tiles per block, spread over the rows of the grid
       int cw_blocks = 0;
@@ -1252,8 +1431,13 @@ int tn_grid_scatter_bin(const TnGrid& grid, const float* origins, const float* d
         const int64_t tiles = tn_cdiv(cowork->N * (int64_t)cowork->S, 32);
         cw_blocks = (int)std::min<int64_t>(tn_cdiv(tn_cdiv(tiles, BIN_THREADS / 64), level_groups), 2048);
       }
-      hipLaunchKernelGGL(k_seg_bin<false>, dim3(blocks + cw_blocks, level_groups), dim3(BIN_THREADS), 0, stream, gk, origins, directions, e_bins, g_enc, ld, N, S,
-                         d_origins, d_directions, level_groups, sk, cowork ? *cowork : DposArgs{}, cw_blocks);
+      FoldAdamScal fs{};
+      if (fold_adam != nullptr) {
+        const FoldAdamHost& h = *fold_adam;
+        fs = FoldAdamScal{h.state, h.skipped, h.flag, h.lag_index, h.step, h.max_steps, h.sched_step, h.lr, h.lr_final, h.beta1, h.beta2};
+      }
+      hipLaunchKernelGGL(k_seg_bin<false>, dim3(blocks + cw_blocks + (fold_adam ? 1 : 0), level_groups), dim3(BIN_THREADS), 0, stream, gk, origins, directions,
+                         e_bins, g_enc, ld, N, S, d_origins, d_directions, level_groups, sk, cowork ? *cowork : DposArgs{}, cw_blocks, fs);
     }
     TN_CHECK_LAUNCH("tn_grid_scatter(bin, segmented)");
     return TN_OK;
@@ -1288,22 +1472,47 @@ int tn_grid_scatter_bin(const TnGrid& grid, const float* origins, const float* d
 }
 
 // fold of levels [level_begin, level_end) of a grid whose records tn_grid_scatter_bin has written (same grid, P and scratch)
-int tn_grid_scatter_fold(const TnGrid& grid, int64_t P, void* scratch, int level_begin, int level_end, hipStream_t stream, const PoseFinishArgs* cowork) {
+int tn_grid_scatter_fold(const TnGrid& grid, int64_t P, void* scratch, int level_begin, int level_end, hipStream_t stream, const PoseFinishArgs* cowork,
+                         const FoldAdamHost* fold_adam) {
   const int L = grid.num_levels;
   TN_REQUIRE(level_begin >= 0 && level_begin < level_end && level_end <= L, "tn_grid_scatter_fold: bad level range");
   TN_REQUIRE(cowork == nullptr || seg_mode(), "tn_grid_scatter_fold: co-work needs the segmented path (tn_grid_scatter_takes_cowork)");
+  TN_REQUIRE(fold_adam == nullptr || (level_begin == 0 && level_end == L && fold_adam->p == grid.table && tn_fold_adam_takes(grid, P, scratch)),
+             "tn_grid_scatter_fold: the fold does not step this table (tn_fold_adam_takes, the whole grid in one launch)");
   if (seg_mode()) {
     SegK sk;
     int rc = seg_plan(grid, P, scratch, sk);
     if (rc) return rc;
     GridK gk = make_gridk(grid);
     const size_t shmem = (size_t)(2u << sk.slice_log2) * sizeof(double) + (size_t)sk.segc * 8 + (FOLD_THREADS / 64) * 4;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_seg_fold), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)((2u << TN_BIN_SLICE_LOG2) * sizeof(double) + 1024 * 8 + (FOLD_THREADS / 64) * 4));
+    const int max_shmem = (int)((2u << TN_BIN_SLICE_LOG2) * sizeof(double) + 1024 * 8 + (FOLD_THREADS / 64) * 4);
     const uint32_t nblk = (uint32_t)(level_end - level_begin) * (uint32_t)sk.nslices * sk.chunks;
     const uint32_t pfb = cowork ? ((uint32_t)cowork->total_blocks + 7u) & ~7u : 0u;
-    hipLaunchKernelGGL(k_seg_fold, dim3(nblk + pfb), dim3(FOLD_THREADS), shmem, stream, gk, sk, (uint32_t)level_begin, (uint32_t)(gk.grad_zero ? 1 : 0),
-                       cowork ? *cowork : PoseFinishArgs{}, pfb);
+    if (fold_adam != nullptr) {
+      const FoldAdamHost& h = *fold_adam;
+      // the launch between bin and fold (one block: see k_fold_adam_prepare)
+      FoldAdamPrep pr{};
+      pr.grads = h.grads;
+      pr.ncheck = h.ncheck;
+      for (int k = 0; k < h.ncheck; ++k) { pr.off[k] = h.check_off[k]; pr.cnt[k] = h.check_cnt[k]; }
+      pr.found_inf_flag = h.found_inf + h.flag;
+      pr.state = h.state;
+      pr.limit = FLT_MAX / (8.0f * (float)P);
+      pr.wmax = sk.wmax;
+      pr.row_words = sk.NB * (BIN_THREADS / 64); pr.row_stride = pr.row_words; pr.rows = (uint32_t)seg_level_groups(L, sk.NB);
+      hipLaunchKernelGGL(k_fold_adam_prepare, dim3(1), dim3(1024), 0, stream, pr);
+      TN_CHECK_LAUNCH("tn_grid_scatter(fold: prepare)");
+      const AdamCoef c = adam_coef(0.f, 0.f, h.beta1, h.beta2, h.eps);
+      FoldAdamK fa{reinterpret_cast<float2*>(h.p), reinterpret_cast<float2*>(h.m), reinterpret_cast<float2*>(h.v), h.state, h.found_inf + h.flag,
+                   c.b1, c.b2, c.omb1, c.omb2, c.eps};
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_seg_fold<true>), hipFuncAttributeMaxDynamicSharedMemorySize, max_shmem);
+      hipLaunchKernelGGL(k_seg_fold<true>, dim3(nblk + pfb), dim3(FOLD_THREADS), shmem, stream, gk, sk, (uint32_t)level_begin, (uint32_t)(gk.grad_zero ? 1 : 0),
+                         cowork ? *cowork : PoseFinishArgs{}, pfb, fa);
+    } else {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_seg_fold<false>), hipFuncAttributeMaxDynamicSharedMemorySize, max_shmem);
+      hipLaunchKernelGGL(k_seg_fold<false>, dim3(nblk + pfb), dim3(FOLD_THREADS), shmem, stream, gk, sk, (uint32_t)level_begin, (uint32_t)(gk.grad_zero ? 1 : 0),
+                         cowork ? *cowork : PoseFinishArgs{}, pfb, FoldAdamK{});
+    }
     TN_CHECK_LAUNCH("tn_grid_scatter(fold, segmented)");
     return TN_OK;
   }
@@ -1360,26 +1569,36 @@ bool tn_grid_scatter_is_binned(const TnGrid& grid, int64_t P, const void* scratc
 }
 
 bool tn_grid_scatter_takes_cowork(const TnGrid& grid, int64_t P, void* scratch) { return seg_mode() && tn_grid_scatter_is_binned(grid, P, scratch); }
+// The fold can step the table itself (tn_adam.h) where ONE block owns a bucket (chunks == 1: P <= 1024 bin blocks), the bucket's slots pair up,
+// nothing else has added to the table gradient (table_grad_is_zero: the fold stores nothing, the arena stays zero) and the moments' 16-byte
+// accesses are aligned.
+bool tn_fold_adam_takes(const TnGrid& grid, int64_t P, void* scratch) {
+  if (!tn_grid_scatter_takes_cowork(grid, P, scratch) || !grid.table_grad_is_zero || grid.log2_hashmap_size < 1) return false;
+  SegK sk;
+  if (seg_plan(grid, P, scratch, sk) != TN_OK) return false;
+  return sk.chunks == 1 && ((uintptr_t)grid.table % 16) == 0;
+}
 
 static int grid_scatter_binned(const TnGrid& grid, const float* origins, const float* directions, const float* e_bins, const float* g_enc, int ld,
                                int64_t N, int S, float* d_origins, float* d_directions, void* scratch, hipStream_t stream, bool counters_zeroed,
-                               const DposArgs* cowork, const PoseFinishArgs* fold_cowork) {
-  int rc = tn_grid_scatter_bin(grid, origins, directions, e_bins, g_enc, ld, N, S, d_origins, d_directions, scratch, stream, counters_zeroed, cowork);
+                               const DposArgs* cowork, const PoseFinishArgs* fold_cowork, const FoldAdamHost* fold_adam) {
+  int rc = tn_grid_scatter_bin(grid, origins, directions, e_bins, g_enc, ld, N, S, d_origins, d_directions, scratch, stream, counters_zeroed, cowork, fold_adam);
   if (rc) return rc;
-  return tn_grid_scatter_fold(grid, N * (int64_t)S, scratch, 0, grid.num_levels, stream, fold_cowork);
+  return tn_grid_scatter_fold(grid, N * (int64_t)S, scratch, 0, grid.num_levels, stream, fold_cowork, fold_adam);
 }
 
 int tn_grid_scatter_launch(const TnGrid& grid, const float* origins, const float* directions, const float* e_bins, const float* g_enc, int ld,
                            int64_t N, int S, float* d_origins, float* d_directions, void* scratch, hipStream_t stream, float* dense_sum,
-                           bool counters_zeroed, const DposArgs* cowork, const PoseFinishArgs* fold_cowork) {
+                           bool counters_zeroed, const DposArgs* cowork, const PoseFinishArgs* fold_cowork, const FoldAdamHost* fold_adam) {
   TN_REQUIRE(grid.table && grid.table_grad && origins && directions && e_bins && g_enc, "tn_grid_scatter: null pointer");
   TN_REQUIRE(grid.num_levels >= 1 && grid.num_levels <= TN_MAX_LEVELS && (ld >= 2 * grid.num_levels || ld == TN_LD_LEVEL_MAJOR),
              "tn_grid_scatter: bad level count / row stride");
   int64_t P = N * (int64_t)S;
   if (P == 0) return TN_OK;
   if (dense_sum == nullptr && tn_grid_scatter_is_binned(grid, P, scratch))
-    return grid_scatter_binned(grid, origins, directions, e_bins, g_enc, ld, N, S, d_origins, d_directions, scratch, stream, counters_zeroed, cowork, fold_cowork);
-  TN_REQUIRE(cowork == nullptr && fold_cowork == nullptr, "tn_grid_scatter: co-work needs the segmented path (tn_grid_scatter_takes_cowork)");
+    return grid_scatter_binned(grid, origins, directions, e_bins, g_enc, ld, N, S, d_origins, d_directions, scratch, stream, counters_zeroed, cowork, fold_cowork,
+                               fold_adam);
+  TN_REQUIRE(cowork == nullptr && fold_cowork == nullptr && fold_adam == nullptr, "tn_grid_scatter: co-work needs the segmented path (tn_grid_scatter_takes_cowork)");
   int grid_dim = (int)std::min<int64_t>(tn_cdiv(P, 64), 256 * 32);
   // resident capacity is 256 CUs x 8 blocks: when the items do not fill a whole number of rounds, split the levels into 2 interleaved groups
   int level_groups = 1;
