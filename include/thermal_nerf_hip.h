@@ -1239,6 +1239,45 @@ TN_API int tn_mesh_emit(const float* values, const float* weights, const float* 
                         float origin_x, float origin_y, float origin_z, float voxel_x, float voxel_y, float voxel_z, float* vertices, float* normals,
                         float* out_rgbt, int64_t num_vertices, int32_t* faces, int64_t num_faces, void* workspace, int64_t workspace_bytes,
                         tn_stream_t stream);
+
+/* ---- Mesh simplification by vertex clustering (where the reference's export runs pymeshlab's quadric edge collapse to a face budget,
+ * exporter_utils.py get_mesh_from_filename with target_num_faces; the algorithm here is a different one and no parity with pymeshlab is claimed).
+ * The vertices of one cell of a regular grid become one vertex, placed by Lindstrom's quadric rule; faces are remapped, degenerate and duplicate ones
+ * dropped.  No atomics: every order comes from a stable sort or a prefix sum, so the same inputs give the same bytes.  The algorithm is stated once,
+ * in the header comment of csrc/tn_mesh_simplify.hip; tests/mesh_simplify_functional.py restates it in float64.  In short:
+ *   the cell of a vertex is floor((v - origin) / cell) per axis in fp32, clamped to [0, dims - 1]; key = (ix dims_y + iy) dims_z + iz; the clusters
+ *   (the vertices of one key) are numbered in key order;
+ *   in double and relative to the cell's centre, every input face adds n n^T to A and (n . p0) n to b (n = (p1 - p0) x (p2 - p0)) in the cluster of
+ *   each of its corners, in face order; with m the cluster's mean vertex and eps = regularization * trace(A) the new vertex solves
+ *   (A + eps I) x = b + eps m, and is m where the trace is 0 or where x leaves the closed cell (by more than 1e-6 cell); rounded to fp32 once;
+ *   out_rgbt = the cluster's mean rgbt, out_normals = its normalised normal sum (zero where the sum is zero), both in double, rounded once;
+ *   a face with two corners in one cluster is dropped, of the faces that name the same three clusters (in any order) the one with the lowest index
+ *   survives, survivors keep their order; clusters no survivor names are not emitted, the others are renumbered in key order.  A face with an index
+ *   outside [0, num_vertices) is dropped.
+ * vertices [V,3], normals [V,3], rgbt [V,4] (16-byte aligned) fp32, faces [F,3] int32; dims_x dims_y dims_z below 2^31 in all; V <= 2^31 - 1 and
+ * 3 F <= 2^31 - 1.  tn_mesh_simplify_count writes to count (DEVICE int64) the number of faces whose corners fall into three different cells -- an upper
+ * bound of the simplified mesh's faces, for a search over the cell size: one pass over the vertices and one over the faces, no sort.
+ * tn_mesh_simplify_plan writes totals = [vertices, faces] of the simplified mesh (DEVICE int64[2]) and leaves the orders in the workspace;
+ * tn_mesh_simplify_emit, called with the SAME workspace, mesh and grid, fills out_vertices / out_normals [num_out_vertices,3], out_rgbt
+ * [num_out_vertices,4] and out_faces [num_out_faces,3]; rows at or beyond the two counts are not written.  All three run on the caller's stream
+ * without a host synchronisation.  Refused with TN_EINVAL before any launch: sizes outside the above, a grid with a dimension below 1 or 2^31 cells and
+ * more, an origin that is not finite, a cell size that is not positive and finite, a negative regularization, null pointers (arrays of 0 rows may be
+ * null), misaligned pointers (the workspace to 256 bytes, rgbt arrays to 16), a short workspace.
+ *
+ * scratch of the three (32 bytes per vertex and 76 per face, and for rocprim's sorts a bound of 36 more per face, or 12 per vertex where that is
+ * more, and 1 MiB: the plan checks rocprim's own figures against it and answers TN_ELAUNCH where they do not fit); -1 for refused sizes */
+TN_API int64_t tn_mesh_simplify_workspace_bytes(int64_t num_vertices, int64_t num_faces);
+TN_API int tn_mesh_simplify_count(const float* vertices, int64_t num_vertices, const int32_t* faces, int64_t num_faces, float origin_x, float origin_y,
+                                  float origin_z, float cell_x, float cell_y, float cell_z, int32_t dims_x, int32_t dims_y, int32_t dims_z,
+                                  int64_t* count, void* workspace, int64_t workspace_bytes, tn_stream_t stream);
+TN_API int tn_mesh_simplify_plan(const float* vertices, int64_t num_vertices, const int32_t* faces, int64_t num_faces, float origin_x, float origin_y,
+                                 float origin_z, float cell_x, float cell_y, float cell_z, int32_t dims_x, int32_t dims_y, int32_t dims_z,
+                                 int64_t* totals, void* workspace, int64_t workspace_bytes, tn_stream_t stream);
+TN_API int tn_mesh_simplify_emit(const float* vertices, const float* normals, const float* rgbt, int64_t num_vertices, const int32_t* faces,
+                                 int64_t num_faces, float origin_x, float origin_y, float origin_z, float cell_x, float cell_y, float cell_z,
+                                 int32_t dims_x, int32_t dims_y, int32_t dims_z, float regularization, float* out_vertices, float* out_normals,
+                                 float* out_rgbt, int64_t num_out_vertices, int32_t* out_faces, int64_t num_out_faces, void* workspace,
+                                 int64_t workspace_bytes, tn_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -264,6 +264,10 @@ SIGNATURES = {
     "tn_mesh_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "tn_mesh_count": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _i64, _p]),
     "tn_mesh_emit": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32] + [_f] * 6 + [_p, _p, _p, _i64, _p, _i64, _p, _i64, _p]),
+    "tn_mesh_simplify_workspace_bytes": (_i64, [_i64, _i64]),
+    "tn_mesh_simplify_count": (C.c_int, [_p, _i64, _p, _i64] + [_f] * 6 + [_i32] * 3 + [_p, _p, _i64, _p]),
+    "tn_mesh_simplify_plan": (C.c_int, [_p, _i64, _p, _i64] + [_f] * 6 + [_i32] * 3 + [_p, _p, _i64, _p]),
+    "tn_mesh_simplify_emit": (C.c_int, [_p, _p, _p, _i64, _p, _i64] + [_f] * 6 + [_i32] * 3 + [_f, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

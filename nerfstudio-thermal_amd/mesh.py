@@ -10,8 +10,13 @@ pymeshlab; neither is used here, and the triangulation is not theirs.
 Two deliberate additions to the reference's fusion: `depth_kind` ("ray": Euclidean distances, the reference's rule and a NeRF's depth; "z": camera z,
 a rasteriser's depth) and voxels behind a camera (camera z <= 0) are skipped, where the reference divides by that z and mirrors them into the image.
 
-The raw calls are `integrate_call`, `mesh_count_call` and `mesh_emit_call`, the only places that know the argument order of their entry points
-(include/thermal_nerf_hip.h).  Everything runs on torch's current stream; there is no CPU fallback.
+Where the reference then decimates the mesh to a face budget with pymeshlab's edge collapse, `simplify_mesh` / `simplify_to_target` cluster the
+vertices on a regular grid (tn_mesh_simplify_count / _plan / _emit: sorts and prefix sums, a quadric solve per cluster); `export_tsdf_mesh` runs it
+when given target_num_faces.
+
+The raw calls are `integrate_call`, `mesh_count_call`, `mesh_emit_call`, `simplify_count_call`, `simplify_plan_call` and `simplify_emit_call`, the only
+places that know the argument order of their entry points (include/thermal_nerf_hip.h).  Everything runs on torch's current stream; there is no CPU
+fallback.
 """
 from __future__ import annotations
 
@@ -106,6 +111,176 @@ def mesh_emit_call(values: Tensor, weights: Tensor, rgbt: Tensor, observed_only:
         _contig(normals, "normals", (V, 3)), _contig(out_rgbt, "vertex rgbt", (V, 4)), V, _contig(faces, "faces", (Fn, 3), torch.int32), Fn,
         C.c_void_p(workspace.data_ptr()), workspace.numel(), _stream())
     _lib.check(rc, "tn_mesh_emit")
+
+
+def simplify_workspace(num_vertices: int, num_faces: int, device) -> Tensor:
+    need = int(_lib.load().tn_mesh_simplify_workspace_bytes(int(num_vertices), int(num_faces)))
+    if need < 0:
+        raise ValueError(f"tn_mesh_simplify_workspace_bytes({num_vertices}, {num_faces}): sizes the library refuses")
+    return torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+
+
+def _simplify_mesh_args(vertices: Tensor, faces: Tensor):
+    V, Fn = vertices.shape[0], faces.shape[0]
+    return _contig(vertices, "vertices", (V, 3)), V, _contig(faces, "faces", (Fn, 3), torch.int32), Fn
+
+
+def _simplify_grid_args(origin: Sequence[float], cell: Sequence[float], dims: Sequence[int]):
+    return [float(v) for v in origin] + [float(v) for v in cell] + [int(v) for v in dims]
+
+
+def simplify_count_call(vertices: Tensor, faces: Tensor, origin: Sequence[float], cell: Sequence[float], dims: Sequence[int], count: Tensor,
+                        workspace: Tensor) -> None:
+    """tn_mesh_simplify_count: into `count` (device int64 [1]) the number of faces whose corners fall into three different cells of the grid."""
+    rc = _lib.load().tn_mesh_simplify_count(*_simplify_mesh_args(vertices, faces), *_simplify_grid_args(origin, cell, dims),
+                                            _contig(count, "count", (1,), torch.int64), C.c_void_p(workspace.data_ptr()), workspace.numel(), _stream())
+    _lib.check(rc, "tn_mesh_simplify_count")
+
+
+def simplify_plan_call(vertices: Tensor, faces: Tensor, origin: Sequence[float], cell: Sequence[float], dims: Sequence[int], totals: Tensor,
+                       workspace: Tensor) -> None:
+    """tn_mesh_simplify_plan: the numbers of vertices and faces of the simplified mesh into `totals` (device int64 [2]); `workspace`
+    (simplify_workspace) then holds what simplify_emit_call needs."""
+    rc = _lib.load().tn_mesh_simplify_plan(*_simplify_mesh_args(vertices, faces), *_simplify_grid_args(origin, cell, dims),
+                                           _contig(totals, "totals", (2,), torch.int64), C.c_void_p(workspace.data_ptr()), workspace.numel(), _stream())
+    _lib.check(rc, "tn_mesh_simplify_plan")
+
+
+def simplify_emit_call(vertices: Tensor, normals: Tensor, rgbt: Tensor, faces: Tensor, origin: Sequence[float], cell: Sequence[float],
+                       dims: Sequence[int], regularization: float, out_vertices: Tensor, out_normals: Tensor, out_rgbt: Tensor, out_faces: Tensor,
+                       workspace: Tensor) -> None:
+    """tn_mesh_simplify_emit after simplify_plan_call on the same mesh, grid and workspace: out_vertices / out_normals [Vo,3], out_rgbt [Vo,4],
+    out_faces [Fo,3] int32."""
+    V, Fn, Vo, Fo = vertices.shape[0], faces.shape[0], out_vertices.shape[0], out_faces.shape[0]
+    rc = _lib.load().tn_mesh_simplify_emit(
+        _contig(vertices, "vertices", (V, 3)), _contig(normals, "normals", (V, 3)), _contig(rgbt, "vertex rgbt", (V, 4)), V,
+        _contig(faces, "faces", (Fn, 3), torch.int32), Fn, *_simplify_grid_args(origin, cell, dims), float(regularization),
+        _contig(out_vertices, "simplified vertices", (Vo, 3)), _contig(out_normals, "simplified normals", (Vo, 3)),
+        _contig(out_rgbt, "simplified rgbt", (Vo, 4)), Vo, _contig(out_faces, "simplified faces", (Fo, 3), torch.int32), Fo,
+        C.c_void_p(workspace.data_ptr()), workspace.numel(), _stream())
+    _lib.check(rc, "tn_mesh_simplify_emit")
+
+
+# ---------------------------------------------------------------------------------------------------- simplification
+MAX_CELLS = 2 ** 31  # a grid holds fewer cells than this (the keys are 31 bits)
+
+
+def _triple(v, name: str) -> np.ndarray:
+    """A number or three -> fp32 [3], as the entry points take them."""
+    a = np.asarray(v.detach().cpu().numpy() if isinstance(v, Tensor) else v, dtype=np.float64).reshape(-1)
+    if a.size == 1:
+        a = np.repeat(a, 3)
+    if a.size != 3 or not np.isfinite(a).all():
+        raise ValueError(f"{name} = {v!r}: one finite number or three")
+    return a.astype(np.float32)
+
+
+def vertex_extent(vertices: Tensor) -> np.ndarray:
+    """[2,3] fp32 on the host: the smallest and largest coordinate per axis (zeros for no vertices).  One read-back."""
+    if vertices.shape[0] == 0:
+        return np.zeros((2, 3), dtype=np.float32)
+    return torch.stack([vertices.amin(dim=0), vertices.amax(dim=0)]).cpu().numpy()
+
+
+def simplify_grid(extent: np.ndarray, cell: np.ndarray, origin: Optional[np.ndarray] = None) -> Tuple[np.ndarray, Tuple[int, int, int]]:
+    """The cell grid over `extent` (vertex_extent): origin (fp32 [3]; without one the smallest coordinates minus half a cell, in fp32) and dims, one
+    more than the cell index of the largest coordinates -- the entry points' own fp32 expression floor((v - origin) / cell), so no vertex is clamped
+    from above.  A dims product of MAX_CELLS or more is for the caller to refuse."""
+    if origin is None:
+        origin = extent[0] - cell * np.float32(0.5)
+    with np.errstate(over="ignore", invalid="ignore"):
+        top = np.floor((extent[1] - origin) / cell).astype(np.float64)
+    top = np.where(top > 0, np.minimum(top, float(MAX_CELLS)), 0.0)  # (a NaN goes to 0, as in the kernel)
+    return origin, tuple(int(t) + 1 for t in top)
+
+
+def simplify_mesh(mesh: Mesh, cell, origin=None, dims: Optional[Sequence[int]] = None, regularization: float = 1e-3,
+                  workspace: Optional[Tensor] = None) -> Mesh:
+    """`mesh` with the vertices of every cell of a regular grid merged into one (vertex clustering; tn_mesh_simplify_plan / tn_mesh_simplify_emit,
+    whose source states the algorithm): the new vertex minimises the summed squared distances to the planes of the cluster's faces, weighted by their
+    squared areas and regularised towards the cluster's mean (`regularization` times the quadric's trace); it is the mean where that point leaves the
+    cell.  RGB+T is the cluster's mean, the normal its normalised normal sum.  Faces that collapse are dropped, of those that name the same three
+    clusters the first stays; vertices no face names are dropped.  `cell` is a size or three, in the mesh's units; without `origin` the grid starts
+    half a cell below the smallest coordinates, without `dims` it reaches the largest.  Not an edge collapse, and no manifold guarantee: clustering
+    cannot give one.  Two read-backs (the extent, when the grid is not given in full; the two sizes)."""
+    dev = mesh.vertices.device
+    V, Fn = int(mesh.vertices.shape[0]), int(mesh.faces.shape[0])
+    cell3 = _triple(cell, "cell")
+    if not (cell3 > 0).all():
+        raise ValueError(f"simplify_mesh: cell = {cell!r} must be positive")
+    origin3 = None if origin is None else _triple(origin, "origin")
+    if origin3 is None or dims is None:
+        origin3, grid_dims = simplify_grid(vertex_extent(mesh.vertices), cell3, origin3)
+        dims = grid_dims if dims is None else dims
+    dims = tuple(int(d) for d in dims)
+    if len(dims) != 3 or min(dims) < 1 or dims[0] * dims[1] * dims[2] >= MAX_CELLS:
+        raise ValueError(f"simplify_mesh: a grid of {dims} cells (three sizes >= 1, below 2^31 cells in all): the cell is too small for the mesh")
+    ws = simplify_workspace(V, Fn, dev) if workspace is None else workspace
+    totals = torch.zeros(2, dtype=torch.int64, device=dev)
+    simplify_plan_call(mesh.vertices, mesh.faces, origin3, cell3, dims, totals, ws)
+    Vo, Fo = (int(v) for v in totals.tolist())
+    out = Mesh(torch.empty((Vo, 3), dtype=F32, device=dev), torch.empty((Fo, 3), dtype=torch.int32, device=dev),
+               torch.empty((Vo, 3), dtype=F32, device=dev), torch.empty((Vo, 4), dtype=F32, device=dev))
+    simplify_emit_call(mesh.vertices, mesh.normals, mesh.rgbt, mesh.faces, origin3, cell3, dims, regularization, out.vertices, out.normals, out.rgbt,
+                       out.faces, ws)
+    return out
+
+
+SEARCH_START, SEARCH_BISECTIONS, SEARCH_MAX_DOUBLINGS = 0.25, 12, 64
+
+
+def search_cell(scale: float, unit: np.ndarray) -> np.ndarray:
+    """cell = scale * unit in float64, rounded to fp32 once"""
+    return (np.float64(scale) * unit.astype(np.float64)).astype(np.float32)
+
+
+def simplify_to_target(mesh: Mesh, target_num_faces: int, unit, origin=None, regularization: float = 1e-3) -> Tuple[Mesh, Optional[Tuple[float, ...]]]:
+    """`mesh` simplified to at most `target_num_faces` faces -> (Mesh, the cell used, three floats; None where the mesh is returned as it is because it
+    has no more faces than that).  The cell is s * `unit` (the voxel size of the volume the mesh came from; a number or three).  tn_mesh_simplify_count
+    gives, per cell size, the faces whose corners lie in three different cells -- an upper bound of the simplified mesh's faces: s starts at 1/4 and
+    doubles until that count is within the target (a grid of 2^31 cells or more counts as over it), then 12 bisections on the geometric mean of the
+    bracket (s / 2, s) narrow it, and the mesh is simplified at the bracket's upper end, so its face count is within the target by construction.
+    One read-back per step; the same mesh gives the same cell."""
+    target = int(target_num_faces)
+    if target < 0:
+        raise ValueError(f"simplify_to_target: target_num_faces = {target_num_faces}")
+    V, Fn = int(mesh.vertices.shape[0]), int(mesh.faces.shape[0])
+    if Fn <= target:
+        return mesh, None
+    dev = mesh.vertices.device
+    unit3 = _triple(unit, "unit")
+    if not (unit3 > 0).all():
+        raise ValueError(f"simplify_to_target: unit = {unit!r} must be positive")
+    origin3 = None if origin is None else _triple(origin, "origin")
+    extent = vertex_extent(mesh.vertices)
+    ws = simplify_workspace(V, Fn, dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def within(scale: float) -> bool:
+        cell = search_cell(scale, unit3)
+        o, dims = simplify_grid(extent, cell, origin3)
+        if not (cell > 0).all() or dims[0] * dims[1] * dims[2] >= MAX_CELLS:
+            return False
+        simplify_count_call(mesh.vertices, mesh.faces, o, cell, dims, count, ws)
+        return int(count.item()) <= target
+
+    hi = SEARCH_START
+    for _ in range(SEARCH_MAX_DOUBLINGS):
+        if within(hi):
+            break
+        hi *= 2.0
+    else:
+        raise ValueError(f"simplify_to_target: no cell up to {hi} units brings the mesh to {target} faces")
+    lo = hi / 2.0
+    for _ in range(SEARCH_BISECTIONS):
+        mid = float(np.sqrt(np.float64(lo) * np.float64(hi)))
+        if within(mid):
+            hi = mid
+        else:
+            lo = mid
+    cell = search_cell(hi, unit3)
+    o, dims = simplify_grid(extent, cell, origin3)
+    return simplify_mesh(mesh, cell, origin=o, dims=dims, regularization=regularization, workspace=ws), tuple(float(c) for c in cell)
 
 
 # ---------------------------------------------------------------------------------------------------- the volume
@@ -239,11 +414,16 @@ def render_frame(model, camera: PinholeCamera) -> Tuple[Tensor, Tensor, Tensor, 
 def export_tsdf_mesh(model, cameras: Sequence[PinholeCamera], resolution: Union[int, Sequence[int]] = 256, downscale_factor: int = 2,
                      batch_size: int = 10, use_bounding_box: bool = True, bounding_box_min: Sequence[float] = (-1.0, -1.0, -1.0),
                      bounding_box_max: Sequence[float] = (1.0, 1.0, 1.0), scene_box=None, truncation_margin: float = 5.0, max_weight: float = 1.0,
-                     min_accumulation: float = 0.5, observed_only: bool = False, return_volume: bool = False):
+                     min_accumulation: float = 0.5, observed_only: bool = False, return_volume: bool = False,
+                     target_num_faces: Optional[int] = None):
     """export_tsdf_mesh (tsdf_utils.py:278-361) for a ThermalSplatfactoModel or a ThermalNerfactoModel: `cameras` (PinholeCamera, undistorted; the
     reference takes the training cameras with distortion off) are rendered at 1 / downscale_factor (rescaled_camera) in eval mode under no_grad (the
     model's mode is restored), fused in their order -- up to batch_size frames of one size per launch, and the batching does not change a bit of the
     result -- into a volume of `resolution` voxels (an int or a triple) over the bounding box -- or, with use_bounding_box False, over `scene_box` ([2,3], the dataparser's scene_box_aabb) -- and meshed.
+    With target_num_faces the mesh is then simplified to at most that many faces (simplify_to_target with the voxel size as the unit and the grid
+    origin half a voxel below the volume's, so that the cells are centred on lattice points: marching-tetrahedra vertices lie on lattice planes in
+    two coordinates, and a cell border there would split them by rounding alone); the reference's export decimates to 50 000 faces by default, with
+    pymeshlab's edge collapse, which this is not.  None, the default, leaves the mesh as extracted.
     -> Mesh, or (Mesh, TSDFVolume) with return_volume."""
     if isinstance(resolution, int):
         dims: List[int] = [resolution] * 3
@@ -279,7 +459,14 @@ def export_tsdf_mesh(model, cameras: Sequence[PinholeCamera], resolution: Union[
     finally:
         model.train(was_training)
     mesh = volume.get_mesh(observed_only)
+    if target_num_faces is not None:
+        mesh, _ = simplify_to_target(mesh, target_num_faces, volume.voxel_size, origin=lattice_centred_origin(volume))
     return (mesh, volume) if return_volume else mesh
+
+
+def lattice_centred_origin(volume: TSDFVolume) -> np.ndarray:
+    """The origin of a simplification grid whose cells of one voxel are centred on the volume's lattice points: origin - voxel_size / 2, in fp32."""
+    return (volume.origin - volume.voxel_size * 0.5).numpy()
 
 
 # ---------------------------------------------------------------------------------------------------- frames and files

@@ -6,11 +6,15 @@ the surface and write `tsdf_mesh.ply`: float x y z nx ny nz, uchar red green blu
     python scripts/export_tsdf_mesh.py [--model nerf|splat] [--data DIR] [--iterations 3000] [--output-dir out/mesh] [--resolution 256 | X Y Z]
                                        [--downscale-factor 2] [--batch-size 10] [--bounding-box-min X Y Z --bounding-box-max X Y Z]
                                        [--no-bounding-box] [--truncation-margin 5] [--max-weight 1] [--observed-only] [--no-save-world-frame] [--ascii]
+                                       [--target-num-faces N | --simplify-cell S]
 
 --max-weight 1 is the reference's fusion (the weight is clamped to 1: every new frame counts for half); a large value gives the running mean over
 all frames.  --observed-only drops the cells that touch a voxel no frame observed, and with them the shell the reference's meshes carry between
 observed free space and the unobserved fill.  --no-bounding-box fuses over the dataparser's scene box.  --save-world-frame (the default) writes the
-mesh in the dataset's own frame (mesh.mesh_to_dataset_frame).  One JSON line reports the sizes and the seconds of every stage.
+mesh in the dataset's own frame (mesh.mesh_to_dataset_frame).  --target-num-faces N simplifies the mesh to at most N faces by vertex clustering
+(mesh.simplify_to_target; the reference's export decimates to 50 000 faces by default, with pymeshlab's quadric edge collapse, which this is not),
+--simplify-cell S clusters with a cell of S voxels; neither is set by default, and the mesh is then written as extracted.  One JSON line reports the
+sizes -- before and after the simplification, with the cell it used -- and the seconds of every stage.
 """
 import argparse
 import functools
@@ -47,10 +51,16 @@ def parse_args(argv=None):
     ap.add_argument("--save-world-frame", dest="save_world_frame", action="store_true", default=True, help="write the mesh in the dataset's frame (default)")
     ap.add_argument("--no-save-world-frame", dest="save_world_frame", action="store_false", help="write it in the model's frame")
     ap.add_argument("--ascii", action="store_true", help="write an ASCII PLY")
+    ap.add_argument("--target-num-faces", type=int, default=None, metavar="N", help="simplify the mesh to at most N faces (the reference's default: 50000)")
+    ap.add_argument("--simplify-cell", type=float, default=None, metavar="S", help="simplify the mesh by clustering its vertices in cells of S voxels")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
     if len(args.resolution) not in (1, 3):
         ap.error("--resolution takes one number or three")
+    if args.target_num_faces is not None and args.simplify_cell is not None:
+        ap.error("--target-num-faces and --simplify-cell exclude each other")
+    if (args.target_num_faces is not None and args.target_num_faces < 0) or (args.simplify_cell is not None and not args.simplify_cell > 0):
+        ap.error("--target-num-faces takes a number >= 0, --simplify-cell a size > 0")
     return args
 
 
@@ -128,7 +138,21 @@ def main(argv=None):
                                       max_weight=args.max_weight, min_accumulation=args.min_accumulation, observed_only=args.observed_only,
                                       return_volume=True)
     sync(); export_s = time.perf_counter() - t1
-    meta = json.load(open(os.path.join(data, "transforms.json"), encoding="utf-8"))
+    simplified = None
+    if args.target_num_faces is not None or args.simplify_cell is not None:
+        before = {"vertices_extracted": int(m.vertices.shape[0]), "faces_extracted": int(m.faces.shape[0])}
+        origin = mesh.lattice_centred_origin(volume)
+        ts = time.perf_counter()
+        if args.target_num_faces is not None:
+            m, cell = mesh.simplify_to_target(m, args.target_num_faces, volume.voxel_size, origin=origin)
+        else:
+            cell = tuple(float(args.simplify_cell * v) for v in volume.voxel_size)
+            m = mesh.simplify_mesh(m, cell, origin=origin)
+        sync()
+        simplified = dict(before, simplify_cell=None if cell is None else list(cell),
+                          simplify_cell_voxels=None if cell is None else float(cell[0]) / float(volume.voxel_size[0]),
+                          target_num_faces=args.target_num_faces, simplify_seconds=time.perf_counter() - ts)
+    meta =json.load(open(os.path.join(data, "transforms.json"), encoding="utf-8"))
     t2 = time.perf_counter()
     ply = mesh.write_mesh_ply(os.path.join(args.output_dir, "tsdf_mesh.ply"), m, binary=not args.ascii,
                               dataparser_outputs=outputs if args.save_world_frame else None, applied_transform=meta.get("applied_transform"))
@@ -137,7 +161,7 @@ def main(argv=None):
                       "train_seconds": train_s, "cameras": len(cameras), "volume_dims": list(volume.dims), "truncation": volume.truncation,
                       "max_weight": args.max_weight, "observed_only": args.observed_only, "observed_voxel_share": float((volume.weights > 0).float().mean()),
                       "vertices": int(m.vertices.shape[0]), "faces": int(m.faces.shape[0]), "render_fuse_and_mesh_seconds": export_s,
-                      "write_seconds": write_s, "frame": "dataset" if args.save_world_frame else "model", "ply": ply}))
+                      "write_seconds": write_s, "frame": "dataset" if args.save_world_frame else "model", "ply": ply, **(simplified or {})}))
     return 0
 
 
