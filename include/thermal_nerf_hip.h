@@ -1278,6 +1278,43 @@ TN_API int tn_mesh_simplify_emit(const float* vertices, const float* normals, co
                                  int32_t dims_x, int32_t dims_y, int32_t dims_z, float regularization, float* out_vertices, float* out_normals,
                                  float* out_rgbt, int64_t num_out_vertices, int32_t* out_faces, int64_t num_out_faces, void* workspace,
                                  int64_t workspace_bytes, tn_stream_t stream);
+
+/* ---- Texture baking for exported meshes (nerfstudio/exporter/texture_utils.py with unwrap_method "custom": unwrap_mesh_per_uv_triangle, and the ray
+ * length and origin offset of export_textured_mesh; xatlas unwrapping is not built).  The atlas, the weights and the kernels are stated once, in the
+ * header comment of csrc/tn_texture.hip; tests/texture_functional.py restates the reference's formula.  In short, for F faces and px =
+ * px_per_uv_triangle >= 2: two faces share a square of (px + 3) x px texels, squares = ceil(F / 2) in row-major order, squares_w = ceil(sqrt(squares)),
+ * squares_h = ceil(squares / squares_w), the image is W = squares_w (px + 3) by H = squares_h px; a texel with the local offsets (i, j) in its square
+ * belongs to the lower-right (odd) face iff i + j >= px + 1 and has the weights w1 = i / (px - 1), w2 = j / (px - 1) (upper-left) or
+ * w1 = (px + 2 - i) / (px - 1), w2 = (px - 1 - j) / (px - 1) (lower-right), w0 = (1 - w1) - w2, in double -- the reference's barycentric weights,
+ * whose corners lie on texel centres, without its float32 cancellation.  A texel whose face index is not below F takes the last face (finite values
+ * no texture coordinate addresses).  A face that names a vertex outside [0, num_vertices) gives zeros.  vertices / normals [V,3], rgbt [V,4] (16-byte
+ * aligned) fp32, faces [F,3] int32; F in 1..(2^31 - 1) / 3, V in 1..2^31 - 1, px in 2..32768.  Texels are counted row-major, texel = y W + x.
+ * Every entry point runs on the caller's stream without a host synchronisation and without atomics: the same inputs give the same bytes.  Refused with
+ * TN_EINVAL before any launch: sizes outside the above, a texel range that leaves the image, null or misaligned pointers (outputs of 0 texels may be
+ * null), a negative or non-finite raylen, a short workspace.
+ *
+ * tn_texture_layout     HOST only, no device: layout = [W, H, squares_w, squares_h] (host int64[4])
+ * tn_texture_coords     texture_coordinates [F,3,2]: (corner texel + 0.5) / (W, H) in double, rounded once; v counts from the image's top row
+ * tn_texture_rays       texels [texel0, texel0 + count): origins [count,3] = sum w_i v_i, directions [count,3] = -sum w_i n_i over max(length, 1e-12)
+ *                       (both in double, rounded once; three zero normals give a zero direction), then origins -= (raylen / 2) directions in fp32
+ * tn_texture_vertex     the same texels: out_rgbt [count,4] = sum w_i rgbt[v_i], in double, rounded once
+ * tn_texture_store      a chunk's rgb (rows of 3 adjacent floats, rgb_stride floats apart) and thermal (thermal_stride apart) into the images of
+ *                       num_texels texels at texel0: rgb_image uint8 [num_texels,3] and thermal_image uint8 [num_texels] = rint(255 clamp(v, 0, 1))
+ *                       (half to even; a NaN gives 0), and, unless null, float_image [num_texels,4] (16-byte aligned) = the values as they are
+ * tn_mesh_mean_edge     mean (DEVICE float) = the mean of |v1 - v0| over the faces (export_textured_mesh's raylen is twice that): norms and sums in
+ *                       double, in a fixed order; scratch of tn_mesh_mean_edge_workspace_bytes (8-byte aligned; -1 for refused sizes) */
+TN_API int tn_texture_layout(int64_t num_faces, int32_t px_per_uv_triangle, int64_t* layout);
+TN_API int tn_texture_coords(int64_t num_faces, int32_t px_per_uv_triangle, float* texture_coordinates, tn_stream_t stream);
+TN_API int tn_texture_rays(const float* vertices, const float* normals, int64_t num_vertices, const int32_t* faces, int64_t num_faces,
+                           int32_t px_per_uv_triangle, float raylen, int64_t texel0, int64_t count, float* origins, float* directions,
+                           tn_stream_t stream);
+TN_API int tn_texture_vertex(const float* rgbt, int64_t num_vertices, const int32_t* faces, int64_t num_faces, int32_t px_per_uv_triangle,
+                             int64_t texel0, int64_t count, float* out_rgbt, tn_stream_t stream);
+TN_API int tn_texture_store(const float* rgb, int64_t rgb_stride, const float* thermal, int64_t thermal_stride, int64_t count, int64_t texel0,
+                            int64_t num_texels, uint8_t* rgb_image, uint8_t* thermal_image, float* float_image, tn_stream_t stream);
+TN_API int64_t tn_mesh_mean_edge_workspace_bytes(int64_t num_faces);
+TN_API int tn_mesh_mean_edge(const float* vertices, int64_t num_vertices, const int32_t* faces, int64_t num_faces, float* mean, void* workspace,
+                             int64_t workspace_bytes, tn_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

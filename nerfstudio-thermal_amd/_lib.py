@@ -268,6 +268,14 @@ SIGNATURES = {
     "tn_mesh_simplify_count": (C.c_int, [_p, _i64, _p, _i64] + [_f] * 6 + [_i32] * 3 + [_p, _p, _i64, _p]),
     "tn_mesh_simplify_plan": (C.c_int, [_p, _i64, _p, _i64] + [_f] * 6 + [_i32] * 3 + [_p, _p, _i64, _p]),
     "tn_mesh_simplify_emit": (C.c_int, [_p, _p, _p, _i64, _p, _i64] + [_f] * 6 + [_i32] * 3 + [_f, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p]),
+    # texture baking: the atlas layout (host only), texture coordinates, per-texel rays and vertex colours over a texel range, the image store
+    "tn_texture_layout": (C.c_int, [_i64, _i32, C.POINTER(_i64)]),
+    "tn_texture_coords": (C.c_int, [_i64, _i32, _p, _p]),
+    "tn_texture_rays": (C.c_int, [_p, _p, _i64, _p, _i64, _i32, _f, _i64, _i64, _p, _p, _p]),
+    "tn_texture_vertex": (C.c_int, [_p, _i64, _p, _i64, _i32, _i64, _i64, _p, _p]),
+    "tn_texture_store": (C.c_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
+    "tn_mesh_mean_edge_workspace_bytes": (_i64, [_i64]),
+    "tn_mesh_mean_edge": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i64, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -7,6 +7,7 @@ the surface and write `tsdf_mesh.ply`: float x y z nx ny nz, uchar red green blu
                                        [--downscale-factor 2] [--batch-size 10] [--bounding-box-min X Y Z --bounding-box-max X Y Z]
                                        [--no-bounding-box] [--truncation-margin 5] [--max-weight 1] [--observed-only] [--no-save-world-frame] [--ascii]
                                        [--target-num-faces N | --simplify-cell S]
+                                       [--texture none|nerf|vertex] [--px-per-uv-triangle 4] [--usemtl rgb|thermal] [--chunk N]
 
 --max-weight 1 is the reference's fusion (the weight is clamped to 1: every new frame counts for half); a large value gives the running mean over
 all frames.  --observed-only drops the cells that touch a voxel no frame observed, and with them the shell the reference's meshes carry between
@@ -15,6 +16,12 @@ mesh in the dataset's own frame (mesh.mesh_to_dataset_frame).  --target-num-face
 (mesh.simplify_to_target; the reference's export decimates to 50 000 faces by default, with pymeshlab's quadric edge collapse, which this is not),
 --simplify-cell S clusters with a cell of S voxels; neither is set by default, and the mesh is then written as extracted.  One JSON line reports the
 sizes -- before and after the simplification, with the cell it used -- and the seconds of every stage.
+
+--texture nerf|vertex also writes the reference's textured OBJ beside the PLY (texture.bake_texture / write_textured_obj: `mesh.obj`, `material_0.mtl`,
+`material_0.png` and, for the thermal channel, `material_0_thermal.png`): "nerf" renders every texel of the atlas through the radiance field along the
+interpolated normal (thermal-nerfacto only), "vertex" spreads the mesh's per-vertex colours and temperatures over the atlas (either model).
+--px-per-uv-triangle is the side of a face's triangle in texels, --usemtl the material the OBJ names, --chunk the texels rendered per call (default:
+the model's eval_num_rays_per_chunk).  The default, none, writes the PLY alone, as before.
 """
 import argparse
 import functools
@@ -53,6 +60,10 @@ def parse_args(argv=None):
     ap.add_argument("--ascii", action="store_true", help="write an ASCII PLY")
     ap.add_argument("--target-num-faces", type=int, default=None, metavar="N", help="simplify the mesh to at most N faces (the reference's default: 50000)")
     ap.add_argument("--simplify-cell", type=float, default=None, metavar="S", help="simplify the mesh by clustering its vertices in cells of S voxels")
+    ap.add_argument("--texture", default="none", choices=("none", "nerf", "vertex"), help="also write a textured OBJ: baked from the NeRF or from the vertices")
+    ap.add_argument("--px-per-uv-triangle", type=int, default=4, metavar="PX", help="texels along a face's triangle in the atlas (at least 2)")
+    ap.add_argument("--usemtl", default="rgb", choices=("rgb", "thermal"), help="the material the OBJ uses: the colour or the thermal texture")
+    ap.add_argument("--chunk", type=int, default=None, metavar="N", help="texels rendered per call (default: the model's eval_num_rays_per_chunk)")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
     if len(args.resolution) not in (1, 3):
@@ -61,6 +72,10 @@ def parse_args(argv=None):
         ap.error("--target-num-faces and --simplify-cell exclude each other")
     if (args.target_num_faces is not None and args.target_num_faces < 0) or (args.simplify_cell is not None and not args.simplify_cell > 0):
         ap.error("--target-num-faces takes a number >= 0, --simplify-cell a size > 0")
+    if args.texture == "nerf" and args.model != "nerf":
+        ap.error("--texture nerf renders rays through the radiance field: use --texture vertex with --model splat")
+    if args.px_per_uv_triangle < 2 or (args.chunk is not None and args.chunk < 1):
+        ap.error("--px-per-uv-triangle takes a number >= 2, --chunk a number >= 1")
     return args
 
 
@@ -157,11 +172,23 @@ def main(argv=None):
     ply = mesh.write_mesh_ply(os.path.join(args.output_dir, "tsdf_mesh.ply"), m, binary=not args.ascii,
                               dataparser_outputs=outputs if args.save_world_frame else None, applied_transform=meta.get("applied_transform"))
     write_s = time.perf_counter() - t2
+    textured = None
+    if args.texture != "none" and int(m.faces.shape[0]) > 0:
+        from nerfstudio_thermal_amd import texture
+
+        t3 = time.perf_counter()
+        tex = texture.bake_texture(m, model, args.px_per_uv_triangle, source=args.texture, chunk=args.chunk)
+        sync(); bake_s = time.perf_counter() - t3
+        t4 = time.perf_counter()
+        paths = texture.write_textured_obj(args.output_dir, m, tex, dataparser_outputs=outputs if args.save_world_frame else None,
+                                           applied_transform=meta.get("applied_transform"), usemtl=args.usemtl)
+        textured = {"texture": args.texture, "px_per_uv_triangle": args.px_per_uv_triangle, "texture_size": [int(tex.rgb.shape[1]), int(tex.rgb.shape[0])],
+                    "raylen": tex.raylen, "usemtl": args.usemtl, "bake_seconds": bake_s, "obj_write_seconds": time.perf_counter() - t4, "obj": paths["obj"]}
     print(json.dumps({"dataset": data if args.data is not None else f"generated cube scene ({data})", "model": args.model, "iterations": args.iterations,
                       "train_seconds": train_s, "cameras": len(cameras), "volume_dims": list(volume.dims), "truncation": volume.truncation,
                       "max_weight": args.max_weight, "observed_only": args.observed_only, "observed_voxel_share": float((volume.weights > 0).float().mean()),
                       "vertices": int(m.vertices.shape[0]), "faces": int(m.faces.shape[0]), "render_fuse_and_mesh_seconds": export_s,
-                      "write_seconds": write_s, "frame": "dataset" if args.save_world_frame else "model", "ply": ply, **(simplified or {})}))
+                      "write_seconds": write_s, "frame": "dataset" if args.save_world_frame else "model", "ply": ply, **(simplified or {}), **(textured or {})}))
     return 0
 
 
