@@ -286,6 +286,10 @@ TN_API int tn_field_bwd_phase(const TnField* field, const float* origins, const 
                        const float* e_bins, const float* d_density, const float* d_rgb, int64_t N, int32_t S, void* workspace,
                        int64_t workspace_bytes, float* d_origins, float* d_directions, int32_t phases, int32_t level_begin, int32_t level_end,
                        tn_stream_t stream);
+/* Caps the grid of the TN_BWD_MLP launch (k_field_bwd_fused: four waves per block, every wave walks a contiguous slab of 32-sample tiles) at
+ * max_blocks blocks; max_blocks <= 0 restores the default, one block per CU.  Process-wide; returns the cap that was in force.  The results do
+ * not depend on it beyond the order of the float sums.  For tests, which make a small batch walk several tiles per wave with it. */
+TN_API int32_t tn_field_bwd_max_blocks(int32_t max_blocks);
 /* Data-parallel exchange of the COARSE levels in dense form.  Levels whose (res+1)^3 cells are fewer than the table's slots are accumulated
  * in dense per-cell replicas anyway; their slice of the table gradient is almost all zeros (332 k possible non-zeros in 2.6 M slots for
  * levels 0-4 of the default grid), so a data-parallel run exchanges the per-cell sums (2.65 MB) instead of the table slice (20 MB):

@@ -775,26 +775,33 @@ __global__ void __launch_bounds__(256, 2) k_field_density_only(const float* __re
 //   Bias gradients are the lane sums of the A operands; the appearance-embedding rows are hw0[:, 31:63]^T times head layer 0's bias gradient
 //   restricted to the camera: running per-camera sums (lane = feature; up to FIELD_MAX_IMAGES cameras, two 128-B atomic segments per camera
 //   change) into cam_bias, multiplied by hw0 in k_field_emb_finish (one 64-thread block per camera behind this launch).
-//   Epilogue: the block's four waves add their accumulators in LDS (plain read-modify-write, one wave per turn) and ONE burst of float
-//   atomics per block goes to the gradient arena (256 blocks x 12.5 k floats).
+//   Epilogue: the block's four waves write their accumulators side by side into LDS (plain stores, all four at once: the packed weights and
+//   the tile buffers are dead by then), every thread adds the four copies of its words in wave order, and ONE burst of float atomics per block
+//   goes to the gradient arena (256 blocks x 10.5 k floats).  Four copies of everything do not fit, so this runs twice: the two 64-wide head
+//   layers, then the rest.  (Until the block sum took this form the waves took turns adding into ONE copy, word by word: read, add, write, each
+//   word a full LDS round trip because the compiler must assume the write aliases the next read -- 17 of the kernel's 115 us for the three
+//   adding turns, profiles/field_bwd.md.  The sums and their order, ((w0 + w1) + w2) + w3, are the same.)
 //   MFMA work per tile: chain 152 + weight gradients 128 (32x32x2) + 64 (16x16x4, half the cycles) -> 20.2 k cycles; 6 tiles per wave at 4096 rays.
 #define TSTR 68                       // LDS row stride (floats) of a [32 samples][<= 64 features] transposition tile
 #define FB_TILE_FLOATS (32 * TSTR)    // one tile buffer
 #define FB_WAVE_FLOATS (2 * FB_TILE_FLOATS + 128 + 32)  // dY tile, X tile, g3 [32][4], camera of each sample [32]
 #define FB_LDS_FLOATS (PACK_BWD_FLOATS + 4 * FB_WAVE_FLOATS)
-// block-sum layout (floats, inside the per-wave region): W3 [64][64] | W2 [64 out][32 slots] (+ 2048 unused) | W0 [64][32] | W4 [16][64] | W1 [16][64] | b3 b2 b0 (64 each) | b4 b1 (16 each)
+// block-sum layout (floats; one copy per wave, copy w at w * FB_RED_x_TOTAL from the start of LDS), first pass: W3 [64][64] | W2 [64 out][32 slots]
 #define FB_RED_W3 0
 #define FB_RED_W2 4096
-#define FB_RED_W0 8192
-#define FB_RED_W4 10240
-#define FB_RED_W1 11264
-#define FB_RED_B3 12288
-#define FB_RED_B2 12352
-#define FB_RED_B0 12416
-#define FB_RED_B4 12480
-#define FB_RED_B1 12496
-#define FB_RED_TOTAL 12512
-static_assert(FB_RED_TOTAL + 4 * 64 + 8 <= 4 * FB_WAVE_FLOATS, "block-sum area (+ the embedding merge) must fit in the per-wave buffers");
+#define FB_RED_A_TOTAL 6144
+// second pass: W0 [64][32] | W4 [16][64] | W1 [16][64] | b3 b2 b0 (64 each) | b4 b1 (16 each)
+#define FB_RED_W0 0
+#define FB_RED_W4 2048
+#define FB_RED_W1 3072
+#define FB_RED_B3 4096
+#define FB_RED_B2 4160
+#define FB_RED_B0 4224
+#define FB_RED_B4 4288
+#define FB_RED_B1 4304
+#define FB_RED_B_TOTAL 4320
+#define FB_EMB_MERGE_FLOATS (4 * 64 + 8)  // the embedding merge: [4 waves][64 sums], [4] cameras -- at the very end of LDS, clear of the copies
+static_assert(4 * FB_RED_A_TOTAL + FB_EMB_MERGE_FLOATS <= FB_LDS_FLOATS && FB_RED_B_TOTAL <= FB_RED_A_TOTAL, "four copies of a block-sum pass (+ the embedding merge) must fit in LDS");
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 #define WAVE_LDS_SYNC()                                   \
@@ -961,12 +968,19 @@ __global__ void __launch_bounds__(256, 1) k_field_bwd_fused(const float* __restr
   extern __shared__ __attribute__((aligned(16))) float lds[];  // FB_LDS_FLOATS
   tn_zero_words(zero_ptr, zero_words);  // the bucket counters of the table scatter that follows on this stream
   const float* src = pack + PACK_BWD_OFF;
-  for (int i = threadIdx.x * 4; i < PACK_BWD_FLOATS; i += blockDim.x * 4) {
+  // The packed weights: all of a thread's 14 loads are requested here, together with the first tile's loads below, and stored in front of the
+  // tile loop.  (As a plain copy loop this compiled to load, wait, store per trip, and the first tile's loads -- themselves a chain of three --
+  // were requested behind the barrier: ~17 global round trips one after the other at the head of every block, profiles/field_bwd.md.)
+  constexpr int PACK_TRIPS = PACK_BWD_FLOATS / (256 * 4);
+  static_assert(PACK_BWD_FLOATS % (256 * 4) == 0, "the packed backward fragments are copied in whole trips of 256 threads x float4");
+  float4 wq[PACK_TRIPS];
+#pragma unroll
+  for (int k = 0; k < PACK_TRIPS; ++k) {
+    const int i = (k * 256 + (int)threadIdx.x) * 4;
     // (split-bf16 head: the two 64-wide head layers' backward fragments -- the same 8192 words -- come from the bf16 region)
     const float* sp = (BF3 && i >= fwd_off(2) && i < fwd_off(4)) ? pack + PACK_BF_BWD_OFF + (i - fwd_off(2)) : src + i;
-    *reinterpret_cast<float4*>(lds + i) = *reinterpret_cast<const float4*>(sp);
+    wq[k] = *reinterpret_cast<const float4*>(sp);
   }
-  __syncthreads();
   const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5, wv = threadIdx.x >> 6;
   float* bufY = lds + PACK_BWD_FLOATS + wv * FB_WAVE_FLOATS;
   float* bufX = bufY + FB_TILE_FLOATS;
@@ -1019,6 +1033,9 @@ __global__ void __launch_bounds__(256, 1) k_field_bwd_fused(const float* __restr
   // next tile find their lines in L2.  Measured 127 -> 132 us: vmcnt retires in order, so this tile's (L2-hit) loads now queue behind the cold
   // warm-up loads of the next one -- the latency moves, it does not go away (profiles/r05_experiments.md).
   float touch_acc = 0.0f;
+#pragma unroll
+  for (int k = 0; k < PACK_TRIPS; ++k) *reinterpret_cast<float4*>(lds + (k * 256 + (int)threadIdx.x) * 4) = wq[k];
+  __syncthreads();
   for (int64_t tile = tile_begin; tile < tile_end; ++tile) {
     const int64_t p = tile * TILE + j;
     const bool valid = p < P;
@@ -1198,99 +1215,138 @@ __global__ void __launch_bounds__(256, 1) k_field_bwd_fused(const float* __restr
 #undef AB
   if (touch_acc == 1.2345678e-30f) cam_bias[0] = touch_acc;  // (never: keeps the warm-up loads alive)
   if (FB_ABLATE & 8) return;
-  // ---- block sum of the accumulators (plain LDS read-modify-write, one wave per turn: ds_add_f32 is lane-serialised on gfx950), then one
-  // burst of global float atomics per block; exact zeros stay exact zeros (v != 0 guard)
-  __syncthreads();  // every wave is done with its tile buffers: the sums go there
-  float* red = lds + PACK_BWD_FLOATS;
+  // ---- block sum of the accumulators (see the header: four copies side by side, added in wave order by every thread for its own words), then
+  // one burst of global float atomics per block; exact zeros stay exact zeros (v != 0 guard)
+  __syncthreads();  // every wave is done with the packed weights and its tile buffers: the copies go there
   if (!DENS_ONLY) {
     // the four waves' running per-camera sums: merged per camera inside the block first (a block's slab of rays usually holds one or two
     // cameras), so that the end of the kernel is not 2048 half-waves adding into the same few 128-B rows at once
-    float* esum = red + FB_RED_TOTAL;                          // [4 waves][64 sums]
+    float* esum = lds + FB_LDS_FLOATS - FB_EMB_MERGE_FLOATS;    // [4 waves][64 sums]
     int* ecam = reinterpret_cast<int*>(esum + 4 * 64);          // [4]
     esum[wv * 64 + lane] = emb_sum;
     if (lane == 0) ecam[wv] = emb_cam;
     __syncthreads();
-    if (threadIdx.x < 64) {
-      for (int e = 0; e < 4; ++e) {
-        const int cam = ecam[e];
-        if (cam < 0) continue;
-        bool first = true;
-        for (int f = 0; f < e; ++f) first = first && (ecam[f] != cam);
-        if (!first) continue;
-        float tot = 0.0f;
-        for (int f = e; f < 4; ++f)
-          if (ecam[f] == cam) tot += esum[f * 64 + threadIdx.x];
-        if (tot != 0.0f) atomicAdd(cam_bias + (int64_t)cam * 64 + threadIdx.x, tot);
+    {
+      // wave e answers for the e-th running sum: the first wave with a camera adds the sums of every wave with that camera (in wave order).
+      // All eight LDS reads are requested together; one wave walking the four sums made ~14 dependent LDS round trips that the block waited for
+      int cams[4];
+      float es[4];
+#pragma unroll
+      for (int f = 0; f < 4; ++f) { cams[f] = ecam[f]; es[f] = esum[f * 64 + lane]; }
+      int cam = cams[0];
+#pragma unroll
+      for (int f = 1; f < 4; ++f) cam = wv == f ? cams[f] : cam;
+      bool first = cam >= 0;
+      float tot = 0.0f;
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        if (f < wv) first = first && (cams[f] != cam);
+        else if (cams[f] == cam) tot += es[f];
       }
+      if (first && tot != 0.0f) atomicAdd(cam_bias + (int64_t)cam * 64 + lane, tot);
     }
   }
   const int c16 = lane & 15, k16 = lane >> 4;
-  for (int w = 0; w < 4; ++w) {
-    if (wv == w) {
-#define RED_PUT(idx, v) { float* d_ = &red[idx]; *d_ = (w == 0) ? (v) : *d_ + (v); }
+  // the sum of the four copies of word t, in wave order
+#define FB_RED_SUM4(total, t) \
+  ((t) < (total) ? ((lds[(t)] + lds[(total) + (t)]) + lds[2 * (total) + (t)]) + lds[3 * (total) + (t)] : 0.0f)
+  if (!DENS_ONLY) {  // first pass: the two 64-wide head layers' weights
+    float* cp = lds + wv * FB_RED_A_TOTAL;
 #pragma unroll
-      for (int a = 0; a < 2; ++a) {
+    for (int a = 0; a < 2; ++a) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int o = 32 * a + RROW(r, h);
-          if (!DENS_ONLY) {
+      for (int r = 0; r < 16; ++r) {
+        const int o = 32 * a + RROW(r, h);
 #pragma unroll
-            for (int b = 0; b < 2; ++b) RED_PUT(FB_RED_W3 + o * 64 + 32 * b + j, acc3[a][b][r]);
-            RED_PUT(FB_RED_W2 + o * 32 + j, acc2[a][0][r]);  // [64 out][32 slots]
-          }
-          RED_PUT(FB_RED_W0 + o * 32 + j, acc0[a][0][r]);
-        }
-        // bias sums: lane (j, h) holds its k-parity share of output 32a + j
-        const float s3 = bs3[a] + __shfl_xor(bs3[a], 32, 64), s2 = bs2[a] + __shfl_xor(bs2[a], 32, 64), s0_ = bs0[a] + __shfl_xor(bs0[a], 32, 64);
-        if (h == 0) {
-          if (!DENS_ONLY) { RED_PUT(FB_RED_B3 + 32 * a + j, s3); RED_PUT(FB_RED_B2 + 32 * a + j, s2); }
-          RED_PUT(FB_RED_B0 + 32 * a + j, s0_);
-        }
+        for (int b = 0; b < 2; ++b) cp[FB_RED_W3 + o * 64 + 32 * b + j] = acc3[a][b][r];
+        cp[FB_RED_W2 + o * 32 + j] = acc2[a][0][r];  // [64 out][32 slots]
       }
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (!DENS_ONLY) RED_PUT(FB_RED_W4 + (4 * k16 + r) * 64 + 16 * b + c16, acc4[b][r]);
-          RED_PUT(FB_RED_W1 + (4 * k16 + r) * 64 + 16 * b + c16, acc1[b][r]);
-        }
-      float s4 = bs4 + __shfl_xor(bs4, 16, 64); s4 += __shfl_xor(s4, 32, 64);
-      float s1_ = bs1 + __shfl_xor(bs1, 16, 64); s1_ += __shfl_xor(s1_, 32, 64);
-      if (lane < 16) {
-        if (!DENS_ONLY) RED_PUT(FB_RED_B4 + lane, s4);
-        RED_PUT(FB_RED_B1 + lane, s1_);
-      }
-#undef RED_PUT
     }
     __syncthreads();
-  }
-  for (int t = threadIdx.x; t < FB_RED_TOTAL; t += blockDim.x) {
-    const float v = red[t];
-    if (v == 0.0f) continue;
-    float* dst = nullptr;
-    if (t < FB_RED_W2) { if (!DENS_ONLY) dst = G.ghw1 + t; }
-    else if (t < FB_RED_W0) {  // d hw0, slots 0..31 (sh | base outputs): [64 out][32 slots] at the head of the region, the rest unused
-      const int q = t - FB_RED_W2;
-      if (q >= 64 * 32) continue;
-      const int col = slot_to_col(q & 31);
-      if (!DENS_ONLY && col >= 0) dst = G.ghw0 + (q >> 5) * 63 + col;
+    {
+      constexpr int NW = FB_RED_A_TOTAL / 256;  // words per thread: every sum is read before the first atomic goes out
+      static_assert(FB_RED_A_TOTAL % 256 == 0, "whole trips");
+      float v[NW];
+#pragma unroll
+      for (int u = 0; u < NW; ++u) v[u] = FB_RED_SUM4(FB_RED_A_TOTAL, (int)threadIdx.x + 256 * u);
+#pragma unroll
+      for (int u = 0; u < NW; ++u) {
+        const int t = (int)threadIdx.x + 256 * u;
+        if (v[u] == 0.0f) continue;
+        if (t < FB_RED_W2) {
+          atomicAdd(G.ghw1 + t, v[u]);
+        } else {  // d hw0, slots 0..31 (sh | base outputs): [64 out][32 slots]
+          const int q = t - FB_RED_W2, col = slot_to_col(q & 31);
+          if (col >= 0) atomicAdd(G.ghw0 + (q >> 5) * 63 + col, v[u]);
+        }
+      }
     }
-    else if (t < FB_RED_W4) dst = G.gw0 + (t - FB_RED_W0);
-    else if (t < FB_RED_W1) { const int q = t - FB_RED_W4; if (!DENS_ONLY && (q >> 6) < C) dst = G.ghw2 + q; }
-    else if (t < FB_RED_B3) dst = G.gw1 + (t - FB_RED_W1);
-    else if (t < FB_RED_B2) { if (!DENS_ONLY) dst = G.ghb1 + (t - FB_RED_B3); }
-    else if (t < FB_RED_B0) { if (!DENS_ONLY) dst = G.ghb0 + (t - FB_RED_B2); }
-    else if (t < FB_RED_B4) dst = G.gb0 + (t - FB_RED_B0);
-    else if (t < FB_RED_B1) { if (!DENS_ONLY && (t - FB_RED_B4) < C) dst = G.ghb2 + (t - FB_RED_B4); }
-    else dst = G.gb1 + (t - FB_RED_B1);
-    if (dst) atomicAdd(dst, v);
+    __syncthreads();  // the second pass's copies overlap the first's
   }
+  {  // second pass: the base MLP, the head's last layer and every bias
+    float* cp = lds + wv * FB_RED_B_TOTAL;
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) cp[FB_RED_W0 + (32 * a + RROW(r, h)) * 32 + j] = acc0[a][0][r];
+      // bias sums: lane (j, h) holds its k-parity share of output 32a + j
+      const float s3 = bs3[a] + __shfl_xor(bs3[a], 32, 64), s2 = bs2[a] + __shfl_xor(bs2[a], 32, 64), s0_ = bs0[a] + __shfl_xor(bs0[a], 32, 64);
+      if (h == 0) {
+        cp[FB_RED_B3 + 32 * a + j] = s3;  // (zeros in the density-only backward, like W4 and b4 below: never added anywhere)
+        cp[FB_RED_B2 + 32 * a + j] = s2;
+        cp[FB_RED_B0 + 32 * a + j] = s0_;
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        cp[FB_RED_W4 + (4 * k16 + r) * 64 + 16 * b + c16] = acc4[b][r];
+        cp[FB_RED_W1 + (4 * k16 + r) * 64 + 16 * b + c16] = acc1[b][r];
+      }
+    float s4 = bs4 + __shfl_xor(bs4, 16, 64); s4 += __shfl_xor(s4, 32, 64);
+    float s1_ = bs1 + __shfl_xor(bs1, 16, 64); s1_ += __shfl_xor(s1_, 32, 64);
+    if (lane < 16) {
+      cp[FB_RED_B4 + lane] = s4;
+      cp[FB_RED_B1 + lane] = s1_;
+    }
+    __syncthreads();
+    {
+      constexpr int NW = (FB_RED_B_TOTAL + 255) / 256;
+      float v[NW];
+#pragma unroll
+      for (int u = 0; u < NW; ++u) v[u] = FB_RED_SUM4(FB_RED_B_TOTAL, (int)threadIdx.x + 256 * u);
+#pragma unroll
+      for (int u = 0; u < NW; ++u) {
+        const int t = (int)threadIdx.x + 256 * u;
+        if (v[u] == 0.0f) continue;  // (also every word beyond the pass)
+        float* dst = nullptr;
+        if (t < FB_RED_W4) dst = G.gw0 + (t - FB_RED_W0);
+        else if (t < FB_RED_W1) { const int q = t - FB_RED_W4; if (!DENS_ONLY && (q >> 6) < C) dst = G.ghw2 + q; }
+        else if (t < FB_RED_B3) dst = G.gw1 + (t - FB_RED_W1);
+        else if (t < FB_RED_B2) { if (!DENS_ONLY) dst = G.ghb1 + (t - FB_RED_B3); }
+        else if (t < FB_RED_B0) { if (!DENS_ONLY) dst = G.ghb0 + (t - FB_RED_B2); }
+        else if (t < FB_RED_B4) dst = G.gb0 + (t - FB_RED_B0);
+        else if (t < FB_RED_B1) { if (!DENS_ONLY && (t - FB_RED_B4) < C) dst = G.ghb2 + (t - FB_RED_B4); }
+        else dst = G.gb1 + (t - FB_RED_B1);
+        if (dst) atomicAdd(dst, v[u]);
+      }
+    }
+  }
+#undef FB_RED_SUM4
 }
 
 // (k_field_bwd_pair -- the same backward with TWO waves per SIMD, each wave of a pair owning half of the output features -- was measured at
 // 136-151 us against this kernel's 126 and removed in round 6; what it taught is in profiles/r05_experiments.md.)
 
 // ---- host entry points -----------------------------------------------------------------------------------------------------
+#define FIELD_BWD_BLOCKS 256  // k_field_bwd_fused's grid: one block per CU
+static int g_field_bwd_max_blocks = FIELD_BWD_BLOCKS;
+extern "C" int32_t tn_field_bwd_max_blocks(int32_t max_blocks) {
+  const int32_t was = g_field_bwd_max_blocks;
+  g_field_bwd_max_blocks = (max_blocks <= 0 || max_blocks > FIELD_BWD_BLOCKS) ? FIELD_BWD_BLOCKS : max_blocks;
+  return was;
+}
 static int check_field(const TnField* f, const char* who, bool need_grad) {
   TN_REQUIRE(f != nullptr, "%s: null field", who);
   TN_REQUIRE(f->grid.table && f->w0 && f->b0 && f->w1 && f->b1 && f->hw0 && f->hb0 && f->hw1 && f->hb1 && f->hw2 && f->hb2 && f->emb,
@@ -1496,7 +1552,7 @@ int tn_field_bwd_phase_ex(const TnField* field, const float* origins, const floa
   if (phases & TN_BWD_MLP) {
     // chain + every weight gradient in one launch (k_field_bwd_fused)
     const size_t shmem = FB_LDS_FLOATS * sizeof(float);
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(tn_cdiv(tn_cdiv(P, TILE), 4), 256));  // one block per CU (one wave per SIMD)
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(tn_cdiv(tn_cdiv(P, TILE), 4), g_field_bwd_max_blocks));  // one block per CU (one wave per SIMD)
     FusedGrads G{field->gw0, field->gb0, field->gw1, field->gb1, field->ghw0, field->ghb0, field->ghw1, field->ghb1, field->ghw2, field->ghb2, field->gemb};
     uint32_t* zp;
     int zw;
