@@ -1145,6 +1145,41 @@ TN_API int tn_splat_mcmc_noise(float* means, const float* log_scales, const floa
 TN_API int tn_splat_mcmc_noise_sep(float* means, const float* log_scales, const float* quats, const float* opacities, const float* opacities_thermal,
                                    const float* randn, int64_t num_gaussians, float scaler, tn_stream_t stream);
 
+/* ---- Gaussian-splat PLY export (ns-export gaussian-splat: nerfstudio/scripts/exporter.py:480-546, ExportGaussianSplat): the model's parameter
+ * tensors become the rows of an Inria-layout splat file on the device, filtered and compacted in their original order.  Runs on the caller's
+ * stream without a host synchronisation and without atomics: the same inputs give the same bytes.  tests/splat_export_functional.py restates it.
+ *
+ * tn_export_splat_pack: the parameters as tn_splat_project_sep takes them -- means, log_scales [N,3], quats [N,4] (written as stored, not
+ * normalised), opacities [N] (logits), features_dc [N,3], features_rest [N,R,3], thermal_dc [N], thermal_rest [N,R] with R = num_rest_coeffs (the
+ * two rest tensors may be null when R is 0), opacities_thermal [N] or null (shared opacity).  spectrum: 0 rgb, 1 thermal, 2 both.  The row of W
+ * floats, with o = 9 + 3 R:
+ *   0..2 x y z | 3..5 nx ny nz = 0 | 6..8 f_dc_0..2 | 9..o-1 f_rest_{c R + k} = features_rest[g,k,c] (channel-major) | o opacity |
+ *   o+1..o+3 scale_0..2 | o+4..o+7 rot_0..3                                                             W = 17 + 3 R for rgb and thermal
+ *   thermal: the same columns with f_dc_c = thermal_dc[g], f_rest_{c R + k} = thermal_rest[g,k], opacity = opacities_thermal[g] where given, else
+ *   opacities[g] -- a grey scene under the Inria property names;
+ *   both: the rgb row, then o+8 f_dc_thermal | o+9..o+8+R f_rest_thermal_0..R-1 | with opacities_thermal, o+9+R opacity_thermal.
+ * colour_mode 0 writes the SH coefficients as stored; colour_mode 1 (the model's sh_degree == 0 convention, colour = sigmoid(dc); R must be 0)
+ * writes f_dc = (sigmoid(dc) - 0.5) / 0.28209479177387814 in double, rounded once, also for f_dc_thermal.
+ * Gaussian g is kept iff
+ *   every parameter its row is made of is finite (a thermal-only parameter does not matter to an rgb row, nor an RGB-only one to a thermal row), and
+ *   the opacity logit of the row >= min_opacity_logit (a float compare; -inf switches it off; with two logits in the row, the larger of them), and
+ *   crop is null, or the mean is inside the box exactly as tn_splat_crop_mask tests it.  crop is a HOST pointer, read before the launch.
+ * The kept rows go to out_rows [N, W] in the Gaussians' order, count (DEVICE int64[1]) is SET to their number, rows at and beyond it are not
+ * written.  num_gaussians == 0 is TN_OK and sets count to 0.  Refused with TN_EINVAL before any launch: num_gaussians outside [0, 2^31),
+ * num_rest_coeffs negative or above 1024, an unknown spectrum or colour_mode, colour_mode 1 with num_rest_coeffs > 0, a NaN threshold, null
+ * pointers, a workspace that is short or not 8-byte aligned.
+ *
+ * (The two entry points are named tn_export_splat_*, outside the tn_splat_* family: the Python package issues every launch of that family from
+ * splat_calls.py, and this call from splat_io.pack_call, as cloud.py and mesh.py issue theirs.)
+ *
+ * scratch of tn_export_splat_pack (a keep flag per Gaussian, a count and an offset per block of 256); -1 for num_gaussians outside [0, 2^31) */
+TN_API int64_t tn_export_splat_workspace_bytes(int64_t num_gaussians);
+TN_API int tn_export_splat_pack(const float* means, const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
+                                const float* features_rest, const float* thermal_dc, const float* thermal_rest, const float* opacities_thermal,
+                                int64_t num_gaussians, int32_t num_rest_coeffs, int32_t spectrum, int32_t colour_mode, float min_opacity_logit,
+                                const TnSplatCrop* crop, float* out_rows, int64_t* count, void* workspace, int64_t workspace_bytes,
+                                tn_stream_t stream);
+
 /* ---- point-cloud export of the NeRF (ns-export pointcloud: nerfstudio/scripts/exporter.py:90-186, nerfstudio/exporter/exporter_utils.py:83-260,
  * generate_point_cloud): rendered rays are back-projected by their depth, the opaque ones inside a box are kept, statistical outliers are
  * removed.  Every point carries the rendered colour and the rendered thermal value.  Both entry points run on the caller's stream without a host

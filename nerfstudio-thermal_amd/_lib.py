@@ -256,6 +256,10 @@ SIGNATURES = {
     "tn_splat_mcmc_relocate_sep": (C.c_int, [_i64, _i32, _p, _p, _i64, _f, _p, _p, _p, _p, _i64, _p]),
     "tn_splat_mcmc_noise": (C.c_int, [_p] * 5 + [_i64, _f, _p]),
     "tn_splat_mcmc_noise_sep": (C.c_int, [_p] * 6 + [_i64, _f, _p]),
+    # Gaussian-splat PLY export: the parameters of tn_splat_project_sep -> the kept Gaussians' file rows, compacted in order
+    # (named tn_export_splat_*, outside the tn_splat_* family: every launch of that family is issued by splat_calls.py, this raw call is splat_io.pack_call's)
+    "tn_export_splat_workspace_bytes": (_i64, [_i64]),
+    "tn_export_splat_pack": (C.c_int, [_p] * 9 + [_i64, _i32, _i32, _i32, _f, C.POINTER(TnSplatCrop), _p, _p, _p, _i64, _p]),
     # point-cloud export of the NeRF: stable append of a rendered batch, statistical outlier removal
     "tn_cloud_append_workspace_bytes": (_i64, [_i64]),
     "tn_cloud_append": (C.c_int, [_p] * 5 + [_i64, _p, _i64, _i64, _f, C.POINTER(TnSplatCrop), _p, _p, _p, _i64, _p, _p, _i64, _p]),

@@ -238,9 +238,9 @@ def _ply_u8(path: str, values: np.ndarray, what: str) -> np.ndarray:
     raise ValueError(f"{path}: {what} of type {values.dtype} (uchar, float or double are read)")
 
 
-def _read_ply_vertices(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
-    with open(path, "rb") as f:
-        data = f.read()
+def _ply_header(path: str, data: bytes) -> Tuple[str, List[Tuple[str, int, List[Tuple[str, str]]]], int]:
+    """The header of a PLY file's bytes -> (format, [(element, count, [(property, numpy type, or "list")])], offset of the body).  ValueError:
+    no PLY header, unknown or big-endian formats, unknown property types.  (The header reader of _read_ply_vertices and of splat_io.)"""
     if not data.startswith(b"ply"):
         raise ValueError(f"{path}: not a PLY file")
     end = data.find(b"end_header")
@@ -272,6 +272,13 @@ def _read_ply_vertices(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.n
                 raise ValueError(f"{path}: unknown PLY property type {tok[1]!r}")
     if fmt is None:
         raise ValueError(f"{path}: PLY header without a format line")
+    return fmt, elements, body
+
+
+def _read_ply_vertices(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+    with open(path, "rb") as f:
+        data = f.read()
+    fmt, elements, body = _ply_header(path, data)
     names = [e[0] for e in elements]
     if "vertex" not in names:
         raise ValueError(f"{path}: PLY without a vertex element")

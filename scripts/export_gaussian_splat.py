@@ -1,0 +1,121 @@
+"""Export thermal splats as a Gaussian-splat PLY (the counterpart of `ns-export gaussian-splat`, nerfstudio/scripts/exporter.py:480-546): train
+ThermalSplatfactoModel on a dataset -- or on the generated RGB+T cube scene of scripts/train_eval_scene.py -- for --iterations steps, or start from a
+splat file (--load), and write `splat.ply` in the Inria layout every splat viewer reads.
+
+    python scripts/export_gaussian_splat.py [--data DIR] [--iterations 3000] [--output-dir out/splat] [--spectrum both|rgb|thermal]
+                                            [--min-opacity 0.005] [--obb-center X Y Z --obb-rotation ROLL PITCH YAW --obb-scale SX SY SZ]
+                                            [--load PLY] [--thermal-opacity-mode shared|separate] [--sh-degree 3] [--gaussians 20000]
+
+--spectrum both (the default) writes the colour scene under the Inria property names followed by f_dc_thermal, f_rest_thermal_* and, in separate
+mode, opacity_thermal: viewers ignore the extras, splat_io.load_gaussian_ply reads them back (bit for bit for --sh-degree > 0).  --spectrum thermal
+writes the thermal parameters under the Inria names, so any viewer shows the thermal scene in grey.  Gaussians with sigmoid(opacity) below
+--min-opacity (in a "both" file of a separate-mode model: in both spectra) and Gaussians with a parameter that is not finite are dropped; the
+--obb-* arguments (all three or none; rotation in radians) keep only the Gaussians whose mean is strictly inside that oriented box, the eval
+render's crop.  --load PLY starts from a splat file instead of random Gaussians -- an Inria file from any trainer, or one written here -- and
+trains on from it for --iterations steps (0: load, filter, write).  The file is in the model's frame.  One JSON line reports the counts and the
+seconds of every stage.
+"""
+import argparse
+import functools
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "scripts")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--data", default=None, help="an RGB+T nerfstudio dataset (default: the generated cube scene)")
+    ap.add_argument("--frames", type=int, default=12, help="frames per spectrum of the generated scene")
+    ap.add_argument("--iterations", type=int, default=3000, help="training steps before the export")
+    ap.add_argument("--gaussians", type=int, default=20000, help="random initial Gaussians")
+    ap.add_argument("--sh-degree", type=int, default=3)
+    ap.add_argument("--thermal-opacity-mode", default="shared", choices=("shared", "separate"))
+    ap.add_argument("--output-dir", default="out/splat")
+    ap.add_argument("--spectrum", default="both", choices=("rgb", "thermal", "both"))
+    ap.add_argument("--min-opacity", type=float, default=0.005, help="drop Gaussians less opaque than this (0: keep every opacity)")
+    ap.add_argument("--obb-center", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
+    ap.add_argument("--obb-rotation", type=float, nargs=3, default=None, metavar=("ROLL", "PITCH", "YAW"), help="radians")
+    ap.add_argument("--obb-scale", type=float, nargs=3, default=None, metavar=("SX", "SY", "SZ"))
+    ap.add_argument("--load", default=None, metavar="PLY", help="start from this Gaussian-splat PLY")
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args(argv)
+    obb = (args.obb_center, args.obb_rotation, args.obb_scale)
+    if any(a is not None for a in obb) and not all(a is not None for a in obb):
+        ap.error("--obb-center, --obb-rotation and --obb-scale go together")
+    if not 0.0 <= args.min_opacity < 1.0:
+        ap.error("--min-opacity takes a value in [0, 1)")
+    if args.iterations < 0 or args.sh_degree < 0:
+        ap.error("--iterations and --sh-degree take numbers >= 0")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import torch
+
+    import nerfstudio_thermal_amd  # noqa: F401
+    from nerfstudio_thermal_amd import ThermalFullImageDatamanagerConfig, splat_io
+    from nerfstudio_thermal_amd.dataparser import ThermalNerfDataParserConfig
+    from nerfstudio_thermal_amd.model import TrainingCallbackLocation
+    from nerfstudio_thermal_amd.optim import SPLAT_BILAGRID_OPTIMIZERS, SPLAT_CAMERA_OPTIMIZERS, SPLAT_OPTIMIZERS, HipAdam, Optimizers
+    from nerfstudio_thermal_amd.splat import OrientedBox, ThermalSplatfactoModel, ThermalSplatfactoModelConfig
+
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(args.seed)
+    os.makedirs(args.output_dir, exist_ok=True)
+    cfg = ThermalSplatfactoModelConfig(num_random=args.gaussians, random_scale=1.0, background_color="random", sh_degree=args.sh_degree,
+                                       thermal_opacity_mode=args.thermal_opacity_mode)
+    sync = torch.cuda.synchronize
+    dm = None
+    if args.iterations > 0:
+        data = args.data
+        if data is None:
+            from train_eval_scene import write_cube_scene
+
+            data = os.path.join(args.output_dir, "scene")
+            write_cube_scene(data, args.frames, dev)
+        dm = ThermalFullImageDatamanagerConfig(dataparser=ThermalNerfDataParserConfig(data=data), seed=args.seed).setup(device=dev)
+    model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=dm.num_train_data if dm else 0,
+                                   train_is_thermal=dm.train_is_thermal if dm else None)
+    loaded = None
+    if args.load is not None:
+        t = time.perf_counter()
+        info = splat_io.load_gaussian_ply(model, args.load)
+        loaded = {"path": args.load, "gaussians": info["num_gaussians"], "sh_degree": info["sh_degree"], "has_thermal": info["has_thermal"],
+                  "separate": info["separate"], "load_seconds": time.perf_counter() - t}
+    sync(); t0 = time.perf_counter()
+    if dm is not None:
+        opts = Optimizers(model.get_param_groups(), {**SPLAT_OPTIMIZERS, **SPLAT_CAMERA_OPTIMIZERS, **SPLAT_BILAGRID_OPTIMIZERS}, optimizer_cls=HipAdam)
+        cbs = model.get_training_callbacks(opts)
+        for step in range(args.iterations):
+            cam, batch = dm.next_train(step)
+            for cb in cbs:
+                cb.run_callback_at_location(step, TrainingCallbackLocation.BEFORE_TRAIN_ITERATION)
+            opts.zero_grad_all()
+            functools.reduce(torch.add, model.get_loss_dict(model.get_train_outputs(cam), batch).values()).backward()
+            opts.optimizer_step_all()
+            opts.scheduler_step_all()
+            for cb in cbs:
+                cb.run_callback_at_location(step, TrainingCallbackLocation.AFTER_TRAIN_ITERATION)
+    sync(); train_s = time.perf_counter() - t0
+    box = OrientedBox.from_params(args.obb_center, args.obb_rotation, args.obb_scale) if args.obb_center is not None else None
+    t1 = time.perf_counter()
+    out = splat_io.export_gaussian_ply(model, os.path.join(args.output_dir, "splat.ply"), spectrum=args.spectrum, min_opacity=args.min_opacity, crop=box)
+    export_s = time.perf_counter() - t1
+    print(json.dumps({"dataset": None if dm is None else (args.data if args.data is not None else "generated cube scene"), "loaded": loaded,
+                      "iterations": args.iterations, "train_seconds": train_s, "gaussians": model.num_points, "exported": out["exported"],
+                      "dropped": out["dropped"], "spectrum": args.spectrum, "min_opacity": args.min_opacity, "sh_degree": args.sh_degree,
+                      "thermal_opacity_mode": args.thermal_opacity_mode, "properties": len(out["properties"]),
+                      "obb": None if box is None else {"center": args.obb_center, "rotation": args.obb_rotation, "scale": args.obb_scale},
+                      "export_seconds": export_s, "file_bytes": os.path.getsize(out["path"]), "ply": out["path"]}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -29,7 +29,9 @@ bilateral_grid / bilateral_grid_thermal with optim.SPLAT_BILAGRID_OPTIMIZERS); -
 scene: every TRAINING frame is multiplied by a gain drawn uniformly in [1 - X, 1 + X] and shifted by an offset in [-X / 2, X / 2] (seeded by --seed,
 clamped to [0, 1]); the held-out frames are left alone, so the val metrics say what the drift did to the scene itself.  Eval renders are never
 corrected by a grid, so the line also reports psnr_rgb_affine_fit / psnr_thermal_affine_fit: each held-out frame's PSNR
-after the least-squares affine colour map of its render onto its ground truth (a diagnostic of this script, plain torch)."""
+after the least-squares affine colour map of its render onto its ground truth (a diagnostic of this script, plain torch).  --export-ply PATH writes
+the trained Gaussians as a Gaussian-splat PLY (splat_io.export_gaussian_ply: spectrum "both", Gaussians below opacity 0.005 in both spectra and
+those with a parameter that is not finite dropped); the line reports how many went out."""
 import argparse
 import functools
 import json
@@ -174,6 +176,8 @@ def main():
     ap.add_argument("--frame-drift", type=float, default=0.0, metavar="X",
                     help="generated scene only: training frames times a per-frame gain in [1-X, 1+X] plus an offset in [-X/2, X/2]; val frames untouched")
     ap.add_argument("--no-undistort", action="store_true", help="train on the raw frames with the parser's intrinsics (the distortion dropped)")
+    ap.add_argument("--export-ply", default=None, metavar="PATH",
+                    help="write the trained Gaussians as a Gaussian-splat PLY (splat_io.export_gaussian_ply, spectrum both, opacity below 0.005 dropped)")
     args = ap.parse_args()
     if args.seed_points and args.data is not None:
         ap.error("--seed-points samples the generated scene's cube; a dataset on disk brings its own ply_file_path")
@@ -268,6 +272,12 @@ def main():
         frames = write_cropped_frames(model, val, crop_box, args.crop_out)
         extra["crop"] = {"pos": args.crop_pos, "rpy": args.crop_rpy, "scale": args.crop_scale, "frames_written": frames, "out": args.crop_out,
                          "gaussians_kept_share": float(crop_box.within(model.means.detach()).float().mean()) if model.num_points else 0.0}
+    if args.export_ply is not None:  # the splat file every viewer reads, with the thermal parameters under names of their own
+        from nerfstudio_thermal_amd import splat_io
+
+        os.makedirs(os.path.dirname(os.path.abspath(args.export_ply)), exist_ok=True)
+        out = splat_io.export_gaussian_ply(model, args.export_ply, spectrum="both", min_opacity=0.005)
+        extra["export_ply"] = {k: out[k] for k in ("path", "exported", "dropped", "spectrum")}
     model.train()
     metrics = {k: sum(v) / len(v) for k, v in sums.items() if all(math.isfinite(x) for x in v)}
     pose_norms = {}
