@@ -1354,6 +1354,43 @@ TN_API int tn_texture_store(const float* rgb, int64_t rgb_stride, const float* t
 TN_API int64_t tn_mesh_mean_edge_workspace_bytes(int64_t num_faces);
 TN_API int tn_mesh_mean_edge(const float* vertices, int64_t num_vertices, const int32_t* faces, int64_t num_faces, float* mean, void* workspace,
                              int64_t workspace_bytes, tn_stream_t stream);
+/* ---- Frames for people: the reference's colour maps and the side-by-side frame of ns-render (nerfstudio/utils/colormaps.py apply_colormap /
+ * apply_float_colormap / apply_depth_colormap, scripts/render.py _render_trajectory_video).  The rule is stated once, in the header comment of
+ * csrc/tn_render.hip; tests/render_functional.py restates it in torch.  In short, for a one-channel value x, in fp32 with every operation rounded on
+ * its own: depth panels x = clip((x - near) / f32(double(far) - double(near) + 1e-10), 0, 1) with near / far the record's planes where TN_FRAME_NEAR /
+ * TN_FRAME_FAR are set and the frame's min / max otherwise; with TN_FRAME_NORMALIZE x = (x - lo) / ((hi - lo) + 1e-9f) over the frame's min / max;
+ * x = clip(x f32(colormap_max - colormap_min) + colormap_min, 0, 1); with TN_FRAME_INVERT 1 - x; a NaN becomes 0; the colour is (x, x, x) without a
+ * table and row trunc(255 x) of the table [256,3] with one; depth panels with an accumulation a then colour a + (1 - a).  Three-channel panels pass
+ * through.  Bytes are trunc(clip(c, 0, 1) 255 + 0.5), a NaN gives 0.  Min and max are over the FINITE values of a frame, (0, 0) where there are none.
+ * Every entry point runs on the caller's stream without a host synchronisation and without atomics: the same inputs give the same bytes.  Refused with
+ * TN_EINVAL before any launch: null pointers (accumulation and table may be null; minmax only where the panel needs none), a panel count outside
+ * 1..TN_FRAME_MAX_PANELS, a channel count other than 1 or 3, sizes below 1 or frames of 2^31 bytes and more, misaligned pointers, a short workspace.
+ *
+ * tn_frame_minmax   out2 (DEVICE float[2]) = the finite min and max of src [n]: a pair per block and a fixed-order final pass, nothing is read back;
+ *                   workspace of TN_FRAME_MINMAX_WORKSPACE_BYTES
+ * tn_frame_compose  out_u8 [H, num_panels W, 3]: the panels (HOST array of records, each an [H,W,channels] image) side by side, in one launch; the
+ *                   records travel as kernel arguments, their tables are copied to LDS once per block
+ * tn_frame_colors   out_rgb [H,W,3] fp32: the colours of one panel before they become bytes (what a viewer takes) */
+#define TN_FRAME_MAX_PANELS 8
+#define TN_FRAME_MINMAX_WORKSPACE_BYTES 2048
+#define TN_FRAME_NORMALIZE 1
+#define TN_FRAME_INVERT 2
+#define TN_FRAME_DEPTH 4
+#define TN_FRAME_NEAR 8  /* near_plane is given (else the frame's min) */
+#define TN_FRAME_FAR 16  /* far_plane is given (else the frame's max) */
+typedef struct TnFramePanel {
+  const float* src;          /* DEVICE [H,W,channels] */
+  const float* accumulation; /* DEVICE [H,W] or NULL: depth panels blend over it */
+  const float* minmax;       /* DEVICE [2] (tn_frame_minmax of src) or NULL where the panel needs none */
+  const float* table;        /* DEVICE [256,3] or NULL (grey) */
+  double near_plane, far_plane;       /* doubles, as the reference's Python scalars are: far - near + 1e-10 is taken in double */
+  double colormap_min, colormap_max;  /* likewise colormap_max - colormap_min */
+  int32_t channels;          /* 1 or 3 */
+  int32_t flags;             /* TN_FRAME_* */
+} TnFramePanel;
+TN_API int tn_frame_minmax(const float* src, int64_t n, float* out2, void* workspace, int64_t workspace_bytes, tn_stream_t stream);
+TN_API int tn_frame_compose(const TnFramePanel* panels, int32_t num_panels, int32_t H, int32_t W, uint8_t* out_u8, tn_stream_t stream);
+TN_API int tn_frame_colors(const TnFramePanel* panel, int32_t H, int32_t W, float* out_rgb, tn_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

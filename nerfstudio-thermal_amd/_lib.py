@@ -19,6 +19,9 @@ TN_LOSS_LINES = 64
 TN_RENDER_TRAIN_OFFSETS = 25
 TN_SPLAT_POSE_CAMERA_FLOATS = 40  # the corrected-camera record of tn_splat_pose_camera
 TN_IMAGE_F32, TN_IMAGE_U8 = 0, 1  # tn_image_resize's input types, tn_image_undistort's input and output types
+TN_FRAME_MAX_PANELS = 8  # tn_frame_compose
+TN_FRAME_MINMAX_WORKSPACE_BYTES = 2048  # tn_frame_minmax
+TN_FRAME_NORMALIZE, TN_FRAME_INVERT, TN_FRAME_DEPTH, TN_FRAME_NEAR, TN_FRAME_FAR = 1, 2, 4, 8, 16  # TnFramePanel.flags
 TN_BWD_MLP, TN_BWD_SCATTER, TN_BWD_JOIN, TN_BWD_SCATTER_BIN, TN_BWD_SCATTER_FOLD, TN_BWD_FORK_DPOS, TN_BWD_COUNTERS_CLEAN = 1, 2, 4, 8, 16, 32, 64
 
 _p = C.c_void_p
@@ -117,6 +120,12 @@ class TnSplatCrop(C.Structure):
 class TnUndistort(C.Structure):
     """include/thermal_nerf_hip.h: the source camera, the pinhole camera of the output and k1 k2 k3 k4 p1 p2 (tn_image_undistort)"""
     _fields_ = [("fx", _f), ("fy", _f), ("cx", _f), ("cy", _f), ("new_fx", _f), ("new_fy", _f), ("new_cx", _f), ("new_cy", _f), ("k", _f * 6)]
+
+
+class TnFramePanel(C.Structure):
+    """include/thermal_nerf_hip.h: one panel of a frame (tn_frame_compose, tn_frame_colors)"""
+    _fields_ = [("src", _p), ("accumulation", _p), ("minmax", _p), ("table", _p), ("near_plane", _d), ("far_plane", _d), ("colormap_min", _d),
+                ("colormap_max", _d), ("channels", _i32), ("flags", _i32)]
 
 
 # name -> (restype, argtypes); must list every symbol include/thermal_nerf_hip.h declares
@@ -281,6 +290,9 @@ SIGNATURES = {
     "tn_texture_store": (C.c_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
     "tn_mesh_mean_edge_workspace_bytes": (_i64, [_i64]),
     "tn_mesh_mean_edge": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i64, _p]),
+    "tn_frame_minmax": (C.c_int, [_p, _i64, _p, _p, _i64, _p]),
+    "tn_frame_compose": (C.c_int, [C.POINTER(TnFramePanel), _i32, _i32, _i32, _p, _p]),
+    "tn_frame_colors": (C.c_int, [C.POINTER(TnFramePanel), _i32, _i32, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None
