@@ -183,6 +183,30 @@ TN_API int tn_pose_apply_fwd(const float* pose_adjustment, const uint8_t* frozen
 TN_API int tn_pose_apply_bwd(const float* pose_adjustment, const uint8_t* frozen, const int64_t* camera_indices, const float* directions_in,
                       const float* d_origins, const float* d_directions, int64_t N, int32_t num_cameras, float* grad_pose,
                       tn_stream_t stream);
+/* CameraOptimizer("shared_SO3xR3").apply_to_raybundle (cameras/camera_optimizers.py:108-117,150-163): ONE row shared_row [6] corrects every
+ * camera that is not frozen: origins_out = origins_in + t, directions_out = R directions_in with [R | t] = exp_map_SO3xR3(shared_row), the
+ * identity where frozen[camera] is set (frozen may be NULL: no camera is).  One launch; the exp map is evaluated once per block, with the device
+ * function tn_pose_apply_fwd uses per ray, so the result equals tn_pose_apply_fwd's on the row tiled to [C,6] bit for bit.  A camera index
+ * outside [0, C) reads camera 0's flag, as in tn_pose_apply_fwd.  N == 0: TN_OK, nothing is touched.  N outside [0, 2^32], num_cameras outside
+ * [1, 2^20] or a NULL pointer: TN_EINVAL before any launch. */
+TN_API int tn_pose_shared_apply(const float* shared_row, const uint8_t* frozen, const int64_t* camera_indices, const float* origins_in,
+                         const float* directions_in, int64_t N, int32_t num_cameras, float* origins_out, float* directions_out,
+                         tn_stream_t stream);
+/* backward of tn_pose_shared_apply, optionally through a per-camera correction applied on top of it (d2 = R_c d1, o2 = o1 + t_c):
+ * d_origins / d_directions [N,3] = the gradient of the rays the render saw; directions_in [N,3] = the directions tn_pose_shared_apply was
+ * given; pose_adjustment [C,6] = the per-camera rows applied behind it, or NULL (R_c = I: per-camera optimiser off, or an eval render).
+ *   grad_row[0:3] += sum d_origins,   grad_row[3:6] += sum J(shared_row; directions_in)^T (R_c^T d_directions)   over the rays of cameras
+ * that are not frozen (J: the derivative tn_pose_apply_bwd uses).  Deterministic: one launch sums per wave and per block, in double, into
+ * workspace (tn_pose_shared_bwd_workspace_bytes(N) bytes), a second single-block launch adds the blocks' sums in block order, in double, and
+ * adds the result to grad_row [6]; no floating-point atomics, the same inputs give the same bits.  With every camera frozen grad_row keeps
+ * its bits; N == 0: TN_OK, nothing is touched.  Range and pointer checks as tn_pose_shared_apply, plus a short workspace: TN_EINVAL before
+ * any launch.  GradScaler's found_inf: this entry point raises no flag -- the shared rows' optimiser groups are covered by the range check
+ * over the gradient arena (tn_grad_nonfinite_ranges), which the engine runs whenever a shared row is trained.  The regulariser of a shared
+ * row and its gradient: tn_camera_reg with num_cameras = 1. */
+TN_API int64_t tn_pose_shared_bwd_workspace_bytes(int64_t N);
+TN_API int tn_pose_shared_bwd(const float* shared_row, const uint8_t* frozen, const int64_t* camera_indices, const float* directions_in,
+                       const float* d_origins, const float* d_directions, const float* pose_adjustment, int64_t N, int32_t num_cameras,
+                       void* workspace, int64_t workspace_bytes, float* grad_row, tn_stream_t stream);
 
 /* ---- a6  UniformLinDispPiecewiseSampler / SpacedSampler.generate_ray_samples (model_components/ray_samplers.py:78-128,225-248).
  * lin_bins [S+1] = torch.linspace(0,1,S+1) supplied by the host; jitter [N] or NULL (eval). Outputs s_bins,e_bins [N,S+1]. */

@@ -143,6 +143,10 @@ SIGNATURES = {
     "tn_pose_bwd_finish_check": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, _f, _f, _f, _p, _p, _i32, _p, _p, _p, _i32, _p, _i32, _p]),
     "tn_pose_apply_fwd": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p]),
     "tn_pose_apply_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p]),
+    # shared (rig) pose correction: one row for every camera of a spectrum
+    "tn_pose_shared_apply": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p]),
+    "tn_pose_shared_bwd_workspace_bytes": (_i64, [_i64]),
+    "tn_pose_shared_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _p, _i64, _p, _p]),
     "tn_spaced_bins": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _p, _p, _p]),
     "tn_prop_density_fwd": (C.c_int, [C.POINTER(TnPropNet), _p, _p, _p, _i64, _i32, _p, _p]),
     "tn_prop_density_bwd": (C.c_int, [C.POINTER(TnPropNet), _p, _p, _p, _p, _i64, _i32, _p, _i64, _p, _p, _p]),

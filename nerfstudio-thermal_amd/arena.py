@@ -11,6 +11,8 @@ state_dict names) are views into it, so
 Layout order: [proposal_networks | fields | camera_opt | proposal_networks_thermal | fields_thermal | camera_opt_thermal].
 In shared mode the thermal proposal nets / thermal pose exist (the reference constructs them unconditionally,
 models/thermal_nerfacto.py:138-186) but belong to no optimiser group: they sit after the live range.
+With a shared (rig) correction enabled, [shared_camera_opt | shared_camera_opt_thermal] follow at the very end (one [1,6] row each); the live
+range then reaches to them.
 """
 from __future__ import annotations
 
@@ -20,7 +22,7 @@ from typing import Dict, List, Tuple
 
 import torch
 
-from .config import ThermalNerfactoModelConfig
+from .config import ThermalNerfactoModelConfig, shared_pose_enabled
 
 
 def field_shapes(prefix: str, cfg: ThermalNerfactoModelConfig, num_images: int, channels: int) -> "OrderedDict[str, Tuple[int, ...]]":
@@ -88,9 +90,16 @@ class ParamArena:
         groups["camera_opt_thermal"] = (
             OrderedDict([("camera_optimizer_thermal.pose_adjustment", (num_images, 6))]) if cfg.camera_optimizer_thermal.mode != "off" else OrderedDict()
         )
+        # the shared (rig) corrections, one [1,6] row per spectrum: only when enabled, and behind every other group -- no other offset moves,
+        # switch on or off.  (The thermal row is the thermal branch's: separate mode only, as its optimiser group in the reference.)
+        shared_on = {sfx: shared_pose_enabled(getattr(cfg, "shared_camera_optimizer" + sfx)) and (separate or not sfx) for sfx in ("", "_thermal")}
+        for sfx in ("", "_thermal"):
+            if shared_on[sfx]:
+                groups["shared_camera_opt" + sfx] = OrderedDict([(f"shared_camera_optimizer{sfx}.pose_adjustment", (1, 6))])
         self.optimised_groups: List[str] = ["proposal_networks", "fields", "camera_opt"]
         if separate:
             self.optimised_groups += ["proposal_networks_thermal", "fields_thermal", "camera_opt_thermal"]
+        self.optimised_groups += [g for g in ("shared_camera_opt", "shared_camera_opt_thermal") if g in groups]
         self.optimised_groups = [g for g in self.optimised_groups if groups[g]]
         self.layout: "OrderedDict[str, Tuple[int, Tuple[int, ...]]]" = OrderedDict()
         self.group_range: Dict[str, Tuple[int, int]] = {}

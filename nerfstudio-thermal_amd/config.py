@@ -19,6 +19,12 @@ class CameraOptimizerConfig:
     scheduler: Optional[object] = None
 
 
+def shared_pose_enabled(co: CameraOptimizerConfig) -> bool:
+    """A shared (rig) camera optimiser that is switched on: CameraOptimizer turns a negative penalty_scale into mode "off"
+    (cameras/camera_optimizers.py:105-106), and that is the reference default."""
+    return co.mode != "off" and co.penalty_scale >= 0
+
+
 def _default_prop_args() -> List[Dict]:
     return [
         {"hidden_dim": 16, "log2_hashmap_size": 17, "num_levels": 5, "max_res": 128, "use_linear": False},
@@ -129,8 +135,8 @@ class ThermalNerfactoModelConfig:
             bad.append("at most 256 samples per ray per level")
         for name in ("shared_camera_optimizer", "shared_camera_optimizer_thermal"):
             co = getattr(self, name)
-            if co.mode != "off" and co.penalty_scale >= 0:
-                bad.append(f"{name} enabled (reference default is off)")
+            if shared_pose_enabled(co) and co.mode != "shared_SO3xR3":
+                bad.append(f"{name}.mode must be 'off' or 'shared_SO3xR3'")
         for name in ("camera_optimizer", "camera_optimizer_thermal"):
             if getattr(self, name).mode not in ("off", "SO3xR3"):
                 bad.append(f"{name}.mode must be 'off' or 'SO3xR3'")

@@ -415,6 +415,14 @@ extern "C" int tn_sample_rays_args(const TnSampleRays* s, tn_stream_t stream) {
 // ------------------------------------------------------------------------------------------------ pose correction
 // (Pose, pose_exp -- exp_map_SO3xR3 -- and its derivative pose_exp_bwd: tn_pose_finish.h)
 
+// one ray through an evaluated pose: o + t, R d (the per-camera path evaluates the pose per ray, the shared path once per block)
+__device__ __forceinline__ void pose_transform_ray(const Pose& p, float ox, float oy, float oz, float dx, float dy, float dz, float (&o)[3],
+                                                   float (&d)[3]) {
+  o[0] = ox + p.t[0]; o[1] = oy + p.t[1]; o[2] = oz + p.t[2];
+  d[0] = p.R[0] * dx + p.R[1] * dy + p.R[2] * dz;
+  d[1] = p.R[3] * dx + p.R[4] * dy + p.R[5] * dz;
+  d[2] = p.R[6] * dx + p.R[7] * dy + p.R[8] * dz;
+}
 // one ray: prow = the camera's pose row, is_frozen = a non-trainable camera (identity)
 __device__ __forceinline__ void pose_apply_ray(const float (&prow)[6], bool is_frozen, float ox, float oy, float oz, float dx, float dy, float dz,
                                                float (&o)[3], float (&d)[3]) {
@@ -424,11 +432,7 @@ __device__ __forceinline__ void pose_apply_ray(const float (&prow)[6], bool is_f
     d[0] = dx; d[1] = dy; d[2] = dz;
     return;
   }
-  Pose p = pose_exp(prow);
-  o[0] = ox + p.t[0]; o[1] = oy + p.t[1]; o[2] = oz + p.t[2];
-  d[0] = p.R[0] * dx + p.R[1] * dy + p.R[2] * dz;
-  d[1] = p.R[3] * dx + p.R[4] * dy + p.R[5] * dz;
-  d[2] = p.R[6] * dx + p.R[7] * dy + p.R[8] * dz;
+  pose_transform_ray(pose_exp(prow), ox, oy, oz, dx, dy, dz, o, d);
 }
 __device__ __forceinline__ void pose_fwd_body(const float* __restrict__ pose, const uint8_t* __restrict__ frozen, const int64_t* __restrict__ cam_idx,
                                               const float* __restrict__ o_in, const float* __restrict__ d_in, int64_t N, int C,
@@ -626,6 +630,147 @@ extern "C" int tn_camera_reg(const float* pose_adjustment, int32_t num_cameras, 
   TN_REQUIRE(pose_adjustment && loss_out && num_cameras >= 1, "tn_camera_reg: bad argument");
   hipLaunchKernelGGL(k_camera_reg, dim3(1), dim3(256), 0, tn_s(stream), pose_adjustment, num_cameras, trans_pen, rot_pen, scale, loss_out, grad_pose);
   TN_CHECK_LAUNCH("tn_camera_reg");
+  return TN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ shared (rig) pose correction
+// CameraOptimizer("shared_SO3xR3"): one row for every camera of a spectrum (cameras/camera_optimizers.py:108-117, 150-163).  Both kernels are
+// streaming passes over the rays; what depends on the row alone (the pose, the derivative's factors) is evaluated by one thread per block.
+#define POSE_SHARED_MAX_BLOCKS 1024
+#define POSE_SHARED_MAX_RAYS (1LL << 32)
+#define POSE_SHARED_MAX_CAMERAS (1 << 20)
+__global__ void __launch_bounds__(256) k_pose_shared_fwd(const float* __restrict__ row, const uint8_t* __restrict__ frozen,
+                                                         const int64_t* __restrict__ cam_idx, const float* __restrict__ o_in,
+                                                         const float* __restrict__ d_in, int64_t N, int C, float* __restrict__ o_out,
+                                                         float* __restrict__ d_out) {
+  __shared__ Pose sp;
+  if (threadIdx.x == 0) {
+    float prow[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) prow[q] = row[q];
+    sp = pose_exp(prow);
+  }
+  __syncthreads();
+  const Pose p = sp;  // (every lane reads the same 12 words: LDS broadcasts)
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t cam = cam_idx[i];
+    if (cam < 0 || cam >= C) cam = 0;
+    float ox = o_in[i * 3], oy = o_in[i * 3 + 1], oz = o_in[i * 3 + 2];
+    float dx = d_in[i * 3], dy = d_in[i * 3 + 1], dz = d_in[i * 3 + 2];
+    float o[3], d[3];
+    if (frozen != nullptr && frozen[cam]) {
+      // identity transform: origins + 0, bmm(I, d) -- as pose_apply_ray
+      o[0] = ox + 0.0f; o[1] = oy + 0.0f; o[2] = oz + 0.0f;
+      d[0] = dx; d[1] = dy; d[2] = dz;
+    } else {
+      pose_transform_ray(p, ox, oy, oz, dx, dy, dz, o, d);
+    }
+    o_out[i * 3] = o[0]; o_out[i * 3 + 1] = o[1]; o_out[i * 3 + 2] = o[2];
+    d_out[i * 3] = d[0]; d_out[i * 3 + 1] = d[1]; d_out[i * 3 + 2] = d[2];
+  }
+}
+
+static int pose_shared_check(const char* who, int64_t N, int32_t num_cameras) {
+  TN_REQUIRE(N >= 0 && N <= POSE_SHARED_MAX_RAYS && num_cameras >= 1 && num_cameras <= POSE_SHARED_MAX_CAMERAS, "%s: bad N=%lld C=%d", who,
+             (long long)N, num_cameras);
+  return TN_OK;
+}
+static unsigned pose_shared_blocks(int64_t N) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(tn_cdiv(N, 256), POSE_SHARED_MAX_BLOCKS)); }
+
+extern "C" int tn_pose_shared_apply(const float* shared_row, const uint8_t* frozen, const int64_t* camera_indices, const float* origins_in,
+                                    const float* directions_in, int64_t N, int32_t num_cameras, float* origins_out, float* directions_out,
+                                    tn_stream_t stream) {
+  int rc = pose_shared_check("tn_pose_shared_apply", N, num_cameras);
+  if (rc) return rc;
+  if (N == 0) return TN_OK;  // empty batches are valid and touch nothing
+  TN_REQUIRE(shared_row && camera_indices && origins_in && directions_in && origins_out && directions_out, "tn_pose_shared_apply: null pointer");
+  hipLaunchKernelGGL(k_pose_shared_fwd, dim3(pose_shared_blocks(N)), dim3(256), 0, tn_s(stream), shared_row, frozen, camera_indices, origins_in,
+                     directions_in, N, num_cameras, origins_out, directions_out);
+  TN_CHECK_LAUNCH("tn_pose_shared_apply");
+  return TN_OK;
+}
+
+// The row's gradient, pass 1: every ray's contribution (t: g_o; w: the exp map's derivative applied to G = (R_c^T g_d) (outer) d0), summed in
+// double per wave (butterfly: a fixed order) and over the block's four waves in wave order -> partials[block][6].
+__global__ void __launch_bounds__(256) k_pose_shared_bwd_partial(const float* __restrict__ row, const uint8_t* __restrict__ frozen,
+                                                                 const int64_t* __restrict__ cam_idx, const float* __restrict__ d_in,
+                                                                 const float* __restrict__ g_o, const float* __restrict__ g_d,
+                                                                 const float* __restrict__ pose, int64_t N, int C, double* __restrict__ partials) {
+  __shared__ PoseExpFactors sf;
+  __shared__ double sw[4][6];
+  const float v[3] = {row[3], row[4], row[5]};
+  if (threadIdx.x == 0) sf = pose_exp_factors(v);
+  __syncthreads();
+  const PoseExpFactors e = sf;
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t cam = cam_idx[i];
+    if (cam < 0 || cam >= C) cam = 0;
+    if (frozen != nullptr && frozen[cam]) continue;
+    float gd[3] = {g_d[i * 3], g_d[i * 3 + 1], g_d[i * 3 + 2]};
+    if (pose != nullptr) {  // d2 = R_c d1: the gradient of d1 is R_c^T g_d2
+      float prow[6];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) prow[q] = pose[cam * 6 + q];
+      const Pose pc = pose_exp(prow);
+      const float a = gd[0], b = gd[1], c = gd[2];
+      gd[0] = pc.R[0] * a + pc.R[3] * b + pc.R[6] * c;
+      gd[1] = pc.R[1] * a + pc.R[4] * b + pc.R[7] * c;
+      gd[2] = pc.R[2] * a + pc.R[5] * b + pc.R[8] * c;
+    }
+    const float dd[3] = {d_in[i * 3], d_in[i * 3 + 1], d_in[i * 3 + 2]};
+    float G[9];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) G[a * 3 + b] = gd[a] * dd[b];
+    float dv[3];
+    pose_exp_bwd(v, e, G, dv);
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      acc[m] += (double)g_o[i * 3 + m];
+      acc[3 + m] += (double)dv[m];
+    }
+  }
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+    const double r = tn_wave_sum_d(acc[q]);
+    if (tn_lane() == 0) sw[wave][q] = r;
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) partials[(int64_t)blockIdx.x * 6 + threadIdx.x] = ((sw[0][threadIdx.x] + sw[1][threadIdx.x]) + sw[2][threadIdx.x]) + sw[3][threadIdx.x];
+}
+// pass 2: the blocks' sums in block order (double), added to the gradient row once
+__global__ void __launch_bounds__(64) k_pose_shared_bwd_fold(const double* __restrict__ partials, int nblk, float* __restrict__ grad_row) {
+  if (threadIdx.x >= 6) return;
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += partials[(int64_t)b * 6 + threadIdx.x];
+  grad_row[threadIdx.x] += (float)s;
+}
+
+extern "C" int64_t tn_pose_shared_bwd_workspace_bytes(int64_t N) {
+  if (N < 0 || N > POSE_SHARED_MAX_RAYS) return TN_EINVAL;
+  return (int64_t)pose_shared_blocks(N) * 6 * (int64_t)sizeof(double);
+}
+
+extern "C" int tn_pose_shared_bwd(const float* shared_row, const uint8_t* frozen, const int64_t* camera_indices, const float* directions_in,
+                                  const float* d_origins, const float* d_directions, const float* pose_adjustment, int64_t N, int32_t num_cameras,
+                                  void* workspace, int64_t workspace_bytes, float* grad_row, tn_stream_t stream) {
+  int rc = pose_shared_check("tn_pose_shared_bwd", N, num_cameras);
+  if (rc) return rc;
+  if (N == 0) return TN_OK;  // empty batches are valid and touch nothing
+  TN_REQUIRE(shared_row && camera_indices && directions_in && d_origins && d_directions && workspace && grad_row, "tn_pose_shared_bwd: null pointer");
+  const unsigned nb = pose_shared_blocks(N);
+  TN_REQUIRE(workspace_bytes >= tn_pose_shared_bwd_workspace_bytes(N) && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
+             "tn_pose_shared_bwd: workspace of %lld bytes, tn_pose_shared_bwd_workspace_bytes needs %lld (8-byte aligned)", (long long)workspace_bytes,
+             (long long)tn_pose_shared_bwd_workspace_bytes(N));
+  double* partials = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(k_pose_shared_bwd_partial, dim3(nb), dim3(256), 0, tn_s(stream), shared_row, frozen, camera_indices, directions_in, d_origins,
+                     d_directions, pose_adjustment, N, num_cameras, partials);
+  TN_CHECK_LAUNCH("tn_pose_shared_bwd");
+  hipLaunchKernelGGL(k_pose_shared_bwd_fold, dim3(1), dim3(64), 0, tn_s(stream), partials, (int)nb, grad_row);
+  TN_CHECK_LAUNCH("tn_pose_shared_bwd (fold)");
   return TN_OK;
 }
 

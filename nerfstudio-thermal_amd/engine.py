@@ -16,7 +16,7 @@ from torch import Tensor
 
 from . import ops
 from .arena import ParamArena
-from .config import ThermalNerfactoModelConfig
+from .config import ThermalNerfactoModelConfig, shared_pose_enabled
 from .netparams import field_params, prop_params
 
 # timing experiments: TN_FUSE_SMALL=0 runs the small operators through one entry point per reference seam (tn_weights_fwd, tn_composite_fwd,
@@ -49,7 +49,7 @@ class Branch:
 
     origins: Tensor
     directions: Tensor
-    origins_in: Tensor
+    origins_in: Tensor     # the rays the per-camera correction was applied to (behind the shared correction, when there is one)
     directions_in: Tensor
     levels: List[Level]
     rgb_samples: Tensor  # [N,S,C] per-sample colours
@@ -63,6 +63,7 @@ class Branch:
     d_origins: Optional[Tensor] = None     # [N,3] gradient of the pose-corrected rays, summed by the backward launches (None: no pose to refine)
     d_directions: Optional[Tensor] = None  # [N,3]
     pose_done: bool = False                # the pose gradient was finished early (data-parallel schedule, step without a proposal update)
+    directions_raw: Optional[Tensor] = None  # [N,3] the directions the SHARED correction was applied to (None: no shared row on this branch)
 
 
 @dataclass
@@ -82,6 +83,11 @@ class BranchNets:
     g_props: str
     g_camera: str
     table_key: str               # arena key of the main hash table
+    shared: Optional[Tensor] = None       # shared (rig) camera optimiser's pose_adjustment [1,6], None when it is off
+    shared_grad: Optional[Tensor] = None
+    shared_opt: object = None             # its CameraOptimizerConfig
+    shared_slot: int = 0                  # index of its regulariser in the loss vector: 13 / 14
+    g_shared: str = ""                    # its optimiser group
 
 
 def exp_decay_lr(step: int, lr_init: float, lr_final: float, max_steps: int) -> float:
@@ -98,6 +104,8 @@ OPTIMIZERS = {
     "fields_thermal": (1e-2, 1e-4, 200000),
     "camera_opt": (1e-3, 1e-4, 5000),
     "camera_opt_thermal": (1e-3, 1e-4, 5000),
+    "shared_camera_opt": (1e-3, 1e-4, 5000),
+    "shared_camera_opt_thermal": (1e-3, 1e-4, 5000),
 }
 
 
@@ -114,7 +122,12 @@ class RenderEngine:
             co = cfg.camera_optimizer_thermal if sfx else cfg.camera_optimizer
             pose_key = f"camera_optimizer{sfx}.pose_adjustment"
             pose = arena.view(pose_key) if co.mode != "off" else None
+            sco = getattr(cfg, "shared_camera_optimizer" + sfx)
+            shared_key = f"shared_camera_optimizer{sfx}.pose_adjustment"
+            shared = arena.view(shared_key) if (shared_pose_enabled(sco) and shared_key in arena.layout) else None
             return BranchNets(
+                shared=shared, shared_grad=arena.grad_view(shared_key) if shared is not None else None, shared_opt=sco,
+                shared_slot=14 if sfx else 13, g_shared="shared_camera_opt" + sfx,
                 sfx=sfx, props=[prop_params(arena, "proposal_networks" + sfx, i, cfg, with_grads=True) for i in range(2)],
                 field=field_params(arena, "field" + sfx, cfg, with_grads=True) if with_field else None,
                 pose=pose, pose_grad=arena.grad_view(pose_key) if pose is not None else None,
@@ -130,6 +143,8 @@ class RenderEngine:
         self.props, self.field, self.pose, self.pose_grad, self.frozen_rgb = rgb.props, rgb.field, rgb.pose, rgb.pose_grad, rgb.frozen
         self.props_thermal, self.field_thermal, self.frozen_thermal = thermal.props, thermal.field, thermal.frozen
         self.pose_thermal, self.pose_thermal_grad = thermal.pose, thermal.pose_grad
+        # a shared (rig) correction on any branch: the paths that bake in "the only pose is the per-camera one" are bypassed (train_step)
+        self.shared_on = any(bn.shared is not None for bn in self.nets.values())
         self.counts = list(cfg.num_proposal_samples_per_ray) + [cfg.num_nerf_samples_per_ray]
         # ProposalNetworkSampler state (model_components/ray_samplers.py:564-575)
         self.anneal = 1.0
@@ -212,7 +227,21 @@ class RenderEngine:
     # ---------------------------------------------------------------- forward of one branch
     def render_branch(self, props, fld, pose, frozen, origins: Tensor, directions: Tensor, cam: Tensor, nears: Tensor, fars: Tensor,
                       training: bool, anneal: float, jitters: Optional[List[Tensor]], prop_grad: bool, tag: str = "main", wait_event=None,
-                      zero_fill: Optional[Tensor] = None) -> Branch:
+                      zero_fill: Optional[Tensor] = None, shared: Optional[Tensor] = None) -> Branch:
+        """shared: the branch's shared (rig) row [1,6] or None.  It is applied first, in training and at inference; the per-camera correction
+        (training only) then takes the corrected rays as its input, so Branch.directions_in is what the per-camera backward differentiates
+        against and Branch.directions_raw what the shared one does."""
+        d_raw = None
+        if shared is not None:
+            d_raw = directions
+            origins, directions = ops.pose_shared_apply(shared, frozen, cam, origins, directions)
+        b = self._render_branch(props, fld, pose, frozen, origins, directions, cam, nears, fars, training, anneal, jitters, prop_grad, tag, wait_event,
+                                zero_fill)
+        b.directions_raw = d_raw
+        return b
+
+    def _render_branch(self, props, fld, pose, frozen, origins: Tensor, directions: Tensor, cam: Tensor, nears: Tensor, fars: Tensor,
+                       training: bool, anneal: float, jitters: Optional[List[Tensor]], prop_grad: bool, tag: str, wait_event, zero_fill) -> Branch:
         o_in, d_in = origins, directions
         if training and _FUSE:
             # the whole training forward of the branch as ONE call of the C ABI (tn_render_rays_train): the library enqueues the eight
@@ -259,8 +288,12 @@ class RenderEngine:
         return Branch(origins=origins, directions=directions, origins_in=o_in, directions_in=d_in, levels=levels, rgb_samples=rgb, comp=comp,
                       accumulation=acc, depth=med, expected_depth=exp, prop_grad=prop_grad)
 
-    def render_branch_eval(self, props, fld, origins: Tensor, directions: Tensor, cam: Tensor, nears: Tensor, fars: Tensor, anneal: float) -> Branch:
-        """render_branch at inference as ONE call of the C ABI (tn_render_rays_eval: the library enqueues the launches back to back)."""
+    def render_branch_eval(self, props, fld, origins: Tensor, directions: Tensor, cam: Tensor, nears: Tensor, fars: Tensor, anneal: float,
+                           shared: Optional[Tensor] = None, frozen: Optional[Tensor] = None) -> Branch:
+        """render_branch at inference as ONE call of the C ABI (tn_render_rays_eval: the library enqueues the launches back to back).
+        shared (+ frozen): the branch's shared (rig) row, applied to the rays first -- the ray's camera index decides whether it is frozen."""
+        if shared is not None:
+            origins, directions = ops.pose_shared_apply(shared, frozen, cam, origins, directions)
         r = ops.render_rays_eval(props, fld, origins, directions, cam, nears, fars, self.counts, anneal)
         med = [r["prop_depth_0"], r["prop_depth_1"], r["depth"]]
         levels = [Level(S=S, s_bins=lv["s_bins"], e_bins=lv["e_bins"], density=lv["density"], weights=lv["weights"], median=med[i])
@@ -300,7 +333,7 @@ class RenderEngine:
             if prop_grads[sfx]:
                 for i in range(2):
                     zkeys.append((f"dw{i}", sfx)); zshapes.append((N, self.counts[i]))
-            if bn.pose is not None:
+            if bn.pose is not None or bn.shared is not None:
                 zkeys.append(("d_o", sfx)); zshapes.append((N, 3))
                 zkeys.append(("d_d", sfx)); zshapes.append((N, 3))
         if self.separate and self.cfg.density_loss_mult > 0:  # the density loss's four gradient buffers (tn_l1_loss accumulates into them)
@@ -346,10 +379,11 @@ class RenderEngine:
             views, zero_fill = self._zeros_many(shapes, fill=False)
             self._step_acc = (N, keys, dict(zip(keys, views)))
         if not training and _FUSE:
-            b = self.render_branch_eval(self.props, self.field, origins, directions, cam, nears, fars, self.anneal)
+            b = self.render_branch_eval(self.props, self.field, origins, directions, cam, nears, fars, self.anneal, shared=self.nets[""].shared,
+                                        frozen=self.frozen_rgb)
         else:
             b = self.render_branch(self.props, self.field, self.pose, self.frozen_rgb, origins, directions, cam, nears, fars, training, self.anneal,
-                                   jitters, prop_grad=updated, wait_event=wait_ev, zero_fill=zero_fill)
+                                   jitters, prop_grad=updated, wait_event=wait_ev, zero_fill=zero_fill, shared=self.nets[""].shared)
         self.last_updated = bool(updated)
         if updated:  # eval renders included, as ProposalNetworkSampler.generate_ray_samples does (ray_samplers.py:612-613)
             self.steps_since_update = 0
@@ -365,10 +399,11 @@ class RenderEngine:
             jitters_thermal = list(self._uniforms().take((3, N)).unbind(0))
         # thermal sampler: never receives step_cb -> anneal stays 1.0 and always "updated" (models/thermal_nerfacto.py:222-250)
         if not training and _FUSE:
-            bt = self.render_branch_eval(self.props_thermal, self.field_thermal, origins, directions, cam, nears, fars, 1.0)
+            bt = self.render_branch_eval(self.props_thermal, self.field_thermal, origins, directions, cam, nears, fars, 1.0,
+                                         shared=self.nets["_thermal"].shared, frozen=self.frozen_thermal)
         else:
             bt = self.render_branch(self.props_thermal, self.field_thermal, self.pose_thermal, self.frozen_thermal, origins, directions, cam, nears,
-                                    fars, training, 1.0, jitters_thermal, prop_grad=True)
+                                    fars, training, 1.0, jitters_thermal, prop_grad=True, shared=self.nets["_thermal"].shared)
         out.update(self._branch_outputs(bt, "_thermal", training))
         branches["_thermal"] = bt
         if self.cfg.density_loss_mult > 0 or not training:
@@ -410,7 +445,7 @@ class RenderEngine:
         pipelined = dp is not None and not self.separate
         for sfx, br in branches.items():
             bn = self.nets[sfx]
-            if bn.pose is not None:  # (cross-evaluation gradients are added to the same two tensors before the pose backward)
+            if bn.pose is not None or bn.shared is not None:  # (cross-evaluation gradients are added to the same two tensors before the pose backward)
                 br.d_origins, br.d_directions = Z[("d_o", sfx)], Z[("d_d", sfx)]
             dc, dws, extra = Z[("d_comp", sfx)], grads_w[sfx], d_dens_extra.get(sfx)
             if pipelined:
@@ -564,7 +599,9 @@ class RenderEngine:
         t0 = self.arena.layout[bn.table_key][0]
         # (d position in line: one stream less -- see above)
         ops.field_bwd_phase(*args, ph.TN_BWD_MLP)
-        if _FUSE and bn.pose is not None and not br.prop_grad:
+        # (not with a shared (rig) row: its gradient is finished behind the per-camera one at the end of the backward, and the arena's tail --
+        # where the row lives -- goes out with dp.finish())
+        if _FUSE and bn.pose is not None and not br.prop_grad and bn.shared is None:
             # Nothing else adds to d origins / d directions on a step without a proposal update: the pose gradient (+ the loss sums and
             # the camera regulariser) can be finished NOW, and with it everything behind the table in the arena is final -- MLP
             # weights, embedding, pose.  Their exchange goes out here, hidden behind the scatter, instead of as one more collective
@@ -654,6 +691,21 @@ class RenderEngine:
         if not finished:
             ops.losses_finish(Lp, L)
         self._kernel_flags_done = bool(handled) and handled == {g for g in self.arena.optimised_groups if g.startswith("camera_opt")}
+        if self.shared_on:
+            self._shared_pose_finish(branches, cam, L)
+
+    def _shared_pose_finish(self, branches: Dict[str, Branch], cam: Tensor, L: Tensor) -> None:
+        """Behind the per-camera finish: every shared (rig) row's gradient -- the rays' gradient pulled back through the per-camera rotation
+        that was applied on top of the shared correction -- and its regulariser (tn_camera_reg over the one row).  The shared rows raise no
+        found_inf flag of their own: optimizer_step runs the range check over the arena when one is trained."""
+        for sfx, br in branches.items():
+            bn = self.nets[sfx]
+            if bn.shared is None:
+                continue
+            so = bn.shared_opt
+            ops.pose_shared_bwd(bn.shared, bn.frozen, cam, br.directions_raw, br.d_origins, br.d_directions, bn.pose, bn.shared_grad)
+            ops.camera_reg(bn.shared, so.trans_l2_penalty, so.rot_l2_penalty, so.penalty_scale, L[bn.shared_slot:bn.shared_slot + 1], bn.shared_grad)
+        self._kernel_flags_done = False
 
     def _loss_dict(self, L: Tensor) -> Dict[str, Tensor]:
         """get_loss_dict's entries as views of the loss vector"""
@@ -664,6 +716,9 @@ class RenderEngine:
         for sfx, bn in self.nets.items():
             if bn.pose is not None:
                 losses["camera_opt_regularizer" + sfx] = L[bn.reg_slot]
+        for sfx, bn in self.nets.items():
+            if bn.shared is not None:
+                losses["camera_opt_regularizer_shared" + sfx] = L[bn.shared_slot]
         return losses
 
     def _table_floats(self, fld) -> int:
@@ -678,7 +733,7 @@ class RenderEngine:
         a = self.arena
         out: List[Tuple[int, int, int]] = []
         for gi, g in enumerate(a.optimised_groups):
-            if g.startswith("camera_opt"):
+            if g.startswith("camera_opt") or g.startswith("shared_camera_opt"):  # (the shared rows: the range check of optimizer_step)
                 continue
             cur = None
             for name in sorted(a.group_keys[g], key=lambda n: a.layout[n][0]):
@@ -808,7 +863,9 @@ class RenderEngine:
             gidx = {g: i for i, g in enumerate(a.optimised_groups)}
             pieces = []
             for lo, hi in ranges:  # (the generator waits for every exchange on the stream as it yields)
-                gname = next(g for g in a.optimised_groups if a.group_range[g][0] <= lo and hi <= a.group_range[g][1])
+                # (None: a stretch of the live range that belongs to no optimised group -- shared mode's thermal proposal networks, which lie
+                # between the camera optimiser and a shared (rig) row at the arena's end)
+                gname = next((g for g in a.optimised_groups if a.group_range[g][0] <= lo and hi <= a.group_range[g][1]), None)
                 if gname in hyper and hi > lo:
                     pieces.append((lo, hi, gname))
             if len(pieces) > 8:
@@ -831,7 +888,7 @@ class RenderEngine:
                 grad_scaler.update()
             return
         for lo, hi in ranges:  # each range lies inside one optimiser group (Adam is element-wise: any partition of a group is the same update)
-            gname = next(g for g in a.optimised_groups if a.group_range[g][0] <= lo and hi <= a.group_range[g][1])
+            gname = next((g for g in a.optimised_groups if a.group_range[g][0] <= lo and hi <= a.group_range[g][1]), None)
             if gname not in hyper:
                 continue
             step, lr = hyper[gname]
@@ -989,6 +1046,15 @@ class RenderEngine:
             ops.train_metrics(dummy, 4, 1.0, poses, m)
             for k, sfx in enumerate(("", "_thermal")[:len(poses)]):
                 out[f"camera_opt_translation{sfx}"], out[f"camera_opt_rotation{sfx}"] = m[2 + 2 * k], m[3 + 2 * k]
+        shared = [(sfx, bn.shared) for sfx, bn in self.nets.items() if bn.shared is not None]
+        if shared:  # the shared (rig) rows' norms: the same launch once more, over the [1,6] rows
+            dummy = self._metric_ones
+            if dummy is None:
+                dummy = self._metric_ones = torch.ones(16, device=self.device)
+            m = torch.empty(8, device=self.device)
+            ops.train_metrics(dummy, 4, 1.0, [p for _, p in shared], m)
+            for k, (sfx, _) in enumerate(shared):
+                out[f"camera_opt_translation_shared{sfx}"], out[f"camera_opt_rotation_shared{sfx}"] = m[2 + 2 * k], m[3 + 2 * k]
         return out
 
     def train_metrics(self, pose_metrics: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
@@ -1028,7 +1094,7 @@ class RenderEngine:
             self.sync_params()
             self.arena.zero_grad()
         if (_ONE_CALL_STEP and _FUSE and _ONE_CALL_BWD and kflags is not None and scheduled and not self.separate and self.pose is not None
-                and not self.overlap_adam and self.scatter_events is None
+                and not self.overlap_adam and self.scatter_events is None and not self.shared_on  # (a shared row: tn_train_step knows one pose only)
                 and self.field.num_channels == 4 and "camera_opt" in self.arena.optimised_groups):
             losses = self._train_step_one_call(origins, directions, cam, image, is_thermal, jitters, grad_scaler, step)
             self._set_grad_zero(False)  # the promise holds for this iteration's scatters only (anybody may call the ops on these grids next)

@@ -13,7 +13,7 @@ models/thermal_nerfacto.py:67-564) over the HIP hot path.
 from __future__ import annotations
 
 from collections import defaultdict
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from enum import Enum, auto
 from typing import Any, Callable, Dict, List, Optional
 
@@ -24,7 +24,7 @@ from torch import Tensor, nn
 from . import autograd_ops as F
 from . import ops
 from .arena import ParamArena
-from .config import ThermalNerfactoModelConfig
+from .config import ThermalNerfactoModelConfig, shared_pose_enabled
 from .engine import RenderEngine
 from .model_components import (
     AccumulationRenderer,
@@ -171,7 +171,7 @@ class _RenderFn(torch.autograd.Function):
         for sfx, br in branches.items():
             g_comp, g_dens, g_w = per[sfx]
             bn = eng.nets[sfx]
-            if bn.pose is not None:
+            if bn.pose is not None or bn.shared is not None:
                 br.d_origins, br.d_directions = torch.zeros((N, 3), device=dev), torch.zeros((N, 3), device=dev)
             dw2 = (g_w[2][..., 0].contiguous() if g_w[2] is not None else z(br.levels[2].weights))  # read only (tn_render_bwd)
             d_comp = g_comp.contiguous() if g_comp is not None else z(br.comp)
@@ -201,6 +201,8 @@ class _RenderFn(torch.autograd.Function):
             bn = eng.nets[sfx]
             if bn.pose is not None:
                 ops.pose_apply_bwd(bn.pose, bn.frozen, cam, br.directions_in, br.d_origins, br.d_directions, bn.pose_grad)
+            if bn.shared is not None:  # the shared (rig) row: the same ray gradients, pulled back through the per-camera rotation
+                ops.pose_shared_bwd(bn.shared, bn.frozen, cam, br.directions_raw, br.d_origins, br.d_directions, bn.pose, bn.shared_grad)
         # Hand the arena's gradient views to autograd as the parameters' gradients.  None (= "no gradient", as under the reference's no_grad)
         # for every parameter this step did not differentiate: the proposal networks on iterations where the sampler did not update them
         # (ray_samplers.py:591,605-610) and the thermal twins that shared mode never evaluates -- torch.optim.Adam skips a parameter whose
@@ -215,6 +217,7 @@ class _RenderFn(torch.autograd.Function):
                 bn = eng.nets[sfx]
                 live.update(arena.group_keys[bn.g_fields])
                 live.update(arena.group_keys[bn.g_camera])
+                live.update(arena.group_keys.get(bn.g_shared, ()))
                 if pgrad:
                     live.update(arena.group_keys[bn.g_props])
             hit = cache[key] = (ctx.names, [i for i, n in enumerate(ctx.names) if n in live])
@@ -307,8 +310,16 @@ class ThermalNerfactoModel(nn.Module):
                                                 pose_param=self._params.get("camera_optimizer.pose_adjustment"))
         self.camera_optimizer_thermal = CameraOptimizer(cfg.camera_optimizer_thermal, self.num_train_data, self._device, th_frozen,
                                                         pose_param=self._params.get("camera_optimizer_thermal.pose_adjustment"), suffix="_thermal")
-        self.shared_camera_optimizer = CameraOptimizer(cfg.shared_camera_optimizer, self.num_train_data, self._device, rgb_frozen, suffix="_shared")
-        self.shared_camera_optimizer_thermal = CameraOptimizer(cfg.shared_camera_optimizer_thermal, self.num_train_data, self._device, th_frozen,
+        # the shared (rig) corrections: one [1,6] row per spectrum, applied in training AND evaluation (models/thermal_nerfacto.py:145-158, 403-434).
+        # The thermal row belongs to the thermal branch: in shared-density mode it is never applied and has no optimiser group, and here it is
+        # not built (penalty_scale -1 switches it off: the construction below must not see a mode without a parameter).
+        sco_t = cfg.shared_camera_optimizer_thermal
+        if shared_pose_enabled(sco_t) and cfg.density_mode != "separate":
+            sco_t = replace(sco_t, penalty_scale=-1)
+        self.shared_camera_optimizer = CameraOptimizer(cfg.shared_camera_optimizer, self.num_train_data, self._device, rgb_frozen,
+                                                       pose_param=self._params.get("shared_camera_optimizer.pose_adjustment"), suffix="_shared")
+        self.shared_camera_optimizer_thermal = CameraOptimizer(sco_t, self.num_train_data, self._device, th_frozen,
+                                                               pose_param=self._params.get("shared_camera_optimizer_thermal.pose_adjustment"),
                                                                suffix="_shared_thermal")
         self.proposal_networks = mk_props("proposal_networks", eng.props)
         self.density_fns = [n.density_fn for n in self.proposal_networks]
@@ -510,7 +521,13 @@ class ThermalNerfactoModel(nn.Module):
             self.camera_optimizer.get_metrics_dict(m)
             if c.density_mode == "separate":
                 self.camera_optimizer_thermal.get_metrics_dict(m)
+        for co in self._shared_camera_optimizers():  # camera_opt_translation_shared / camera_opt_rotation_shared (+ _thermal)
+            co.get_metrics_dict(m)
         return m
+
+    def _shared_camera_optimizers(self):
+        """the shared (rig) optimisers of the branches that exist (a switched-off one adds nothing to the dicts it is asked to fill)"""
+        return (self.shared_camera_optimizer, self.shared_camera_optimizer_thermal) if self.config.density_mode == "separate" else (self.shared_camera_optimizer,)
 
     def _pixel_terms(self, outputs, batch):
         """Eval mode: the four pixel losses + the RGB-ray count, one launch shared by get_metrics_dict (PSNRs) and get_loss_dict."""
@@ -548,6 +565,8 @@ class ThermalNerfactoModel(nn.Module):
                 if co.config.mode != "off":
                     ld[f"camera_opt_regularizer{co.suffix}"] = L[k]
                     k += 1
+            for co in self._shared_camera_optimizers():  # (outside the reference's `if self.training`: below for evaluation)
+                co.get_loss_dict(ld)
             return ld
         rgb_l, th_l, tv_l, cross_l, _ = self._pixel_terms(outputs, batch)
         ld["rgb_loss"], ld["thermal_loss"] = rgb_l, th_l
@@ -559,6 +578,8 @@ class ThermalNerfactoModel(nn.Module):
             ld["tv_pixel_loss"] = tv_l
         if c.cross_channel_loss_mult > 0:
             ld["cross_channel_loss"] = cross_l
+        for co in self._shared_camera_optimizers():
+            co.get_loss_dict(ld)
         return ld
 
     # ------------------------------------------------------------------------------------------------ fused fast path
@@ -592,7 +613,10 @@ class ThermalNerfactoModel(nn.Module):
     def get_outputs_for_camera(self, camera, obb_box=None) -> Dict[str, Tensor]:
         """models/base_model.py:165-175: one full image of `camera` -- anything with the Cameras fields for ONE camera: camera_to_worlds [3,4],
         fx, fy, cx, cy, width, height, optional distortion_params [6] and camera index (attribute `camera_index`, default 0; it selects the
-        pose correction / appearance row, as Cameras.generate_rays(camera_indices=0) + set_camera_indices do for an eval camera)."""
+        pose correction / appearance row, as Cameras.generate_rays(camera_indices=0) + set_camera_indices do for an eval camera).
+        With a shared (rig) correction enabled, `camera_index` also decides whether the render is corrected: the shared row of a branch is the
+        identity on the cameras of the other spectrum, and that flag is looked up with the ray's camera index against the TRAINING cameras'
+        spectra, as the reference does (cameras/camera_optimizers.py:139-146).  Give an eval camera the index of a training camera of its spectrum."""
         if obb_box is not None:
             raise NotImplementedError("obb_box cropping is outside the thermal-nerfacto path")
         dev = self.device

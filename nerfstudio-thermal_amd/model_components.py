@@ -150,7 +150,8 @@ class NearFarCollider(nn.Module):
 
 
 class CameraOptimizer(nn.Module):
-    """cameras/camera_optimizers.py:89-213, modes 'off' and 'SO3xR3'."""
+    """cameras/camera_optimizers.py:89-213, modes 'off', 'SO3xR3' (a row per camera, pose_adjustment [C,6]) and 'shared_SO3xR3' (ONE row for
+    every camera that is not frozen, pose_adjustment [1,6]: the rig offset between the two spectra's cameras)."""
 
     def __init__(self, config, num_cameras: int, device, non_trainable_camera_indices: Optional[Tensor] = None, pose_param: Optional[nn.Parameter] = None,
                  **kwargs) -> None:
@@ -166,15 +167,34 @@ class CameraOptimizer(nn.Module):
         if non_trainable_camera_indices is not None:
             frozen[non_trainable_camera_indices] = 1
         self.register_buffer("_frozen", frozen.to(device), persistent=False)
+        if config.mode not in ("off", "SO3xR3", "shared_SO3xR3"):
+            raise NotImplementedError(f"CameraOptimizer mode {config.mode!r} is outside the HIP hot path")
+        self.shared = config.mode == "shared_SO3xR3"
         if config.mode != "off":
-            assert pose_param is not None
+            assert pose_param is not None and tuple(pose_param.shape) == ((1, 6) if self.shared else (num_cameras, 6))
             self.pose_adjustment = pose_param
 
     def apply_to_raybundle(self, raybundle: RayBundle) -> None:
         if self.config.mode != "off":
             cam = raybundle.camera_indices.reshape(-1).contiguous()
-            o, d = ops.pose_apply_fwd(self.pose_adjustment.detach(), self._frozen, cam, raybundle.origins.contiguous(), raybundle.directions.contiguous())
-            raybundle.origins, raybundle.directions = o, d
+            shape = raybundle.origins.shape
+            apply = ops.pose_shared_apply if self.shared else ops.pose_apply_fwd
+            o, d = apply(self.pose_adjustment.detach(), self._frozen, cam, raybundle.origins.reshape(-1, 3).contiguous(),
+                         raybundle.directions.reshape(-1, 3).contiguous())
+            raybundle.origins, raybundle.directions = o.view(shape), d.view(shape)
+
+    def get_correction_matrices(self) -> Tensor:
+        """cameras/camera_optimizers.py:197-199: the [C,3,4] correction of every camera (identity rows for the frozen ones), through the same
+        kernel as the rays: the columns of R are the corrected unit directions, t the corrected zero origin."""
+        C_ = self.num_cameras
+        dev = self._frozen.device
+        if self.config.mode == "off":
+            return torch.eye(4, device=dev)[None, :3, :4].tile(C_, 1, 1)
+        cam = torch.arange(C_, device=dev).repeat_interleave(3).contiguous()
+        dirs = torch.eye(3, device=dev).repeat(C_, 1).contiguous()
+        apply = ops.pose_shared_apply if self.shared else ops.pose_apply_fwd
+        o, d = apply(self.pose_adjustment.detach(), self._frozen, cam, torch.zeros_like(dirs), dirs)
+        return torch.cat([d.view(C_, 3, 3).transpose(1, 2), o.view(C_, 3, 3)[:, :1].transpose(1, 2)], dim=2)
 
     def get_loss_dict(self, loss_dict: dict) -> None:
         if self.config.mode != "off":

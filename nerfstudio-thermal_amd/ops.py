@@ -445,6 +445,32 @@ def pose_apply_bwd(pose: Tensor, frozen: Optional[Tensor], cam: Tensor, directio
                                         N, Cn, _f32(grad_pose, "grad_pose", (Cn, 6)), _stream()), "tn_pose_apply_bwd")
 
 
+def pose_shared_apply(row: Tensor, frozen: Optional[Tensor], cam: Tensor, origins: Tensor, directions: Tensor):
+    """CameraOptimizer("shared_SO3xR3").apply_to_raybundle: the one row [1,6] corrects every ray whose camera is not frozen (tn_pose_shared_apply)."""
+    N = origins.shape[0]
+    o, d = torch.empty_like(origins), torch.empty_like(directions)
+    Cn = max(int(frozen.shape[0]), 1) if frozen is not None else 1
+    check(_lib.load().tn_pose_shared_apply(_f32(row, "shared row", (1, 6)), _u8(frozen, Cn), _i64(cam, "camera_indices", (N,)),
+                                           _f32(origins, "origins", (N, 3)), _f32(directions, "directions", (N, 3)), N, Cn, _f32(o, "o"), _f32(d, "d"),
+                                           _stream()), "tn_pose_shared_apply")
+    return o, d
+
+
+def pose_shared_bwd(row: Tensor, frozen: Optional[Tensor], cam: Tensor, directions_in: Tensor, d_o: Tensor, d_d: Tensor, pose: Optional[Tensor],
+                    grad_row: Tensor) -> None:
+    """The shared row's gradient from the gradient of the rays the render saw, accumulated into grad_row [1,6] (tn_pose_shared_bwd: deterministic).
+    directions_in: what pose_shared_apply was given; pose [C,6]: the per-camera correction applied behind the shared one, or None."""
+    N = directions_in.shape[0]
+    Cn = max(int(frozen.shape[0]), 1) if frozen is not None else (int(pose.shape[0]) if pose is not None else 1)
+    lib = _lib.load()
+    ws = _scratch(("pose_shared", directions_in.device.index, _stream().value), int(lib.tn_pose_shared_bwd_workspace_bytes(max(N, 0))) // 8, torch.float64,
+                  directions_in.device)
+    check(lib.tn_pose_shared_bwd(_f32(row, "shared row", (1, 6)), _u8(frozen, Cn), _i64(cam, "camera_indices", (N,)),
+                                 _f32(directions_in, "directions", (N, 3)), _f32(d_o, "d_origins", (N, 3)), _f32(d_d, "d_directions", (N, 3)),
+                                 _f32(pose, "pose", (Cn, 6), True), N, Cn, C.c_void_p(ws.data_ptr()), _nbytes(ws), _f32(grad_row, "grad_row", (1, 6)),
+                                 _stream()), "tn_pose_shared_bwd")
+
+
 # ------------------------------------------------------------------------------------------------ samplers
 _TABLES: dict = {}
 

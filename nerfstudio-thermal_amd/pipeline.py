@@ -67,6 +67,14 @@ class ThermalPipeline:
 
     def eval_camera(self, i: int):
         c = self.eval_outputs.cameras
+        if self.model.engine.shared_on:
+            # a shared (rig) correction is the identity on the cameras of the other spectrum, looked up by camera index among the TRAINING cameras
+            # (Model.get_outputs_for_camera): an eval image renders under the index of the first training camera of its own spectrum
+            th = int(self.eval_outputs.metadata["is_thermal"][i]) != 0
+            same = [k for k, x in enumerate(self.train_outputs.metadata["is_thermal"]) if (int(x) != 0) == th]
+            index = same[0] if same else i
+            return types.SimpleNamespace(camera_to_worlds=c["c2w"][i], fx=float(c["fx"][i]), fy=float(c["fy"][i]), cx=float(c["cx"][i]), cy=float(c["cy"][i]),
+                                         width=int(c["width"][i]), height=int(c["height"][i]), distortion_params=c["distortion"][i], camera_index=index)
         return types.SimpleNamespace(camera_to_worlds=c["c2w"][i], fx=float(c["fx"][i]), fy=float(c["fy"][i]), cx=float(c["cx"][i]), cy=float(c["cy"][i]),
                                      width=int(c["width"][i]), height=int(c["height"][i]), distortion_params=c["distortion"][i], camera_index=i)
 
