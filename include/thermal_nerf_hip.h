@@ -1204,6 +1204,43 @@ TN_API int tn_export_splat_pack(const float* means, const float* log_scales, con
                                 const TnSplatCrop* crop, float* out_rows, int64_t* count, void* workspace, int64_t workspace_bytes,
                                 tn_stream_t stream);
 
+/* ---- a rigid move of the Gaussians: the similarity x' = s R x + t (s > 0, R a proper rotation) applied to every Gaussian, so that the moved
+ * model seen from the moved camera renders the same frame -- what an export to, or an import from, the dataset's frame needs.  One launch on the
+ * caller's stream, no atomics, no workspace, no host synchronisation; the same inputs give the same bytes.  tests/splat_transform_functional.py
+ * restates it.
+ *
+ * TnSplatTransform is filled on the host in double (nerfstudio_thermal_amd.splat_transform.transform_struct): A = s R row-major, t, log_scale =
+ * log s, q = the quaternion (w, x, y, z) of R, and sh1 [3,3], sh2 [5,5], sh3 [7,7] row-major, the rotation matrices of the real SH bands 1 to 3 in
+ * tn_splat_project's basis (gsplat's constants, order and signs): Y_l(R d) = sh_l Y_l(d).
+ *
+ * tn_transform_splat: means, log_scales [N,3], quats [N,4] as stored, features_rest [N,R,3], thermal_rest [N,R] with R = num_rest_coeffs in
+ * {0, 3, 8, 15} (degrees 0 to 3; with R = 0 only the geometry moves and the four rest pointers may be null).  Every output value is evaluated in
+ * double from the float inputs widened, in this order, and rounded once to float:
+ *   means'[i]  = ((A[i][0] x + A[i][1] y) + A[i][2] z) + t[i]
+ *   scales'[i] = scales[i] + log_scale
+ *   quats'     = q (x) quat, the Hamilton product, each component the left-to-right sum of its four products:
+ *                w' = ((w1 w2 - x1 x2) - y1 y2) - z1 z2      x' = ((w1 x2 + x1 w2) + y1 z2) - z1 y2
+ *                y' = ((w1 y2 - x1 z2) + y1 w2) + z1 x2      z' = ((w1 z2 + x1 y2) - y1 x2) + z1 w2      (1: q, 2: the Gaussian's; its norm is kept)
+ *   rest'[k]   = ((M[k][0] rest[0] + M[k][1] rest[1]) + ...), j ascending, within each band present (k = 0..2 with sh1, 3..7 with sh2, 8..14 with
+ *                sh3), per channel, for features_rest and thermal_rest alike
+ * A parameter that is not finite leaves its group (means, scales, quats, a band of a channel) of its Gaussian not finite.
+ * Each *_out may be its own input (in place): a block reads all of its Gaussians before it stores any.  Otherwise an output must not overlap any
+ * other buffer of the call: pointers are equal or disjoint.
+ * num_gaussians == 0 is TN_OK without a launch.  Refused with TN_EINVAL before any launch: a null transform, num_gaussians outside [0, 2^31),
+ * num_rest_coeffs not one of 0, 3, 8, 15, null pointers the call needs.
+ * (Named tn_transform_splat, outside the tn_splat_* family, as tn_export_splat_pack is: that family is the frame, training and refinement stages.) */
+typedef struct TnSplatTransform {
+  double A[9];
+  double t[3];
+  double log_scale;
+  double q[4];
+  double sh1[9], sh2[25], sh3[49];
+} TnSplatTransform;
+TN_API int tn_transform_splat(const TnSplatTransform* transform, const float* means, const float* log_scales, const float* quats,
+                              const float* features_rest, const float* thermal_rest, int64_t num_gaussians, int32_t num_rest_coeffs,
+                              float* means_out, float* log_scales_out, float* quats_out, float* features_rest_out, float* thermal_rest_out,
+                              tn_stream_t stream);
+
 /* ---- point-cloud export of the NeRF (ns-export pointcloud: nerfstudio/scripts/exporter.py:90-186, nerfstudio/exporter/exporter_utils.py:83-260,
  * generate_point_cloud): rendered rays are back-projected by their depth, the opaque ones inside a box are kept, statistical outliers are
  * removed.  Every point carries the rendered colour and the rendered thermal value.  Both entry points run on the caller's stream without a host

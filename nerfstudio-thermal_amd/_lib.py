@@ -117,6 +117,11 @@ class TnSplatCrop(C.Structure):
     _fields_ = [("world_to_box", _f * 12), ("half_extent", _f * 3)]
 
 
+class TnSplatTransform(C.Structure):
+    """include/thermal_nerf_hip.h: a similarity of the Gaussians -- A = s R, t, log s, the quaternion of R and its three SH band matrices, row-major doubles (tn_transform_splat)"""
+    _fields_ = [("A", _d * 9), ("t", _d * 3), ("log_scale", _d), ("q", _d * 4), ("sh1", _d * 9), ("sh2", _d * 25), ("sh3", _d * 49)]
+
+
 class TnUndistort(C.Structure):
     """include/thermal_nerf_hip.h: the source camera, the pinhole camera of the output and k1 k2 k3 k4 p1 p2 (tn_image_undistort)"""
     _fields_ = [("fx", _f), ("fy", _f), ("cx", _f), ("cy", _f), ("new_fx", _f), ("new_fy", _f), ("new_cx", _f), ("new_cy", _f), ("k", _f * 6)]
@@ -273,6 +278,8 @@ SIGNATURES = {
     # (named tn_export_splat_*, outside the tn_splat_* family: every launch of that family is issued by splat_calls.py, this raw call is splat_io.pack_call's)
     "tn_export_splat_workspace_bytes": (_i64, [_i64]),
     "tn_export_splat_pack": (C.c_int, [_p] * 9 + [_i64, _i32, _i32, _i32, _f, C.POINTER(TnSplatCrop), _p, _p, _p, _i64, _p]),
+    # a similarity applied to every Gaussian (means, log scales, quaternions and the SH bands 1 to 3 of both spectra), in place or not
+    "tn_transform_splat": (C.c_int, [C.POINTER(TnSplatTransform)] + [_p] * 5 + [_i64, _i32] + [_p] * 5 + [_p]),
     # point-cloud export of the NeRF: stable append of a rendered batch, statistical outlier removal
     "tn_cloud_append_workspace_bytes": (_i64, [_i64]),
     "tn_cloud_append": (C.c_int, [_p] * 5 + [_i64, _p, _i64, _i64, _f, C.POINTER(TnSplatCrop), _p, _p, _p, _i64, _p, _p, _i64, _p]),

@@ -1,4 +1,4 @@
-"""The call layer of the splat path: the one module that names the tn_splat_* / tn_knn / tn_image_* / tn_thermal_reg / tn_depth_loss / tn_bilagrid_* entry points of
+"""The call layer of the splat path: the one module that names the tn_splat_* / tn_knn / tn_image_* / tn_thermal_reg / tn_depth_loss / tn_bilagrid_* / tn_transform_splat entry points of
 libthermal_nerf_hip.so and knows their argument order (include/thermal_nerf_hip.h).  The three gsplat calls (project_gaussians,
 spherical_harmonics, rasterize_gaussians x2) run as tn_splat_project / tn_splat_bin / tn_splat_raster of libthermal_nerf_hip.so; separate thermal
 opacity runs the _sep family (tn_splat_project_sep ... tn_splat_refine_apply_sep: the same kernels instantiated with the second chain), and _crop,
@@ -205,6 +205,21 @@ def pose_camera(cam, p00, p11, pose, row, rec) -> None:
 def crop_mask(crop, pts, mask) -> None:
     """tn_splat_crop_mask: uint8 `mask` [n] of which `pts` [n,3] are strictly inside the box -- the device function the cropped projection uses."""
     _call("tn_splat_crop_mask", C.byref(crop), *_f32(pts=pts), pts.shape[0], _raw(mask))
+
+
+def transform_call(transform, means, scales, quats, rest, rest_thermal, means_out, scales_out, quats_out, rest_out, rest_thermal_out) -> None:
+    """tn_transform_splat: the similarity of the TnSplatTransform `transform` applied to means, scales [N,3], quats [N,4], features_rest [N,R,3] and
+    features_rest_thermal [N,R,1] into the five outputs.  An output may be its own input (in place); otherwise it must overlap no other tensor of the
+    call.  R must be 0, 3, 8 or 15; with R == 0 the rest tensors go in as null."""
+    N, R = means.shape[0], rest.shape[1]
+    for name, t, o, shape in (("means", means, means_out, (N, 3)), ("scales", scales, scales_out, (N, 3)), ("quats", quats, quats_out, (N, 4)),
+                              ("features_rest", rest, rest_out, (N, R, 3)), ("features_rest_thermal", rest_thermal, rest_thermal_out, (N, R, 1))):
+        if tuple(t.shape) != shape or tuple(o.shape) != shape:
+            raise ValueError(f"transform_call: {name} and its output must be {shape}, got {tuple(t.shape)} and {tuple(o.shape)}")
+    geo = _f32(means=means, scales=scales, quats=quats), _f32(means_out=means_out, scales_out=scales_out, quats_out=quats_out)
+    sh = ([None, None], [None, None]) if R == 0 else (_f32(features_rest=rest, features_rest_thermal=rest_thermal),
+                                                    _f32(features_rest_out=rest_out, features_rest_thermal_out=rest_thermal_out))
+    _call("tn_transform_splat", C.byref(transform), *geo[0], *sh[0], N, R, *geo[1], *sh[1])
 
 
 # ---------------------------------------------------------------------------------------------------- refinement

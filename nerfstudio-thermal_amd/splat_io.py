@@ -15,8 +15,13 @@ place that knows that entry point's argument order.  There is no CPU fallback fo
 
 Every stored SH coefficient is exported whatever degree the training step has activated, as in the reference.  A model with sh_degree == 0 keeps
 sigmoid colours in features_dc; its file carries f_dc = (sigmoid(dc) - 0.5) / C0, which a viewer's 0.5 + C0 f_dc turns back into the colour, and no
-f_rest.  The reference writes uint8 `colors` for such a model instead; that layout is not reproduced.  The file is in the model's frame: a
-world-frame export would have to rotate the higher SH bands, and the reference does not offer one for splats either.
+f_rest.  The reference writes uint8 `colors` for such a model instead; that layout is not reproduced.
+
+Without a `transform` the file is in the model's frame.  `export_gaussian_ply(..., transform=T)` writes the Gaussians moved by the Similarity `T`
+(splat_transform.py: means, scales, quaternions and the SH bands 1 to 3 of both spectra, on the device by tn_transform_splat, then the same pack);
+`T = dataset_frame(dataparser_outputs, applied_transform)` puts the file into the dataset's own frame, where the point-cloud and mesh exports put
+theirs.  `load_gaussian_ply(..., transform=T)` moves the file's Gaussians before they are loaded: `dataset_frame(...).inverse()` brings a
+dataset-frame file home.  The reference offers no world-frame export for splats.
 """
 from __future__ import annotations
 
@@ -33,6 +38,7 @@ from .dataparser import _ply_header
 from .ops import _stream
 from .splat_calls import _param_ptrs, _ptr
 from .splat_camera import OrientedBox
+from .splat_transform import Similarity, transform_gaussians
 
 SPECTRA = {"rgb": 0, "thermal": 1, "both": 2}
 SH_C0 = 0.28209479177387814
@@ -203,16 +209,29 @@ def pack_call(params: Sequence[Tensor], spectrum: int, colour_mode: int, min_opa
 
 
 # ---------------------------------------------------------------------------------------------------- export and import of a model
-def export_gaussian_ply(model, path: str, spectrum: str = "both", min_opacity: float = 0.0, crop: Box = None) -> dict:
+def export_gaussian_ply(model, path: str, spectrum: str = "both", min_opacity: float = 0.0, crop: Box = None,
+                        transform: Optional[Similarity] = None) -> dict:
     """`model`'s Gaussians as the splat file `path`.  Dropped: Gaussians with a parameter of the row that is not finite, with
     sigmoid(opacity) < min_opacity (the row's opacity; in a "both" file of a separate-mode model the larger of the two, the MCMC strategy's notion
     of a live Gaussian; 0 keeps every opacity), and, with `crop` (an OrientedBox), those whose mean is not strictly inside the box.  One read-back
-    of the kept number, one device-to-host copy of the kept rows.  Returns {"path", "exported", "dropped", "spectrum", "properties"}; no kept
-    Gaussian gives a valid file with `element vertex 0`."""
+    of the kept number, one device-to-host copy of the kept rows.  Returns {"path", "exported", "dropped", "spectrum", "properties", "frame"}; no
+    kept Gaussian gives a valid file with `element vertex 0`.
+
+    `transform` None writes the model's frame ("frame": "model").  With a Similarity the parameters are moved out of place on the device
+    (transform_gaussians; the model is not touched) and then packed as before ("frame": "transformed").  `crop` is still given in the model's
+    frame, as an OrientedBox: it is moved with `transform.apply_box` and tested on the moved means, so a mean within rounding of a face may fall
+    either way.  A parameter that is not finite stays not finite through the move, so the same Gaussians are dropped; `min_opacity` is not affected."""
     if spectrum not in SPECTRA:
         raise ValueError(f"spectrum must be one of {sorted(SPECTRA)}, got {spectrum!r}")
     colour_mode = 1 if model.config.sh_degree == 0 else 0
-    params = [model.gauss_params[k].detach().contiguous() for k in model.param_names]
+    named = {k: model.gauss_params[k].detach().contiguous() for k in model.param_names}
+    if transform is not None:
+        if crop is not None and not transform.is_identity:
+            if not isinstance(crop, OrientedBox):
+                raise ValueError(f"crop must be an OrientedBox to be moved with the Gaussians, got {type(crop).__name__}")
+            crop = transform.apply_box(crop)
+        named = transform_gaussians(named, transform)
+    params = [named[k] for k in model.param_names]
     n, R = int(params[0].shape[0]), int(params[5].shape[1])
     props = ply_properties(spectrum, R + 1, model.separate, colour_mode)
     logit, box = opacity_logit(min_opacity), _crop(crop)
@@ -226,18 +245,23 @@ def export_gaussian_ply(model, path: str, spectrum: str = "both", min_opacity: f
         kept = int(count.item())
         rows = out[:kept].cpu().numpy()
     write_gaussian_ply(path, rows, props)
-    return {"path": path, "exported": kept, "dropped": n - kept, "spectrum": spectrum, "properties": props}
+    return {"path": path, "exported": kept, "dropped": n - kept, "spectrum": spectrum, "properties": props,
+            "frame": "model" if transform is None else "transformed"}
 
 
-def load_gaussian_ply(model, path: str) -> dict:
+def load_gaussian_ply(model, path: str, transform: Optional[Similarity] = None) -> dict:
     """Replace `model`'s Gaussians by the file's (read_gaussian_ply, then model.load_gaussians, whose shared / separate rules apply: a file
     without opacity_thermal starts a separate-mode model's thermal logits as a copy of the opacities, a file with it is refused by a shared-mode
-    model).  The file's K must be the model's (sh_degree + 1)^2.  Returns read_gaussian_ply's info."""
+    model).  The file's K must be the model's (sh_degree + 1)^2.  With `transform` the file's Gaussians are moved on the device before they are
+    loaded (transform_gaussians): `dataset_frame(...).inverse()` for a file in the dataset's frame.  Returns read_gaussian_ply's info."""
     want = int(model.config.sh_degree)
     params, info = read_gaussian_ply(path, sh_degree=want)
     if info["K"] != (want + 1) ** 2:
         raise ValueError(f"{path}: {info['K']} SH coefficients per channel (degree {info['sh_degree']}), the model has sh_degree {want}")
     if info["separate"] and not model.separate:
         raise ValueError(f'{path}: the file has opacity_thermal, the model has thermal_opacity_mode "shared"')
+    if transform is not None and not transform.is_identity:
+        params = {k: v.to(model.means.device).contiguous() for k, v in params.items()}
+        params = transform_gaussians(params, transform, out=params)
     model.load_gaussians(params)
     return info

@@ -5,6 +5,7 @@ splat file (--load), and write `splat.ply` in the Inria layout every splat viewe
     python scripts/export_gaussian_splat.py [--data DIR] [--iterations 3000] [--output-dir out/splat] [--spectrum both|rgb|thermal]
                                             [--min-opacity 0.005] [--obb-center X Y Z --obb-rotation ROLL PITCH YAW --obb-scale SX SY SZ]
                                             [--load PLY] [--thermal-opacity-mode shared|separate] [--sh-degree 3] [--gaussians 20000]
+                                            [--save-world-frame] [--load-world-frame]
 
 --spectrum both (the default) writes the colour scene under the Inria property names followed by f_dc_thermal, f_rest_thermal_* and, in separate
 mode, opacity_thermal: viewers ignore the extras, splat_io.load_gaussian_ply reads them back (bit for bit for --sh-degree > 0).  --spectrum thermal
@@ -12,8 +13,11 @@ writes the thermal parameters under the Inria names, so any viewer shows the the
 --min-opacity (in a "both" file of a separate-mode model: in both spectra) and Gaussians with a parameter that is not finite are dropped; the
 --obb-* arguments (all three or none; rotation in radians) keep only the Gaussians whose mean is strictly inside that oriented box, the eval
 render's crop.  --load PLY starts from a splat file instead of random Gaussians -- an Inria file from any trainer, or one written here -- and
-trains on from it for --iterations steps (0: load, filter, write).  The file is in the model's frame.  One JSON line reports the counts and the
-seconds of every stage.
+trains on from it for --iterations steps (0: load, filter, write).  Without --save-world-frame the file is in the model's frame; with it the
+Gaussians are moved into the dataset's own frame (splat_transform.dataset_frame: the inverse of the dataparser's transform and scale, the SH bands
+rotated with the geometry), where scripts/export_point_cloud.py and scripts/export_tsdf_mesh.py put theirs.  The generated scene's dataparser
+transform is the identity, so there the two frames are one and the line says so.  --load-world-frame reads the --load file as a dataset-frame file.
+Both need a dataset: --data, or the generated scene of a run that trains.  One JSON line reports the counts and the seconds of every stage.
 """
 import argparse
 import functools
@@ -43,8 +47,14 @@ def parse_args(argv=None):
     ap.add_argument("--obb-rotation", type=float, nargs=3, default=None, metavar=("ROLL", "PITCH", "YAW"), help="radians")
     ap.add_argument("--obb-scale", type=float, nargs=3, default=None, metavar=("SX", "SY", "SZ"))
     ap.add_argument("--load", default=None, metavar="PLY", help="start from this Gaussian-splat PLY")
+    ap.add_argument("--save-world-frame", action="store_true", help="write the file in the dataset's frame (default: the model's)")
+    ap.add_argument("--load-world-frame", action="store_true", help="the --load file is in the dataset's frame")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
+    if args.load_world_frame and args.load is None:
+        ap.error("--load-world-frame goes with --load")
+    if (args.save_world_frame or args.load_world_frame) and args.data is None and args.iterations == 0:
+        ap.error("--save-world-frame and --load-world-frame need a dataset: --data, or a run that trains on the generated scene")
     obb = (args.obb_center, args.obb_rotation, args.obb_scale)
     if any(a is not None for a in obb) and not all(a is not None for a in obb):
         ap.error("--obb-center, --obb-rotation and --obb-scale go together")
@@ -65,6 +75,7 @@ def main(argv=None):
     from nerfstudio_thermal_amd.model import TrainingCallbackLocation
     from nerfstudio_thermal_amd.optim import SPLAT_BILAGRID_OPTIMIZERS, SPLAT_CAMERA_OPTIMIZERS, SPLAT_OPTIMIZERS, HipAdam, Optimizers
     from nerfstudio_thermal_amd.splat import OrientedBox, ThermalSplatfactoModel, ThermalSplatfactoModelConfig
+    from nerfstudio_thermal_amd.splat_transform import dataset_frame
 
     dev = torch.device("cuda", 0)
     torch.manual_seed(args.seed)
@@ -73,8 +84,8 @@ def main(argv=None):
                                        thermal_opacity_mode=args.thermal_opacity_mode)
     sync = torch.cuda.synchronize
     dm = None
+    data = args.data
     if args.iterations > 0:
-        data = args.data
         if data is None:
             from train_eval_scene import write_cube_scene
 
@@ -83,12 +94,17 @@ def main(argv=None):
         dm = ThermalFullImageDatamanagerConfig(dataparser=ThermalNerfDataParserConfig(data=data), seed=args.seed).setup(device=dev)
     model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=dm.num_train_data if dm else 0,
                                    train_is_thermal=dm.train_is_thermal if dm else None)
+    world = None  # model frame -> dataset frame
+    if args.save_world_frame or args.load_world_frame:
+        outputs = dm.train_dataparser_outputs if dm is not None else ThermalNerfDataParserConfig(data=data).setup().get_dataparser_outputs("train")
+        meta = json.load(open(os.path.join(data, "transforms.json"), encoding="utf-8"))
+        world = dataset_frame(outputs, meta.get("applied_transform"))
     loaded = None
     if args.load is not None:
         t = time.perf_counter()
-        info = splat_io.load_gaussian_ply(model, args.load)
+        info = splat_io.load_gaussian_ply(model, args.load, transform=world.inverse() if args.load_world_frame else None)
         loaded = {"path": args.load, "gaussians": info["num_gaussians"], "sh_degree": info["sh_degree"], "has_thermal": info["has_thermal"],
-                  "separate": info["separate"], "load_seconds": time.perf_counter() - t}
+                  "separate": info["separate"], "frame": "dataset" if args.load_world_frame else "model", "load_seconds": time.perf_counter() - t}
     sync(); t0 = time.perf_counter()
     if dm is not None:
         opts = Optimizers(model.get_param_groups(), {**SPLAT_OPTIMIZERS, **SPLAT_CAMERA_OPTIMIZERS, **SPLAT_BILAGRID_OPTIMIZERS}, optimizer_cls=HipAdam)
@@ -106,14 +122,16 @@ def main(argv=None):
     sync(); train_s = time.perf_counter() - t0
     box = OrientedBox.from_params(args.obb_center, args.obb_rotation, args.obb_scale) if args.obb_center is not None else None
     t1 = time.perf_counter()
-    out = splat_io.export_gaussian_ply(model, os.path.join(args.output_dir, "splat.ply"), spectrum=args.spectrum, min_opacity=args.min_opacity, crop=box)
+    out = splat_io.export_gaussian_ply(model, os.path.join(args.output_dir, "splat.ply"), spectrum=args.spectrum, min_opacity=args.min_opacity, crop=box,
+                                       transform=world if args.save_world_frame else None)
     export_s = time.perf_counter() - t1
     print(json.dumps({"dataset": None if dm is None else (args.data if args.data is not None else "generated cube scene"), "loaded": loaded,
                       "iterations": args.iterations, "train_seconds": train_s, "gaussians": model.num_points, "exported": out["exported"],
                       "dropped": out["dropped"], "spectrum": args.spectrum, "min_opacity": args.min_opacity, "sh_degree": args.sh_degree,
                       "thermal_opacity_mode": args.thermal_opacity_mode, "properties": len(out["properties"]),
                       "obb": None if box is None else {"center": args.obb_center, "rotation": args.obb_rotation, "scale": args.obb_scale},
-                      "export_seconds": export_s, "file_bytes": os.path.getsize(out["path"]), "ply": out["path"]}))
+                      "frame": ("dataset (the dataparser's transform is the identity: also the model's)" if world.is_identity else "dataset")
+                      if args.save_world_frame else "model", "export_seconds": export_s, "file_bytes": os.path.getsize(out["path"]), "ply": out["path"]}))
     return 0
 
 

@@ -31,7 +31,9 @@ clamped to [0, 1]); the held-out frames are left alone, so the val metrics say w
 corrected by a grid, so the line also reports psnr_rgb_affine_fit / psnr_thermal_affine_fit: each held-out frame's PSNR
 after the least-squares affine colour map of its render onto its ground truth (a diagnostic of this script, plain torch).  --export-ply PATH writes
 the trained Gaussians as a Gaussian-splat PLY (splat_io.export_gaussian_ply: spectrum "both", Gaussians below opacity 0.005 in both spectra and
-those with a parameter that is not finite dropped); the line reports how many went out."""
+those with a parameter that is not finite dropped); the line reports how many went out.  --export-world-frame writes that file in the dataset's own
+frame (splat_transform.dataset_frame), where the point-cloud and mesh exports put theirs; the generated scene's dataparser transform is the identity,
+so there it is the model's frame too and the line says so."""
 import argparse
 import functools
 import json
@@ -178,7 +180,10 @@ def main():
     ap.add_argument("--no-undistort", action="store_true", help="train on the raw frames with the parser's intrinsics (the distortion dropped)")
     ap.add_argument("--export-ply", default=None, metavar="PATH",
                     help="write the trained Gaussians as a Gaussian-splat PLY (splat_io.export_gaussian_ply, spectrum both, opacity below 0.005 dropped)")
+    ap.add_argument("--export-world-frame", action="store_true", help="write the --export-ply file in the dataset's frame (default: the model's)")
     args = ap.parse_args()
+    if args.export_world_frame and args.export_ply is None:
+        ap.error("--export-world-frame goes with --export-ply")
     if args.seed_points and args.data is not None:
         ap.error("--seed-points samples the generated scene's cube; a dataset on disk brings its own ply_file_path")
     if args.frame_drift and args.data is not None:
@@ -276,8 +281,16 @@ def main():
         from nerfstudio_thermal_amd import splat_io
 
         os.makedirs(os.path.dirname(os.path.abspath(args.export_ply)), exist_ok=True)
-        out = splat_io.export_gaussian_ply(model, args.export_ply, spectrum="both", min_opacity=0.005)
+        world = None
+        if args.export_world_frame:
+            from nerfstudio_thermal_amd.splat_transform import dataset_frame
+
+            meta = json.load(open(os.path.join(data, "transforms.json"), encoding="utf-8"))
+            world = dataset_frame(dm.train_dataparser_outputs, meta.get("applied_transform"))
+        out = splat_io.export_gaussian_ply(model, args.export_ply, spectrum="both", min_opacity=0.005, transform=world)
         extra["export_ply"] = {k: out[k] for k in ("path", "exported", "dropped", "spectrum")}
+        extra["export_ply"]["frame"] = "model" if world is None else \
+            ("dataset (the dataparser's transform is the identity: also the model's)" if world.is_identity else "dataset")
     model.train()
     metrics = {k: sum(v) / len(v) for k, v in sums.items() if all(math.isfinite(x) for x in v)}
     pose_norms = {}
