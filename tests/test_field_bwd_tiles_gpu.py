@@ -26,6 +26,7 @@ import pytest
 import torch
 
 import thermal_nerfacto_oracle as orc
+from field_stage_cases import _ws_float_offsets
 from helpers import make_params, tiny_cfg, SEED
 from nerfstudio_thermal_amd import _lib, ops, synth
 from nerfstudio_thermal_amd.arena import ParamArena
@@ -45,21 +46,6 @@ SHAPES = {
     "uneven_blocks": (2054, 16, 0),          # P = 32 * (4 * 256 + 3): 1027 tiles on 1024 waves -> blocks with 8, 3 and 0 tiles
 }
 GRADS = ("w0", "b0", "w1", "b1", "hw0", "hb0", "hw1", "hb1", "hw2", "hb2", "emb")
-
-
-def _ws_float_offsets(P):
-    """float offsets of the workspace regions the test looks at (ws_layout in csrc/tn_field.hip: every region rounded up to 256 bytes)"""
-    lib = _lib.load()
-    r = lambda floats: ((floats * 4 + 255) // 256) * 256  # noqa: E731
-    PT = (P + 31) // 32 * 32
-    off = int(lib.tn_field_workspace_bytes(0, 0))  # the packed weights: every other region is empty at 0 points
-    regions = {}
-    for name, floats in (("pos", P * 4), ("enc", PT * 32), ("sel", P), ("sh", P * 16), ("h1", PT * 64), ("hin", PT * 16), ("hh1", PT * 64),
-                         ("hh2", PT * 64), ("y", P * 4), ("g_enc", P * 32)):
-        regions[name] = off // 4
-        off += r(floats)
-    assert off < int(lib.tn_field_workspace_bytes(P, 1))
-    return regions
 
 
 def _restatement(p64, k, enc, sel, sh, cam, g_dens, g_rgb, num_images):
