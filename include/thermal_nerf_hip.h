@@ -1284,6 +1284,41 @@ TN_API int64_t tn_cloud_remove_outliers_workspace_bytes(int64_t n, int32_t nb_ne
 TN_API int tn_cloud_remove_outliers(const float* xyz, const float* rgb, const float* thermal, int64_t n, int32_t nb_neighbors, double std_ratio,
                                     float* out_xyz, float* out_rgb, float* out_thermal, int64_t* out_count, double* stats, double* mean, uint8_t* keep,
                                     void* workspace, int64_t workspace_bytes, tn_stream_t stream);
+/* The view directions beside the points, for the normals below.  tn_cloud_append_view is tn_cloud_append plus out_view [cap,3] (after out_thermal):
+ * the direction of every kept ray, as given and not renormalised, goes to the row its point goes to.  tn_cloud_remove_outliers_view is
+ * tn_cloud_remove_outliers plus view [n,3] (after thermal) and out_view [n,3] (after out_thermal), compacted with the points.  Both run the plain
+ * entry points' launches with one more pointer pair in the write kernel, so every other output is what the plain call writes, bit for bit, and
+ * everything the plain calls refuse is refused; the new pointers must not be null (out_view may be when cap is 0). */
+TN_API int tn_cloud_append_view(const float* origins, const float* directions, const float* depth, const float* accumulation, const float* rgb,
+                                int64_t rgb_stride, const float* thermal, int64_t thermal_stride, int64_t num_rays, float alpha_thresh,
+                                const TnSplatCrop* box, float* out_xyz, float* out_rgb, float* out_thermal, float* out_view, int64_t cap, int64_t* count,
+                                void* workspace, int64_t workspace_bytes, tn_stream_t stream);
+TN_API int tn_cloud_remove_outliers_view(const float* xyz, const float* rgb, const float* thermal, const float* view, int64_t n, int32_t nb_neighbors,
+                                         double std_ratio, float* out_xyz, float* out_rgb, float* out_thermal, float* out_view, int64_t* out_count,
+                                         double* stats, double* mean, uint8_t* keep, void* workspace, int64_t workspace_bytes, tn_stream_t stream);
+/* tn_cloud_estimate_normals: an oriented unit normal per point of xyz [n,3] (finite fp32), the rule of Open3D's estimate_normals with
+ * KDTreeSearchParamKNN(knn) followed by the reference's reorient_normals (exporter_utils.py:215-237).  knn in 3..32 counts the point itself.
+ *   Neighbourhood  N_i = point i, then its knn - 1 nearest OTHER points in tn_knn's order: d2 = (dx*dx + dy*dy) + dz*dz in fp32, ties to the smaller
+ *                  index, exact.  A duplicate of i is a neighbour at distance 0.
+ *   Covariance     in double: c_j = p_j - p_i (exact), S1 = sum c_j and S2 = sum c_j c_j^T over N_i in that order,
+ *                  C = S2 / knn - (S1 / knn)(S1 / knn)^T.
+ *   Normal         the unit eigenvector of C's smallest eigenvalue, rounded once to fp32.  C is scaled by its trace and diagonalised by cyclic
+ *                  Jacobi rotations in double until its off-diagonal sum is at most 2^-100 (12 sweeps at the most), so the vector's error is of
+ *                  the order of 2^-52 lambda_max / (lambda_1 - lambda_0).
+ *   Zero C         C exactly zero (all knn points coincide): the normal is (0, 0, 1), Open3D's fallback.
+ *   Sign, view     with view [n,3] (the direction of the ray that produced the point): the normal is negated when v_i . n > 0, the dot product
+ *                  ((vx nx + vy ny) + vz nz) in double on the unrounded normal.
+ *   Sign, no view  view null: the first non-zero of (n_z, n_y, n_x) is positive.
+ * Every output is finite and of unit length, degenerate neighbourhoods included (a collinear run gives some unit vector normal to the line).
+ * Nothing but out_normals[i] is written; no atomics, no host synchronisation, the same inputs give the same bits.  The search is the wide form of
+ * tn_knn's query (lists of 7, 15, 19 or 31 in registers, chosen by knn - 1), the neighbours are gathered by their original indices; no [n,k] table.
+ * n == 0 is TN_OK and touches nothing.  Refused with TN_EINVAL before any launch: knn outside 3..32, n < knn, n at or above 2^31, null pointers
+ * (view may be null), a short workspace.  tests/cloud_normals_functional.py restates the rule.
+ *
+ * scratch of tn_cloud_estimate_normals (tn_knn's tree); 0 for n == 0, -1 on sizes the call refuses or when the sort's scratch cannot be sized */
+TN_API int64_t tn_cloud_normals_workspace_bytes(int64_t n, int32_t knn);
+TN_API int tn_cloud_estimate_normals(const float* xyz, int64_t n, int32_t knn, const float* view, float* out_normals, void* workspace,
+                                     int64_t workspace_bytes, tn_stream_t stream);
 
 /* ---- TSDF mesh export (ns-export tsdf: nerfstudio/exporter/tsdf_utils.py, TSDF.integrate_tsdf and get_mesh): rendered depth frames are fused into
  * a truncated signed distance volume with an RGB+thermal value per voxel, and the zero level of the volume is extracted as an indexed triangle mesh.

@@ -285,6 +285,11 @@ SIGNATURES = {
     "tn_cloud_append": (C.c_int, [_p] * 5 + [_i64, _p, _i64, _i64, _f, C.POINTER(TnSplatCrop), _p, _p, _p, _i64, _p, _p, _i64, _p]),
     "tn_cloud_remove_outliers_workspace_bytes": (_i64, [_i64, _i32]),
     "tn_cloud_remove_outliers": (C.c_int, [_p, _p, _p, _i64, _i32, C.c_double] + [_p] * 8 + [_i64, _p]),
+    # the same two with the view directions carried beside the points, and the oriented normals of the cloud (a kNN PCA)
+    "tn_cloud_append_view": (C.c_int, [_p] * 5 + [_i64, _p, _i64, _i64, _f, C.POINTER(TnSplatCrop), _p, _p, _p, _p, _i64, _p, _p, _i64, _p]),
+    "tn_cloud_remove_outliers_view": (C.c_int, [_p, _p, _p, _p, _i64, _i32, C.c_double] + [_p] * 9 + [_i64, _p]),
+    "tn_cloud_normals_workspace_bytes": (_i64, [_i64, _i32]),
+    "tn_cloud_estimate_normals": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _i64, _p]),
     "tn_tsdf_integrate": (C.c_int, [_p, _p, _p, _i32, _i32, _i32] + [_f] * 8 + [_p, _p, _p, _f, _p, _i32, _i32, _i32, _i32, _p]),
     "tn_mesh_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "tn_mesh_count": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _i64, _p]),

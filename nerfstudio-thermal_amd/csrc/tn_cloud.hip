@@ -3,6 +3,10 @@
 // tn_cloud_append           one batch of rendered rays -> the kept rays' points, colours and thermal values appended to the cloud, in ray order
 // tn_cloud_remove_outliers  Open3D's remove_statistical_outlier: neighbour means over the Morton tree of tn_knn (tn_splat_init.hip), their mean and
 //                           standard deviation in double, the kept points compacted in their original order
+// tn_cloud_append_view / tn_cloud_remove_outliers_view   the same two with the kept rays' directions carried beside the points (one optional pointer
+//                           pair through the same write kernels: the plain entry points pass null and write what they always wrote)
+// tn_cloud_estimate_normals a normal per point from the covariance of its knn nearest points (tn_knn_normals, tn_splat_init.hip: the wide search
+//                           again), flipped against the point's view direction
 //
 // Both are stable compactions and share one scheme of three launches, none of which lets an atomic decide an order:
 //   k_cloud_count<Keep>  one block per CB consecutive rows: the number of kept rows of the block
@@ -114,7 +118,7 @@ __device__ inline int block_rank(bool k) {
 __global__ void __launch_bounds__(CB) k_cloud_append_write(RayKeep keep, int64_t n, const float* __restrict__ rgb, int64_t rgb_stride,
                                                            const float* __restrict__ thermal, int64_t thermal_stride, const int64_t* __restrict__ offset,
                                                            int64_t cap, float* __restrict__ out_xyz, float* __restrict__ out_rgb,
-                                                           float* __restrict__ out_thermal) {
+                                                           float* __restrict__ out_thermal, float* __restrict__ out_view) {
   const int64_t r = (int64_t)blockIdx.x * CB + threadIdx.x;
   float x = 0.0f, y = 0.0f, z = 0.0f;
   const bool k = r < n && keep.point(r, x, y, z);
@@ -124,12 +128,16 @@ __global__ void __launch_bounds__(CB) k_cloud_append_write(RayKeep keep, int64_t
   const float* c = rgb + r * rgb_stride;
   out_rgb[3 * at] = c[0], out_rgb[3 * at + 1] = c[1], out_rgb[3 * at + 2] = c[2];
   out_thermal[at] = thermal[r * thermal_stride];
+  if (out_view) {  // the ray's direction as given, beside its point
+#pragma unroll
+    for (int a = 0; a < 3; ++a) out_view[3 * at + a] = keep.directions[3 * r + a];
+  }
 }
 
 __global__ void __launch_bounds__(CB) k_cloud_filter_write(MeanKeep keep, int64_t n, const float* __restrict__ xyz, const float* __restrict__ rgb,
                                                            const float* __restrict__ thermal, const int64_t* __restrict__ offset,
                                                            float* __restrict__ out_xyz, float* __restrict__ out_rgb, float* __restrict__ out_thermal,
-                                                           uint8_t* __restrict__ keep_out) {
+                                                           uint8_t* __restrict__ keep_out, const float* __restrict__ view, float* __restrict__ out_view) {
   const int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x;
   const bool k = i < n && keep(i);
   const int64_t at = offset[blockIdx.x] + block_rank(k);  // < n: at most i rows are kept before row i
@@ -138,6 +146,10 @@ __global__ void __launch_bounds__(CB) k_cloud_filter_write(MeanKeep keep, int64_
 #pragma unroll
   for (int a = 0; a < 3; ++a) out_xyz[3 * at + a] = xyz[3 * i + a], out_rgb[3 * at + a] = rgb[3 * i + a];
   out_thermal[at] = thermal[i];
+  if (out_view) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) out_view[3 * at + a] = view[3 * i + a];
+  }
 }
 
 // ---- statistics: sums over the points with a positive mean, in double and in a fixed order
@@ -212,15 +224,19 @@ extern "C" int64_t tn_cloud_append_workspace_bytes(int64_t num_rays) {
   return align256(nb * 4) + align256(nb * 8);
 }
 
-extern "C" int tn_cloud_append(const float* origins, const float* directions, const float* depth, const float* accumulation, const float* rgb,
-                               int64_t rgb_stride, const float* thermal, int64_t thermal_stride, int64_t num_rays, float alpha_thresh,
-                               const TnSplatCrop* box, float* out_xyz, float* out_rgb, float* out_thermal, int64_t cap, int64_t* count, void* workspace,
-                               int64_t workspace_bytes, tn_stream_t stream) {
+namespace {
+
+// tn_cloud_append (with_view false, out_view null) and tn_cloud_append_view
+int cloud_append(const float* origins, const float* directions, const float* depth, const float* accumulation, const float* rgb, int64_t rgb_stride,
+                 const float* thermal, int64_t thermal_stride, int64_t num_rays, float alpha_thresh, const TnSplatCrop* box, float* out_xyz, float* out_rgb,
+                 float* out_thermal, bool with_view, float* out_view, int64_t cap, int64_t* count, void* workspace, int64_t workspace_bytes,
+                 tn_stream_t stream) {
   TN_REQUIRE(num_rays >= 0 && num_rays <= CLOUD_MAX_ROWS, "tn_cloud_append: %lld rays (0..2^31 - 1)", (long long)num_rays);
   TN_REQUIRE(cap >= 0, "tn_cloud_append: a capacity of %lld rows", (long long)cap);
   if (num_rays == 0) return TN_OK;
   TN_REQUIRE(origins && directions && depth && accumulation && rgb && thermal && count && workspace, "tn_cloud_append: null pointer");
-  TN_REQUIRE(cap == 0 || (out_xyz && out_rgb && out_thermal), "tn_cloud_append: null pointer (an output of %lld rows)", (long long)cap);
+  TN_REQUIRE(cap == 0 || (out_xyz && out_rgb && out_thermal && (out_view || !with_view)), "tn_cloud_append: null pointer (an output of %lld rows)",
+             (long long)cap);
   TN_REQUIRE(rgb_stride >= 3 && thermal_stride >= 1, "tn_cloud_append: strides of %lld (rgb, >= 3) and %lld (thermal, >= 1) elements per ray",
              (long long)rgb_stride, (long long)thermal_stride);
   const int64_t need = tn_cloud_append_workspace_bytes(num_rays);
@@ -236,9 +252,27 @@ extern "C" int tn_cloud_append(const float* origins, const float* directions, co
   hipLaunchKernelGGL(k_cloud_offsets, dim3(1), dim3(CB), 0, st, counts, nb, cap, offsets, count, false);
   TN_CHECK_LAUNCH("tn_cloud_append(offsets)");
   hipLaunchKernelGGL(k_cloud_append_write, dim3((unsigned)nb), dim3(CB), 0, st, keep, num_rays, rgb, rgb_stride, thermal, thermal_stride, offsets, cap,
-                     out_xyz, out_rgb, out_thermal);
+                     out_xyz, out_rgb, out_thermal, with_view ? out_view : nullptr);
   TN_CHECK_LAUNCH("tn_cloud_append(write)");
   return TN_OK;
+}
+
+}  // namespace
+
+extern "C" int tn_cloud_append(const float* origins, const float* directions, const float* depth, const float* accumulation, const float* rgb,
+                               int64_t rgb_stride, const float* thermal, int64_t thermal_stride, int64_t num_rays, float alpha_thresh,
+                               const TnSplatCrop* box, float* out_xyz, float* out_rgb, float* out_thermal, int64_t cap, int64_t* count, void* workspace,
+                               int64_t workspace_bytes, tn_stream_t stream) {
+  return cloud_append(origins, directions, depth, accumulation, rgb, rgb_stride, thermal, thermal_stride, num_rays, alpha_thresh, box, out_xyz, out_rgb,
+                      out_thermal, false, nullptr, cap, count, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tn_cloud_append_view(const float* origins, const float* directions, const float* depth, const float* accumulation, const float* rgb,
+                                    int64_t rgb_stride, const float* thermal, int64_t thermal_stride, int64_t num_rays, float alpha_thresh,
+                                    const TnSplatCrop* box, float* out_xyz, float* out_rgb, float* out_thermal, float* out_view, int64_t cap,
+                                    int64_t* count, void* workspace, int64_t workspace_bytes, tn_stream_t stream) {
+  return cloud_append(origins, directions, depth, accumulation, rgb, rgb_stride, thermal, thermal_stride, num_rays, alpha_thresh, box, out_xyz, out_rgb,
+                      out_thermal, true, out_view, cap, count, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t tn_cloud_remove_outliers_workspace_bytes(int64_t n, int32_t nb_neighbors) {
@@ -247,13 +281,17 @@ extern "C" int64_t tn_cloud_remove_outliers_workspace_bytes(int64_t n, int32_t n
   return tree < 0 ? -1 : filter_layout(n, tree).total;
 }
 
-extern "C" int tn_cloud_remove_outliers(const float* xyz, const float* rgb, const float* thermal, int64_t n, int32_t nb_neighbors, double std_ratio,
-                                        float* out_xyz, float* out_rgb, float* out_thermal, int64_t* out_count, double* stats, double* mean,
-                                        uint8_t* keep, void* workspace, int64_t workspace_bytes, tn_stream_t stream) {
+namespace {
+
+// tn_cloud_remove_outliers (with_view false, view and out_view null) and tn_cloud_remove_outliers_view
+int cloud_remove_outliers(const float* xyz, const float* rgb, const float* thermal, bool with_view, const float* view, int64_t n, int32_t nb_neighbors,
+                          double std_ratio, float* out_xyz, float* out_rgb, float* out_thermal, float* out_view, int64_t* out_count, double* stats,
+                          double* mean, uint8_t* keep, void* workspace, int64_t workspace_bytes, tn_stream_t stream) {
   TN_REQUIRE(nb_neighbors >= 2 && nb_neighbors <= 32, "tn_cloud_remove_outliers: nb_neighbors = %d (2..32)", nb_neighbors);
   TN_REQUIRE(n >= 0 && n <= CLOUD_MAX_ROWS, "tn_cloud_remove_outliers: %lld points (below 2^31)", (long long)n);
   TN_REQUIRE(n >= nb_neighbors, "tn_cloud_remove_outliers: %lld points, nb_neighbors = %d needs at least as many", (long long)n, nb_neighbors);
-  TN_REQUIRE(xyz && rgb && thermal && out_xyz && out_rgb && out_thermal && out_count && stats && workspace, "tn_cloud_remove_outliers: null pointer");
+  TN_REQUIRE(xyz && rgb && thermal && out_xyz && out_rgb && out_thermal && out_count && stats && workspace && (!with_view || (view && out_view)),
+             "tn_cloud_remove_outliers: null pointer");
   const int64_t tree = tn_knn_tree_workspace_bytes(n);
   if (tree < 0) {
     tn_set_error("tn_cloud_remove_outliers: rocprim could not size its scratch for %lld points", (long long)n);
@@ -283,7 +321,45 @@ extern "C" int tn_cloud_remove_outliers(const float* xyz, const float* rgb, cons
   TN_CHECK_LAUNCH("tn_cloud_remove_outliers(count)");
   hipLaunchKernelGGL(k_cloud_offsets, dim3(1), dim3(CB), 0, st, counts, nb, n, offsets, out_count, true);
   TN_CHECK_LAUNCH("tn_cloud_remove_outliers(offsets)");
-  hipLaunchKernelGGL(k_cloud_filter_write, dim3((unsigned)nb), dim3(CB), 0, st, pred, n, xyz, rgb, thermal, offsets, out_xyz, out_rgb, out_thermal, keep);
+  hipLaunchKernelGGL(k_cloud_filter_write, dim3((unsigned)nb), dim3(CB), 0, st, pred, n, xyz, rgb, thermal, offsets, out_xyz, out_rgb, out_thermal, keep,
+                     with_view ? view : nullptr, with_view ? out_view : nullptr);
   TN_CHECK_LAUNCH("tn_cloud_remove_outliers(write)");
   return TN_OK;
+}
+
+}  // namespace
+
+extern "C" int tn_cloud_remove_outliers(const float* xyz, const float* rgb, const float* thermal, int64_t n, int32_t nb_neighbors, double std_ratio,
+                                        float* out_xyz, float* out_rgb, float* out_thermal, int64_t* out_count, double* stats, double* mean,
+                                        uint8_t* keep, void* workspace, int64_t workspace_bytes, tn_stream_t stream) {
+  return cloud_remove_outliers(xyz, rgb, thermal, false, nullptr, n, nb_neighbors, std_ratio, out_xyz, out_rgb, out_thermal, nullptr, out_count, stats, mean,
+                               keep, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tn_cloud_remove_outliers_view(const float* xyz, const float* rgb, const float* thermal, const float* view, int64_t n, int32_t nb_neighbors,
+                                             double std_ratio, float* out_xyz, float* out_rgb, float* out_thermal, float* out_view, int64_t* out_count,
+                                             double* stats, double* mean, uint8_t* keep, void* workspace, int64_t workspace_bytes, tn_stream_t stream) {
+  return cloud_remove_outliers(xyz, rgb, thermal, true, view, n, nb_neighbors, std_ratio, out_xyz, out_rgb, out_thermal, out_view, out_count, stats, mean,
+                               keep, workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t tn_cloud_normals_workspace_bytes(int64_t n, int32_t knn) {
+  if (knn < 3 || knn > 32 || n < 0 || n > CLOUD_MAX_ROWS || (n > 0 && n < knn)) return -1;
+  return n == 0 ? 0 : tn_knn_tree_workspace_bytes(n);
+}
+
+extern "C" int tn_cloud_estimate_normals(const float* xyz, int64_t n, int32_t knn, const float* view, float* out_normals, void* workspace,
+                                         int64_t workspace_bytes, tn_stream_t stream) {
+  TN_REQUIRE(knn >= 3 && knn <= 32, "tn_cloud_estimate_normals: knn = %d (3..32, the point itself counted)", knn);
+  TN_REQUIRE(n >= 0 && n <= CLOUD_MAX_ROWS, "tn_cloud_estimate_normals: %lld points (below 2^31)", (long long)n);
+  if (n == 0) return TN_OK;
+  TN_REQUIRE(n >= knn, "tn_cloud_estimate_normals: %lld points, knn = %d needs at least as many", (long long)n, knn);
+  TN_REQUIRE(xyz && out_normals && workspace, "tn_cloud_estimate_normals: null pointer");
+  const int64_t tree = tn_knn_tree_workspace_bytes(n);
+  if (tree < 0) {
+    tn_set_error("tn_cloud_estimate_normals: rocprim could not size its scratch for %lld points", (long long)n);
+    return TN_ELAUNCH;
+  }
+  TN_REQUIRE(workspace_bytes >= tree, "tn_cloud_estimate_normals: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)tree);
+  return tn_knn_normals(xyz, n, knn, view, out_normals, workspace, workspace_bytes, tn_s(stream));
 }

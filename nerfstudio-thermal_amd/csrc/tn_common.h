@@ -83,6 +83,11 @@ int tn_field_fwd_ex(const TnField* field, const float* origins, const float* dir
 int64_t tn_knn_tree_workspace_bytes(int64_t n);  // -1 when rocprim cannot size its sort
 int tn_knn_neighbor_means(const float* points, int64_t n, int32_t nb_neighbors, double* mean, void* workspace, int64_t workspace_bytes,
                           hipStream_t stream);
+// The oriented normals of tn_cloud_estimate_normals (include/thermal_nerf_hip.h states the rule) over the same tree and the same wide search:
+// points [n,3] fp32, view [n,3] fp32 or null -> normals [n,3] fp32, one row per point and nothing else.  The caller has checked 3 <= knn <= 32 and
+// knn <= n <= INT32_MAX; the scratch is the tree's.
+int tn_knn_normals(const float* points, int64_t n, int32_t knn, const float* view, float* normals, void* workspace, int64_t workspace_bytes,
+                   hipStream_t stream);
 
 // ---------------------------------------------------------------- device side
 // The crop box of the splat eval render and of the point-cloud export (OrientedBox: splatfacto.py:690-698, scene_box.py:82-114): m = rows of the

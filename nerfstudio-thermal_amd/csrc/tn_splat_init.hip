@@ -18,7 +18,9 @@
 //                     still hold a better (d2, j); the row is written at the point's original index.
 //   k_knn_query_mean<K>  the same search (knn_search) with a wide list, K in {7, 15, 19, 31}, for the statistical outlier rule of the point-cloud
 //                     export (tn_knn_neighbor_means, called by tn_cloud_remove_outliers): it writes one double per point, no [n,k] table.
-// knn_build_tree builds the tree for both; tn_knn itself stays at k = 1..8.
+//   k_knn_query_normal<K>  the same wide search for the normals of the exported cloud (tn_knn_normals, called by tn_cloud_estimate_normals): the
+//                     neighbours' covariance in double, its smallest eigenvector by Jacobi rotations, oriented; one fp32 row per point.
+// knn_build_tree builds the tree for all three; tn_knn itself stays at k = 1..8.
 //
 // Pruning is exact: the box distance uses the point formula on the box's nearest coordinate, and correctly rounded subtraction, squaring
 // and addition are monotone, so it is a lower bound of every computed d2 inside the box.  A node is skipped when that bound exceeds the
@@ -284,6 +286,84 @@ __global__ void __launch_bounds__(KB) k_knn_query_mean(const float4* __restrict_
   mean[__float_as_int(q.w)] = sum / divisor;
 }
 
+// One Jacobi rotation in the (p, q) plane of a symmetric 3x3 matrix: a_pq becomes zero, r is the third index, and the columns p and q of the
+// accumulated eigenvector matrix V turn with it (t = tan of the angle, the smaller root; theta * theta may overflow to inf, which gives t = 0).
+__device__ inline void jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q, double& v1p, double& v1q,
+                                     double& v2p, double& v2q) {
+  if (apq == 0.0) return;
+  const double theta = (aqq - app) / (2.0 * apq);
+  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  app -= t * apq, aqq += t * apq, apq = 0.0;
+  const double rp = c * arp - s * arq, rq = s * arp + c * arq;
+  arp = rp, arq = rq;
+  const double x0 = c * v0p - s * v0q, x1 = c * v1p - s * v1q, x2 = c * v2p - s * v2q;
+  v0q = s * v0p + c * v0q, v1q = s * v1p + c * v1q, v2q = s * v2p + c * v2q;
+  v0p = x0, v1p = x1, v2p = x2;
+}
+
+constexpr int JACOBI_SWEEPS = 12;        // a 3x3 reaches the threshold below in 5..7 sweeps (the off-diagonal shrinks quadratically); the cap only bounds the loop
+constexpr double JACOBI_DONE = 0x1p-100;  // on a matrix of trace 1: what is left moves an eigenvector by 2^-100 / (its eigenvalue gap)
+
+// The query of tn_cloud_estimate_normals: the same search, then -- the distance list is dead, only the index list is live -- the `used` neighbours
+// are gathered from the cloud by their original indices (queries run in Morton order, so neighbouring threads gather neighbouring rows), their
+// differences to the point are summed in double in list order (the point itself, first of its neighbourhood, adds zeros), the covariance
+// C = S2 / knn - (S1 / knn)(S1 / knn)^T is scaled by its trace and diagonalised by cyclic Jacobi rotations in double, and the unit eigenvector of
+// the smallest eigenvalue is oriented and rounded once.  Nothing but normals[self] is written.
+template <int K>
+__global__ void __launch_bounds__(KB) k_knn_query_normal(const float4* __restrict__ sp, int64_t n, const KNode* __restrict__ nodes, int64_t num_padded,
+                                                         const float* __restrict__ xyz, int used, double knn, const float* __restrict__ view,
+                                                         float* __restrict__ normals) {
+  const int64_t s = (int64_t)blockIdx.x * KB + threadIdx.x;
+  if (s >= n) return;
+  const float4 q = sp[s];
+  KBest<K> best;
+  knn_search<K>(sp, n, nodes, num_padded, s, q, best);
+  const int64_t self = __float_as_int(q.w);
+  const double px = q.x, py = q.y, pz = q.z;
+  double s1x = 0.0, s1y = 0.0, s1z = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
+#pragma unroll
+  for (int m = 0; m < K; ++m) {
+    if (m < used) {  // n - 1 >= used other points exist: the first `used` slots are real indices in 0..n-1
+      const int64_t j = best.j[m];
+      const double cx = (double)xyz[3 * j] - px, cy = (double)xyz[3 * j + 1] - py, cz = (double)xyz[3 * j + 2] - pz;
+      s1x += cx, s1y += cy, s1z += cz;
+      sxx += cx * cx, sxy += cx * cy, sxz += cx * cz, syy += cy * cy, syz += cy * cz, szz += cz * cz;
+    }
+  }
+  const double mx = s1x / knn, my = s1y / knn, mz = s1z / knn;
+  double a00 = sxx / knn - mx * mx, a01 = sxy / knn - mx * my, a02 = sxz / knn - mx * mz;
+  double a11 = syy / knn - my * my, a12 = syz / knn - my * mz, a22 = szz / knn - mz * mz;
+  double nx = 0.0, ny = 0.0, nz = 1.0;  // a covariance that is exactly zero (all knn points coincide): Open3D's fallback
+  if (a00 != 0.0 || a01 != 0.0 || a02 != 0.0 || a11 != 0.0 || a12 != 0.0 || a22 != 0.0) {
+    const double tr = (a00 + a11) + a22;
+    const double big = fmax(fmax(fmax(fabs(a00), fabs(a11)), fmax(fabs(a22), fabs(a01))), fmax(fabs(a02), fabs(a12)));
+    const double scale = tr > 0.0 ? tr : big;  // the trace of a covariance is positive; rounding alone could take a tiny one below zero
+    a00 /= scale, a01 /= scale, a02 /= scale, a11 /= scale, a12 /= scale, a22 /= scale;
+    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+    for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
+      if ((fabs(a01) + fabs(a02)) + fabs(a12) <= JACOBI_DONE) break;
+      jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+      jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+      jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+    }
+    // the column of the smallest eigenvalue (ties: the lowest index), selected without indexing
+    const bool c1 = a11 < a00 && a11 <= a22, c2 = a22 < a00 && a22 < a11;
+    nx = c2 ? v02 : (c1 ? v01 : v00), ny = c2 ? v12 : (c1 ? v11 : v10), nz = c2 ? v22 : (c1 ? v21 : v20);
+    const double len = sqrt((nx * nx + ny * ny) + nz * nz);
+    if (len > 0.0 && len < INFINITY) nx /= len, ny /= len, nz /= len;
+    else nx = 0.0, ny = 0.0, nz = 1.0;
+  }
+  bool flip;
+  if (view) {
+    const double dot = ((double)view[3 * self] * nx + (double)view[3 * self + 1] * ny) + (double)view[3 * self + 2] * nz;
+    flip = dot > 0.0;
+  } else {
+    flip = nz != 0.0 ? nz < 0.0 : (ny != 0.0 ? ny < 0.0 : nx < 0.0);
+  }
+  normals[3 * self] = (float)(flip ? -nx : nx), normals[3 * self + 1] = (float)(flip ? -ny : ny), normals[3 * self + 2] = (float)(flip ? -nz : nz);
+}
+
 constexpr int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
 
 int64_t padded_leaves(int64_t n) {
@@ -367,6 +447,12 @@ void launch_query_mean(const KnnTree& T, int64_t n, int used, int32_t nb, double
 }
 
 template <int K>
+void launch_query_normal(const KnnTree& T, int64_t n, const float* xyz, int used, int32_t knn, const float* view, float* normals, hipStream_t st) {
+  hipLaunchKernelGGL(k_knn_query_normal<K>, dim3((unsigned)tn_cdiv(n, KB)), dim3(KB), 0, st, (const float4*)T.sp, n, (const KNode*)T.nodes, padded_leaves(n), xyz,
+                     used, (double)knn, view, normals);
+}
+
+template <int K>
 void launch_query(const float4* sp, int64_t n, const KNode* nodes, int64_t P, float* out_dist, int32_t* out_index, hipStream_t st) {
   hipLaunchKernelGGL(k_knn_query<K>, dim3((unsigned)tn_cdiv(n, KB)), dim3(KB), 0, st, sp, n, nodes, P, out_dist, out_index);
 }
@@ -435,5 +521,24 @@ int tn_knn_neighbor_means(const float* points, int64_t n, int32_t nb_neighbors, 
   else if (used <= 19) launch_query_mean<19>(T, n, used, nb_neighbors, mean, st);
   else launch_query_mean<31>(T, n, used, nb_neighbors, mean, st);
   TN_CHECK_LAUNCH("tn_cloud_remove_outliers(query)");
+  return TN_OK;
+}
+
+// ---- internal (tn_common.h): the oriented normals of tn_cloud_estimate_normals (tn_cloud.hip)
+int tn_knn_normals(const float* points, int64_t n, int32_t knn, const float* view, float* normals, void* workspace, int64_t workspace_bytes, hipStream_t st) {
+  const KnnLayout L = knn_layout(n);
+  if (!L.ok) {
+    tn_set_error("tn_cloud_estimate_normals: rocprim could not size its scratch for %lld points", (long long)n);
+    return TN_ELAUNCH;
+  }
+  TN_REQUIRE(workspace_bytes >= L.total, "tn_cloud_estimate_normals: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)L.total);
+  const KnnTree T = knn_tree_views(workspace, L);
+  if (const int rc = knn_build_tree(points, n, L, T, st)) return rc;
+  const int used = knn - 1;  // 2..31 other points, of which n - 1 >= used exist
+  if (used <= 7) launch_query_normal<7>(T, n, points, used, knn, view, normals, st);
+  else if (used <= 15) launch_query_normal<15>(T, n, points, used, knn, view, normals, st);
+  else if (used <= 19) launch_query_normal<19>(T, n, points, used, knn, view, normals, st);
+  else launch_query_normal<31>(T, n, points, used, knn, view, normals, st);
+  TN_CHECK_LAUNCH("tn_cloud_estimate_normals(query)");
   return TN_OK;
 }

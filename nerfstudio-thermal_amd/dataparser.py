@@ -219,15 +219,19 @@ def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray]:
     nerfstudio_dataparser.py:461 computes them; clipped to 0..255 first).  Other vertex properties and the elements after `vertex` are
     ignored; fixed-size elements before it are skipped.  ValueError: big-endian or unknown formats, a missing x, y or z, a list property at or
     before the vertices, a truncated body."""
-    xyz, rgb, _ = _read_ply_vertices(path)
-    return xyz, rgb
+    return _read_ply_vertices(path)[:2]
 
 
 def read_ply_thermal(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
     """read_ply plus the vertices' `thermal` property -> (xyz, rgb, thermal [M,1] uint8, or None when the file has no such property): the rendered
     temperature a NeRF point cloud carries (cloud.py).  uchar as stored; float / double as the colours are read, (t * 255).astype(uint8) after
     clipping to 0..255."""
-    return _read_ply_vertices(path)
+    return _read_ply_vertices(path)[:3]
+
+
+def read_ply_normals(path: str) -> Optional[np.ndarray]:
+    """The vertices' normals -> [M,3] float32 (nx ny nz of any numeric type, cast), or None when the file lacks one of the three properties."""
+    return _read_ply_vertices(path)[3]
 
 
 def _ply_u8(path: str, values: np.ndarray, what: str) -> np.ndarray:
@@ -275,7 +279,8 @@ def _ply_header(path: str, data: bytes) -> Tuple[str, List[Tuple[str, int, List[
     return fmt, elements, body
 
 
-def _read_ply_vertices(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+def _read_ply_vertices(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
+    """-> (xyz, rgb, thermal or None, normals or None) of the vertex element."""
     with open(path, "rb") as f:
         data = f.read()
     fmt, elements, body = _ply_header(path, data)
@@ -307,20 +312,29 @@ def _read_ply_vertices(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.n
         cols = {p: arr[p] for p in pnames}
     xyz = np.stack([cols[a].astype(np.float64) for a in ("x", "y", "z")], -1).astype(np.float32)
     thermal = _ply_u8(path, np.asarray(cols["thermal"]), "vertex thermal values").reshape(-1, 1) if "thermal" in pnames else None
+    normals = np.stack([cols[a].astype(np.float32) for a in ("nx", "ny", "nz")], -1) if all(a in pnames for a in ("nx", "ny", "nz")) else None
     if not all(c in pnames for c in ("red", "green", "blue")):
-        return xyz, np.zeros((0, 3), dtype=np.uint8), thermal
-    return xyz, _ply_u8(path, np.stack([cols[c] for c in ("red", "green", "blue")], -1), "vertex colours"), thermal
+        return xyz, np.zeros((0, 3), dtype=np.uint8), thermal, normals
+    return xyz, _ply_u8(path, np.stack([cols[c] for c in ("red", "green", "blue")], -1), "vertex colours"), thermal, normals
 
 
-def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, binary: bool = True, thermal: Optional[np.ndarray] = None) -> str:
+def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, binary: bool = True, thermal: Optional[np.ndarray] = None,
+              normals: Optional[np.ndarray] = None) -> str:
     """xyz [M,3] (float32 or float64 -> float / double properties) and optional rgb [M,3] (uint8 -> uchar, float -> float / double) as one
     PLY vertex element, binary little-endian or ascii.  With `thermal` ([M] or [M,1] uint8) one more property, `uchar thermal`, follows; without
-    it the file is byte for byte what it was before the property existed."""
+    it the file is byte for byte what it was before the property existed.  With `normals` ([M,3], written as float) nx ny nz follow x y z
+    directly, Open3D's order and mesh.write_mesh_ply's; without them, again, the file is what it was."""
     xyz = np.asarray(xyz)
     if xyz.dtype not in (np.float32, np.float64):
         xyz = xyz.astype(np.float32)
     ptype = {np.dtype("u1"): "uchar", np.dtype("f4"): "float", np.dtype("f8"): "double"}
     fields = [(a, xyz.dtype) for a in ("x", "y", "z")]
+    if normals is not None:
+        normals = np.asarray(normals)
+        if normals.shape != (xyz.shape[0], 3) or normals.dtype.kind != "f":
+            raise ValueError(f"write_ply: normals must be [{xyz.shape[0]},3] floats, got {normals.shape} of type {normals.dtype}")
+        normals = normals.astype(np.float32)
+        fields += [(a, normals.dtype) for a in ("nx", "ny", "nz")]
     if rgb is not None:
         rgb = np.asarray(rgb)
         if rgb.dtype not in ptype:
@@ -336,6 +350,9 @@ def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, bina
     rec = np.empty(xyz.shape[0], dtype=[(n, np.dtype(t).newbyteorder("<")) for n, t in fields])
     for i, a in enumerate(("x", "y", "z")):
         rec[a] = xyz[:, i]
+    if normals is not None:
+        for i, a in enumerate(("nx", "ny", "nz")):
+            rec[a] = normals[:, i]
     if rgb is not None:
         for i, c in enumerate(("red", "green", "blue")):
             rec[c] = rgb[:, i]
@@ -354,8 +371,9 @@ def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, bina
 def load_3D_points(ply_path: str, transform: Tensor, scale: float) -> Dict[str, Tensor]:
     """nerfstudio_dataparser.py:429-466: the cloud in the dataparser's frame, points3D_xyz = cat(xyz, 1) @ transform.T * scale (transform =
     auto_orient_and_center_poses' [3,4], scale = the final scale, applied_scale included), and points3D_rgb uint8.  A file with a `thermal` vertex property (a NeRF point cloud, cloud.py) adds points3D_thermal uint8 [M,1]; a
-    file without it adds no such key.  No keys for an empty cloud."""
-    xyz, rgb, thermal = read_ply_thermal(ply_path)
+    file without it adds no such key.  A file with all of nx ny nz adds points3D_normals float32 [M,3] = n @ transform[:, :3].T: the normals
+    turn with the points and are neither scaled nor translated.  No keys for an empty cloud."""
+    xyz, rgb, thermal, normals = _read_ply_vertices(ply_path)
     if xyz.shape[0] == 0:
         return {}
     points = torch.from_numpy(xyz)
@@ -364,6 +382,8 @@ def load_3D_points(ply_path: str, transform: Tensor, scale: float) -> Dict[str, 
     out = {"points3D_xyz": points, "points3D_rgb": torch.from_numpy(rgb)}
     if thermal is not None:
         out["points3D_thermal"] = torch.from_numpy(thermal)
+    if normals is not None:
+        out["points3D_normals"] = torch.from_numpy(normals) @ transform[:, :3].T.to(torch.float32)
     return out
 
 

@@ -5,11 +5,15 @@ inside the box, remove statistical outliers on the device and write `point_cloud
     python scripts/export_point_cloud.py [--data DIR] [--iterations 3000] [--output-dir out/cloud] [--num-points 1000000] [--std-ratio 10]
                                          [--no-remove-outliers] [--obb-center X Y Z --obb-rotation R P Y --obb-scale SX SY SZ]
                                          [--no-save-world-frame] [--set-ply-file-path]
+                                         [--normal-method none|knn] [--normals-knn 30] [--no-reorient-normals]
 
 --save-world-frame (the default) writes the cloud in the dataset's own frame (cloud.to_dataset_frame), where a `ply_file_path` entry expects it.
 --set-ply-file-path writes a COPY of the dataset's transforms.json next to the cloud, with `ply_file_path` naming it and the frames' file paths
 made absolute; the dataset itself is never edited.  Point the splat trainer's dataparser (load_3D_points=True) at that copy to seed thermal splats
-with the NeRF's colours and temperatures.  One JSON line reports the sizes and the seconds of every stage.
+with the NeRF's colours and temperatures.  --normal-method knn (the reference's default, normal_method="open3d") estimates a unit normal per
+point from its --normals-knn nearest points after the outliers are gone, flips it against the ray that produced the point unless
+--no-reorient-normals, and writes float nx ny nz after x y z (rotated into the dataset's frame with the points); the default, none, writes the
+file this script always wrote.  One JSON line reports the sizes and the seconds of every stage.
 """
 import argparse
 import json
@@ -41,12 +45,19 @@ def parse_args(argv=None):
                     help="write the cloud in the dataset's frame (default)")
     ap.add_argument("--no-save-world-frame", dest="save_world_frame", action="store_false", help="write it in the model's frame")
     ap.add_argument("--set-ply-file-path", action="store_true", help="write a copy of transforms.json that names the cloud as ply_file_path")
+    ap.add_argument("--normal-method", default="none", choices=("none", "knn"),
+                    help="knn: estimate normals from each point's nearest neighbours and write nx ny nz (default: none)")
+    ap.add_argument("--normals-knn", type=int, default=30, help="points per neighbourhood, the point itself counted (3..32)")
+    ap.add_argument("--no-reorient-normals", dest="reorient_normals", action="store_false",
+                    help="leave the normals' sign to the rule of the library, not to the view directions")
     ap.add_argument("--ascii", action="store_true", help="write an ASCII PLY")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
     obb = (args.obb_center, args.obb_rotation, args.obb_scale)
     if any(v is not None for v in obb) and not all(v is not None for v in obb):
         ap.error("--obb-center, --obb-rotation and --obb-scale go together")
+    if not 3 <= args.normals_knn <= 32:
+        ap.error("--normals-knn must be in 3..32")
     return args
 
 
@@ -96,20 +107,27 @@ def main(argv=None):
 
     box = OrientedBox.from_params(args.obb_center, args.obb_rotation, args.obb_scale) if args.obb_center is not None else None
     t1 = time.perf_counter()
-    raw = cloud.generate_point_cloud(pipe.model, next_rays, num_points=args.num_points, remove_outliers=False, box=box,
-                                     use_bounding_box=args.use_bounding_box)
+    want_normals = args.normal_method == "knn"
+    raw = cloud.gather_points(pipe.model, next_rays, num_points=args.num_points, box=box, use_bounding_box=args.use_bounding_box,
+                              with_view=want_normals)  # generate_point_cloud's loop; its other two stages follow, timed on their own
     sync(); gather_s = time.perf_counter() - t1
     t2 = time.perf_counter()
     details = {}
     pc = cloud.remove_outliers(raw, 20, args.std_ratio, details) if args.remove_outliers else raw
     sync(); clean_s = time.perf_counter() - t2
+    t3 = time.perf_counter()
+    if want_normals:
+        cloud.estimate_normals(pc, args.normals_knn, reorient=args.reorient_normals)
+    sync(); normals_s = time.perf_counter() - t3
     meta = json.load(open(os.path.join(data, "transforms.json"), encoding="utf-8"))
     xyz = cloud.to_dataset_frame(pc.xyz, pipe.train_outputs, meta.get("applied_transform")) if args.save_world_frame else pc.xyz
-    ply = cloud.write_cloud_ply(os.path.join(args.output_dir, "point_cloud.ply"), pc, xyz, binary=not args.ascii)
+    nrm = cloud.normals_to_dataset_frame(pc.normals, pipe.train_outputs, meta.get("applied_transform")) if want_normals and args.save_world_frame else None
+    ply = cloud.write_cloud_ply(os.path.join(args.output_dir, "point_cloud.ply"), pc, xyz, binary=not args.ascii, normals=nrm)
     copy = transforms_copy(data, args.output_dir, "point_cloud.ply") if args.set_ply_file_path else None
     print(json.dumps({"dataset": data if args.data is not None else f"generated cube scene ({data})", "iterations": args.iterations, "train_seconds": train_s,
                       "final_losses": losses, "num_points": args.num_points, "points_written": len(pc), "render_and_append_seconds": gather_s,
-                      "remove_outliers_seconds": clean_s, "outlier_stats_m_s_thr": details["stats"].tolist() if details else None,
+                      "remove_outliers_seconds": clean_s, "normal_method": args.normal_method,
+                      "estimate_normals_seconds": normals_s if want_normals else None, "outlier_stats_m_s_thr": details["stats"].tolist() if details else None,
                       "frame": "dataset" if args.save_world_frame else "model", "ply": ply, "transforms_copy": copy}))
     return 0
 
