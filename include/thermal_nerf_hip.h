@@ -1414,6 +1414,68 @@ TN_API int tn_mesh_simplify_emit(const float* vertices, const float* normals, co
                                  float* out_rgbt, int64_t num_out_vertices, int32_t* out_faces, int64_t num_out_faces, void* workspace,
                                  int64_t workspace_bytes, tn_stream_t stream);
 
+/* ---- Poisson surface reconstruction from an oriented point cloud (ns-export poisson: nerfstudio/scripts/exporter.py ExportPoissonMesh, Open3D's
+ * create_from_point_cloud_poisson).  A dense-grid solve, not Kazhdan's adaptive octree: no parity with Open3D's triangulation is claimed.  The
+ * normals are splatted onto a lattice, a Poisson equation is solved on it by conjugate gradients, and tn_mesh_count / tn_mesh_emit extract a level
+ * of the solution.  tests/poisson_functional.py restates every rule below in float64.
+ *
+ * All volumes are [X,Y,Z] fp32, z fastest; lattice point (i, j, k) sits at origin + (i, j, k) * voxel (the volume of the TSDF export).  X, Y and Z are
+ * at least 2 and X * Y * Z is below 2^31.  `double` below means: the fp32 inputs widened, every operation rounded on its own (no fused multiply-add).
+ *
+ * tn_poisson_bin   the plan of a cloud on a grid.  For point p and each axis t = (p - origin) / voxel in double and c = floor(t).  A point is
+ *                  skipped when a coordinate (or its t) is not finite or when any c lies outside 0..dim - 2 (a point on the upper outer faces has
+ *                  c = dim - 1 and is skipped).  The kept points are ordered by cell key (cx (Y - 1) + cy) (Z - 1) + cz and, inside a cell, by
+ *                  ascending point index: rocprim's stable radix sort of (key, index); the first row of every cell is a lower bound over the sorted
+ *                  keys.  The plan lives in the workspace and serves any number of tn_poisson_splat calls with the same points and grid.
+ * tn_poisson_splat out [X,Y,Z,C] = sum over the kept points of (w_p tri_p(q)) value_p[c], for values [n,C], C in 1..4 (null: all ones, C = 1, the
+ *                  density) and weights [n] (null: 1).  A point whose weight or any of whose C values is not finite is skipped.  With f = t - floor(t),
+ *                  tri_p(q) = (wx wy) wz in double, w_a = 1 - f_a where q is the lower corner of the point's cell along a and f_a where it is the
+ *                  upper one.  A gather: one thread per lattice point walks its eight adjacent cells in lexicographic order of the offset
+ *                  (-1 | 0 along x slowest, z fastest) and, inside a cell, the plan's order; it accumulates in double and rounds once to fp32.  No
+ *                  atomics: the same inputs give the same bits.  With normalize = 1 the output is sum / den, den = sum of w_p tri_p(q) over the same
+ *                  points in the same order, and 0 where den is not positive (RGB+T per lattice point).  n == 0 writes zeros.
+ * tn_poisson_sample out [n] DOUBLE = the trilinear interpolation of volume at the points: t as above, c = clamp(floor(t), 0, dim - 2), f = t - c (a
+ *                  point outside the grid extrapolates its border cell), the sum over the eight corners in lexicographic order of the offset
+ *                  (0 | 1, x slowest) of ((wx wy) wz) value, w_a = 1 - f_a | f_a, in double.  A point with a non-finite t gives NaN.
+ * tn_poisson_divergence  out = -div V for V [X,Y,Z,3]: d_a = (V_a(q + e_a) - V_a(q - e_a)) / (2 voxel_a) with V = 0 outside the grid,
+ *                  out = -((d_x + d_y) + d_z), in double, rounded once.
+ * tn_poisson_apply out = A x: a_a = ((2 x(q) - x(q - e_a)) - x(q + e_a)) / (voxel_a voxel_a) with x = 0 outside the grid (a Dirichlet boundary),
+ *                  out = (a_x + a_y) + a_z, plus screening(q) x(q) where screening [X,Y,Z] (non-negative; null: none) is given; in double, rounded
+ *                  once.  out must not be x.
+ * tn_poisson_solve conjugate gradients on A x = b.  x is in/out and is the starting guess.  x, r, p and A p are stored in fp32; r = b - A x with A x
+ *                  rounded as tn_poisson_apply rounds it; every update (x += alpha p, r -= alpha A p, p = r + beta p) is evaluated in double and
+ *                  rounded once.  Every dot product is one double partial per block (at most 1024 blocks of 256 threads, grid-stride beyond) folded
+ *                  in a fixed order; alpha = r.r / p.Ap and beta = r.r(new) / r.r stay on the device in double.  The run stops after the first
+ *                  iteration with r.r <= tol^2 b.b (r the recursive residual; before the first one if the guess already satisfies it) or after
+ *                  max_iterations.  The stop is decided on the device: later launches read a flag and return, so the result does not depend on
+ *                  check_every.  Three launches per iteration and no host synchronisation inside one; the host reads the state back every
+ *                  check_every iterations only, so this call synchronises the stream and cannot be captured into a graph.  record (HOST double[3])
+ *                  receives [iterations run, r.r, b.b].  tol = 0 runs exactly max_iterations iterations (unless r.r reaches 0).
+ * Refused with TN_EINVAL before any launch: null pointers (values, weights and screening may be null; arrays of 0 points may be), a dimension below
+ * 2 or 2^31 lattice points and more, n negative or at or above 2^31, C outside 1..4 (or above 1 without values), normalize other than 0 or 1, an origin
+ * that is not finite, a voxel size that is not positive and finite, a negative or non-finite tol, a negative max_iterations, check_every below 1, a
+ * workspace that is short or not 256-byte aligned.  n == 0 is TN_OK everywhere.
+ *
+ * scratch of tn_poisson_bin / tn_poisson_splat (12 bytes per point, 4 per cell, and for rocprim's sort a bound of 12 more per point and 1 MiB:
+ * the plan checks rocprim's own figure against it and answers TN_ELAUNCH where it does not fit); 0 for n == 0, -1 for refused sizes */
+TN_API int64_t tn_poisson_workspace_bytes(int64_t n, int32_t X, int32_t Y, int32_t Z);
+TN_API int tn_poisson_bin(const float* points, int64_t n, int32_t X, int32_t Y, int32_t Z, float origin_x, float origin_y, float origin_z,
+                          float voxel_x, float voxel_y, float voxel_z, void* workspace, int64_t workspace_bytes, tn_stream_t stream);
+TN_API int tn_poisson_splat(const float* points, int64_t n, const float* values, int32_t C, const float* weights, int32_t normalize, int32_t X,
+                            int32_t Y, int32_t Z, float origin_x, float origin_y, float origin_z, float voxel_x, float voxel_y, float voxel_z,
+                            float* out, const void* workspace, int64_t workspace_bytes, tn_stream_t stream);
+TN_API int tn_poisson_sample(const float* points, int64_t n, const float* volume, int32_t X, int32_t Y, int32_t Z, float origin_x, float origin_y,
+                             float origin_z, float voxel_x, float voxel_y, float voxel_z, double* out, tn_stream_t stream);
+TN_API int tn_poisson_divergence(const float* field, int32_t X, int32_t Y, int32_t Z, float voxel_x, float voxel_y, float voxel_z, float* out,
+                                 tn_stream_t stream);
+TN_API int tn_poisson_apply(const float* x, const float* screening, int32_t X, int32_t Y, int32_t Z, float voxel_x, float voxel_y, float voxel_z,
+                            float* out, tn_stream_t stream);
+/* scratch of tn_poisson_solve (r, p and A p, two rows of block partials, two state slots); -1 for refused sizes */
+TN_API int64_t tn_poisson_solve_workspace_bytes(int32_t X, int32_t Y, int32_t Z);
+TN_API int tn_poisson_solve(const float* b, const float* screening, float* x, int32_t X, int32_t Y, int32_t Z, float voxel_x, float voxel_y,
+                            float voxel_z, double tol, int32_t max_iterations, int32_t check_every, double* record, void* workspace,
+                            int64_t workspace_bytes, tn_stream_t stream);
+
 /* ---- Texture baking for exported meshes (nerfstudio/exporter/texture_utils.py with unwrap_method "custom": unwrap_mesh_per_uv_triangle, and the ray
  * length and origin offset of export_textured_mesh; xatlas unwrapping is not built).  The atlas, the weights and the kernels are stated once, in the
  * header comment of csrc/tn_texture.hip; tests/texture_functional.py restates the reference's formula.  In short, for F faces and px =

@@ -298,6 +298,15 @@ SIGNATURES = {
     "tn_mesh_simplify_count": (C.c_int, [_p, _i64, _p, _i64] + [_f] * 6 + [_i32] * 3 + [_p, _p, _i64, _p]),
     "tn_mesh_simplify_plan": (C.c_int, [_p, _i64, _p, _i64] + [_f] * 6 + [_i32] * 3 + [_p, _p, _i64, _p]),
     "tn_mesh_simplify_emit": (C.c_int, [_p, _p, _p, _i64, _p, _i64] + [_f] * 6 + [_i32] * 3 + [_f, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p]),
+    # Poisson reconstruction on a dense grid: the plan of a cloud, the gather splat, the trilinear sample, -div, the operator and the CG solve
+    "tn_poisson_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "tn_poisson_bin": (C.c_int, [_p, _i64] + [_i32] * 3 + [_f] * 6 + [_p, _i64, _p]),
+    "tn_poisson_splat": (C.c_int, [_p, _i64, _p, _i32, _p, _i32] + [_i32] * 3 + [_f] * 6 + [_p, _p, _i64, _p]),
+    "tn_poisson_sample": (C.c_int, [_p, _i64, _p] + [_i32] * 3 + [_f] * 6 + [_p, _p]),
+    "tn_poisson_divergence": (C.c_int, [_p] + [_i32] * 3 + [_f] * 3 + [_p, _p]),
+    "tn_poisson_apply": (C.c_int, [_p, _p] + [_i32] * 3 + [_f] * 3 + [_p, _p]),
+    "tn_poisson_solve_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "tn_poisson_solve": (C.c_int, [_p, _p, _p] + [_i32] * 3 + [_f] * 3 + [_d, _i32, _i32, C.POINTER(_d), _p, _i64, _p]),
     # texture baking: the atlas layout (host only), texture coordinates, per-texel rays and vertex colours over a texel range, the image store
     "tn_texture_layout": (C.c_int, [_i64, _i32, C.POINTER(_i64)]),
     "tn_texture_coords": (C.c_int, [_i64, _i32, _p, _p]),
