@@ -1241,6 +1241,49 @@ TN_API int tn_transform_splat(const TnSplatTransform* transform, const float* me
                               float* means_out, float* log_scales_out, float* quats_out, float* features_rest_out, float* thermal_rest_out,
                               tn_stream_t stream);
 
+/* ---- Mip-Splatting's 3D smoothing filter (ThermalSplatfactoModelConfig.use_3d_filter; "Mip-Splatting: Alias-free 3D Gaussian Splatting", eq. 6-7
+ * and 9): every Gaussian is band-limited to the highest frequency any training camera could have sampled, as a per-Gaussian pre-transform of the
+ * log-scales and opacity logits the rasteriser reads.  Everything runs on the caller's stream without atomics, host synchronisation or read-back;
+ * every value is evaluated in double from the float inputs widened and rounded once; the same inputs give the same bits.
+ * tests/splat_filter3d_functional.py restates all three.
+ *
+ * tn_filter3d_splat_compute: means [N,3], cameras [num_cameras,18] fp32 -- per row the 12 entries of the world -> camera matrix in
+ * TnSplatCamera.viewmat's convention, then fx, fy, cx, cy, width, height -> filter_3d [N].  With (x, y, z) = viewmat [p; 1], each coordinate
+ * ((m0 px + m1 py) + m2 pz) + m3, u = fx x / z + cx and v = fy y / z + cy, camera n sees Gaussian k iff z > near_plane and
+ * -0.15 width <= u <= 1.15 width and -0.15 height <= v <= 1.15 height.  nu_k = the maximum of max(fx, fy) / z over the cameras that see k, and
+ * filter_3d[k] = sqrt(variance) / nu_k.  A Gaussian no camera sees takes the smallest nu of the seen ones (the largest filter); when no Gaussian is
+ * seen (or num_cameras == 0) every row is 0: the filter is off.  The maximum is taken per camera as the paper states it, NOT by the official code's
+ * shortcut of one global focal length over each Gaussian's smallest depth, which is wrong by the ratio of the focal lengths on a rig whose
+ * cameras differ (a thermal camera at a quarter of the RGB resolution).  Two launches: per-block minima of nu go to the workspace, the second
+ * launch folds them and writes the unseen rows.  num_gaussians == 0 is TN_OK without a launch.  Refused with TN_EINVAL before any launch:
+ * num_gaussians outside [0, 2^31), num_cameras < 0, near_plane or variance negative or not finite, null pointers, a workspace that is short or not
+ * 8-byte aligned.
+ * (Named tn_filter3d_splat_*, outside the tn_splat_* family, as tn_transform_splat is: that family is the frame, training and refinement stages.)
+ *
+ * scratch of tn_filter3d_splat_compute (a double per block of 256 Gaussians); -1 on bad sizes */
+TN_API int64_t tn_filter3d_splat_workspace_bytes(int64_t num_gaussians);
+TN_API int tn_filter3d_splat_compute(const float* means, int64_t num_gaussians, const float* cameras, int32_t num_cameras, double near_plane,
+                                     double variance, float* filter_3d, void* workspace, int64_t workspace_bytes, tn_stream_t stream);
+/* log_scales [N,3], opacities [N] (logits), opacities_thermal [N] or NULL, filter_3d [N] -> the scales and opacities the rasteriser is to read.
+ * With f = filter_3d[k], s_i = exp(log_scales[k][i]), r_i = s_i^2 / (s_i^2 + f^2), c = sqrt(r_0 r_1 r_2) -- evaluated as log c = -1/2 ((log1p(t_0) +
+ * log1p(t_1)) + log1p(t_2)), t_i = f^2 / s_i^2, and 1 - c = -expm1(log c), so that 1 - c does not cancel where f is far below the scales:
+ *   log_scales_out[k][i] = 1/2 log(s_i^2 + f^2)          opacities_out[k] = (o + log c) - log1p(e^o (1 - c))   (the logit of sigmoid(o) c)
+ * and opacities_thermal_out likewise from opacities_thermal.  A row with f == 0 is copied bit for bit.  One launch, a thread per Gaussian.  The two
+ * thermal pointers are both NULL (shared mode) or both set.  An output may be its own input.  Refused with TN_EINVAL before any launch:
+ * num_gaussians outside [0, 2^31), null pointers, a thermal pointer pair that is half set. */
+TN_API int tn_filter3d_splat_apply(const float* log_scales, const float* opacities, const float* opacities_thermal, const float* filter_3d,
+                                   int64_t num_gaussians, float* log_scales_out, float* opacities_out, float* opacities_thermal_out,
+                                   tn_stream_t stream);
+/* The exact derivative of tn_filter3d_splat_apply in the raw log-scales and logits (filter_3d takes none), closed form, one launch.  With
+ * 1 - p = 1 / (1 + e^o), p = 1 / (1 + e^-o), 1 - p' = (1 - p) + p (1 - c), 1 - r_i = f^2 / (s_i^2 + f^2), per chain:
+ *   v_log_scales[k][i] = v_log_scales_out[k][i] r_i + (v_opacities_out[k] / (1 - p') + v_opacities_thermal_out[k] / (1 - p'_th)) (1 - r_i)
+ *   v_opacities[k]     = v_opacities_out[k] (1 - p) / (1 - p')                              (and the thermal chain's likewise)
+ * A row with f == 0 copies its upstream gradients bit for bit.  The three thermal pointers are all NULL or all set. */
+TN_API int tn_filter3d_splat_apply_backward(const float* log_scales, const float* opacities, const float* opacities_thermal, const float* filter_3d,
+                                            const float* v_log_scales_out, const float* v_opacities_out, const float* v_opacities_thermal_out,
+                                            int64_t num_gaussians, float* v_log_scales, float* v_opacities, float* v_opacities_thermal,
+                                            tn_stream_t stream);
+
 /* ---- point-cloud export of the NeRF (ns-export pointcloud: nerfstudio/scripts/exporter.py:90-186, nerfstudio/exporter/exporter_utils.py:83-260,
  * generate_point_cloud): rendered rays are back-projected by their depth, the opaque ones inside a box are kept, statistical outliers are
  * removed.  Every point carries the rendered colour and the rendered thermal value.  Both entry points run on the caller's stream without a host

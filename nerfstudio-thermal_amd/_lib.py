@@ -280,6 +280,12 @@ SIGNATURES = {
     "tn_export_splat_pack": (C.c_int, [_p] * 9 + [_i64, _i32, _i32, _i32, _f, C.POINTER(TnSplatCrop), _p, _p, _p, _i64, _p]),
     # a similarity applied to every Gaussian (means, log scales, quaternions and the SH bands 1 to 3 of both spectra), in place or not
     "tn_transform_splat": (C.c_int, [C.POINTER(TnSplatTransform)] + [_p] * 5 + [_i64, _i32] + [_p] * 5 + [_p]),
+    # Mip-Splatting's 3D smoothing filter: the filter value per Gaussian from the training cameras, its application to log-scales and opacity
+    # logits (a NULL thermal pointer group is shared mode) and the closed-form backward (named outside the tn_splat_* family, as tn_transform_splat)
+    "tn_filter3d_splat_workspace_bytes": (_i64, [_i64]),
+    "tn_filter3d_splat_compute": (C.c_int, [_p, _i64, _p, _i32, _d, _d, _p, _p, _i64, _p]),
+    "tn_filter3d_splat_apply": (C.c_int, [_p] * 4 + [_i64] + [_p] * 3 + [_p]),
+    "tn_filter3d_splat_apply_backward": (C.c_int, [_p] * 7 + [_i64] + [_p] * 3 + [_p]),
     # point-cloud export of the NeRF: stable append of a rendered batch, statistical outlier removal
     "tn_cloud_append_workspace_bytes": (_i64, [_i64]),
     "tn_cloud_append": (C.c_int, [_p] * 5 + [_i64, _p, _i64, _i64, _f, C.POINTER(TnSplatCrop), _p, _p, _p, _i64, _p, _p, _i64, _p]),

@@ -63,7 +63,13 @@ camera's automatic gain control and flat-field corrections, an RGB camera's auto
 ones (this project's addition), both the identity at first, which returns the render bit for bit; their groups are bilateral_grid /
 bilateral_grid_thermal (optim.SPLAT_BILAGRID_OPTIMIZERS, splatfacto's rates; its 1000-step warm-up of the group is not built:
 ExponentialDecayLR has none).  Eval renders are never corrected.  What the grid is worth on a drifting scene is an observation in
-profiles/splat_bilagrid.md, not a claim.  Masks are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
+profiles/splat_bilagrid.md, not a claim.  With `use_3d_filter` every render -- training, eval, cropped, removal, and so the TSDF exporter and
+the camera paths -- reads Mip-Splatting's 3D smoothing filter (splat_filter.py; the world-space companion of "antialiased"): `filter_3D` [N], a
+buffer computed from the cameras given to `set_filter_cameras` (tn_filter3d_splat_compute; again every `filter_3d_every` training steps and whenever
+the cameras or the Gaussians change), widens the log-scales and compensates the opacity logits in one launch before the projection
+(tn_filter3d_splat_apply, its backward closed form), so the gradients reach the raw parameters, which refinement, culls, the opacity reset and the
+scale regulariser keep reading.  Without cameras the render is the unfiltered one, bit for bit; strategy "mcmc" refuses the switch (its relocation
+preserves the render of raw parameters: out of scope).  Whether the filter improves a real RGB + thermal capture is not claimed.  Masks are not built.  Parity is unpinned (gsplat is a third-party package outside the reference
 tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 
 splat_calls.py: the C entry points, their names and argument order, the workspaces, `knn_distances`, `mcmc_relocate`, `mcmc_noise`.
@@ -85,6 +91,7 @@ from .config import CameraOptimizerConfig
 from .splat_calls import KNN_MAX_K, _PARAM_NAMES, knn_distances, mcmc_noise, mcmc_relocate, param_names  # noqa: F401
 from .splat_camera import (CAMERA_OPTIMIZER_MODES, OrientedBox, PinholeCamera, SplatCameraOptimizer, camera_struct, downscale_factor,  # noqa: F401
                            pose_camera_record, projection_matrix, rescaled_camera, undistorted_camera)
+from .splat_filter import apply_3d_filter, compute_3d_filter, filter_camera_table  # noqa: F401
 from .splat_image import (MAX_IMAGE_SIDE, _psnr, bilateral_grid_tv, bilateral_slice, depth_losses, image_loss, resize_image, ssim,  # noqa: F401
                           thermal_regularizers, undistort_image)
 
@@ -171,6 +178,16 @@ class ThermalSplatfactoModelConfig:
     # renders too).  RGB frames read camera_optimizer, thermal frames camera_optimizer_thermal; penalty_scale < 0 also means off
     camera_optimizer: CameraOptimizerConfig = field(default_factory=CameraOptimizerConfig)
     camera_optimizer_thermal: CameraOptimizerConfig = field(default_factory=CameraOptimizerConfig)
+    # Mip-Splatting's 3D smoothing filter (splat_filter.py), the world-space companion of rasterize_mode "antialiased": every render reads scales
+    # convolved with a per-Gaussian filter of standard deviation sqrt(filter_3d_variance) / nu_k -- nu_k the highest sampling rate (focal length in
+    # pixels over depth) of any camera given to `set_filter_cameras` that sees the Gaussian beyond filter_3d_near -- and the compensated opacity;
+    # the buffer is recomputed every filter_3d_every training steps and whenever the cameras or the Gaussians change.  The parameters stay raw:
+    # refinement, culls, the opacity reset and the scale regulariser read them as before.  Not with strategy "mcmc", whose relocation preserves
+    # the render of the raw parameters only.  Off: nothing new is called
+    use_3d_filter: bool = False
+    filter_3d_variance: float = 0.2
+    filter_3d_near: float = 0.2
+    filter_3d_every: int = 100
     # per-frame colour correction (current splatfacto's use_bilateral_grid / grid_shape; gsplat's bilateral grids): every training frame has a grid
     # of affine colour transforms, grid_shape = (GW, GH, L) -- indexed by pixel position and brightness -- applied to its training render only and
     # regularised by tv_loss = bilateral_grid_tv_mult * total variation (10: splatfacto's constant).  RGB frames have 3 x 4 matrices (bil_grids),
@@ -212,6 +229,14 @@ class ThermalSplatfactoModelConfig:
             raise ValueError(f"mcmc_min_opacity = {self.mcmc_min_opacity}: an opacity inside (0, 1)")
         if not self.mcmc_grow_factor >= 1:
             raise ValueError(f"mcmc_grow_factor = {self.mcmc_grow_factor}: a factor >= 1")
+        if self.use_3d_filter and self.strategy == "mcmc":
+            raise ValueError('use_3d_filter does not go with strategy "mcmc": the relocation\'s render-preserving opacity and scale correction is '
+                             "stated on the raw parameters, not on the filtered ones the render would read")
+        for name in ("filter_3d_variance", "filter_3d_near"):
+            if not (getattr(self, name) >= 0 and math.isfinite(getattr(self, name))):
+                raise ValueError(f"{name} = {getattr(self, name)}: a finite number >= 0")
+        if isinstance(self.filter_3d_every, bool) or not isinstance(self.filter_3d_every, int) or self.filter_3d_every < 1:
+            raise ValueError(f"filter_3d_every = {self.filter_3d_every!r}: a number of steps >= 1")
         if self.removal_min_opacity_diff is not None:
             if self.thermal_opacity_mode != "separate":
                 raise ValueError('removal_min_opacity_diff needs thermal_opacity_mode "separate": the removal renders compare the two opacities')
@@ -465,6 +490,14 @@ class ThermalSplatfactoModel(nn.Module):
                 self.bil_grids = nn.Parameter(identity_bilateral_grids(n_rgb, 3, self.config.grid_shape, dev))
             if n_th > 0:
                 self.bil_grids_thermal = nn.Parameter(identity_bilateral_grids(n_th, 1, self.config.grid_shape, dev))
+        # Mip-Splatting's 3D filter: a value per Gaussian (a buffer -- no parameter, in no optimiser group, and not in the state dict: it follows
+        # from the means and the cameras), the device table of the cameras it is computed from, and what says that it must be computed again
+        self._filter_table: Optional[Tensor] = None
+        self._filter_stale = True
+        self._filter_epoch = 0  # step // filter_3d_every at the last refresh
+        self.filter_refreshes = 0
+        if self.config.use_3d_filter:
+            self.register_buffer("filter_3D", torch.zeros(self.gauss_params["means"].shape[0], device=dev), persistent=False)
         self.step = 0
         self._ws: Optional[Tensor] = None
         self._cap = 0
@@ -568,6 +601,56 @@ class ThermalSplatfactoModel(nn.Module):
         if not self.separate and "opacities_thermal" in params:
             raise ValueError('load_gaussians: opacities_thermal belongs to thermal_opacity_mode "separate"')
         self.gauss_params = nn.ParameterDict({k: nn.Parameter(v.detach().float().contiguous().to(dev)) for k, v in params.items()})
+        self._filter_stale = True
+
+    # ------------------------------------------------------------------------------------------------ Mip-Splatting's 3D filter (splat_filter.py)
+    def set_filter_cameras(self, cameras) -> None:
+        """The cameras the 3D filter is computed from: the full-resolution training cameras of both spectra, uncorrected by any pose optimiser
+        (ThermalFullImageDatamanager.train_cameras); None or an empty list takes them away, which switches the filter off.  The table goes to the
+        device now, the buffer is recomputed before the next render."""
+        cameras = list(cameras) if cameras is not None else []
+        self._filter_table = filter_camera_table(cameras, self.means.device).contiguous() if cameras else None
+        self._filter_stale = True
+
+    def _current_filter(self, training: bool = False) -> Optional[Tensor]:
+        """filter_3D [N] as every render of this moment must read it, or None when there is nothing to apply (the switch is off, or no cameras
+        are set: the buffer is zero then).  Recomputed (`compute_3d_filter`: two launches, nothing read back) when the cameras were set, when the
+        Gaussians were replaced or their number changed, and in training every filter_3d_every steps; a buffer whose row count is not N is never
+        handed out."""
+        if not self.config.use_3d_filter:
+            return None
+        N = self.num_points
+        if self._filter_table is None:
+            if self.filter_3D.shape[0] != N or self._filter_stale:
+                self.filter_3D = torch.zeros(N, device=self.means.device)
+                self._filter_stale = False
+            return None
+        epoch = self.step // self.config.filter_3d_every
+        if self._filter_stale or self.filter_3D.shape[0] != N or (training and epoch != self._filter_epoch):
+            with torch.no_grad():
+                self.filter_3D = compute_3d_filter(self.gauss_params["means"].detach().contiguous(), self._filter_table, self.config.filter_3d_near,
+                                                   self.config.filter_3d_variance)
+            self._filter_stale, self._filter_epoch = False, epoch
+            self.filter_refreshes += 1
+        return self.filter_3D
+
+    def _render_params(self, training: bool = False) -> List[Tensor]:
+        """The gauss_params tensors in param_names order as the projection reads them: with use_3d_filter and cameras the log-scales and the
+        opacity logits (both, in separate mode) are the filtered ones (`apply_3d_filter`: one launch, differentiable in the raw parameters)."""
+        params = [self.gauss_params[k] for k in self.param_names]
+        f = self._current_filter(training)
+        if f is not None and self.num_points > 0:
+            out = apply_3d_filter(params[1], params[3], f, params[8] if self.separate else None)
+            params[1], params[3] = out[0], out[1]
+            if self.separate:
+                params[8] = out[2]
+        return params
+
+    @torch.no_grad()
+    def filtered_gaussians(self) -> Dict[str, Tensor]:
+        """name -> tensor, detached: the Gaussians every render shows -- gauss_params with the 3D filter fused into scales and opacities (what
+        Mip-Splatting's save_fused_ply writes); the raw parameters themselves when the filter is off or has no cameras."""
+        return {k: v.detach() for k, v in zip(self.param_names, self._render_params())}
 
     def _background4(self, training: bool) -> List[float]:
         """The frame's background, RGB + thermal (splatfacto.py:668-682): "white", "random" (training: four uniform draws of the model's own
@@ -632,7 +715,7 @@ class ThermalSplatfactoModel(nn.Module):
         if N == 0:  # every Gaussian culled: the background (splatfacto.py:759-764); last_projection stays what it was
             return _background_outputs(H, W, bgl, dev, self.separate, thr is not None)
         cam = camera_struct(camera)
-        params = [self.gauss_params[k] for k in self.param_names]
+        params = self._render_params()
         pose, row = self._pose_row(camera, training=False)  # a shared row corrects eval renders of its spectrum too; per-frame rows never do
         rec = pose_camera_record(camera, cam, pose.detach(), row) if row is not None else None
         _, ws, cap, total = _project_and_bin(self, cam, params, H, W, deg, aa, max(self._cap, 1 << 16), self._workspace, self._crop(), rec)
@@ -701,7 +784,7 @@ class ThermalSplatfactoModel(nn.Module):
         pose, row = self._pose_row(camera, training=True)
         if row is not None:  # the frame's pose row: one more differentiable input
             frame["pose_row"] = row
-        rgbt, alpha, depth, *alpha_th = _SplatRender.apply(frame, *(self.gauss_params[k] for k in names), *([pose] if row is not None else []))
+        rgbt, alpha, depth, *alpha_th = _SplatRender.apply(frame, *self._render_params(training=True), *([pose] if row is not None else []))
         alpha_th = alpha_th[0] if alpha_th else None  # separate mode: the thermal chain's accumulation (differentiable)
         if self.last_num_intersections == 0:  # the background as get_outputs returns it (no clamp)
             rgb, thermal = rgbt[..., :3], rgbt[..., 3:]
@@ -898,6 +981,7 @@ class ThermalSplatfactoModel(nn.Module):
         dev = self.means.device
         self.gauss_params = nn.ParameterDict({k: nn.Parameter(torch.zeros((n,) + tuple(self.gauss_params[k].shape[1:]), device=dev)) for k in self.param_names})
         self.xys_grad_norm = self.vis_counts = self.max_2Dsize = None
+        self._filter_stale = True
         return super().load_state_dict(state_dict, strict=strict, **kwargs)
 
     def _refine_struct(self) -> _lib.TnSplatRefine:
@@ -1000,6 +1084,7 @@ class ThermalSplatfactoModel(nn.Module):
         exp_avg_sq) installed where given; step counts and every other state key are kept."""
         old = {k: self.gauss_params[k] for k in self.param_names}
         self.gauss_params = nn.ParameterDict({k: nn.Parameter(new[k]) for k in self.param_names})
+        self._filter_stale = True  # other Gaussians: the 3D filter's buffer is recomputed before the next render
         for g, k in self.group_params.items():
             o = opts.get(g)
             if o is None:

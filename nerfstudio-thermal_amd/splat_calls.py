@@ -1,4 +1,4 @@
-"""The call layer of the splat path: the one module that names the tn_splat_* / tn_knn / tn_image_* / tn_thermal_reg / tn_depth_loss / tn_bilagrid_* / tn_transform_splat entry points of
+"""The call layer of the splat path: the one module that names the tn_splat_* / tn_knn / tn_image_* / tn_thermal_reg / tn_depth_loss / tn_bilagrid_* / tn_transform_splat / tn_filter3d_splat_* entry points of
 libthermal_nerf_hip.so and knows their argument order (include/thermal_nerf_hip.h).  The three gsplat calls (project_gaussians,
 spherical_harmonics, rasterize_gaussians x2) run as tn_splat_project / tn_splat_bin / tn_splat_raster of libthermal_nerf_hip.so; separate thermal
 opacity runs the _sep family (tn_splat_project_sep ... tn_splat_refine_apply_sep: the same kernels instantiated with the second chain), and _crop,
@@ -220,6 +220,42 @@ def transform_call(transform, means, scales, quats, rest, rest_thermal, means_ou
     sh = ([None, None], [None, None]) if R == 0 else (_f32(features_rest=rest, features_rest_thermal=rest_thermal),
                                                     _f32(features_rest_out=rest_out, features_rest_thermal_out=rest_thermal_out))
     _call("tn_transform_splat", C.byref(transform), *geo[0], *sh[0], N, R, *geo[1], *sh[1])
+
+
+FILTER_CAMERA_FLOATS = 18  # a row of the 3D filter's camera table: viewmat 12 | fx fy cx cy | width height
+
+
+def filter3d_compute(means, camera_table, near: float, variance: float, out) -> None:
+    """tn_filter3d_splat_compute: Mip-Splatting's 3D filter value of every Gaussian, `out` [N], from means [N,3] and the camera table
+    [C,18] (splat_filter.filter_camera_table).  Two launches, no read-back; the partial minima's workspace is this call's own."""
+    N, Cn = means.shape[0], camera_table.shape[0]
+    if tuple(means.shape) != (N, 3) or tuple(camera_table.shape) != (Cn, FILTER_CAMERA_FLOATS) or tuple(out.shape) != (N,):
+        raise ValueError(f"filter3d_compute: means [N,3], a camera table [C,{FILTER_CAMERA_FLOATS}] and out [N] expected, got {tuple(means.shape)}, "
+                         f"{tuple(camera_table.shape)} and {tuple(out.shape)}")
+    ws = workspace("tn_filter3d_splat_workspace_bytes", N, device=means.device, what="bad Gaussian count")
+    _call("tn_filter3d_splat_compute", *_f32(means=means), N, *_f32(camera_table=camera_table if Cn else None), Cn, float(near), float(variance),
+          *_f32(filter_3D=out), _raw(ws), ws.numel())
+
+
+def filter3d_apply(scales, opacities, filter_3d, scales_out, opacities_out, opacities_thermal=None, opacities_thermal_out=None) -> None:
+    """tn_filter3d_splat_apply: the filtered log-scales [N,3] and opacity logits [N,1] (and thermal logits, where given) of one launch."""
+    N = scales.shape[0]
+    th = [None, None] if opacities_thermal is None else _f32(opacities_thermal=opacities_thermal.reshape(-1),
+                                                              opacities_thermal_out=opacities_thermal_out.reshape(-1))
+    _call("tn_filter3d_splat_apply", *_f32(scales=scales, opacities=opacities.reshape(-1)), th[0], *_f32(filter_3D=filter_3d), N,
+          *_f32(scales_out=scales_out, opacities_out=opacities_out.reshape(-1)), th[1])
+
+
+def filter3d_apply_backward(scales, opacities, filter_3d, v_scales_out, v_opacities_out, v_scales, v_opacities, opacities_thermal=None,
+                            v_opacities_thermal_out=None, v_opacities_thermal=None) -> None:
+    """tn_filter3d_splat_apply_backward: dL/d raw log-scales and logits from the gradients of the filtered ones, one launch."""
+    N = scales.shape[0]
+    th = [None, None, None] if opacities_thermal is None else _f32(opacities_thermal=opacities_thermal.reshape(-1),
+                                                                    v_opacities_thermal_out=v_opacities_thermal_out.reshape(-1),
+                                                                    v_opacities_thermal=v_opacities_thermal.reshape(-1))
+    _call("tn_filter3d_splat_apply_backward", *_f32(scales=scales, opacities=opacities.reshape(-1)), th[0], *_f32(filter_3D=filter_3d),
+          *_f32(v_scales_out=v_scales_out, v_opacities_out=v_opacities_out.reshape(-1)), th[1], N,
+          *_f32(v_scales=v_scales, v_opacities=v_opacities.reshape(-1)), th[2])
 
 
 # ---------------------------------------------------------------------------------------------------- refinement

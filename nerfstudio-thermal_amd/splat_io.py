@@ -210,7 +210,7 @@ def pack_call(params: Sequence[Tensor], spectrum: int, colour_mode: int, min_opa
 
 # ---------------------------------------------------------------------------------------------------- export and import of a model
 def export_gaussian_ply(model, path: str, spectrum: str = "both", min_opacity: float = 0.0, crop: Box = None,
-                        transform: Optional[Similarity] = None) -> dict:
+                        transform: Optional[Similarity] = None, fuse_3d_filter: bool = True) -> dict:
     """`model`'s Gaussians as the splat file `path`.  Dropped: Gaussians with a parameter of the row that is not finite, with
     sigmoid(opacity) < min_opacity (the row's opacity; in a "both" file of a separate-mode model the larger of the two, the MCMC strategy's notion
     of a live Gaussian; 0 keeps every opacity), and, with `crop` (an OrientedBox), those whose mean is not strictly inside the box.  One read-back
@@ -220,11 +220,18 @@ def export_gaussian_ply(model, path: str, spectrum: str = "both", min_opacity: f
     `transform` None writes the model's frame ("frame": "model").  With a Similarity the parameters are moved out of place on the device
     (transform_gaussians; the model is not touched) and then packed as before ("frame": "transformed").  `crop` is still given in the model's
     frame, as an OrientedBox: it is moved with `transform.apply_box` and tested on the moved means, so a mean within rounding of a face may fall
-    either way.  A parameter that is not finite stays not finite through the move, so the same Gaussians are dropped; `min_opacity` is not affected."""
+    either way.  A parameter that is not finite stays not finite through the move, so the same Gaussians are dropped; `min_opacity` is not affected.
+
+    A model with use_3d_filter writes, by default, the scales and opacities its renders read -- the 3D filter fused in (model.filtered_gaussians;
+    Mip-Splatting's save_fused_ply), so a viewer shows what was trained, and `min_opacity` then compares the filtered opacity;
+    `fuse_3d_filter=False` writes the raw parameters.  A move by `transform` comes after the fusion."""
     if spectrum not in SPECTRA:
         raise ValueError(f"spectrum must be one of {sorted(SPECTRA)}, got {spectrum!r}")
     colour_mode = 1 if model.config.sh_degree == 0 else 0
-    named = {k: model.gauss_params[k].detach().contiguous() for k in model.param_names}
+    if fuse_3d_filter and getattr(model.config, "use_3d_filter", False):
+        named = {k: v.contiguous() for k, v in model.filtered_gaussians().items()}
+    else:
+        named = {k: model.gauss_params[k].detach().contiguous() for k in model.param_names}
     if transform is not None:
         if crop is not None and not transform.is_identity:
             if not isinstance(crop, OrientedBox):

@@ -175,6 +175,8 @@ def main():
     ap.add_argument("--noise-lr", type=float, default=5e5, help="the MCMC strategy's position noise, in units of the means' learning rate")
     ap.add_argument("--use-bilateral-grid", action="store_true",
                     help="a bilateral grid of affine colour transforms per training frame, applied to its training render (tv_loss regularises it)")
+    ap.add_argument("--use-3d-filter", action="store_true",
+                    help="Mip-Splatting's 3D smoothing filter from the full-resolution training cameras of both spectra (not with --strategy mcmc)")
     ap.add_argument("--frame-drift", type=float, default=0.0, metavar="X",
                     help="generated scene only: training frames times a per-frame gain in [1-X, 1+X] plus an offset in [-X/2, X/2]; val frames untouched")
     ap.add_argument("--no-undistort", action="store_true", help="train on the raw frames with the parser's intrinsics (the distortion dropped)")
@@ -192,6 +194,8 @@ def main():
         ap.error("--frame-drift takes X in [0, 1)")
     if args.seed_from_dataset and args.data is None:
         ap.error("--seed-from-dataset reads the ply_file_path of a dataset on disk: it needs --data")
+    if args.use_3d_filter and args.strategy == "mcmc":
+        ap.error("--use-3d-filter does not go with --strategy mcmc")
     if args.removal_min_opacity_diff is not None and args.thermal_opacity_mode != "separate":
         ap.error("--removal-min-opacity-diff compares the two opacities: it needs --thermal-opacity-mode separate")
     crop_args = (args.crop_pos, args.crop_rpy, args.crop_scale)
@@ -228,9 +232,11 @@ def main():
                                        camera_optimizer=CameraOptimizerConfig(mode=args.camera_optimizer),
                                        camera_optimizer_thermal=CameraOptimizerConfig(mode=args.camera_optimizer_thermal), use_absgrad=args.use_absgrad,
                                        densify_grad_thresh=args.densify_grad_thresh, strategy=args.strategy, max_gs_num=args.max_gs_num,
-                                       noise_lr=args.noise_lr, use_bilateral_grid=args.use_bilateral_grid)
+                                       noise_lr=args.noise_lr, use_bilateral_grid=args.use_bilateral_grid, use_3d_filter=args.use_3d_filter)
     model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=dm.num_train_data, seed_points=seed_points,
                                    train_is_thermal=dm.train_is_thermal)
+    if args.use_3d_filter:
+        model.set_filter_cameras(dm.train_cameras)
     initial = model.num_points
     opts = Optimizers(model.get_param_groups(), {**SPLAT_OPTIMIZERS, **SPLAT_CAMERA_OPTIMIZERS, **SPLAT_BILAGRID_OPTIMIZERS}, optimizer_cls=HipAdam)
     cbs = model.get_training_callbacks(opts)
@@ -317,7 +323,8 @@ def main():
                       "cross_channel_loss_mult": args.cross_channel_loss_mult, "undistort": not args.no_undistort, "thermal_opacity_mode": args.thermal_opacity_mode,
                       "opacity_loss_mult": args.opacity_loss_mult, "camera_optimizer": args.camera_optimizer,
                       "camera_optimizer_thermal": args.camera_optimizer_thermal, "strategy": args.strategy, "max_gs_num": args.max_gs_num,
-                      "noise_lr": args.noise_lr, "use_bilateral_grid": args.use_bilateral_grid, "frame_drift": args.frame_drift, **extra, "stages": stages, "val_metrics": metrics, "curve": curve}))
+                      "noise_lr": args.noise_lr, "use_bilateral_grid": args.use_bilateral_grid, "use_3d_filter": args.use_3d_filter,
+                      "filter_refreshes": model.filter_refreshes, "frame_drift": args.frame_drift, **extra, "stages": stages, "val_metrics": metrics, "curve": curve}))
 
 
 if __name__ == "__main__":
