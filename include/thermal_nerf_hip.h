@@ -1284,6 +1284,31 @@ TN_API int tn_filter3d_splat_apply_backward(const float* log_scales, const float
                                             int64_t num_gaussians, float* v_log_scales, float* v_opacities, float* v_opacities_thermal,
                                             tn_stream_t stream);
 
+/* ---- ray contribution of every Gaussian (splat_prune.py: RadSplat's max over rays of alpha T, LightGaussian's hit-weighted sum), the score trained
+ * splats are pruned by.  tn_contrib_splat_raster runs on the frame workspace tn_splat_project* and tn_splat_bin left, exactly as tn_splat_raster
+ * does, and walks ONE transmittance chain of the frame's tile lists: chain 0 is the chain RGB, accumulation and depth are blended with, chain 1
+ * the thermal chain of a frame projected by a _sep entry point (only such a frame has one: the workspace does not say how it was projected,
+ * the caller must).  In antialiased mode the alpha is the one the chain's colour is blended with, the compensated one; the workspace's records hold it already,
+ * so `antialiased` (0 or 1, the frame's flag) is validated and selects nothing.  For every pixel p and every list entry g the forward would blend on
+ * that chain -- the same power >= 0 test, 1/255 gate, 0.999 clamp and nT <= 1e-4 stop, from the rasteriser's own helpers --
+ *   w = pixel_weight[p] * alpha * T          pixel_weight: [H,W] fp32, non-negative; NULL means 1
+ * and a Gaussian at which a pixel stops is not blended there and scores nothing there.  Four accumulators [num_gaussians] are updated IN PLACE, so
+ * a loop over cameras needs no temporaries and no read-back (the caller zeroes them before the first frame):
+ *   max_acc   fp32   max(old, max over p of w)
+ *   sum_acc   fp64   old + sum over p of w    (the frame's sum is formed in fp32 in a fixed order and added to the double once)
+ *   hits_acc  int64  old + the number of pixels with w > 0
+ *   views_acc int32  old + 1 if the frame's max is > 0
+ * Three launches, no atomics, no host synchronisation: the same inputs give the same bits.  The raster writes one (sum, max, count) record per
+ * (Gaussian, tile) pair into `scratch` -- every pair of every tile, zeros where nothing is blended -- and a fold per Gaussian walks its run.
+ * num_gaussians == 0 is TN_OK without a launch.  Refused with TN_EINVAL before any launch: a bad camera, sizes outside [0, 2^31), antialiased or
+ * chain other than 0 or 1, null pointers, a scratch shorter than tn_contrib_splat_workspace_bytes(num_gaussians, max_intersections) (-1 on bad
+ * sizes).  max_intersections is the capacity the frame workspace was laid out with.
+ * (Named tn_contrib_splat_*, outside the tn_splat_* family, as tn_depth_splat_raster_backward is.) */
+TN_API int64_t tn_contrib_splat_workspace_bytes(int64_t num_gaussians, int64_t max_intersections);
+TN_API int tn_contrib_splat_raster(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                   int32_t antialiased, int32_t chain, const float* pixel_weight, void* scratch, int64_t scratch_bytes,
+                                   float* max_acc, double* sum_acc, int64_t* hits_acc, int32_t* views_acc, tn_stream_t stream);
+
 /* ---- point-cloud export of the NeRF (ns-export pointcloud: nerfstudio/scripts/exporter.py:90-186, nerfstudio/exporter/exporter_utils.py:83-260,
  * generate_point_cloud): rendered rays are back-projected by their depth, the opaque ones inside a box are kept, statistical outliers are
  * removed.  Every point carries the rendered colour and the rendered thermal value.  Both entry points run on the caller's stream without a host

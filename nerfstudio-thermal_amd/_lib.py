@@ -286,6 +286,10 @@ SIGNATURES = {
     "tn_filter3d_splat_compute": (C.c_int, [_p, _i64, _p, _i32, _d, _d, _p, _p, _i64, _p]),
     "tn_filter3d_splat_apply": (C.c_int, [_p] * 4 + [_i64] + [_p] * 3 + [_p]),
     "tn_filter3d_splat_apply_backward": (C.c_int, [_p] * 7 + [_i64] + [_p] * 3 + [_p]),
+    # ray contribution of every Gaussian on one chain of a projected and binned frame, accumulated in place: max fp32, sum fp64, hits int64,
+    # views int32 (named outside the tn_splat_* family, as tn_depth_splat_raster_backward is)
+    "tn_contrib_splat_workspace_bytes": (_i64, [_i64, _i64]),
+    "tn_contrib_splat_raster": (C.c_int, [C.POINTER(TnSplatCamera), _i64, _p, _i64, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p, _p]),
     # point-cloud export of the NeRF: stable append of a rendered batch, statistical outlier removal
     "tn_cloud_append_workspace_bytes": (_i64, [_i64]),
     "tn_cloud_append": (C.c_int, [_p] * 5 + [_i64, _p, _i64, _i64, _f, C.POINTER(TnSplatCrop), _p, _p, _p, _i64, _p, _p, _i64, _p]),

@@ -1929,6 +1929,190 @@ extern "C" int tn_depth_splat_raster_backward(const TnSplatCamera* camera, int64
                                bwd_workspace_bytes, v_xys, v_xys_abs, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, depth, v_depth, v_depths, stream);
 }
 
+// ------------------------------------------------------------------------------------------------ ray contribution (splat_prune.py)
+// What every Gaussian contributes to a frame's rays: for each pixel p and each list entry g the forward blends on one transmittance chain,
+// w = pixel_weight[p] alpha T -- the weight the forward multiplies g's colour with.  Per Gaussian: the largest w (RadSplat's importance), the sum
+// (LightGaussian's hit-weighted score), the number of pixels with w > 0 and whether the frame saw it at all, accumulated over frames in place.
+//   k_splat_raster_contrib  the forward's walk (block = tile, wave = 8x8 quadrant, ballot culling, pipelined record fetch, the splat_* rules) on ONE
+//                           chain, reducing per Gaussian instead of per pixel: (sum, max, count) over the wave's 64 lanes by a fixed butterfly
+//                           (the count is a popcount of the ballot), parked per wave in LDS, the four waves combined in order, ONE record written to
+//                           the pair's slot -- addressed as k_splat_raster_bwd addresses it.  EVERY slot of the tile's list is written: zeros for the
+//                           Gaussians a wave's ballot skipped and for everything behind the batch at which all 256 pixels are done (the forward's
+//                           `break`), so the fold never reads what nobody wrote and nothing is cleared beforehand.
+//   k_splat_contrib_fold    thread = Gaussian: walks its run in list order and updates the four accumulators.
+// No atomics: the same inputs give the same bits.  A Gaussian at which a pixel stops (nT <= 1e-4) is not blended there and scores nothing there.
+// chain 0: SplatRec::b.y, the opacity RGB, accumulation and (classic) depth blend with; chain 1: SplatRec::d.w, the thermal chain of separate mode.
+// Both are the compensated opacity in antialiased mode -- what the chain's COLOUR is blended with, not the depth pass's plain one.
+// Static LDS: 8 KB of records + 1 KB of opacities + 12 KB of partial results.
+#define SPLAT_PAIR_CONTRIB 3  // per pair: sum of w over the tile's pixels, max of w, pixels with w > 0 (<= 256: exact in a float)
+__global__ void __launch_bounds__(256) k_splat_raster_contrib(const SplatRec* __restrict__ recs, const int32_t* __restrict__ sorted_ids,
+                                                              const int32_t* __restrict__ tile_bins, const int32_t* __restrict__ tile_order, int W, int H,
+                                                              int tbx, int chain, const float* __restrict__ pixel_weight, const int32_t* __restrict__ start,
+                                                              const int32_t* __restrict__ tbox, float* __restrict__ pair) {
+  __shared__ float4 sa[SPLAT_BATCH], sb[SPLAT_BATCH];
+  __shared__ float sl[SPLAT_BATCH];                          // l2op of the chain
+  __shared__ float sp[4][SPLAT_PAIR_CONTRIB][SPLAT_BATCH];  // per wave (sum, max, count) of the batch's Gaussians
+  const int tile = tile_order[blockIdx.x];
+  const int tile_x = tile % tbx, tile_y = tile / tbx;
+  int lane, wv, ix, iy;
+  float pxf, pyf, qcx, qcy;
+  const bool inside = splat_lane_pixel(tile_x, tile_y, W, H, lane, wv, ix, iy, pxf, pyf, qcx, qcy);
+  const int begin = tile_bins[2 * tile], end = tile_bins[2 * tile + 1];
+  const float pw = inside ? (pixel_weight ? pixel_weight[(int64_t)iy * W + ix] : 1.0f) : 0.0f;
+  float T = 1.0f;
+  bool done = !inside;
+  // software pipeline, as the forward's: batch i+1's records (and the slots of their pair records) are fetched while batch i is walked
+  float4 ra, rb;
+  float rl = 0.f;
+  int64_t ndst = -1;
+  ra = rb = make_float4(0.f, 0.f, 0.f, 0.f);
+  auto fetch = [&](int idx) {
+    ndst = -1;
+    if (idx < end) {
+      const int g = sorted_ids[idx];
+      const SplatRec* r = recs + g;
+      ra = r->a; rb = r->b;
+      rl = chain ? r->d.w : r->b.y;
+      const int4 bx = reinterpret_cast<const int4*>(tbox)[g];
+      ndst = (int64_t)start[g] + (tile_y - bx.y) * (bx.z - bx.x) + (tile_x - bx.x);
+    }
+  };
+  fetch(begin + (int)threadIdx.x);
+  for (int base = begin; base < end; base += SPLAT_BATCH) {
+    // all 256 pixels finished (where the forward leaves the tile): the rest of the list scores nothing, its records are zeros.  The barrier also
+    // says that the previous batch's records and partial results are consumed.
+    const bool fin = __syncthreads_count(done ? 1 : 0) == 256;
+    const int64_t dst = ndst;
+    if (!fin) {
+      sa[threadIdx.x] = ra; sb[threadIdx.x] = rb; sl[threadIdx.x] = rl;
+#pragma unroll
+      for (int w = 0; w < 4; ++w)
+#pragma unroll
+        for (int c = 0; c < SPLAT_PAIR_CONTRIB; ++c) sp[w][c][threadIdx.x] = 0.f;
+    }
+    fetch(base + SPLAT_BATCH + (int)threadIdx.x);
+    if (fin) {  // (block-uniform)
+      if (dst >= 0) {
+        float* o = pair + dst * SPLAT_PAIR_CONTRIB;
+        o[0] = 0.f; o[1] = 0.f; o[2] = 0.f;
+      }
+      continue;
+    }
+    __syncthreads();
+    const int n = min(SPLAT_BATCH, end - base);
+    if (!__all(done ? 1 : 0)) {  // a wave whose 64 pixels are done leaves its zeros
+#pragma unroll 1
+      for (int q = 0; q < SPLAT_BATCH / 64; ++q) {
+        if (q * 64 >= n) break;
+        const int kk = q * 64 + lane;
+        bool keep = false;
+        if (kk < n) {
+          float4 a = sa[kk], b = sb[kk];
+          keep = splat_axis_hit(a.x, b.z, qcx) && splat_axis_hit(a.y, b.w, qcy);
+        }
+        uint64_t live = __ballot(keep);
+        while (live) {
+          const int k = q * 64 + __builtin_ctzll(live);
+          live &= live - 1;
+          const float4 a = sa[k], b = sb[k];
+          const float l2op = sl[k];
+          const float dx = a.x - pxf, dy = a.y - pyf;
+          const float power = splat_power(a.z, a.w, b.x, dx, dy);
+          // nobody in the wave can reach alpha >= 1/255 = 2^-7.994 on this chain (or the form is negative): the record stays zero
+          if (!__any((power >= 0.f && l2op - power >= -8.0f) ? 1 : 0)) continue;
+          float w = 0.f;
+          if (power >= 0.f) {
+            const float alpha = splat_alpha(splat_alpha_raw(l2op, power));
+            if (!done && splat_visible(alpha)) {
+              const float nT = fmaf(-alpha, T, T);
+              if (nT <= 1e-4f) done = true;  // the pixel stops BEFORE this Gaussian: it scores nothing here
+              else {
+                w = pw * (alpha * T);
+                T = nT;
+              }
+            }
+          }
+          const int cnt = __popcll(__ballot(w > 0.f));
+          float s = w, m = w;
+#pragma unroll
+          for (int o = 32; o > 0; o >>= 1) {
+            s += __shfl_xor(s, o, 64);
+            m = fmaxf(m, __shfl_xor(m, o, 64));
+          }
+          if (lane == 0) { sp[wv][0][k] = s; sp[wv][1][k] = m; sp[wv][2][k] = (float)cnt; }
+        }
+      }
+    }
+    __syncthreads();
+    if (dst >= 0) {
+      const int t = threadIdx.x;
+      float* o = pair + dst * SPLAT_PAIR_CONTRIB;
+      o[0] = ((sp[0][0][t] + sp[1][0][t]) + sp[2][0][t]) + sp[3][0][t];
+      o[1] = fmaxf(fmaxf(sp[0][1][t], sp[1][1][t]), fmaxf(sp[2][1][t], sp[3][1][t]));
+      o[2] = ((sp[0][2][t] + sp[1][2][t]) + sp[2][2][t]) + sp[3][2][t];
+    }
+  }
+}
+
+// thread = Gaussian: its run of pair records in list order (a fixed fp32 sum), then the four accumulators in place
+__global__ void __launch_bounds__(256) k_splat_contrib_fold(const float* __restrict__ pair, const int32_t* __restrict__ start,
+                                                            const int32_t* __restrict__ thits, int64_t N, float* __restrict__ max_acc,
+                                                            double* __restrict__ sum_acc, int64_t* __restrict__ hits_acc, int32_t* __restrict__ views_acc) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int cnt = thits[i];
+  if (cnt <= 0) return;  // not on screen: nothing to add
+  float s = 0.f, m = 0.f;
+  int32_t hits = 0;
+  const float* p = pair + (int64_t)start[i] * SPLAT_PAIR_CONTRIB;
+  for (int j = 0; j < cnt; ++j, p += SPLAT_PAIR_CONTRIB) {
+    s += p[0];
+    m = fmaxf(m, p[1]);
+    hits += (int32_t)p[2];
+  }
+  max_acc[i] = fmaxf(max_acc[i], m);
+  sum_acc[i] += (double)s;
+  hits_acc[i] += (int64_t)hits;
+  views_acc[i] += m > 0.f ? 1 : 0;
+}
+
+extern "C" int64_t tn_contrib_splat_workspace_bytes(int64_t num_gaussians, int64_t max_intersections) {
+  if (num_gaussians < 0 || num_gaussians >= (1ll << 31) || max_intersections < 0) return -1;
+  size_t total = 0;
+  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, SPLAT_PAIR_CONTRIB, &total);
+  return (int64_t)total;
+}
+
+// `antialiased` is the frame's flag as tn_splat_project took it: the records already hold the chain's compensated opacity, so it selects nothing
+// here and is only validated (the signature is tn_splat_raster's).
+extern "C" int tn_contrib_splat_raster(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                       int32_t antialiased, int32_t chain, const float* pixel_weight, void* scratch, int64_t scratch_bytes,
+                                       float* max_acc, double* sum_acc, int64_t* hits_acc, int32_t* views_acc, tn_stream_t stream) {
+  const char* who = "tn_contrib_splat_raster";
+  int rc = check_cam(camera, who);
+  if (rc) return rc;
+  TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31) && max_intersections >= 0 && max_intersections < (1ll << 31), "%s: bad sizes", who);
+  TN_REQUIRE((antialiased == 0 || antialiased == 1) && (chain == 0 || chain == 1), "%s: antialiased = %d, chain = %d (each 0 or 1)", who, antialiased, chain);
+  if (num_gaussians == 0) return TN_OK;
+  TN_REQUIRE(workspace && scratch && max_acc && sum_acc && hits_acc && views_acc, "%s: null pointer", who);
+  const int64_t need = tn_contrib_splat_workspace_bytes(num_gaussians, max_intersections);
+  TN_REQUIRE(scratch_bytes >= need, "%s: scratch of %lld bytes, %lld needed (tn_contrib_splat_workspace_bytes)", who, (long long)scratch_bytes, (long long)need);
+  SplatCamK k = make_camk(camera);
+  const int num_tiles = k.tbx * k.tby;
+  SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, num_tiles, nullptr);
+  SplatBwdWs cw = splat_bwd_layout(scratch, num_gaussians, max_intersections, SPLAT_PAIR_CONTRIB, nullptr);
+  hipStream_t st = tn_s(stream);
+  hipLaunchKernelGGL(k_splat_run_start, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, st, ws.order, ws.cum, ws.thits, num_gaussians, cw.start);
+  TN_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(k_splat_raster_contrib, dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, chain, pixel_weight,
+                     cw.start, ws.tbox, cw.pair);
+  TN_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(k_splat_contrib_fold, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, st, cw.pair, cw.start, ws.thits, num_gaussians, max_acc,
+                     sum_acc, hits_acc, views_acc);
+  TN_CHECK_LAUNCH(who);
+  return TN_OK;
+}
+
 struct PoseBwdArgs {  // what the pose entry points add to the projection backward (null: the entry points without _pose)
   const float* rec;
   const float* pose_row;

@@ -74,6 +74,8 @@ tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 
 splat_calls.py: the C entry points, their names and argument order, the workspaces, `knn_distances`, `mcmc_relocate`, `mcmc_noise`.
 splat_camera.py: `PinholeCamera`, `camera_struct`, the resolution schedule's camera, `undistorted_camera`, `OrientedBox`, the pose optimiser.
+splat_prune.py: `score_gaussians`, `prune_mask`, `prune_gaussians` -- every Gaussian's ray contribution (tn_contrib_splat_raster) and pruning by it;
+                `prune_at_steps` / `set_prune_cameras` run it from the refinement callback (off by default).
 splat_image.py: `image_loss`, `resize_image`, `undistort_image`, `thermal_regularizers`, `depth_losses`, `bilateral_slice`, `bilateral_grid_tv`, `ssim`.
 """
 from __future__ import annotations
@@ -188,6 +190,13 @@ class ThermalSplatfactoModelConfig:
     filter_3d_variance: float = 0.2
     filter_3d_near: float = 0.2
     filter_3d_every: int = 100
+    # pruning by ray contribution (splat_prune.py; RadSplat prunes at steps 16000 and 24000 below 0.01): at each of prune_at_steps the refinement
+    # callback, after its own work, scores every Gaussian over the cameras given to `set_prune_cameras` and removes those whose largest blending
+    # weight alpha T on any training ray of either spectrum is below prune_min_contribution.  The steps lie after stop_split_at (a prune right
+    # after an opacity reset would score clamped opacities, and resets end there) and are refinement steps (multiples of refine_every: the
+    # callback runs on no other).  Not with strategy "mcmc", whose budget is the user's stated N.  Empty: nothing new is called
+    prune_at_steps: Tuple[int, ...] = ()
+    prune_min_contribution: float = 0.01
     # per-frame colour correction (current splatfacto's use_bilateral_grid / grid_shape; gsplat's bilateral grids): every training frame has a grid
     # of affine colour transforms, grid_shape = (GW, GH, L) -- indexed by pixel position and brightness -- applied to its training render only and
     # regularised by tv_loss = bilateral_grid_tv_mult * total variation (10: splatfacto's constant).  RGB frames have 3 x 4 matrices (bil_grids),
@@ -197,6 +206,20 @@ class ThermalSplatfactoModelConfig:
     bilateral_grid_tv_mult: float = 10.0
 
     def __post_init__(self):
+        steps = tuple(self.prune_at_steps) if isinstance(self.prune_at_steps, (tuple, list)) else None
+        if steps is None or not all(isinstance(s, int) and not isinstance(s, bool) for s in steps) or any(b <= a for a, b in zip(steps, steps[1:])):
+            raise ValueError(f"prune_at_steps = {self.prune_at_steps!r}: increasing integer steps")
+        self.prune_at_steps = steps
+        if not self.prune_min_contribution >= 0:
+            raise ValueError(f"prune_min_contribution = {self.prune_min_contribution}: a contribution threshold cannot be negative")
+        if steps and self.strategy == "mcmc":
+            raise ValueError('prune_at_steps does not go with strategy "mcmc": its budget max_gs_num is the stated number of Gaussians')
+        if steps and steps[0] <= self.stop_split_at:
+            raise ValueError(f"prune_at_steps = {steps}: every step must lie after stop_split_at = {self.stop_split_at} (a prune right after an opacity "
+                             "reset would score clamped opacities, and the resets end there)")
+        if self.refine_every > 0 and any(s % self.refine_every for s in steps):
+            raise ValueError(f"prune_at_steps = {steps}: the refinement callback runs every refine_every = {self.refine_every} steps, a prune on another "
+                             "step would never happen")
         shape = tuple(self.grid_shape) if isinstance(self.grid_shape, (tuple, list)) else ()
         if len(shape) != 3 or not all(isinstance(v, int) and not isinstance(v, bool) and 2 <= v <= splat_calls.BILAGRID_MAX_SIDE for v in shape):
             raise ValueError(f"grid_shape = {self.grid_shape!r}: (GW, GH, L), three integers in 2..{splat_calls.BILAGRID_MAX_SIDE}")
@@ -498,6 +521,9 @@ class ThermalSplatfactoModel(nn.Module):
         self.filter_refreshes = 0
         if self.config.use_3d_filter:
             self.register_buffer("filter_3D", torch.zeros(self.gauss_params["means"].shape[0], device=dev), persistent=False)
+        # pruning by ray contribution (splat_prune.py): the cameras it scores over, and (Gaussians before, removed) of the last prune
+        self._prune_cameras: List[PinholeCamera] = []
+        self.last_prune_counts: Optional[Tuple[int, int]] = None
         self.step = 0
         self._ws: Optional[Tensor] = None
         self._cap = 0
@@ -611,6 +637,11 @@ class ThermalSplatfactoModel(nn.Module):
         cameras = list(cameras) if cameras is not None else []
         self._filter_table = filter_camera_table(cameras, self.means.device).contiguous() if cameras else None
         self._filter_stale = True
+
+    def set_prune_cameras(self, cameras) -> None:
+        """The cameras the pruning steps (config.prune_at_steps) score the Gaussians over: the full-resolution training cameras of both spectra
+        (ThermalFullImageDatamanager.train_cameras), as `set_filter_cameras` takes them; None or an empty list takes them away."""
+        self._prune_cameras = list(cameras) if cameras is not None else []
 
     def _current_filter(self, training: bool = False) -> Optional[Tensor]:
         """filter_3D [N] as every render of this moment must read it, or None when there is nothing to apply (the switch is off, or no cameras
@@ -1023,8 +1054,27 @@ class ThermalSplatfactoModel(nn.Module):
         the statistics.  `optimizers`: an `Optimizers` (or a dict group -> torch.optim optimiser, or None); every optimiser's parameter is
         replaced by the model's new one, surviving Gaussians keep their Adam moments, new ones start at zero, step counts are kept.
         Strategy "mcmc": when warmup_length < step < stop_split_at and step % refine_every == 0, relocate the dead Gaussians and grow towards
-        max_gs_num (`_mcmc_refine`); nothing else."""
+        max_gs_num (`_mcmc_refine`); nothing else.  After that, at a step of config.prune_at_steps, the Gaussians are scored by their ray
+        contribution over the cameras of `set_prune_cameras` and those below config.prune_min_contribution are removed through the same
+        optimisers (splat_prune.py); `last_prune_counts` = (Gaussians before, removed)."""
         assert step == self.step
+        self._refinement_step(optimizers)
+        if self.step in self.config.prune_at_steps:
+            self._prune_step(optimizers)
+
+    def _prune_step(self, optimizers) -> None:
+        """One pruning step: score_gaussians over the prune cameras, RadSplat's threshold, prune_gaussians."""
+        from . import splat_prune
+
+        if not self._prune_cameras:
+            raise RuntimeError(f"step {self.step} is in prune_at_steps but the model has no cameras to score over: call set_prune_cameras(train cameras) first")
+        before = self.num_points
+        scores = splat_prune.score_gaussians(self, self._prune_cameras)
+        keep = splat_prune.prune_mask(scores, min_contribution=self.config.prune_min_contribution)
+        self.last_prune_counts = (before, splat_prune.prune_gaussians(self, keep, optimizers))
+
+    def _refinement_step(self, optimizers) -> None:
+        """The refinement proper of `refinement_after`."""
         cfg = self.config
         if self.step <= cfg.warmup_length:
             return

@@ -1,4 +1,4 @@
-"""The call layer of the splat path: the one module that names the tn_splat_* / tn_knn / tn_image_* / tn_thermal_reg / tn_depth_loss / tn_bilagrid_* / tn_transform_splat / tn_filter3d_splat_* entry points of
+"""The call layer of the splat path: the one module that names the tn_splat_* / tn_knn / tn_image_* / tn_thermal_reg / tn_depth_loss / tn_bilagrid_* / tn_transform_splat / tn_filter3d_splat_* / tn_contrib_splat_* entry points of
 libthermal_nerf_hip.so and knows their argument order (include/thermal_nerf_hip.h).  The three gsplat calls (project_gaussians,
 spherical_harmonics, rasterize_gaussians x2) run as tn_splat_project / tn_splat_bin / tn_splat_raster of libthermal_nerf_hip.so; separate thermal
 opacity runs the _sep family (tn_splat_project_sep ... tn_splat_refine_apply_sep: the same kernels instantiated with the second chain), and _crop,
@@ -147,6 +147,20 @@ def raster_train(cam, N, ws, cap, bg4, aa, rgbt, depth, alpha, final_t, last, al
 def raster_removal(cam, N, ws, cap, bg4, thr, rem) -> None:
     """tn_splat_raster_removal_sep: the removal renders [H,W,4], one more walk over the frame's tile lists (separate mode only)."""
     _call("tn_splat_raster_removal_sep", C.byref(cam), N, _raw(ws), cap, bg4, float(thr), *_f32(removal=rem))
+
+
+def raster_contrib(cam, N, ws, cap, aa, chain, pixel_weight, max_acc, sum_acc, hits_acc, views_acc) -> None:
+    """tn_contrib_splat_raster over the projected and binned frame in `ws`: every Gaussian's ray contribution w = pixel_weight * alpha * T on
+    `chain` (0: the RGB chain, 1: the thermal chain of a separate-mode frame) accumulated in place into max_acc [N] fp32, sum_acc [N] fp64,
+    hits_acc [N] int64 and views_acc [N] int32.  pixel_weight: [H,W] fp32, non-negative, or None for 1.  The pair records' scratch is this call's."""
+    if pixel_weight is not None and tuple(pixel_weight.shape) != (int(cam.height), int(cam.width)):
+        raise ValueError(f"raster_contrib: pixel_weight must be [{int(cam.height)},{int(cam.width)}], got {tuple(pixel_weight.shape)}")
+    for name, t in (("max_acc", max_acc), ("sum_acc", sum_acc), ("hits_acc", hits_acc), ("views_acc", views_acc)):
+        if tuple(t.shape) != (N,):
+            raise ValueError(f"raster_contrib: {name} must be [{N}], got {tuple(t.shape)}")
+    scratch = workspace("tn_contrib_splat_workspace_bytes", N, cap, device=max_acc.device)
+    _call("tn_contrib_splat_raster", C.byref(cam), N, _raw(ws), cap, int(aa), int(chain), _ptr(pixel_weight, F32, "pixel_weight"), _raw(scratch), scratch.numel(),
+          _ptr(max_acc, F32, "max_acc"), _ptr(sum_acc, torch.float64, "sum_acc"), _ptr(hits_acc, torch.int64, "hits_acc"), _ptr(views_acc, I32, "views_acc"))
 
 
 def raster_backward(cam, N, ws, cap, total, bg4, final_t, last, conics, v_rgbt, v_alpha, v_xys, v_conics, v_colors, v_lnop, final_t_th=None, last_th=None,

@@ -6,7 +6,11 @@ splat file (--load), and write `splat.ply` in the Inria layout every splat viewe
                                             [--min-opacity 0.005] [--obb-center X Y Z --obb-rotation ROLL PITCH YAW --obb-scale SX SY SZ]
                                             [--load PLY] [--thermal-opacity-mode shared|separate] [--sh-degree 3] [--gaussians 20000]
                                             [--save-world-frame] [--load-world-frame]
+                                            [--prune-min-contribution X | --prune-keep-ratio R]
 
+--prune-min-contribution X (RadSplat's rule; 0.01 is its value) or --prune-keep-ratio R scores every Gaussian of the in-memory model by its ray
+contribution over the dataset's training cameras of both spectra (splat_prune.score_gaussians: tn_contrib_splat_raster) and removes the others
+before the export; opacity (--min-opacity) says little about what a Gaussian adds to any frame.  Needs a dataset, as the frame options do.
 --spectrum both (the default) writes the colour scene under the Inria property names followed by f_dc_thermal, f_rest_thermal_* and, in separate
 mode, opacity_thermal: viewers ignore the extras, splat_io.load_gaussian_ply reads them back (bit for bit for --sh-degree > 0).  --spectrum thermal
 writes the thermal parameters under the Inria names, so any viewer shows the thermal scene in grey.  Gaussians with sigmoid(opacity) below
@@ -50,7 +54,17 @@ def parse_args(argv=None):
     ap.add_argument("--save-world-frame", action="store_true", help="write the file in the dataset's frame (default: the model's)")
     ap.add_argument("--load-world-frame", action="store_true", help="the --load file is in the dataset's frame")
     ap.add_argument("--seed", type=int, default=0)
+    prune = ap.add_mutually_exclusive_group()
+    prune.add_argument("--prune-min-contribution", type=float, default=None, metavar="X",
+                       help="before the export, drop the Gaussians whose largest blending weight on any training ray is below X (RadSplat: 0.01)")
+    prune.add_argument("--prune-keep-ratio", type=float, default=None, metavar="R", help="or keep the ceil(R N) Gaussians that contribute most")
     args = ap.parse_args(argv)
+    if (args.prune_min_contribution is not None or args.prune_keep_ratio is not None) and args.data is None and args.iterations == 0:
+        ap.error("--prune-min-contribution and --prune-keep-ratio score over a dataset's training cameras: --data, or a run that trains on the generated scene")
+    if args.prune_min_contribution is not None and not args.prune_min_contribution >= 0:
+        ap.error("--prune-min-contribution takes a number >= 0")
+    if args.prune_keep_ratio is not None and not 0.0 <= args.prune_keep_ratio <= 1.0:
+        ap.error("--prune-keep-ratio takes a ratio in [0, 1]")
     if args.load_world_frame and args.load is None:
         ap.error("--load-world-frame goes with --load")
     if (args.save_world_frame or args.load_world_frame) and args.data is None and args.iterations == 0:
@@ -120,13 +134,26 @@ def main(argv=None):
             for cb in cbs:
                 cb.run_callback_at_location(step, TrainingCallbackLocation.AFTER_TRAIN_ITERATION)
     sync(); train_s = time.perf_counter() - t0
+    pruned = None
+    if args.prune_min_contribution is not None or args.prune_keep_ratio is not None:  # the in-memory model, before the pack kernel sees it
+        from nerfstudio_thermal_amd import splat_prune
+
+        t = time.perf_counter()
+        cams = (dm if dm is not None else ThermalFullImageDatamanagerConfig(dataparser=ThermalNerfDataParserConfig(data=data), seed=args.seed).setup(device=dev)).train_cameras
+        model.eval()
+        before = model.num_points
+        keep = splat_prune.prune_mask(splat_prune.score_gaussians(model, cams), min_contribution=args.prune_min_contribution, keep_ratio=args.prune_keep_ratio)
+        removed = splat_prune.prune_gaussians(model, keep)
+        sync()
+        pruned = {"min_contribution": args.prune_min_contribution, "keep_ratio": args.prune_keep_ratio, "cameras": len(cams), "gaussians_before": before,
+                  "removed": removed, "seconds": time.perf_counter() - t}
     box = OrientedBox.from_params(args.obb_center, args.obb_rotation, args.obb_scale) if args.obb_center is not None else None
     t1 = time.perf_counter()
     out = splat_io.export_gaussian_ply(model, os.path.join(args.output_dir, "splat.ply"), spectrum=args.spectrum, min_opacity=args.min_opacity, crop=box,
                                        transform=world if args.save_world_frame else None)
     export_s = time.perf_counter() - t1
     print(json.dumps({"dataset": None if dm is None else (args.data if args.data is not None else "generated cube scene"), "loaded": loaded,
-                      "iterations": args.iterations, "train_seconds": train_s, "gaussians": model.num_points, "exported": out["exported"],
+                      "iterations": args.iterations, "train_seconds": train_s, "pruned": pruned, "gaussians": model.num_points, "exported": out["exported"],
                       "dropped": out["dropped"], "spectrum": args.spectrum, "min_opacity": args.min_opacity, "sh_degree": args.sh_degree,
                       "thermal_opacity_mode": args.thermal_opacity_mode, "properties": len(out["properties"]),
                       "obb": None if box is None else {"center": args.obb_center, "rotation": args.obb_rotation, "scale": args.obb_scale},

@@ -33,7 +33,11 @@ after the least-squares affine colour map of its render onto its ground truth (a
 the trained Gaussians as a Gaussian-splat PLY (splat_io.export_gaussian_ply: spectrum "both", Gaussians below opacity 0.005 in both spectra and
 those with a parameter that is not finite dropped); the line reports how many went out.  --export-world-frame writes that file in the dataset's own
 frame (splat_transform.dataset_frame), where the point-cloud and mesh exports put theirs; the generated scene's dataparser transform is the identity,
-so there it is the model's frame too and the line says so."""
+so there it is the model's frame too and the line says so.  --prune-at STEP ... prunes by ray contribution at those steps (splat_prune.py: every
+Gaussian scored over the training cameras of both spectra by its largest blending weight alpha T, tn_contrib_splat_raster; those below
+--prune-min-contribution, RadSplat's 0.01 by default, are removed); the steps lie after --stop-split-at and are multiples of --refine-every, and the
+line lists each prune's count.  --prune-observe scores the val split again after pruning the trained model at 0.01 and at keep ratios 0.5 and 0.25,
+without fine-tuning, and puts the Gaussians back."""
 import argparse
 import functools
 import json
@@ -130,6 +134,36 @@ def write_cropped_frames(model, val, box, out_dir: str) -> int:
     return n
 
 
+def observe_pruning(model, train_cameras, val):
+    """What pruning by ray contribution does to the trained model without fine-tuning: the Gaussians are scored once over the training cameras,
+    then for RadSplat's threshold 0.01 and for keep ratios 0.5 and 0.25 the model is pruned, the val split scored (PSNR / SSIM per spectrum, means
+    over its frames) and the Gaussians put back.  Returns {"before": ..., rule: ...}, each with its number of Gaussians."""
+    from nerfstudio_thermal_amd import splat_prune
+
+    def scored():
+        sums = {}
+        with torch.no_grad():
+            for cam, batch in val:
+                metrics, _ = model.get_image_metrics_and_images(model.get_outputs(cam), batch)
+                for k, v in metrics.items():
+                    sums.setdefault(k, []).append(v)
+        return {"gaussians": model.num_points, **{k: sum(v) / len(v) for k, v in sums.items()}}
+
+    was_training = model.training
+    model.eval()
+    saved = {k: model.gauss_params[k].detach().clone() for k in model.param_names}
+    scores = splat_prune.score_gaussians(model, train_cameras)
+    seen = scores.views_rgb + scores.views_thermal
+    out = {"before": scored(), "seen_by_no_training_frame": int((seen == 0).sum()),
+           "importance_quantiles_10_50_90": [float(q) for q in torch.quantile(scores.importance(), torch.tensor([0.1, 0.5, 0.9], device=seen.device))]}
+    for name, rule in (("min_contribution_0.01", {"min_contribution": 0.01}), ("keep_ratio_0.5", {"keep_ratio": 0.5}), ("keep_ratio_0.25", {"keep_ratio": 0.25})):
+        splat_prune.prune_gaussians(model, splat_prune.prune_mask(scores, **rule))
+        out[name] = scored()
+        model.load_gaussians(saved)
+    model.train(was_training)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", default=None)
@@ -183,6 +217,15 @@ def main():
     ap.add_argument("--export-ply", default=None, metavar="PATH",
                     help="write the trained Gaussians as a Gaussian-splat PLY (splat_io.export_gaussian_ply, spectrum both, opacity below 0.005 dropped)")
     ap.add_argument("--export-world-frame", action="store_true", help="write the --export-ply file in the dataset's frame (default: the model's)")
+    ap.add_argument("--prune-at", type=int, nargs="+", default=[], metavar="STEP",
+                    help="prune by ray contribution at these steps (RadSplat: 16000 24000): after --stop-split-at, multiples of --refine-every")
+    ap.add_argument("--prune-min-contribution", type=float, default=0.01,
+                    help="a Gaussian goes when its largest blending weight alpha T on any training ray of either spectrum is below this")
+    ap.add_argument("--stop-split-at", type=int, default=15000, help="the step densification and opacity resets end at")
+    ap.add_argument("--refine-every", type=int, default=100, help="steps between refinements")
+    ap.add_argument("--prune-observe", action="store_true",
+                    help="after training: the val metrics of the model pruned at 0.01 and at keep ratios 0.5 and 0.25, without fine-tuning "
+                         "(the trained model itself is left as it is)")
     args = ap.parse_args()
     if args.export_world_frame and args.export_ply is None:
         ap.error("--export-world-frame goes with --export-ply")
@@ -232,11 +275,16 @@ def main():
                                        camera_optimizer=CameraOptimizerConfig(mode=args.camera_optimizer),
                                        camera_optimizer_thermal=CameraOptimizerConfig(mode=args.camera_optimizer_thermal), use_absgrad=args.use_absgrad,
                                        densify_grad_thresh=args.densify_grad_thresh, strategy=args.strategy, max_gs_num=args.max_gs_num,
-                                       noise_lr=args.noise_lr, use_bilateral_grid=args.use_bilateral_grid, use_3d_filter=args.use_3d_filter)
+                                       noise_lr=args.noise_lr, use_bilateral_grid=args.use_bilateral_grid, use_3d_filter=args.use_3d_filter,
+                                       stop_split_at=args.stop_split_at, refine_every=args.refine_every, prune_at_steps=tuple(args.prune_at),
+                                       prune_min_contribution=args.prune_min_contribution)
     model = ThermalSplatfactoModel(cfg, device=dev, seed=args.seed, num_train_data=dm.num_train_data, seed_points=seed_points,
                                    train_is_thermal=dm.train_is_thermal)
     if args.use_3d_filter:
         model.set_filter_cameras(dm.train_cameras)
+    if args.prune_at:
+        model.set_prune_cameras(dm.train_cameras)
+    prunes = []  # (step, Gaussians before, removed) of every pruning step
     initial = model.num_points
     opts = Optimizers(model.get_param_groups(), {**SPLAT_OPTIMIZERS, **SPLAT_CAMERA_OPTIMIZERS, **SPLAT_BILAGRID_OPTIMIZERS}, optimizer_cls=HipAdam)
     cbs = model.get_training_callbacks(opts)
@@ -259,6 +307,8 @@ def main():
         opts.scheduler_step_all()
         for cb in cbs:
             cb.run_callback_at_location(step, TrainingCallbackLocation.AFTER_TRAIN_ITERATION)
+        if step in args.prune_at:
+            prunes.append({"step": step, "gaussians": model.last_prune_counts[0], "removed": model.last_prune_counts[1]})
         if (step + 1) % 500 == 0 or step + 1 == args.steps:
             torch.cuda.synchronize()
             curve.append({"step": step + 1, "seconds": time.perf_counter() - t0, "main_loss": float(loss["main_loss"].detach()), "gaussians": model.num_points})
@@ -279,6 +329,10 @@ def main():
             for k, v in metrics.items():
                 sums.setdefault(k, []).append(v)
     extra = {}
+    if args.prune_at:
+        extra["prunes"] = prunes
+    if args.prune_observe:
+        extra["prune_observation"] = observe_pruning(model, dm.train_cameras, val)
     if crop_box is not None:  # the same frames cropped to the box, written out; the whole-scene metrics above are untouched
         frames = write_cropped_frames(model, val, crop_box, args.crop_out)
         extra["crop"] = {"pos": args.crop_pos, "rpy": args.crop_rpy, "scale": args.crop_scale, "frames_written": frames, "out": args.crop_out,
