@@ -677,12 +677,25 @@ TN_API int64_t tn_splat_workspace_bytes(int64_t num_gaussians, int64_t max_inter
  * (K = num_rest_coeffs).  sh_degree 0..3 = degree evaluated this step (min(step // interval, sh_degree)); -1 = sigmoid(features_dc)
  * (config.sh_degree == 0).  antialiased != 0: opacity x compensation (rasterize_mode "antialiased").  Outputs as gsplat returns them:
  * xys [N,2], depths [N], radii [N] int32, conics [N,3], compensation [N], num_tiles_hit [N] int32, plus tile_box [N,4] int32
- * (x0, y0, x1, y1 in tiles).  Colours and opacities go into the workspace for tn_splat_raster. */
-TN_API int tn_splat_project(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
-                     const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
-                     int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys, float* depths,
-                     int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
-                     int64_t max_intersections, tn_stream_t stream);
+ * (x0, y0, x1, y1 in tiles).  Colours and opacities go into the workspace for tn_splat_raster.
+ *
+ * Optional inputs of the splat entry points are GROUPS of nullable pointers: a group is given whole or not at all, and a partly given group is
+ * TN_EINVAL before any launch.  Which groups a call gives picks the instantiation of the same kernel.  Here, each on its own:
+ *   pose_camera        the record tn_splat_pose_camera wrote (DEVICE): view, projection rows and position come from it (camera still gives the
+ *                      intrinsics, the clip threshold and the image size).
+ *   opacities_thermal  [N] logits: separate thermal opacity (see "N4 separate thermal opacity" below); max_intersections must then be >= 0.
+ *   crop               a TnSplatCrop (HOST, read before the launch; see "N4 crop box" below): the box test on the mean comes first; a Gaussian
+ *                      outside leaves exactly as one behind the clip plane does (radius 0, no tiles, zeros in every output), one inside goes
+ *                      through the same arithmetic as without the box, and a block whose Gaussians are all outside does not read its higher-order
+ *                      SH coefficients.  tn_splat_bin and the rasters run unchanged on what this leaves: the frame of the Gaussians inside, bit for
+ *                      bit. */
+typedef struct TnSplatCrop TnSplatCrop;
+TN_API int tn_splat_project(const TnSplatCamera* camera, const float* pose_camera, const float* means, const float* log_scales, const float* quats,
+                            const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
+                            const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs,
+                            int32_t sh_degree, int32_t antialiased, float* xys, float* depths, int32_t* radii, float* conics, float* compensation,
+                            int32_t* num_tiles_hit, int32_t* tile_box, void* workspace, int64_t max_intersections, const TnSplatCrop* crop,
+                            tn_stream_t stream);
 /* tile binning of rasterize_gaussians: depth sort of the Gaussians, scan, (tile, Gaussian) pairs in depth order, stable radix sort by
  * tile, tile ranges.  The pairs come from the TIGHT tile boxes tn_splat_project left in the workspace (gsplat's 3-sigma box cut down to
  * the tiles where alpha >= 1/255 is reachable: exact, fewer pairs than sum(num_tiles_hit)).  Reads the pair count back to the host
@@ -695,38 +708,74 @@ TN_API int tn_splat_bin(const TnSplatCamera* camera, const float* depths, int64_
 TN_API int tn_splat_raster(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections, const float* background4,
                     int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, tn_stream_t stream);
 
-/* ---- N4 backward: the exact derivative of the render above with respect to the Gaussians (rgb, thermal, accumulation; depth is not
- * differentiated).  Deterministic: no float atomics, the same inputs give bit-identical gradients.  Call order of one training frame:
- * tn_splat_project -> tn_splat_bin -> tn_splat_raster_train, then tn_splat_raster_backward -> tn_splat_project_backward on the SAME
- * workspace (nothing may run a frame through it in between).
+/* tn_splat_raster with every optional output.  Groups:
+ *   {out_alpha_thermal}                              [H,W], the thermal chain's accumulation, on a frame projected with opacities_thermal
+ *                                                    (out_rgbt's thermal channel then comes from that chain, out_alpha is the RGB chain's);
+ *   {out_transmittance, out_last}                    the training render: per pixel the final T [H,W] and, int32 [H,W], the number of entries of
+ *                                                    the pixel's tile list up to and including the last Gaussian that contributed (0 = none).
+ *                                                    out_rgbt then holds the colour BEFORE the clamp to 1 (the caller clamps, and owns the clamp's
+ *                                                    gradient);
+ *   {out_transmittance_thermal, out_last_thermal}    the same of the thermal chain; given exactly when both groups above are.
+ * out_depth and out_alpha are as tn_splat_raster writes them.  Refuses null pointers and negative sizes. */
+TN_API int tn_splat_raster_chains(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                  const float* background4, int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha,
+                                  float* out_alpha_thermal, float* out_transmittance, int32_t* out_last, float* out_transmittance_thermal,
+                                  int32_t* out_last_thermal, tn_stream_t stream);
+
+/* ---- N4 backward: the exact derivative of the render above with respect to the Gaussians (rgb, thermal, accumulation; depth with the depth
+ * group).  Deterministic: no float atomics, the same inputs give bit-identical gradients.  Call order of one training frame:
+ * tn_splat_project -> tn_splat_bin -> tn_splat_raster_chains, then tn_splat_raster_backward -> tn_splat_project_backward on the SAME
+ * workspace (nothing may run a frame through it in between), with the same groups throughout.
  *
- * tn_splat_raster_train: tn_splat_raster plus, per pixel, out_transmittance [H,W] (final T) and out_last [H,W] int32 (number of entries of the
- * pixel's tile list up to and including the last Gaussian that contributed; 0 = none).  out_rgbt [H,W,4] holds the colour BEFORE the clamp to
- * 1 (the caller clamps, and owns the clamp's gradient); out_depth and out_alpha are as tn_splat_raster writes them. */
-TN_API int tn_splat_raster_train(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections, const float* background4,
-                          int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, float* out_transmittance, int32_t* out_last,
-                          tn_stream_t stream);
-/* scratch of tn_splat_raster_backward: one record of partial gradients per (Gaussian, tile) pair and a per-Gaussian map; -1 on bad sizes */
-TN_API int64_t tn_splat_backward_workspace_bytes(int64_t num_gaussians, int64_t max_intersections);
-/* raster backward.  num_intersections = tn_splat_bin's count; transmittance / last from tn_splat_raster_train; conics [N,3] from
- * tn_splat_project; v_rgbt [H,W,4] = dL / d(colour before the clamp), v_alpha [H,W] = dL / d accumulation.  Outputs per Gaussian: v_xys [N,2],
- * v_conics [N,3], v_colors [N,4] (RGB + thermal after the SH clamp / sigmoid), v_log_opacity [N] = dL / d ln(opacity used by the rasteriser,
- * x compensation in antialiased mode).  Gaussians the forward culled get zeros. */
+ * scratch of tn_splat_raster_backward: one record of partial gradients per (Gaussian, tile) pair -- one more sum with the thermal chain (sep), two
+ * more with v_xys_abs (absgrad), one more with the depth group (depth); each flag 0 or 1 -- and a per-Gaussian map; -1 on bad sizes */
+TN_API int64_t tn_splat_backward_workspace_bytes(int64_t num_gaussians, int64_t max_intersections, int32_t sep, int32_t absgrad, int32_t depth);
+/* raster backward.  num_intersections = tn_splat_bin's count; antialiased = the frame's flag; transmittance / last from tn_splat_raster_chains;
+ * conics [N,3] from tn_splat_project; v_rgbt [H,W,4] = dL / d(colour before the clamp), v_alpha [H,W] = dL / d accumulation.  Outputs per Gaussian:
+ * v_xys [N,2], v_conics [N,3], v_colors [N,4] (RGB + thermal after the SH clamp / sigmoid), v_log_opacity [N] = dL / d ln(opacity used by the
+ * rasteriser, x compensation in antialiased mode).  Gaussians the forward culled get zeros.  Groups:
+ *   {transmittance_thermal, last_thermal, v_alpha_thermal, v_log_opacity_thermal}   both chains: v_rgbt's RGB channels and v_alpha feed the RGB
+ *       chain, its thermal channel and v_alpha_thermal [H,W] the thermal chain; v_xys and v_conics are the sums over both; v_log_opacity_thermal [N]
+ *       = dL / d ln(the thermal opacity as the rasteriser used it).
+ *   {v_xys_abs}   absgrad (AbsGS; gsplat's `absgrad`, splatfacto's `use_absgrad`): [N,2] = sum over the pixels p a Gaussian blends of (|J_p.x|,
+ *       |J_p.y|), where J_p = d sigma_p * (cx dx + cy dy, cy dx + cz dy) is the pixel's term of v_xys (with both chains d sigma_p is the sum of both
+ *       chains' terms, taken before the absolute value).  A blend on the 0.999 clamp contributes nothing, a Gaussian without a pair gets (0, 0).
+ *       Nothing is chained through it, so the projection backward is unchanged.
+ *   {depth, v_depth, v_depths}   the depth gradient (see "N4 depth gradient" below): depth [H,W] = the normalised image the forward wrote, v_depth
+ *       [H,W] = dL / d depth, v_depths [N] = dL / d depths (out).  Refused with antialiased != 0.
+ * Every output a group does not add is bit-equal with and without it.  Refuses a bad Gaussian count, num_intersections outside
+ * [0, max_intersections], null pointers (N > 0) and a bwd_workspace_bytes below tn_splat_backward_workspace_bytes of the groups given. */
 TN_API int tn_splat_raster_backward(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                             int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last, const float* conics,
-                             const float* v_rgbt, const float* v_alpha, void* bwd_workspace, int64_t bwd_workspace_bytes, float* v_xys, float* v_conics,
-                             float* v_colors, float* v_log_opacity, tn_stream_t stream);
+                                    int64_t num_intersections, const float* background4, int32_t antialiased, const float* transmittance,
+                                    const int32_t* last, const float* transmittance_thermal, const int32_t* last_thermal, const float* conics,
+                                    const float* v_rgbt, const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace,
+                                    int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors,
+                                    float* v_log_opacity, float* v_log_opacity_thermal, const float* depth, const float* v_depth, float* v_depths,
+                                    tn_stream_t stream);
 /* projection + SH backward: the parameters and settings of the tn_splat_project call, its radii, and tn_splat_raster_backward's outputs ->
  * gradients in the parameters' layouts: v_means [N,3], v_log_scales [N,3], v_quats [N,4] (through the normalisation), v_opacities [N]
  * (logits), v_features_dc [N,3], v_features_rest [N,K,3], v_thermal_dc [N,1], v_thermal_rest [N,K,1] (zero beyond sh_degree).  The view
- * directions of the SH colours carry no gradient (splatfacto.py:770 detaches the means there). */
-TN_API int tn_splat_project_backward(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
-                              const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
-                              int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, const int32_t* radii,
-                              const float* v_xys, const float* v_conics, const float* v_colors, const float* v_log_opacity, float* v_means,
-                              float* v_log_scales, float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest,
-                              float* v_thermal_dc, float* v_thermal_rest, tn_stream_t stream);
-
+ * directions of the SH colours carry no gradient (splatfacto.py:770 detaches the means there).  Groups:
+ *   {opacities_thermal, v_log_opacity_thermal, v_opacities_thermal}   v_opacities_thermal [N] (logits) from v_log_opacity_thermal; in antialiased
+ *       mode the covariance receives the compensation's gradient from both opacities.
+ *   {pose_camera, pose_row, workspace, grad_pose_row}   for a frame projected with pose_camera (the same record, and the row it was made from): the
+ *       pose gradient.  Every Gaussian with radii > 0 contributes to dL/d view' through its view-space point (frustum clamp included), the
+ *       covariance's T = J W and the projection rows xys reads; the 12 sums are reduced per wave, per block (double) and over the blocks in block
+ *       order -- no float atomics, bit-reproducible -- and chained through D to the row.  The result is ADDED to grad_pose_row [6] (the caller's row
+ *       of a zeroed or accumulating grad_pose [C,6]); dview_out [12] (optional inside the group) receives dL/d view'.  workspace:
+ *       tn_splat_pose_workspace_bytes; workspace_bytes is ignored without the group.
+ *   {v_depths}   [N] = dL / d depths, what the raster backward's depth group left: depths[i] is the view-space z of the mean, so every Gaussian with
+ *       radii > 0 adds v_depths[i] * view[2, :3] to v_means, and with a pose v_depths[i] * (mean, 1) to row 2 of dL/d view' before the
+ *       double-precision sums.  Refused with antialiased != 0. */
+TN_API int tn_splat_project_backward(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
+                                     const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
+                                     const float* features_rest, const float* thermal_dc, const float* thermal_rest, const float* opacities_thermal,
+                                     int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, const int32_t* radii,
+                                     const float* v_xys, const float* v_conics, const float* v_colors, const float* v_log_opacity,
+                                     const float* v_log_opacity_thermal, const float* v_depths, float* v_means, float* v_log_scales, float* v_quats,
+                                     float* v_opacities, float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest,
+                                     float* v_opacities_thermal, void* workspace, int64_t workspace_bytes, float* grad_pose_row, float* dview_out,
+                                     tn_stream_t stream);
 
 /* ---- N4 refinement: splatfacto's densification, culling and statistics (SplatfactoModel.after_train / refinement_after,
  * nerfstudio/models/splatfacto.py:346-498).  No float atomics: the results are bit-reproducible.
@@ -759,19 +808,22 @@ TN_API int tn_splat_grad_stats(const float* xys_grad, const int32_t* radii, int6
 TN_API int64_t tn_splat_refine_workspace_bytes(int64_t num_gaussians, int32_t n_split_samples);
 /* Classifies every Gaussian (split, duplicate, cull of each row it ends up in) and places every surviving output row.  counts_out (HOST,
  * 4 entries): split Gaussians, surviving originals, surviving split children (all samples), surviving duplicates.  One device-to-host copy
- * of the counts (a stream synchronisation).  When the step neither densifies nor culls nothing is launched and the counts are (0, N, 0, 0). */
-TN_API int tn_splat_refine_plan(const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities, const float* grad_norm_sum,
-                                const float* vis_counts, const float* max_2d_size, int64_t num_gaussians, void* workspace, int64_t workspace_bytes,
-                                int64_t* counts_out, tn_stream_t stream);
+ * of the counts (a stream synchronisation).  When the step neither densifies nor culls nothing is launched and the counts are (0, N, 0, 0).
+ * With opacities_thermal [N] (optional) the both-below cull rule: a Gaussian is culled for low opacity only when sigmoid(opacities) AND
+ * sigmoid(opacities_thermal) are below cull_alpha_thresh (one that is visible in either spectrum stays). */
+TN_API int tn_splat_refine_plan(const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities,
+                                const float* opacities_thermal, const float* grad_norm_sum, const float* vis_counts, const float* max_2d_size,
+                                int64_t num_gaussians, void* workspace, int64_t workspace_bytes, int64_t* counts_out, tn_stream_t stream);
 /* Writes the refined Gaussians: rows = surviving originals, split children (sample-major, in index order), duplicates (in index order).
- * params / exp_avg / exp_avg_sq / new_*: HOST arrays of 8 device pointers in the order means [N,3], log-scales [N,3], quats [N,4],
- * opacities [N,1], features_dc [N,3], features_rest [N,K,3], features_dc_thermal [N,1], features_rest_thermal [N,K,1] (K = num_rest_coeffs;
- * the two rest entries are ignored when K = 0).  A parameter's four moment pointers are all null (no Adam state) or all set.  Outputs hold
+ * params / exp_avg / exp_avg_sq / new_*: HOST arrays of num_tensors device pointers (8 or 9; anything else is refused) in the order means [N,3],
+ * log-scales [N,3], quats [N,4], opacities [N,1], features_dc [N,3], features_rest [N,K,3], features_dc_thermal [N,1], features_rest_thermal
+ * [N,K,1] (K = num_rest_coeffs; the two rest entries are ignored when K = 0) and, ninth, opacities_thermal [N,1], which -- with its moments -- is
+ * carried exactly as the opacities are.  A parameter's four moment pointers are all null (no Adam state) or all set.  Outputs hold
  * counts[1] + counts[2] + counts[3] rows.  Surviving originals keep their moments, new rows get zero moments.  Split children take
  * mean + R(q / |q|) (exp(log-scale) * noise row) and log(exp(log-scale) / 1.6); noise [counts[0] * n_split_samples, 3] is torch.randn's sample-major
  * layout.  counts and workspace must be those of the tn_splat_refine_plan call on the same inputs. */
 TN_API int tn_splat_refine_apply(const TnSplatRefine* config, int64_t num_gaussians, int32_t num_rest_coeffs, const void* workspace,
-                                 int64_t workspace_bytes, const int64_t* counts, const float* noise, const float* const* params,
+                                 int64_t workspace_bytes, const int64_t* counts, const float* noise, int32_t num_tensors, const float* const* params,
                                  const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params, float* const* new_exp_avg,
                                  float* const* new_exp_avg_sq, tn_stream_t stream);
 
@@ -779,96 +831,23 @@ TN_API int tn_splat_refine_apply(const TnSplatRefine* config, int64_t num_gaussi
  * density_mode "separate"): every Gaussian has a second opacity logit, opacities_thermal [N].  RGB, accumulation and depth composite with
  * sigmoid(opacities) as above; the thermal channel composites with sigmoid(opacities_thermal) through a transmittance chain of its own over the
  * same depth-sorted tile lists, with its own stop (a pixel's chain stops before the Gaussian that would take T to 1e-4 or below), and the thermal
- * background is weighted by that chain's final transmittance.  In antialiased mode both opacities take the same compensation.  Each _sep entry
- * point is the entry point it is named after plus the thermal-opacity arguments; both share one implementation, and the entry points above keep
- * their signatures and results.  A frame is one family throughout: tn_splat_project_sep -> tn_splat_bin -> tn_splat_raster_sep, or
- * -> tn_splat_raster_train_sep -> tn_splat_raster_backward_sep -> tn_splat_project_backward_sep, on the same workspace (a workspace projected
- * by tn_splat_project holds no thermal opacities).  Same determinism: no float atomics, bit-identical gradients for the same inputs.  Every
- * refusal below is TN_EINVAL before any launch.
- *
- * tn_splat_project_sep: tn_splat_project with opacities_thermal [N] (logits; null is refused for N > 0).  The tight tile box and the half
- * extents of {alpha >= 1/255} come from the LARGER of the two opacities, so neither chain loses a contributor; radii, num_tiles_hit and
- * tile_box are gsplat's, as before.  Refuses what tn_splat_project refuses, and a negative max_intersections. */
-TN_API int tn_splat_project_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
-                                const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
-                                const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased,
-                                float* xys, float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box,
-                                void* workspace, int64_t max_intersections, tn_stream_t stream);
-/* tn_splat_raster on a workspace of tn_splat_project_sep: out_rgbt [H,W,4] (thermal from its own chain), out_depth, out_alpha [H,W] (the RGB
- * chain's accumulation) and out_alpha_thermal [H,W] (the thermal chain's).  Refuses null pointers and negative sizes. */
-TN_API int tn_splat_raster_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections, const float* background4,
-                               int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, float* out_alpha_thermal, tn_stream_t stream);
+ * background is weighted by that chain's final transmittance.  In antialiased mode both opacities take the same compensation.  It is the thermal
+ * group of every entry point above, and a frame gives it throughout or not at all (a workspace projected without opacities_thermal holds no
+ * thermal opacities).  In the projection the tight tile box and the half extents of {alpha >= 1/255} come from the LARGER of the two opacities, so
+ * neither chain loses a contributor; radii, num_tiles_hit and tile_box are gsplat's, as before.  Same determinism: no float atomics, bit-identical
+ * gradients for the same inputs. */
 /* ThermalNeRF's removal renders (models/thermal_nerfacto.py:460-487, with opacities for densities): the frame composited only from the
- * Gaussians on which the two spectra agree.  One more launch over the tile lists of a frame, after tn_splat_project_sep and tn_splat_bin on the
- * same workspace (before or after tn_splat_raster_sep; it reads the workspace only).  With o = sigmoid(opacities), ot = sigmoid(opacities_thermal)
- * and thr = min_opacity_diff: out_removal [H,W,4] holds in .xyz the RGB colour composited as tn_splat_raster_sep's RGB chain does, except that a
+ * Gaussians on which the two spectra agree.  One more launch over the tile lists of a frame, after tn_splat_project (with opacities_thermal) and tn_splat_bin on the
+ * same workspace (before or after tn_splat_raster_chains; it reads the workspace only).  With o = sigmoid(opacities), ot = sigmoid(opacities_thermal)
+ * and thr = min_opacity_diff: out_removal [H,W,4] holds in .xyz the RGB colour composited as tn_splat_raster_chains' RGB chain does, except that a
  * Gaussian with |o - ot| < thr * o false has alpha 0, over background4.xyz with this chain's own final transmittance; in .w the thermal colour
  * likewise with ot's chain, |ot - o| < thr * ot, and background4.w; both clamped to <= 1.  The comparisons are strict and use the plain
  * opacities (in antialiased mode the chains blend with the compensated ones, as the workspace holds them): thr = 0 keeps nothing -- the
- * background --, thr = inf everything -- tn_splat_raster_sep's out_rgbt bit for bit.  No float atomics: two calls give identical bits.
+ * background --, thr = inf everything -- tn_splat_raster_chains' out_rgbt bit for bit.  No float atomics: two calls give identical bits.
  * num_gaussians == 0 is TN_OK: tn_splat_bin left every tile list empty, and every pixel receives background4 (clamped to <= 1).  Refuses a null
  * pointer, a bad camera, a num_gaussians outside [0, 2^31), a negative max_intersections and a min_opacity_diff that is negative or NaN. */
 TN_API int tn_splat_raster_removal_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
                                        const float* background4, float min_opacity_diff, float* out_removal, tn_stream_t stream);
-/* tn_splat_raster_train likewise: out_transmittance / out_last are the RGB chain's, out_transmittance_thermal [H,W] / out_last_thermal [H,W] int32
- * the thermal chain's final T and last contributor.  Refuses null pointers and negative sizes. */
-TN_API int tn_splat_raster_train_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                                     const float* background4, int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha,
-                                     float* out_alpha_thermal, float* out_transmittance, int32_t* out_last, float* out_transmittance_thermal,
-                                     int32_t* out_last_thermal, tn_stream_t stream);
-/* scratch of tn_splat_raster_backward_sep (one more partial sum per pair than tn_splat_backward_workspace_bytes); -1 on bad sizes */
-TN_API int64_t tn_splat_backward_workspace_bytes_sep(int64_t num_gaussians, int64_t max_intersections);
-/* raster backward of both chains: the arguments of tn_splat_raster_backward plus the thermal chain's transmittance_thermal / last_thermal (from
- * tn_splat_raster_train_sep) and v_alpha_thermal [H,W] = dL / d thermal accumulation.  v_rgbt's RGB channels and v_alpha feed the RGB chain, its
- * thermal channel and v_alpha_thermal the thermal chain; v_xys and v_conics are the sums over both chains; v_log_opacity [N] and
- * v_log_opacity_thermal [N] = dL / d ln(each opacity as the rasteriser used it).  Refuses a bad Gaussian count, num_intersections outside
- * [0, max_intersections], null pointers (N > 0) and a bwd_workspace_bytes below tn_splat_backward_workspace_bytes_sep. */
-TN_API int tn_splat_raster_backward_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                                        int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
-                                        const float* transmittance_thermal, const int32_t* last_thermal, const float* conics, const float* v_rgbt,
-                                        const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace, int64_t bwd_workspace_bytes, float* v_xys,
-                                        float* v_conics, float* v_colors, float* v_log_opacity, float* v_log_opacity_thermal, tn_stream_t stream);
-/* ---- N4 absgrad (AbsGS; gsplat's `absgrad`, splatfacto's `use_absgrad`): the raster backwards above plus the densification statistic
- * v_xys_abs [N,2] = sum over the pixels p a Gaussian blends of (|J_p.x|, |J_p.y|), where J_p = d sigma_p * (cx dx + cy dy, cy dx + cz dy) is the
- * pixel's term of v_xys (v_xys = sum_p J_p; in separate mode d sigma_p is the sum of both chains' terms, taken before the absolute value).  A
- * blend on the 0.999 clamp contributes nothing, a Gaussian without a pair gets (0, 0).  No atomics: bit-reproducible.  Nothing is chained
- * through v_xys_abs, so the projection backward is unchanged; every other output is bit-equal to the entry point without _abs.  The pair record
- * grows by two sums: the scratch is sized by the _abs functions below (-1 on bad sizes).  Refusals as tn_splat_raster_backward / _sep, plus a
- * null v_xys_abs and a bwd_workspace_bytes below the _abs size. */
-TN_API int64_t tn_splat_backward_workspace_bytes_abs(int64_t num_gaussians, int64_t max_intersections);
-TN_API int64_t tn_splat_backward_workspace_bytes_abs_sep(int64_t num_gaussians, int64_t max_intersections);
-TN_API int tn_splat_raster_backward_abs(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                                        int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
-                                        const float* conics, const float* v_rgbt, const float* v_alpha, void* bwd_workspace,
-                                        int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors,
-                                        float* v_log_opacity, tn_stream_t stream);
-TN_API int tn_splat_raster_backward_abs_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                                            int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
-                                            const float* transmittance_thermal, const int32_t* last_thermal, const float* conics,
-                                            const float* v_rgbt, const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace,
-                                            int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors,
-                                            float* v_log_opacity, float* v_log_opacity_thermal, tn_stream_t stream);
-/* tn_splat_project_backward plus v_opacities_thermal [N] (logits) from v_log_opacity_thermal; in antialiased mode the covariance receives the
- * compensation's gradient from both opacities.  Refuses what tn_splat_project_backward refuses, and null thermal-opacity pointers. */
-TN_API int tn_splat_project_backward_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
-                                         const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
-                                         const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs,
-                                         int32_t sh_degree, int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics,
-                                         const float* v_colors, const float* v_log_opacity, const float* v_log_opacity_thermal, float* v_means,
-                                         float* v_log_scales, float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest,
-                                         float* v_thermal_dc, float* v_thermal_rest, float* v_opacities_thermal, tn_stream_t stream);
-/* tn_splat_refine_plan with the both-below cull rule: a Gaussian is culled for low opacity only when sigmoid(opacities) AND
- * sigmoid(opacities_thermal) are below cull_alpha_thresh (one that is visible in either spectrum stays).  Same workspace, counts and refusals,
- * plus a null opacities_thermal on a step that refines. */
-TN_API int tn_splat_refine_plan_sep(const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities,
-                                    const float* opacities_thermal, const float* grad_norm_sum, const float* vis_counts, const float* max_2d_size,
-                                    int64_t num_gaussians, void* workspace, int64_t workspace_bytes, int64_t* counts_out, tn_stream_t stream);
-/* tn_splat_refine_apply over HOST arrays of 9 device pointers: the eight of tn_splat_refine_apply, then opacities_thermal [N,1], which -- with its
- * moments -- is carried exactly as the opacities are.  counts and workspace must be those of the tn_splat_refine_plan_sep call on the same inputs. */
-TN_API int tn_splat_refine_apply_sep(const TnSplatRefine* config, int64_t num_gaussians, int32_t num_rest_coeffs, const void* workspace,
-                                     int64_t workspace_bytes, const int64_t* counts, const float* noise, const float* const* params,
-                                     const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params, float* const* new_exp_avg,
-                                     float* const* new_exp_avg_sq, tn_stream_t stream);
 
 /* ---- N4 crop box: the oriented box of the eval render (SplatfactoModel.crop_box / get_outputs_for_camera, nerfstudio/models/splatfacto.py:
  * 374-376, 690-698, 904-915; OrientedBox.within, nerfstudio/data/scene_box.py:82-114).  The reference gathers the six parameter tensors
@@ -881,22 +860,6 @@ typedef struct TnSplatCrop {
   float world_to_box[12];
   float half_extent[3];
 } TnSplatCrop;
-/* tn_splat_project / tn_splat_project_sep with a crop box (a HOST pointer, read before the launch; null is refused): the crop instantiation
- * of the same kernel.  The box test on the mean comes first; a Gaussian outside leaves exactly as one behind the clip plane does (radius 0, no
- * tiles, zeros in every output), a Gaussian inside goes through the same arithmetic as without the box, and a block whose Gaussians are all outside
- * does not read its higher-order SH coefficients.  No new workspace: tn_splat_bin and every raster entry point run unchanged on what this
- * leaves, so the frame is the frame of the Gaussians inside, bit for bit.  Refuses what the entry point without _crop refuses. */
-TN_API int tn_splat_project_crop(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
-                                 const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
-                                 int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys, float* depths,
-                                 int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
-                                 int64_t max_intersections, const TnSplatCrop* crop, tn_stream_t stream);
-TN_API int tn_splat_project_crop_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
-                                     const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
-                                     const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs,
-                                     int32_t sh_degree, int32_t antialiased, float* xys, float* depths, int32_t* radii, float* conics, float* compensation,
-                                     int32_t* num_tiles_hit, int32_t* tile_box, void* workspace, int64_t max_intersections, const TnSplatCrop* crop,
-                                     tn_stream_t stream);
 /* the same box test on a bare point list: means [n,3] fp32 -> mask [n] uint8 (1 inside, 0 outside).  n == 0 is TN_OK; refuses a null box, null
  * pointers for n > 0 and n outside [0, 2^31). */
 TN_API int tn_splat_crop_mask(const TnSplatCrop* crop, const float* means, int64_t n, uint8_t* mask, tn_stream_t stream);
@@ -906,7 +869,7 @@ TN_API int tn_splat_crop_mask(const TnSplatCrop* crop, const float* means, int64
  * vector -- gives A(p) = [R(w) | t] = exp_map_SO3xR3 (cameras/lie_groups.py:24-58, theta = sqrt(clamp(|w|^2, 1e-4))), applied as
  * c2w' = c2w [A(p); 0 0 0 1] (apply_to_camera, :178-186).  With F = diag(1, -1, -1) and V0 = camera->viewmat that is view' = D V0 with the rigid
  * D = F A(p)^-1 F.  The pose stays on the device: tn_splat_pose_camera writes the corrected camera into a record of
- * TN_SPLAT_POSE_CAMERA_FLOATS floats, the _pose entry points read their camera from it.  Record: [0..11] view' (3x4 rows), [12..27] proj' (4x4
+ * TN_SPLAT_POSE_CAMERA_FLOATS floats, tn_splat_project and tn_splat_project_backward read their camera from it.  Record: [0..11] view' (3x4 rows), [12..27] proj' (4x4
  * rows; row 2 is not read and is 0), [28..30] position' = c2w'[:3, 3] (the SH view directions; a value, no gradient: splatfacto.py:770),
  * [31] proj_x, [32] proj_y, the rest 0.  Everything additive: no other entry point changes.
  *
@@ -916,43 +879,8 @@ TN_API int tn_splat_crop_mask(const TnSplatCrop* crop, const float* means, int64
  * number of the record equals the corresponding number of `camera` (D is exactly the identity and zero terms are skipped, not added). */
 #define TN_SPLAT_POSE_CAMERA_FLOATS 40
 TN_API int tn_splat_pose_camera(const TnSplatCamera* camera, float proj_x, float proj_y, const float* pose_row, float* pose_camera, tn_stream_t stream);
-/* tn_splat_project / tn_splat_project_sep with view, projection rows and position taken from pose_camera (the pose instantiation of the same
- * kernel; camera still gives the intrinsics, the clip threshold and the image size).  crop: a box as tn_splat_project_crop takes it, or null. */
-TN_API int tn_splat_project_pose(const TnSplatCamera* camera, const float* pose_camera, const float* means, const float* log_scales, const float* quats,
-                                 const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
-                                 const float* thermal_rest, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased,
-                                 float* xys, float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box,
-                                 void* workspace, int64_t max_intersections, const TnSplatCrop* crop, tn_stream_t stream);
-TN_API int tn_splat_project_pose_sep(const TnSplatCamera* camera, const float* pose_camera, const float* means, const float* log_scales,
-                                     const float* quats, const float* opacities, const float* features_dc, const float* features_rest,
-                                     const float* thermal_dc, const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians,
-                                     int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys, float* depths, int32_t* radii,
-                                     float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
-                                     int64_t max_intersections, const TnSplatCrop* crop, tn_stream_t stream);
 /* scratch of the pose backward: one partial sum of dL/d view' (12 doubles) per block of 256 Gaussians; -1 on a bad count */
 TN_API int64_t tn_splat_pose_workspace_bytes(int64_t num_gaussians);
-/* tn_splat_project_backward / _sep for a frame projected with tn_splat_project_pose / _sep (the same record, and the row it was made from), plus
- * the pose gradient: every Gaussian with radii > 0 contributes to dL/d view' through its view-space point (frustum clamp included), the
- * covariance's T = J W and the projection rows xys reads; the 12 sums are reduced per wave, per block (double) and over the blocks in block
- * order -- no float atomics, bit-reproducible -- and chained through D to the row.  The result is ADDED to grad_pose_row [6] (the caller's row
- * of a zeroed or accumulating grad_pose [C,6]); dview_out [12] (may be null) receives dL/d view'.  workspace: tn_splat_pose_workspace_bytes. */
-TN_API int tn_splat_project_backward_pose(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
-                                          const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
-                                          const float* features_rest, const float* thermal_dc, const float* thermal_rest, int64_t num_gaussians,
-                                          int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, const int32_t* radii, const float* v_xys,
-                                          const float* v_conics, const float* v_colors, const float* v_log_opacity, float* v_means, float* v_log_scales,
-                                          float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest, float* v_thermal_dc,
-                                          float* v_thermal_rest, void* workspace, int64_t workspace_bytes, float* grad_pose_row, float* dview_out,
-                                          tn_stream_t stream);
-TN_API int tn_splat_project_backward_pose_sep(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
-                                              const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
-                                              const float* features_rest, const float* thermal_dc, const float* thermal_rest,
-                                              const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
-                                              int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics,
-                                              const float* v_colors, const float* v_log_opacity, const float* v_log_opacity_thermal, float* v_means,
-                                              float* v_log_scales, float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest,
-                                              float* v_thermal_dc, float* v_thermal_rest, float* v_opacities_thermal, void* workspace,
-                                              int64_t workspace_bytes, float* grad_pose_row, float* dview_out, tn_stream_t stream);
 
 /* ---- N4 depth gradient: the training render's depth image as a differentiable output (splatfacto's training depth carries gradients,
  * nerfstudio/models/splatfacto.py:805-820).  Classic mode only.  There depth = D / A where A = accumulation > 0, with D = sum alpha_i T_i z_i on
@@ -961,37 +889,7 @@ TN_API int tn_splat_project_backward_pose_sep(const TnSplatCamera* camera, const
  * channel with upstream vD and no background term, and v_alpha becomes v_alpha - vD * depth.  The pair record grows by one sum, d z, reduced as the
  * others are (lane, fixed butterfly, LDS, four waves in order, one write): no float atomics, bit-reproducible.  In antialiased mode the depth is
  * blended by a chain of its own with the uncompensated opacity, whose final transmittance and last contributor the training forward does not keep:
- * both entry points refuse antialiased != 0.
- *
- * scratch of tn_depth_splat_raster_backward: one more partial sum per pair than the entry point without it (sep, absgrad: 0 or 1); -1 on bad sizes */
-TN_API int64_t tn_splat_depth_backward_workspace_bytes(int64_t num_gaussians, int64_t max_intersections, int32_t sep, int32_t absgrad);
-/* The arguments of tn_splat_raster_backward_abs_sep, `antialiased` (must be 0) behind background4, and at the end depth [H,W] (the normalised image
- * tn_splat_raster_train / _sep wrote), v_depth [H,W] and v_depths [N] = dL / d depths (out).  The thermal group (transmittance_thermal, last_thermal,
- * v_alpha_thermal, v_log_opacity_thermal) all null selects shared mode, a null v_xys_abs no absgrad; every other output is what the entry point of
- * that mode computes from v_alpha - vD * depth and the fifth channel.  Refuses what that entry point refuses, null depth pointers (N > 0),
- * antialiased != 0 and a bwd_workspace_bytes below tn_splat_depth_backward_workspace_bytes. */
-TN_API int tn_depth_splat_raster_backward(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                                          int64_t num_intersections, const float* background4, int32_t antialiased, const float* transmittance,
-                                          const int32_t* last, const float* transmittance_thermal, const int32_t* last_thermal, const float* conics,
-                                          const float* v_rgbt, const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace,
-                                          int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors,
-                                          float* v_log_opacity, float* v_log_opacity_thermal, const float* depth, const float* v_depth,
-                                          float* v_depths, tn_stream_t stream);
-/* The arguments of tn_splat_project_backward_pose_sep plus v_depths [N] (behind v_log_opacity_thermal): depths[i] is the view-space z of the mean,
- * so every Gaussian with radii > 0 adds v_depths[i] * view[2, :3] to v_means, and with a pose v_depths[i] * (mean, 1) to row 2 of dL/d view' before
- * the double-precision sums.  A null pose_camera means no pose (pose_row, workspace, grad_pose_row and dview_out are then not read); the thermal
- * opacity pointers (opacities_thermal, v_log_opacity_thermal, v_opacities_thermal) all null select shared mode.  Refuses what the entry point of
- * that mode refuses, a null v_depths (N > 0) and antialiased != 0. */
-TN_API int tn_depth_splat_project_backward(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
-                                           const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
-                                           const float* features_rest, const float* thermal_dc, const float* thermal_rest,
-                                           const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
-                                           int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics,
-                                           const float* v_colors, const float* v_log_opacity, const float* v_log_opacity_thermal,
-                                           const float* v_depths, float* v_means, float* v_log_scales, float* v_quats, float* v_opacities,
-                                           float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest,
-                                           float* v_opacities_thermal, void* workspace, int64_t workspace_bytes, float* grad_pose_row,
-                                           float* dview_out, tn_stream_t stream);
+ * tn_splat_raster_backward and tn_splat_project_backward refuse their depth groups with antialiased != 0. */
 
 /* ---- N4 training loss: splatfacto's (1 - ssim_lambda) * L1 + ssim_lambda * (1 - SSIM) (nerfstudio/models/splatfacto.py:863-903), SSIM as
  * pytorch_msssim computes it: an 11-tap Gaussian window (sigma 1.5) applied separably as a VALID correlation, C1 = 0.01^2, C2 = 0.03^2 (data
@@ -1134,8 +1032,10 @@ TN_API int tn_knn(const float* points, int64_t n, int32_t k, float* out_dist, in
  * faint ones exploring.  tests/splat_mcmc_functional.py restates both operations in float64.
  *
  * tn_splat_mcmc_relocate: num_draws draws (src_idx[j] -> dst_idx[j]; both DEVICE int64 [num_draws]) on tensors of num_rows rows, in place.
- * params / exp_avg / exp_avg_sq: HOST arrays of 8 device pointers in tn_splat_refine_apply's order (K = num_rest_coeffs; the two rest entries are
- * ignored when K = 0); a parameter's two moment pointers are both null (no Adam state) or both set.  With ratio r = min(1 + the number of times a
+ * params / exp_avg / exp_avg_sq: HOST arrays of num_tensors device pointers (8 or 9; anything else is refused) in tn_splat_refine_apply's order
+ * (K = num_rest_coeffs; the two rest entries are ignored when K = 0; ninth, opacities_thermal [N,1]: the thermal opacity takes its own o_th' by the
+ * rule below, and the scale follows the larger of the two opacities, a tie going to o); a parameter's two moment pointers are both null (no Adam
+ * state) or both set.  With ratio r = min(1 + the number of times a
  * source row was drawn, 51), o = sigmoid(opacity) and s = exp(log-scale) of the source BEFORE the call:
  *   o' = clamp(1 - (1 - o)^(1/r), min_opacity, 1 - FLT_EPSILON), stored as log(o' / (1 - o'));
  *   p' = 1 - (1 - o)^(1/r) unclamped, denom = sum_{i=1..r} sum_{k=0..i-1} binom(i-1, k) (-1)^k p'^(k+1) / sqrt(k+1), s' = (o / denom) s, stored as
@@ -1151,29 +1051,22 @@ TN_API int tn_knn(const float* points, int64_t n, int32_t k, float* out_dist, in
  * scratch of tn_splat_mcmc_relocate (a counter and five values per row, a flag per draw); -1 on bad sizes */
 TN_API int64_t tn_splat_mcmc_workspace_bytes(int64_t num_rows, int64_t num_draws);
 TN_API int tn_splat_mcmc_relocate(int64_t num_rows, int32_t num_rest_coeffs, const int64_t* src_idx, const int64_t* dst_idx, int64_t num_draws,
-                                  float min_opacity, float* const* params, float* const* exp_avg, float* const* exp_avg_sq, void* workspace,
-                                  int64_t workspace_bytes, tn_stream_t stream);
-/* the same over HOST arrays of 9 device pointers (tn_splat_refine_apply_sep's order: opacities_thermal [N,1] last): the thermal opacity takes its own
- * o_th' by the same rule, and the scale follows the larger of the two opacities (a tie goes to o) */
-TN_API int tn_splat_mcmc_relocate_sep(int64_t num_rows, int32_t num_rest_coeffs, const int64_t* src_idx, const int64_t* dst_idx, int64_t num_draws,
-                                      float min_opacity, float* const* params, float* const* exp_avg, float* const* exp_avg_sq, void* workspace,
-                                      int64_t workspace_bytes, tn_stream_t stream);
+                                  float min_opacity, int32_t num_tensors, float* const* params, float* const* exp_avg, float* const* exp_avg_sq,
+                                  void* workspace, int64_t workspace_bytes, tn_stream_t stream);
 /* The position noise of one training step, in place: means [N,3] += Sigma (randn * g * scaler) with Sigma = R diag(exp(log_scales)^2) R^T,
- * R the rotation of quats / |quats| (w x y z, the projection's convention), g = 1 / (1 + exp(-100 ((1 - o) - 0.995))), o = sigmoid(opacities),
+ * R the rotation of quats / |quats| (w x y z, the projection's convention), g = 1 / (1 + exp(-100 ((1 - o) - 0.995))), o = sigmoid(opacities) -- or, with
+ * opacities_thermal (optional), the larger of the two sigmoids: a Gaussian visible in either spectrum is left in place --,
  * randn [N,3] standard normal draws, scaler = noise_lr times the means' learning rate.  One launch, one thread per Gaussian, fp32, no [N,3,3]
  * temporary; memory-bound at 68 bytes per Gaussian.  quats must be 16-byte aligned.  num_gaussians == 0 launches nothing.  Refused with TN_EINVAL
  * before any launch: a count that is negative or above INT32_MAX, null pointers, a scaler that is negative or not finite. */
-TN_API int tn_splat_mcmc_noise(float* means, const float* log_scales, const float* quats, const float* opacities, const float* randn,
-                               int64_t num_gaussians, float scaler, tn_stream_t stream);
-/* the same with o = max(sigmoid(opacities), sigmoid(opacities_thermal)): a Gaussian visible in either spectrum is left in place */
-TN_API int tn_splat_mcmc_noise_sep(float* means, const float* log_scales, const float* quats, const float* opacities, const float* opacities_thermal,
-                                   const float* randn, int64_t num_gaussians, float scaler, tn_stream_t stream);
+TN_API int tn_splat_mcmc_noise(float* means, const float* log_scales, const float* quats, const float* opacities, const float* opacities_thermal,
+                               const float* randn, int64_t num_gaussians, float scaler, tn_stream_t stream);
 
 /* ---- Gaussian-splat PLY export (ns-export gaussian-splat: nerfstudio/scripts/exporter.py:480-546, ExportGaussianSplat): the model's parameter
  * tensors become the rows of an Inria-layout splat file on the device, filtered and compacted in their original order.  Runs on the caller's
  * stream without a host synchronisation and without atomics: the same inputs give the same bytes.  tests/splat_export_functional.py restates it.
  *
- * tn_export_splat_pack: the parameters as tn_splat_project_sep takes them -- means, log_scales [N,3], quats [N,4] (written as stored, not
+ * tn_export_splat_pack: the parameters as tn_splat_project takes them -- means, log_scales [N,3], quats [N,4] (written as stored, not
  * normalised), opacities [N] (logits), features_dc [N,3], features_rest [N,R,3], thermal_dc [N], thermal_rest [N,R] with R = num_rest_coeffs (the
  * two rest tensors may be null when R is 0), opacities_thermal [N] or null (shared opacity).  spectrum: 0 rgb, 1 thermal, 2 both.  The row of W
  * floats, with o = 9 + 3 R:
@@ -1192,9 +1085,6 @@ TN_API int tn_splat_mcmc_noise_sep(float* means, const float* log_scales, const 
  * written.  num_gaussians == 0 is TN_OK and sets count to 0.  Refused with TN_EINVAL before any launch: num_gaussians outside [0, 2^31),
  * num_rest_coeffs negative or above 1024, an unknown spectrum or colour_mode, colour_mode 1 with num_rest_coeffs > 0, a NaN threshold, null
  * pointers, a workspace that is short or not 8-byte aligned.
- *
- * (The two entry points are named tn_export_splat_*, outside the tn_splat_* family: the Python package issues every launch of that family from
- * splat_calls.py, and this call from splat_io.pack_call, as cloud.py and mesh.py issue theirs.)
  *
  * scratch of tn_export_splat_pack (a keep flag per Gaussian, a count and an offset per block of 256); -1 for num_gaussians outside [0, 2^31) */
 TN_API int64_t tn_export_splat_workspace_bytes(int64_t num_gaussians);
@@ -1227,8 +1117,7 @@ TN_API int tn_export_splat_pack(const float* means, const float* log_scales, con
  * Each *_out may be its own input (in place): a block reads all of its Gaussians before it stores any.  Otherwise an output must not overlap any
  * other buffer of the call: pointers are equal or disjoint.
  * num_gaussians == 0 is TN_OK without a launch.  Refused with TN_EINVAL before any launch: a null transform, num_gaussians outside [0, 2^31),
- * num_rest_coeffs not one of 0, 3, 8, 15, null pointers the call needs.
- * (Named tn_transform_splat, outside the tn_splat_* family, as tn_export_splat_pack is: that family is the frame, training and refinement stages.) */
+ * num_rest_coeffs not one of 0, 3, 8, 15, null pointers the call needs. */
 typedef struct TnSplatTransform {
   double A[9];
   double t[3];
@@ -1258,7 +1147,6 @@ TN_API int tn_transform_splat(const TnSplatTransform* transform, const float* me
  * launch folds them and writes the unseen rows.  num_gaussians == 0 is TN_OK without a launch.  Refused with TN_EINVAL before any launch:
  * num_gaussians outside [0, 2^31), num_cameras < 0, near_plane or variance negative or not finite, null pointers, a workspace that is short or not
  * 8-byte aligned.
- * (Named tn_filter3d_splat_*, outside the tn_splat_* family, as tn_transform_splat is: that family is the frame, training and refinement stages.)
  *
  * scratch of tn_filter3d_splat_compute (a double per block of 256 Gaussians); -1 on bad sizes */
 TN_API int64_t tn_filter3d_splat_workspace_bytes(int64_t num_gaussians);
@@ -1285,9 +1173,9 @@ TN_API int tn_filter3d_splat_apply_backward(const float* log_scales, const float
                                             tn_stream_t stream);
 
 /* ---- ray contribution of every Gaussian (splat_prune.py: RadSplat's max over rays of alpha T, LightGaussian's hit-weighted sum), the score trained
- * splats are pruned by.  tn_contrib_splat_raster runs on the frame workspace tn_splat_project* and tn_splat_bin left, exactly as tn_splat_raster
+ * splats are pruned by.  tn_splat_raster_contrib runs on the frame workspace tn_splat_project and tn_splat_bin left, exactly as tn_splat_raster
  * does, and walks ONE transmittance chain of the frame's tile lists: chain 0 is the chain RGB, accumulation and depth are blended with, chain 1
- * the thermal chain of a frame projected by a _sep entry point (only such a frame has one: the workspace does not say how it was projected,
+ * the thermal chain of a frame projected with opacities_thermal (only such a frame has one: the workspace does not say how it was projected,
  * the caller must).  In antialiased mode the alpha is the one the chain's colour is blended with, the compensated one; the workspace's records hold it already,
  * so `antialiased` (0 or 1, the frame's flag) is validated and selects nothing.  For every pixel p and every list entry g the forward would blend on
  * that chain -- the same power >= 0 test, 1/255 gate, 0.999 clamp and nT <= 1e-4 stop, from the rasteriser's own helpers --
@@ -1301,11 +1189,10 @@ TN_API int tn_filter3d_splat_apply_backward(const float* log_scales, const float
  * Three launches, no atomics, no host synchronisation: the same inputs give the same bits.  The raster writes one (sum, max, count) record per
  * (Gaussian, tile) pair into `scratch` -- every pair of every tile, zeros where nothing is blended -- and a fold per Gaussian walks its run.
  * num_gaussians == 0 is TN_OK without a launch.  Refused with TN_EINVAL before any launch: a bad camera, sizes outside [0, 2^31), antialiased or
- * chain other than 0 or 1, null pointers, a scratch shorter than tn_contrib_splat_workspace_bytes(num_gaussians, max_intersections) (-1 on bad
- * sizes).  max_intersections is the capacity the frame workspace was laid out with.
- * (Named tn_contrib_splat_*, outside the tn_splat_* family, as tn_depth_splat_raster_backward is.) */
-TN_API int64_t tn_contrib_splat_workspace_bytes(int64_t num_gaussians, int64_t max_intersections);
-TN_API int tn_contrib_splat_raster(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+ * chain other than 0 or 1, null pointers, a scratch shorter than tn_splat_contrib_workspace_bytes(num_gaussians, max_intersections) (-1 on bad
+ * sizes).  max_intersections is the capacity the frame workspace was laid out with. */
+TN_API int64_t tn_splat_contrib_workspace_bytes(int64_t num_gaussians, int64_t max_intersections);
+TN_API int tn_splat_raster_contrib(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
                                    int32_t antialiased, int32_t chain, const float* pixel_weight, void* scratch, int64_t scratch_bytes,
                                    float* max_acc, double* sum_acc, int64_t* hits_acc, int32_t* views_acc, tn_stream_t stream);
 

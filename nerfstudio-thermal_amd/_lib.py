@@ -11,7 +11,7 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TN_LIB names another build of the same library (A/B timing of kernel variants); there is still no fallback if it cannot be loaded
 LIB_PATH = os.path.abspath(os.environ["TN_LIB"]) if os.environ.get("TN_LIB") else os.path.join(_HERE, "libthermal_nerf_hip.so")
-ABI_VERSION = 313  # include/thermal_nerf_hip.h as this binding was written for (tn_version() of the library must match)
+ABI_VERSION = 314  # include/thermal_nerf_hip.h as this binding was written for (tn_version() of the library must match)
 TN_MAX_LEVELS = 16
 TN_MAX_SAMPLES = 256
 TN_RENDER_SCRATCH_FLOATS = 4096
@@ -113,7 +113,7 @@ class TnSplatRefine(C.Structure):
 
 
 class TnSplatCrop(C.Structure):
-    """include/thermal_nerf_hip.h: the crop box of the eval render, rows of the 3x4 world -> box matrix and S / 2 (tn_splat_project_crop, tn_splat_crop_mask)"""
+    """include/thermal_nerf_hip.h: the crop box of the eval render, rows of the 3x4 world -> box matrix and S / 2 (tn_splat_project, tn_splat_crop_mask)"""
     _fields_ = [("world_to_box", _f * 12), ("half_extent", _f * 3)]
 
 
@@ -212,46 +212,23 @@ SIGNATURES = {
     "tn_render_rays_train_bwd_tmp_floats": (_i64, [_i64, _i32, _i32, _i32, _i32]),
     "tn_render_rays_train_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32] + [_p] * 7 + [_i64, _p, _i64, _p, _i64] + [_p] * 3 + [_i32, _p]),
     "tn_splat_workspace_bytes": (_i64, [_i64, _i64, _i32]),
-    "tn_splat_project": (C.c_int, [_p] * 9 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, _p]),
+    # the splat frame, its backward and refinement: one entry point per stage; optional inputs (pose camera, thermal opacity, crop box, absgrad,
+    # depth gradient) are groups of nullable pointers
+    "tn_splat_project": (C.c_int, [_p] * 11 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, C.POINTER(TnSplatCrop), _p]),
     "tn_splat_bin": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _p]),
     "tn_splat_raster": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _p, _p, _p]),
-    "tn_splat_raster_train": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _p, _p, _p, _p, _p]),
-    "tn_splat_backward_workspace_bytes": (_i64, [_i64, _i64]),
-    "tn_splat_raster_backward": (C.c_int, [_p, _i64, _p, _i64, _i64] + [_p] * 7 + [_i64] + [_p] * 5),
-    "tn_splat_project_backward": (C.c_int, [_p] * 9 + [_i64, _i32, _i32, _i32] + [_p] * 14),
+    "tn_splat_raster_chains": (C.c_int, [_p, _i64, _p, _i64, _p, _i32] + [_p] * 8 + [_p]),
+    "tn_splat_raster_removal_sep": (C.c_int, [_p, _i64, _p, _i64, _p, _f, _p, _p]),
+    "tn_splat_backward_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
+    "tn_splat_raster_backward": (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _i32] + [_p] * 9 + [_i64] + [_p] * 10),
+    "tn_splat_project_backward": (C.c_int, [_p] * 12 + [_i64, _i32, _i32, _i32] + [_p] * 17 + [_i64, _p, _p, _p]),
     "tn_splat_grad_stats": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p]),
     "tn_splat_refine_workspace_bytes": (_i64, [_i64, _i32]),
-    "tn_splat_refine_plan": (C.c_int, [C.POINTER(TnSplatRefine), _i32] + [_p] * 5 + [_i64, _p, _i64, _p, _p]),
-    "tn_splat_refine_apply": (C.c_int, [C.POINTER(TnSplatRefine), _i64, _i32, _p, _i64, _p, _p] + [_p] * 6 + [_p]),
-    # separate thermal opacity: each entry point above plus the thermal-opacity arguments
-    "tn_splat_project_sep": (C.c_int, [_p] * 10 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, _p]),
-    "tn_splat_raster_sep": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _p, _p, _p, _p]),
-    "tn_splat_raster_removal_sep": (C.c_int, [_p, _i64, _p, _i64, _p, _f, _p, _p]),
-    "tn_splat_raster_train_sep": (C.c_int, [_p, _i64, _p, _i64, _p, _i32] + [_p] * 8 + [_p]),
-    "tn_splat_backward_workspace_bytes_sep": (_i64, [_i64, _i64]),
-    "tn_splat_raster_backward_sep": (C.c_int, [_p, _i64, _p, _i64, _i64] + [_p] * 10 + [_i64] + [_p] * 6),
-    "tn_splat_backward_workspace_bytes_abs": (_i64, [_i64, _i64]),
-    "tn_splat_backward_workspace_bytes_abs_sep": (_i64, [_i64, _i64]),
-    "tn_splat_raster_backward_abs": (C.c_int, [_p, _i64, _p, _i64, _i64] + [_p] * 7 + [_i64] + [_p] * 6),
-    "tn_splat_raster_backward_abs_sep": (C.c_int, [_p, _i64, _p, _i64, _i64] + [_p] * 10 + [_i64] + [_p] * 7),
-    "tn_splat_project_backward_sep": (C.c_int, [_p] * 10 + [_i64, _i32, _i32, _i32] + [_p] * 16),
-    "tn_splat_refine_plan_sep": (C.c_int, [C.POINTER(TnSplatRefine), _i32] + [_p] * 6 + [_i64, _p, _i64, _p, _p]),
-    "tn_splat_refine_apply_sep": (C.c_int, [C.POINTER(TnSplatRefine), _i64, _i32, _p, _i64, _p, _p] + [_p] * 6 + [_p]),
-    # crop box of the eval render: the projection entry points plus the box, and the box test on a point list
-    "tn_splat_project_crop": (C.c_int, [_p] * 9 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, C.POINTER(TnSplatCrop), _p]),
-    "tn_splat_project_crop_sep": (C.c_int, [_p] * 10 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, C.POINTER(TnSplatCrop), _p]),
+    "tn_splat_refine_plan": (C.c_int, [C.POINTER(TnSplatRefine), _i32] + [_p] * 6 + [_i64, _p, _i64, _p, _p]),
+    "tn_splat_refine_apply": (C.c_int, [C.POINTER(TnSplatRefine), _i64, _i32, _p, _i64, _p, _p, _i32] + [_p] * 6 + [_p]),
     "tn_splat_crop_mask": (C.c_int, [C.POINTER(TnSplatCrop), _p, _i64, _p, _p]),
-    # pose refinement: the corrected camera as a device record, the projection entry points that read it, the pose gradient
     "tn_splat_pose_camera": (C.c_int, [_p, _f, _f, _p, _p, _p]),
-    "tn_splat_project_pose": (C.c_int, [_p] * 10 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, C.POINTER(TnSplatCrop), _p]),
-    "tn_splat_project_pose_sep": (C.c_int, [_p] * 11 + [_i64, _i32, _i32, _i32] + [_p] * 8 + [_i64, C.POINTER(TnSplatCrop), _p]),
     "tn_splat_pose_workspace_bytes": (_i64, [_i64]),
-    "tn_splat_project_backward_pose": (C.c_int, [_p] * 11 + [_i64, _i32, _i32, _i32] + [_p] * 14 + [_i64, _p, _p, _p]),
-    "tn_splat_project_backward_pose_sep": (C.c_int, [_p] * 12 + [_i64, _i32, _i32, _i32] + [_p] * 16 + [_i64, _p, _p, _p]),
-    # depth gradient (classic mode): the raster and projection backwards with v_depth / v_depths; thermal, absgrad and pose groups are nullable
-    "tn_splat_depth_backward_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
-    "tn_depth_splat_raster_backward": (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _i32] + [_p] * 9 + [_i64] + [_p] * 10),
-    "tn_depth_splat_project_backward": (C.c_int, [_p] * 12 + [_i64, _i32, _i32, _i32] + [_p] * 17 + [_i64, _p, _p, _p]),
     "tn_image_loss_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "tn_image_loss": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _f, _f, _p, _i64, _p, _p, _p]),
     "tn_image_resize": (C.c_int, [_p, _i32, _i64, _i32, _i32, _i32, _p, _i32, _i32, _p]),
@@ -270,26 +247,23 @@ SIGNATURES = {
     "tn_knn": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _i64, _p]),
     # MCMC strategy: relocation / growth in place (8 or 9 tensors with their moments) and the per-step position noise
     "tn_splat_mcmc_workspace_bytes": (_i64, [_i64, _i64]),
-    "tn_splat_mcmc_relocate": (C.c_int, [_i64, _i32, _p, _p, _i64, _f, _p, _p, _p, _p, _i64, _p]),
-    "tn_splat_mcmc_relocate_sep": (C.c_int, [_i64, _i32, _p, _p, _i64, _f, _p, _p, _p, _p, _i64, _p]),
-    "tn_splat_mcmc_noise": (C.c_int, [_p] * 5 + [_i64, _f, _p]),
-    "tn_splat_mcmc_noise_sep": (C.c_int, [_p] * 6 + [_i64, _f, _p]),
-    # Gaussian-splat PLY export: the parameters of tn_splat_project_sep -> the kept Gaussians' file rows, compacted in order
-    # (named tn_export_splat_*, outside the tn_splat_* family: every launch of that family is issued by splat_calls.py, this raw call is splat_io.pack_call's)
+    "tn_splat_mcmc_relocate": (C.c_int, [_i64, _i32, _p, _p, _i64, _f, _i32, _p, _p, _p, _p, _i64, _p]),
+    "tn_splat_mcmc_noise": (C.c_int, [_p] * 6 + [_i64, _f, _p]),
+    # Gaussian-splat PLY export: the parameters of tn_splat_project -> the kept Gaussians' file rows, compacted in order
     "tn_export_splat_workspace_bytes": (_i64, [_i64]),
     "tn_export_splat_pack": (C.c_int, [_p] * 9 + [_i64, _i32, _i32, _i32, _f, C.POINTER(TnSplatCrop), _p, _p, _p, _i64, _p]),
     # a similarity applied to every Gaussian (means, log scales, quaternions and the SH bands 1 to 3 of both spectra), in place or not
     "tn_transform_splat": (C.c_int, [C.POINTER(TnSplatTransform)] + [_p] * 5 + [_i64, _i32] + [_p] * 5 + [_p]),
     # Mip-Splatting's 3D smoothing filter: the filter value per Gaussian from the training cameras, its application to log-scales and opacity
-    # logits (a NULL thermal pointer group is shared mode) and the closed-form backward (named outside the tn_splat_* family, as tn_transform_splat)
+    # logits (a NULL thermal pointer group is shared mode) and the closed-form backward
     "tn_filter3d_splat_workspace_bytes": (_i64, [_i64]),
     "tn_filter3d_splat_compute": (C.c_int, [_p, _i64, _p, _i32, _d, _d, _p, _p, _i64, _p]),
     "tn_filter3d_splat_apply": (C.c_int, [_p] * 4 + [_i64] + [_p] * 3 + [_p]),
     "tn_filter3d_splat_apply_backward": (C.c_int, [_p] * 7 + [_i64] + [_p] * 3 + [_p]),
     # ray contribution of every Gaussian on one chain of a projected and binned frame, accumulated in place: max fp32, sum fp64, hits int64,
-    # views int32 (named outside the tn_splat_* family, as tn_depth_splat_raster_backward is)
-    "tn_contrib_splat_workspace_bytes": (_i64, [_i64, _i64]),
-    "tn_contrib_splat_raster": (C.c_int, [C.POINTER(TnSplatCamera), _i64, _p, _i64, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p, _p]),
+    # views int32
+    "tn_splat_contrib_workspace_bytes": (_i64, [_i64, _i64]),
+    "tn_splat_raster_contrib": (C.c_int, [C.POINTER(TnSplatCamera), _i64, _p, _i64, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p, _p]),
     # point-cloud export of the NeRF: stable append of a rendered batch, statistical outlier removal
     "tn_cloud_append_workspace_bytes": (_i64, [_i64]),
     "tn_cloud_append": (C.c_int, [_p] * 5 + [_i64, _p, _i64, _i64, _f, C.POINTER(TnSplatCrop), _p, _p, _p, _i64, _p, _p, _i64, _p]),

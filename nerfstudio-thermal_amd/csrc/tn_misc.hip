@@ -105,7 +105,7 @@ extern "C" int tn_shutdown(void) {
   return rc;
 }
 
-extern "C" int tn_version(void) { return 313; }  // 313: thermal regularisers of the splat loss (tn_thermal_reg, tn_thermal_reg_workspace_bytes), and -- added without a new number, tests/test_splat_thermal_reg_cpu.py pins this one; load() resolves every declared symbol, so a library without it still fails to load -- splat frame undistortion (TnUndistort, tn_image_undistort); 312: splat resolution schedule (tn_image_resize); 311: splat seeding (tn_knn, tn_knn_workspace_bytes); 310: splat training loss (tn_image_loss, tn_image_loss_workspace_bytes); 309: splat refinement (TnSplatRefine, tn_splat_grad_stats, tn_splat_refine_plan, tn_splat_refine_apply, tn_splat_refine_workspace_bytes); 308: splat backward (tn_splat_raster_train, tn_splat_raster_backward, tn_splat_project_backward, tn_splat_backward_workspace_bytes); 307: tn_comm_* / tn_allreduce_grads; 306 (round 6): TnNextSampling, TnTrainStep::next_sampling / sampling_done; 305 (round 5): TnSampleRays, TnTrainStep::next_sample; 304: tn_render_losses_bwd; 303: tn_train_step (one call per training iteration), TN_FIELD_MAX_IMAGES; 302 (round 4): workspace_bytes behind every workspace pointer (a short buffer is TN_EINVAL, not an out-of-bounds write), tn_field_encode_plan; 301: TN_BWD_COUNTERS_CLEAN, proposal workspaces hand d enc over level-major; 300 (round 3): signatures of tn_hash_scatter_workspace_bytes / tn_field_density_fwd changed in round 2, AMP Adam + train-step entry points added
+extern "C" int tn_version(void) { return 314; }  // 314: one splat entry point per stage, optional inputs as groups of nullable pointers (the _sep / _abs / _crop / _pose and tn_depth_splat_* names are gone; tn_splat_raster_chains, num_tensors of tn_splat_refine_apply / tn_splat_mcmc_relocate); 313: thermal regularisers of the splat loss (tn_thermal_reg, tn_thermal_reg_workspace_bytes), and -- added without a new number, tests/test_splat_thermal_reg_cpu.py pins this one; load() resolves every declared symbol, so a library without it still fails to load -- splat frame undistortion (TnUndistort, tn_image_undistort); 312: splat resolution schedule (tn_image_resize); 311: splat seeding (tn_knn, tn_knn_workspace_bytes); 310: splat training loss (tn_image_loss, tn_image_loss_workspace_bytes); 309: splat refinement (TnSplatRefine, tn_splat_grad_stats, tn_splat_refine_plan, tn_splat_refine_apply, tn_splat_refine_workspace_bytes); 308: splat backward (the training raster, tn_splat_raster_backward, tn_splat_project_backward, tn_splat_backward_workspace_bytes); 307: tn_comm_* / tn_allreduce_grads; 306 (round 6): TnNextSampling, TnTrainStep::next_sampling / sampling_done; 305 (round 5): TnSampleRays, TnTrainStep::next_sample; 304: tn_render_losses_bwd; 303: tn_train_step (one call per training iteration), TN_FIELD_MAX_IMAGES; 302 (round 4): workspace_bytes behind every workspace pointer (a short buffer is TN_EINVAL, not an out-of-bounds write), tn_field_encode_plan; 301: TN_BWD_COUNTERS_CLEAN, proposal workspaces hand d enc over level-major; 300 (round 3): signatures of tn_hash_scatter_workspace_bytes / tn_field_density_fwd changed in round 2, AMP Adam + train-step entry points added
 
 extern "C" int tn_fill_zero(void* ptr, int64_t bytes, tn_stream_t stream) {
   TN_REQUIRE(ptr != nullptr && bytes >= 0, "tn_fill_zero: bad argument");

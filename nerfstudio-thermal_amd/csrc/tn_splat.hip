@@ -21,9 +21,10 @@
 //                      one); every lane then walks the batch front to back.  The LDS reads are wave-uniform broadcasts (conflict-free);
 //                      a wave whose 64 pixels are all finished skips the arithmetic; the colour (RGB+T) and depth images come out of ONE
 //                      pass (the reference runs the rasteriser twice; in "antialiased" mode the depth pass uses the uncompensated
-//                      opacity, so that variant carries a second transmittance).  The TRAIN instantiation (tn_splat_raster_train) also
+//                      opacity, so that variant carries a second transmittance).  The TRAIN instantiation (tn_splat_raster_chains with out_transmittance / out_last) also
 //                      keeps each pixel's final transmittance and last contributor for the backward.
 #include <cstring>
+#include <tuple>
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -480,7 +481,7 @@ __device__ __forceinline__ bool splat_visible(float alpha) { return alpha >= (1.
 // The SEP instantiations' extra kernel arguments ride in a parameter pack (empty without SEP; pack_arg, above k_splat_project), so that the
 // SEP = false kernels keep the argument list -- and with it every kernel-argument offset -- they had before SEP existed: their instruction stream
 // is the parent's, bit for bit.
-// TRAIN: the training variant (tn_splat_raster_train) also leaves what the backward needs per pixel -- the final transmittance and the number
+// TRAIN: the training variant (tn_splat_raster_chains with out_transmittance / out_last) also leaves what the backward needs per pixel -- the final transmittance and the number
 // of list entries up to and including the last Gaussian that contributed -- and writes the colour BEFORE the clamp to 1 (the caller clamps,
 // so the clamp's gradient mask is the caller's).  TRAIN = false is the eval rasteriser, unchanged.
 // SEP: the thermal channel blends with its own opacity (SplatRec::d.w) through a transmittance chain of its own (Tt / done_t, the pattern of the
@@ -746,7 +747,7 @@ __global__ void __launch_bounds__(256) k_splat_raster_removal(const SplatRec* __
 
 // ------------------------------------------------------------------------------------------------ backward
 // The exact derivative of the forward above (rgb, thermal, accumulation; depth only through the DEPTH instantiations below, which the
-// tn_depth_splat_* entry points run).  Three steps, no float atomics, so the gradients are bit-reproducible:
+// depth groups of the two backward entry points select).  Three steps, no float atomics, so the gradients are bit-reproducible:
 //   k_splat_raster_bwd  block = one tile, same lane -> pixel map as the forward.  Every pixel walks its list from the last contributor back
 //                       to the front, recomputing alpha under the forward's rules and the transmittance before each Gaussian as T / (1 - alpha).
 //                       The SPLAT_PAIR_GRADS partial sums of a (tile, Gaussian) pair are reduced over the wave (fixed butterfly), then over the
@@ -791,42 +792,14 @@ static SplatBwdWs splat_bwd_layout(void* base, int64_t N, int64_t capacity, int 
   return w;
 }
 
-extern "C" int64_t tn_splat_backward_workspace_bytes(int64_t num_gaussians, int64_t max_intersections) {
-  if (num_gaussians < 0 || max_intersections < 0) return -1;
-  size_t total = 0;
-  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, SPLAT_PAIR_GRADS, &total);
-  return (int64_t)total;
-}
-
-extern "C" int64_t tn_splat_backward_workspace_bytes_sep(int64_t num_gaussians, int64_t max_intersections) {
-  if (num_gaussians < 0 || max_intersections < 0) return -1;
-  size_t total = 0;
-  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, SPLAT_PAIR_GRADS_SEP, &total);
-  return (int64_t)total;
-}
-
-extern "C" int64_t tn_splat_backward_workspace_bytes_abs(int64_t num_gaussians, int64_t max_intersections) {
-  if (num_gaussians < 0 || max_intersections < 0) return -1;
-  size_t total = 0;
-  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, SPLAT_PAIR_GRADS + SPLAT_PAIR_ABS, &total);
-  return (int64_t)total;
-}
-
-extern "C" int64_t tn_splat_backward_workspace_bytes_abs_sep(int64_t num_gaussians, int64_t max_intersections) {
-  if (num_gaussians < 0 || max_intersections < 0) return -1;
-  size_t total = 0;
-  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, SPLAT_PAIR_GRADS_SEP + SPLAT_PAIR_ABS, &total);
-  return (int64_t)total;
-}
-
 static int splat_pair_grads(bool sep, bool absgrad, bool depth) {
   return (sep ? SPLAT_PAIR_GRADS_SEP : SPLAT_PAIR_GRADS) + (depth ? SPLAT_PAIR_DEPTH : 0) + (absgrad ? SPLAT_PAIR_ABS : 0);
 }
 
-extern "C" int64_t tn_splat_depth_backward_workspace_bytes(int64_t num_gaussians, int64_t max_intersections, int32_t sep, int32_t absgrad) {
+extern "C" int64_t tn_splat_backward_workspace_bytes(int64_t num_gaussians, int64_t max_intersections, int32_t sep, int32_t absgrad, int32_t depth) {
   if (num_gaussians < 0 || max_intersections < 0) return -1;
   size_t total = 0;
-  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, splat_pair_grads(sep != 0, absgrad != 0, true), &total);
+  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, splat_pair_grads(sep != 0, absgrad != 0, depth != 0), &total);
   return (int64_t)total;
 }
 
@@ -1474,18 +1447,43 @@ static SplatCamK make_camk(const TnSplatCamera* cam) {
   return k;
 }
 
-// The _sep entry points (separate thermal opacity) share their implementation with the entry points they extend: `sep` picks the SEP
-// instantiation of the kernels, and the thermal-opacity pointers, null in shared mode, are then required.  `who` names the entry point in messages.
-static int splat_project(const char* who, bool sep, const TnSplatCrop* crop, const float* pose_rec, const TnSplatCamera* camera, const float* means, const float* log_scales,
-                         const float* quats, const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
-                         const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
-                         int32_t antialiased, float* xys, float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit,
-                         int32_t* tile_box, void* workspace, int64_t max_intersections, tn_stream_t stream) {
+// Optional inputs are groups of nullable pointers, and which groups a call gives picks the kernel instantiation.  with_flags turns the runtime
+// flags into std::bool_constant arguments of `f`, in order, so every stage below writes its launch once; opt_args is the trailing kernel
+// arguments a flag adds (a tuple, empty when the flag is off), and group_state tells a group given whole (1) from an absent (0) or a partly
+// given (-1) one.
+template <typename F>
+static void with_flags(F&& f) { f(); }
+template <typename F, typename... B>
+static void with_flags(F&& f, bool flag, B... rest) {
+  if (flag) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+template <bool ON, typename... T>
+static auto opt_args(std::bool_constant<ON>, T... t) {
+  if constexpr (ON) return std::make_tuple(t...);
+  else return std::tuple<>();
+}
+template <typename... P>
+static int group_state(P... p) {
+  const int n = (int(p != nullptr) + ...);
+  return n == 0 ? 0 : n == (int)sizeof...(P) ? 1 : -1;
+}
+
+// opacities_thermal (separate thermal opacity), crop (a HOST box) and pose_camera (tn_splat_pose_camera's device record, from which the kernel
+// then reads its camera) are each optional on their own: SEP x CROP x POSE instantiations of one kernel.
+extern "C" int tn_splat_project(const TnSplatCamera* camera, const float* pose_camera, const float* means, const float* log_scales, const float* quats,
+                                const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
+                                const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs,
+                                int32_t sh_degree, int32_t antialiased, float* xys, float* depths, int32_t* radii, float* conics, float* compensation,
+                                int32_t* num_tiles_hit, int32_t* tile_box, void* workspace, int64_t max_intersections, const TnSplatCrop* crop,
+                                tn_stream_t stream) {
+  const char* who = "tn_splat_project";
+  const bool sep = opacities_thermal != nullptr;
   int rc = check_cam(camera, who);
   if (rc) return rc;
   if (num_gaussians == 0) return TN_OK;
   TN_REQUIRE(means && log_scales && quats && opacities && features_dc && thermal_dc && xys && depths && radii && conics && compensation &&
-                 num_tiles_hit && tile_box && workspace && (!sep || opacities_thermal),
+                 num_tiles_hit && tile_box && workspace,
              "%s: null pointer", who);
   TN_REQUIRE(num_gaussians > 0 && num_gaussians < (1ll << 31), "%s: bad Gaussian count", who);
   TN_REQUIRE(max_intersections >= 0 || !sep, "%s: bad workspace capacity", who);
@@ -1498,84 +1496,20 @@ static int splat_project(const char* who, bool sep, const TnSplatCrop* crop, con
   const int PB = 128;  // Gaussians per block: 30 KB of LDS at degree 3 -> 5 blocks per CU (256 per block = 61 KB = 2 blocks: 136 vs 1xx us)
   const size_t lds = (size_t)PB * num_rest_coeffs * 4 * sizeof(float);
   TN_REQUIRE(lds <= (crop ? 65536 - 256 : 65536), "%s: %d higher-order coefficients do not fit the LDS staging", who, num_rest_coeffs);  // 256 B of static LDS: the words of __syncthreads_or
-  if (pose_rec) {  // the pose instantiations: the camera comes from the device record (with or without the box)
-    const SplatPoseK pk{pose_rec};
-    auto launch = [&](auto kernel, auto... extra) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)tn_cdiv(num_gaussians, PB)), dim3(PB), lds, tn_s(stream), k, means, log_scales, quats, opacities, features_dc,
-                         features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, (float2*)xys, depths, radii, conics,
-                         compensation, num_tiles_hit, tile_box, ws.recs, ws.tbox, ws.thits, opacities_thermal, extra...);
-    };
-    if (crop && sep) launch(k_splat_project<true, SplatCropK, SplatPoseK>, make_cropk(crop), pk);
-    else if (crop) launch(k_splat_project<false, SplatCropK, SplatPoseK>, make_cropk(crop), pk);
-    else if (sep) launch(k_splat_project<true, SplatPoseK>, pk);
-    else launch(k_splat_project<false, SplatPoseK>, pk);
-    TN_CHECK_LAUNCH(who);
-    return TN_OK;
-  }
-  if (crop) {  // the crop instantiation: the same launch plus the box
-    hipLaunchKernelGGL((sep ? k_splat_project<true, SplatCropK> : k_splat_project<false, SplatCropK>), dim3((unsigned)tn_cdiv(num_gaussians, PB)), dim3(PB), lds,
-                       tn_s(stream), k, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree,
-                       num_rest_coeffs, antialiased, (float2*)xys, depths, radii, conics, compensation, num_tiles_hit, tile_box, ws.recs, ws.tbox, ws.thits,
-                       opacities_thermal, make_cropk(crop));
-    TN_CHECK_LAUNCH(who);
-    return TN_OK;
-  }
-  hipLaunchKernelGGL(sep ? k_splat_project<true> : k_splat_project<false>, dim3((unsigned)tn_cdiv(num_gaussians, PB)), dim3(PB), lds, tn_s(stream), k, means,
-                     log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased,
-                     (float2*)xys, depths, radii, conics, compensation, num_tiles_hit, tile_box, ws.recs, ws.tbox, ws.thits, opacities_thermal);
+  const SplatCropK ck = crop ? make_cropk(crop) : SplatCropK{};
+  with_flags([&](auto SEP, auto CROP, auto POSE) {
+    std::apply([&](auto... extra) {
+      hipLaunchKernelGGL((k_splat_project<decltype(SEP)::value, decltype(extra)...>), dim3((unsigned)tn_cdiv(num_gaussians, PB)), dim3(PB), lds, tn_s(stream), k,
+                         means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs,
+                         antialiased, (float2*)xys, depths, radii, conics, compensation, num_tiles_hit, tile_box, ws.recs, ws.tbox, ws.thits, opacities_thermal,
+                         extra...);
+    }, std::tuple_cat(opt_args(CROP, ck), opt_args(POSE, SplatPoseK{pose_camera})));
+  }, sep, crop != nullptr, pose_camera != nullptr);
   TN_CHECK_LAUNCH(who);
   return TN_OK;
 }
 
-extern "C" int tn_splat_project(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
-                                const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
-                                int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys, float* depths,
-                                int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
-                                int64_t max_intersections, tn_stream_t stream) {
-  return splat_project("tn_splat_project", false, nullptr, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
-                       nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation, num_tiles_hit, tile_box,
-                       workspace, max_intersections, stream);
-}
-
-extern "C" int tn_splat_project_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
-                                    const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
-                                    const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased,
-                                    float* xys, float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box,
-                                    void* workspace, int64_t max_intersections, tn_stream_t stream) {
-  return splat_project("tn_splat_project_sep", true, nullptr, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
-                       thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation,
-                       num_tiles_hit, tile_box, workspace, max_intersections, stream);
-}
-
-// The crop entry points: the entry point each is named after, with the crop instantiation of the projection kernel.  A null box is refused (the
-// uncropped frame is the entry point without _crop).
-extern "C" int tn_splat_project_crop(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats, const float* opacities,
-                                     const float* features_dc, const float* features_rest, const float* thermal_dc, const float* thermal_rest,
-                                     int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys, float* depths,
-                                     int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
-                                     int64_t max_intersections, const TnSplatCrop* crop, tn_stream_t stream) {
-  TN_REQUIRE(crop != nullptr, "tn_splat_project_crop: null crop box");
-  return splat_project("tn_splat_project_crop", false, crop, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
-                       nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation, num_tiles_hit, tile_box,
-                       workspace, max_intersections, stream);
-}
-
-extern "C" int tn_splat_project_crop_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
-                                         const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
-                                         const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs,
-                                         int32_t sh_degree, int32_t antialiased, float* xys, float* depths, int32_t* radii, float* conics, float* compensation,
-                                         int32_t* num_tiles_hit, int32_t* tile_box, void* workspace, int64_t max_intersections, const TnSplatCrop* crop,
-                                         tn_stream_t stream) {
-  TN_REQUIRE(crop != nullptr, "tn_splat_project_crop_sep: null crop box");
-  return splat_project("tn_splat_project_crop_sep", true, crop, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
-                       thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation,
-                       num_tiles_hit, tile_box, workspace, max_intersections, stream);
-}
-
-// the box test of the crop projection on a bare point list: mask[i] = 1 where means[i] is inside, else 0
-// The pose entry points.  tn_splat_pose_camera: the frame's camera and one pose row (device) -> the corrected camera record (device), one launch,
-// nothing read back.  tn_splat_project_pose / _sep: tn_splat_project / _sep with the camera taken from that record (camera still gives the
-// intrinsics, the clip threshold and the image size); crop may be null.
+// tn_splat_pose_camera: the frame's camera and one pose row (device) -> the corrected camera record (device), one launch, nothing read back.
 extern "C" int tn_splat_pose_camera(const TnSplatCamera* camera, float proj_x, float proj_y, const float* pose_row, float* pose_camera, tn_stream_t stream) {
   int rc = check_cam(camera, "tn_splat_pose_camera");
   if (rc) return rc;
@@ -1583,29 +1517,6 @@ extern "C" int tn_splat_pose_camera(const TnSplatCamera* camera, float proj_x, f
   hipLaunchKernelGGL(k_splat_pose_camera, dim3(1), dim3(64), 0, tn_s(stream), make_camk(camera), proj_x, proj_y, pose_row, pose_camera);
   TN_CHECK_LAUNCH("tn_splat_pose_camera");
   return TN_OK;
-}
-
-extern "C" int tn_splat_project_pose(const TnSplatCamera* camera, const float* pose_camera, const float* means, const float* log_scales, const float* quats,
-                                     const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
-                                     const float* thermal_rest, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased,
-                                     float* xys, float* depths, int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box,
-                                     void* workspace, int64_t max_intersections, const TnSplatCrop* crop, tn_stream_t stream) {
-  TN_REQUIRE(pose_camera != nullptr, "tn_splat_project_pose: null pose camera record");
-  return splat_project("tn_splat_project_pose", false, crop, pose_camera, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
-                       thermal_rest, nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics, compensation, num_tiles_hit,
-                       tile_box, workspace, max_intersections, stream);
-}
-
-extern "C" int tn_splat_project_pose_sep(const TnSplatCamera* camera, const float* pose_camera, const float* means, const float* log_scales,
-                                         const float* quats, const float* opacities, const float* features_dc, const float* features_rest,
-                                         const float* thermal_dc, const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians,
-                                         int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, float* xys, float* depths, int32_t* radii,
-                                         float* conics, float* compensation, int32_t* num_tiles_hit, int32_t* tile_box, void* workspace,
-                                         int64_t max_intersections, const TnSplatCrop* crop, tn_stream_t stream) {
-  TN_REQUIRE(pose_camera != nullptr, "tn_splat_project_pose_sep: null pose camera record");
-  return splat_project("tn_splat_project_pose_sep", true, crop, pose_camera, camera, means, log_scales, quats, opacities, features_dc, features_rest,
-                       thermal_dc, thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, xys, depths, radii, conics,
-                       compensation, num_tiles_hit, tile_box, workspace, max_intersections, stream);
 }
 
 __global__ void __launch_bounds__(256) k_splat_crop_mask(SplatCropK crop, const float* __restrict__ means, int64_t n, uint8_t* __restrict__ mask) {
@@ -1692,8 +1603,8 @@ extern "C" int tn_splat_bin(const TnSplatCamera* camera, const float* depths, in
   return TN_OK;
 }
 
-// The raster of both entry points below: AA x TRAIN dispatch (TRAIN = the caller wants the transmittance and last-contributor images), then
-// the depth normalisation.  `who` / `who_depth` name the entry point's two launches in error messages.
+// The raster of both entry points below: AA x TRAIN x SEP (TRAIN = the caller wants the transmittance and last-contributor images, SEP = the
+// thermal chain's outputs), then the depth normalisation.  `who` / `who_depth` name the entry point's two launches in error messages.
 static int splat_raster(const char* who, const char* who_depth, const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
                         const float* background4, int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, float* out_T, int32_t* out_last,
                         float* out_alpha_th, float* out_T_th, int32_t* out_last_th, tn_stream_t stream) {
@@ -1701,17 +1612,13 @@ static int splat_raster(const char* who, const char* who_depth, const TnSplatCam
   SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, k.tbx * k.tby, nullptr);
   float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
   hipStream_t st = tn_s(stream);
-  if (out_alpha_th) {  // the caller is a _sep entry point (separate thermal opacity)
-    auto kernel = antialiased ? (out_T ? k_splat_raster<true, true, true, float*, float*, int32_t*> : k_splat_raster<true, false, true, float*, float*, int32_t*>)
-                              : (out_T ? k_splat_raster<false, true, true, float*, float*, int32_t*> : k_splat_raster<false, false, true, float*, float*, int32_t*>);
-    hipLaunchKernelGGL(kernel, dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, out_rgbt, out_depth,
-                       out_alpha, ws.depth_max, out_T, out_last, out_alpha_th, out_T_th, out_last_th);
-  } else {
-    auto kernel = antialiased ? (out_T ? k_splat_raster<true, true, false> : k_splat_raster<true, false, false>)
-                              : (out_T ? k_splat_raster<false, true, false> : k_splat_raster<false, false, false>);
-    hipLaunchKernelGGL(kernel, dim3(k.tbx * k.tby), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, out_rgbt, out_depth,
-                       out_alpha, ws.depth_max, out_T, out_last);
-  }
+  with_flags([&](auto AA, auto TRAIN, auto SEP) {
+    std::apply([&](auto... sep_args) {
+      hipLaunchKernelGGL((k_splat_raster<decltype(AA)::value, decltype(TRAIN)::value, decltype(SEP)::value, decltype(sep_args)...>), dim3(k.tbx * k.tby), dim3(256), 0,
+                         st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, out_rgbt, out_depth, out_alpha, ws.depth_max, out_T, out_last,
+                         sep_args...);
+    }, opt_args(SEP, out_alpha_th, out_T_th, out_last_th));
+  }, antialiased != 0, out_T != nullptr, out_alpha_th != nullptr);
   TN_CHECK_LAUNCH(who);
   int64_t n = (int64_t)k.W * k.H;
   hipLaunchKernelGGL(k_splat_depth_finalize, dim3((unsigned)tn_cdiv(n, 256)), dim3(256), 0, st, out_depth, out_alpha, ws.depth_max, n);
@@ -1719,6 +1626,7 @@ static int splat_raster(const char* who, const char* who_depth, const TnSplatCam
   return TN_OK;
 }
 
+// the short form: three images, shared opacity
 extern "C" int tn_splat_raster(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections, const float* background4,
                                int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, tn_stream_t stream) {
   int rc = check_cam(camera, "tn_splat_raster");
@@ -1728,14 +1636,24 @@ extern "C" int tn_splat_raster(const TnSplatCamera* camera, int64_t num_gaussian
                       nullptr, nullptr, nullptr, nullptr, stream);
 }
 
-extern "C" int tn_splat_raster_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections, const float* background4,
-                                   int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha, float* out_alpha_thermal, tn_stream_t stream) {
-  int rc = check_cam(camera, "tn_splat_raster_sep");
+// the raster with every optional output: {out_alpha_thermal} on a separate-opacity frame, {out_transmittance, out_last} for the backward, and
+// the thermal chain's {out_transmittance_thermal, out_last_thermal}, which needs both of the others
+extern "C" int tn_splat_raster_chains(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                      const float* background4, int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha,
+                                      float* out_alpha_thermal, float* out_transmittance, int32_t* out_last, float* out_transmittance_thermal,
+                                      int32_t* out_last_thermal, tn_stream_t stream) {
+  const char* who = "tn_splat_raster_chains";
+  int rc = check_cam(camera, who);
   if (rc) return rc;
-  TN_REQUIRE(workspace && background4 && out_rgbt && out_depth && out_alpha && out_alpha_thermal, "tn_splat_raster_sep: null pointer");
-  TN_REQUIRE(num_gaussians >= 0 && max_intersections >= 0, "tn_splat_raster_sep: bad sizes");
-  return splat_raster("tn_splat_raster_sep", "tn_splat_raster_sep(depth)", camera, num_gaussians, workspace, max_intersections, background4, antialiased, out_rgbt,
-                      out_depth, out_alpha, nullptr, nullptr, out_alpha_thermal, nullptr, nullptr, stream);
+  TN_REQUIRE(workspace && background4 && out_rgbt && out_depth && out_alpha, "%s: null pointer", who);
+  TN_REQUIRE(num_gaussians >= 0 && max_intersections >= 0, "%s: bad sizes", who);
+  const int train = group_state(out_transmittance, out_last), train_th = group_state(out_transmittance_thermal, out_last_thermal);
+  TN_REQUIRE(train >= 0 && train_th >= 0, "%s: null pointer (a transmittance / last-contributor pair is partly given)", who);
+  // (the TRAIN x SEP kernel writes both chains' pairs: the thermal pair goes with the other two groups, and only with them)
+  TN_REQUIRE((train_th != 0) == (train && out_alpha_thermal), "%s: the thermal chain's transmittance and last contributor go with out_alpha_thermal and the RGB chain's pair",
+             who);
+  return splat_raster(who, "tn_splat_raster_chains(depth)", camera, num_gaussians, workspace, max_intersections, background4, antialiased, out_rgbt, out_depth, out_alpha,
+                      out_transmittance, out_last, out_alpha_thermal, out_transmittance_thermal, out_last_thermal, stream);
 }
 
 extern "C" int tn_splat_raster_removal_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
@@ -1755,52 +1673,33 @@ extern "C" int tn_splat_raster_removal_sep(const TnSplatCamera* camera, int64_t 
   return TN_OK;
 }
 
-extern "C" int tn_splat_raster_train(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                                     const float* background4, int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha,
-                                     float* out_transmittance, int32_t* out_last, tn_stream_t stream) {
-  int rc = check_cam(camera, "tn_splat_raster_train");
-  if (rc) return rc;
-  TN_REQUIRE(workspace && background4 && out_rgbt && out_depth && out_alpha && out_transmittance && out_last, "tn_splat_raster_train: null pointer");
-  TN_REQUIRE(num_gaussians >= 0 && max_intersections >= 0, "tn_splat_raster_train: bad sizes");
-  return splat_raster("tn_splat_raster_train", "tn_splat_raster_train(depth)", camera, num_gaussians, workspace, max_intersections, background4, antialiased, out_rgbt, out_depth, out_alpha,
-                      out_transmittance, out_last, nullptr, nullptr, nullptr, stream);
-}
-
-extern "C" int tn_splat_raster_train_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                                         const float* background4, int32_t antialiased, float* out_rgbt, float* out_depth, float* out_alpha,
-                                         float* out_alpha_thermal, float* out_transmittance, int32_t* out_last, float* out_transmittance_thermal,
-                                         int32_t* out_last_thermal, tn_stream_t stream) {
-  int rc = check_cam(camera, "tn_splat_raster_train_sep");
-  if (rc) return rc;
-  TN_REQUIRE(workspace && background4 && out_rgbt && out_depth && out_alpha && out_alpha_thermal && out_transmittance && out_last &&
-                 out_transmittance_thermal && out_last_thermal,
-             "tn_splat_raster_train_sep: null pointer");
-  TN_REQUIRE(num_gaussians >= 0 && max_intersections >= 0, "tn_splat_raster_train_sep: bad sizes");
-  return splat_raster("tn_splat_raster_train_sep", "tn_splat_raster_train_sep(depth)", camera, num_gaussians, workspace, max_intersections, background4, antialiased,
-                      out_rgbt, out_depth, out_alpha, out_transmittance, out_last, out_alpha_thermal, out_transmittance_thermal, out_last_thermal, stream);
-}
-
-static int splat_raster_backward(const char* who, bool sep, bool absgrad, const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                                 int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
-                                 const float* transmittance_th, const int32_t* last_th, const float* conics, const float* v_rgbt, const float* v_alpha,
-                                 const float* v_alpha_th, void* bwd_workspace, int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics,
-                                 float* v_colors, float* v_log_opacity, float* v_log_opacity_th, const float* depth, const float* v_depth, float* v_depths,
-                                 tn_stream_t stream) {
+// The raster backward.  Optional groups: the thermal chain {transmittance_thermal, last_thermal, v_alpha_thermal, v_log_opacity_thermal} (SEP),
+// {v_xys_abs} (ABS: v_xys_abs [N,2] = sum over pixels of |the pixel's term of v_xys|, per component) and the depth gradient {depth, v_depth,
+// v_depths} (DEPTH; classic mode only: in antialiased mode the depth is blended by a chain of its own whose final transmittance and last
+// contributor the training forward does not keep).  Every output a group does not add is bit-equal with and without it.
+extern "C" int tn_splat_raster_backward(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+                                        int64_t num_intersections, const float* background4, int32_t antialiased, const float* transmittance,
+                                        const int32_t* last, const float* transmittance_thermal, const int32_t* last_thermal, const float* conics,
+                                        const float* v_rgbt, const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace,
+                                        int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors,
+                                        float* v_log_opacity, float* v_log_opacity_thermal, const float* depth, const float* v_depth, float* v_depths,
+                                        tn_stream_t stream) {
+  const char* who = "tn_splat_raster_backward";
+  const int sep_group = group_state(transmittance_thermal, last_thermal, v_alpha_thermal, v_log_opacity_thermal), depth_group = group_state(depth, v_depth, v_depths);
+  const bool sep = sep_group != 0, absgrad = v_xys_abs != nullptr, with_depth = depth_group != 0;
+  TN_REQUIRE(!with_depth || antialiased == 0, "%s: the depth gradient exists in classic mode only (antialiased depth rides a chain of its own)", who);
   int rc = check_cam(camera, who);
   if (rc) return rc;
-  const bool with_depth = depth || v_depth || v_depths;  // the DEPTH instantiations (tn_depth_splat_raster_backward)
   TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31), "%s: bad Gaussian count", who);
   TN_REQUIRE(max_intersections >= 0 && num_intersections >= 0 && num_intersections <= max_intersections, "%s: %lld intersections for a workspace of %lld", who,
              (long long)num_intersections, (long long)max_intersections);
   if (num_gaussians == 0) return TN_OK;
-  TN_REQUIRE(workspace && background4 && transmittance && last && conics && v_rgbt && v_alpha && bwd_workspace && v_xys && v_conics && v_colors &&
-                 v_log_opacity && (!sep || (transmittance_th && last_th && v_alpha_th && v_log_opacity_th)) && (!absgrad || v_xys_abs) &&
-                 (!with_depth || (depth && v_depth && v_depths)),
+  TN_REQUIRE(sep_group >= 0, "%s: null pointer (the thermal chain's group transmittance_thermal, last_thermal, v_alpha_thermal, v_log_opacity_thermal is partly given)", who);
+  TN_REQUIRE(depth_group >= 0, "%s: null pointer (the depth group depth, v_depth, v_depths is partly given)", who);
+  TN_REQUIRE(workspace && background4 && transmittance && last && conics && v_rgbt && v_alpha && bwd_workspace && v_xys && v_conics && v_colors && v_log_opacity,
              "%s: null pointer", who);
   const int ng = splat_pair_grads(sep, absgrad, with_depth);
-  size_t need_sz = 0;
-  (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, ng, &need_sz);
-  const int64_t need = (int64_t)need_sz;
+  const int64_t need = tn_splat_backward_workspace_bytes(num_gaussians, max_intersections, sep, absgrad, with_depth);
   TN_REQUIRE(bwd_workspace_bytes >= need, "%s: backward workspace of %lld bytes, %lld needed", who, (long long)bwd_workspace_bytes, (long long)need);
   SplatCamK k = make_camk(camera);
   const int num_tiles = k.tbx * k.tby;
@@ -1816,117 +1715,24 @@ static int splat_raster_backward(const char* who, bool sep, bool absgrad, const 
       return TN_ELAUNCH;
     }
     float4 bg = make_float4(background4[0], background4[1], background4[2], background4[3]);
-    const SplatDepthBwdK dk{depth, v_depth};
-    if (with_depth && sep && absgrad)
-      hipLaunchKernelGGL((k_splat_raster_bwd<true, true, const float*, const int32_t*, const float*, SplatDepthBwdK>), dim3(num_tiles), dim3(256), 0, st, ws.recs,
-                         ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, transmittance_th,
-                         last_th, v_alpha_th, dk);
-    else if (with_depth && sep)
-      hipLaunchKernelGGL((k_splat_raster_bwd<true, false, const float*, const int32_t*, const float*, SplatDepthBwdK>), dim3(num_tiles), dim3(256), 0, st, ws.recs,
-                         ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, transmittance_th,
-                         last_th, v_alpha_th, dk);
-    else if (with_depth && absgrad)
-      hipLaunchKernelGGL((k_splat_raster_bwd<false, true, SplatDepthBwdK>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H,
-                         k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, dk);
-    else if (with_depth)
-      hipLaunchKernelGGL((k_splat_raster_bwd<false, false, SplatDepthBwdK>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H,
-                         k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, dk);
-    else if (sep && absgrad)
-      hipLaunchKernelGGL((k_splat_raster_bwd<true, true, const float*, const int32_t*, const float*>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1],
-                         ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, transmittance_th, last_th,
-                         v_alpha_th);
-    else if (sep)
-      hipLaunchKernelGGL((k_splat_raster_bwd<true, false, const float*, const int32_t*, const float*>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1],
-                         ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, transmittance_th, last_th,
-                         v_alpha_th);
-    else if (absgrad)
-      hipLaunchKernelGGL((k_splat_raster_bwd<false, true>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg,
-                         transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair);
-    else
-      hipLaunchKernelGGL((k_splat_raster_bwd<false, false>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1], ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg,
-                         transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair);
+    with_flags([&](auto SEP, auto ABS, auto DEPTH) {
+      std::apply([&](auto... extra) {
+        hipLaunchKernelGGL((k_splat_raster_bwd<decltype(SEP)::value, decltype(ABS)::value, decltype(extra)...>), dim3(num_tiles), dim3(256), 0, st, ws.recs, ws.vals[1],
+                           ws.tile_bins, ws.lvals[1], k.W, k.H, k.tbx, bg, transmittance, last, v_rgbt, v_alpha, bw.start, ws.tbox, bw.pair, extra...);
+      }, std::tuple_cat(opt_args(SEP, transmittance_thermal, last_thermal, v_alpha_thermal), opt_args(DEPTH, SplatDepthBwdK{depth, v_depth})));
+    }, sep, absgrad, with_depth);
     TN_CHECK_LAUNCH(who);
   }
-  const dim3 fold_grid((unsigned)tn_cdiv(num_gaussians, 256));
-  const SplatDepthFoldK fk{v_depths};
-  if (with_depth && absgrad)
-    hipLaunchKernelGGL((sep ? k_splat_pair_fold<SPLAT_PAIR_GRADS_SEP + SPLAT_PAIR_DEPTH + SPLAT_PAIR_ABS, float*, SplatDepthFoldK>
-                            : k_splat_pair_fold<SPLAT_PAIR_GRADS + SPLAT_PAIR_DEPTH + SPLAT_PAIR_ABS, float*, SplatDepthFoldK>),
-                       fold_grid, dim3(256), 0, st, bw.pair, bw.start, ws.thits, conics, num_gaussians, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_th,
-                       v_xys_abs, fk);
-  else if (with_depth)
-    hipLaunchKernelGGL((sep ? k_splat_pair_fold<SPLAT_PAIR_GRADS_SEP + SPLAT_PAIR_DEPTH, SplatDepthFoldK> : k_splat_pair_fold<SPLAT_PAIR_GRADS + SPLAT_PAIR_DEPTH, SplatDepthFoldK>),
-                       fold_grid, dim3(256), 0, st, bw.pair, bw.start, ws.thits, conics, num_gaussians, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_th, fk);
-  else if (absgrad)
-    hipLaunchKernelGGL((sep ? k_splat_pair_fold<SPLAT_PAIR_GRADS_SEP + SPLAT_PAIR_ABS, float*> : k_splat_pair_fold<SPLAT_PAIR_GRADS + SPLAT_PAIR_ABS, float*>), fold_grid,
-                       dim3(256), 0, st, bw.pair, bw.start, ws.thits, conics, num_gaussians, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_th, v_xys_abs);
-  else
-    hipLaunchKernelGGL(sep ? k_splat_pair_fold<SPLAT_PAIR_GRADS_SEP> : k_splat_pair_fold<SPLAT_PAIR_GRADS>, fold_grid, dim3(256), 0, st, bw.pair, bw.start, ws.thits,
-                       conics, num_gaussians, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_th);
+  with_flags([&](auto SEP, auto ABS, auto DEPTH) {
+    constexpr int NG = (decltype(SEP)::value ? SPLAT_PAIR_GRADS_SEP : SPLAT_PAIR_GRADS) + (decltype(DEPTH)::value ? SPLAT_PAIR_DEPTH : 0) +
+                       (decltype(ABS)::value ? SPLAT_PAIR_ABS : 0);
+    std::apply([&](auto... extra) {
+      hipLaunchKernelGGL((k_splat_pair_fold<NG, decltype(extra)...>), dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, st, bw.pair, bw.start, ws.thits, conics,
+                         num_gaussians, v_xys, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, extra...);
+    }, std::tuple_cat(opt_args(ABS, v_xys_abs), opt_args(DEPTH, SplatDepthFoldK{v_depths})));
+  }, sep, absgrad, with_depth);
   TN_CHECK_LAUNCH(who);
   return TN_OK;
-}
-
-extern "C" int tn_splat_raster_backward(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                                        int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
-                                        const float* conics, const float* v_rgbt, const float* v_alpha, void* bwd_workspace,
-                                        int64_t bwd_workspace_bytes, float* v_xys, float* v_conics, float* v_colors, float* v_log_opacity,
-                                        tn_stream_t stream) {
-  return splat_raster_backward("tn_splat_raster_backward", false, false, camera, num_gaussians, workspace, max_intersections, num_intersections, background4, transmittance,
-                               last, nullptr, nullptr, conics, v_rgbt, v_alpha, nullptr, bwd_workspace, bwd_workspace_bytes, v_xys, nullptr, v_conics, v_colors,
-                               v_log_opacity, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-extern "C" int tn_splat_raster_backward_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                                            int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
-                                            const float* transmittance_thermal, const int32_t* last_thermal, const float* conics, const float* v_rgbt,
-                                            const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace, int64_t bwd_workspace_bytes, float* v_xys,
-                                            float* v_conics, float* v_colors, float* v_log_opacity, float* v_log_opacity_thermal, tn_stream_t stream) {
-  return splat_raster_backward("tn_splat_raster_backward_sep", true, false, camera, num_gaussians, workspace, max_intersections, num_intersections, background4,
-                               transmittance, last, transmittance_thermal, last_thermal, conics, v_rgbt, v_alpha, v_alpha_thermal, bwd_workspace,
-                               bwd_workspace_bytes, v_xys, nullptr, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, nullptr, nullptr, nullptr, stream);
-}
-
-// The two entry points above with the absgrad statistic: v_xys_abs [N,2] = sum over pixels of |the pixel's term of v_xys|, per component
-// (SPLAT_PAIR_ABS).  The workspace is tn_splat_backward_workspace_bytes_abs / _abs_sep; every other output is bit-equal to the entry point without _abs.
-extern "C" int tn_splat_raster_backward_abs(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                                            int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
-                                            const float* conics, const float* v_rgbt, const float* v_alpha, void* bwd_workspace,
-                                            int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors,
-                                            float* v_log_opacity, tn_stream_t stream) {
-  return splat_raster_backward("tn_splat_raster_backward_abs", false, true, camera, num_gaussians, workspace, max_intersections, num_intersections, background4,
-                               transmittance, last, nullptr, nullptr, conics, v_rgbt, v_alpha, nullptr, bwd_workspace, bwd_workspace_bytes, v_xys, v_xys_abs, v_conics,
-                               v_colors, v_log_opacity, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-extern "C" int tn_splat_raster_backward_abs_sep(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                                                int64_t num_intersections, const float* background4, const float* transmittance, const int32_t* last,
-                                                const float* transmittance_thermal, const int32_t* last_thermal, const float* conics, const float* v_rgbt,
-                                                const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace, int64_t bwd_workspace_bytes,
-                                                float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors, float* v_log_opacity,
-                                                float* v_log_opacity_thermal, tn_stream_t stream) {
-  return splat_raster_backward("tn_splat_raster_backward_abs_sep", true, true, camera, num_gaussians, workspace, max_intersections, num_intersections, background4,
-                               transmittance, last, transmittance_thermal, last_thermal, conics, v_rgbt, v_alpha, v_alpha_thermal, bwd_workspace,
-                               bwd_workspace_bytes, v_xys, v_xys_abs, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, nullptr, nullptr, nullptr, stream);
-}
-
-// The raster backward with an upstream gradient of the depth image (SPLAT_PAIR_DEPTH; classic mode only: in antialiased mode the depth is blended by a
-// chain of its own whose final transmittance and last contributor the training forward does not keep).  The arguments of
-// tn_splat_raster_backward_abs_sep plus `antialiased`, depth (the forward's normalised image), v_depth and v_depths; a null thermal group selects
-// shared mode, a null v_xys_abs no absgrad.  Workspace: tn_splat_depth_backward_workspace_bytes.
-extern "C" int tn_depth_splat_raster_backward(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
-                                              int64_t num_intersections, const float* background4, int32_t antialiased, const float* transmittance,
-                                              const int32_t* last, const float* transmittance_thermal, const int32_t* last_thermal, const float* conics,
-                                              const float* v_rgbt, const float* v_alpha, const float* v_alpha_thermal, void* bwd_workspace,
-                                              int64_t bwd_workspace_bytes, float* v_xys, float* v_xys_abs, float* v_conics, float* v_colors,
-                                              float* v_log_opacity, float* v_log_opacity_thermal, const float* depth, const float* v_depth,
-                                              float* v_depths, tn_stream_t stream) {
-  TN_REQUIRE(antialiased == 0, "tn_depth_splat_raster_backward: the depth gradient exists in classic mode only (antialiased depth rides a chain of its own)");
-  const bool sep = transmittance_thermal || last_thermal || v_alpha_thermal || v_log_opacity_thermal;
-  TN_REQUIRE(num_gaussians == 0 || (depth && v_depth && v_depths), "tn_depth_splat_raster_backward: null pointer");
-  return splat_raster_backward("tn_depth_splat_raster_backward", sep, v_xys_abs != nullptr, camera, num_gaussians, workspace, max_intersections, num_intersections,
-                               background4, transmittance, last, transmittance_thermal, last_thermal, conics, v_rgbt, v_alpha, v_alpha_thermal, bwd_workspace,
-                               bwd_workspace_bytes, v_xys, v_xys_abs, v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, depth, v_depth, v_depths, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ ray contribution (splat_prune.py)
@@ -2076,7 +1882,7 @@ __global__ void __launch_bounds__(256) k_splat_contrib_fold(const float* __restr
   views_acc[i] += m > 0.f ? 1 : 0;
 }
 
-extern "C" int64_t tn_contrib_splat_workspace_bytes(int64_t num_gaussians, int64_t max_intersections) {
+extern "C" int64_t tn_splat_contrib_workspace_bytes(int64_t num_gaussians, int64_t max_intersections) {
   if (num_gaussians < 0 || num_gaussians >= (1ll << 31) || max_intersections < 0) return -1;
   size_t total = 0;
   (void)splat_bwd_layout(nullptr, num_gaussians, max_intersections, SPLAT_PAIR_CONTRIB, &total);
@@ -2085,18 +1891,18 @@ extern "C" int64_t tn_contrib_splat_workspace_bytes(int64_t num_gaussians, int64
 
 // `antialiased` is the frame's flag as tn_splat_project took it: the records already hold the chain's compensated opacity, so it selects nothing
 // here and is only validated (the signature is tn_splat_raster's).
-extern "C" int tn_contrib_splat_raster(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
+extern "C" int tn_splat_raster_contrib(const TnSplatCamera* camera, int64_t num_gaussians, void* workspace, int64_t max_intersections,
                                        int32_t antialiased, int32_t chain, const float* pixel_weight, void* scratch, int64_t scratch_bytes,
                                        float* max_acc, double* sum_acc, int64_t* hits_acc, int32_t* views_acc, tn_stream_t stream) {
-  const char* who = "tn_contrib_splat_raster";
+  const char* who = "tn_splat_raster_contrib";
   int rc = check_cam(camera, who);
   if (rc) return rc;
   TN_REQUIRE(num_gaussians >= 0 && num_gaussians < (1ll << 31) && max_intersections >= 0 && max_intersections < (1ll << 31), "%s: bad sizes", who);
   TN_REQUIRE((antialiased == 0 || antialiased == 1) && (chain == 0 || chain == 1), "%s: antialiased = %d, chain = %d (each 0 or 1)", who, antialiased, chain);
   if (num_gaussians == 0) return TN_OK;
   TN_REQUIRE(workspace && scratch && max_acc && sum_acc && hits_acc && views_acc, "%s: null pointer", who);
-  const int64_t need = tn_contrib_splat_workspace_bytes(num_gaussians, max_intersections);
-  TN_REQUIRE(scratch_bytes >= need, "%s: scratch of %lld bytes, %lld needed (tn_contrib_splat_workspace_bytes)", who, (long long)scratch_bytes, (long long)need);
+  const int64_t need = tn_splat_contrib_workspace_bytes(num_gaussians, max_intersections);
+  TN_REQUIRE(scratch_bytes >= need, "%s: scratch of %lld bytes, %lld needed (tn_splat_contrib_workspace_bytes)", who, (long long)scratch_bytes, (long long)need);
   SplatCamK k = make_camk(camera);
   const int num_tiles = k.tbx * k.tby;
   SplatWs ws = splat_layout(workspace, num_gaussians, max_intersections, num_tiles, nullptr);
@@ -2113,165 +1919,59 @@ extern "C" int tn_contrib_splat_raster(const TnSplatCamera* camera, int64_t num_
   return TN_OK;
 }
 
-struct PoseBwdArgs {  // what the pose entry points add to the projection backward (null: the entry points without _pose)
-  const float* rec;
-  const float* pose_row;
-  void* workspace;
-  int64_t workspace_bytes;
-  float* grad_pose_row;
-  float* dview_out;
-};
 extern "C" int64_t tn_splat_pose_workspace_bytes(int64_t num_gaussians) {
   if (num_gaussians < 0 || num_gaussians >= (1ll << 31)) return -1;
   return (int64_t)al256((size_t)std::max<int64_t>(tn_cdiv(num_gaussians, 256), 1) * 12 * sizeof(double));
 }
 
-static int splat_project_backward(const char* who, bool sep, const PoseBwdArgs* pose, const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
-                                  const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
-                                  const float* thermal_rest, const float* opacities_th, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
-                                  int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics, const float* v_colors,
-                                  const float* v_log_opacity, const float* v_log_opacity_th, float* v_means, float* v_log_scales, float* v_quats,
-                                  float* v_opacities, float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest,
-                                  float* v_opacities_th, const float* v_depths, tn_stream_t stream) {
+// The projection + SH backward.  Optional groups: the thermal opacity {opacities_thermal, v_log_opacity_thermal, v_opacities_thermal} (SEP), the
+// pose {pose_camera, pose_row, workspace, grad_pose_row} (POSE: the camera of the forward's record, dL/d pose ADDED to grad_pose_row through the
+// finishing launch, dL/d view' left in dview_out where that is given) and {v_depths} (DEPTH, classic mode only).
+extern "C" int tn_splat_project_backward(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
+                                         const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
+                                         const float* features_rest, const float* thermal_dc, const float* thermal_rest, const float* opacities_thermal,
+                                         int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, const int32_t* radii,
+                                         const float* v_xys, const float* v_conics, const float* v_colors, const float* v_log_opacity,
+                                         const float* v_log_opacity_thermal, const float* v_depths, float* v_means, float* v_log_scales, float* v_quats,
+                                         float* v_opacities, float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest,
+                                         float* v_opacities_thermal, void* workspace, int64_t workspace_bytes, float* grad_pose_row, float* dview_out,
+                                         tn_stream_t stream) {
+  const char* who = "tn_splat_project_backward";
+  TN_REQUIRE(!v_depths || antialiased == 0, "%s: the depth gradient exists in classic mode only (antialiased depth rides a chain of its own)", who);
   int rc = check_cam(camera, who);
   if (rc) return rc;
   if (num_gaussians == 0) return TN_OK;
   TN_REQUIRE(num_gaussians > 0 && num_gaussians < (1ll << 31), "%s: bad Gaussian count", who);
+  const int sep_group = group_state(opacities_thermal, v_log_opacity_thermal, v_opacities_thermal), pose_group = group_state(pose_camera, pose_row, workspace, grad_pose_row);
+  TN_REQUIRE(sep_group >= 0, "%s: null pointer (the thermal opacity's group opacities_thermal, v_log_opacity_thermal, v_opacities_thermal is partly given)", who);
+  TN_REQUIRE(pose_group >= 0 && (pose_group || !dview_out), "%s: null pointer (the pose group pose_camera, pose_row, workspace, grad_pose_row is partly given)", who);
   TN_REQUIRE(means && log_scales && quats && opacities && features_dc && thermal_dc && radii && v_xys && v_conics && v_colors && v_log_opacity &&
-                 v_means && v_log_scales && v_quats && v_opacities && v_features_dc && v_thermal_dc &&
-                 (!sep || (opacities_th && v_log_opacity_th && v_opacities_th)),
+                 v_means && v_log_scales && v_quats && v_opacities && v_features_dc && v_thermal_dc,
              "%s: null pointer", who);
   TN_REQUIRE(sh_degree >= -1 && sh_degree <= 3, "%s: sh_degree %d unsupported (-1 = sigmoid of the DC term, 0..3)", who, sh_degree);
   TN_REQUIRE(num_rest_coeffs >= (sh_degree < 1 ? 0 : (sh_degree + 1) * (sh_degree + 1) - 1) && num_rest_coeffs <= 15,
              "%s: %d higher-order coefficients for degree %d", who, num_rest_coeffs, sh_degree);
   TN_REQUIRE(num_rest_coeffs == 0 || (features_rest && thermal_rest && v_features_rest && v_thermal_rest), "%s: null SH coefficients", who);
-  SplatCamK k = make_camk(camera);
-  if (pose) {  // the pose instantiation, then the launch that folds the blocks' partials and chains them to the pose row
-    TN_REQUIRE(pose->rec && pose->pose_row && pose->workspace && pose->grad_pose_row, "%s: null pointer", who);
+  if (pose_group) {
     const int64_t need = tn_splat_pose_workspace_bytes(num_gaussians);
-    TN_REQUIRE(pose->workspace_bytes >= need, "%s: workspace of %lld bytes, tn_splat_pose_workspace_bytes asks for %lld", who,
-               (long long)pose->workspace_bytes, (long long)need);
-    const int nblk = (int)tn_cdiv(num_gaussians, 256);
-    const SplatPoseBwdK pk{pose->rec, (double*)pose->workspace};
-    const SplatDepthProjK zk{v_depths};
-    if (v_depths && sep)
-      hipLaunchKernelGGL((k_splat_project_bwd<true, SplatPoseBwdK, SplatDepthProjK>), dim3((unsigned)nblk), dim3(256), 0, tn_s(stream), k, means, log_scales, quats,
-                         opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii, v_xys,
-                         v_conics, v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
-                         v_thermal_rest, opacities_th, v_log_opacity_th, v_opacities_th, pk, zk);
-    else if (v_depths)
-      hipLaunchKernelGGL((k_splat_project_bwd<false, SplatPoseBwdK, SplatDepthProjK>), dim3((unsigned)nblk), dim3(256), 0, tn_s(stream), k, means, log_scales, quats,
-                         opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii, v_xys,
-                         v_conics, v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
-                         v_thermal_rest, opacities_th, v_log_opacity_th, v_opacities_th, pk, zk);
-    else if (sep)
-      hipLaunchKernelGGL((k_splat_project_bwd<true, SplatPoseBwdK>), dim3((unsigned)nblk), dim3(256), 0, tn_s(stream), k, means, log_scales, quats, opacities,
-                         features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii, v_xys, v_conics,
-                         v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc, v_thermal_rest,
-                         opacities_th, v_log_opacity_th, v_opacities_th, pk);
-    else
-      hipLaunchKernelGGL((k_splat_project_bwd<false, SplatPoseBwdK>), dim3((unsigned)nblk), dim3(256), 0, tn_s(stream), k, means, log_scales, quats, opacities,
-                         features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii, v_xys, v_conics,
-                         v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc, v_thermal_rest,
-                         opacities_th, v_log_opacity_th, v_opacities_th, pk);
-    TN_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(k_splat_pose_finish, dim3(1), dim3(12 * SPLAT_POSE_SEGS), 0, tn_s(stream), k, pose->pose_row, (const double*)pose->workspace, nblk,
-                       pose->grad_pose_row, pose->dview_out);
-    TN_CHECK_LAUNCH(who);
-    return TN_OK;
+    TN_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes, tn_splat_pose_workspace_bytes asks for %lld", who, (long long)workspace_bytes, (long long)need);
   }
-  if (v_depths)
-    hipLaunchKernelGGL((sep ? k_splat_project_bwd<true, SplatDepthProjK> : k_splat_project_bwd<false, SplatDepthProjK>), dim3((unsigned)tn_cdiv(num_gaussians, 256)),
-                       dim3(256), 0, tn_s(stream), k, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree,
-                       num_rest_coeffs, antialiased, radii, v_xys, v_conics, v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc,
-                       v_features_rest, v_thermal_dc, v_thermal_rest, opacities_th, v_log_opacity_th, v_opacities_th, SplatDepthProjK{v_depths});
-  else
-    hipLaunchKernelGGL(sep ? k_splat_project_bwd<true> : k_splat_project_bwd<false>, dim3((unsigned)tn_cdiv(num_gaussians, 256)), dim3(256), 0, tn_s(stream), k, means,
-                       log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii,
-                       v_xys, v_conics, v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
-                       v_thermal_rest, opacities_th, v_log_opacity_th, v_opacities_th);
+  SplatCamK k = make_camk(camera);
+  const int nblk = (int)tn_cdiv(num_gaussians, 256);
+  with_flags([&](auto SEP, auto POSE, auto DEPTH) {
+    std::apply([&](auto... extra) {
+      hipLaunchKernelGGL((k_splat_project_bwd<decltype(SEP)::value, decltype(extra)...>), dim3((unsigned)nblk), dim3(256), 0, tn_s(stream), k, means, log_scales, quats,
+                         opacities, features_dc, features_rest, thermal_dc, thermal_rest, num_gaussians, sh_degree, num_rest_coeffs, antialiased, radii, v_xys,
+                         v_conics, v_colors, v_log_opacity, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
+                         v_thermal_rest, opacities_thermal, v_log_opacity_thermal, v_opacities_thermal, extra...);
+    }, std::tuple_cat(opt_args(POSE, SplatPoseBwdK{pose_camera, (double*)workspace}), opt_args(DEPTH, SplatDepthProjK{v_depths})));
+  }, sep_group != 0, pose_group != 0, v_depths != nullptr);
   TN_CHECK_LAUNCH(who);
+  if (pose_group) {  // folds the blocks' partials and chains them to the pose row
+    hipLaunchKernelGGL(k_splat_pose_finish, dim3(1), dim3(12 * SPLAT_POSE_SEGS), 0, tn_s(stream), k, pose_row, (const double*)workspace, nblk, grad_pose_row, dview_out);
+    TN_CHECK_LAUNCH(who);
+  }
   return TN_OK;
-}
-
-extern "C" int tn_splat_project_backward(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
-                                         const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
-                                         const float* thermal_rest, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
-                                         int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics, const float* v_colors,
-                                         const float* v_log_opacity, float* v_means, float* v_log_scales, float* v_quats, float* v_opacities,
-                                         float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest, tn_stream_t stream) {
-  return splat_project_backward("tn_splat_project_backward", false, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc, thermal_rest,
-                                nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics, v_colors, v_log_opacity, nullptr, v_means,
-                                v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc, v_thermal_rest, nullptr, nullptr, stream);
-}
-
-extern "C" int tn_splat_project_backward_sep(const TnSplatCamera* camera, const float* means, const float* log_scales, const float* quats,
-                                             const float* opacities, const float* features_dc, const float* features_rest, const float* thermal_dc,
-                                             const float* thermal_rest, const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs,
-                                             int32_t sh_degree, int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics,
-                                             const float* v_colors, const float* v_log_opacity, const float* v_log_opacity_thermal, float* v_means,
-                                             float* v_log_scales, float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest,
-                                             float* v_thermal_dc, float* v_thermal_rest, float* v_opacities_thermal, tn_stream_t stream) {
-  return splat_project_backward("tn_splat_project_backward_sep", true, nullptr, camera, means, log_scales, quats, opacities, features_dc, features_rest, thermal_dc,
-                                thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics, v_colors,
-                                v_log_opacity, v_log_opacity_thermal, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
-                                v_thermal_rest, v_opacities_thermal, nullptr, stream);
-}
-
-// The pose backward: tn_splat_project_backward / _sep with the camera of the forward's record, plus dL/d(pose row): pose_camera and pose_row as
-// tn_splat_pose_camera took and wrote them; workspace of tn_splat_pose_workspace_bytes(num_gaussians); the gradient is ADDED to grad_pose_row [6]
-// (the caller's row of grad_pose [C,6]); dview_out [12] (may be null) receives dL/d view'.  With zero Gaussians nothing is launched.
-extern "C" int tn_splat_project_backward_pose(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
-                                              const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
-                                              const float* features_rest, const float* thermal_dc, const float* thermal_rest, int64_t num_gaussians,
-                                              int32_t num_rest_coeffs, int32_t sh_degree, int32_t antialiased, const int32_t* radii, const float* v_xys,
-                                              const float* v_conics, const float* v_colors, const float* v_log_opacity, float* v_means, float* v_log_scales,
-                                              float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest, float* v_thermal_dc,
-                                              float* v_thermal_rest, void* workspace, int64_t workspace_bytes, float* grad_pose_row, float* dview_out,
-                                              tn_stream_t stream) {
-  const PoseBwdArgs pa{pose_camera, pose_row, workspace, workspace_bytes, grad_pose_row, dview_out};
-  return splat_project_backward("tn_splat_project_backward_pose", false, &pa, camera, means, log_scales, quats, opacities, features_dc, features_rest,
-                                thermal_dc, thermal_rest, nullptr, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics, v_colors,
-                                v_log_opacity, nullptr, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest, v_thermal_dc,
-                                v_thermal_rest, nullptr, nullptr, stream);
-}
-
-extern "C" int tn_splat_project_backward_pose_sep(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
-                                                  const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
-                                                  const float* features_rest, const float* thermal_dc, const float* thermal_rest,
-                                                  const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
-                                                  int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics,
-                                                  const float* v_colors, const float* v_log_opacity, const float* v_log_opacity_thermal, float* v_means,
-                                                  float* v_log_scales, float* v_quats, float* v_opacities, float* v_features_dc, float* v_features_rest,
-                                                  float* v_thermal_dc, float* v_thermal_rest, float* v_opacities_thermal, void* workspace,
-                                                  int64_t workspace_bytes, float* grad_pose_row, float* dview_out, tn_stream_t stream) {
-  const PoseBwdArgs pa{pose_camera, pose_row, workspace, workspace_bytes, grad_pose_row, dview_out};
-  return splat_project_backward("tn_splat_project_backward_pose_sep", true, &pa, camera, means, log_scales, quats, opacities, features_dc, features_rest,
-                                thermal_dc, thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys, v_conics,
-                                v_colors, v_log_opacity, v_log_opacity_thermal, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest,
-                                v_thermal_dc, v_thermal_rest, v_opacities_thermal, nullptr, stream);
-}
-
-// The projection backward with dL / d depths (SplatDepthProjK): the arguments of tn_splat_project_backward_pose_sep plus v_depths [N].  A null pose group
-// (pose_camera) means no pose, null thermal-opacity pointers select shared mode.  Classic mode only, as tn_depth_splat_raster_backward.
-extern "C" int tn_depth_splat_project_backward(const TnSplatCamera* camera, const float* pose_camera, const float* pose_row, const float* means,
-                                               const float* log_scales, const float* quats, const float* opacities, const float* features_dc,
-                                               const float* features_rest, const float* thermal_dc, const float* thermal_rest,
-                                               const float* opacities_thermal, int64_t num_gaussians, int32_t num_rest_coeffs, int32_t sh_degree,
-                                               int32_t antialiased, const int32_t* radii, const float* v_xys, const float* v_conics,
-                                               const float* v_colors, const float* v_log_opacity, const float* v_log_opacity_thermal,
-                                               const float* v_depths, float* v_means, float* v_log_scales, float* v_quats, float* v_opacities,
-                                               float* v_features_dc, float* v_features_rest, float* v_thermal_dc, float* v_thermal_rest,
-                                               float* v_opacities_thermal, void* workspace, int64_t workspace_bytes, float* grad_pose_row,
-                                               float* dview_out, tn_stream_t stream) {
-  TN_REQUIRE(antialiased == 0, "tn_depth_splat_project_backward: the depth gradient exists in classic mode only (antialiased depth rides a chain of its own)");
-  TN_REQUIRE(num_gaussians == 0 || v_depths, "tn_depth_splat_project_backward: null pointer");
-  const bool sep = opacities_thermal || v_log_opacity_thermal || v_opacities_thermal;
-  const PoseBwdArgs pa{pose_camera, pose_row, workspace, workspace_bytes, grad_pose_row, dview_out};
-  return splat_project_backward("tn_depth_splat_project_backward", sep, pose_camera ? &pa : nullptr, camera, means, log_scales, quats, opacities, features_dc,
-                                features_rest, thermal_dc, thermal_rest, opacities_thermal, num_gaussians, num_rest_coeffs, sh_degree, antialiased, radii, v_xys,
-                                v_conics, v_colors, v_log_opacity, v_log_opacity_thermal, v_means, v_log_scales, v_quats, v_opacities, v_features_dc, v_features_rest,
-                                v_thermal_dc, v_thermal_rest, v_opacities_thermal, v_depths, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ refinement
@@ -2500,9 +2200,11 @@ extern "C" int tn_splat_grad_stats(const float* xys_grad, const int32_t* radii, 
   return TN_OK;
 }
 
-static int splat_refine_plan(const char* who, bool sep, const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities,
-                             const float* opacities_th, const float* grad_norm_sum, const float* vis_counts, const float* max_2d_size, int64_t num_gaussians,
-                                    void* workspace, int64_t workspace_bytes, int64_t* counts_out, tn_stream_t stream) {
+// opacities_thermal (separate thermal opacity) is optional: with it the both-below cull rule (k_refine_classify<true>)
+extern "C" int tn_splat_refine_plan(const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities,
+                                    const float* opacities_thermal, const float* grad_norm_sum, const float* vis_counts, const float* max_2d_size,
+                                    int64_t num_gaussians, void* workspace, int64_t workspace_bytes, int64_t* counts_out, tn_stream_t stream) {
+  const char* who = "tn_splat_refine_plan";
   RefineK k;
   int cull = 0;
   int rc = refine_k(config, step, who, &k, &cull);
@@ -2512,13 +2214,13 @@ static int splat_refine_plan(const char* who, bool sep, const TnSplatRefine* con
   const int64_t N = num_gaussians;
   counts_out[0] = 0, counts_out[1] = N, counts_out[2] = 0, counts_out[3] = 0;
   if (N == 0 || !cull) return TN_OK;  // nothing to refine: every Gaussian stays where it is
-  TN_REQUIRE(log_scales && opacities && grad_norm_sum && vis_counts && max_2d_size && workspace && (!sep || opacities_th), "%s: null pointer", who);
+  TN_REQUIRE(log_scales && opacities && grad_norm_sum && vis_counts && max_2d_size && workspace, "%s: null pointer", who);
   const int64_t need = tn_splat_refine_workspace_bytes(N, config->n_split_samples);
   TN_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", who, (long long)workspace_bytes, (long long)need);
   RefineWs ws = refine_layout(workspace, N, config->n_split_samples, nullptr);
   hipStream_t st = tn_s(stream);
-  hipLaunchKernelGGL(sep ? k_refine_classify<true> : k_refine_classify<false>, dim3((unsigned)tn_cdiv(N, 256)), dim3(256), 0, st, log_scales, opacities, grad_norm_sum,
-                     vis_counts, max_2d_size, N, k, ws.cnt, opacities_th);
+  hipLaunchKernelGGL(opacities_thermal ? k_refine_classify<true> : k_refine_classify<false>, dim3((unsigned)tn_cdiv(N, 256)), dim3(256), 0, st, log_scales, opacities,
+                     grad_norm_sum, vis_counts, max_2d_size, N, k, ws.cnt, opacities_thermal);
   TN_CHECK_LAUNCH(who);
   size_t tb = ws.tmp_bytes;
   if (rocprim::inclusive_scan(ws.tmp, tb, (const RefCnt*)ws.cnt, ws.incl, (size_t)N, RefCntSum(), st) != hipSuccess) {
@@ -2532,20 +2234,6 @@ static int splat_refine_plan(const char* who, bool sep, const TnSplatRefine* con
   }
   counts_out[0] = tot.split, counts_out[1] = tot.orig, counts_out[2] = (int64_t)tot.child * config->n_split_samples, counts_out[3] = tot.dup;
   return TN_OK;
-}
-
-extern "C" int tn_splat_refine_plan(const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities,
-                                    const float* grad_norm_sum, const float* vis_counts, const float* max_2d_size, int64_t num_gaussians,
-                                    void* workspace, int64_t workspace_bytes, int64_t* counts_out, tn_stream_t stream) {
-  return splat_refine_plan("tn_splat_refine_plan", false, config, step, log_scales, opacities, nullptr, grad_norm_sum, vis_counts, max_2d_size, num_gaussians,
-                           workspace, workspace_bytes, counts_out, stream);
-}
-
-extern "C" int tn_splat_refine_plan_sep(const TnSplatRefine* config, int32_t step, const float* log_scales, const float* opacities,
-                                        const float* opacities_thermal, const float* grad_norm_sum, const float* vis_counts, const float* max_2d_size,
-                                        int64_t num_gaussians, void* workspace, int64_t workspace_bytes, int64_t* counts_out, tn_stream_t stream) {
-  return splat_refine_plan("tn_splat_refine_plan_sep", true, config, step, log_scales, opacities, opacities_thermal, grad_norm_sum, vis_counts, max_2d_size,
-                           num_gaussians, workspace, workspace_bytes, counts_out, stream);
 }
 
 template <int NT>
@@ -2596,18 +2284,13 @@ static int splat_refine_apply(const char* who, const TnSplatRefine* config, int6
   return TN_OK;
 }
 
+// num_tensors says how many entries each of the six HOST arrays holds: 8, or 9 with the separate thermal opacity
 extern "C" int tn_splat_refine_apply(const TnSplatRefine* config, int64_t num_gaussians, int32_t num_rest_coeffs, const void* workspace,
-                                     int64_t workspace_bytes, const int64_t* counts, const float* noise, const float* const* params,
+                                     int64_t workspace_bytes, const int64_t* counts, const float* noise, int32_t num_tensors, const float* const* params,
                                      const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params, float* const* new_exp_avg,
                                      float* const* new_exp_avg_sq, tn_stream_t stream) {
-  return splat_refine_apply<8>("tn_splat_refine_apply", config, num_gaussians, num_rest_coeffs, workspace, workspace_bytes, counts, noise, params, exp_avg,
-                               exp_avg_sq, new_params, new_exp_avg, new_exp_avg_sq, stream);
-}
-
-extern "C" int tn_splat_refine_apply_sep(const TnSplatRefine* config, int64_t num_gaussians, int32_t num_rest_coeffs, const void* workspace,
-                                         int64_t workspace_bytes, const int64_t* counts, const float* noise, const float* const* params,
-                                         const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params, float* const* new_exp_avg,
-                                         float* const* new_exp_avg_sq, tn_stream_t stream) {
-  return splat_refine_apply<9>("tn_splat_refine_apply_sep", config, num_gaussians, num_rest_coeffs, workspace, workspace_bytes, counts, noise, params, exp_avg,
-                               exp_avg_sq, new_params, new_exp_avg, new_exp_avg_sq, stream);
+  TN_REQUIRE(num_tensors == 8 || num_tensors == 9, "tn_splat_refine_apply: %d tensors per array (8, or 9 with the thermal opacity)", num_tensors);
+  return (num_tensors == 8 ? splat_refine_apply<8> : splat_refine_apply<9>)("tn_splat_refine_apply", config, num_gaussians, num_rest_coeffs, workspace, workspace_bytes,
+                                                                            counts, noise, params, exp_avg, exp_avg_sq, new_params, new_exp_avg, new_exp_avg_sq,
+                                                                            stream);
 }

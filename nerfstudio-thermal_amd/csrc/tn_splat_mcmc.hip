@@ -1,7 +1,7 @@
 // N4 training, MCMC strategy ("3D Gaussian Splatting as Markov Chain Monte Carlo"; gsplat's MCMCStrategy, splatfacto's strategy = "mcmc"):
 // the two device operations of ThermalSplatfactoModelConfig.strategy = "mcmc".  tests/splat_mcmc_functional.py restates both in float64.
 //
-// tn_splat_mcmc_relocate / _sep -- M draws (src_idx[j] -> dst_idx[j]) on tensors of num_rows rows, in place:
+// tn_splat_mcmc_relocate -- M draws (src_idx[j] -> dst_idx[j]) on tensors of num_rows rows, in place:
 //   memset            count[num_rows] = 0 (workspace)
 //   k_mcmc_count      count[src_idx[j]] += 1 (integer atomics: the sums do not depend on the order), own[j] = this draw saw 0 -- exactly one
 //                     draw per drawn source owns it; which one varies between runs, what is written does not
@@ -18,7 +18,7 @@
 // Cost: a refinement step only (every refine_every steps); it moves (2 reads or 1 read + 1 write) x 4 bytes x the row width (31 + 64 (K / 15)
 // floats, + 1 separate) per draw plus 4 num_rows bytes of counters -- at 1 M Gaussians and 50 k draws about 40 MB, tens of microseconds of HBM time.
 //
-// tn_splat_mcmc_noise / _sep -- means += Sigma (z g scaler) in place, Sigma = R(q / |q|) diag(exp(log-scale)^2) R^T, g = 1 / (1 + exp(-100 ((1 - o_vis)
+// tn_splat_mcmc_noise -- means += Sigma (z g scaler) in place, Sigma = R(q / |q|) diag(exp(log-scale)^2) R^T, g = 1 / (1 + exp(-100 ((1 - o_vis)
 // - 0.995))), o_vis = sigmoid(opacity) (separate: the larger of the two sigmoids), z = randn [N,3], scaler = noise_lr x the means' learning rate:
 //   k_mcmc_noise      one thread per Gaussian, fp32, no [N,3,3] temporary: Sigma v = R (s^2 * (R^T v)).
 // Bound: memory.  Per Gaussian it reads means 12 + log-scales 12 + quats 16 + opacity 4 + randn 12 and writes means 12 = 68 bytes (72 separate)
@@ -242,26 +242,17 @@ extern "C" int64_t tn_splat_mcmc_workspace_bytes(int64_t num_rows, int64_t num_d
   return (int64_t)total;
 }
 
+// num_tensors says how many entries each of the three HOST arrays holds: 8, or 9 with the separate thermal opacity
 extern "C" int tn_splat_mcmc_relocate(int64_t num_rows, int32_t num_rest_coeffs, const int64_t* src_idx, const int64_t* dst_idx, int64_t num_draws,
-                                      float min_opacity, float* const* params, float* const* exp_avg, float* const* exp_avg_sq, void* workspace,
-                                      int64_t workspace_bytes, tn_stream_t stream) {
-  return mcmc_relocate<8>("tn_splat_mcmc_relocate", num_rows, num_rest_coeffs, src_idx, dst_idx, num_draws, min_opacity, params, exp_avg, exp_avg_sq,
-                          workspace, workspace_bytes, stream);
+                                      float min_opacity, int32_t num_tensors, float* const* params, float* const* exp_avg, float* const* exp_avg_sq,
+                                      void* workspace, int64_t workspace_bytes, tn_stream_t stream) {
+  TN_REQUIRE(num_tensors == 8 || num_tensors == 9, "tn_splat_mcmc_relocate: %d tensors per array (8, or 9 with the thermal opacity)", num_tensors);
+  return (num_tensors == 8 ? mcmc_relocate<8> : mcmc_relocate<9>)("tn_splat_mcmc_relocate", num_rows, num_rest_coeffs, src_idx, dst_idx, num_draws, min_opacity, params,
+                                                                  exp_avg, exp_avg_sq, workspace, workspace_bytes, stream);
 }
 
-extern "C" int tn_splat_mcmc_relocate_sep(int64_t num_rows, int32_t num_rest_coeffs, const int64_t* src_idx, const int64_t* dst_idx, int64_t num_draws,
-                                          float min_opacity, float* const* params, float* const* exp_avg, float* const* exp_avg_sq, void* workspace,
-                                          int64_t workspace_bytes, tn_stream_t stream) {
-  return mcmc_relocate<9>("tn_splat_mcmc_relocate_sep", num_rows, num_rest_coeffs, src_idx, dst_idx, num_draws, min_opacity, params, exp_avg,
-                          exp_avg_sq, workspace, workspace_bytes, stream);
-}
-
-extern "C" int tn_splat_mcmc_noise(float* means, const float* log_scales, const float* quats, const float* opacities, const float* randn,
-                                   int64_t num_gaussians, float scaler, tn_stream_t stream) {
-  return mcmc_noise("tn_splat_mcmc_noise", false, means, log_scales, quats, opacities, nullptr, randn, num_gaussians, scaler, stream);
-}
-
-extern "C" int tn_splat_mcmc_noise_sep(float* means, const float* log_scales, const float* quats, const float* opacities, const float* opacities_thermal,
-                                       const float* randn, int64_t num_gaussians, float scaler, tn_stream_t stream) {
-  return mcmc_noise("tn_splat_mcmc_noise_sep", true, means, log_scales, quats, opacities, opacities_thermal, randn, num_gaussians, scaler, stream);
+// opacities_thermal is optional: with it a Gaussian visible in either spectrum stays where it is (k_mcmc_noise<true>)
+extern "C" int tn_splat_mcmc_noise(float* means, const float* log_scales, const float* quats, const float* opacities, const float* opacities_thermal,
+                                   const float* randn, int64_t num_gaussians, float scaler, tn_stream_t stream) {
+  return mcmc_noise("tn_splat_mcmc_noise", opacities_thermal != nullptr, means, log_scales, quats, opacities, opacities_thermal, randn, num_gaussians, scaler, stream);
 }

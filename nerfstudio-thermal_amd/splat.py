@@ -8,7 +8,7 @@ same rasteriser -- the splat analogue of thermal-nerfacto's shared density (`the
 Gaussian also has `opacities_thermal` [N,1] (logits, started at logit(0.1) like `opacities`, its own optimiser group): RGB, accumulation and
 depth composite with sigmoid(opacities), the thermal channel with sigmoid(opacities_thermal) through a transmittance chain of its own over the
 same depth-sorted tile lists (its own 1e-4 stop, its background weighted by its own final transmittance; `accumulation_thermal` [H,W,1] is its
-accumulation), so glass can be clear in RGB and opaque in thermal.  That mode runs the _sep family of entry points; its backward is as exact and
+accumulation), so glass can be clear in RGB and opaque in thermal.  That mode gives every entry point its thermal group; its backward is as exact and
 bit-reproducible, `last_xys_grad` sums both chains; refinement culls a Gaussian for low opacity only when BOTH opacities are below
 `cull_alpha_thresh`, and carries, copies and resets the thermal logits exactly as the opacities.  `opacity_loss_mult` > 0 adds the NeRF model's
 `density_loss` (models/thermal_nerfacto.py:328-344) on the two opacities.  With `removal_min_opacity_diff` = thr set (separate mode only; None = off)
@@ -21,9 +21,9 @@ and background weight of its own -- what sits behind glass or an IR-transparent 
 backward (tn_splat_raster_backward / tn_splat_project_backward) is the exact, bit-reproducible derivative of the forward this file computes,
 and it leaves dL/d xys per Gaussian in `last_xys_grad` (what splatfacto's densification reads as `self.xys.grad`, splatfacto.py:355).
 Depth is returned detached unless `differentiable_depth` is on (classic mode): then `depth` [H,W,1] carries gradients too -- depth = D / accumulation
-where the pixel is covered, D riding the RGB chain as a fifth channel; the fill value elsewhere takes none -- through tn_depth_splat_raster_backward /
-tn_depth_splat_project_backward, as exact and atomic-free as the rest; a backward whose loss never touched depth runs the entry points of before and
-gives their bits.  `depth_loss_mult` / `depth_tv_loss_mult` above 0 (both default 0) add `depth_loss` -- the L1 distance to the batch's `depth_image`, a
+where the pixel is covered, D riding the RGB chain as a fifth channel; the fill value elsewhere takes none -- through the depth groups of tn_splat_raster_backward /
+tn_splat_project_backward, as exact and atomic-free as the rest; a backward whose loss never touched depth leaves the groups out and gives the
+bits of before.  `depth_loss_mult` / `depth_tv_loss_mult` above 0 (both default 0) add `depth_loss` -- the L1 distance to the batch's `depth_image`, a
 sensor depth -- and `depth_tv_loss` -- the depth's 2 x 2 total variation -- over the covered pixels, on RGB and thermal frames alike (`depth_losses`:
 tn_depth_loss).  Training follows splatfacto's refinement (splatfacto.py:346-498): `after_train` accumulates the gradient
 statistics (tn_splat_grad_stats), `refinement_after` splits, duplicates and culls the Gaussians (tn_splat_refine_plan / tn_splat_refine_apply)
@@ -37,20 +37,20 @@ cube of before.  Under the resolution schedule the eval render is always full si
 splatfacto's crop box: `set_crop(box)` / `crop_box` and `get_outputs_for_camera(camera, obb_box)`, the door of the viewer, ns-render and the
 exporter.  With a box set `get_outputs` renders only the Gaussians whose mean is strictly inside it, bit for bit the frame of a model holding those
 alone -- rgb, thermal, depth, the accumulations and the removal renders.  The reference gathers six parameter tensors through a boolean index per
-frame; here the box test is the first thing the projection kernel does (tn_splat_project_crop / _crop_sep): a Gaussian outside leaves with radius 0
+frame; here the box test is the first thing the projection kernel does (tn_splat_project with its box): a Gaussian outside leaves with radius 0
 and no tiles, as one behind the camera, a block of Gaussians that are all outside never reads its SH coefficients, and nothing is copied, allocated or
 read back.  The training render never crops (the reference crops only outside training), and the box is neither a parameter nor in the state dict.
 With a pose row `get_train_outputs` is differentiable in it: the pose instantiations of the projection kernels read the corrected camera
-(tn_splat_project_pose / tn_splat_project_backward_pose), and the backward reduces dL/d view' over the Gaussians without atomics, bit-reproducibly;
+(the pose groups of tn_splat_project / tn_splat_project_backward), and the backward reduces dL/d view' over the Gaussians without atomics, bit-reproducibly;
 the SH view directions take the corrected position as a value (splatfacto.py:770).  Densification has a second strategy,
 `strategy` = "mcmc" ("3D Gaussian Splatting as Markov Chain Monte Carlo": gsplat's MCMCStrategy, current splatfacto's strategy "mcmc" with
 `max_gs_num`): a fixed budget of Gaussians instead of gradient thresholds.  Every `refine_every` steps (between warmup_length and stop_split_at)
 the refinement callback relocates the dead Gaussians -- visible opacity (the larger of the two sigmoids in separate mode) <= `mcmc_min_opacity` --
 onto live ones drawn with probability proportional to their visible opacity (torch.multinomial of the model's noise_generator), correcting the
 opacity and the scale of source and copies so that the render is preserved, then grows the population by `mcmc_grow_factor` up to `max_gs_num`
-in the same way; both go through tn_splat_mcmc_relocate / _sep, in place on every parameter tensor and both Adam moments (source rows lose their
+in the same way; both go through tn_splat_mcmc_relocate, in place on every parameter tensor and both Adam moments (source rows lose their
 moments, as in gsplat), with the relocation values evaluated in double.  One more callback adds position noise after every step,
-means += Sigma (randn * g * noise_lr * lr of the means), g = sigmoid(100 ((1 - o_vis) - 0.995)), in one tn_splat_mcmc_noise / _sep launch, and
+means += Sigma (randn * g * noise_lr * lr of the means), g = sigmoid(100 ((1 - o_vis) - 0.995)), in one tn_splat_mcmc_noise launch, and
 `get_loss_dict` adds `mcmc_opacity_reg` * mean(sigmoid(opacities)) (+ the thermal mean in separate mode) and `mcmc_scale_reg` * mean(exp(scales)).
 No gradient statistics, no cull, no opacity reset; `last_refine_counts` = (dead, relocated, added).  "default" (the default) takes the code path
 of before, untouched.  Whether "mcmc" trains thermal scenes better is not established (profiles/splat_mcmc.md).  With `use_bilateral_grid` every training frame has a bilateral grid
@@ -74,7 +74,7 @@ tree; oracle/splat_oracle.py restates its published algorithm).  No CPU path.
 
 splat_calls.py: the C entry points, their names and argument order, the workspaces, `knn_distances`, `mcmc_relocate`, `mcmc_noise`.
 splat_camera.py: `PinholeCamera`, `camera_struct`, the resolution schedule's camera, `undistorted_camera`, `OrientedBox`, the pose optimiser.
-splat_prune.py: `score_gaussians`, `prune_mask`, `prune_gaussians` -- every Gaussian's ray contribution (tn_contrib_splat_raster) and pruning by it;
+splat_prune.py: `score_gaussians`, `prune_mask`, `prune_gaussians` -- every Gaussian's ray contribution (tn_splat_raster_contrib) and pruning by it;
                 `prune_at_steps` / `set_prune_cameras` run it from the refinement callback (off by default).
 splat_image.py: `image_loss`, `resize_image`, `undistort_image`, `thermal_regularizers`, `depth_losses`, `bilateral_slice`, `bilateral_grid_tv`, `ssim`.
 """
@@ -148,7 +148,7 @@ class ThermalSplatfactoModelConfig:
     reset_alpha_every: int = 30
     densify_grad_thresh: float = 0.0002
     # AbsGS's statistic (gsplat's `absgrad`, splatfacto's `use_absgrad`): densify on the norm of sum over pixels |d L_p / d xys| per component
-    # instead of |sum over pixels d L_p / d xys|, whose pixel terms cancel on a large Gaussian over fine structure (tn_splat_raster_backward_abs;
+    # instead of |sum over pixels d L_p / d xys|, whose pixel terms cancel on a large Gaussian over fine structure (tn_splat_raster_backward with v_xys_abs;
     # `last_xys_absgrad`).  The absolute statistic is several times the signed one (a median 3.5 to 12.5 times on the backward test scenes), so
     # densify_grad_thresh wants raising with it: gsplat's documentation advises about 0.0008 with absgrad where 0.0002 is used without.  The
     # default above is NOT changed by the flag, and no scene has been trained here to pick a value.
@@ -353,10 +353,10 @@ def _background_outputs(H: int, W: int, bgl: List[float], dev, sep: bool = False
 class _SplatRender(torch.autograd.Function):
     """project -> bin -> training raster; backward = raster backward -> projection backward.  Inputs after `frame` are the gauss_params in
     _PARAM_NAMES order; outputs: colour before the clamp [H,W,4] (RGB + thermal over the background), accumulation [H,W,1], depth [H,W,1]
-    (not differentiable, unless frame["depth_grad"]: then a backward that receives a gradient for it runs the tn_depth_splat_* entry points, and one
-    that does not runs the others).  Nine parameters (separate thermal opacity, opacities_thermal last): the _sep entry points, and a fourth output,
+    (not differentiable, unless frame["depth_grad"]: then a backward that receives a gradient for it passes the depth groups of the two backward entry points, and one
+    that does not leaves them out).  Nine parameters (separate thermal opacity, opacities_thermal last): the thermal group of every entry point, and a fourth output,
     the thermal chain's accumulation [H,W,1].  A frame with a pose row (frame["pose_row"]) passes its optimiser's pose_adjustment [C,6] as one
-    more input behind the parameters: the camera is corrected on the device (pose_camera_record), the _pose entry points run, and the backward
+    more input behind the parameters: the camera is corrected on the device (pose_camera_record), the projection and its backward read that record, and the backward
     also returns dL/d pose_adjustment [C,6], zero outside the frame's row, and leaves dL/d view' [3,4] in `last_view_grad`."""
 
     @staticmethod
@@ -406,7 +406,7 @@ class _SplatRender(torch.autograd.Function):
         params, rest = ctx.saved_tensors[:P], ctx.saved_tensors[P:]
         N, dev = params[0].shape[0], params[0].device
         pose, row = ctx.pose, frame.get("pose_row")
-        absgrad = bool(model.config.use_absgrad)  # the _abs entry points: the same gradients plus last_xys_absgrad, the densification statistic
+        absgrad = bool(model.config.use_absgrad)  # v_xys_abs of the raster backward: the same gradients plus last_xys_absgrad, the densification statistic
         if ctx.empty:
             model.last_xys_grad = torch.zeros((N, 2), device=dev)
             model.last_xys_absgrad = torch.zeros((N, 2), device=dev) if absgrad else None
@@ -593,7 +593,7 @@ class ThermalSplatfactoModel(nn.Module):
 
     @property
     def separate(self) -> bool:
-        """thermal_opacity_mode == "separate": gauss_params holds opacities_thermal and the _sep entry points run."""
+        """thermal_opacity_mode == "separate": gauss_params holds opacities_thermal and the entry points take their thermal groups."""
         return self.config.thermal_opacity_mode == "separate"
 
     @property

@@ -1,12 +1,10 @@
-"""The call layer of the splat path: the one module that names the tn_splat_* / tn_knn / tn_image_* / tn_thermal_reg / tn_depth_loss / tn_bilagrid_* / tn_transform_splat / tn_filter3d_splat_* / tn_contrib_splat_* entry points of
-libthermal_nerf_hip.so and knows their argument order (include/thermal_nerf_hip.h).  The three gsplat calls (project_gaussians,
-spherical_harmonics, rasterize_gaussians x2) run as tn_splat_project / tn_splat_bin / tn_splat_raster of libthermal_nerf_hip.so; separate thermal
-opacity runs the _sep family (tn_splat_project_sep ... tn_splat_refine_apply_sep: the same kernels instantiated with the second chain), and _crop,
-_pose and _abs are instantiations too.  A variant takes the arguments of its base, in the same order, with the optional ones inserted at fixed
-places, so every stage here is ONE call whose argument list is built from segments; which optional tensors the caller passes picks the variant
-(`entry` composes its name).  The depth gradient is the exception: its three entry points have fixed names and take the thermal-chain, absgrad and
-pose arguments as nullable pointers, so `raster_backward` / `project_backward` switch to them when `v_depth` / `v_depths` are given.  The caller decides which tensors exist: nothing is allocated here but workspaces.  Everything goes to the current
-stream; nothing but refine_plan's counts is read back.
+"""The call layer of the splat path: the one module that names the tn_splat_* / tn_knn / tn_image_* / tn_thermal_reg / tn_depth_loss / tn_bilagrid_* /
+tn_transform_splat / tn_filter3d_splat_* entry points of libthermal_nerf_hip.so and knows their argument order (include/thermal_nerf_hip.h).  The
+three gsplat calls (project_gaussians, spherical_harmonics, rasterize_gaussians x2) run as tn_splat_project / tn_splat_bin / tn_splat_raster_chains.
+Every stage has ONE entry point with a fixed argument list; what a frame may or may not have -- the thermal opacity of separate mode, a crop box,
+a pose record, absgrad, the depth gradient -- is a group of nullable pointers, and a tensor the caller does not pass goes in as None (null): the
+library picks the kernel instantiation from the groups it is given and refuses a group given in part.  The caller decides which tensors exist:
+nothing is allocated here but workspaces.  Everything goes to the current stream; nothing but refine_plan's counts is read back.
 """
 from __future__ import annotations
 
@@ -26,24 +24,6 @@ F32, I32 = torch.float32, torch.int32
 _PARAM_NAMES = ("means", "scales", "quats", "opacities", "features_dc", "features_rest", "features_dc_thermal", "features_rest_thermal")
 # thermal_opacity_mode "separate": the thermal opacity logits come ninth, in a group of their own
 _PARAM_NAMES_SEP = _PARAM_NAMES + ("opacities_thermal",)
-
-# entry-point family -> the variant flags the header has for it, in the order they enter the name
-FAMILIES = {"tn_splat_project": ("crop", "pose", "sep"), "tn_splat_raster": ("sep",), "tn_splat_raster_train": ("sep",),
-            "tn_splat_raster_backward": ("abs", "sep"), "tn_splat_backward_workspace_bytes": ("abs", "sep"),
-            "tn_splat_project_backward": ("pose", "sep"), "tn_splat_refine_plan": ("sep",), "tn_splat_refine_apply": ("sep",),
-            "tn_splat_mcmc_relocate": ("sep",), "tn_splat_mcmc_noise": ("sep",)}
-
-
-@functools.lru_cache(maxsize=None)
-def entry(base: str, *, abs: bool = False, crop: bool = False, pose: bool = False, sep: bool = False) -> str:  # noqa: A002
-    """The name of a variant: base + {"_abs", "_crop", "_pose"} + {"_sep"}.  A combination the header does not have is a ValueError -- a flag the
-    family lacks, or crop and pose together (the pose entry takes the box as a nullable argument, so `crop` is not in its name)."""
-    on = {"abs": abs, "crop": crop, "pose": pose, "sep": sep}
-    flags = FAMILIES.get(base)
-    if flags is None or (crop and pose) or any(v and f not in flags for f, v in on.items()):
-        raise ValueError(f"{base} has no variant with {[f for f, v in on.items() if v]}")
-    return base + "".join("_" + f for f in flags if on[f])
-
 
 def param_names(mode: str) -> Tuple[str, ...]:
     """The gauss_params entries of a thermal_opacity_mode, in the order the C entry points take them."""
@@ -79,7 +59,7 @@ def _pose_row_ptr(pose: Tensor, row: int, name: str = "pose_adjustment"):
 def _param_ptrs(tensors) -> list:
     """Pointers of eight tensors laid out as the gauss_params, in _PARAM_NAMES order, as the C entry points take them: without higher-order SH
     coefficients (K == 0) the two features_rest tensors are null, and opacities [N,1] goes in flat.  Nine tensors (separate thermal opacity):
-    opacities_thermal [N,1] follows, flat too, where the _sep entry points take it."""
+    opacities_thermal [N,1] follows, flat too."""
     K = tensors[5].shape[1]
     pp = [_ptr(t, F32, n) if (K or not n.startswith("features_rest")) else None for t, n in zip(tensors, _PARAM_NAMES_SEP)]
     for j in (3, 8)[:len(tensors) - 7]:
@@ -108,14 +88,17 @@ frame_workspace_bytes = functools.partial(workspace_bytes, "tn_splat_workspace_b
 
 
 # ---------------------------------------------------------------------------------------------------- the frame: project -> bin -> raster
+def _param_ptrs9(tensors) -> list:
+    """_param_ptrs in the fixed nine places of the frame's entry points: eight tensors (shared opacity) leave the thermal opacity's place null."""
+    return _param_ptrs(tensors) + [None] * (9 - len(tensors))
+
+
 def project(cam, params, deg, aa, proj, ws, cap, crop=None, pose_rec=None) -> None:
-    """tn_splat_project of the 8 (9: _sep) `params` into the seven tensors of `proj` (in the header's order) and the frame workspace `ws`.  With
-    `crop` (a TnSplatCrop) it is tn_splat_project_crop / _crop_sep: Gaussians outside the box leave with radius 0.  With `pose_rec`
-    (pose_camera's record) it is tn_splat_project_pose / _pose_sep, which reads the corrected camera from that record (and takes the box too)."""
-    pose, box = pose_rec is not None, (C.byref(crop) if crop is not None else None)
-    _call(entry("tn_splat_project", crop=crop is not None and not pose, pose=pose, sep=len(params) == 9), C.byref(cam),
-          *([_ptr(pose_rec, F32, "pose camera")] if pose else []), *_param_ptrs(params), params[0].shape[0], params[5].shape[1], deg, aa,
-          *[_ptr(t, t.dtype, k) for k, t in proj.items()], _raw(ws), cap, *([box] if pose or crop is not None else []))
+    """tn_splat_project of the 8 (9: separate thermal opacity) `params` into the seven tensors of `proj` (in the header's order) and the frame
+    workspace `ws`.  With `crop` (a TnSplatCrop) Gaussians outside the box leave with radius 0; with `pose_rec` (pose_camera's record) the
+    corrected camera is read from that record."""
+    _call("tn_splat_project", C.byref(cam), _ptr(pose_rec, F32, "pose camera"), *_param_ptrs9(params), params[0].shape[0], params[5].shape[1], deg, aa,
+          *[_ptr(t, t.dtype, k) for k, t in proj.items()], _raw(ws), cap, C.byref(crop) if crop is not None else None)
 
 
 def bin(cam, depths, N, ws, cap, total, may_grow: bool) -> bool:  # noqa: A001
@@ -128,20 +111,20 @@ def bin(cam, depths, N, ws, cap, total, may_grow: bool) -> bool:  # noqa: A001
     return True
 
 
-def raster(cam, N, ws, cap, bg4, aa, rgbt, depth, alpha, alpha_th=None) -> None:
-    """The eval render, tn_splat_raster; with `alpha_th` (the thermal chain's accumulation) tn_splat_raster_sep."""
-    sep = alpha_th is not None
-    _call(entry("tn_splat_raster", sep=sep), C.byref(cam), N, _raw(ws), cap, bg4, aa, *_f32(rgbt=rgbt, depth=depth, alpha=alpha),
-          *(_f32(alpha_thermal=alpha_th) if sep else []))
-
-
 def raster_train(cam, N, ws, cap, bg4, aa, rgbt, depth, alpha, final_t, last, alpha_th=None, final_t_th=None, last_th=None) -> None:
-    """The training render, tn_splat_raster_train: the eval render plus what the backward reads (final transmittance and last blended index per
-    pixel); with the thermal chain's three (`alpha_th`, `final_t_th`, `last_th`) tn_splat_raster_train_sep."""
-    sep = alpha_th is not None
-    _call(entry("tn_splat_raster_train", sep=sep), C.byref(cam), N, _raw(ws), cap, bg4, aa, *_f32(rgbt=rgbt, depth=depth, alpha=alpha),
-          *(_f32(alpha_thermal=alpha_th) if sep else []), *_f32(transmittance=final_t), _ptr(last, I32, "last"),
-          *(_f32(transmittance_thermal=final_t_th) + [_ptr(last_th, I32, "last_thermal")] if sep else []))
+    """tn_splat_raster_chains.  The training render: the eval render plus what the backward reads (`final_t`, `last`: final transmittance and last
+    blended index per pixel); a separate-opacity frame adds the thermal chain's three (`alpha_th`, `final_t_th`, `last_th`)."""
+    _call("tn_splat_raster_chains", C.byref(cam), N, _raw(ws), cap, bg4, aa, *_f32(rgbt=rgbt, depth=depth, alpha=alpha, alpha_thermal=alpha_th, transmittance=final_t),
+          _ptr(last, I32, "last"), *_f32(transmittance_thermal=final_t_th), _ptr(last_th, I32, "last_thermal"))
+
+
+def raster(cam, N, ws, cap, bg4, aa, rgbt, depth, alpha, alpha_th=None) -> None:
+    """The eval render: tn_splat_raster, the short form (three images, shared opacity); with `alpha_th`, the thermal chain's accumulation of a
+    separate-opacity frame, tn_splat_raster_chains without the backward's images."""
+    if alpha_th is None:
+        _call("tn_splat_raster", C.byref(cam), N, _raw(ws), cap, bg4, aa, *_f32(rgbt=rgbt, depth=depth, alpha=alpha))
+    else:
+        _call("tn_splat_raster_chains", C.byref(cam), N, _raw(ws), cap, bg4, aa, *_f32(rgbt=rgbt, depth=depth, alpha=alpha, alpha_thermal=alpha_th), None, None, None, None)
 
 
 def raster_removal(cam, N, ws, cap, bg4, thr, rem) -> None:
@@ -150,7 +133,7 @@ def raster_removal(cam, N, ws, cap, bg4, thr, rem) -> None:
 
 
 def raster_contrib(cam, N, ws, cap, aa, chain, pixel_weight, max_acc, sum_acc, hits_acc, views_acc) -> None:
-    """tn_contrib_splat_raster over the projected and binned frame in `ws`: every Gaussian's ray contribution w = pixel_weight * alpha * T on
+    """tn_splat_raster_contrib over the projected and binned frame in `ws`: every Gaussian's ray contribution w = pixel_weight * alpha * T on
     `chain` (0: the RGB chain, 1: the thermal chain of a separate-mode frame) accumulated in place into max_acc [N] fp32, sum_acc [N] fp64,
     hits_acc [N] int64 and views_acc [N] int32.  pixel_weight: [H,W] fp32, non-negative, or None for 1.  The pair records' scratch is this call's."""
     if pixel_weight is not None and tuple(pixel_weight.shape) != (int(cam.height), int(cam.width)):
@@ -158,56 +141,38 @@ def raster_contrib(cam, N, ws, cap, aa, chain, pixel_weight, max_acc, sum_acc, h
     for name, t in (("max_acc", max_acc), ("sum_acc", sum_acc), ("hits_acc", hits_acc), ("views_acc", views_acc)):
         if tuple(t.shape) != (N,):
             raise ValueError(f"raster_contrib: {name} must be [{N}], got {tuple(t.shape)}")
-    scratch = workspace("tn_contrib_splat_workspace_bytes", N, cap, device=max_acc.device)
-    _call("tn_contrib_splat_raster", C.byref(cam), N, _raw(ws), cap, int(aa), int(chain), _ptr(pixel_weight, F32, "pixel_weight"), _raw(scratch), scratch.numel(),
+    scratch = workspace("tn_splat_contrib_workspace_bytes", N, cap, device=max_acc.device)
+    _call("tn_splat_raster_contrib", C.byref(cam), N, _raw(ws), cap, int(aa), int(chain), _ptr(pixel_weight, F32, "pixel_weight"), _raw(scratch), scratch.numel(),
           _ptr(max_acc, F32, "max_acc"), _ptr(sum_acc, torch.float64, "sum_acc"), _ptr(hits_acc, torch.int64, "hits_acc"), _ptr(views_acc, I32, "views_acc"))
 
 
 def raster_backward(cam, N, ws, cap, total, bg4, final_t, last, conics, v_rgbt, v_alpha, v_xys, v_conics, v_colors, v_lnop, final_t_th=None, last_th=None,
                     v_alpha_th=None, v_lnop_th=None, v_xys_abs=None, aa=0, depth=None, v_depth=None, v_depths=None) -> None:
-    """tn_splat_raster_backward over the training frame's workspace `ws`: _sep with the thermal chain's four tensors, _abs with `v_xys_abs`.  With
-    `v_depth` (dL / d depth [H,W,1]; then also `depth`, the forward's normalised image, `v_depths` [N] to fill, and the frame's `aa` flag) it is
-    tn_depth_splat_raster_backward, which takes the thermal chain's tensors and `v_xys_abs` as nullable pointers.  The backward's own workspace is
-    this call's."""
-    sep, absgrad = final_t_th is not None, v_xys_abs is not None
-    if v_depth is not None:
-        bws = workspace("tn_splat_depth_backward_workspace_bytes", N, cap, int(sep), int(absgrad), device=v_xys.device)
-        _call("tn_depth_splat_raster_backward", C.byref(cam), N, _raw(ws), cap, total, bg4, int(aa), *_f32(transmittance=final_t), _ptr(last, I32, "last"),
-              *_f32(transmittance_thermal=final_t_th), _ptr(last_th, I32, "last_thermal"), *_f32(conics=conics, v_rgbt=v_rgbt, v_alpha=v_alpha,
-                                                                                              v_alpha_thermal=v_alpha_th), _raw(bws), bws.numel(),
-              *_f32(v_xys=v_xys, v_xys_abs=v_xys_abs, v_conics=v_conics, v_colors=v_colors, v_log_opacity=v_lnop, v_log_opacity_thermal=v_lnop_th, depth=depth,
-                    v_depth=v_depth, v_depths=v_depths))
-        return
-    bws = workspace(entry("tn_splat_backward_workspace_bytes", abs=absgrad, sep=sep), N, cap, device=v_xys.device)
-    _call(entry("tn_splat_raster_backward", abs=absgrad, sep=sep), C.byref(cam), N, _raw(ws), cap, total, bg4, *_f32(transmittance=final_t),
-          _ptr(last, I32, "last"), *(_f32(transmittance_thermal=final_t_th) + [_ptr(last_th, I32, "last_thermal")] if sep else []),
-          *_f32(conics=conics, v_rgbt=v_rgbt, v_alpha=v_alpha), *(_f32(v_alpha_thermal=v_alpha_th) if sep else []), _raw(bws), bws.numel(),
-          *_f32(v_xys=v_xys), *(_f32(v_xys_abs=v_xys_abs) if absgrad else []), *_f32(v_conics=v_conics, v_colors=v_colors, v_log_opacity=v_lnop),
-          *(_f32(v_log_opacity_thermal=v_lnop_th) if sep else []))
+    """tn_splat_raster_backward over the training frame's workspace `ws`.  Optional groups: the thermal chain's four tensors (`final_t_th`, `last_th`,
+    `v_alpha_th`, `v_lnop_th`), `v_xys_abs` (absgrad), and the depth gradient -- `v_depth` (dL / d depth [H,W,1]) with `depth`, the forward's
+    normalised image, and `v_depths` [N] to fill; `aa` is the frame's flag.  The backward's own workspace is this call's."""
+    bws = workspace("tn_splat_backward_workspace_bytes", N, cap, int(final_t_th is not None), int(v_xys_abs is not None), int(v_depth is not None), device=v_xys.device)
+    _call("tn_splat_raster_backward", C.byref(cam), N, _raw(ws), cap, total, bg4, int(aa), *_f32(transmittance=final_t), _ptr(last, I32, "last"),
+          *_f32(transmittance_thermal=final_t_th), _ptr(last_th, I32, "last_thermal"), *_f32(conics=conics, v_rgbt=v_rgbt, v_alpha=v_alpha, v_alpha_thermal=v_alpha_th),
+          _raw(bws), bws.numel(), *_f32(v_xys=v_xys, v_xys_abs=v_xys_abs, v_conics=v_conics, v_colors=v_colors, v_log_opacity=v_lnop, v_log_opacity_thermal=v_lnop_th,
+                                        depth=depth, v_depth=v_depth, v_depths=v_depths))
 
 
 def project_backward(cam, params, deg, aa, radii, v_xys, v_conics, v_colors, v_lnop, grads, v_lnop_th=None, pose_rec=None, pose=None, row=None,
                      g_pose=None, dview=None, v_depths=None) -> None:
-    """tn_splat_project_backward: fills `grads` (laid out as `params`; _sep with nine of each and `v_lnop_th`).  With `pose_rec` the pose
-    instantiation (tn_splat_project_backward_pose / _pose_sep), which reads the corrected camera and row `row` of `pose` [C,6], adds dL/d pose into
-    that row of `g_pose` through its finishing kernel and leaves dL/d view' in `dview` [3,4].  With `v_depths` (dL / d depths [N], what the depth raster
-    backward left) it is tn_depth_splat_project_backward, which takes the pose group and the thermal opacities as nullable pointers.  The partials'
-    workspace is this call's own."""
-    N, sep, posed = params[0].shape[0], len(params) == 9, pose_rec is not None
-    head = tail = []
-    if posed:
+    """tn_splat_project_backward: fills `grads` (laid out as `params`; nine of each and `v_lnop_th` with the separate thermal opacity).  With
+    `pose_rec` the pose group: the kernel reads the corrected camera and row `row` of `pose` [C,6], adds dL/d pose into that row of `g_pose`
+    through its finishing kernel and leaves dL/d view' in `dview` [3,4]; the partials' workspace is this call's own.  With `v_depths` (dL / d depths
+    [N], what the depth raster backward left) the depth gradient."""
+    N = params[0].shape[0]
+    head, tail = [None, None], [None, 0, None, None]
+    if pose_rec is not None:
         pws = workspace("tn_splat_pose_workspace_bytes", N, device=pose.device, what="bad Gaussian count")
         head = [_ptr(pose_rec, F32, "pose camera"), _pose_row_ptr(pose, row)]
         tail = [_raw(pws), pws.numel(), _pose_row_ptr(g_pose, row, "grad_pose"), *_f32(dview=dview)]
-    if v_depths is not None:  # fixed argument list: null pose group / thermal pointers where the frame has none
-        pp, gg = _param_ptrs(params) + [None] * (9 - len(params)), _param_ptrs(grads) + [None] * (9 - len(grads))
-        _call("tn_depth_splat_project_backward", C.byref(cam), *(head or [None, None]), *pp, N, params[5].shape[1], deg, aa, _ptr(radii, I32, "radii"),
-              *_f32(v_xys=v_xys, v_conics=v_conics, v_colors=v_colors, v_log_opacity=v_lnop, v_log_opacity_thermal=v_lnop_th, v_depths=v_depths), *gg,
-              *(tail or [None, 0, None, None]))
-        return
-    _call(entry("tn_splat_project_backward", pose=posed, sep=sep), C.byref(cam), *head, *_param_ptrs(params), N, params[5].shape[1], deg, aa,
-          _ptr(radii, I32, "radii"), *_f32(v_xys=v_xys, v_conics=v_conics, v_colors=v_colors, v_log_opacity=v_lnop),
-          *(_f32(v_log_opacity_thermal=v_lnop_th) if sep else []), *_param_ptrs(grads), *tail)
+    _call("tn_splat_project_backward", C.byref(cam), *head, *_param_ptrs9(params), N, params[5].shape[1], deg, aa, _ptr(radii, I32, "radii"),
+          *_f32(v_xys=v_xys, v_conics=v_conics, v_colors=v_colors, v_log_opacity=v_lnop, v_log_opacity_thermal=v_lnop_th, v_depths=v_depths),
+          *_param_ptrs9(grads), *tail)
 
 
 def pose_camera(cam, p00, p11, pose, row, rec) -> None:
@@ -280,29 +245,28 @@ def grad_stats(xys_grad, radii, N, max_size, first, grad_norm_sum, vis_counts, m
 
 
 def refine_plan(rs, step, scales, opacities, stats, N, S, counts, opacities_thermal=None) -> Tensor:
-    """tn_splat_refine_plan (_sep with `opacities_thermal`): classify every Gaussian from `stats` = (grad_norm_sum, vis_counts, max_2d_size) and
+    """tn_splat_refine_plan (the both-below cull rule with `opacities_thermal`): classify every Gaussian from `stats` = (grad_norm_sum, vis_counts, max_2d_size) and
     leave (n_split, n_orig, n_child, n_dup) in `counts`, a host (c_int64 * 4): one host synchronisation.  Returns the workspace with the plan for
     S split samples, which refine_apply reads."""
-    sep = opacities_thermal is not None
     ws = workspace("tn_splat_refine_workspace_bytes", N, S, device=scales.device)
-    _call(entry("tn_splat_refine_plan", sep=sep), C.byref(rs), int(step), *_f32(scales=scales, opacities=opacities.reshape(-1)),
-          *(_f32(opacities_thermal=opacities_thermal.reshape(-1)) if sep else []),
+    _call("tn_splat_refine_plan", C.byref(rs), int(step), *_f32(scales=scales, opacities=opacities.reshape(-1)),
+          *_f32(opacities_thermal=None if opacities_thermal is None else opacities_thermal.reshape(-1)),
           *_f32(grad_norm_sum=stats[0], vis_counts=stats[1], max_2d_size=stats[2]), N, _raw(ws), ws.numel(), counts)
     return ws
 
 
 def refine_apply(rs, N, K, ws, counts, noise, old, exp_avg, exp_avg_sq, new, new_exp_avg, new_exp_avg_sq) -> None:
-    """tn_splat_refine_apply (_sep with nine tensors per list): gather / split / duplicate `old` and its Adam moments into `new` and theirs by the
+    """tn_splat_refine_apply (eight or nine tensors per list): gather / split / duplicate `old` and its Adam moments into `new` and theirs by the
     plan in `ws`.  Each list holds a tensor or None per parameter; None and empty tensors go in as null."""
     arr = lambda ts: (C.c_void_p * len(old))(*[t.data_ptr() if t is not None and t.numel() else None for t in ts])  # noqa: E731
-    _call(entry("tn_splat_refine_apply", sep=len(old) == 9), C.byref(rs), N, K, _raw(ws), ws.numel(), counts,
-          *_f32(noise=noise if noise is not None and noise.numel() else None), arr(old), arr(exp_avg), arr(exp_avg_sq), arr(new), arr(new_exp_avg),
+    _call("tn_splat_refine_apply", C.byref(rs), N, K, _raw(ws), ws.numel(), counts,
+          *_f32(noise=noise if noise is not None and noise.numel() else None), len(old), arr(old), arr(exp_avg), arr(exp_avg_sq), arr(new), arr(new_exp_avg),
           arr(new_exp_avg_sq))
 
 
 def mcmc_relocate(params: List[Tensor], exp_avg: List[Optional[Tensor]], exp_avg_sq: List[Optional[Tensor]], src_idx: Tensor, dst_idx: Tensor,
                   min_opacity: float) -> None:
-    """tn_splat_mcmc_relocate / _sep in place on the current stream, without a host synchronisation.  params: the 8 (9: separate thermal opacity)
+    """tn_splat_mcmc_relocate in place on the current stream, without a host synchronisation.  params: the 8 (9: separate thermal opacity)
     gauss_params tensors in param_names order, contiguous fp32 on the device, all with the same number of rows; exp_avg / exp_avg_sq: per tensor
     its Adam moments or None (both); src_idx / dst_idx: int64 [M] on the device.  Row dst_idx[j] becomes a copy of row src_idx[j] with gsplat's
     relocation opacity and scale (ratio = 1 + how often the source was drawn, capped at 51; evaluated in double), every drawn source takes that
@@ -328,21 +292,21 @@ def mcmc_relocate(params: List[Tensor], exp_avg: List[Optional[Tensor]], exp_avg
         return (C.c_void_p * len(params))(*[_ptr(t, F32, what).value if t is not None and p is not None else None for t, p in zip(ts, pp)])
 
     ws = workspace("tn_splat_mcmc_workspace_bytes", rows, M, device=params[0].device)
-    _call(entry("tn_splat_mcmc_relocate", sep=len(params) == 9), rows, K, _ptr(src_idx, torch.int64, "src_idx"), _ptr(dst_idx, torch.int64, "dst_idx"), M,
-          float(min_opacity), arr(params, "params"), arr(exp_avg, "exp_avg"), arr(exp_avg_sq, "exp_avg_sq"), _raw(ws), ws.numel())
+    _call("tn_splat_mcmc_relocate", rows, K, _ptr(src_idx, torch.int64, "src_idx"), _ptr(dst_idx, torch.int64, "dst_idx"), M,
+          float(min_opacity), len(params), arr(params, "params"), arr(exp_avg, "exp_avg"), arr(exp_avg_sq, "exp_avg_sq"), _raw(ws), ws.numel())
 
 
 def mcmc_noise(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor, randn: Tensor, scaler: float,
                opacities_thermal: Optional[Tensor] = None) -> None:
-    """tn_splat_mcmc_noise / _sep: means [N,3] += Sigma (randn * g * scaler) in place, one launch on the current stream, fp32.  Sigma =
+    """tn_splat_mcmc_noise: means [N,3] += Sigma (randn * g * scaler) in place, one launch on the current stream, fp32.  Sigma =
     R diag(exp(scales)^2) R^T with R the rotation of quats / |quats|; g = 1 / (1 + exp(-100 ((1 - o_vis) - 0.995))), o_vis = sigmoid(opacities)
     or, with opacities_thermal, the larger of the two sigmoids: a Gaussian anyone can see stays where it is.  Contiguous fp32 device tensors."""
     N, sep = means.shape[0], opacities_thermal is not None
     if means.shape != (N, 3) or scales.shape != (N, 3) or quats.shape != (N, 4) or randn.shape != (N, 3) or opacities.numel() != N or \
             (sep and opacities_thermal.numel() != N):
         raise ValueError("mcmc_noise: means, scales, randn [N,3], quats [N,4], opacities [N,1] of one N expected")
-    _call(entry("tn_splat_mcmc_noise", sep=sep), *_f32(means=means, scales=scales, quats=quats, opacities=opacities.reshape(-1)),
-          *(_f32(opacities_thermal=opacities_thermal.reshape(-1)) if sep else []), *_f32(randn=randn), N, float(scaler))
+    _call("tn_splat_mcmc_noise", *_f32(means=means, scales=scales, quats=quats, opacities=opacities.reshape(-1),
+                                       opacities_thermal=opacities_thermal.reshape(-1) if sep else None, randn=randn), N, float(scaler))
 
 
 # ---------------------------------------------------------------------------------------------------- seeding and the image kernels

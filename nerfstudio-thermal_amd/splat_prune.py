@@ -4,7 +4,7 @@ Opacity is a poor proxy for importance: an opaque Gaussian buried behind a wall 
 all a pixel shows, and a Gaussian may matter only to the quarter-resolution thermal frames.  RadSplat ("RadSplat: Radiance Field-Informed Gaussian
 Splatting", section 4.2) scores a Gaussian by the maximum over all training rays of its blending weight alpha T and prunes below 0.01; LightGaussian
 uses the hit-weighted sum.  `score_gaussians` computes both, and the hit and view counts, in one walk per training frame
-(tn_contrib_splat_raster: the forward rasteriser's walk reduced per Gaussian instead of per pixel, without atomics, accumulated on the device),
+(tn_splat_raster_contrib: the forward rasteriser's walk reduced per Gaussian instead of per pixel, without atomics, accumulated on the device),
 per spectrum: an RGB frame is walked on the chain its loss trains, a thermal frame of a separate-mode model on the thermal chain.
 `prune_mask` turns the scores into a keep mask (a threshold on the importance, or a ratio to keep), `prune_gaussians` removes the others from the
 model and from every optimiser, Adam moments and step counts carried along.

@@ -9,7 +9,7 @@ splat file (--load), and write `splat.ply` in the Inria layout every splat viewe
                                             [--prune-min-contribution X | --prune-keep-ratio R]
 
 --prune-min-contribution X (RadSplat's rule; 0.01 is its value) or --prune-keep-ratio R scores every Gaussian of the in-memory model by its ray
-contribution over the dataset's training cameras of both spectra (splat_prune.score_gaussians: tn_contrib_splat_raster) and removes the others
+contribution over the dataset's training cameras of both spectra (splat_prune.score_gaussians: tn_splat_raster_contrib) and removes the others
 before the export; opacity (--min-opacity) says little about what a Gaussian adds to any frame.  Needs a dataset, as the frame options do.
 --spectrum both (the default) writes the colour scene under the Inria property names followed by f_dc_thermal, f_rest_thermal_* and, in separate
 mode, opacity_thermal: viewers ignore the extras, splat_io.load_gaussian_ply reads them back (bit for bit for --sh-degree > 0).  --spectrum thermal

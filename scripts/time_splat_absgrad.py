@@ -1,8 +1,8 @@
 """The raster backward with and without the absgrad statistic at the benchmark's splat shape (1 M synthetic Gaussians, 1920 x 1080, degree-3 SH,
-classic, shared opacity; SPLAT_SEP=1: separate): device time of one tn_splat_raster_backward / _sep call (memset of the pair records,
-k_splat_run_start, k_splat_raster_bwd, k_splat_pair_fold) against tn_splat_raster_backward_abs / _abs_sep on the same frame.  The projection
-backward behind it is the same call either way and is not timed.  --parent-lib names a build of the parent commit's library: its
-tn_splat_raster_backward is timed in the same loop on the same workspace (the off path before this feature).
+classic, shared opacity; SPLAT_SEP=1: separate): device time of one tn_splat_raster_backward call without v_xys_abs (memset of the pair records,
+k_splat_run_start, k_splat_raster_bwd, k_splat_pair_fold) against the call with v_xys_abs on the same frame.  The projection
+backward behind it is the same call either way and is not timed.  --parent-lib names another build of the library with the same ABI (an earlier
+commit's): its tn_splat_raster_backward without v_xys_abs is timed in the same loop on the same workspace.
 HIP events on torch's current stream; 4 back-to-back calls per timed window, the variants alternated inside an iteration; every figure is the
 median of SPLAT_ITERS iterations after warm-up, the whole measurement repeated SPLAT_REPEATS times and reported as [min, median, max] of those
 medians (the in-process spread; run the script again for the process-to-process one).  The upstream images are random.  Also checks that the off
@@ -34,13 +34,12 @@ BATCH = 4
 H, W = 1080, 1920
 dev = "cuda"
 i32 = torch.int32
-sfx = "_sep" if sep else ""
 
 lib = _lib.load()
 parent = None
 if args.parent_lib:
     parent = C.CDLL(os.path.abspath(args.parent_lib))
-    name = "tn_splat_raster_backward" + sfx
+    name = "tn_splat_raster_backward"  # (a build with the same ABI)
     getattr(parent, name).restype, getattr(parent, name).argtypes = _lib.SIGNATURES[name]
 
 cam = PinholeCamera(synth.look_at_camera((3.2, 0.5, 0.8)), 1400.0, 1400.0, 960.0, 540.0, W, H)
@@ -58,18 +57,17 @@ bg4 = (C.c_float * 4)(0.0, 0.0, 0.0, 0.0)
 proj, ws, cap, total = splat._project_and_bin(m, cs, params, H, W, 3, 0, 1 << 22, m._new_workspace)
 rgbt, depth, alpha = torch.empty((H, W, 4), device=dev), torch.empty((H, W, 1), device=dev), torch.empty((H, W, 1), device=dev)
 final_t, last = torch.empty((H, W), device=dev), torch.empty((H, W), dtype=i32, device=dev)
+alpha_th = final_t_th = last_th = None  # the thermal chain's three: separate mode only
 if sep:
     alpha_th, final_t_th, last_th = torch.empty((H, W, 1), device=dev), torch.empty((H, W), device=dev), torch.empty((H, W), dtype=i32, device=dev)
-    _lib.check(lib.tn_splat_raster_train_sep(C.byref(cs), N, ptr(ws), cap, bg4, 0, ptr(rgbt), ptr(depth), ptr(alpha), ptr(alpha_th), ptr(final_t), ptr(last),
-                                             ptr(final_t_th), ptr(last_th), _stream()), "tn_splat_raster_train_sep")
-else:
-    _lib.check(lib.tn_splat_raster_train(C.byref(cs), N, ptr(ws), cap, bg4, 0, ptr(rgbt), ptr(depth), ptr(alpha), ptr(final_t), ptr(last), _stream()),
-               "tn_splat_raster_train")
+opt = lambda t: None if t is None else ptr(t)  # noqa: E731
+_lib.check(lib.tn_splat_raster_chains(C.byref(cs), N, ptr(ws), cap, bg4, 0, ptr(rgbt), ptr(depth), ptr(alpha), opt(alpha_th), ptr(final_t), ptr(last), opt(final_t_th),
+                                      opt(last_th), _stream()), "tn_splat_raster_chains")
 gen = torch.Generator(device=dev).manual_seed(3)
 v_rgbt = torch.randn((H, W, 4), device=dev, generator=gen)
 v_alpha = torch.randn((H, W, 1), device=dev, generator=gen)
 v_alpha_th = torch.randn((H, W, 1), device=dev, generator=gen)
-need = {v: int(getattr(lib, "tn_splat_backward_workspace_bytes" + ("_abs" if v == "abs" else "") + sfx)(N, cap)) for v in ("off", "abs")}
+need = {v: int(lib.tn_splat_backward_workspace_bytes(N, cap, int(sep), int(v == "abs"), 0)) for v in ("off", "abs")}
 bws = torch.empty(need["abs"], dtype=torch.uint8, device=dev)
 variants = (["parent"] if parent is not None else []) + ["off", "abs"]
 outs = {v: {"xys": torch.empty((N, 2), device=dev), "xys_abs": torch.empty((N, 2), device=dev), "conics": torch.empty((N, 3), device=dev),
@@ -78,13 +76,11 @@ outs = {v: {"xys": torch.empty((N, 2), device=dev), "xys_abs": torch.empty((N, 2
 
 def backward(v):
     o = outs[v]
-    fn = getattr(parent if v == "parent" else lib, "tn_splat_raster_backward" + ("_abs" if v == "abs" else "") + sfx)
-    chain = [ptr(final_t), ptr(last)] + ([ptr(final_t_th), ptr(last_th)] if sep else [])
-    up = [ptr(v_rgbt), ptr(v_alpha)] + ([ptr(v_alpha_th)] if sep else [])
-    xys = [ptr(o["xys"])] + ([ptr(o["xys_abs"])] if v == "abs" else [])
-    tail = [ptr(o["conics"]), ptr(o["colors"]), ptr(o["lnop"])] + ([ptr(o["lnop_th"])] if sep else [])
-    _lib.check(fn(C.byref(cs), N, ptr(ws), cap, total, bg4, *chain, ptr(proj["conics"]), *up, ptr(bws), need["off" if v == "parent" else v], *xys, *tail,
-                  _stream()), "raster backward " + v)
+    fn = (parent if v == "parent" else lib).tn_splat_raster_backward
+    th = lambda t: ptr(t) if sep else None  # noqa: E731  (the thermal chain's group: all four or none)
+    _lib.check(fn(C.byref(cs), N, ptr(ws), cap, total, bg4, 0, ptr(final_t), ptr(last), opt(final_t_th), opt(last_th), ptr(proj["conics"]), ptr(v_rgbt), ptr(v_alpha),
+                  th(v_alpha_th), ptr(bws), need["off" if v == "parent" else v], ptr(o["xys"]), ptr(o["xys_abs"]) if v == "abs" else None, ptr(o["conics"]), ptr(o["colors"]),
+                  ptr(o["lnop"]), th(o["lnop_th"]), None, None, None, _stream()), "raster backward " + v)
 
 
 def timed(fn):

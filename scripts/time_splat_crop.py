@@ -107,19 +107,15 @@ for order in ("random", "morton"):
     # the launches alone, on the eval workspace and the projection tensors the last frame left
     cs, ws, cap = camera_struct(cam), m._ws, m._cap
     proj = m.last_projection
-    pp = splat_calls._param_ptrs([m.gauss_params[k] for k in m.param_names])
+    pp = splat_calls._param_ptrs9([m.gauss_params[k] for k in m.param_names])  # the thermal opacity's place is null in shared mode
     K = m.gauss_params["features_rest"].shape[1]
     outs = [ptr(proj[k]) for k in ("xys", "depths", "radii", "conics", "compensation", "num_tiles_hit", "tile_box")]
     total = C.c_int64(0)
     aa, deg = m._frame_settings()  # what the model's own frames pass
 
     def project(box):
-        if box is None:
-            fn = lib.tn_splat_project_sep if sep else lib.tn_splat_project
-            return lambda: _lib.check(fn(C.byref(cs), *pp, N, K, deg, aa, *outs, ptr(ws), cap, _stream()))
-        crop = box.crop_struct()
-        fn = lib.tn_splat_project_crop_sep if sep else lib.tn_splat_project_crop
-        return lambda: _lib.check(fn(C.byref(cs), *pp, N, K, deg, aa, *outs, ptr(ws), cap, C.byref(crop), _stream()))
+        crop = box.crop_struct() if box is not None else None  # a null box is the uncropped frame
+        return lambda: _lib.check(lib.tn_splat_project(C.byref(cs), None, *pp, N, K, deg, aa, *outs, ptr(ws), cap, C.byref(crop) if crop is not None else None, _stream()))
 
     def binning():
         _lib.check(lib.tn_splat_bin(C.byref(cs), outs[1], N, ptr(ws), cap, C.byref(total), _stream()))

@@ -1,8 +1,8 @@
 """The splat backward with and without a depth upstream at the benchmark's splat shape (1 M synthetic Gaussians, 1920 x 1080, degree-3 SH, classic,
 shared opacity; SPLAT_SEP=1: separate; SPLAT_ABS=1: with the absgrad statistic): device time of the raster backward (memset of the pair records,
-k_splat_run_start, k_splat_raster_bwd, k_splat_pair_fold) plus the projection backward through splat_calls -- `off`, the entry points a loss
-without depth runs, against `depth`, tn_depth_splat_raster_backward + tn_depth_splat_project_backward on the same frame.  --parent-lib names a build
-of the parent commit's library: its backward (`parent`, the off path before this feature) is timed in the same loop on the same workspace.
+k_splat_run_start, k_splat_raster_bwd, k_splat_pair_fold) plus the projection backward through splat_calls -- `off`, what a loss
+without depth runs, against `depth`, tn_splat_raster_backward + tn_splat_project_backward with their depth groups on the same frame.  --parent-lib names
+another build of the library with the same ABI (an earlier commit's): its backward without depth (`parent`) is timed in the same loop on the same workspace.
 HIP events on torch's current stream; 4 back-to-back backwards per timed window, the variants alternated inside an iteration; every figure is the
 median of SPLAT_ITERS iterations after warm-up, the whole measurement repeated SPLAT_REPEATS times and reported as [min, median, max] of those
 medians (the in-process spread; run the script again for the process-to-process one).  The upstream images are random.  Also checks that the off
@@ -40,10 +40,8 @@ lib = _lib.load()
 parent = None
 if args.parent_lib:
     parent = C.CDLL(os.path.abspath(args.parent_lib))
-    for name in (splat_calls.entry(base, abs=absgrad, sep=sep) for base in ("tn_splat_raster_backward", "tn_splat_backward_workspace_bytes")):
+    for name in ("tn_splat_raster_backward", "tn_splat_backward_workspace_bytes", "tn_splat_project_backward"):
         getattr(parent, name).restype, getattr(parent, name).argtypes = _lib.SIGNATURES[name]
-    name = splat_calls.entry("tn_splat_project_backward", sep=sep)
-    getattr(parent, name).restype, getattr(parent, name).argtypes = _lib.SIGNATURES[name]
     parent.tn_last_error.restype = C.c_char_p
 
 cam = PinholeCamera(synth.look_at_camera((3.2, 0.5, 0.8)), 1400.0, 1400.0, 960.0, 540.0, W, H)
@@ -106,8 +104,7 @@ backward("zero", torch.zeros_like(v_depth))
 torch.cuda.synchronize()
 res = {"gaussians": N, "image": [W, H], "iters": iters, "repeats": repeats, "thermal_opacity_mode": "separate" if sep else "shared", "absgrad": absgrad,
        "visible": int((proj["radii"] > 0).sum()), "pairs": total,
-       "pair_record_bytes": {"off": splat_calls.workspace_bytes(splat_calls.entry("tn_splat_backward_workspace_bytes", abs=absgrad, sep=sep), N, cap),
-                             "depth": splat_calls.workspace_bytes("tn_splat_depth_backward_workspace_bytes", N, cap, int(sep), int(absgrad))}}
+       "pair_record_bytes": {k: splat_calls.workspace_bytes("tn_splat_backward_workspace_bytes", N, cap, int(sep), int(absgrad), d) for k, d in (("off", 0), ("depth", 1))}}
 
 
 def same(a, b):

@@ -1,5 +1,5 @@
 """The MCMC strategy's two device operations at SPLAT_N Gaussians (default 1 M, degree-3 SH; SPLAT_SEP=1: separate thermal opacity):
-  - the position noise of one training step: one tn_splat_mcmc_noise / _sep launch against the same formula in plain torch ops (gsplat's
+  - the position noise of one training step: one tn_splat_mcmc_noise launch against the same formula in plain torch ops (gsplat's
     inject_noise_to_position: covariances [N,3,3], two bmm), both from the same randn draw, which is not timed;
   - one refinement (ThermalSplatfactoModel.refinement_after under strategy "mcmc"): SPLAT_DEAD (default 5 %) of the Gaussians dead, relocated, and
     the population grown by 5 % -- two torch.multinomial draws, the growth of every tensor and both moments by torch.cat, and two

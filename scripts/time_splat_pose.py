@@ -1,10 +1,10 @@
 """The pose instantiations of the splat projection at the benchmark's splat shape (1 M synthetic Gaussians, 1920 x 1080, degree-3 SH, shared
 opacity; SPLAT_SEP=1: separate): device time of
-  * the projection forward launch -- tn_splat_project against tn_splat_pose_camera + tn_splat_project_pose,
-  * the projection backward -- tn_splat_project_backward against tn_splat_project_backward_pose (the kernel with the per-block reduction of
+  * the projection forward launch -- tn_splat_project without a pose record against tn_splat_pose_camera + tn_splat_project with it,
+  * the projection backward -- tn_splat_project_backward without the pose group against the call with it (the kernel with the per-block reduction of
     dL/d view' plus the single-block finishing launch),
-with the row at zero and at a moved pose.  --parent-lib names a build of the parent commit's library: its tn_splat_project /
-tn_splat_project_backward are timed in the same loop (the off path before this feature; the two libraries share the process and the stream).
+with the row at zero and at a moved pose.  --parent-lib names another build of the library with the same ABI (an earlier commit's): its tn_splat_project /
+tn_splat_project_backward without the pose are timed in the same loop (the two libraries share the process and the stream).
 HIP events on torch's current stream; 8 back-to-back calls per timed window, the variants alternated inside an iteration; every figure is the
 median of SPLAT_ITERS iterations after warm-up, the whole measurement repeated SPLAT_REPEATS times and reported as [min, median, max] of those
 medians.  The upstream gradients of the backward are random (its cost does not depend on their values); radii come from the forward.  Also
@@ -41,7 +41,7 @@ lib = _lib.load()
 parent = None
 if args.parent_lib:
     parent = C.CDLL(os.path.abspath(args.parent_lib))
-    for name in ("tn_splat_project", "tn_splat_project_sep", "tn_splat_project_backward", "tn_splat_project_backward_sep"):
+    for name in ("tn_splat_project", "tn_splat_project_backward"):
         getattr(parent, name).restype, getattr(parent, name).argtypes = _lib.SIGNATURES[name]
 
 cam = PinholeCamera(synth.look_at_camera((3.2, 0.5, 0.8)), 1400.0, 1400.0, 960.0, 540.0, W, H, cam_idx=0)
@@ -63,20 +63,19 @@ def outputs():
             torch.empty(N, device=dev), torch.empty(N, dtype=i32, device=dev), torch.empty((N, 4), dtype=i32, device=dev)]
 
 
-pp = splat_calls._param_ptrs(params)
+pp = splat_calls._param_ptrs9(params)  # nine places: the thermal opacity's is null in shared mode
 pose = torch.zeros((2, 6), device=dev)
 pose[1] = torch.tensor([0.02, -0.015, 0.01, 0.012, -0.02, 0.015])
-sfx = "_sep" if sep else ""
 
 
 def forward(which, out):
     o = [ptr(t) for t in out]
     if which in ("off", "parent"):
-        fn = getattr(parent if which == "parent" else lib, "tn_splat_project" + sfx)
-        _lib.check(fn(C.byref(cs), *pp, N, K, deg, aa, *o, ptr(ws), cap, _stream()), "project")
+        fn = (parent if which == "parent" else lib).tn_splat_project
+        _lib.check(fn(C.byref(cs), None, *pp, N, K, deg, aa, *o, ptr(ws), cap, None, _stream()), "project")
         return None
     rec = pose_camera_record(cam, cs, pose, 0 if which == "pose_zero" else 1)
-    _lib.check(getattr(lib, "tn_splat_project_pose" + sfx)(C.byref(cs), ptr(rec), *pp, N, K, deg, aa, *o, ptr(ws), cap, None, _stream()), "project_pose")
+    _lib.check(lib.tn_splat_project(C.byref(cs), ptr(rec), *pp, N, K, deg, aa, *o, ptr(ws), cap, None, _stream()), "project with a pose record")
     return rec
 
 
@@ -84,7 +83,7 @@ gen = torch.Generator(device=dev).manual_seed(3)
 up = [torch.randn((N, 2), device=dev, generator=gen), torch.randn((N, 3), device=dev, generator=gen), torch.randn((N, 4), device=dev, generator=gen),
       torch.randn(N, device=dev, generator=gen)] + ([torch.randn(N, device=dev, generator=gen)] if sep else [])
 grads = [torch.empty_like(t) for t in params]
-gp = splat_calls._param_ptrs(grads)
+gp = splat_calls._param_ptrs9(grads)
 need = int(lib.tn_splat_pose_workspace_bytes(N))
 pws = torch.empty(need, dtype=torch.uint8, device=dev)
 g_pose = torch.zeros((2, 6), device=dev)
@@ -92,15 +91,14 @@ dview = torch.empty((3, 4), device=dev)
 
 
 def backward(which, radii, rec):
-    u = [ptr(t) for t in up]
+    u = [ptr(t) for t in up] + [None] * (5 - len(up)) + [None]  # v_log_opacity_thermal (separate mode only), no v_depths
     if which in ("off", "parent"):
-        fn = getattr(parent if which == "parent" else lib, "tn_splat_project_backward" + sfx)
-        _lib.check(fn(C.byref(cs), *pp, N, K, deg, aa, ptr(radii), *u, *gp, _stream()), "project_backward")
+        fn = (parent if which == "parent" else lib).tn_splat_project_backward
+        _lib.check(fn(C.byref(cs), None, None, *pp, N, K, deg, aa, ptr(radii), *u, *gp, None, 0, None, None, _stream()), "project_backward")
         return
     row = 0 if which == "pose_zero" else 1
-    _lib.check(getattr(lib, "tn_splat_project_backward_pose" + sfx)(C.byref(cs), ptr(rec), C.c_void_p(pose.data_ptr() + 24 * row), *pp, N, K, deg, aa,
-                                                                    ptr(radii), *u, *gp, ptr(pws), need, C.c_void_p(g_pose.data_ptr() + 24 * row), ptr(dview),
-                                                                    _stream()), "project_backward_pose")
+    _lib.check(lib.tn_splat_project_backward(C.byref(cs), ptr(rec), C.c_void_p(pose.data_ptr() + 24 * row), *pp, N, K, deg, aa, ptr(radii), *u, *gp, ptr(pws), need,
+                                             C.c_void_p(g_pose.data_ptr() + 24 * row), ptr(dview), _stream()), "project_backward with the pose group")
 
 
 def timed(fn):

@@ -1,4 +1,4 @@
-"""The ray-contribution pass (tn_contrib_splat_raster: run starts, k_splat_raster_contrib, k_splat_contrib_fold) at the benchmark's splat shape
+"""The ray-contribution pass (tn_splat_raster_contrib: run starts, k_splat_raster_contrib, k_splat_contrib_fold) at the benchmark's splat shape
 (1 M synthetic Gaussians) on a 1920 x 1080 frame, a 640 x 480 frame and a 160 x 120 frame, beside the eval rasteriser (tn_splat_raster) and the
 training rasteriser's backward (tn_splat_raster_backward: k_splat_raster_bwd + k_splat_pair_fold) on the same projected and binned frame, the three
 alternated in one loop so that all see the same machine state.  HIP events on torch's current stream (the stream the library launches on), medians

@@ -1,6 +1,6 @@
 """The removal renders of the separate thermal opacity at the benchmark's splat shape (1 M synthetic Gaussians, 1920 x 1080): device time of the
 eval frame (get_outputs) with removal off and with removal on, alternated, and of the two rasteriser launches alone on the frame's own workspace
--- tn_splat_raster_sep (the yardstick: three chains in classic mode, four in antialiased) and tn_splat_raster_removal_sep (two chains, no depth)
+-- tn_splat_raster_chains with out_alpha_thermal alone (the separate-mode eval raster, the yardstick: three chains in classic mode, four in antialiased) and tn_splat_raster_removal_sep (two chains, no depth)
 -- alternated as well.  HIP events on torch's current stream (the stream the library launches on), medians and minima over SPLAT_ITERS
 iterations after warm-up.  opacities_thermal = opacities + SPLAT_NOISE * randn on the logits (default 0.08; the line reports the share each render
 keeps); SPLAT_THR = removal_min_opacity_diff (0.05; 1e30 keeps everything, the launch's worst case).  One JSON line.
@@ -62,7 +62,7 @@ rgbt, rem = torch.empty((H, W, 4), device="cuda"), torch.empty((H, W, 4), device
 depth, alpha, alpha_th = (torch.empty((H, W, 1), device="cuda") for _ in range(3))
 ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
 launches = {
-    "raster_sep_launch": lambda: _lib.check(lib.tn_splat_raster_sep(C.byref(cs), N, ptr(ws), cap, bg, aa, ptr(rgbt), ptr(depth), ptr(alpha), ptr(alpha_th), _stream())),
+    "raster_sep_launch": lambda: _lib.check(lib.tn_splat_raster_chains(C.byref(cs), N, ptr(ws), cap, bg, aa, ptr(rgbt), ptr(depth), ptr(alpha), ptr(alpha_th), None, None, None, None, _stream())),
     "raster_removal_launch": lambda: _lib.check(lib.tn_splat_raster_removal_sep(C.byref(cs), N, ptr(ws), cap, bg, thr, ptr(rem), _stream())),
 }
 res = {}

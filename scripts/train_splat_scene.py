@@ -34,7 +34,7 @@ the trained Gaussians as a Gaussian-splat PLY (splat_io.export_gaussian_ply: spe
 those with a parameter that is not finite dropped); the line reports how many went out.  --export-world-frame writes that file in the dataset's own
 frame (splat_transform.dataset_frame), where the point-cloud and mesh exports put theirs; the generated scene's dataparser transform is the identity,
 so there it is the model's frame too and the line says so.  --prune-at STEP ... prunes by ray contribution at those steps (splat_prune.py: every
-Gaussian scored over the training cameras of both spectra by its largest blending weight alpha T, tn_contrib_splat_raster; those below
+Gaussian scored over the training cameras of both spectra by its largest blending weight alpha T, tn_splat_raster_contrib; those below
 --prune-min-contribution, RadSplat's 0.01 by default, are removed); the steps lie after --stop-split-at and are multiples of --refine-every, and the
 line lists each prune's count.  --prune-observe scores the val split again after pruning the trained model at 0.01 and at keep ratios 0.5 and 0.25,
 without fine-tuning, and puts the Gaussians back."""

@@ -1,4 +1,4 @@
-"""Float64 restatement of the crop box of the splat eval render (OrientedBox / tn_splat_project_crop / tn_splat_crop_mask), and the scenes of
+"""Float64 restatement of the crop box of the splat eval render (OrientedBox / tn_splat_project's crop / tn_splat_crop_mask), and the scenes of
 the crop tests.  Plain torch, no import of the package: a box is anything with R [3,3], T [3] and S [3] (`Box` here, OrientedBox there).
 
 The rule (nerfstudio/data/scene_box.py:82-114): box -> world is p = R q + T; a point is inside iff -S_i/2 < q_i < S_i/2 on all three axes,

@@ -111,7 +111,7 @@ def test_cloud_remove_outliers_view_arguments_are_refused_before_any_launch(lib)
 
 def test_header_and_binding_agree_and_the_abi_version_stays(lib):
     hdr = open(os.path.join(ROOT, "include", "thermal_nerf_hip.h"), encoding="utf-8").read()
-    assert _lib.ABI_VERSION == 313 and lib.tn_version() == 313
+    assert _lib.ABI_VERSION == 314 and lib.tn_version() == 314
     new = ("tn_cloud_normals_workspace_bytes", "tn_cloud_estimate_normals", "tn_cloud_append_view", "tn_cloud_remove_outliers_view")
     for name in new:
         decl = re.search(r"TN_API\s+\w+\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)

@@ -158,7 +158,7 @@ def test_every_entry_point_refuses_bad_arguments_before_any_launch(lib):
 def test_header_binding_and_kernel_constants_agree(lib):
     hdr = open(os.path.join(ROOT, "include", "thermal_nerf_hip.h"), encoding="utf-8").read()
     src = open(os.path.join(ROOT, "nerfstudio-thermal_amd", "csrc", "tn_poisson.hip"), encoding="utf-8").read()
-    assert _lib.ABI_VERSION == 313 and lib.tn_version() == 313  # additions only: the version stays
+    assert _lib.ABI_VERSION == 314 and lib.tn_version() == 314  # additions only: the version stays
     names = ("tn_poisson_workspace_bytes", "tn_poisson_bin", "tn_poisson_splat", "tn_poisson_sample", "tn_poisson_divergence", "tn_poisson_apply",
              "tn_poisson_solve_workspace_bytes", "tn_poisson_solve")
     for name in names:

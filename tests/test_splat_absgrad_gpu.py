@@ -1,5 +1,5 @@
 """The absgrad densification statistic on the GPU (ThermalSplatfactoModelConfig.use_absgrad: the ABS instantiations of k_splat_raster_bwd and
-k_splat_pair_fold behind tn_splat_raster_backward_abs / _abs_sep, through ThermalSplatfactoModel.get_train_outputs and .backward()) against the
+k_splat_pair_fold behind tn_splat_raster_backward with v_xys_abs, through ThermalSplatfactoModel.get_train_outputs and .backward()) against the
 float64 walk of tests/splat_absgrad_functional.py, on scenes of tests/splat_backward_cases.py:
 
   deep-classic-3                  four 256-record batches with a partial front batch

@@ -9,6 +9,7 @@ import torch
 import nerfstudio_thermal_amd  # noqa: F401
 from nerfstudio_thermal_amd import _lib
 
+import splat_abi
 import splat_functional as sf
 import splat_oracle as so
 
@@ -31,10 +32,15 @@ def _camera(W=64, H=48):
 
 
 def test_backward_workspace_size(lib):
-    assert lib.tn_splat_backward_workspace_bytes(-1, 10) == -1
-    assert lib.tn_splat_backward_workspace_bytes(10, -1) == -1
-    small, big = lib.tn_splat_backward_workspace_bytes(100, 1000), lib.tn_splat_backward_workspace_bytes(100, 2000)
+    size = lib.tn_splat_backward_workspace_bytes
+    assert size(-1, 10, 0, 0, 0) == -1
+    assert size(10, -1, 0, 0, 0) == -1
+    small, big = size(100, 1000, 0, 0, 0), size(100, 2000, 0, 0, 0)
     assert 0 < small < big and big - small >= 1000 * 10 * 4 - 256  # one record of 10 floats per (Gaussian, tile) pair (256-byte aligned)
+    # every combination of the groups asks for exactly what its own size function used to
+    assert {flags: (size(10, 100, *flags), size(1000, 5000, *flags)) for flags in splat_abi.BACKWARD_WORKSPACE_BYTES} == splat_abi.BACKWARD_WORKSPACE_BYTES
+    for flags in splat_abi.BACKWARD_WORKSPACE_BYTES:
+        assert size(-1, 5, *flags) == -1 and size(5, -1, *flags) == -1
 
 
 def test_raster_train_argument_validation(lib):
@@ -42,22 +48,23 @@ def test_raster_train_argument_validation(lib):
     bad.width = 0
     bg = (C.c_float * 4)()
     d = C.c_void_p(256)  # never dereferenced: every call below is refused before anything is read or launched
-    assert lib.tn_splat_raster_train(None, 10, d, 100, bg, 0, d, d, d, d, d, None) == EINVAL
-    assert lib.tn_splat_raster_train(C.byref(bad), 10, d, 100, bg, 0, d, d, d, d, d, None) == EINVAL
-    assert lib.tn_splat_raster_train(C.byref(cam), 10, d, 100, bg, 0, d, d, d, None, d, None) == EINVAL
+    train = lambda camera, n, out_t, out_last: lib.tn_splat_raster_chains(camera, n, d, 100, bg, 0, d, d, d, None, out_t, out_last, None, None, None)  # noqa: E731
+    assert train(None, 10, d, d) == EINVAL
+    assert train(C.byref(bad), 10, d, d) == EINVAL
+    assert train(C.byref(cam), 10, None, d) == EINVAL
     assert b"null pointer" in lib.tn_last_error()
-    assert lib.tn_splat_raster_train(C.byref(cam), 10, d, 100, bg, 0, d, d, d, d, None, None) == EINVAL
-    assert lib.tn_splat_raster_train(C.byref(cam), -1, d, 100, bg, 0, d, d, d, d, d, None) == EINVAL
+    assert train(C.byref(cam), 10, d, None) == EINVAL
+    assert train(C.byref(cam), -1, d, d) == EINVAL
 
 
 def test_raster_backward_argument_validation(lib):
     cam = _camera()
     bg = (C.c_float * 4)()
     d = C.c_void_p(256)
-    need = lib.tn_splat_backward_workspace_bytes(10, 100)
+    need = lib.tn_splat_backward_workspace_bytes(10, 100, 0, 0, 0)
 
     def call(camera=C.byref(cam), n=10, cap=100, total=50, bws=need, v_xys=d):
-        return lib.tn_splat_raster_backward(camera, n, d, cap, total, bg, d, d, d, d, d, d, bws, v_xys, d, d, d, None)
+        return lib.tn_splat_raster_backward(camera, n, d, cap, total, bg, 0, d, d, None, None, d, d, d, None, d, bws, v_xys, None, d, d, d, None, None, None, None, None)
 
     assert call(camera=None) == EINVAL
     assert call(n=-1) == EINVAL
@@ -76,7 +83,8 @@ def test_project_backward_argument_validation(lib):
     d = C.c_void_p(256)
 
     def call(n=10, K=15, deg=3, rest=d, v_rest=d, radii=d):
-        return lib.tn_splat_project_backward(C.byref(cam), d, d, d, d, d, rest, d, rest, n, K, deg, 0, radii, d, d, d, d, d, d, d, d, d, v_rest, d, v_rest, None)
+        return lib.tn_splat_project_backward(C.byref(cam), None, None, d, d, d, d, d, rest, d, rest, None, n, K, deg, 0, radii, d, d, d, d, None, None, d, d, d, d, d, v_rest, d,
+                                             v_rest, None, None, 0, None, None, None)
 
     assert call(deg=4) == EINVAL
     assert b"sh_degree" in lib.tn_last_error()

@@ -129,23 +129,23 @@ def test_config_refusals():
 def test_entry_points_validate_on_the_host():
     """A short scratch answers TN_EINVAL before any launch, as every workspace-writing entry point does; so do bad sizes, flags and null pointers."""
     lib = _lib.load()
-    assert _lib.ABI_VERSION == 313 and lib.tn_version() == 313  # additions only: the version stays
-    assert {"tn_contrib_splat_raster", "tn_contrib_splat_workspace_bytes"} <= set(_lib.SIGNATURES)
-    wb = lib.tn_contrib_splat_workspace_bytes
+    assert _lib.ABI_VERSION == 314 and lib.tn_version() == 314  # additions only: the version stays
+    assert {"tn_splat_raster_contrib", "tn_splat_contrib_workspace_bytes"} <= set(_lib.SIGNATURES)
+    wb = lib.tn_splat_contrib_workspace_bytes
     assert wb(-1, 10) == -1 and wb(10, -1) == -1 and wb(1 << 31, 10) == -1
     need = wb(1000, 5000)
     assert need >= 5000 * 3 * 4 + 1000 * 4 and wb(0, 0) > 0
     cam = _lib.TnSplatCamera()
     cam.width, cam.height, cam.fx, cam.fy = 64, 48, 50.0, 50.0
     fake = C.c_void_p(256 * 4096)  # never dereferenced
-    call = lambda *a: lib.tn_contrib_splat_raster(*a, None)  # noqa: E731
+    call = lambda *a: lib.tn_splat_raster_contrib(*a, None)  # noqa: E731
     good = [C.byref(cam), 1000, fake, 5000, 0, 0, None, fake, need, fake, fake, fake, fake]
     assert call(C.byref(cam), 0, None, 0, 0, 0, None, None, 0, None, None, None, None) == 0  # no Gaussians: nothing to do
     for i, bad in ((8, need - 1), (4, 2), (5, 2), (5, -1), (1, -1), (3, -1), (2, None), (7, None), (9, None), (10, None), (11, None), (12, None), (0, None)):
         args = list(good)
         args[i] = bad
         assert call(*args) == -22, i
-    assert call(*good[:8], need - 1, *good[9:]) == -22 and b"tn_contrib_splat_workspace_bytes" in lib.tn_last_error()
+    assert call(*good[:8], need - 1, *good[9:]) == -22 and b"tn_splat_contrib_workspace_bytes" in lib.tn_last_error()
     assert math.isfinite(need)
 
 

@@ -1,4 +1,4 @@
-"""Ray-contribution scoring (tn_contrib_splat_raster: k_splat_raster_contrib -> k_splat_contrib_fold, through splat_prune.score_gaussians) and
+"""Ray-contribution scoring (tn_splat_raster_contrib: k_splat_raster_contrib -> k_splat_contrib_fold, through splat_prune.score_gaussians) and
 pruning on the GPU, on the backward-parity scenes of tests/splat_backward_cases.py: lists of three and more 256-record batches with a partial front
 batch, stopped and running pixels in one wave, ragged edges, a sub-tile image, opacities on the 1/255 gate, blends on the 0.999 clamp, N = 1; in
 separate mode both chains.  tests/test_splat_contrib_cpu.py holds the conditions on the scenes.

@@ -1,5 +1,5 @@
 """The crop box of the splat eval render without a GPU: OrientedBox (from_params, within on CPU tensors, the singular and empty cases), the
-C ABI of the three crop entry points, the model's crop API, and the conditions the GPU tests' scene has to meet so that they may demand exact
+C ABI of the box (the projection's nullable crop argument, tn_splat_crop_mask), the model's crop API, and the conditions the GPU tests' scene has to meet so that they may demand exact
 keep sets (tests/splat_crop_functional.py)."""
 import ctypes as C
 import math
@@ -9,6 +9,7 @@ import re
 import pytest
 import torch
 
+import splat_abi
 import splat_crop_functional as scf
 
 import nerfstudio_thermal_amd  # noqa: F401
@@ -116,19 +117,17 @@ def _declaration(hdr: str, name: str) -> str:
 
 def test_the_header_declares_the_crop_entry_points_and_the_binding_matches():
     hdr = open(os.path.join(ROOT, "include", "thermal_nerf_hip.h")).read()
-    for name, base in (("tn_splat_project_crop", "tn_splat_project"), ("tn_splat_project_crop_sep", "tn_splat_project_sep")):
-        args, base_args = _declaration(hdr, name).split(","), _declaration(hdr, base).split(",")
-        norm = lambda a: " ".join(a.split())  # noqa: E731
-        # the arguments of the entry point it extends, then the box, then the stream
-        assert [norm(a) for a in args[:-2]] == [norm(a) for a in base_args[:-1]], name
-        assert norm(args[-2]) == "const TnSplatCrop* crop" and norm(args[-1]) == norm(base_args[-1]) == "tn_stream_t stream"
-        res, argtypes = _lib.SIGNATURES[name]
-        assert res is C.c_int and len(argtypes) == len(args) == len(_lib.SIGNATURES[base][1]) + 1
-        assert argtypes[:-2] == _lib.SIGNATURES[base][1][:-1] and argtypes[-2] is C.POINTER(_lib.TnSplatCrop)
+    args = [" ".join(a.split()) for a in _declaration(hdr, "tn_splat_project").split(",")]
+    # the box is the projection's last argument before the stream, and the binding's type there is the struct pointer
+    assert args[-2:] == ["const TnSplatCrop* crop", "tn_stream_t stream"] and args[:2] == ["const TnSplatCamera* camera", "const float* pose_camera"]
+    res, argtypes = _lib.SIGNATURES["tn_splat_project"]
+    assert res is C.c_int and len(argtypes) == len(args) and argtypes[-2] is C.POINTER(_lib.TnSplatCrop)
+    for name in splat_abi.RETIRED:
+        assert not re.search(r"\b%s\s*\(" % name, hdr) and name not in _lib.SIGNATURES, name
     mask_args = _declaration(hdr, "tn_splat_crop_mask").split(",")
     assert [" ".join(a.split()) for a in mask_args] == ["const TnSplatCrop* crop", "const float* means", "int64_t n", "uint8_t* mask", "tn_stream_t stream"]
     assert len(_lib.SIGNATURES["tn_splat_crop_mask"][1]) == 5 and _lib.SIGNATURES["tn_splat_crop_mask"][1][2] is C.c_int64
-    assert _lib.ABI_VERSION == 313
+    assert _lib.ABI_VERSION == 314
     body = hdr[hdr.index("typedef struct TnSplatCrop {"):hdr.index("} TnSplatCrop;")]
     assert re.findall(r"float\s+(\w+)\[(\d+)\]", body) == [("world_to_box", "12"), ("half_extent", "3")]
     assert [(n, t._length_) for n, t in _lib.TnSplatCrop._fields_] == [("world_to_box", 12), ("half_extent", 3)] and C.sizeof(_lib.TnSplatCrop) == 60
@@ -146,11 +145,12 @@ def test_the_library_refuses_bad_crop_arguments_before_any_launch():
     assert lib.tn_splat_crop_mask(C.byref(crop), None, -1, None, None) == -22
     assert lib.tn_splat_crop_mask(C.byref(crop), None, 0, None, None) == 0
     cam = _lib.TnSplatCamera(fx=10.0, fy=10.0, width=16, height=16)
+    # (a null box of the projection is no refusal any more: it is the uncropped frame)
     none = [None] * 8
-    assert lib.tn_splat_project_crop(C.byref(cam), *none, 4, 0, 0, 0, *[None] * 8, 0, None, None) == -22 and b"null crop box" in lib.tn_last_error()
-    assert lib.tn_splat_project_crop_sep(C.byref(cam), *none, None, 4, 0, 0, 0, *[None] * 8, 0, None, None) == -22 and b"null crop box" in lib.tn_last_error()
-    assert lib.tn_splat_project_crop(C.byref(cam), *none, 4, 0, 0, 0, *[None] * 8, 0, C.byref(crop), None) == -22 and b"null pointer" in lib.tn_last_error()
-    assert lib.tn_version() == 313
+    for oth in (None, C.c_void_p(256)):
+        assert lib.tn_splat_project(C.byref(cam), None, *none, oth, 4, 0, 0, 0, *[None] * 8, 0, C.byref(crop), None) == -22
+        assert b"tn_splat_project: null pointer" in lib.tn_last_error()
+    assert lib.tn_version() == 314
 
 
 class _Bare(ThermalSplatfactoModel):

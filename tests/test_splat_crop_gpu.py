@@ -1,5 +1,5 @@
 """The crop box of the splat eval render on the GPU: tn_splat_crop_mask, OrientedBox.within on device tensors and the cropped
-ThermalSplatfactoModel.get_outputs (tn_splat_project_crop / tn_splat_project_crop_sep; under a shared pose row tn_splat_project_pose / _pose_sep).
+ThermalSplatfactoModel.get_outputs (tn_splat_project with its crop box; under a shared pose row with the pose record too).
 
 Everything here is exact.  The scene (scf.crop_scene: 300 Gaussians = projection blocks of 128, 128 and 44; frame 96 x 72 = 6 x 4.5 tiles) has no
 mean within the rounding band of a face of any box used (tests/test_splat_crop_cpu.py checks that on the inputs), so the kernel must keep exactly
@@ -148,7 +148,7 @@ def test_cropped_render_is_the_render_of_the_kept_gaussians(mode, thr, raster, s
 
 @pytest.mark.parametrize("mode,thr", [("shared", None), ("separate", scf.THR)], ids=["shared", "separate-removal"])
 def test_cropped_render_under_a_shared_pose_row(mode, thr):
-    """The pose instantiation of the projection with a non-null box (tn_splat_project_pose / _pose_sep): an eval render under a shared pose row
+    """The pose instantiation of the projection with a non-null box (tn_splat_project with pose_camera and crop): an eval render under a shared pose row
     with the crop set equals, bit for bit, the render of the kept Gaussians under the same row.  The box test is on world-space means, so the
     pose does not change which Gaussians are kept."""
     from nerfstudio_thermal_amd.config import CameraOptimizerConfig

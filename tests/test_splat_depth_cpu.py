@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import nerfstudio_thermal_amd  # noqa: F401
+import splat_abi
 import splat_backward_cases as bc
 import splat_depth_functional as df
 import thermal_reg_functional as trf
@@ -16,8 +17,8 @@ from nerfstudio_thermal_amd import _lib, splat_calls
 from nerfstudio_thermal_amd.splat import ThermalSplatfactoModelConfig
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_NAMES = ("tn_splat_depth_backward_workspace_bytes", "tn_depth_splat_raster_backward", "tn_depth_splat_project_backward", "tn_depth_loss_workspace_bytes",
-             "tn_depth_loss")
+# the depth groups live in the two backward entry points and their size function (the names they replaced: splat_abi.RETIRED)
+NEW_NAMES = ("tn_splat_backward_workspace_bytes", "tn_splat_raster_backward", "tn_splat_project_backward", "tn_depth_loss_workspace_bytes", "tn_depth_loss")
 
 
 @pytest.mark.parametrize("cfg", [df.SHARED_CONFIGS[0], df.SHARED_CONFIGS[5], df.SEP_CONFIGS[0]], ids=df.config_id)
@@ -138,7 +139,7 @@ def test_config_refusals():
 
 
 def test_new_names_are_in_the_header_the_map_and_the_bindings():
-    hdr = open(os.path.join(ROOT, "include", "thermal_nerf_hip.h")).read()
+    hdr = splat_abi.header()
     declared = set(re.findall(r"\b(tn_[a-z0-9_]+)\s*\(", hdr))
     exports = open(os.path.join(ROOT, "nerfstudio-thermal_amd", "csrc", "exports.map")).read()
     assert "global: tn_*;" in exports  # the map exports the prefix, so every declared name is covered
@@ -147,8 +148,11 @@ def test_new_names_are_in_the_header_the_map_and_the_bindings():
         assert name in declared and name.startswith("tn_"), name
         assert name in _lib.SIGNATURES, name
         assert f'"{name}"' in src, name  # spelled as a literal in the call layer
-    assert _lib.ABI_VERSION == 313  # the additions are backward compatible: the version stays
-    assert "depth" not in "".join(splat_calls.FAMILIES) and all("depth" not in f for flags in splat_calls.FAMILIES.values() for f in flags)
+    for name in splat_abi.RETIRED:
+        assert name not in declared and name not in _lib.SIGNATURES and name not in src, name
+    assert _lib.ABI_VERSION == 314
+    for name, group in (("tn_splat_raster_backward", ["depth", "v_depth", "v_depths"]), ("tn_splat_project_backward", ["v_depths"])):
+        assert [p for p in splat_abi.param_names(hdr, name) if p in group] == group and "antialiased" in splat_abi.param_names(hdr, name)
 
 
 def test_library_exports_and_refuses_without_a_gpu():
@@ -157,29 +161,31 @@ def test_library_exports_and_refuses_without_a_gpu():
 
         __graft_entry__.build()
     lib = _lib.load()
-    assert lib.tn_version() == 313
+    assert lib.tn_version() == 314
+    splat_abi.assert_unified(lib, NEW_NAMES)
+    size = lib.tn_splat_backward_workspace_bytes
     for sep in (0, 1):
         for absgrad in (0, 1):
-            base = getattr(lib, "tn_splat_backward_workspace_bytes" + ("_abs" if absgrad else "") + ("_sep" if sep else ""))(1000, 5000)
             al = lambda x: (x + 255) // 256 * 256  # noqa: E731
             sums = 10 + sep + 2 * absgrad  # per pair without the depth slot
-            assert base == al(4 * sums * 5000) + al(4 * 1000)
-            assert lib.tn_splat_depth_backward_workspace_bytes(1000, 5000, sep, absgrad) == al(4 * (sums + 1) * 5000) + al(4 * 1000)
-    assert lib.tn_splat_depth_backward_workspace_bytes(-1, 0, 0, 0) == -1
+            assert size(1000, 5000, sep, absgrad, 0) == al(4 * sums * 5000) + al(4 * 1000)
+            assert size(1000, 5000, sep, absgrad, 1) == al(4 * (sums + 1) * 5000) + al(4 * 1000)
+            assert (size(10, 100, sep, absgrad, 1), size(1000, 5000, sep, absgrad, 1)) == splat_abi.BACKWARD_WORKSPACE_BYTES[(sep, absgrad, 1)]
+    assert size(-1, 0, 0, 0, 1) == -1 and size(0, -1, 1, 1, 1) == -1
     assert lib.tn_depth_loss_workspace_bytes(1, 5) == -1 and lib.tn_depth_loss_workspace_bytes(37, 70) > 0
     cam = _lib.TnSplatCamera()
     one = C.c_void_p(256)  # never read: the refusal comes first
-    rc = lib.tn_depth_splat_raster_backward(C.byref(cam), 1, one, 1, 1, one, 1, *[one] * 9, 1 << 20, *[one] * 9, None)
+    rc = lib.tn_splat_raster_backward(C.byref(cam), 1, one, 1, 1, one, 1, *[one] * 9, 1 << 20, *[one] * 9, None)
     assert rc == -22 and b"classic mode only" in lib.tn_last_error()
-    rc = lib.tn_depth_splat_project_backward(C.byref(cam), None, None, *[one] * 8, None, 1, 0, 0, 1, *[one] * 6, one, *[one] * 8, None, None, 0, None, None, None)
+    rc = lib.tn_splat_project_backward(C.byref(cam), None, None, *[one] * 8, None, 1, 0, 0, 1, *[one] * 6, one, *[one] * 8, None, None, 0, None, None, None)
     assert rc == -22 and b"classic mode only" in lib.tn_last_error()
     assert lib.tn_depth_loss(None, None, None, 8, 8, 1.0, 1.0, None, 0, None, None, None) == -22 and b"null pointer" in lib.tn_last_error()
     assert lib.tn_depth_loss(one, one, None, 8, 8, -1.0, 1.0, one, 1 << 20, one, None, None) == -22 and b"negative" in lib.tn_last_error()
 
 
 def test_the_call_layer_passes_as_many_arguments_as_the_bindings_declare(monkeypatch):
-    """tests/test_splat_calls_cpu.py's check for the entry points with fixed names: every combination of the nullable groups adds up to the one
-    argument list, and without the depth tensors the stages still go to the names `entry` composes."""
+    """The depth tensors through the call layer (tests/test_splat_calls_cpu.py checks every combination of every stage's groups and where the Nones
+    sit): with and without them the two backward stages go to their one entry point, and the depth loss to its own."""
     sc, seen = splat_calls, []
     monkeypatch.setattr(sc, "_call", lambda name, *args: seen.append((name, len(args) + 1)))  # + the stream
     monkeypatch.setattr(sc, "_ptr", lambda t, dtype, name: None if t is None else C.c_void_p(1))
@@ -196,7 +202,5 @@ def test_the_call_layer_passes_as_many_arguments_as_the_bindings_declare(monkeyp
             sc.raster_backward(cam, 5, T(4), 10, 7, bg, *[T(1)] * 9, *([th] * 4 if n == 9 else []), v_xys_abs=v_abs, aa=0, depth=T(1), v_depth=T(1), v_depths=T(5))
             sc.raster_backward(cam, 5, T(4), 10, 7, bg, *[T(1)] * 9, *([th] * 4 if n == 9 else []), v_xys_abs=v_abs)
     sc.depth_loss(T(1), T(1), None, 8, 8, 1.0, 1.0, T(2), None)
-    names = {name for name, _ in seen}
-    assert {"tn_depth_splat_raster_backward", "tn_depth_splat_project_backward", "tn_depth_loss"} <= names
-    assert {"tn_splat_raster_backward", "tn_splat_raster_backward_abs_sep"} <= names
+    assert {name for name, _ in seen} == {"tn_splat_raster_backward", "tn_splat_project_backward", "tn_depth_loss"}
     assert [(name, n) for name, n in seen if n != len(_lib.SIGNATURES[name][1])] == []

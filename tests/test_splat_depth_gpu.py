@@ -1,5 +1,5 @@
 """The differentiable depth of the splat training render on the GPU (ThermalSplatfactoModelConfig.differentiable_depth: the DEPTH instantiations of
-k_splat_raster_bwd, k_splat_pair_fold and k_splat_project_bwd behind tn_depth_splat_raster_backward / tn_depth_splat_project_backward, through
+k_splat_raster_bwd, k_splat_pair_fold and k_splat_project_bwd behind the depth groups of tn_splat_raster_backward / tn_splat_project_backward, through
 ThermalSplatfactoModel.get_train_outputs and .backward()) and the fused depth losses (tn_depth_loss), against the float64 references of
 tests/splat_depth_functional.py on scenes of tests/splat_backward_cases.py, all classic:
 

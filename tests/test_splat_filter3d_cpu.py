@@ -165,7 +165,7 @@ def test_the_entry_points_are_bound_and_spelled_in_the_call_layer():
 
 def test_arguments_are_validated_on_the_host():
     lib = _lib.load()
-    assert _lib.ABI_VERSION == 313 and lib.tn_version() == 313  # additions only: the version stays
+    assert _lib.ABI_VERSION == 314 and lib.tn_version() == 314  # additions only: the version stays
     assert lib.tn_filter3d_splat_workspace_bytes(-1) == -1 and lib.tn_filter3d_splat_workspace_bytes(1 << 31) == -1
     assert lib.tn_filter3d_splat_workspace_bytes(0) == 8 and lib.tn_filter3d_splat_workspace_bytes(1037) == 8 * 5
     fake = C.c_void_p(256 * 4096)  # never dereferenced: validation comes before any launch

@@ -1,4 +1,4 @@
-"""The HIP splat forward (tn_splat_project -> tn_splat_bin -> tn_splat_raster / tn_splat_raster_train) against the float64 restatement
+"""The HIP splat forward (tn_splat_project -> tn_splat_bin -> tn_splat_raster / tn_splat_raster_chains) against the float64 restatement
 tests/splat_functional.py, on the scenes of tests/test_splat_forward_cpu.py: ragged image sizes, an image inside one tile, lists longer than
 two 256-record batches, frames where most pixels stop early, opacities around 1/255, Gaussians that cover every tile, equal depths; both
 raster modes, a non-zero RGB and thermal background, through get_outputs and get_train_outputs.

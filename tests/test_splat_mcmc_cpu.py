@@ -13,11 +13,12 @@ import nerfstudio_thermal_amd  # noqa: F401
 from nerfstudio_thermal_amd import _lib, splat
 from nerfstudio_thermal_amd.splat import ThermalSplatfactoModelConfig
 
+import splat_abi
 import splat_mcmc_functional as mf
 
 EINVAL = -22
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("tn_splat_mcmc_workspace_bytes", "tn_splat_mcmc_relocate", "tn_splat_mcmc_relocate_sep", "tn_splat_mcmc_noise", "tn_splat_mcmc_noise_sep")
+NEW = ("tn_splat_mcmc_workspace_bytes", "tn_splat_mcmc_relocate", "tn_splat_mcmc_noise")  # (the _sep names they absorbed: splat_abi.RETIRED)
 
 
 @pytest.fixture(scope="module")
@@ -60,8 +61,9 @@ def test_header_binding_and_exports_agree_on_the_new_names(lib):
     for name in NEW:
         assert name in declared and name in _lib.SIGNATURES, name
         assert getattr(lib, name) is not None
+    splat_abi.assert_unified(lib, NEW)
     assert {n for n in declared if "mcmc" in n} == set(NEW) == {n for n in _lib.SIGNATURES if "mcmc" in n}
-    assert _lib.ABI_VERSION == 313 and lib.tn_version() == 313  # the additions are backward compatible: the version stays
+    assert _lib.ABI_VERSION == 314 and lib.tn_version() == 314
     src = open(os.path.join(ROOT, "nerfstudio-thermal_amd", "csrc", "build.sh")).read()
     assert "tn_splat_mcmc" in src  # the new translation unit is in the build
 
@@ -77,7 +79,6 @@ def test_workspace_size(lib):
 
 @pytest.mark.parametrize("sep", [False, True])
 def test_relocate_refusals_before_any_launch(lib, sep):
-    fn = lib.tn_splat_mcmc_relocate_sep if sep else lib.tn_splat_mcmc_relocate
     n = 9 if sep else 8
     d = C.c_void_p(256)  # never dereferenced: every call below is refused (or returns) before anything is read or launched
     ptrs = (C.c_void_p * n)(*([256] * n))
@@ -86,7 +87,7 @@ def test_relocate_refusals_before_any_launch(lib, sep):
     need = lib.tn_splat_mcmc_workspace_bytes(10, 4)
 
     def call(rows=10, K=3, src=d, dst=d, M=4, min_op=0.005, params=ptrs, m1=ptrs, m2=ptrs, ws=d, ws_bytes=need):
-        return fn(rows, K, src, dst, M, min_op, params, m1, m2, ws, ws_bytes, None)
+        return lib.tn_splat_mcmc_relocate(rows, K, src, dst, M, min_op, n, params, m1, m2, ws, ws_bytes, None)
 
     assert call(rows=-1) == EINVAL
     assert call(M=-1) == EINVAL
@@ -111,14 +112,15 @@ def test_relocate_short_workspace_is_refused(lib):
     d = C.c_void_p(256)
     ptrs = (C.c_void_p * 8)(*([256] * 8))
     need = lib.tn_splat_mcmc_workspace_bytes(100000, 4)
-    assert lib.tn_splat_mcmc_relocate(100000, 0, d, d, 4, 0.005, ptrs, ptrs, ptrs, d, lib.tn_splat_mcmc_workspace_bytes(10, 4), None) == EINVAL
+    assert lib.tn_splat_mcmc_relocate(100000, 0, d, d, 4, 0.005, 8, ptrs, ptrs, ptrs, d, lib.tn_splat_mcmc_workspace_bytes(10, 4), None) == EINVAL
     assert need > lib.tn_splat_mcmc_workspace_bytes(10, 4)
 
 
 def test_noise_refusals_before_any_launch(lib):
     d = C.c_void_p(256)
     odd = C.c_void_p(260)
-    f, g = lib.tn_splat_mcmc_noise, lib.tn_splat_mcmc_noise_sep
+    g = lib.tn_splat_mcmc_noise  # opacities_thermal fifth: null is the shared opacity (and so no refusal)
+    f = lambda means, scales, quats, opacities, randn, *rest: g(means, scales, quats, opacities, None, randn, *rest)  # noqa: E731
     assert f(d, d, d, d, d, -1, 1.0, None) == EINVAL
     assert f(d, d, d, d, d, 1 << 31, 1.0, None) == EINVAL
     assert f(d, d, d, d, d, 10, -1.0, None) == EINVAL
@@ -132,7 +134,10 @@ def test_noise_refusals_before_any_launch(lib):
         assert b"null pointer" in lib.tn_last_error()
     assert f(d, d, odd, d, d, 10, 1.0, None) == EINVAL
     assert b"aligned" in lib.tn_last_error()
-    assert g(d, d, d, d, None, d, 10, 1.0, None) == EINVAL
+    for i in (0, 1, 2, 3, 5):
+        args = [d] * 6
+        args[i] = None
+        assert g(*args, 10, 1.0, None) == EINVAL and b"null pointer" in lib.tn_last_error()
     assert g(d, d, d, d, d, d, -1, 1.0, None) == EINVAL
     assert f(None, None, None, None, None, 0, 1.0, None) == 0 and g(None, None, None, None, None, None, 0, 1.0, None) == 0  # N = 0: nothing launched
 

@@ -151,9 +151,9 @@ def test_refine_plan_argument_validation(lib):
 
     def call(rs=None, step=600, n=10, ws_bytes=need, scales=d, out=counts):
         rs = rs or _refine_struct()
-        return lib.tn_splat_refine_plan(C.byref(rs), step, scales, d, d, d, d, n, d, ws_bytes, out, None)
+        return lib.tn_splat_refine_plan(C.byref(rs), step, scales, d, None, d, d, d, n, d, ws_bytes, out, None)
 
-    assert lib.tn_splat_refine_plan(None, 600, d, d, d, d, d, 10, d, need, counts, None) == EINVAL
+    assert lib.tn_splat_refine_plan(None, 600, d, d, None, d, d, d, 10, d, need, counts, None) == EINVAL
     assert call(n=-1) == EINVAL
     assert call(step=-1) == EINVAL
     assert call(rs=_refine_struct(refine_every=0)) == EINVAL
@@ -178,7 +178,7 @@ def test_refine_apply_argument_validation(lib):
 
     def call(n=10, K=3, ws_bytes=need, counts=(2, 7, 4, 1), noise=d, params=ptrs, m1=ptrs, m2=ptrs, new_m1=ptrs, rs=None):
         rs = rs or _refine_struct()
-        return lib.tn_splat_refine_apply(C.byref(rs), n, K, d, ws_bytes, (C.c_int64 * 4)(*counts), noise, params, m1, m2, ptrs, new_m1, ptrs, None)
+        return lib.tn_splat_refine_apply(C.byref(rs), n, K, d, ws_bytes, (C.c_int64 * 4)(*counts), noise, 8, params, m1, m2, ptrs, new_m1, ptrs, None)
 
     assert call(n=-1) == EINVAL
     assert call(K=16) == EINVAL

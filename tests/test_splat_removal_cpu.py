@@ -133,7 +133,7 @@ def test_symbol_is_declared_exported_and_bound(lib):
     if nm:
         exported = set(re.findall(r" T (tn_\w+)", subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout))
         assert name in exported
-    assert lib.tn_version() == _lib.ABI_VERSION == 313
+    assert lib.tn_version() == _lib.ABI_VERSION == 314
 
 
 def test_entry_point_refuses_bad_arguments_without_a_gpu(lib):

@@ -1,11 +1,8 @@
 """The separate thermal opacity (thermal_opacity_mode "separate") without a GPU: configuration, the key sets of both modes, the float64
 restatement (tests/splat_sep_functional.py) against the shared one and against hand-written gradient formulas, the both-below cull rule, the
-density loss and its detaches, and the ABI of the _sep entry points (declared, exported, bound, refusing bad arguments before any launch)."""
+density loss and its detaches, and the ABI of the thermal groups (declared, exported, bound, refusing bad arguments before any launch)."""
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 import torch
@@ -14,14 +11,16 @@ import nerfstudio_thermal_amd  # noqa: F401
 from nerfstudio_thermal_amd import _lib, optim, splat
 from nerfstudio_thermal_amd.splat import ThermalSplatfactoModelConfig
 
+import splat_abi
 import splat_functional as sf
 import splat_oracle as so
 import splat_sep_functional as ssf
 
 EINVAL = -22
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEP_SYMBOLS = ("tn_splat_project_sep", "tn_splat_raster_sep", "tn_splat_raster_train_sep", "tn_splat_backward_workspace_bytes_sep",
-               "tn_splat_raster_backward_sep", "tn_splat_project_backward_sep", "tn_splat_refine_plan_sep", "tn_splat_refine_apply_sep")
+# the entry points that take the thermal opacity as a nullable group (the _sep names they replaced are splat_abi.RETIRED)
+SEP_SYMBOLS = ("tn_splat_project", "tn_splat_raster_chains", "tn_splat_backward_workspace_bytes", "tn_splat_raster_backward", "tn_splat_project_backward",
+               "tn_splat_refine_plan", "tn_splat_refine_apply")
 # the shared mode's sets as they were before the separate mode existed
 SHARED_PARAMS = ("means", "scales", "quats", "opacities", "features_dc", "features_rest", "features_dc_thermal", "features_rest_thermal")
 SHARED_GROUPS = {"xyz": "means", "features_dc": "features_dc", "features_rest": "features_rest", "opacity": "opacities", "scaling": "scales",
@@ -204,53 +203,46 @@ def test_density_loss_value_and_detaches():
 
 # ------------------------------------------------------------------------------------------------ ABI
 def test_sep_symbols_are_declared_exported_and_bound(lib):
-    hdr = open(os.path.join(ROOT, "include", "thermal_nerf_hip.h")).read()
-    declared = set(re.findall(r"\b(tn_[a-z0-9_]+)\s*\(", hdr))
-    for name in SEP_SYMBOLS:
-        assert name in declared, name
-        assert name in _lib.SIGNATURES, name
-        assert getattr(lib, name).argtypes == _lib.SIGNATURES[name][1], name
-    nm = shutil.which("nm")
-    if nm:
-        exported = set(re.findall(r" T (tn_\w+)", subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout))
-        assert set(SEP_SYMBOLS) <= exported, set(SEP_SYMBOLS) - exported
-    assert lib.tn_version() == _lib.ABI_VERSION == 313
+    splat_abi.assert_unified(lib, SEP_SYMBOLS)
+    assert lib.tn_version() == _lib.ABI_VERSION == 314
 
 
 def test_sep_entry_points_refuse_bad_arguments_without_a_gpu(lib):
+    """The thermal group of every entry point.  (A null opacities_thermal of tn_splat_project / tn_splat_refine_plan and a null out_alpha_thermal of
+    the eval raster are no refusals any more: a group of one pointer left out is the shared mode.)"""
     d = C.c_void_p(256)
     cam = _lib.TnSplatCamera()
     cam.fx = cam.fy = 30.0
     cam.width, cam.height = 40, 24
     bad_cam = _lib.TnSplatCamera()
     c, bc = C.byref(cam), C.byref(bad_cam)
-    assert lib.tn_splat_backward_workspace_bytes_sep(-1, 0) == -1 and lib.tn_splat_backward_workspace_bytes_sep(0, -1) == -1
+    size = lib.tn_splat_backward_workspace_bytes
+    assert size(-1, 0, 1, 0, 0) == -1 and size(0, -1, 1, 0, 0) == -1
     n, cap = 100, 1000
-    assert lib.tn_splat_backward_workspace_bytes_sep(n, cap) >= 11 * 4 * cap > lib.tn_splat_backward_workspace_bytes(n, cap) - 4 * n - 512 >= 10 * 4 * cap - 512
-    # project: camera, null thermal opacities, Gaussian count, SH degree
-    proj = lambda cam=c, oth=d, n=10, deg=0, k=0: lib.tn_splat_project_sep(cam, d, d, d, d, d, d, d, d, oth, n, k, deg, 0, d, d, d, d, d, d, d, d, 100, None)  # noqa: E731
+    assert size(n, cap, 1, 0, 0) >= 11 * 4 * cap > size(n, cap, 0, 0, 0) - 4 * n - 512 >= 10 * 4 * cap - 512
+    # project: camera, Gaussian count, SH degree, the capacity
+    proj = lambda cam=c, oth=d, n=10, deg=0, k=0, cap=100: lib.tn_splat_project(cam, None, d, d, d, d, d, d, d, d, oth, n, k, deg, 0, d, d, d, d, d, d, d, d, cap, None, None)  # noqa: E731
     assert proj(cam=None) == EINVAL and proj(cam=bc) == EINVAL
-    assert proj(oth=None) == EINVAL and b"tn_splat_project_sep: null pointer" in lib.tn_last_error()
     assert proj(n=-1) == EINVAL and proj(deg=4) == EINVAL and proj(deg=3, k=3) == EINVAL
+    assert proj(cap=-1) == EINVAL and b"tn_splat_project: bad workspace capacity" in lib.tn_last_error()
     assert proj(n=0, oth=None) == 0
     # raster / training raster
-    assert lib.tn_splat_raster_sep(c, 10, d, 100, d, 0, d, d, d, None, None) == EINVAL
-    assert lib.tn_splat_raster_sep(c, -1, d, 100, d, 0, d, d, d, d, None) == EINVAL
-    assert lib.tn_splat_raster_sep(bc, 10, d, 100, d, 0, d, d, d, d, None) == EINVAL
-    tr = lambda **kw: lib.tn_splat_raster_train_sep(c, kw.get("n", 10), d, kw.get("cap", 100), d, 0, d, d, d, kw.get("ath", d), d, d, kw.get("tth", d), kw.get("lth", d), None)  # noqa: E731
+    assert lib.tn_splat_raster_chains(c, -1, d, 100, d, 0, d, d, d, d, None, None, None, None, None) == EINVAL
+    assert lib.tn_splat_raster_chains(bc, 10, d, 100, d, 0, d, d, d, d, None, None, None, None, None) == EINVAL
+    tr = lambda **kw: lib.tn_splat_raster_chains(c, kw.get("n", 10), d, kw.get("cap", 100), d, 0, d, d, d, kw.get("ath", d), d, d, kw.get("tth", d), kw.get("lth", d), None)  # noqa: E731
     assert tr(ath=None) == EINVAL and tr(tth=None) == EINVAL and tr(lth=None) == EINVAL and tr(n=-1) == EINVAL and tr(cap=-1) == EINVAL
     # raster backward
-    need = lib.tn_splat_backward_workspace_bytes_sep(10, 100)
-    bw = lambda **kw: lib.tn_splat_raster_backward_sep(c, kw.get("n", 10), d, 100, kw.get("tot", 50), d, d, d, kw.get("tth", d), kw.get("lth", d), d, d, d,  # noqa: E731
-                                                       kw.get("vath", d), d, kw.get("bytes", need), d, d, d, d, kw.get("vlt", d), None)
+    need = size(10, 100, 1, 0, 0)
+    bw = lambda **kw: lib.tn_splat_raster_backward(c, kw.get("n", 10), d, 100, kw.get("tot", 50), d, 0, d, d, kw.get("tth", d), kw.get("lth", d), d, d, d,  # noqa: E731
+                                                   kw.get("vath", d), d, kw.get("bytes", need), d, None, d, d, d, kw.get("vlt", d), None, None, None, None)
     assert bw(tth=None) == EINVAL and bw(lth=None) == EINVAL and bw(vath=None) == EINVAL and bw(vlt=None) == EINVAL
     assert bw(tot=101) == EINVAL and bw(n=-1) == EINVAL
     assert bw(bytes=need - 1) == EINVAL and b"workspace" in lib.tn_last_error()
-    assert bw(bytes=lib.tn_splat_backward_workspace_bytes(10, 100)) == EINVAL  # the shared mode's size is too small
+    assert bw(bytes=size(10, 100, 0, 0, 0)) == EINVAL  # the shared mode's size is too small
     assert bw(n=0, tth=None) == 0
     # projection backward
-    pb = lambda **kw: lib.tn_splat_project_backward_sep(c, d, d, d, d, d, d, d, d, kw.get("oth", d), kw.get("n", 10), 0, kw.get("deg", 0), 0, d, d, d, d, d,  # noqa: E731
-                                                        kw.get("vlt", d), d, d, d, d, d, d, d, d, kw.get("goth", d), None)
+    pb = lambda **kw: lib.tn_splat_project_backward(c, None, None, d, d, d, d, d, d, d, d, kw.get("oth", d), kw.get("n", 10), 0, kw.get("deg", 0), 0, d, d, d, d, d,  # noqa: E731
+                                                    kw.get("vlt", d), None, d, d, d, d, d, d, d, d, kw.get("goth", d), None, 0, None, None, None)
     assert pb(oth=None) == EINVAL and pb(vlt=None) == EINVAL and pb(goth=None) == EINVAL and pb(deg=5) == EINVAL and pb(n=-3) == EINVAL
     # refinement
     rs = _lib.TnSplatRefine()
@@ -259,15 +251,14 @@ def test_sep_entry_points_refuse_bad_arguments_without_a_gpu(lib):
     rs.stop_screen_size_at, rs.stop_split_at, rs.n_split_samples, rs.continue_cull_post_densification, rs.max_size = 4000, 15000, 2, 1, 40
     counts = (C.c_int64 * 4)()
     wneed = lib.tn_splat_refine_workspace_bytes(10, 2)
-    plan = lambda **kw: lib.tn_splat_refine_plan_sep(C.byref(rs), kw.get("step", 600), d, d, kw.get("oth", d), d, d, d, kw.get("n", 10), d,  # noqa: E731
-                                                     kw.get("bytes", wneed), counts, None)
-    assert plan(oth=None) == EINVAL and b"tn_splat_refine_plan_sep: null pointer" in lib.tn_last_error()
+    plan = lambda **kw: lib.tn_splat_refine_plan(C.byref(rs), kw.get("step", 600), d, d, kw.get("oth", d), d, d, d, kw.get("n", 10), d,  # noqa: E731
+                                                 kw.get("bytes", wneed), counts, None)
     assert plan(n=-1) == EINVAL and plan(step=-1) == EINVAL and plan(bytes=wneed - 1) == EINVAL
     assert plan(step=3100, oth=None, bytes=0) == 0 and list(counts) == [0, 10, 0, 0]  # a step that neither densifies nor culls: nothing launched
     arr9 = (C.c_void_p * 9)(*([256] * 9))
     null9 = (C.c_void_p * 9)()
     cnt = (C.c_int64 * 4)(0, 10, 0, 0)
-    ap = lambda params=arr9, new=arr9, cnt=cnt, bytes=wneed: lib.tn_splat_refine_apply_sep(C.byref(rs), 10, 0, d, bytes, cnt, None, params, null9, null9, new, null9, null9, None)  # noqa: E731
+    ap = lambda params=arr9, new=arr9, cnt=cnt, bytes=wneed: lib.tn_splat_refine_apply(C.byref(rs), 10, 0, d, bytes, cnt, None, 9, params, null9, null9, new, null9, null9, None)  # noqa: E731
     assert ap(bytes=wneed - 1) == EINVAL
     assert ap(cnt=(C.c_int64 * 4)(0, 11, 0, 0)) == EINVAL
     p8 = (C.c_void_p * 9)(*([256] * 8 + [None]))

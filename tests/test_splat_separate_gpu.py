@@ -1,4 +1,4 @@
-"""The separate thermal opacity on the GPU (thermal_opacity_mode "separate": the _sep entry points of tn_splat.hip through
+"""The separate thermal opacity on the GPU (thermal_opacity_mode "separate": the thermal groups of the entry points of tn_splat.hip through
 ThermalSplatfactoModel) against the float64 restatement tests/splat_sep_functional.py.
 
 Scenes (ssf.awkward_scene, ~300 Gaussians, frames of 40 x 24 and 33 x 17: partial tiles and quadrants): a tile whose list is longer than one
@@ -319,15 +319,17 @@ def test_entry_points_refuse_bad_arguments_without_a_launch():
     d = C.c_void_p(buf.data_ptr())
     EINVAL = -22
     torch.cuda.synchronize()
-    assert lib.tn_splat_project_sep(c, d, d, d, d, d, d, d, d, None, 10, 0, 0, 0, d, d, d, d, d, d, d, d, 100, None) == EINVAL
-    assert lib.tn_splat_project_sep(c, d, d, d, d, d, d, d, d, d, 1 << 31, 0, 0, 0, d, d, d, d, d, d, d, d, 100, None) == EINVAL
-    assert lib.tn_splat_raster_sep(c, 10, d, 100, d, 0, d, d, d, None, None) == EINVAL
-    assert lib.tn_splat_raster_train_sep(c, 10, d, -1, d, 0, d, d, d, d, d, d, d, d, None) == EINVAL
-    assert lib.tn_splat_raster_train_sep(c, 10, d, 100, d, 0, d, d, d, d, d, d, None, d, None) == EINVAL
-    need = lib.tn_splat_backward_workspace_bytes_sep(10, 100)
-    assert lib.tn_splat_raster_backward_sep(c, 10, d, 100, 50, d, d, d, d, d, d, d, d, d, d, need - 1, d, d, d, d, d, None) == EINVAL
-    assert lib.tn_splat_raster_backward_sep(c, 10, d, 100, 50, d, d, d, None, d, d, d, d, d, d, need, d, d, d, d, d, None) == EINVAL
-    assert lib.tn_splat_raster_backward_sep(c, 10, d, 100, 101, d, d, d, d, d, d, d, d, d, d, need, d, d, d, d, d, None) == EINVAL
-    assert lib.tn_splat_project_backward_sep(c, d, d, d, d, d, d, d, d, None, 10, 0, 0, 0, d, d, d, d, d, d, d, d, d, d, d, d, d, d, d, None) == EINVAL
+    # (a null opacities_thermal of the projection and a null out_alpha_thermal of the eval raster are the shared mode now, not refusals)
+    assert lib.tn_splat_project(c, None, d, d, d, d, d, d, d, d, d, 1 << 31, 0, 0, 0, d, d, d, d, d, d, d, d, 100, None, None) == EINVAL
+    assert lib.tn_splat_raster_chains(c, 10, d, -1, d, 0, d, d, d, d, d, d, d, d, None) == EINVAL
+    assert lib.tn_splat_raster_chains(c, 10, d, 100, d, 0, d, d, d, d, d, d, None, d, None) == EINVAL
+    assert lib.tn_splat_raster_chains(c, 10, d, 100, d, 0, d, d, d, None, d, d, d, d, None) == EINVAL
+    need = lib.tn_splat_backward_workspace_bytes(10, 100, 1, 0, 0)
+    bw = lambda total, tth, nbytes: lib.tn_splat_raster_backward(c, 10, d, 100, total, d, 0, d, d, tth, d, d, d, d, d, d, nbytes, d, None, d, d, d, d, None, None, None, None)  # noqa: E731
+    assert bw(50, d, need - 1) == EINVAL
+    assert bw(50, None, need) == EINVAL
+    assert bw(101, d, need) == EINVAL
+    assert lib.tn_splat_project_backward(c, None, None, d, d, d, d, d, d, d, d, None, 10, 0, 0, 0, d, d, d, d, d, d, None, d, d, d, d, d, d, d, d, d, None, 0, None, None,
+                                         None) == EINVAL
     torch.cuda.synchronize()
     assert float(buf.abs().max()) == 0.0  # nothing ran

@@ -123,7 +123,7 @@ def _header_symbols():
 def test_header_binding_and_exports_agree(lib):
     assert SYMBOLS <= _header_symbols()
     assert SYMBOLS <= set(_lib.SIGNATURES)
-    assert _lib.ABI_VERSION == 313 and lib.tn_version() == 313
+    assert _lib.ABI_VERSION == 314 and lib.tn_version() == 314
     res, args = _lib.SIGNATURES["tn_thermal_reg"]
     assert res is C.c_int and len(args) == 13 and args[6] is C.c_float and args[7] is C.c_float
     assert _lib.SIGNATURES["tn_thermal_reg_workspace_bytes"] == (C.c_int64, [C.c_int32, C.c_int32])
